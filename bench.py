@@ -7,11 +7,16 @@ embeddings -> brute-force cosine/IP top-10 over the HBM-resident corpus -> ranke
 id) lists.
 
   python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --steps 50 --warmup 5 --full
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-ONE JSON line on stdout:
+ONE JSON line on stdout.  A plain run sets up, warms up, times the steps and prints the headline:
   value / ms_per_step   exactly --steps timed steps between barrier + synchronize pairs, 4 batches
                         in flight, inputs (queries too) resident in HBM when the region starts
+  flags_clean           every batch in flight came back with zero flags (an exact answer) and the same ids
+--dump-outputs DIR writes the last timed step's results (scores, ids, exact_scores, flags) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+Everything below is measured only with --full:
   survey_8d             the same step as SURVEY.md 8d words the metric: queries uploaded from
                         pinned host memory and scores + ids downloaded to pinned host memory
                         inside the step, median of >= 30 timed groups (PCIe-inclusive; reported
@@ -27,7 +32,7 @@ ONE JSON line on stdout:
   recall / exactness    ALL queries of the batch against the C oracle
 N > 1: the corpus is row-sharded, the query batch replicated, each step ends with ONE RCCL
 all-gather of the per-shard top-k + flags and a merge (rag_fin_amd/sharded.py).  Default =
-STRONG scaling of the metric's 1 M-row corpus; the same line carries `weak` = BASELINE
+STRONG scaling of the metric's 1 M-row corpus; with --full the same line carries `weak` = BASELINE
 configs[4]'s shard (1.25 M x 768 rows PER GPU, generated on the device) so that one SCALE run
 answers both questions.  `--scaling weak` makes the weak job the headline instead.
 """
@@ -46,6 +51,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F16_PEAK_TFLOPS = 2500.0   # dense fp16/bf16 MFMA peak (same guide)
+SETTLE_STEPS = 512              # untimed steps before the first timed region (setup, not --warmup)
 
 
 def parse():
@@ -62,9 +68,16 @@ def parse():
     ap.add_argument("--streams", type=int, default=0,
                     help="batches in flight (one HIP stream + workspace each); 1 = strictly serial steps; "
                          "0 = 4 on one GPU, 8 for the sharded step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs[1..3] / weak side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: serial timing, stage times and roofline, "
+                         "survey_8d, oracle checks, CPU baselines, configs[1..3] / the weak job")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (scores, ids, exact scores, flags) as "
+                         "DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the oracle checks")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the configs[1..3] / weak side measurements")
     return ap.parse_args()
 
 
@@ -196,6 +209,17 @@ def all_ranks_agree(flag: bool, world, cdev) -> bool:
     t = torch.tensor([1 if flag else 0], dtype=torch.int32, device=cdev)
     dist.all_reduce(t, op=dist.ReduceOp.MIN)
     return bool(int(t.item()))
+
+
+def dump_outputs(out_dir, names, tensors):
+    """The arrays of one step as <out_dir>/<name>.npy: floats keep float32 / float64, integers (ids, flags)
+    are widened to float64, which holds them exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(names, tensors):
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -339,13 +363,16 @@ def main():
                         index.search_raw(q, k, want_exact=True, out=l["out"], workspace=l["ws"])
         barrier()
 
-        def timed_region(n_lanes):
-            """W untimed + exactly K timed steps, barrier + synchronize on both sides."""
+        last = [None]   # the lane of the last step timed
+
+        def timed_region(n_lanes, settle=0):
+            """settle + W untimed + exactly K timed steps, barrier + synchronize on both sides."""
             counter = [0]
 
             def step():
                 lane = lanes[counter[0] % n_lanes]
                 counter[0] += 1
+                last[0] = lane
                 if searcher is not None and bare:
                     lane["res"] = searcher.search_on(q, k, lane["ws"], lane["stream"])
                 elif searcher is not None:
@@ -353,7 +380,7 @@ def main():
                         lane["res"] = searcher.search(q, k, workspace=lane["ws"], resolve=False)
                 else:
                     index.enqueue_search(*lane["bare"])   # one ctypes call, cached pointers, the lane's stream
-            for _ in range(warmup):
+            for _ in range(settle + warmup):
                 step()
             barrier()
             t0 = time.perf_counter()
@@ -362,10 +389,14 @@ def main():
             barrier()
             return max_over_ranks(time.perf_counter() - t0)
 
-        serial_s = timed_region(1)
+        # setup, too: the first region timed starts after SETTLE_STEPS untimed steps of sustained load (from
+        # a cold start the headline step runs ~8 % slow for its first ~250 steps, ~30 ms, then holds steady).
+        # The serial view (one batch at a time) is a measurement of its own: --full only, unless it is the
+        # headline itself (--streams 1)
+        serial_s = timed_region(1, SETTLE_STEPS) if (args.full or max_lanes == 1) else None
         elapsed, n_lanes = serial_s, 1
         if max_lanes > 1:
-            elapsed = timed_region(max_lanes)
+            elapsed = timed_region(max_lanes, 0 if serial_s is not None else SETTLE_STEPS)
             n_lanes = max_lanes
         # flags must be clean for the number to count as an exact search: every lane, every rank
         # (the sharded step's flags are already the OR over the shards; the reduction below also
@@ -381,8 +412,10 @@ def main():
                 all(torch.equal(r[1], done[0][1]) for r in done)
             res = done[-1]
         clean = all_ranks_agree(clean, world, dev)
+        # what a caller of the timed path receives from its last step
+        outputs = last[0]["out"] if searcher is None else last[0]["res"]
         return dict(index=index, q=q, searcher=searcher, lanes=lanes, serial_s=serial_s, elapsed=elapsed,
-                    n_lanes=n_lanes, flags_clean=clean, res=res, bare=bare, label=label)
+                    n_lanes=n_lanes, flags_clean=clean, res=res, bare=bare, label=label, outputs=outputs)
 
     def global_check(job, q16, c16_local, row_base, nq):
         """N > 1: every rank runs the C oracle on ITS shard for the first nq queries, the per-shard
@@ -406,7 +439,10 @@ def main():
         c16 = osearch.synth_unit_rows(rows, dim, 1234 + rank)
     q16 = osearch.synth_unit_rows(B, dim, 5678)
     job = run_job(rows, row_base, rows_total, dim, c16, q16, args.steps, args.warmup, max(1, args.streams), "headline")
-    gcheck = global_check(job, q16, c16, row_base, min(16, B)) if (world > 1 and not args.no_check) else {}
+    if args.dump_outputs and rank == 0:
+        names = ("scores", "ids", "exact_scores", "flags") if job["searcher"] is None else ("scores", "ids", "flags")
+        dump_outputs(args.dump_outputs, names, job["outputs"])
+    gcheck = global_check(job, q16, c16, row_base, min(16, B)) if (world > 1 and args.full and not args.no_check) else {}
 
     index, q, lanes = job["index"], job["q"], job["lanes"]
     result = None
@@ -414,13 +450,7 @@ def main():
         elapsed, serial_s, n_lanes = job["elapsed"], job["serial_s"], job["n_lanes"]
         ms_per_step = elapsed * 1e3 / args.steps
         qps = B * args.steps / elapsed
-        # dominant kernel (emit scan) timed with HIP events on its stream, stage by stage
-        stages = [index.search_profile(q, k) for _ in range(max(10, min(50, args.steps)))]
-        emit_ms = float(np.mean([s["emit"] for s in stages]))
-        stage_avg = {n: float(np.mean([s[n] for s in stages])) for n in stages[0]}
         alg_bytes = rows * dim * 2  # corpus read once per batch
-        achieved = alg_bytes / (emit_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(rows, dim, B)
         result = {
             "metric": "queries/sec, brute-force cosine/IP top-%d over a %s x %d-d fp16 corpus, "
                       "batch=%d (recall@10 vs CPU oracle reported alongside)" % (k, f"{rows_total:,}", dim, B),
@@ -441,21 +471,31 @@ def main():
                        "sharding": ("none" if not force_sharded else "one-rank RCCL all-gather (overhead rehearsal)")
                        if world == 1 else f"rows/{world} + RCCL all-gather"},
             "rows_per_s": round(rows_total * args.steps / elapsed, 1),
-            "serial": {"batches_in_flight": 1, "value": round(B * args.steps / serial_s, 1),
-                       "ms_per_step": round(serial_s * 1e3 / args.steps, 5),
-                       "whole_step_GBps": round(alg_bytes / (serial_s / args.steps) / 1e9, 1)},
             "whole_step_GBps": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-            "stage_ms": {n: round(v, 5) for n, v in stage_avg.items()},
             "flags_clean": job["flags_clean"],
-            "roofline": {"bound": "hbm", "kernel": "k_scan<MODE_EMIT>", "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "traffic_source": (traffic_src + " (committed rocprofv3 --pmc pass of this workload; "
-                                            "not measured by this run)") if traffic_src else None,
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "timing": "HIP events around the kernel on its stream (rf_search_profile), mean of %d" % len(stages)},
         }
+        if serial_s is not None:
+            result["serial"] = {"batches_in_flight": 1, "value": round(B * args.steps / serial_s, 1),
+                                "ms_per_step": round(serial_s * 1e3 / args.steps, 5),
+                                "whole_step_GBps": round(alg_bytes / (serial_s / args.steps) / 1e9, 1)}
         result.update(gcheck)
+
+    # ---- everything beside the headline figure: --full only
+    if rank == 0 and args.full:
+        # dominant kernel (emit scan) timed with HIP events on its stream, stage by stage
+        stages = [index.search_profile(q, k) for _ in range(max(10, min(50, args.steps)))]
+        emit_ms = float(np.mean([s["emit"] for s in stages]))
+        stage_avg = {n: float(np.mean([s[n] for s in stages])) for n in stages[0]}
+        achieved = alg_bytes / (emit_ms * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic(rows, dim, B)
+        result["stage_ms"] = {n: round(v, 5) for n, v in stage_avg.items()}
+        result["roofline"] = {"bound": "hbm", "kernel": "k_scan<MODE_EMIT>", "achieved": round(achieved, 1),
+                              "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                              "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                              "traffic_source": (traffic_src + " (committed rocprofv3 --pmc pass of this workload; "
+                                                 "not measured by this run)") if traffic_src else None,
+                              "algorithmic_bytes_per_launch": alg_bytes,
+                              "timing": "HIP events around the kernel on its stream (rf_search_profile), mean of %d" % len(stages)}
 
         # ---- SURVEY.md 8d wording of the metric: queries come from pinned host memory and scores +
         # ids go back to pinned host memory inside the step; median of >= 30 timed groups
@@ -508,7 +548,7 @@ def main():
             result["cpu_baseline"] = cpu_search_baseline(q16, c16, k, budget_s=20.0)
 
     # ---- the other single-GPU configs of BASELINE.json, each with its own roofline / baseline / check
-    if world == 1 and not sharded and not args.no_configs and (rows, dim, B) == (1_000_000, 384, 64):
+    if args.full and world == 1 and not sharded and not args.no_configs and (rows, dim, B) == (1_000_000, 384, 64):
         configs = []
         for fn in (config2, config3, config4):
             try:
@@ -518,7 +558,7 @@ def main():
         result["configs"] = configs
 
     # ---- N > 1: the weak-scaling job (BASELINE configs[4]: 1.25 M x 768 rows PER GPU) in the same line
-    if world > 1 and not args.no_configs and args.scaling == "strong":
+    if args.full and world > 1 and not args.no_configs and args.scaling == "strong":
         try:
             weak = weak_job(args, dev, rank, world, run_job, k)
             if rank == 0:
