@@ -65,7 +65,10 @@ int rf_device_check(int device);
 /* ---- corpus index: replaces the Milvus collection -----------------------
  * Reference: schema + index build "chunking_storing (1).py":14-29 (FLOAT_VECTOR
  * dim 384, COSINE); the vectors live here as fp16 in an MFMA-fragment tiled
- * layout, scalar fields stay host-side in Python. */
+ * layout.  The scalar fields live host-side in Python; the four that
+ * filtered search tests (period, chunk_type, statement_type as dictionary codes,
+ * primary_value as fp64) are mirrored on the device by the caller and handed to
+ * rf_filter_eval (section "filtered search" below). */
 size_t rf_index_storage_bytes(int dim, int64_t capacity_rows);
 int rf_index_create(rf_index_t** out, int dim, int64_t capacity_rows,
                     void* storage_dev, size_t storage_bytes, int device);
@@ -134,6 +137,84 @@ int rf_search_exhaustive_after(const rf_index_t* ix, const void* q_dev, int B, i
                                const int64_t* after_id_dev, float* scores_dev, int64_t* ids_dev,
                                double* exact_dev, void* workspace_dev, size_t workspace_bytes,
                                void* stream);
+/* ---- filtered search: Collection.search(..., expr=...) --------------------------------------
+ * Reference: the `expr` argument of pymilvus Collection.search / query (the schema's scalar
+ * fields, "chunking_storing (1).py":14-22).  rag_fin_amd/filter_expr.py parses a Milvus
+ * boolean-expression subset and compiles it into the postfix program below; the scan then
+ * visits only the 32-row blocks that hold a passing row and tests every candidate row's bit.
+ *
+ * Filter buffer (caller-owned device memory, rf_filter_bytes(n_rows) bytes, 16-byte aligned):
+ *   uint32 header[4]   {n_rows, n_pass_rows, n_pass_blocks, n_tiles}
+ *   uint32 mask[nblk]  nblk = ceil(n_rows / 32); bit r of word b: row 32 b + r passes;
+ *                      bits past n_rows are zero
+ *   uint32 blocks[nblk] the ASCENDING list of the n_pass_blocks blocks with a passing row
+ *   (then scratch of the compaction: per-tile counts)
+ * The header counts are written on the device; the host reads them only if it wants to.
+ * Compaction is deterministic (per-tile counts, a scan, then the writes): the same mask always
+ * gives the same buffer, bit for bit.
+ *
+ * Program: n_ops (1..RF_FILTER_MAX_OPS) rf_filter_op in HOST memory (copied into the launch's
+ * arguments, so the call captures into a hipGraph), evaluated per row on a bool stack of at
+ * most RF_FILTER_MAX_DEPTH entries; the program must leave exactly one value.  Leaves:
+ *   RF_FOP_CODESET  column c in 0..2: the row's int32 dictionary code x passes iff
+ *                   0 <= x < 32 len and bit x of code_sets_dev[off .. off + len) is set
+ *   RF_FOP_RANGE    column 3 (fp64): lo <(=) x <(=) hi, RF_FRANGE_* bits say which ends are
+ *                   inclusive; IEEE comparisons, so a NaN value fails
+ *   RF_FOP_ROWLIST  the row number is in row_lists_dev[off .. off + len) (sorted ascending,
+ *                   binary search)
+ *   RF_FOP_TRUE / RF_FOP_FALSE
+ * and RF_FOP_AND / RF_FOP_OR (two operands) / RF_FOP_NOT (one).
+ * columns: HOST array of RF_FILTER_COLUMNS device pointers {int32 period codes [n_rows],
+ * int32 chunk_type codes, int32 statement_type codes, fp64 primary_value [n_rows]}; an entry
+ * the program does not read may be NULL.  code_sets_dev / row_lists_dev may be NULL when the
+ * program has no leaf of that kind.
+ * rf_filter_from_mask: the same buffer from a caller's own row mask (mask_dev uint32 [nblk],
+ * same bit layout; bits past n_rows are ignored) -- compaction only.
+ *
+ * rf_search_filtered: rf_search restricted to the rows the filter passes; same outputs and
+ * flag contract (flags 0 = proven equal to the exact ranking of the PASSING rows).  Fewer
+ * passing rows than k: the tail is padded with -inf / -1 and flags stay 0.  The filter must
+ * have been built for n_rows == rf_index_size(ix) (a header for another row count passes no
+ * row).  Filtered searches run as 64-query sweeps whatever B is (no wide sweep).
+ * rf_search_exhaustive_filtered: the fp64 fallback for flagged queries; after_score_dev /
+ * after_id_dev are both NULL, or both set for paging above RF_MAX_K as in
+ * rf_search_exhaustive_after.
+ * New in this build; the reference calls Milvus without `expr` on this path. */
+#define RF_FILTER_MAX_OPS 64
+#define RF_FILTER_MAX_DEPTH 32
+#define RF_FILTER_COLUMNS 4
+#define RF_FOP_CODESET 1
+#define RF_FOP_RANGE 2
+#define RF_FOP_ROWLIST 3
+#define RF_FOP_TRUE 4
+#define RF_FOP_FALSE 5
+#define RF_FOP_AND 6
+#define RF_FOP_OR 7
+#define RF_FOP_NOT 8
+#define RF_FRANGE_LO_INCL 1
+#define RF_FRANGE_HI_INCL 2
+typedef struct rf_filter_op {
+  int32_t op;      /* RF_FOP_* */
+  int32_t column;  /* CODESET: 0..2; RANGE: 3 */
+  int32_t off;     /* CODESET: first word in code_sets_dev; ROWLIST: first entry in row_lists_dev */
+  int32_t len;     /* CODESET: words; ROWLIST: entries */
+  int32_t flags;   /* RANGE: RF_FRANGE_* bits */
+  int32_t pad;
+  double lo, hi;   /* RANGE bounds */
+} rf_filter_op;
+size_t rf_filter_bytes(int64_t n_rows);
+int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
+                   const uint32_t* row_lists_dev, const void* const* columns, int64_t n_rows,
+                   void* filter_dev, void* stream);
+int rf_filter_from_mask(const uint32_t* mask_dev, int64_t n_rows, void* filter_dev, void* stream);
+int rf_search_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                       int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                       uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B,
+                                  int k, int64_t id_base, const double* after_score_dev,
+                                  const int64_t* after_id_dev, float* scores_dev, int64_t* ids_dev,
+                                  double* exact_dev, void* workspace_dev, size_t workspace_bytes,
+                                  void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

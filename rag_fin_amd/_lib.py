@@ -31,6 +31,20 @@ class EncoderConfig(Structure):
                 ("type_vocab", c_int32), ("ln_eps", c_float)]
 
 
+# filtered search (include/ragfin.h, "filtered search")
+RF_FILTER_MAX_OPS = 64
+RF_FILTER_MAX_DEPTH = 32
+RF_FILTER_COLUMNS = 4
+RF_FOP_CODESET, RF_FOP_RANGE, RF_FOP_ROWLIST, RF_FOP_TRUE, RF_FOP_FALSE, RF_FOP_AND, RF_FOP_OR, RF_FOP_NOT = range(1, 9)
+RF_FRANGE_LO_INCL = 1
+RF_FRANGE_HI_INCL = 2
+
+
+class FilterOp(Structure):
+    _fields_ = [("op", c_int32), ("column", c_int32), ("off", c_int32), ("len", c_int32),
+                ("flags", c_int32), ("pad", c_int32), ("lo", c_double), ("hi", c_double)]
+
+
 ENCODER_WEIGHT_FIELDS = ["word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b", "qkv_w",
                          "qkv_b", "ao_w", "ao_b", "ln1_g", "ln1_b", "ff1_w", "ff1_b", "ff2_w",
                          "ff2_b", "ln2_g", "ln2_b"]
@@ -65,6 +79,14 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_exhaustive_after": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_filter_bytes": (c_size_t, [c_int64]),
+    "rf_filter_eval": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rf_filter_from_mask": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "rf_search_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_search_exhaustive_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
     "rf_packed_shard_words": (c_size_t, [c_int, c_int]),

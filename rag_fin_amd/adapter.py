@@ -3,7 +3,8 @@
 Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
   GET /            service card                         (:121-132)
   GET /health      {"status": "healthy", "mcp": ...} | {"status": "unhealthy", "mcp": "unavailable"}
-  POST /search     {query: str >= 5 chars, top_k: 1..20 = 3}   -> tool search_vectors
+  POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional)}
+                                                               -> tool search_vectors
   POST /answer     {question: str >= 5 chars, top_k: 1..10 = 3} -> tool answer_question
   GET /stats       -> tool get_collection_stats
 Transport: JSON-RPC 2.0 over MCP streamable HTTP; one session, initialised on
@@ -16,6 +17,7 @@ from __future__ import annotations
 import json
 import logging
 import os
+from typing import Optional
 
 import httpx
 from fastapi import FastAPI, HTTPException
@@ -31,6 +33,17 @@ PROTOCOL_VERSION = "2024-11-05"
 class SearchRequest(BaseModel):
     query: str = Field(..., min_length=5)
     top_k: int = Field(default=3, ge=1, le=20)
+    # boolean expression over the scalar fields (rag_fin_amd.filter_expr); new, not in the reference
+    filter: Optional[str] = None
+
+
+def search_args(req: SearchRequest) -> dict:
+    """Tool arguments of POST /search: `filter` only when it was given, so the reference's
+    payload {"query", "top_k"} is unchanged."""
+    args = {"query": req.query, "top_k": req.top_k}
+    if req.filter is not None:
+        args["filter"] = req.filter
+    return args
 
 
 class AnswerRequest(BaseModel):
@@ -124,7 +137,7 @@ async def health():
 
 @app.post("/search")
 async def search(req: SearchRequest):
-    return await mcp.call_tool("search_vectors", {"query": req.query, "top_k": req.top_k})
+    return await mcp.call_tool("search_vectors", search_args(req))
 
 
 @app.post("/answer")

@@ -100,7 +100,7 @@ static void fill_empty(int B, int k, float* scores, int64_t* ids, double* exact,
 
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, float* scores_dev,
                           int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
-                          hipStream_t st);
+                          hipStream_t st, const rf_filter_view* filt = nullptr);
 
 // More than one 64-query sweep left and dim 384: one wide sweep of up to 256 queries.
 // Small corpora -- every row a candidate -- stay on the 64-query kernel (its inline flushes take
@@ -123,9 +123,10 @@ extern "C" int rf_search(const rf_index_t* ix, const void* q_dev, int B, int k, 
   return search_enqueue(ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, workspace_dev, st);
 }
 
+// filt: the masked sweep of filtered search (never the wide sweep: B > 64 runs as 64-query sweeps)
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, float* scores_dev,
                           int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
-                          hipStream_t st) {
+                          hipStream_t st, const rf_filter_view* filt) {
   int rc = RF_OK;
   if (ix->size == 0) {
     fill_empty(B, k, scores_dev, ids_dev, exact_dev, flags_dev, st);
@@ -137,7 +138,7 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
   const int dim = ix->dim;
   for (int q0 = 0; q0 < B;) {
     const int left = B - q0;
-    const bool wide = take_wide(ix, left, k);
+    const bool wide = !filt && take_wide(ix, left, k);
     const int nb = wide ? (left < RF_QWIDE ? left : RF_QWIDE) : (left < RF_QCHUNK ? left : RF_QCHUNK);
     const int JB = nb <= 32 ? 1 : 2;
     const _Float16* qc = (const _Float16*)q_dev + (size_t)q0 * dim;
@@ -154,12 +155,12 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
     } else {
       int P = 0;
       if (ix->size > RF_SMALL_ROWS) {
-        rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st);
+        rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st, filt);
         if (rc != RF_OK) return rc;
       }
       rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st);
       if (rc != RF_OK) return rc;
-      rc = rf_launch_emit(ix, qc, nb, JB, ws, st);
+      rc = rf_launch_emit(ix, qc, nb, JB, ws, st, filt);
       if (rc != RF_OK) return rc;
     }
     rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, scores_dev + (size_t)q0 * k,
@@ -211,7 +212,7 @@ extern "C" int rf_search_profile(const rf_index_t* ix, const void* q_dev, int B,
 static int exhaustive_impl(const char* fn, const rf_index_t* ix, const void* q_dev, int B, int k,
                            int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
                            const double* after_s, const int64_t* after_r, void* workspace_dev,
-                           size_t workspace_bytes, void* stream) {
+                           size_t workspace_bytes, void* stream, const uint32_t* mask = nullptr) {
   int rc = check_search_args(fn, ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev, workspace_bytes);
   if (rc != RF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -227,7 +228,7 @@ static int exhaustive_impl(const char* fn, const rf_index_t* ix, const void* q_d
     rc = rf_launch_exhaustive(ix, (const _Float16*)q_dev + (size_t)q0 * ix->dim, nb, k, id_base, ws,
                               scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k,
                               exact_dev ? exact_dev + (size_t)q0 * k : nullptr,
-                              after_s ? after_s + q0 : nullptr, after_r ? after_r + q0 : nullptr, st);
+                              after_s ? after_s + q0 : nullptr, after_r ? after_r + q0 : nullptr, st, mask);
     if (rc != RF_OK) return rc;
   }
   return RF_OK;
@@ -252,6 +253,46 @@ extern "C" int rf_search_exhaustive_after(const rf_index_t* ix, const void* q_de
   }
   return exhaustive_impl("rf_search_exhaustive_after", ix, q_dev, B, k, id_base, scores_dev, ids_dev,
                          exact_dev, after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream);
+}
+
+// ---- filtered search (include/ragfin.h, "filtered search") ---------------------------------------
+static int check_filter_arg(const char* fn, const void* filter_dev) {
+  if (!filter_dev || (((uintptr_t)filter_dev) & 15)) {
+    rf_set_error("%s: filter buffer null or not 16-byte aligned", fn);
+    return RF_ERR_INVALID;
+  }
+  return RF_OK;
+}
+
+extern "C" int rf_search_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                                  int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                                  uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  int rc = check_search_args("rf_search_filtered", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc != RF_OK) return rc;
+  rc = check_filter_arg("rf_search_filtered", filter_dev);
+  if (rc != RF_OK) return rc;
+  const rf_filter_view f = rf_filter_carve(filter_dev, ix->size);
+  return search_enqueue(ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, workspace_dev,
+                        (hipStream_t)stream, &f);
+}
+
+extern "C" int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev,
+                                             int B, int k, int64_t id_base, const double* after_score_dev,
+                                             const int64_t* after_id_dev, float* scores_dev, int64_t* ids_dev,
+                                             double* exact_dev, void* workspace_dev, size_t workspace_bytes,
+                                             void* stream) {
+  int rc = check_filter_arg("rf_search_exhaustive_filtered", filter_dev);
+  if (rc != RF_OK) return rc;
+  if ((after_score_dev == nullptr) != (after_id_dev == nullptr)) {
+    rf_set_error("rf_search_exhaustive_filtered: give both bound arrays or neither");
+    return RF_ERR_INVALID;
+  }
+  // (the masked exhaustive kernel checks no header: the mask of a buffer built for this index
+  // covers exactly ix->size rows)
+  const rf_filter_view f = rf_filter_carve(filter_dev, ix ? ix->size : 0);
+  return exhaustive_impl("rf_search_exhaustive_filtered", ix, q_dev, B, k, id_base, scores_dev, ids_dev,
+                         exact_dev, after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream, f.mask);
 }
 
 extern "C" int rf_merge_shards(const double* exact_dev, const int64_t* ids_dev, int W, int B, int k,

@@ -137,11 +137,22 @@ void rf_set_error(const char* fmt, ...);
 // index.hip: row-major fp16 [n, 16*KS] -> fragment-tiled (also used for encoder weights)
 void rf_launch_tile_rows(const void* rows, uint4* tiles, int64_t first_row, int64_t n, int KS,
                          hipStream_t st);
-// scan.hip
+// filter.hip: views into a caller's filter buffer (include/ragfin.h, "filtered search")
+#define RF_FILTER_HDR_WORDS 4
+#define RF_FILTER_MAX_TILES 1024   // compaction tiles; a tile is 32 * rows_per_thread mask words
+struct rf_filter_view {
+  const uint32_t* hdr;     // {n_rows, n_pass_rows, n_pass_blocks, n_tiles}
+  const uint32_t* mask;    // [nblk]
+  const uint32_t* blocks;  // [nblk], the first hdr[2] entries valid
+};
+size_t rf_filter_layout(int64_t n_rows, size_t* mask_off, size_t* blocks_off, size_t* tiles_off);
+rf_filter_view rf_filter_carve(const void* filter, int64_t n_rows);
+
+// scan.hip (filt: nullptr = every row; otherwise the masked sweep over the filter's blocks)
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                     int* P_out, hipStream_t st);
+                     int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr);
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st);
+                   hipStream_t st, const rf_filter_view* filt = nullptr);
 int rf_launch_debug_scores(const rf_index* ix, const void* q, int B, int64_t n, float* out,
                            hipStream_t st);
 int rf_scan_supported_dim(int dim);
@@ -158,7 +169,8 @@ int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_
                     uint32_t* flags, hipStream_t st);
 int rf_launch_exhaustive(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                          const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
-                         const double* after_s, const int64_t* after_r, hipStream_t st);
+                         const double* after_s, const int64_t* after_r, hipStream_t st,
+                         const uint32_t* mask = nullptr);
 int rf_launch_merge_shards(const double* exact, const int64_t* ids, size_t shard_stride, int W, int B, int k,
                            float* scores_out, int64_t* ids_out, const uint32_t* flags_in, size_t flag_stride,
                            uint32_t* flags_out, hipStream_t st);

@@ -26,14 +26,16 @@
 #include "rf_internal.h"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "scan_common.h"
 
-template <int KS, int R, int JB, int MODE, bool LAST>
+template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false>
 __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
                                            const uint4* nxt, const u32x4* smemQ, int lane,
                                            uint32_t row0, float (&th)[JB], float (&pm)[JB],
-                                           EmitState& es, const ScanParams& p) {
+                                           EmitState& es, const ScanParams& p,
+                                           uint32_t mword = 0u) {
   static_assert(KS % R == 0, "ring must divide the block");
   // keep the query-fragment LDS reads inside the block: hoisted out of the
   // block loop they would pin JB*KS*4 registers and spill
@@ -61,7 +63,17 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
   }
 
   if (MODE == MODE_SAMPLE) {
-    if (row0 + 32u > p.n_rows) {  // wave-uniform: only the corpus' last block
+    if (FILTER) {
+      // rows the filter rejects (and rows past the end: their bits are zero) leave the maximum
+      if (mword != 0xFFFFFFFFu) {  // wave-uniform
+        const int h = lane >> 5;
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (((mword >> acc_row(i, h)) & 1u) == 0u) acc[jb][i] = -INFINITY;
+      }
+    } else if (row0 + 32u > p.n_rows) {  // wave-uniform: only the corpus' last block
       const int h = lane >> 5;
 #pragma unroll
       for (int jb = 0; jb < JB; ++jb)
@@ -75,13 +87,14 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
     bool hit = false;
 #pragma unroll
     for (int jb = 0; jb < JB; ++jb) hit |= (max16(acc[jb]) >= th[jb]);
-    if (__ballot(hit) != 0ull) emit_slow<JB>(acc, th, row0, lane, es, p);
+    if (__ballot(hit) != 0ull) emit_slow<JB, ScanParams, FILTER>(acc, th, row0, lane, es, p, mword);
   }
 }
 
-template <int KS, int R, int JB, int WAVES, int MODE>
-__global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+// FILTER (filtered search, p is a ScanParamsF): the work items are the filter's pass blocks
+// (sample pass: every bstride-th of them), counted on the device; see scan_common.h.
+template <int KS, int R, int JB, int WAVES, int MODE, bool FILTER, class PT>
+__device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   u32x4* smemQ = (u32x4*)smem_raw;                                   // JB*KS*64 uint4
   unsigned char* tail = smem_raw + (size_t)JB * KS * RF_FRAG_BYTES;  // per-mode scratch
 
@@ -113,11 +126,29 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
   // work items w = gw, gw + W, ...  (one item = one 32-row block)
   const uint32_t W = gridDim.x * WAVES;
   const uint32_t gw = blockIdx.x * WAVES + wave;
+  if constexpr (FILTER) {
+    // pass blocks of the filter (a header built for another row count passes nothing)
+    uint32_t npb = p.hdr[0] == p.n_rows ? p.hdr[2] : 0u;
+    npb = npb < p.n_blocks ? npb : p.n_blocks;
+    if (MODE == MODE_SAMPLE) {  // ~1/16 of the pass blocks, spread evenly (rf_launch_sample)
+      uint32_t n = npb / 16;
+      n = n < p.work_lo ? p.work_lo : n;
+      n = n > p.work_hi ? p.work_hi : n;
+      n = n > npb ? npb : n;
+      p.n_work = n;
+      p.bstride = n ? npb / n : 1u;
+    } else {
+      p.n_work = npb;
+      p.bstride = 1u;
+    }
+  }
   const uint32_t cnt = (p.n_work > gw) ? (p.n_work - gw + W - 1) / W : 0u;
 
   u32x4 ring[R];
   if (cnt > 0) {
-    const uint4* src = p.corpus + (size_t)gw * p.bstride * (KS * 64) + lane;
+    const uint4* src;
+    if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[gw * p.bstride] * (KS * 64) + lane;
+    else src = p.corpus + (size_t)gw * p.bstride * (KS * 64) + lane;
 #pragma unroll
     for (int s = 0; s < R; ++s) ring[s] = ld_frag(src + s * 64);
   }
@@ -139,16 +170,35 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
   if (cnt > 0) {
 
     uint32_t w = gw;
-    for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
-      const uint32_t b = w * p.bstride;
-      const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-      const uint4* nxt = p.corpus + (size_t)(b + W * p.bstride) * (KS * 64) + lane;
-      block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, es, p);
-    }
-    {
-      const uint32_t b = w * p.bstride;
-      const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-      block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, es, p);
+    if constexpr (FILTER) {
+      uint32_t b = p.blocks[w * p.bstride];
+      for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
+        // scalar loads at the top of the step: the next block's index is needed only when the
+        // ring re-arms across the boundary, the mask word only after the MFMA chain
+        const uint32_t bn = p.blocks[(w + W) * p.bstride];
+        const uint32_t mw = p.mask[b];
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, false, true>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, es, p, mw);
+        b = bn;
+      }
+      {
+        const uint32_t mw = p.mask[b];
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, true, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, es, p, mw);
+      }
+    } else {
+      for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
+        const uint32_t b = w * p.bstride;
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        const uint4* nxt = p.corpus + (size_t)(b + W * p.bstride) * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, es, p);
+      }
+      {
+        const uint32_t b = w * p.bstride;
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, es, p);
+      }
     }
   }
 
@@ -167,6 +217,18 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
       p.pmax[(size_t)tid * p.P + blockIdx.x] = m;
     }
   }
+}
+
+template <int KS, int R, int JB, int WAVES, int MODE>
+__global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  scan_body<KS, R, JB, WAVES, MODE, false>(p, smem_raw);
+}
+
+template <int KS, int R, int JB, int WAVES, int MODE>
+__global__ void __launch_bounds__(WAVES * 64, 2) k_scan_filtered(ScanParamsF p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  scan_body<KS, R, JB, WAVES, MODE, true>(p, smem_raw);
 }
 
 // ---- raw score dump (test hook) ---------------------------------------------
@@ -198,12 +260,15 @@ __global__ void __launch_bounds__(64) k_debug_scores(const uint4* corpus, const 
 }
 
 // ---- host side ----------------------------------------------------------------
-template <int KS, int R, int JB, int WAVES, int MODE>
-static int launch_scan(const ScanParams& p, int grid, hipStream_t st) {
+template <int KS, int R, int JB, int WAVES, int MODE, class PT>
+static int launch_scan(const PT& p, int grid, hipStream_t st) {
   size_t lds = (size_t)JB * KS * RF_FRAG_BYTES;
   if (MODE == MODE_EMIT) lds += (size_t)3 * WAVES * SCAP * 4;
   else lds += (size_t)WAVES * 2 * JB * 32 * 4;
-  auto kern = k_scan<KS, R, JB, WAVES, MODE>;
+  auto kern = [] {
+    if constexpr (std::is_same<PT, ScanParamsF>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE>;
+    else return k_scan<KS, R, JB, WAVES, MODE>;
+  }();
   static rf_lds_attr attr;  // per instantiation, per device
   RF_HIP(rf_ensure_lds(attr, (const void*)kern, lds));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, st, p);
@@ -246,8 +311,8 @@ extern "C" int rf_set_tuning(const char* key, int value) {
 }
 #endif
 
-template <int MODE>
-static int dispatch_scan(int KS, int JB, const ScanParams& p, int grid4, int grid8,
+template <int MODE, class PT>
+static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
                          hipStream_t st) {
 #define RF_CASE(ks, r, waves, grid)                                              \
   case ks:                                                                       \
@@ -308,7 +373,7 @@ static inline int waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
 static inline int wgs_per_cu(int KS) { return KS >= 48 ? 1 : 2; }
 
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                     int* P_out, hipStream_t st) {
+                     int* P_out, hipStream_t st, const rf_filter_view* filt) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = waves_per_wg(KS);
@@ -338,11 +403,24 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
   p.pmax = ws.pmax;
   p.P = grid;
   *P_out = grid;
+  if (filt) {
+    // the grid (= partitions) is sized from the whole corpus; the kernel derives the sampled
+    // count and stride from the filter's device count of pass blocks, within the same bounds
+    ScanParamsF f{};
+    static_cast<ScanParams&>(f) = p;
+    f.hdr = filt->hdr;
+    f.mask = filt->mask;
+    f.blocks = filt->blocks;
+    f.n_blocks = nblk;
+    f.work_lo = lo;
+    f.work_hi = hi;
+    return dispatch_scan<MODE_SAMPLE>(KS, JB, f, grid, grid, st);
+  }
   return dispatch_scan<MODE_SAMPLE>(KS, JB, p, grid, grid, st);
 }
 
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st) {
+                   hipStream_t st, const rf_filter_view* filt) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = waves_per_wg(KS);
@@ -362,6 +440,16 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
   p.cand_cnt = ws.cand_cnt;
   p.cand = ws.cand;
   p.cap = RF_SHARD_CAP;
+  if (filt) {
+    // grid and ring depth as for the whole corpus; waves past the device count exit
+    ScanParamsF f{};
+    static_cast<ScanParams&>(f) = p;
+    f.hdr = filt->hdr;
+    f.mask = filt->mask;
+    f.blocks = filt->blocks;
+    f.n_blocks = nblk;
+    return dispatch_scan<MODE_EMIT>(KS, JB, f, grid, grid, st);
+  }
   return dispatch_scan<MODE_EMIT>(KS, JB, p, grid, grid, st);
 }
 

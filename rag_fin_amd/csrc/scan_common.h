@@ -25,6 +25,18 @@ struct ScanParams {
   int P;
 };
 
+// The masked sweep (filtered search): work item w is block blocks[w * bstride] of the filter's
+// ascending pass list instead of block w * bstride, and a row is a candidate only if its mask bit
+// is set.  The work count comes from the filter header on the device; the host sizes the grid
+// from the index's total block count.
+struct ScanParamsF : ScanParams {
+  const uint32_t* hdr;     // filter header {n_rows, n_pass_rows, n_pass_blocks, n_tiles}
+  const uint32_t* mask;    // [nblk] row bits
+  const uint32_t* blocks;  // ascending pass blocks
+  uint32_t n_blocks;       // blocks of the index (clamp of the device count)
+  uint32_t work_lo, work_hi;  // sample pass: bounds of the sampled block count (n_work is unused)
+};
+
 #ifndef RF_RING24
 #define RF_RING24 24
 #endif
@@ -79,9 +91,13 @@ __device__ __forceinline__ void emit_flush(EmitState& es, const P& p, int lane) 
 // Branch-free build of a per-lane 32-bit hit mask (bit jb*16+i), then a wave loop
 // that retires each lane's lowest set bit per iteration: the usual case (one or two
 // hits in the whole wave) costs one iteration instead of 32 ballot+branch rounds.
-template <int JB, class P>
+// FILTER: `mword` is the block's filter word; a row whose bit is clear is never a candidate,
+// whatever its score (an explicit test: the threshold may be -inf, so masking by writing -inf
+// into the accumulators would not keep rejected rows out).
+template <int JB, class P, bool FILTER = false>
 __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (&th)[JB],
-                                          uint32_t row0, int lane, EmitState& es, const P& p) {
+                                          uint32_t row0, int lane, EmitState& es, const P& p,
+                                          uint32_t mword = 0u) {
   const int h = lane >> 5;
   const uint32_t lim = p.n_rows - row0;  // rows of this block that exist (>= 32 except the last block)
   uint32_t bits = 0u;
@@ -89,7 +105,8 @@ __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (
   for (int jb = 0; jb < JB; ++jb)
 #pragma unroll
     for (int i = 0; i < 16; ++i)
-      bits |= ((acc[jb][i] >= th[jb]) && (acc_row(i, h) < lim)) ? (1u << (jb * 16 + i)) : 0u;
+      bits |= ((acc[jb][i] >= th[jb]) && (acc_row(i, h) < lim) &&
+               (!FILTER || ((mword >> acc_row(i, h)) & 1u) != 0u)) ? (1u << (jb * 16 + i)) : 0u;
   unsigned long long mask;
   while ((mask = __ballot(bits != 0u)) != 0ull) {
     const bool pass = bits != 0u;

@@ -1,0 +1,501 @@
+"""Boolean filter expressions of filtered search: `CorpusStore.search(..., expr=...)` and
+`CorpusStore.query(expr=...)`, the `expr` argument of pymilvus `Collection.search` / `query`.
+
+A Milvus boolean-expression subset over the reference's scalar schema
+("chunking_storing (1).py":14-22) is parsed by recursive descent into an AST, then compiled into
+the postfix program `rf_filter_eval` runs on the device (include/ragfin.h, "filtered search").
+
+Grammar (keywords case-insensitive; precedence not > and > or)::
+
+    expr    := and_ (("or" | "||") and_)*
+    and_    := unary (("and" | "&&") unary)*
+    unary   := ("not" | "!") unary | "(" expr ")" | compare
+    compare := FIELD CMP literal | literal CMP FIELD [CMP literal]
+             | FIELD ["not"] "in" "[" [literal ("," literal)*] "]" | FIELD "like" STRING
+
+Fields and what they accept:
+  period, chunk_type, statement_type (VARCHAR)  == != < <= > >= (code-point order), in / not in,
+                                                like "p%" / "%s" / "%i%" (no other wildcard)
+  primary_value (DOUBLE)                        == != < <= > >= (chains such as 1 < x <= 5),
+                                                in / not in; IEEE semantics: NaN fails every
+                                                comparison except !=
+  id (primary key)                              == != in / not in
+String literals take single or double quotes (backslash escapes the next character).  Anything
+else -- an unknown field, `text` or `embedding`, a type mismatch such as `period > 3` or
+`primary_value == "x"`, a syntax error -- raises ValueError naming the token and its position.
+
+Compilation.  A VARCHAR leaf is evaluated once against the column's dictionary (every distinct
+string, in first-seen order = its code) and becomes a set of codes, so a literal that is not in
+the dictionary matches nothing; numeric leaves become interval tests; id leaves become a sorted
+list of row numbers; and / or / not become stack operations.
+"""
+from __future__ import annotations
+
+import math
+import re
+from dataclasses import dataclass, field
+from typing import Any, Sequence
+
+import numpy as np
+
+from . import _lib
+
+VARCHAR_FIELDS = ("period", "chunk_type", "statement_type")   # device columns 0, 1, 2
+DOUBLE_FIELDS = ("primary_value",)                             # device column 3
+PK_FIELD = "id"
+UNFILTERABLE = ("text", "embedding")
+COLUMN_OF = {"period": 0, "chunk_type": 1, "statement_type": 2, "primary_value": 3}
+
+_CMP = ("==", "!=", "<", "<=", ">", ">=")
+_FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<=", "==": "==", "!=": "!="}
+
+
+def is_empty(expr) -> bool:
+    """None, "" and whitespace mean "no filter"."""
+    return expr is None or (isinstance(expr, str) and expr.strip() == "")
+
+
+# ---- tokens ------------------------------------------------------------------------------------
+@dataclass
+class Tok:
+    kind: str      # "name" | "str" | "num" | "op" | "end"
+    value: Any
+    pos: int
+    text: str
+
+
+_TOKEN = re.compile(r"""
+    (?P<ws>\s+)
+  | (?P<num>(?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?)
+  | (?P<name>[A-Za-z_][A-Za-z0-9_]*)
+  | (?P<op>==|!=|<=|>=|&&|\|\||[<>()\[\],!+-])
+""", re.X)
+
+
+def _err(msg: str, tok: Tok | None = None, pos: int | None = None) -> ValueError:
+    if tok is not None:
+        where = "end of expression" if tok.kind == "end" else f"{tok.text!r} at position {tok.pos}"
+        return ValueError(f"filter expression: {msg}: {where}")
+    return ValueError(f"filter expression: {msg} at position {pos}")
+
+
+def tokenize(s: str) -> list[Tok]:
+    out: list[Tok] = []
+    i = 0
+    while i < len(s):
+        c = s[i]
+        if c in "'\"":
+            j = i + 1
+            buf = []
+            while j < len(s) and s[j] != c:
+                if s[j] == "\\" and j + 1 < len(s):
+                    j += 1
+                buf.append(s[j])
+                j += 1
+            if j >= len(s):
+                raise _err("unterminated string", pos=i)
+            out.append(Tok("str", "".join(buf), i, s[i:j + 1]))
+            i = j + 1
+            continue
+        m = _TOKEN.match(s, i)
+        if not m:
+            raise _err(f"unexpected character {c!r}", pos=i)
+        kind = m.lastgroup
+        text = m.group(0)
+        if kind == "num":
+            out.append(Tok("num", float(text) if any(ch in text for ch in ".eE") else int(text), i, text))
+        elif kind == "name":
+            out.append(Tok("name", text, i, text))
+        elif kind == "op":
+            out.append(Tok("op", text, i, text))
+        i = m.end()
+    out.append(Tok("end", None, len(s), ""))
+    return out
+
+
+# ---- AST ---------------------------------------------------------------------------------------
+class Node:
+    def eval(self, row: dict) -> bool:   # host reference semantics (tests, docs)
+        raise NotImplementedError
+
+
+@dataclass
+class Cmp(Node):
+    field: str
+    op: str
+    value: Any
+
+    def eval(self, row):
+        return _compare(row[self.field], self.op, self.value)
+
+
+@dataclass
+class In(Node):
+    field: str
+    values: list
+    negate: bool = False
+
+    def eval(self, row):
+        x = row[self.field]
+        hit = any(_compare(x, "==", v) for v in self.values)
+        return not hit if self.negate else hit
+
+
+@dataclass
+class Like(Node):
+    field: str
+    pattern: str
+
+    def eval(self, row):
+        return like_match(row[self.field], self.pattern)
+
+
+@dataclass
+class And(Node):
+    a: Node
+    b: Node
+
+    def eval(self, row):
+        return self.a.eval(row) and self.b.eval(row)
+
+
+@dataclass
+class Or(Node):
+    a: Node
+    b: Node
+
+    def eval(self, row):
+        return self.a.eval(row) or self.b.eval(row)
+
+
+@dataclass
+class Not(Node):
+    a: Node
+
+    def eval(self, row):
+        return not self.a.eval(row)
+
+
+def _compare(x, op: str, v) -> bool:
+    # IEEE for floats (NaN: only != holds), code-point order for str
+    if op == "==":
+        return x == v
+    if op == "!=":
+        return x != v
+    if op == "<":
+        return x < v
+    if op == "<=":
+        return x <= v
+    if op == ">":
+        return x > v
+    return x >= v
+
+
+def like_match(s: str, pattern: str) -> bool:
+    core = pattern.strip("%")
+    lead, trail = pattern.startswith("%"), pattern.endswith("%") and len(pattern) > 1
+    if lead and trail:
+        return core in s
+    if lead:
+        return s.endswith(core)
+    if trail:
+        return s.startswith(core)
+    return s == pattern
+
+
+# ---- parser ------------------------------------------------------------------------------------
+class _Parser:
+    def __init__(self, text: str):
+        self.toks = tokenize(text)
+        self.i = 0
+
+    def peek(self, k: int = 0) -> Tok:
+        return self.toks[min(self.i + k, len(self.toks) - 1)]
+
+    def take(self) -> Tok:
+        t = self.toks[self.i]
+        self.i = min(self.i + 1, len(self.toks) - 1)
+        return t
+
+    def kw(self, word: str, k: int = 0) -> bool:
+        t = self.peek(k)
+        return t.kind == "name" and t.value.lower() == word
+
+    def op(self, sym: str, k: int = 0) -> bool:
+        t = self.peek(k)
+        return t.kind == "op" and t.value == sym
+
+    def parse(self) -> Node:
+        if self.peek().kind == "end":
+            raise _err("empty expression", self.peek())
+        node = self.expr()
+        if self.peek().kind != "end":
+            raise _err("unexpected token", self.peek())
+        return node
+
+    def expr(self) -> Node:
+        node = self.and_()
+        while self.kw("or") or self.op("||"):
+            self.take()
+            node = Or(node, self.and_())
+        return node
+
+    def and_(self) -> Node:
+        node = self.unary()
+        while self.kw("and") or self.op("&&"):
+            self.take()
+            node = And(node, self.unary())
+        return node
+
+    def unary(self) -> Node:
+        if self.kw("not") or self.op("!"):
+            self.take()
+            return Not(self.unary())
+        if self.op("("):
+            self.take()
+            node = self.expr()
+            if not self.op(")"):
+                raise _err("expected ')'", self.peek())
+            self.take()
+            return node
+        return self.compare()
+
+    # -- leaves ------------------------------------------------------------------------------
+    def field(self) -> tuple[str, Tok]:
+        t = self.take()
+        if t.kind != "name" or t.value.lower() in ("and", "or", "not", "in", "like"):
+            raise _err("expected a field name", t)
+        name = t.value
+        if name in UNFILTERABLE:
+            raise _err(f"field {name!r} cannot be filtered on", t)
+        if name not in VARCHAR_FIELDS + DOUBLE_FIELDS + (PK_FIELD,):
+            raise _err(f"unknown field {name!r}", t)
+        return name, t
+
+    def literal(self) -> tuple[Any, Tok]:
+        t = self.take()
+        if t.kind == "str":
+            return t.value, t
+        sign = 1
+        first = t
+        if t.kind == "op" and t.value in "+-":
+            sign = -1 if t.value == "-" else 1
+            t = self.take()
+        if t.kind == "num":
+            return sign * t.value, first
+        raise _err("expected a literal", first)
+
+    def cmp_op(self) -> Tok | None:
+        t = self.peek()
+        if t.kind == "op" and t.value in _CMP:
+            return self.take()
+        return None
+
+    def compare(self) -> Node:
+        t = self.peek()
+        if t.kind in ("str", "num") or (t.kind == "op" and t.value in "+-"):
+            # literal CMP field [CMP literal]
+            lit, lt = self.literal()
+            o1 = self.cmp_op()
+            if o1 is None:
+                raise _err("expected a comparison operator", self.peek())
+            name, ft = self.field()
+            left = self._leaf_cmp(name, ft, _FLIP[o1.value], lit, lt, o1)
+            o2 = self.cmp_op()
+            if o2 is None:
+                return left
+            lit2, lt2 = self.literal()
+            return And(left, self._leaf_cmp(name, ft, o2.value, lit2, lt2, o2))
+        name, ft = self.field()
+        o = self.cmp_op()
+        if o is not None:
+            lit, lt = self.literal()
+            return self._leaf_cmp(name, ft, o.value, lit, lt, o)
+        negate = False
+        if self.kw("not") and self.kw("in", 1):
+            self.take()
+            negate = True
+        if self.kw("in"):
+            kt = self.take()
+            return In(name, self._list(name, kt), negate)
+        if self.kw("like"):
+            kt = self.take()
+            if name not in VARCHAR_FIELDS:
+                raise _err(f"'like' needs a VARCHAR field, {name!r} is not one", kt)
+            pt = self.take()
+            if pt.kind != "str":
+                raise _err("'like' needs a string pattern", pt)
+            if "%" in pt.value.strip("%") or pt.value in ("%", "%%"):
+                raise _err("'like' supports 'p%', '%s' and '%i%' only", pt)
+            return Like(name, pt.value)
+        raise _err("expected a comparison, 'in' or 'like'", self.peek())
+
+    def _list(self, name: str, kt: Tok) -> list:
+        if not self.op("["):
+            raise _err("expected '['", self.peek())
+        self.take()
+        vals = []
+        if not self.op("]"):
+            while True:
+                lit, lt = self.literal()
+                vals.append(_check_type(name, lit, lt))
+                if self.op(","):
+                    self.take()
+                    continue
+                break
+        if not self.op("]"):
+            raise _err("expected ']'", self.peek())
+        self.take()
+        return vals
+
+    def _leaf_cmp(self, name, ft, op, lit, lt, ot) -> Node:
+        if name == PK_FIELD and op not in ("==", "!="):
+            raise _err(f"the primary key supports == != in / not in only, not {ot.value!r}", ot)
+        return Cmp(name, op, _check_type(name, lit, lt))
+
+
+def _check_type(name: str, lit, tok: Tok):
+    if name in VARCHAR_FIELDS:
+        if not isinstance(lit, str):
+            raise _err(f"{name} is VARCHAR, the literal is not a string", tok)
+        return lit
+    if name in DOUBLE_FIELDS:
+        if isinstance(lit, str):
+            raise _err(f"{name} is DOUBLE, the literal is a string", tok)
+        return float(lit)
+    return lit   # id: int or str keys, as inserted
+
+
+def parse(text: str) -> Node:
+    if not isinstance(text, str):
+        raise ValueError(f"filter expression must be a string, got {type(text).__name__}")
+    return _Parser(text).parse()
+
+
+# ---- compilation -------------------------------------------------------------------------------
+@dataclass
+class Program:
+    """The postfix program of rf_filter_eval: ops (tuples op, column, off, len, flags, lo, hi),
+    the code-set bitmap words and the sorted row lists the leaves point into."""
+    ops: list = field(default_factory=list)
+    code_sets: list = field(default_factory=list)
+    row_lists: list = field(default_factory=list)
+
+    def ops_ctypes(self):
+        arr = (_lib.FilterOp * len(self.ops))()
+        for i, (op, col, off, ln, flags, lo, hi) in enumerate(self.ops):
+            arr[i].op, arr[i].column, arr[i].off, arr[i].len = op, col, off, ln
+            arr[i].flags, arr[i].lo, arr[i].hi = flags, lo, hi
+        return arr
+
+    def max_depth(self) -> int:
+        d = m = 0
+        for o in self.ops:
+            d += 1 if o[0] <= _lib.RF_FOP_FALSE else (-1 if o[0] in (_lib.RF_FOP_AND, _lib.RF_FOP_OR) else 0)
+            m = max(m, d)
+        return m
+
+
+class _Compiler:
+    def __init__(self, dicts: dict[str, Sequence[str]], pk_row: dict):
+        self.dicts = dicts
+        self.pk_row = pk_row
+        self.p = Program()
+
+    def leaf(self, op, col=0, off=0, ln=0, flags=0, lo=0.0, hi=0.0):
+        self.p.ops.append((op, col, off, ln, flags, lo, hi))
+
+    def emit(self, n: Node) -> None:
+        if isinstance(n, (And, Or)):
+            self.emit(n.a)
+            self.emit(n.b)
+            self.leaf(_lib.RF_FOP_AND if isinstance(n, And) else _lib.RF_FOP_OR)
+        elif isinstance(n, Not):
+            self.emit(n.a)
+            self.leaf(_lib.RF_FOP_NOT)
+        elif n.field in VARCHAR_FIELDS:
+            self.codeset(n)
+        elif n.field in DOUBLE_FIELDS:
+            self.numeric(n)
+        else:
+            self.pk(n)
+
+    def codeset(self, n: Node) -> None:
+        d = self.dicts.get(n.field, ())
+        codes = [c for c, s in enumerate(d) if n.eval({n.field: s})]
+        if not codes:
+            self.leaf(_lib.RF_FOP_FALSE)
+            return
+        words = [0] * ((max(codes) >> 5) + 1)
+        for c in codes:
+            words[c >> 5] |= 1 << (c & 31)
+        off = len(self.p.code_sets)
+        self.p.code_sets.extend(words)
+        self.leaf(_lib.RF_FOP_CODESET, COLUMN_OF[n.field], off, len(words))
+
+    def interval(self, op: str, v: float) -> None:
+        inf = math.inf
+        L, H = _lib.RF_FRANGE_LO_INCL, _lib.RF_FRANGE_HI_INCL
+        lo, hi, flags = {"==": (v, v, L | H), "<": (-inf, v, L), "<=": (-inf, v, L | H),
+                         ">": (v, inf, H), ">=": (v, inf, L | H)}[op]
+        self.leaf(_lib.RF_FOP_RANGE, 3, 0, 0, flags, lo, hi)
+
+    def numeric(self, n: Node) -> None:
+        if isinstance(n, Cmp):
+            if n.op == "!=":     # NaN != v holds: the negation of an IEEE == test
+                self.interval("==", n.value)
+                self.leaf(_lib.RF_FOP_NOT)
+            else:
+                self.interval(n.op, n.value)
+            return
+        # in / not in: an or-chain of equality tests
+        if not n.values:
+            self.leaf(_lib.RF_FOP_FALSE)
+        for j, v in enumerate(n.values):
+            self.interval("==", v)
+            if j:
+                self.leaf(_lib.RF_FOP_OR)
+        if n.negate:
+            self.leaf(_lib.RF_FOP_NOT)
+
+    def pk(self, n: Node) -> None:
+        keys = [n.value] if isinstance(n, Cmp) else n.values
+        rows = sorted({self.pk_row[k] for k in keys if _hashable(k) and k in self.pk_row})
+        if rows:
+            off = len(self.p.row_lists)
+            self.p.row_lists.extend(rows)
+            self.leaf(_lib.RF_FOP_ROWLIST, 0, off, len(rows))
+        else:
+            self.leaf(_lib.RF_FOP_FALSE)
+        if (isinstance(n, Cmp) and n.op == "!=") or (isinstance(n, In) and n.negate):
+            self.leaf(_lib.RF_FOP_NOT)
+
+
+def _hashable(k) -> bool:
+    try:
+        hash(k)
+        return True
+    except TypeError:
+        return False
+
+
+def compile_expr(node: Node | str, dicts: dict[str, Sequence[str]], pk_row: dict) -> Program:
+    """AST (or expression text) -> Program.  dicts: VARCHAR field -> its dictionary (code i =
+    dicts[field][i]); pk_row: primary key -> row number."""
+    if isinstance(node, str):
+        node = parse(node)
+    c = _Compiler(dicts, pk_row)
+    c.emit(node)
+    p = c.p
+    if len(p.ops) > _lib.RF_FILTER_MAX_OPS:
+        raise ValueError(f"filter expression: compiles to {len(p.ops)} operations, more than the "
+                         f"{_lib.RF_FILTER_MAX_OPS} the device program holds")
+    if p.max_depth() > _lib.RF_FILTER_MAX_DEPTH:
+        raise ValueError(f"filter expression: nests deeper than {_lib.RF_FILTER_MAX_DEPTH} operands")
+    return p
+
+
+def program_arrays(p: Program) -> tuple[np.ndarray, np.ndarray]:
+    """(code-set words uint32, row lists uint32) as contiguous numpy arrays."""
+    return (np.asarray(p.code_sets, dtype=np.uint32).reshape(-1),
+            np.asarray(p.row_lists, dtype=np.uint32).reshape(-1))

@@ -55,10 +55,15 @@ def _searcher():
     return _batcher
 
 
-def search_vectors(query: str, top_k: int = 3):
-    """Semantic search in vector store"""
+def search_vectors(query: str, top_k: int = 3, filter: str = ""):
+    """Semantic search in vector store.  filter: an optional boolean expression over the
+    scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax)."""
     try:
-        contexts = _searcher().search(query, top_k)
+        if filter and filter.strip():
+            # filtered calls bypass the micro-batcher: one batch shares one filter
+            contexts = get_rag().search(query, top_k, expr=filter)
+        else:
+            contexts = _searcher().search(query, top_k)
         return {"status": "success", "query": query, "results": contexts,
                 "result_count": len(contexts)}
     except Exception as e:

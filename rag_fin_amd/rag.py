@@ -52,10 +52,11 @@ class VectorRAG:
                  "primary_value": h.entity.primary_value, "score": float(h.score)}
                 for i, h in enumerate(hits)]
 
-    def search(self, query: str, top_k: int = 3) -> list[dict]:
-        """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70."""
+    def search(self, query: str, top_k: int = 3, expr: str | None = None) -> list[dict]:
+        """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
+        over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'."""
         q = self._embed([query])
-        results = self.collection.search(q, "embedding", {"metric_type": "COSINE"}, top_k,
+        results = self.collection.search(q, "embedding", {"metric_type": "COSINE"}, top_k, expr=expr,
                                          output_fields=OUTPUT_FIELDS)
         return self._contexts(results[0])
 
@@ -68,13 +69,14 @@ class VectorRAG:
 
     retrieve = search  # BASELINE.json's "retrieve(query, k)" name for the same call
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 3) -> list[list[dict]]:
+    def search_batch(self, queries: Sequence[str], top_k: int = 3,
+                     expr: str | None = None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
-        is strictly one query per call)."""
+        is strictly one query per call); expr: one filter for the whole batch."""
         if not queries:
             return []
         q = self._embed(list(queries))
-        results = self.collection.search(q, "embedding", {"metric_type": "COSINE"}, top_k,
+        results = self.collection.search(q, "embedding", {"metric_type": "COSINE"}, top_k, expr=expr,
                                          output_fields=OUTPUT_FIELDS)
         return [self._contexts(r) for r in results]
 

@@ -28,7 +28,7 @@ import numpy as np
 import logging
 import threading
 
-from . import _lib
+from . import _lib, filter_expr
 from .sharded import HipShardBackend, ShardedSearcher
 from .store import SCALAR_FIELDS, CorpusStore
 
@@ -225,6 +225,16 @@ class ShardedCorpusStore(CorpusStore):
             return
         self.dist.broadcast(torch.zeros(2, dtype=torch.int64, device=self._bdev), src=0, group=self.group)
         self._leading = False
+
+    # -- filters: not over shards (yet) -----------------------------------------------------------------
+    def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
+               output_fields=None):
+        if not filter_expr.is_empty(expr):
+            raise NotImplementedError("filtered search is not implemented for the sharded store")
+        return super().search(data, anns_field, param, limit, expr, output_fields)
+
+    def _expr_rows(self, expr):
+        raise NotImplementedError(f"query expression {expr!r}: the sharded store supports '' and 'id in [...]' only")
 
     # -- scalar queries: columns are replicated, vectors live on their owner ----------------------------
     def query(self, expr: str = "", limit=None, output_fields=None):

@@ -13,8 +13,10 @@ Reference surface mirrored (pymilvus `Collection`, as the reference uses it):
                                         test_vector.py:35-39
 
 Vectors live on the GPU (fp16, MFMA-fragment tiled); the scalar
-columns stay in host Python lists.  All arithmetic goes through libragfin_hip.so;
-there is no CPU path.
+columns stay in host Python lists, and the four a filter can test are mirrored on the
+device on demand (filtered search: `search(..., expr=...)`, `query(expr=...)`,
+rag_fin_amd/filter_expr.py).  All arithmetic goes through libragfin_hip.so; there is no
+CPU path.
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 from . import _lib
+from . import filter_expr
 
 import os as _os
 # RAGFIN_ZERO_COPY=0: search_host copies results with async memcpys instead of letting the merge kernel
@@ -138,10 +141,12 @@ class GpuIndex:
         return torch.zeros(self.workspace_bytes, dtype=torch.uint8, device=self.device)
 
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None):
+                   workspace=None, stream_ptr=None, filt=None):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
         hipStream_t of this device); no host sync.  Returns
-        (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B])."""
+        (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
+        filt: a filter buffer built for this index (CorpusStore.build_filter / rf_filter_eval):
+        rf_search_filtered, the same outputs over the passing rows only."""
         torch = _torch()
         if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
             raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
@@ -155,13 +160,16 @@ class GpuIndex:
             flags = torch.empty((B,), dtype=torch.int32, device=self.device)
         else:
             scores, ids, exact, flags = out
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_search(
-                self.handle, c_void_p(q16.data_ptr()), B, k, id_base, c_void_p(scores.data_ptr()),
+        args = (c_void_p(q16.data_ptr()), B, k, id_base, c_void_p(scores.data_ptr()),
                 c_void_p(ids.data_ptr()), c_void_p(exact.data_ptr()) if exact is not None else None,
                 c_void_p(flags.data_ptr()),
                 c_void_p((workspace if workspace is not None else self.workspace).data_ptr()),
-                self.workspace_bytes, stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+                self.workspace_bytes, stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
+        with torch.cuda.device(self.device):
+            if filt is None:
+                _lib.check(self.lib.rf_search(self.handle, *args))
+            else:
+                _lib.check(self.lib.rf_search_filtered(self.handle, c_void_p(filt.data_ptr()), *args))
         return scores, ids, exact, flags
 
     def enqueue_search(self, q_ptr: int, B: int, k: int, id_base: int, scores_ptr: int, ids_ptr: int,
@@ -191,7 +199,7 @@ class GpuIndex:
                 _lib.current_stream_ptr(), ms))
         return {"sample": ms[0], "threshold": ms[1], "emit": ms[2], "merge": ms[3]}
 
-    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False):
+    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
@@ -199,23 +207,31 @@ class GpuIndex:
         ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
         exact = torch.empty((B, k), dtype=torch.float64, device=self.device) if want_exact else None
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_search_exhaustive(
-                self.handle, c_void_p(q16.data_ptr()), B, k, id_base, c_void_p(scores.data_ptr()),
-                c_void_p(ids.data_ptr()), c_void_p(exact.data_ptr()) if exact is not None else None,
-                c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
-                _lib.current_stream_ptr()))
+            if filt is None:
+                _lib.check(self.lib.rf_search_exhaustive(
+                    self.handle, c_void_p(q16.data_ptr()), B, k, id_base, c_void_p(scores.data_ptr()),
+                    c_void_p(ids.data_ptr()), c_void_p(exact.data_ptr()) if exact is not None else None,
+                    c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
+                    _lib.current_stream_ptr()))
+            else:
+                _lib.check(self.lib.rf_search_exhaustive_filtered(
+                    self.handle, c_void_p(filt.data_ptr()), c_void_p(q16.data_ptr()), B, k, id_base, None, None,
+                    c_void_p(scores.data_ptr()), c_void_p(ids.data_ptr()),
+                    c_void_p(exact.data_ptr()) if exact is not None else None,
+                    c_void_p(self.workspace.data_ptr()), self.workspace_bytes, _lib.current_stream_ptr()))
         return scores, ids, exact
 
-    def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False):
+    def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
         """Limits above RF_MAX_K: the first page through the fused path, further pages
         of RF_MAX_K through rf_search_exhaustive_after (each page = the hits ranked
         strictly after the previous page's last hit).  Returns (scores, ids) [B, k]
-        (+ the fp64 ranking scores with want_exact: what a cross-shard merge ranks by)."""
+        (+ the fp64 ranking scores with want_exact: what a cross-shard merge ranks by).
+        filt: the same over the passing rows (rf_search_exhaustive_filtered pages)."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
         page = _lib.RF_MAX_K
-        s0, i0, e0 = self.search(q16, page, id_base, want_exact=True)
+        s0, i0, e0 = self.search(q16, page, id_base, want_exact=True, filt=filt)
         scores, ids, exacts = [s0], [i0], [e0]
         last_s, last_i = e0[:, -1].contiguous(), i0[:, -1].contiguous()
         got = page
@@ -227,11 +243,18 @@ class GpuIndex:
             bs = torch.where(last_i >= 0, last_s, torch.full_like(last_s, float("-inf")))
             bi = torch.where(last_i >= 0, last_i, torch.full_like(last_i, 2 ** 62))
             with self._lock, torch.cuda.device(self.device):
-                _lib.check(self.lib.rf_search_exhaustive_after(
-                    self.handle, c_void_p(q16.data_ptr()), B, page, id_base, c_void_p(bs.data_ptr()),
-                    c_void_p(bi.data_ptr()), c_void_p(s.data_ptr()), c_void_p(i.data_ptr()),
-                    c_void_p(e.data_ptr()), c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
-                    _lib.current_stream_ptr()))
+                if filt is None:
+                    _lib.check(self.lib.rf_search_exhaustive_after(
+                        self.handle, c_void_p(q16.data_ptr()), B, page, id_base, c_void_p(bs.data_ptr()),
+                        c_void_p(bi.data_ptr()), c_void_p(s.data_ptr()), c_void_p(i.data_ptr()),
+                        c_void_p(e.data_ptr()), c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
+                        _lib.current_stream_ptr()))
+                else:
+                    _lib.check(self.lib.rf_search_exhaustive_filtered(
+                        self.handle, c_void_p(filt.data_ptr()), c_void_p(q16.data_ptr()), B, page, id_base,
+                        c_void_p(bs.data_ptr()), c_void_p(bi.data_ptr()), c_void_p(s.data_ptr()),
+                        c_void_p(i.data_ptr()), c_void_p(e.data_ptr()), c_void_p(self.workspace.data_ptr()),
+                        self.workspace_bytes, _lib.current_stream_ptr()))
             scores.append(s)
             ids.append(i)
             exacts.append(e)
@@ -244,17 +267,17 @@ class GpuIndex:
         out = (torch.cat(scores, 1)[:, :k].contiguous(), torch.cat(ids, 1)[:, :k].contiguous())
         return out + (torch.cat(exacts, 1)[:, :k].contiguous(),) if want_exact else out
 
-    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False):
+    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
         """rf_search, then re-run any query the fused path could not prove exact
         (flags != 0) through the exhaustive fp64 kernel.  Serialised: the index
-        workspace is shared (SURVEY.md 8b threading row)."""
+        workspace is shared (SURVEY.md 8b threading row).  filt: over the passing rows."""
         torch = _torch()
         with self._lock:
-            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact)
+            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt)
             bad = torch.nonzero(flags != 0).flatten()
             if bad.numel() > 0:
                 qb = q16.to(self.device)[bad].contiguous()
-                s2, i2, e2 = self.search_exhaustive(qb, k, id_base, want_exact)
+                s2, i2, e2 = self.search_exhaustive(qb, k, id_base, want_exact, filt=filt)
                 scores[bad] = s2
                 ids[bad] = i2
                 if exact is not None:
@@ -263,10 +286,10 @@ class GpuIndex:
 
     ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
 
-    def search_host(self, q16, k: int):
+    def search_host(self, q16, k: int, filt=None):
         """search() whose results land on the host with ONE synchronisation: scores, ids and
         flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
-        ids i64 [B,k]) numpy arrays (the caller's own copies)."""
+        ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows."""
         torch = _torch()
         with self._lock:
             B = q16.shape[0]
@@ -280,9 +303,9 @@ class GpuIndex:
                 # query-sized results: the merge kernel stores straight into the pinned host buffers
                 # (host-coherent memory, mapped at the same address on the device) -- no copy commands,
                 # only the synchronisation
-                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]))
+                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]), filt=filt)
             else:
-                scores, ids, _, flags = self.search_raw(q16, k)
+                scores, ids, _, flags = self.search_raw(q16, k, filt=filt)
                 bufs[0].copy_(scores, non_blocking=True)
                 bufs[1].copy_(ids, non_blocking=True)
                 bufs[2].copy_(flags, non_blocking=True)
@@ -290,7 +313,7 @@ class GpuIndex:
             if bool(bufs[2].any()):
                 bad = torch.nonzero(bufs[2] != 0).flatten()
                 qb = q16.to(self.device)[bad.to(self.device)].contiguous()
-                s2, i2, _ = self.search_exhaustive(qb, k)
+                s2, i2, _ = self.search_exhaustive(qb, k, filt=filt)
                 bufs[0][bad] = s2.cpu()
                 bufs[1][bad] = i2.cpu()
             # private copies, taken while the lock is still held: the pinned buffers are shared by every caller with
@@ -306,6 +329,77 @@ class GpuIndex:
             _lib.check(self.lib.rf_debug_scores(self.handle, c_void_p(q16.data_ptr()), q16.shape[0], n,
                                                 c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
         return out
+
+
+def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int):
+    """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
+    rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors
+    {period, chunk_type, statement_type codes int32 [n_rows], primary_value fp64 [n_rows]}."""
+    torch = _torch()
+    lib = _lib.load_library()
+    cs, rl = filter_expr.program_arrays(program)
+    with torch.cuda.device(device):
+        buf = torch.empty(lib.rf_filter_bytes(n_rows), dtype=torch.uint8, device=device)
+        cs_d = torch.from_numpy(cs.view(np.int32)).to(device) if cs.size else None
+        rl_d = torch.from_numpy(rl.view(np.int32)).to(device) if rl.size else None
+        ptrs = (c_void_p * _lib.RF_FILTER_COLUMNS)(*[c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+                                                     for t in columns])
+        ops = program.ops_ctypes()
+        _lib.check(lib.rf_filter_eval(ops, len(ops), c_void_p(cs_d.data_ptr()) if cs_d is not None else None,
+                                      c_void_p(rl_d.data_ptr()) if rl_d is not None else None, ptrs, n_rows,
+                                      c_void_p(buf.data_ptr()), _lib.current_stream_ptr()))
+    # (cs_d / rl_d may be freed now: the caching allocator reuses their memory in stream order)
+    return buf
+
+
+def filter_mask_bits(buf, n_rows: int):
+    """The row mask of a filter buffer as a host bool array [n_rows] (synchronises)."""
+    nblk = (n_rows + 31) // 32
+    words = buf[16:16 + 4 * nblk].cpu().numpy().view(np.uint32)
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little").astype(bool)
+    return bits[:n_rows]
+
+
+class _DeviceColumns:
+    """The device mirror of the four filterable scalar columns: period / chunk_type /
+    statement_type as int32 codes into append-only dictionaries, primary_value as fp64.
+    Synced lazily from the host lists: rows appended since the last sync are encoded; a
+    shorter collection (after drop) is re-encoded from row 0 (the dictionaries stay)."""
+
+    def __init__(self, device):
+        torch = _torch()
+        self.device = device
+        self.dicts = {f: [] for f in filter_expr.VARCHAR_FIELDS}
+        self._code = {f: {} for f in filter_expr.VARCHAR_FIELDS}
+        self.codes = {f: torch.empty(0, dtype=torch.int32, device=device) for f in filter_expr.VARCHAR_FIELDS}
+        self.values = torch.empty(0, dtype=torch.float64, device=device)
+        self.n = 0
+
+    def sync(self, columns: dict, n: int) -> None:
+        torch = _torch()
+        if n < self.n:
+            self.codes = {f: t[:0] for f, t in self.codes.items()}
+            self.values = self.values[:0]
+            self.n = 0
+        if n == self.n:
+            return
+        lo = self.n
+        for f in filter_expr.VARCHAR_FIELDS:
+            d, code = self.dicts[f], self._code[f]
+            enc = np.empty(n - lo, dtype=np.int32)
+            for j, v in enumerate(columns[f][lo:n]):
+                c = code.get(v)
+                if c is None:
+                    c = code[v] = len(d)
+                    d.append(v)
+                enc[j] = c
+            self.codes[f] = torch.cat([self.codes[f], torch.from_numpy(enc).to(self.device)])
+        vals = np.asarray(columns["primary_value"][lo:n], dtype=np.float64)
+        self.values = torch.cat([self.values, torch.from_numpy(vals).to(self.device)])
+        self.n = n
+
+    def tensors(self):
+        return [self.codes[f] for f in filter_expr.VARCHAR_FIELDS] + [self.values]
 
 
 class _Entity:
@@ -351,6 +445,8 @@ class CorpusStore:
         self.index = index if index is not None else GpuIndex(dim, capacity, device)
         self.columns: dict[str, list] = {f: [] for f in SCALAR_FIELDS}
         self._pk_row: dict[Any, int] = {}
+        self._dcols = None                  # _DeviceColumns, built by the first filtered call
+        self._filter_lock = threading.Lock()
 
     # -- pymilvus-shaped lifecycle ---------------------------------------------
     def flush(self) -> None:
@@ -368,6 +464,7 @@ class CorpusStore:
         for col in self.columns.values():
             col.clear()
         self._pk_row.clear()
+        self._dcols = None
 
     @property
     def num_entities(self) -> int:
@@ -440,16 +537,18 @@ class CorpusStore:
             q = q[None, :]
         return self.index.to_fp16(q, normalize=self.metric_type == "COSINE")
 
-    def search_rows(self, data, limit: int):
-        """(scores f32 [B,k'], rows i64 [B,k']) as host numpy, k' = min(limit, N)."""
+    def search_rows(self, data, limit: int, filt=None):
+        """(scores f32 [B,k'], rows i64 [B,k']) as host numpy, k' = min(limit, N).  filt: a
+        filter buffer (build_filter): the top-k of the passing rows, padded with -1 rows."""
         if limit < 1:
             raise ValueError("limit must be >= 1")
         q16 = self._prepare_queries(data)
+        kw = {} if filt is None else {"filt": filt}
         if limit > _lib.RF_MAX_K:
-            scores, rows = self.index.search_large(q16, limit)   # paged, exhaustive beyond 64
+            scores, rows = self.index.search_large(q16, limit, **kw)   # paged, exhaustive beyond 64
             kk = min(limit, self.num_entities)
             return scores[:, :kk].cpu().numpy(), rows[:, :kk].cpu().numpy()
-        scores, rows = self.index.search_host(q16, limit)   # one synchronisation for the whole download
+        scores, rows = self.index.search_host(q16, limit, **kw)   # one synchronisation for the whole download
         kk = min(limit, self.num_entities)
         return scores[:, :kk], rows[:, :kk]
 
@@ -461,13 +560,14 @@ class CorpusStore:
         metric = (param or {}).get("metric_type", self.metric_type).upper()
         if metric != self.metric_type:
             raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
-        if expr not in (None, ""):
-            raise NotImplementedError("filtered search is outside the reference's use of this path")
         fields = list(output_fields or [])
         for f in fields:
             if f not in self.columns:
                 raise KeyError(f"unknown output field {f!r}")
-        scores, rows = self.search_rows(data, limit)
+        if filter_expr.is_empty(expr):
+            scores, rows = self.search_rows(data, limit)
+        else:
+            scores, rows = self.search_rows(data, limit, filt=self.build_filter(expr))
         out = []
         for b in range(rows.shape[0]):
             hits = []
@@ -535,10 +635,30 @@ class CorpusStore:
         st._pk_row = {pk: i for i, pk in enumerate(st.columns["id"])}
         return st
 
+    # -- filters -------------------------------------------------------------------------
+    def build_filter(self, expr: str):
+        """Parse + compile `expr` (rag_fin_amd.filter_expr; ValueError on a bad expression) and
+        evaluate it on the device into a fresh filter buffer for this collection's rows.  One
+        buffer per call: concurrent searches with different filters do not share one."""
+        node = filter_expr.parse(expr)
+        with self._filter_lock:
+            n = self.num_entities
+            if self._dcols is None:
+                self._dcols = _DeviceColumns(self.index.device)
+            self._dcols.sync(self.columns, n)
+            prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row)
+            return eval_filter(self.index.device, prog, self._dcols.tensors(), n)
+
+    def filter_rows(self, expr: str) -> np.ndarray:
+        """Row numbers (ascending) that pass `expr`."""
+        return np.flatnonzero(filter_mask_bits(self.build_filter(expr), self.num_entities))
+
     # -- scalar queries ----------------------------------------------------------------
     def query(self, expr: str = "", limit: int | None = None,
               output_fields: Iterable[str] | None = None) -> list[dict]:
-        """`query(expr="id in [...]")` fetch-by-PK and `query(expr="", limit=n)` scan."""
+        """`query(expr="id in [...]")` fetch-by-PK (key order), `query(expr="", limit=n)` scan, and
+        any other filter expression (rag_fin_amd.filter_expr): the matching rows in ascending
+        row order."""
         fields = list(output_fields or ["id"])
         want_vec = "embedding" in fields
         fields = [f for f in fields if f != "embedding"]
@@ -548,13 +668,11 @@ class CorpusStore:
         if expr is None or expr.strip() == "":
             rows = list(range(self.num_entities))
         else:
-            m = _ID_IN.match(expr)
-            if not m:
-                raise NotImplementedError(f"unsupported expr {expr!r} (only 'id in [...]')")
-            import ast
-            body = m.group(1).strip()
-            keys = list(ast.literal_eval("[" + body + "]")) if body else []
-            rows = [self._pk_row[k] for k in keys if k in self._pk_row]
+            keys = _id_in_keys(expr)
+            if keys is not None:
+                rows = [self._pk_row[k] for k in keys if k in self._pk_row]
+            else:
+                rows = self._expr_rows(expr).tolist()
         if limit is not None:
             rows = rows[:limit]
         vecs = self.index.get_rows(np.asarray(rows, dtype=np.int64)).float().cpu().numpy() \
@@ -568,3 +686,20 @@ class CorpusStore:
                 rec["embedding"] = vecs[j].tolist()
             out.append(rec)
         return out
+
+    def _expr_rows(self, expr: str) -> np.ndarray:
+        return self.filter_rows(expr)
+
+
+def _id_in_keys(expr: str):
+    """The keys of the original `id in [...]` form (a Python list literal, kept in key order),
+    or None when `expr` is not of that form."""
+    m = _ID_IN.match(expr)
+    if not m:
+        return None
+    import ast
+    body = m.group(1).strip()
+    try:
+        return list(ast.literal_eval("[" + body + "]")) if body else []
+    except (ValueError, SyntaxError):
+        return None
