@@ -19,8 +19,8 @@
  *   - device pointers must be 16-byte aligned.
  *   - threading: an rf_index_t / rf_encoder_t may be used by any number of host threads at
  *     once as long as each concurrent call has its OWN workspace (and normally its own
- *     stream); the handles hold no per-call state.  rf_index_add_f16 / rf_index_reset must
- *     not run concurrently with a search on the same index.  A process may hold indexes and
+ *     stream); the handles hold no per-call state.  rf_index_add_f16 / rf_index_reset /
+ *     rf_index_compact must not run concurrently with a search on the same index.  A process may hold indexes and
  *     encoders on several devices; the calling thread's current HIP device must be the
  *     handle's device (hipSetDevice / torch.cuda.device).
  */
@@ -76,6 +76,19 @@ int rf_index_destroy(rf_index_t* ix);
 /* Collection.insert/flush/load -- "chunking_storing (1).py":383-396.
  * rows_dev: fp16 [n, dim] row-major.  Appends n rows (ids size .. size+n-1). */
 int rf_index_add_f16(rf_index_t* ix, const void* rows_dev, int64_t n, void* stream);
+/* Collection.delete(expr) / upsert: keep rows keep_rows_dev[0..n_keep) (int64, STRICTLY ascending,
+ * all < size) in that order and drop the rest; row keep_rows_dev[j] becomes row j.  Afterwards
+ * the index is bit-identical to one created empty and given the surviving rows with
+ * rf_index_add_f16 in order: same tiles for blocks [0, ceil(n_keep/32)), pad rows of the last
+ * block zero, same max_norm2 word (recomputed over the survivors, not kept).  size becomes n_keep
+ * (host counter, no sync).  scratch_dev: caller-owned, 16-byte aligned, >= 32 * dim * 2 bytes; the
+ * compaction runs in windows of scratch_bytes / (2 * dim) rows (rounded down to a multiple of 32),
+ * so a larger scratch means fewer windows.  n_keep == 0 acts as rf_index_reset (keep_rows_dev and
+ * scratch_dev may then be null); n_keep == size still rewrites the index.  Ascending order is a
+ * precondition the caller checks (it is not verified on the device).  Stream-ordered; like
+ * rf_index_add_f16 it must not run concurrently with a search of the same index. */
+int rf_index_compact(rf_index_t* ix, const int64_t* keep_rows_dev, int64_t n_keep,
+                     void* scratch_dev, size_t scratch_bytes, void* stream);
 /* Collection.num_entities -- vector_rag_mcp/main.py:113,120,164 */
 int64_t rf_index_size(const rf_index_t* ix);
 int rf_index_dim(const rf_index_t* ix);

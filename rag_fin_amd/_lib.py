@@ -67,6 +67,7 @@ SIGNATURES = {
     "rf_index_size": (c_int64, [c_void_p]),
     "rf_index_dim": (c_int, [c_void_p]),
     "rf_index_reset": (c_int, [c_void_p, c_void_p]),
+    "rf_index_compact": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "rf_index_get_rows_f16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_normalize_f32_to_f16": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "rf_search_workspace_bytes": (c_size_t, [c_void_p]),

@@ -170,6 +170,17 @@ __global__ void k_get_rows(const uint4* __restrict__ tiles, const int64_t* __res
   }
 }
 
+// Zero rows [row0, row0 + n) of the tiled layout, every chunk (the pad rows of the last block
+// after a compaction).  One thread per 16-byte chunk.
+__global__ void k_zero_rows(uint4* __restrict__ tiles, int64_t row0, int64_t n, int KS) {
+  const int chunks = KS * 2;
+  const int64_t total = n * chunks;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < total; i += stride)
+    tiles[rf_chunk_index(row0 + i / chunks, (int)(i % chunks), KS)] = make_uint4(0, 0, 0, 0);
+}
+
 // fp32 row -> (optionally L2-normalised) fp16 row.  One wave per row; the sum
 // of squares is accumulated per lane over d = lane, lane+64, ... and combined
 // with an xor butterfly (fixed order, so the result is reproducible).
@@ -246,6 +257,70 @@ extern "C" int rf_index_add_f16(rf_index_t* ix, const void* rows_dev, int64_t n,
                      (const _Float16*)rows_dev, n, ix->dim, ix->max_norm2);
   RF_HIP(hipGetLastError());
   ix->size += n;
+  return RF_OK;
+}
+
+// In-place compaction (include/ragfin.h).  Output rows are produced in windows [j0, j1) of W rows
+// (W a multiple of 32, so every window starts on a block boundary), in ascending order:
+//   (a) k_get_rows gathers source rows keep[j0..j1) into the scratch, row-major;
+//   (b) k_tile_rows writes the scratch to destination rows j0..j1;
+//   (c) k_max_norm2 folds the scratch rows into the (zeroed) norm tracker.
+// Why in place is safe: keep is strictly ascending, so keep[j] >= j and every source row of window
+// w is >= j0, while windows before w wrote only rows < j0.  Inside a window the whole gather
+// completes (stream order) before the first tile store.  Each 16-byte chunk holds dims of exactly
+// one row (rf_chunk_index), so a store to row j never touches another row's bytes.  Rows
+// [n_keep, 32 * ceil(n_keep / 32)) are zeroed last: the sample pass reads whole blocks and a later
+// rf_index_add_f16 zeroes only blocks past the last live one, so pad rows must read as 0.
+// (c) sums each row in the order rf_index_add_f16 does and the tracker is a max, so the word equals
+// that of a fresh build of the survivors.
+extern "C" int rf_index_compact(rf_index_t* ix, const int64_t* keep_rows_dev, int64_t n_keep,
+                                void* scratch_dev, size_t scratch_bytes, void* stream) {
+  if (!ix) {
+    rf_set_error("rf_index_compact: null index");
+    return RF_ERR_INVALID;
+  }
+  if (n_keep < 0 || n_keep > ix->size) {
+    rf_set_error("rf_index_compact: n_keep %lld outside [0, size %lld]", (long long)n_keep,
+                 (long long)ix->size);
+    return RF_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (n_keep == 0) {  // what rf_index_reset does; keep_rows / scratch are not read
+    ix->size = 0;
+    RF_HIP(hipMemsetAsync(ix->max_norm2, 0, 256, st));
+    return RF_OK;
+  }
+  if (!keep_rows_dev || !scratch_dev) {
+    rf_set_error("rf_index_compact: null keep_rows or scratch");
+    return RF_ERR_INVALID;
+  }
+  if (((uintptr_t)keep_rows_dev & 7) != 0 || ((uintptr_t)scratch_dev & 15) != 0) {
+    rf_set_error("rf_index_compact: keep_rows must be 8-byte and scratch 16-byte aligned");
+    return RF_ERR_INVALID;
+  }
+  const size_t row_bytes = (size_t)ix->dim * 2;
+  if (scratch_bytes < RF_BLOCK_ROWS * row_bytes) {
+    rf_set_error("rf_index_compact: scratch %zu B < %zu B (32 rows)", scratch_bytes,
+                 RF_BLOCK_ROWS * row_bytes);
+    return RF_ERR_CAPACITY;
+  }
+  const int KS = ix->KS;
+  const int64_t W = (int64_t)(scratch_bytes / row_bytes) / RF_BLOCK_ROWS * RF_BLOCK_ROWS;
+  RF_HIP(hipMemsetAsync(ix->max_norm2, 0, 256, st));
+  for (int64_t j0 = 0; j0 < n_keep; j0 += W) {
+    const int64_t nw = (n_keep - j0 < W) ? n_keep - j0 : W;
+    hipLaunchKernelGGL(k_get_rows, dim3(grid_for(nw * KS * 2, 256)), dim3(256), 0, st, ix->tiles,
+                       keep_rows_dev + j0, nw, KS, ix->size, (uint4*)scratch_dev);
+    rf_launch_tile_rows(scratch_dev, ix->tiles, j0, nw, KS, st);
+    hipLaunchKernelGGL(k_max_norm2, dim3(grid_for(nw * 64, 256)), dim3(256), 0, st,
+                       (const _Float16*)scratch_dev, nw, ix->dim, ix->max_norm2);
+  }
+  const int64_t pad = blocks_for(n_keep) * RF_BLOCK_ROWS - n_keep;
+  if (pad > 0)
+    hipLaunchKernelGGL(k_zero_rows, dim3(grid_for(pad * KS * 2, 256)), dim3(256), 0, st, ix->tiles,
+                       n_keep, pad, KS);
+  RF_HIP(hipGetLastError());
+  ix->size = n_keep;
   return RF_OK;
 }
 

@@ -37,7 +37,8 @@ struct rf_index {
 };
 // An index is immutable during searches (no mutable host state: any number of threads may
 // search one index concurrently, each with its own workspace and stream); rf_index_add_f16 /
-// rf_index_reset must not run concurrently with a search (include/ragfin.h, "Threading").
+// rf_index_reset / rf_index_compact must not run concurrently with a search (include/ragfin.h,
+// "Threading").
 
 // ---- tuning knobs ------------------------------------------------------------------------
 // The shipped library has NO run-time tuning surface: every knob below is a compile-time

@@ -17,14 +17,18 @@ import os
 from . import chunker
 
 
-def ingest(store, embedder, chunks) -> int:
+def ingest(store, embedder, chunks, upsert: bool = False) -> int:
     """The reference's encode + insert + flush + load
     ("chunking_storing (1).py":377-397) on the GPU: texts are embedded by rf_encode
-    and the fp16 rows go straight into the HBM corpus (no host round trip)."""
+    and the fp16 rows go straight into the HBM corpus (no host round trip).
+    upsert=True: chunks whose id is already stored replace the stored rows (a restated
+    quarter is re-ingested in place of dropping the collection); otherwise an existing id
+    raises ValueError."""
     if not chunks:
         return 0
     emb = embedder.encode_to_device([c["text"] for c in chunks])
-    n = store.insert(chunker.insert_columns(chunks, emb))
+    cols = chunker.insert_columns(chunks, emb)
+    n = store.upsert(cols).upsert_count if upsert else store.insert(cols)
     store.flush()
     store.load()
     return n
@@ -41,16 +45,21 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator)
 
 
-def ingest_sharded(store, embedder, chunks) -> int:
+def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
     """COLLECTIVE form of ingest(): every rank holds the whole chunk list (text work is cheap),
-    embeds only ITS slice (encoder replicas) and keeps those rows in its HBM."""
+    embeds only ITS slice (encoder replicas) and keeps those rows in its HBM.
+    upsert: as for ingest()."""
     from .sharded import ShardedSearcher
     if not chunks:
         return 0
     lo, hi = ShardedSearcher.shard_bounds(len(chunks), store.world, store.rank)
     emb = embedder.encode_to_device([c["text"] for c in chunks[lo:hi]])
     cols = chunker.insert_columns(chunks, None)
-    n = store.add(cols[0], cols[1], emb, cols[3], cols[4], cols[5], cols[6], local=True)
+    if upsert:
+        cols[2] = emb
+        n = store.upsert(cols, local=True).upsert_count
+    else:
+        n = store.add(cols[0], cols[1], emb, cols[3], cols[4], cols[5], cols[6], local=True)
     store.flush()
     store.load()
     return n

@@ -30,7 +30,7 @@ import threading
 
 from . import _lib, filter_expr
 from .sharded import HipShardBackend, ShardedSearcher
-from .store import SCALAR_FIELDS, CorpusStore
+from .store import SCALAR_FIELDS, CorpusStore, MutationResult, _id_in_keys
 
 
 logger = logging.getLogger(__name__)
@@ -76,6 +76,12 @@ class ShardedCorpusStore(CorpusStore):
         batch [n, dim] (each rank keeps its slice), or with local=True only this rank's slice
         [hi - lo, dim] where (lo, hi) = ShardedSearcher.shard_bounds(n, world, rank) -- the
         encoder runs as replicas, each rank embedding its own rows."""
+        with self._rw.write():
+            return self._add_sharded(ids, texts, embeddings, periods, chunk_types, statement_types,
+                                     primary_values, local)
+
+    def _add_sharded(self, ids, texts, embeddings, periods, chunk_types, statement_types, primary_values,
+                     local: bool) -> int:
         torch = _torch()
         n = len(ids)
         cols = (texts, periods, chunk_types, statement_types, primary_values)
@@ -117,8 +123,63 @@ class ShardedCorpusStore(CorpusStore):
 
     def drop(self) -> None:
         torch = _torch()
-        super().drop()
-        self._id_map = torch.empty(0, dtype=torch.int64, device=self.index.device)
+        with self._rw.write():
+            super().drop()
+            self._id_map = torch.empty(0, dtype=torch.int64, device=self.index.device)
+            self._searcher = None
+
+    # -- mutation (COLLECTIVE) ----------------------------------------------------------------------
+    # Every rank holds the full columns, so every rank computes the same global keep mask without
+    # talking to the others; each compacts its own shard (its local rows whose global id survives)
+    # and renumbers _id_map through new_global = cumsum(keep) - 1.  Shards become uneven; add
+    # (shard_bounds per batch), _save (through _id_map) and the paged large-limit path do not care.
+    def delete(self, expr: str) -> MutationResult:
+        """COLLECTIVE.  `id in [...]` only (other expressions raise NotImplementedError, as the
+        sharded query / filtered search do)."""
+        if filter_expr.is_empty(expr):
+            raise ValueError("delete needs a non-empty expression (use drop() to remove everything)")
+        keys = _id_in_keys(expr)
+        if keys is None:
+            raise NotImplementedError(f"delete expression {expr!r}: the sharded store supports 'id in [...]' only")
+        with self._rw.write(), self._coll_lock:
+            self._check_not_leading()
+            return self._delete_mask(self._pk_mask(keys))
+
+    def upsert(self, data, local: bool = False) -> MutationResult:
+        """COLLECTIVE.  As CorpusStore.upsert; `local` as for add (the embedding column holds
+        only this rank's slice of the batch)."""
+        if len(data) != 7:
+            raise ValueError("upsert expects 7 columns: id, text, embedding, period, chunk_type, "
+                             "statement_type, primary_value")
+        ids, texts, emb, periods, ctypes_, stypes, pvals = data
+        ids = list(ids)
+        n = len(ids)
+        if any(len(c) != n for c in (texts, periods, ctypes_, stypes, pvals)):
+            raise ValueError("upsert columns differ in length")
+        if len(set(ids)) != n:
+            raise ValueError("duplicate primary keys in upsert")
+        lo, hi = ShardedSearcher.shard_bounds(n, self.world, self.rank)
+        want = (hi - lo if local else n, self.dim)
+        if tuple(emb.shape if hasattr(emb, "shape") else np.asarray(emb).shape) != want:
+            raise ValueError(f"rank {self.rank}: embeddings must be {list(want)}")
+        with self._rw.write(), self._coll_lock:
+            self._check_not_leading()
+            self._delete_mask(self._pk_mask(ids))
+            self.add(ids, texts, emb, periods, ctypes_, stypes, pvals, local=local)
+            return MutationResult(ids, insert_count=n, upsert_count=n)
+
+    def _check_not_leading(self) -> None:
+        if self._leading:
+            raise RuntimeError("delete / upsert are COLLECTIVE: call stop_workers() first so that every rank "
+                               "takes part")
+
+    def _compact_index(self, keep_mask: np.ndarray, keep: np.ndarray) -> None:
+        torch = _torch()
+        gmap = self._id_map.cpu().numpy()
+        local_keep = np.flatnonzero(keep_mask[gmap])
+        new_global = np.cumsum(keep_mask, dtype=np.int64) - 1
+        self.index.compact(local_keep)
+        self._id_map = torch.from_numpy(new_global[gmap[local_keep]]).to(self._id_map.device)
         self._searcher = None
 
     def flush(self) -> None:
@@ -177,7 +238,8 @@ class ShardedCorpusStore(CorpusStore):
         if limit < 1:
             raise ValueError("limit must be >= 1")
         q16 = self._prepare_queries(data).contiguous()
-        with self._coll_lock:   # broadcasts + collective + download as ONE unit (see __init__)
+        # the store's read lock first, then the collective lock: delete / upsert take them in that order
+        with self._rw.read(), self._coll_lock:   # broadcasts + collective + download as ONE unit (see __init__)
             if self._leading:
                 hdr = torch.tensor([q16.shape[0], limit], dtype=torch.int64, device=self._bdev)
                 self.dist.broadcast(hdr, src=0, group=self.group)
@@ -242,7 +304,7 @@ class ShardedCorpusStore(CorpusStore):
         if "embedding" not in fields:
             return super().query(expr, limit, fields)
         # COLLECTIVE when vectors are asked for: every rank contributes the rows it owns
-        with self._coll_lock:
+        with self._rw.read(), self._coll_lock:
             return self._query_with_vectors(expr, limit, fields)
 
     def _query_with_vectors(self, expr, limit, fields):
@@ -271,7 +333,7 @@ class ShardedCorpusStore(CorpusStore):
     # -- persistence: the single-GPU format, written / read in place by every rank (one node) -------------
     def save(self, path: str, chunk_rows: int = 1 << 18) -> None:
         """COLLECTIVE."""
-        with self._coll_lock:
+        with self._rw.read(), self._coll_lock:
             self._save(path, chunk_rows)
 
     def _save(self, path: str, chunk_rows: int) -> None:

@@ -20,7 +20,9 @@ CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import itertools
 import re
 import threading
 from ctypes import c_void_p
@@ -122,6 +124,35 @@ class GpuIndex:
                                                         c_void_p(out.data_ptr()),
                                                         _lib.current_stream_ptr()))
         return out
+
+    COMPACT_WINDOW_ROWS = 1 << 16   # rows per rf_index_compact window (scratch = rows * dim * 2 bytes)
+
+    def compact(self, keep_rows, window_rows: int | None = None) -> None:
+        """Keep rows `keep_rows` (strictly ascending row numbers) in that order and drop the rest,
+        in place (rf_index_compact): the index then equals a fresh one given the survivors.
+        window_rows: rows per compaction window (a multiple of 32; default COMPACT_WINDOW_ROWS).
+        Takes the index lock, so it cannot interleave with search / search_host / a page of
+        search_large."""
+        torch = _torch()
+        keep = np.asarray(keep_rows, dtype=np.int64).reshape(-1)
+        n = keep.size
+        size = self.size
+        if n and (keep[0] < 0 or keep[-1] >= size or (n > 1 and bool((np.diff(keep) <= 0).any()))):
+            raise ValueError(f"keep_rows must be strictly ascending row numbers in [0, {size})")
+        w = self.COMPACT_WINDOW_ROWS if window_rows is None else int(window_rows)
+        if w < 32 or w % 32:
+            raise ValueError("window_rows must be a positive multiple of 32")
+        w = min(w, max(32, (n + 31) // 32 * 32))
+        with self._lock, torch.cuda.device(self.device):
+            if n == 0:
+                _lib.check(self.lib.rf_index_compact(self.handle, None, 0, None, 0, _lib.current_stream_ptr()))
+                return
+            keep_d = torch.from_numpy(keep).to(self.device)
+            scratch = torch.empty(w * self.dim * 2, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rf_index_compact(self.handle, c_void_p(keep_d.data_ptr()), n,
+                                                 c_void_p(scratch.data_ptr()), scratch.numel(),
+                                                 _lib.current_stream_ptr()))
+        # keep_d / scratch are released in stream order (caching allocator): no sync needed
 
     def get_rows(self, row_ids):
         torch = _torch()
@@ -398,8 +429,105 @@ class _DeviceColumns:
         self.values = torch.cat([self.values, torch.from_numpy(vals).to(self.device)])
         self.n = n
 
+    def compact(self, keep: np.ndarray) -> None:
+        """Keep rows `keep` (ascending) of a mirror synced to the whole collection; the
+        dictionaries are append-only and stay valid."""
+        torch = _torch()
+        k = torch.from_numpy(np.ascontiguousarray(keep, dtype=np.int64)).to(self.device)
+        self.codes = {f: t.index_select(0, k) for f, t in self.codes.items()}
+        self.values = self.values.index_select(0, k)
+        self.n = int(keep.size)
+
     def tensors(self):
         return [self.codes[f] for f in filter_expr.VARCHAR_FIELDS] + [self.values]
+
+
+class _RWLock:
+    """Readers/writer lock of a store: any number of readers (search, query, save) at once, or
+    one writer (add, delete, upsert, drop).  Re-entrant per thread: a reader may read again, a
+    writer may read or write again; a reader asking to write raises.  A waiting writer holds
+    off new readers, so a stream of searches cannot starve an upsert."""
+
+    def __init__(self):
+        self._cond = threading.Condition(threading.Lock())
+        self._readers = 0
+        self._writer = None          # thread ident of the writer
+        self._writer_depth = 0
+        self._writers_waiting = 0
+        self._tls = threading.local()
+
+    @contextlib.contextmanager
+    def read(self):
+        depth = getattr(self._tls, "depth", 0)
+        if depth or self._writer == threading.get_ident():
+            self._tls.depth = depth + 1
+            try:
+                yield
+            finally:
+                self._tls.depth = depth
+            return
+        with self._cond:
+            while self._writer is not None or self._writers_waiting:
+                self._cond.wait()
+            self._readers += 1
+        self._tls.depth = 1
+        try:
+            yield
+        finally:
+            self._tls.depth = 0
+            with self._cond:
+                self._readers -= 1
+                if self._readers == 0:
+                    self._cond.notify_all()
+
+    @contextlib.contextmanager
+    def write(self):
+        me = threading.get_ident()
+        if self._writer == me:
+            self._writer_depth += 1
+            try:
+                yield
+            finally:
+                self._writer_depth -= 1
+            return
+        if getattr(self._tls, "depth", 0):
+            raise RuntimeError("a store mutation was called while this thread holds the store's read lock")
+        with self._cond:
+            self._writers_waiting += 1
+            try:
+                while self._writer is not None or self._readers:
+                    self._cond.wait()
+            finally:
+                self._writers_waiting -= 1
+            self._writer = me
+        try:
+            yield
+        finally:
+            with self._cond:
+                self._writer = None
+                self._cond.notify_all()
+
+
+class MutationResult:
+    """What delete / upsert return, shaped like pymilvus' MutationResult."""
+
+    def __init__(self, primary_keys=(), insert_count: int = 0, delete_count: int = 0, upsert_count: int = 0):
+        self.primary_keys = list(primary_keys)
+        self.insert_count = insert_count
+        self.delete_count = delete_count
+        self.upsert_count = upsert_count
+
+    @property
+    def succ_count(self) -> int:
+        return max(self.insert_count, self.delete_count, self.upsert_count)
+
+    @property
+    def err_count(self) -> int:
+        return 0
+
+    def __repr__(self):
+        return (f"(insert count: {self.insert_count}, delete count: {self.delete_count}, "
+                f"upsert count: {self.upsert_count})")
 
 
 class _Entity:
@@ -447,6 +575,10 @@ class CorpusStore:
         self._pk_row: dict[Any, int] = {}
         self._dcols = None                  # _DeviceColumns, built by the first filtered call
         self._filter_lock = threading.Lock()
+        # search / query / save read; add / delete / upsert / drop write.  A search hands out row
+        # numbers and then reads the host columns at those rows (search_large over several pages):
+        # a delete in between would pin another row's entity on a hit.
+        self._rw = _RWLock()
 
     # -- pymilvus-shaped lifecycle ---------------------------------------------
     def flush(self) -> None:
@@ -460,11 +592,12 @@ class CorpusStore:
 
     def drop(self) -> None:
         """utility.drop_collection + recreate ("chunking_storing (1).py":25-28)."""
-        self.index.reset()
-        for col in self.columns.values():
-            col.clear()
-        self._pk_row.clear()
-        self._dcols = None
+        with self._rw.write():
+            self.index.reset()
+            for col in self.columns.values():
+                col.clear()
+            self._pk_row.clear()
+            self._dcols = None
 
     @property
     def num_entities(self) -> int:
@@ -484,6 +617,10 @@ class CorpusStore:
     def add(self, ids: Sequence, texts: Sequence[str], embeddings, periods: Sequence[str],
             chunk_types: Sequence[str], statement_types: Sequence[str],
             primary_values: Sequence[float]) -> int:
+        with self._rw.write():
+            return self._add(ids, texts, embeddings, periods, chunk_types, statement_types, primary_values)
+
+    def _add(self, ids, texts, embeddings, periods, chunk_types, statement_types, primary_values) -> int:
         torch = _torch()
         n = len(ids)
         cols = (texts, periods, chunk_types, statement_types, primary_values)
@@ -526,6 +663,94 @@ class CorpusStore:
         ids, texts, emb, periods, ctypes_, stypes, pvals = data
         return self.add(ids, texts, emb, periods, ctypes_, stypes, pvals)
 
+    # -- mutation: Collection.delete(expr) / Collection.upsert(data) -----------------------
+    # Deletes compact eagerly: the index, the host columns, the pk map and the device filter
+    # mirror are left exactly as a fresh insert of the surviving rows (in their old order) would
+    # leave them, so no search path knows about deletes.
+    def delete(self, expr: str) -> MutationResult:
+        """Remove every row `expr` matches (any expression filtered search accepts, `id in [...]`
+        included; the predicate runs on the GPU).  An empty expression raises ValueError, as
+        Milvus refuses to delete everything: use drop().  Matching nothing changes nothing."""
+        if filter_expr.is_empty(expr):
+            raise ValueError("delete needs a non-empty expression (use drop() to remove everything)")
+        with self._rw.write():
+            return self._delete_mask(self._match_mask(expr))
+
+    def upsert(self, data: Sequence[Sequence]) -> MutationResult:
+        """Column-major rows as for insert.  Rows whose primary key exists are deleted, then every
+        row is appended in the given order: a replaced row moves to the END of the collection (so
+        on an exact score tie -- ranked by score desc, then row asc -- it ranks after older rows).
+        Duplicate keys inside one batch raise ValueError, as insert does."""
+        if len(data) != 7:
+            raise ValueError("upsert expects 7 columns: id, text, embedding, period, chunk_type, "
+                             "statement_type, primary_value")
+        ids, texts, emb, periods, ctypes_, stypes, pvals = data
+        ids = list(ids)
+        with self._rw.write():
+            emb = self._check_upsert(ids, (texts, periods, ctypes_, stypes, pvals), emb)
+            self._delete_mask(self._pk_mask(ids))
+            n = self.add(ids, texts, emb, periods, ctypes_, stypes, pvals)
+            return MutationResult(ids, insert_count=n, upsert_count=n)
+
+    def _check_upsert(self, ids, cols, emb):
+        """Everything add() would refuse, checked BEFORE the old rows go; returns the batch's
+        vectors as the fp16 rows add() stores."""
+        torch = _torch()
+        n = len(ids)
+        if any(len(c) != n for c in cols):
+            raise ValueError("upsert columns differ in length")
+        if len(set(ids)) != n:
+            raise ValueError("duplicate primary keys in upsert")
+        if torch.is_tensor(emb) and emb.dtype == torch.float16:
+            if tuple(emb.shape) != (n, self.dim):
+                raise ValueError(f"embeddings must be [{n}, {self.dim}]")
+            return emb
+        e = np.asarray(emb, dtype=np.float32) if not torch.is_tensor(emb) else emb
+        if tuple(e.shape) != (n, self.dim):
+            raise ValueError(f"embeddings must be [{n}, {self.dim}], got {tuple(e.shape)}")
+        return self.index.to_fp16(e, normalize=self.metric_type == "COSINE")
+
+    def _match_mask(self, expr: str) -> np.ndarray:
+        """bool [num_entities]: the rows `expr` matches, evaluated on the device."""
+        n = self.num_entities
+        if n == 0:
+            with self._filter_lock:   # still reject a bad expression
+                filter_expr.compile_expr(filter_expr.parse(expr), {f: [] for f in filter_expr.VARCHAR_FIELDS}, {})
+            return np.zeros(0, dtype=bool)
+        return filter_mask_bits(self.build_filter(expr), n)
+
+    def _pk_mask(self, keys) -> np.ndarray:
+        mask = np.zeros(self.num_entities, dtype=bool)
+        rows = [self._pk_row[k] for k in keys if k in self._pk_row]
+        mask[rows] = True
+        return mask
+
+    def _delete_mask(self, mask: np.ndarray) -> MutationResult:
+        """Drop the rows set in `mask` (bool [num_entities]) everywhere.  Caller holds the write lock."""
+        gone = np.flatnonzero(mask)
+        if gone.size == 0:
+            return MutationResult(delete_count=0)
+        ids = self.columns["id"]
+        pks = [ids[i] for i in gone.tolist()]
+        keep_mask = ~mask
+        keep = np.flatnonzero(keep_mask)
+        n_old = self.num_entities
+        self._compact_index(keep_mask, keep)
+        sel = keep_mask.tolist()
+        for f in SCALAR_FIELDS:
+            self.columns[f] = list(itertools.compress(self.columns[f], sel))
+        self._pk_row = dict(zip(self.columns["id"], range(keep.size)))
+        with self._filter_lock:
+            if self._dcols is not None:
+                if self._dcols.n == n_old:
+                    self._dcols.compact(keep)
+                else:   # not synced to the old rows: the next filtered call re-encodes from row 0
+                    self._dcols = None
+        return MutationResult(pks, delete_count=len(pks))
+
+    def _compact_index(self, keep_mask: np.ndarray, keep: np.ndarray) -> None:
+        self.index.compact(keep)
+
     # -- search --------------------------------------------------------------------
     def _prepare_queries(self, data):
         torch = _torch()
@@ -542,6 +767,10 @@ class CorpusStore:
         filter buffer (build_filter): the top-k of the passing rows, padded with -1 rows."""
         if limit < 1:
             raise ValueError("limit must be >= 1")
+        with self._rw.read():
+            return self._search_rows(data, limit, filt)
+
+    def _search_rows(self, data, limit: int, filt=None):
         q16 = self._prepare_queries(data)
         kw = {} if filt is None else {"filt": filt}
         if limit > _lib.RF_MAX_K:
@@ -555,6 +784,10 @@ class CorpusStore:
     def search(self, data, anns_field: str = "embedding", param: dict | None = None,
                limit: int = 3, expr=None, output_fields: Iterable[str] | None = None):
         """pymilvus-shaped search: one list of hits per query vector, best first."""
+        with self._rw.read():   # the rows handed back are marshalled below: no delete in between
+            return self._search(data, anns_field, param, limit, expr, output_fields)
+
+    def _search(self, data, anns_field, param, limit, expr, output_fields):
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         metric = (param or {}).get("metric_type", self.metric_type).upper()
@@ -587,6 +820,10 @@ class CorpusStore:
     #   vectors.f16   raw little-endian fp16, row-major [n, dim]   (np.memmap-able)
     #   columns.json  {"name", "dim", "metric_type", "n", "columns": {field: [...]}}
     def save(self, path: str, chunk_rows: int = 1 << 18) -> None:
+        with self._rw.read():
+            self._save(path, chunk_rows)
+
+    def _save(self, path: str, chunk_rows: int) -> None:
         import json
         import os
         os.makedirs(path, exist_ok=True)
@@ -659,6 +896,10 @@ class CorpusStore:
         """`query(expr="id in [...]")` fetch-by-PK (key order), `query(expr="", limit=n)` scan, and
         any other filter expression (rag_fin_amd.filter_expr): the matching rows in ascending
         row order."""
+        with self._rw.read():
+            return self._query(expr, limit, output_fields)
+
+    def _query(self, expr, limit, output_fields) -> list[dict]:
         fields = list(output_fields or ["id"])
         want_vec = "embedding" in fields
         fields = [f for f in fields if f != "embedding"]
