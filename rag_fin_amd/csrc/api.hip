@@ -19,6 +19,10 @@ static size_t carve(unsigned char* base, rf_workspace* ws) {
   uint32_t* cnt = (uint32_t*)take((size_t)RF_QWIDE * RF_CAND_SHARDS * sizeof(uint32_t));
   float* pmax = (float*)take((size_t)RF_QWIDE * RF_SAMPLE_WGS * sizeof(float));
   uint2* cand = (uint2*)take((size_t)RF_QWIDE * RF_CAND_SHARDS * RF_SHARD_CAP * sizeof(uint2));
+  uint4* fold = (uint4*)take((size_t)RF_FOLD_WAVES * RF_QCHUNK * sizeof(uint4));
+  unsigned long long* rmask = (unsigned long long*)take((size_t)RF_FOLD_WAVES * sizeof(unsigned long long));
+  uint32_t* rlist = (uint32_t*)take((size_t)RF_FOLD_BLOCKS * sizeof(uint32_t));
+  uint32_t* rcnt = (uint32_t*)take(sizeof(uint32_t));
   double* exs = (double*)take((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K * sizeof(double));
   int64_t* exr = (int64_t*)take((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K * sizeof(int64_t));
   if (ws) {
@@ -27,6 +31,10 @@ static size_t carve(unsigned char* base, rf_workspace* ws) {
     ws->cand_cnt = cnt;
     ws->pmax = pmax;
     ws->cand = cand;
+    ws->fold = fold;
+    ws->rmask = rmask;
+    ws->rlist = rlist;
+    ws->rcnt = rcnt;
     ws->ex_score = exs;
     ws->ex_row = exr;
   }
@@ -34,7 +42,8 @@ static size_t carve(unsigned char* base, rf_workspace* ws) {
 }
 
 #ifdef RF_EXPERIMENTS
-// Diagnostic hook: byte offset of a named workspace array ("pmax", "cand", "thr").
+// Diagnostic hook: byte offset of a named workspace array ("pmax", "cand", "thr", "cand_cnt",
+// "rmask", "rcnt").
 extern "C" size_t rf_debug_workspace_offset(const char* field) {
   unsigned char* base = (unsigned char*)(uintptr_t)4096;   // never dereferenced
   rf_workspace ws;
@@ -42,6 +51,9 @@ extern "C" size_t rf_debug_workspace_offset(const char* field) {
   if (field && !strcmp(field, "pmax")) return (size_t)((unsigned char*)ws.pmax - base);
   if (field && !strcmp(field, "cand")) return (size_t)((unsigned char*)ws.cand - base);
   if (field && !strcmp(field, "thr")) return (size_t)((unsigned char*)ws.thr - base);
+  if (field && !strcmp(field, "cand_cnt")) return (size_t)((unsigned char*)ws.cand_cnt - base);
+  if (field && !strcmp(field, "rmask")) return (size_t)((unsigned char*)ws.rmask - base);
+  if (field && !strcmp(field, "rcnt")) return (size_t)((unsigned char*)ws.rcnt - base);
   return (size_t)-1;
 }
 #endif
@@ -154,13 +166,14 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
       if (rc != RF_OK) return rc;
     } else {
       int P = 0;
+      rf_fold fold{};  // n_samp = 0 unless the sample pass keeps its lists
       if (ix->size > RF_SMALL_ROWS) {
-        rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st, filt);
+        rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st, filt, &fold);
         if (rc != RF_OK) return rc;
       }
-      rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st);
+      rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, &fold);
       if (rc != RF_OK) return rc;
-      rc = rf_launch_emit(ix, qc, nb, JB, ws, st, filt);
+      rc = rf_launch_emit(ix, qc, nb, JB, ws, st, filt, &fold);
       if (rc != RF_OK) return rc;
     }
     rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, scores_dev + (size_t)q0 * k,
@@ -192,13 +205,14 @@ extern "C" int rf_search_profile(const rf_index_t* ix, const void* q_dev, int B,
   const int nb = wide ? (B < RF_QWIDE ? B : RF_QWIDE) : (B < RF_QCHUNK ? B : RF_QCHUNK);
   const int JB = nb <= 32 ? 1 : 2;
   int P = 0;
+  rf_fold fold{};  // the chain rf_search runs: the 64-query sweep folds the sample into the emit
   RF_HIP(hipEventRecord(ev[0], st));
   if (ix->size > RF_SMALL_ROWS)
-    rc = wide ? rf_launch_wide_sample(ix, q_dev, nb, ws, &P, st) : rf_launch_sample(ix, q_dev, nb, JB, ws, &P, st);
+    rc = wide ? rf_launch_wide_sample(ix, q_dev, nb, ws, &P, st) : rf_launch_sample(ix, q_dev, nb, JB, ws, &P, st, nullptr, &fold);
   RF_HIP(hipEventRecord(ev[1], st));
-  if (rc == RF_OK) rc = rf_launch_threshold(ix, q_dev, nb, k, P, ws, st);
+  if (rc == RF_OK) rc = rf_launch_threshold(ix, q_dev, nb, k, P, ws, st, wide ? nullptr : &fold);
   RF_HIP(hipEventRecord(ev[2], st));
-  if (rc == RF_OK) rc = wide ? rf_launch_wide_emit(ix, q_dev, nb, ws, st) : rf_launch_emit(ix, q_dev, nb, JB, ws, st);
+  if (rc == RF_OK) rc = wide ? rf_launch_wide_emit(ix, q_dev, nb, ws, st) : rf_launch_emit(ix, q_dev, nb, JB, ws, st, nullptr, &fold);
   RF_HIP(hipEventRecord(ev[3], st));
   if (rc == RF_OK)
     rc = rf_launch_merge(ix, q_dev, nb, k, id_base, ws, scores_dev, ids_dev, exact_dev, flags_dev, st);

@@ -83,13 +83,52 @@ __device__ __forceinline__ bool ranks_before(double s1, int64_t r1, double s2, i
 // covers dim roundings of the fp32 accumulator at one ulp each).  The scan
 // keeps every row whose MFMA score is >= kth - 2*eps, which provably contains
 // every row of the exact top-k ("why the result is exact").
+//
+// Sample fold (fold != nullptr, scan.hip): then the wave also walks its query's kept lists, one
+// per sample wave.  A list whose second best score is below thr holds every row of its wave with
+// a score >= thr (at most its best): that row is appended here, with the same {row, score bits}
+// the emit would have appended.  Otherwise the query's bit is set in the sample wave's rescan
+// mask and nothing of that wave is appended; the first query to mark a wave lists the wave's
+// blocks for the emit sweep.  The counters start at what was appended (no atomics: the wave owns
+// its query's lists until the emit runs).  The lists are loaded before the k-th maximum is
+// selected: their HBM round trip runs under the extraction rounds.
+struct ThrFold {
+  const uint4* lists;         // nullptr: no fold (the counters start at zero)
+  unsigned long long* rmask;
+  uint32_t* rlist;
+  uint32_t* rcnt;
+  uint2* cand;
+  uint32_t cap;
+  uint32_t n_samp, bstride, W;
+  int force;                  // every list counts as incomplete (diagnostics)
+};
 __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q, int B, int dim,
                                                   int k, const float* __restrict__ pmax, int P,
                                                   const uint32_t* __restrict__ max_norm2,
                                                   float* __restrict__ thr, float* __restrict__ eps_out,
-                                                  uint32_t* __restrict__ cand_cnt) {
+                                                  uint32_t* __restrict__ cand_cnt, ThrFold fd) {
   const int qi = blockIdx.x;
   const int lane = threadIdx.x;
+  // kept lists per lane and chunk: the first chunk (1024 sample waves, all of a 4-wave sample
+  // pass) is in flight during the extraction rounds; an 8-wave pass has a second
+  constexpr int FI = 16;
+  const bool folding = fd.lists && qi < B;  // wave-uniform
+  uint32_t f_best[FI], f_row[FI], f_second[FI];
+  auto load_lists = [&](uint32_t base) {
+#pragma unroll
+    for (int i = 0; i < FI; ++i) {
+      const uint32_t sw = base + (uint32_t)(lane + 64 * i);
+      f_best[i] = f_second[i] = 0xFF800000u;  // -inf: nothing to append, complete
+      f_row[i] = 0u;
+      if (folding && sw < fd.W) {
+        const uint4 e = fd.lists[(size_t)qi * RF_FOLD_WAVES + sw];  // a query's lists are contiguous
+        f_best[i] = e.x;
+        f_row[i] = e.y;
+        f_second[i] = e.z;
+      }
+    }
+  };
+  load_lists(0u);
   float s = 0.f;
   if (qi < B)
     for (int d = lane; d < dim; d += 64) {
@@ -138,7 +177,42 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
     thr[qi] = t;
     eps_out[qi] = eps;
   }
-  if (lane < RF_CAND_SHARDS) cand_cnt[qi * RF_CAND_SHARDS + lane] = 0u;
+  uint32_t appended = 0u;  // wave-uniform; entry g goes to shard g % RF_CAND_SHARDS
+  if (folding) {
+    uint2* lists = fd.cand + (size_t)qi * RF_CAND_SHARDS * fd.cap;
+    for (uint32_t base = 0; base < fd.W; base += 64u * FI) {
+      if (base) load_lists(base);
+      uint32_t incomplete = 0u;  // bit i: the list of sample wave base + lane + 64 i
+#pragma unroll
+      for (int i = 0; i < FI; ++i) {
+        const uint32_t sw = base + (uint32_t)(lane + 64 * i);
+        const bool valid = sw < fd.W;
+        const bool complete = !fd.force && __builtin_bit_cast(float, f_second[i]) < t;
+        incomplete |= (valid && !complete) ? (1u << i) : 0u;
+        const bool app = valid && complete && __builtin_bit_cast(float, f_best[i]) >= t;
+        const unsigned long long m = __ballot(app);
+        if (app) {
+          const uint32_t g = appended + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+          const uint32_t slot = g / RF_CAND_SHARDS;
+          if (slot < fd.cap) lists[(size_t)(g % RF_CAND_SHARDS) * fd.cap + slot] = make_uint2(f_row[i], f_best[i]);
+        }
+        appended += (uint32_t)__popcll(m);
+      }
+      // rare: mark the query in the waves it cannot take from the lists
+      while (incomplete) {
+        const uint32_t sw = base + (uint32_t)lane + 64u * (uint32_t)(__ffs((int)incomplete) - 1);
+        incomplete &= incomplete - 1u;
+        const unsigned long long old = atomicOr(&fd.rmask[sw], 1ull << qi);
+        if (old == 0ull && sw < fd.n_samp) {
+          const uint32_t nb = (fd.n_samp - sw + fd.W - 1u) / fd.W;
+          const uint32_t at = atomicAdd(fd.rcnt, nb);
+          for (uint32_t j = 0; j < nb; ++j)
+            if (at + j < (uint32_t)RF_FOLD_BLOCKS) fd.rlist[at + j] = (sw + j * fd.W) * fd.bstride;
+        }
+      }
+    }
+  }
+  if (lane < RF_CAND_SHARDS) cand_cnt[qi * RF_CAND_SHARDS + lane] = (appended + RF_CAND_SHARDS - 1u - lane) / RF_CAND_SHARDS;
 }
 
 // ---- candidate merge + exact rescoring --------------------------------------------
@@ -177,7 +251,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
     uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
     int64_t* __restrict__ ids, double* __restrict__ exact, uint32_t* __restrict__ flags,
-    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows) {
+    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned long long* skeys = (unsigned long long*)lds;                       // [1024]
   unsigned long long* wtop = skeys + MERGE_RANK_MAX;                          // [4][RF_MAX_K]
@@ -384,7 +458,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   // leave the counters zero (every thread of this workgroup read them before the barriers
   // above); k_threshold zeroes them again at the start of every search, so a search never
   // depends on what an earlier one -- or an error return mid-pipeline -- left behind
-  if (tid < RF_CAND_SHARDS) cand_cnt_rw[qi * RF_CAND_SHARDS + tid] = 0u;
+  if (tid < RF_CAND_SHARDS && !keep_cnt) cand_cnt_rw[qi * RF_CAND_SHARDS + tid] = 0u;
 }
 // ---- exhaustive exact path ----------------------------------------------------------
 // Workgroup-level running top-k list (sorted, in LDS) updated 256 entries at a
@@ -587,10 +661,23 @@ __global__ void __launch_bounds__(EX_THREADS) k_merge_shards(
 
 // ---- host side --------------------------------------------------------------------------
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
-                        const rf_workspace& ws, hipStream_t st) {
+                        const rf_workspace& ws, hipStream_t st, const rf_fold* fold) {
+  ThrFold fd{};
+  if (fold && fold->n_samp > 0u && P > 0 && B <= RF_QCHUNK) {
+    fd.lists = ws.fold;
+    fd.rmask = ws.rmask;
+    fd.rlist = ws.rlist;
+    fd.rcnt = ws.rcnt;
+    fd.cand = ws.cand;
+    fd.cap = RF_SHARD_CAP;
+    fd.n_samp = fold->n_samp;
+    fd.bstride = fold->bstride;
+    fd.W = fold->W;
+    fd.force = rf_knob_fold_dbg & 1;
+  }
   // one wave per query slot of the sweep (64, or up to RF_QWIDE for a wide sweep)
   hipLaunchKernelGGL(k_threshold, dim3(B > RF_QCHUNK ? RF_QWIDE : RF_QCHUNK), dim3(64), 0, st, (const _Float16*)q, B, ix->dim,
-                     k, ws.pmax, P, ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt);
+                     k, ws.pmax, P, ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }
@@ -603,7 +690,7 @@ int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_
   RF_HIP(rf_ensure_lds(lds_attr, (const void*)k_merge, lds));
   hipLaunchKernelGGL(k_merge, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim,
                      ix->KS, ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP,
-                     ws.eps, scores, ids, exact, flags, ws.cand_cnt, (uint32_t)ix->size);
+                     ws.eps, scores, ids, exact, flags, ws.cand_cnt, (uint32_t)ix->size, (rf_knob_fold_dbg & 2) ? 1 : 0);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }

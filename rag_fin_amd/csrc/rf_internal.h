@@ -53,6 +53,8 @@ struct rf_index {
 RF_KNOB(rf_knob_ring24, 8)             // register-ring depth (fragments) of the dim-384 emit sweep: 6 | 8 | 12 | 24
 RF_KNOB(rf_knob_emit_wgs_per_cu, 0)    // emit grid = CUs x this (0 = default for the dim)
 RF_KNOB(rf_knob_sample_bpw, 2)         // sample blocks per wave
+RF_KNOB(rf_knob_sample_fold, 1)        // 64-query sweep: the emit skips the sampled blocks (k_threshold appends what the sample kept)
+RF_KNOB(rf_knob_fold_dbg, 0)           // sample fold diagnostics: 1 = every kept list counts as incomplete (all rescanned), 2 = k_merge leaves the candidate counters
 RF_KNOB(rf_knob_wide_sample_pairs, 4)  // wide sample pass: block pairs per workgroup, at most
 RF_KNOB(rf_knob_wide_dbg, 0)           // wide sweep diagnostic bits (clock stamps, cached-KiB ablation)
 RF_KNOB(rf_knob_wide_form, 0)          // wide sweep kernel: 0 = eight waves x 32 queries (k_scan_w16), 1 = four waves x 64 queries (k_scan_w64)
@@ -111,6 +113,10 @@ static inline hipError_t rf_ensure_lds(rf_lds_attr& a, const void* fn, size_t ld
 #define RF_SAMPLE_WGS 256
 // rescoring-set capacity per query
 #define RF_RESCORE_CAP 256
+// sample fold: waves of a sample pass (RF_SAMPLE_WGS workgroups of at most 8 waves) and the
+// most blocks it reads (at most 8 per wave: rf_knob_sample_bpw)
+#define RF_FOLD_WAVES (RF_SAMPLE_WGS * 8)
+#define RF_FOLD_BLOCKS (RF_FOLD_WAVES * 8)
 
 struct rf_workspace {
   float* thr;          // [64]
@@ -118,6 +124,11 @@ struct rf_workspace {
   uint32_t* cand_cnt;  // [64][RF_CAND_SHARDS]
   float* pmax;         // [64][RF_SAMPLE_WGS]
   uint2* cand;         // [64][RF_CAND_SHARDS][RF_SHARD_CAP]  {row, score bits}
+  // sample fold (scan.hip, k_threshold): what the sample pass saw, per sample wave
+  uint4* fold;         // [64 queries][RF_FOLD_WAVES] {best score bits, its row, second best score bits, 0}
+  unsigned long long* rmask;  // [RF_FOLD_WAVES] queries whose kept list of that wave is incomplete
+  uint32_t* rlist;     // [RF_FOLD_BLOCKS] sampled blocks the emit sweeps again (of waves with rmask != 0)
+  uint32_t* rcnt;      // [1] entries of rlist
   // exhaustive path
   double* ex_score;    // [RF_EX_LISTS][RF_MAX_K]
   int64_t* ex_row;     // [RF_EX_LISTS][RF_MAX_K]
@@ -149,11 +160,22 @@ struct rf_filter_view {
 size_t rf_filter_layout(int64_t n_rows, size_t* mask_off, size_t* blocks_off, size_t* tiles_off);
 rf_filter_view rf_filter_carve(const void* filter, int64_t n_rows);
 
+// Sample fold: the geometry of a sample pass that kept its lists (n_samp = 0: none kept; the
+// threshold appends nothing and the emit sweeps every block).  Sample wave s read blocks
+// (s + j W) * bstride for s + j W < n_samp.
+struct rf_fold {
+  uint32_t n_samp;   // sampled blocks
+  uint32_t bstride;  // block stride of the sample
+  uint32_t W;        // waves of the sample pass
+};
 // scan.hip (filt: nullptr = every row; otherwise the masked sweep over the filter's blocks)
+// fold: rf_launch_sample fills it (the fold is off for a filtered sweep and with the knob off);
+// rf_launch_threshold and rf_launch_emit take what it filled, nullptr = no fold
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                     int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr);
+                     int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr,
+                     rf_fold* fold = nullptr);
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st, const rf_filter_view* filt = nullptr);
+                   hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr);
 int rf_launch_debug_scores(const rf_index* ix, const void* q, int B, int64_t n, float* out,
                            hipStream_t st);
 int rf_scan_supported_dim(int dim);
@@ -164,7 +186,7 @@ int rf_launch_wide_sample(const rf_index* ix, const void* q, int B, const rf_wor
 int rf_launch_wide_emit(const rf_index* ix, const void* q, int B, const rf_workspace& ws, hipStream_t st);
 // merge.hip
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
-                        const rf_workspace& ws, hipStream_t st);
+                        const rf_workspace& ws, hipStream_t st, const rf_fold* fold = nullptr);
 int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                     const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                     uint32_t* flags, hipStream_t st);

@@ -23,6 +23,15 @@
 //   MODE_EMIT    every score >= threshold is appended to that query's
 //                candidate list (wave-level ballot compaction into LDS,
 //                flushed with one global atomic per entry).
+//
+// Sample fold (64-query sweep without a filter): the sample pass
+// (MODE_FOLD) also keeps, per lane, the best score of its query over the lane's rows
+// with that row, and the second best score.  k_threshold (merge.hip) appends the best
+// row wherever the second best is below the threshold -- then no other row of that lane
+// can be a candidate -- and otherwise marks the query in its sample wave's rescan mask.
+// The emit sweep then reads only the blocks the sample did not read, plus the blocks of
+// the marked sample waves, filtered to the marked queries: every corpus byte is read
+// once per batch instead of the sampled 1/16 twice.
 #include "rf_internal.h"
 #include <stdlib.h>
 #include <string.h>
@@ -30,10 +39,34 @@
 
 #include "scan_common.h"
 
+// MODE_FOLD: the best of the 16 scores of a lane with its row (the first on ties), and the second
+// best, folded into the lane's running (m1, r1, m2).  m1 is selected, never computed, so it is
+// the bit pattern the emit would append for row r1; a NaN is never selected (m1 is the maximum
+// of the other scores, as max16 is, and serves as the partition maximum pm).  fminf / fmaxf drop
+// a NaN: it can only raise m2, which makes a list incomplete, never wrongly complete.
+__device__ __forceinline__ void fold_top2(const f32x16& a, uint32_t rbase, float& m1, uint32_t& r1,
+                                          float& m2) {
+  float b1 = -INFINITY, b2 = -INFINITY;
+  uint32_t bi = acc_row(0, 0);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float x = a[i];
+    const bool c = x > b1;
+    b2 = fmaxf(b2, fminf(b1, x));
+    bi = c ? acc_row(i, 0) : bi;
+    b1 = c ? x : b1;
+  }
+  m2 = fmaxf(fmaxf(m2, b2), fminf(m1, b1));
+  const bool c = b1 > m1;
+  r1 = c ? rbase + bi : r1;
+  m1 = c ? b1 : m1;
+}
+
 template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false>
 __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
                                            const uint4* nxt, const u32x4* smemQ, int lane,
-                                           uint32_t row0, float (&th)[JB], float (&pm)[JB],
+                                           uint32_t row0, const float (&th)[JB], float (&pm)[JB],
+                                           float (&m1)[JB], uint32_t (&r1)[JB], float (&m2)[JB],
                                            EmitState& es, const ScanParams& p,
                                            uint32_t mword = 0u) {
   static_assert(KS % R == 0, "ring must divide the block");
@@ -62,7 +95,7 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
     }
   }
 
-  if (MODE == MODE_SAMPLE) {
+  if (MODE != MODE_EMIT) {
     if (FILTER) {
       // rows the filter rejects (and rows past the end: their bits are zero) leave the maximum
       if (mword != 0xFFFFFFFFu) {  // wave-uniform
@@ -81,8 +114,13 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
         for (int i = 0; i < 16; ++i)
           if (row0 + acc_row(i, h) >= p.n_rows) acc[jb][i] = -INFINITY;
     }
+    if (MODE == MODE_FOLD) {
 #pragma unroll
-    for (int jb = 0; jb < JB; ++jb) pm[jb] = fmaxf(pm[jb], max16(acc[jb]));
+      for (int jb = 0; jb < JB; ++jb) fold_top2(acc[jb], row0 + 4u * (uint32_t)(lane >> 5), m1[jb], r1[jb], m2[jb]);
+    } else {
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) pm[jb] = fmaxf(pm[jb], max16(acc[jb]));
+    }
   } else {
     bool hit = false;
 #pragma unroll
@@ -105,9 +143,15 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
 
   float th[JB];
   float pm[JB];
+  float m1[JB];     // MODE_FOLD: best score (the partition maximum), its row, second best score
+  uint32_t r1[JB];
+  float m2[JB];
 #pragma unroll
   for (int jb = 0; jb < JB; ++jb) {
     pm[jb] = -INFINITY;
+    m1[jb] = -INFINITY;
+    r1[jb] = 0xFFFFFFFFu;
+    m2[jb] = -INFINITY;
     th[jb] = (MODE == MODE_EMIT) ? p.thr[jb * 32 + (lane & 31)] : 0.f;
   }
   EmitState es;
@@ -142,12 +186,34 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
       p.bstride = 1u;
     }
   }
-  const uint32_t cnt = (p.n_work > gw) ? (p.n_work - gw + W - 1) / W : 0u;
+  // Emit sweep with a sample fold (s_n > 0): item i < M is the i-th block the sample did not read
+  // (L of them inside the sample's stride groups, then the tail past the last group), item M + j
+  // is rlist[j].  Dense items keep every wave busy: skipping the sampled blocks inside the plain
+  // round-robin would idle the waves whose blocks are the sample's (W is a multiple of s_bs).
+  // With s_n = 0 item i is block i.
+  const bool folded = !FILTER && MODE == MODE_EMIT && p.s_n > 0u;  // wave-uniform
+  const uint32_t M = folded ? p.n_work - p.s_n : p.n_work;
+  const uint32_t L = folded ? p.s_n * (p.s_bs - 1u) : 0u;
+  uint32_t n_res = 0u;
+  if (folded) {  // (consumed after the query staging)
+    n_res = *p.rcnt;
+    n_res = n_res < p.s_n ? n_res : p.s_n;  // rlist holds each sampled block at most once
+  }
+  auto block_of = [&](uint32_t i) -> uint32_t {
+    if (i < L) {
+      const uint32_t g = i / (p.s_bs - 1u);
+      return g * p.s_bs + 1u + (i - g * (p.s_bs - 1u));
+    }
+    if (i < M) return i + (folded ? p.s_n : 0u);
+    const uint32_t r = p.rlist[i - M];
+    return r < p.n_work ? r : 0u;  // (k_threshold lists sampled blocks only: never past the corpus)
+  };
 
   u32x4 ring[R];
-  if (cnt > 0) {
+  if (FILTER ? gw < p.n_work : gw < M) {
     const uint4* src;
     if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[gw * p.bstride] * (KS * 64) + lane;
+    else if constexpr (MODE == MODE_EMIT) src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
     else src = p.corpus + (size_t)gw * p.bstride * (KS * 64) + lane;
 #pragma unroll
     for (int s = 0; s < R; ++s) ring[s] = ld_frag(src + s * 64);
@@ -167,6 +233,13 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   }
 
   __syncthreads();
+  const uint32_t n_items = M + n_res;
+  const uint32_t cnt = (n_items > gw) ? (n_items - gw + W - 1) / W : 0u;
+  if (!FILTER && cnt > 0 && gw >= M) {  // the wave's first item is a rescan (a corpus of few blocks)
+    const uint4* src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
+#pragma unroll
+    for (int s = 0; s < R; ++s) ring[s] = ld_frag(src + s * 64);
+  }
   if (cnt > 0) {
 
     uint32_t w = gw;
@@ -179,25 +252,55 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
         const uint32_t mw = p.mask[b];
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
         const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, false, true>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, es, p, mw);
+        block_step<KS, R, JB, MODE, false, true>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw);
         b = bn;
       }
       {
         const uint32_t mw = p.mask[b];
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, true, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, es, p, mw);
+        block_step<KS, R, JB, MODE, true, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw);
+      }
+    } else if constexpr (MODE == MODE_EMIT) {
+      // a rescanned block (item >= M) appends only for the queries its sample wave marked:
+      // the others' rows of it came from k_threshold (an MFMA score is finite, never >= +inf)
+      auto item_th = [&](uint32_t i, uint32_t b, float (&te)[JB]) {
+        if (i < M) {
+#pragma unroll
+          for (int jb = 0; jb < JB; ++jb) te[jb] = th[jb];
+        } else {
+          const unsigned long long qm = p.rmask[(b / p.s_bs) % p.s_W];
+#pragma unroll
+          for (int jb = 0; jb < JB; ++jb)
+            te[jb] = ((qm >> (jb * 32 + (lane & 31))) & 1ull) ? th[jb] : INFINITY;
+        }
+      };
+      uint32_t b = block_of(w);
+      for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
+        const uint32_t bn = block_of(w + W);
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
+        float te[JB];
+        item_th(w, b, te);
+        block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, te, pm, m1, r1, m2, es, p);
+        b = bn;
+      }
+      {
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        float te[JB];
+        item_th(w, b, te);
+        block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, te, pm, m1, r1, m2, es, p);
       }
     } else {
       for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
         const uint32_t b = w * p.bstride;
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
         const uint4* nxt = p.corpus + (size_t)(b + W * p.bstride) * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, es, p);
+        block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p);
       }
       {
         const uint32_t b = w * p.bstride;
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, es, p);
+        block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p);
       }
     }
   }
@@ -205,6 +308,29 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   if (MODE == MODE_EMIT) {
     if (es.cnt > 0) emit_flush(es, p, lane);
   } else {
+    if (MODE == MODE_FOLD) {
+      // this wave's kept list per query: the two lane halves' lists merged into the best score
+      // with its row and the second best score over all the wave's rows of that query (a wave
+      // without blocks writes -inf: complete, nothing to append); its rescan mask and the rescan
+      // count start at zero for k_threshold
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) {
+        const float o1 = __shfl_xor(m1[jb], 32);
+        const uint32_t orow = (uint32_t)__shfl_xor((int)r1[jb], 32);
+        const float o2 = __shfl_xor(m2[jb], 32);
+        if (lane < 32) {
+          const bool mine = !(o1 > m1[jb]);
+          const float s2 = fmaxf(fmaxf(m2[jb], o2), fminf(m1[jb], o1));
+          p.fold[(size_t)(jb * 32 + lane) * RF_FOLD_WAVES + gw] =
+              make_uint4(__builtin_bit_cast(uint32_t, mine ? m1[jb] : o1), mine ? r1[jb] : orow,
+                         __builtin_bit_cast(uint32_t, s2), 0u);
+        }
+      }
+      if (lane == 0) p.rmask[gw] = 0ull;
+      if (gw == 0 && lane == 0) *p.rcnt = 0u;
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) pm[jb] = m1[jb];
+    }
     // workgroup partition maximum per query: max over waves and lane halves
     float* red = (float*)tail;  // [WAVES*2][JB*32]
 #pragma unroll
@@ -279,7 +405,7 @@ static int launch_scan(const PT& p, int grid, hipStream_t st) {
 // ---- tuning knobs: compile-time constants in the shipped library (rf_internal.h); the
 // experiments build (tools/ only) makes them process-wide ints behind rf_set_tuning -----------
 #ifdef RF_EXPERIMENTS
-int rf_knob_ring24 = 8, rf_knob_emit_wgs_per_cu = 0, rf_knob_sample_bpw = 2;
+int rf_knob_ring24 = 8, rf_knob_emit_wgs_per_cu = 0, rf_knob_sample_bpw = 2, rf_knob_sample_fold = 1, rf_knob_fold_dbg = 0;
 int rf_knob_wide_sample_pairs = 4, rf_knob_wide_dbg = 0, rf_knob_wide_ne = 0, rf_knob_wide_form = 0;
 int rf_knob_linear_dma = 1, rf_knob_linear_small = 1, rf_knob_k384_ntb = 4, rf_knob_ffn2_ntb = 4;
 int rf_knob_gemm_tile = 3, rf_knob_encode_graph = 1, rf_knob_linear_dbg = 0, rf_knob_debug_epi = 1, rf_knob_att_heads = 1, rf_knob_gemm_tile_dma = 0, rf_knob_one_query = 1, rf_knob_post_block = 1, rf_knob_post_dbg = 0, rf_knob_post_qkv = 1;
@@ -294,7 +420,8 @@ extern "C" int rf_set_tuning(const char* key, int value) {
   ++rf_tuning_generation;   // cached encode graphs were captured under the old settings
   struct K { const char* name; int* var; int lo, hi; };
   const K keys[] = {{"ring24", &rf_knob_ring24, 6, 24}, {"emit_wgs_per_cu", &rf_knob_emit_wgs_per_cu, 0, 4},
-                    {"sample_bpw", &rf_knob_sample_bpw, 1, 8}, {"wide_sample_pairs", &rf_knob_wide_sample_pairs, 1, 8},
+                    {"sample_bpw", &rf_knob_sample_bpw, 1, 8}, {"sample_fold", &rf_knob_sample_fold, 0, 1}, {"fold_dbg", &rf_knob_fold_dbg, 0, 3},
+                    {"wide_sample_pairs", &rf_knob_wide_sample_pairs, 1, 8},
                     {"wide_dbg", &rf_knob_wide_dbg, 0, 127}, {"wide_ne", &rf_knob_wide_ne, 0, 112}, {"wide_form", &rf_knob_wide_form, 0, 1}, {"linear_dma", &rf_knob_linear_dma, 0, 3},
                     {"linear_small", &rf_knob_linear_small, 0, 1}, {"k384_ntb", &rf_knob_k384_ntb, 2, 4},
                     {"ffn2_ntb", &rf_knob_ffn2_ntb, 2, 4}, {"gemm_tile", &rf_knob_gemm_tile, 0, 15}, {"encode_graph", &rf_knob_encode_graph, 0, 1},
@@ -373,7 +500,7 @@ static inline int waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
 static inline int wgs_per_cu(int KS) { return KS >= 48 ? 1 : 2; }
 
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                     int* P_out, hipStream_t st, const rf_filter_view* filt) {
+                     int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = waves_per_wg(KS);
@@ -403,6 +530,7 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
   p.pmax = ws.pmax;
   p.P = grid;
   *P_out = grid;
+  if (fold) *fold = rf_fold{0u, 1u, 1u};
   if (filt) {
     // the grid (= partitions) is sized from the whole corpus; the kernel derives the sampled
     // count and stride from the filter's device count of pass blocks, within the same bounds
@@ -416,11 +544,19 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
     f.work_hi = hi;
     return dispatch_scan<MODE_SAMPLE>(KS, JB, f, grid, grid, st);
   }
+  if (fold && rf_knob_sample_fold && B <= RF_QCHUNK && n_work <= (uint32_t)RF_FOLD_BLOCKS &&
+      (uint32_t)grid * WAVES <= (uint32_t)RF_FOLD_WAVES) {
+    p.fold = ws.fold;
+    p.rmask = ws.rmask;
+    p.rcnt = ws.rcnt;
+    *fold = rf_fold{n_work, bstride, (uint32_t)grid * WAVES};
+    return dispatch_scan<MODE_FOLD>(KS, JB, p, grid, grid, st);
+  }
   return dispatch_scan<MODE_SAMPLE>(KS, JB, p, grid, grid, st);
 }
 
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st, const rf_filter_view* filt) {
+                   hipStream_t st, const rf_filter_view* filt, const rf_fold* fold) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = waves_per_wg(KS);
@@ -440,6 +576,16 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
   p.cand_cnt = ws.cand_cnt;
   p.cand = ws.cand;
   p.cap = RF_SHARD_CAP;
+  if (fold && fold->n_samp > 0u && !filt) {
+    // the sweep skips the sampled blocks (scan_body): the grid and the ring depth stay those of
+    // the whole corpus
+    p.rmask = ws.rmask;
+    p.rlist = ws.rlist;
+    p.rcnt = ws.rcnt;
+    p.s_n = fold->n_samp;
+    p.s_bs = fold->bstride;
+    p.s_W = fold->W;
+  }
   if (filt) {
     // grid and ring depth as for the whole corpus; waves past the device count exit
     ScanParamsF f{};

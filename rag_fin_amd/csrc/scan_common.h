@@ -6,7 +6,9 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-enum { MODE_SAMPLE = 0, MODE_EMIT = 1 };
+// MODE_FOLD: the sample pass that also keeps, per lane, its query's best score with its row and
+// its second best score (scan.hip, "sample fold")
+enum { MODE_SAMPLE = 0, MODE_EMIT = 1, MODE_FOLD = 2 };
 
 #define SCAP 64  // per-wave LDS staging entries (>= 64: one ballot round can add 64)
 
@@ -23,6 +25,14 @@ struct ScanParams {
   uint32_t cap;
   float* pmax;           // [64][P]
   int P;
+  // sample fold (rf_fold; the 64-query sweep without a filter).  MODE_FOLD writes `fold` and
+  // zeroes rmask / rcnt; MODE_EMIT with s_n > 0 sweeps the n_work - s_n blocks the sample did not
+  // read, then the rcnt blocks of rlist, each for the queries of its sample wave's rmask only
+  uint4* fold;                   // [64][RF_FOLD_WAVES]
+  unsigned long long* rmask;     // [sample waves]
+  uint32_t* rlist;
+  uint32_t* rcnt;
+  uint32_t s_n, s_bs, s_W;       // sampled blocks, their stride, sample waves
 };
 
 // The masked sweep (filtered search): work item w is block blocks[w * bstride] of the filter's
