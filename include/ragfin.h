@@ -20,7 +20,8 @@
  *   - threading: an rf_index_t / rf_encoder_t may be used by any number of host threads at
  *     once as long as each concurrent call has its OWN workspace (and normally its own
  *     stream); the handles hold no per-call state.  rf_index_add_f16 / rf_index_reset /
- *     rf_index_compact must not run concurrently with a search on the same index.  A process may hold indexes and
+ *     rf_index_compact / rf_index_attach_sq8 / rf_index_detach_sq8 must not run concurrently with a
+ *     search on the same index.  A process may hold indexes and
  *     encoders on several devices; the calling thread's current HIP device must be the
  *     handle's device (hipSetDevice / torch.cuda.device).
  */
@@ -292,6 +293,46 @@ int rf_search_sharded(const rf_index_t* ix, rf_comm_t* comm, const void* q_dev, 
 int rf_debug_scores(const rf_index_t* ix, const void* q_dev, int B, int64_t n,
                     float* out_dev, void* stream);
 
+/* ---- SQ8 index: Collection.create_index("embedding", {"index_type": "SQ8", ...}) -------------------
+ * Reference: "chunking_storing (1).py":29 picks the index type.  SQ8 keeps an int8 copy of the corpus
+ * (the "shadow") next to the fp16 tiles and sweeps it with v_mfma_i32_32x32x32_i8: dim + 8 bytes per
+ * row instead of 2 dim, plus the fp16 sample pass.  The answer
+ * stays EXACT: the int8 scores only nominate candidates, each row tested against its own error bound,
+ * and the merge rescores them in fp64 from the fp16 tiles.  Ids, ranks, scores and
+ * the flag contract are those of rf_search.
+ *   rf_sq8_storage_bytes   bytes of the shadow for `capacity_rows` rows (0 unless dim % 32 == 0 and the
+ *                          dim has a scan kernel); a SEPARATE caller-owned allocation, 16-byte aligned
+ *   rf_index_attach_sq8    quantize every existing row into the shadow (stream-ordered); from then on
+ *                          rf_index_add_f16 / rf_index_compact / rf_index_reset keep it current, and
+ *                          it is byte-identical to a fresh attach over the same rows.  Other dims:
+ *                          RF_ERR_UNSUPPORTED.  Like rf_index_add_f16: never concurrent with a search.
+ *   rf_index_detach_sq8    forget the shadow (the caller frees it after the stream has drained)
+ *   rf_search_sq8          rf_search's arguments and outputs; 64-query sweeps for any B.  A corpus of
+ *                          <= 8192 rows (every row a candidate) runs the FLAT path.  A flagged query
+ *                          is re-run through rf_search and, only if that flags too, rf_search_exhaustive.
+ *                          A query whose bound is too loose for the int8 sweep (most sample partitions
+ *                          clear its threshold) is given up before the sweep and flagged.
+ *                          workspace_bytes >= rf_search_sq8_workspace_bytes (> rf_search_workspace_bytes)
+ *   rf_search_sq8_profile  the first sweep with HIP events: stage_ms_host (host) receives {query
+ *                          quantization, sample, threshold, int8 emit, merge} in ms; SYNCHRONISES
+ *   rf_debug_scores_sq8    test hook: a~ fp32 [B, n] of the first n rows, delta_dev (nullable) fp32 [B]
+ *                          the bound delta_q >= |a - a~| of every row
+ *   rf_index_get_rows_sq8  test hook: the un-tiled int8 rows [n, dim], s_r fp32 [n], e_r fp32 [n] */
+size_t rf_sq8_storage_bytes(int dim, int64_t capacity_rows);
+int rf_index_attach_sq8(rf_index_t* ix, void* storage_dev, size_t storage_bytes, void* stream);
+int rf_index_detach_sq8(rf_index_t* ix);
+size_t rf_search_sq8_workspace_bytes(const rf_index_t* ix);
+int rf_search_sq8(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                  float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                  void* workspace_dev, size_t workspace_bytes, void* stream);
+int rf_search_sq8_profile(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                          float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream, float* stage_ms_host);
+int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int B, int64_t n, float* out_dev,
+                        float* delta_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+int rf_index_get_rows_sq8(const rf_index_t* ix, const int64_t* rows_dev, int64_t n, void* out_dev,
+                          float* scales_dev, float* err_dev, void* stream);
+
 #ifdef RF_EXPERIMENTS
 /* ---- experiments build only (python -m rag_fin_amd.build --experiments ->
  * libragfin_hip_exp.so; used by tools/, never by the product or the tests) -------------------
@@ -301,7 +342,8 @@ int rf_debug_scores(const rf_index_t* ix, const void* q_dev, int B, int64_t n,
  * "sample_bpw" (1..8), "wide_sample_pairs" (1..8), "wide_dbg"; encoder: "linear_dma" (0..3),
  * "linear_small", "encode_graph" (0|1), "k384_ntb", "ffn2_ntb" (2|4), "linear_dbg", "debug_epi". */
 int rf_set_tuning(const char* key, int value);
-/* byte offset of a named array ("pmax", "cand", "thr") inside a search workspace */
+/* byte offset of a named array ("pmax", "cand", "thr", "eps", "cand_cnt", "rmask", "rcnt") inside a
+ * search workspace (the same in an SQ8 workspace, whose query area follows the FLAT arrays) */
 size_t rf_debug_workspace_offset(const char* field);
 /* a device buffer (>= 64 KiB, or NULL to switch off) that instrumented kernels fill with
  * clock stamps (encoder k_linear_dma: 8 floats per wave) */

@@ -108,6 +108,17 @@ SIGNATURES = {
     "rf_tokenize_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
     "rf_utf8_offsets": (c_int, [c_char_p, c_int64, c_void_p, c_int, c_void_p]),
     "rf_debug_scores": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "rf_sq8_storage_bytes": (c_size_t, [c_int, c_int64]),
+    "rf_index_attach_sq8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_index_detach_sq8": (c_int, [c_void_p]),
+    "rf_search_sq8_workspace_bytes": (c_size_t, [c_void_p]),
+    "rf_search_sq8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_search_sq8_profile": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
+    "rf_debug_scores_sq8": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "rf_index_get_rows_sq8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rf_encoder_storage_bytes": (c_size_t, [POINTER(EncoderConfig)]),
     "rf_encoder_create": (c_int, [POINTER(c_void_p), POINTER(EncoderConfig),
                                   POINTER(EncoderWeights), c_void_p, c_size_t, c_int, c_void_p]),

@@ -42,7 +42,7 @@ static size_t carve(unsigned char* base, rf_workspace* ws) {
 }
 
 #ifdef RF_EXPERIMENTS
-// Diagnostic hook: byte offset of a named workspace array ("pmax", "cand", "thr", "cand_cnt",
+// Diagnostic hook: byte offset of a named workspace array ("pmax", "cand", "thr", "eps", "cand_cnt",
 // "rmask", "rcnt").
 extern "C" size_t rf_debug_workspace_offset(const char* field) {
   unsigned char* base = (unsigned char*)(uintptr_t)4096;   // never dereferenced
@@ -51,6 +51,7 @@ extern "C" size_t rf_debug_workspace_offset(const char* field) {
   if (field && !strcmp(field, "pmax")) return (size_t)((unsigned char*)ws.pmax - base);
   if (field && !strcmp(field, "cand")) return (size_t)((unsigned char*)ws.cand - base);
   if (field && !strcmp(field, "thr")) return (size_t)((unsigned char*)ws.thr - base);
+  if (field && !strcmp(field, "eps")) return (size_t)((unsigned char*)ws.eps - base);
   if (field && !strcmp(field, "cand_cnt")) return (size_t)((unsigned char*)ws.cand_cnt - base);
   if (field && !strcmp(field, "rmask")) return (size_t)((unsigned char*)ws.rmask - base);
   if (field && !strcmp(field, "rcnt")) return (size_t)((unsigned char*)ws.rcnt - base);
@@ -181,6 +182,139 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
                          flags_dev ? flags_dev + q0 : nullptr, st);
     if (rc != RF_OK) return rc;
     q0 += nb;
+  }
+  return RF_OK;
+}
+
+// ---- SQ8 (include/ragfin.h, "SQ8 index") ------------------------------------------------------------
+// The SQ8 workspace is the FLAT one followed by the per-sweep query quantization (q^ for 64 queries
+// of up to 1024 dims, then t_q, n_q, f_q).
+static size_t carve_sq8(unsigned char* base, rf_workspace* ws, rf_sq8_ws* sw) {
+  size_t off = carve(base, ws);
+  auto take = [&](size_t bytes) {
+    unsigned char* p = base ? base + off : nullptr;
+    off = align_up(off + bytes, 256);
+    return p;
+  };
+  int8_t* q8 = (int8_t*)take((size_t)RF_QCHUNK * 1024);
+  float* tq = (float*)take(RF_QCHUNK * sizeof(float));
+  float* nq = (float*)take(RF_QCHUNK * sizeof(float));
+  float* fq = (float*)take(RF_QCHUNK * sizeof(float));
+  if (sw) *sw = rf_sq8_ws{q8, tq, nq, fq};
+  return off;
+}
+
+extern "C" size_t rf_search_sq8_workspace_bytes(const rf_index_t* ix) {
+  (void)ix;
+  return carve_sq8(nullptr, nullptr, nullptr);
+}
+
+static int check_sq8(const char* fn, const rf_index_t* ix, size_t ws_bytes) {
+  if (!ix->sq8_tiles) {
+    rf_set_error("%s: no SQ8 shadow attached (rf_index_attach_sq8)", fn);
+    return RF_ERR_INVALID;
+  }
+  if (ws_bytes < rf_search_sq8_workspace_bytes(ix)) {
+    rf_set_error("%s: workspace %zu B < required %zu B", fn, ws_bytes, rf_search_sq8_workspace_bytes(ix));
+    return RF_ERR_CAPACITY;
+  }
+  return RF_OK;
+}
+
+// One 64-query sweep: quantize the queries, the fp16 sample pass (no fold), the threshold with its
+// SQ8 argument, the int8 emit sweep, the unchanged merge.  stage_ev: nullable, 6 events around the
+// five stages.
+static int sq8_sweep(const rf_index_t* ix, const _Float16* qc, int nb, int k, int64_t id_base, float* scores,
+                     int64_t* ids, double* exact, uint32_t* flags, const rf_workspace& ws, const rf_sq8_ws& sw,
+                     hipStream_t st, hipEvent_t* ev) {
+  const int JB = nb <= 32 ? 1 : 2;
+  int P = 0;
+  if (ev) RF_HIP(hipEventRecord(ev[0], st));
+  int rc = rf_launch_sq8_queries(ix, qc, nb, sw, st);
+  if (ev) RF_HIP(hipEventRecord(ev[1], st));
+  if (rc == RF_OK) rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st);
+  if (ev) RF_HIP(hipEventRecord(ev[2], st));
+  if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, nullptr, &sw);
+  if (ev) RF_HIP(hipEventRecord(ev[3], st));
+  if (rc == RF_OK) rc = rf_launch_sq8_emit(ix, nb, JB, ws, sw, st);
+  if (ev) RF_HIP(hipEventRecord(ev[4], st));
+  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, scores, ids, exact, flags, st);
+  if (ev) RF_HIP(hipEventRecord(ev[5], st));
+  return rc;
+}
+
+extern "C" int rf_search_sq8(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                             float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream) {
+  int rc = check_search_args("rf_search_sq8", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc != RF_OK) return rc;
+  rc = check_sq8("rf_search_sq8", ix, workspace_bytes);
+  if (rc != RF_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // small corpora: every row is a candidate on the FLAT path anyway (no sample pass to gain from)
+  if (ix->size <= RF_SMALL_ROWS)
+    return search_enqueue(ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, workspace_dev, st);
+  rf_workspace ws;
+  rf_sq8_ws sw;
+  carve_sq8((unsigned char*)workspace_dev, &ws, &sw);
+  for (int q0 = 0; q0 < B; q0 += RF_QCHUNK) {
+    const int nb = (B - q0) < RF_QCHUNK ? (B - q0) : RF_QCHUNK;
+    rc = sq8_sweep(ix, (const _Float16*)q_dev + (size_t)q0 * ix->dim, nb, k, id_base, scores_dev + (size_t)q0 * k,
+                   ids_dev + (size_t)q0 * k, exact_dev ? exact_dev + (size_t)q0 * k : nullptr,
+                   flags_dev ? flags_dev + q0 : nullptr, ws, sw, st, nullptr);
+    if (rc != RF_OK) return rc;
+  }
+  return RF_OK;
+}
+
+extern "C" int rf_search_sq8_profile(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                                     float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                                     void* workspace_dev, size_t workspace_bytes, void* stream,
+                                     float* stage_ms_host) {
+  int rc = check_search_args("rf_search_sq8_profile", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc != RF_OK) return rc;
+  rc = check_sq8("rf_search_sq8_profile", ix, workspace_bytes);
+  if (rc != RF_OK) return rc;
+  if (!stage_ms_host || ix->size <= RF_SMALL_ROWS) {
+    rf_set_error("rf_search_sq8_profile: null stage buffer or a corpus of <= %d rows", RF_SMALL_ROWS);
+    return RF_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  rf_workspace ws;
+  rf_sq8_ws sw;
+  carve_sq8((unsigned char*)workspace_dev, &ws, &sw);
+  hipEvent_t ev[6];
+  for (int i = 0; i < 6; ++i) RF_HIP(hipEventCreate(&ev[i]));
+  const int nb = B < RF_QCHUNK ? B : RF_QCHUNK;
+  rc = sq8_sweep(ix, (const _Float16*)q_dev, nb, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, ws, sw, st,
+                 ev);
+  if (rc == RF_OK) {
+    RF_HIP(hipEventSynchronize(ev[5]));
+    for (int i = 0; i < 5; ++i) RF_HIP(hipEventElapsedTime(&stage_ms_host[i], ev[i], ev[i + 1]));
+  }
+  for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]);
+  return rc;
+}
+
+extern "C" int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int B, int64_t n, float* out_dev,
+                                   float* delta_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (!ix || !q_dev || !out_dev || !workspace_dev || B <= 0 || n <= 0 || n > ix->size) {
+    rf_set_error("rf_debug_scores_sq8: bad argument");
+    return RF_ERR_INVALID;
+  }
+  int rc = check_sq8("rf_debug_scores_sq8", ix, workspace_bytes);
+  if (rc != RF_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  rf_sq8_ws sw;
+  carve_sq8((unsigned char*)workspace_dev, nullptr, &sw);
+  for (int q0 = 0; q0 < B; q0 += RF_QCHUNK) {
+    const int nb = (B - q0) < RF_QCHUNK ? (B - q0) : RF_QCHUNK;
+    rc = rf_launch_sq8_queries(ix, (const _Float16*)q_dev + (size_t)q0 * ix->dim, nb, sw, st);
+    if (rc == RF_OK)
+      rc = rf_launch_sq8_debug(ix, nb, n, sw, out_dev + (size_t)q0 * n, delta_dev ? delta_dev + q0 : nullptr, st);
+    if (rc != RF_OK) return rc;
   }
   return RF_OK;
 }

@@ -223,6 +223,7 @@ extern "C" int rf_index_reset(rf_index_t* ix, void* stream) {
   }
   ix->size = 0;
   RF_HIP(hipMemsetAsync(ix->max_norm2, 0, 256, (hipStream_t)stream));
+  if (ix->sq8_max) RF_HIP(hipMemsetAsync(ix->sq8_max, 0, 256, (hipStream_t)stream));
   return RF_OK;
 }
 
@@ -256,6 +257,11 @@ extern "C" int rf_index_add_f16(rf_index_t* ix, const void* rows_dev, int64_t n,
   hipLaunchKernelGGL(k_max_norm2, dim3(grid_for(n * 64, 256)), dim3(256), 0, st,
                      (const _Float16*)rows_dev, n, ix->dim, ix->max_norm2);
   RF_HIP(hipGetLastError());
+  if (ix->sq8_tiles) {  // keep the SQ8 shadow current: quantize the new rows from the tiles
+    if (ix->size == 0) RF_HIP(hipMemsetAsync(ix->sq8_max, 0, 256, st));
+    const int rc = rf_sq8_quantize_rows(ix, ix->size, ix->size + n, st);
+    if (rc != RF_OK) return rc;
+  }
   ix->size += n;
   return RF_OK;
 }
@@ -288,6 +294,7 @@ extern "C" int rf_index_compact(rf_index_t* ix, const int64_t* keep_rows_dev, in
   if (n_keep == 0) {  // what rf_index_reset does; keep_rows / scratch are not read
     ix->size = 0;
     RF_HIP(hipMemsetAsync(ix->max_norm2, 0, 256, st));
+    if (ix->sq8_max) RF_HIP(hipMemsetAsync(ix->sq8_max, 0, 256, st));
     return RF_OK;
   }
   if (!keep_rows_dev || !scratch_dev) {
@@ -320,6 +327,11 @@ extern "C" int rf_index_compact(rf_index_t* ix, const int64_t* keep_rows_dev, in
     hipLaunchKernelGGL(k_zero_rows, dim3(grid_for(pad * KS * 2, 256)), dim3(256), 0, st, ix->tiles,
                        n_keep, pad, KS);
   RF_HIP(hipGetLastError());
+  if (ix->sq8_tiles) {  // the SQ8 shadow: re-quantized from the compacted tiles (a pure function of each row)
+    RF_HIP(hipMemsetAsync(ix->sq8_max, 0, 256, st));
+    const int rc = rf_sq8_quantize_rows(ix, 0, n_keep, st);
+    if (rc != RF_OK) return rc;
+  }
   ix->size = n_keep;
   return RF_OK;
 }

@@ -11,6 +11,7 @@
 // The MFMA scan only nominates candidates; every returned score comes from the
 // fp64 chain, so ids and ranks are bit-reproducible on the CPU.
 #include "rf_internal.h"
+#include "sq8.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -102,11 +103,19 @@ struct ThrFold {
   uint32_t n_samp, bstride, W;
   int force;                  // every list counts as incomplete (diagnostics)
 };
+// SQ8 (rf_search_sq8; mx == nullptr: FLAT).  The k-th partition maximum m_k of the fp16 sample
+// then becomes the int8 emit threshold thr_q = m_k - eps - f_q N' - slack, and eps_out receives
+// delta_q = n_q E + f_q N' + slack, the bound the merge widens its rescoring set by.
+struct ThrSq8 {
+  const float* nq;
+  const float* fq;
+  const uint32_t* mx;         // {N', E} bits
+};
 __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q, int B, int dim,
                                                   int k, const float* __restrict__ pmax, int P,
                                                   const uint32_t* __restrict__ max_norm2,
                                                   float* __restrict__ thr, float* __restrict__ eps_out,
-                                                  uint32_t* __restrict__ cand_cnt, ThrFold fd) {
+                                                  uint32_t* __restrict__ cand_cnt, ThrFold fd, ThrSq8 sq) {
   const int qi = blockIdx.x;
   const int lane = threadIdx.x;
   // kept lists per lane and chunk: the first chunk (1024 sample waves, all of a 4-wave sample
@@ -140,6 +149,7 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
   const float eps = 1.25f * (float)dim * 1.1920929e-7f * sqrtf(s) * sqrtf(cmax2);
 
   float t;
+  bool give_up = false;  // SQ8 only: the query is left to FLAT (see below)
   if (qi >= B) {
     t = INFINITY;
   } else if (P <= 0) {
@@ -172,10 +182,30 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
       }
     }
     t = (kth == -INFINITY) ? -INFINITY : kth - 2.f * eps;
+    if (sq.mx && kth != -INFINITY) {
+      t = rf_sq8_thr(kth, eps, sq.nq[qi], sq.fq[qi], __builtin_bit_cast(float, sq.mx[0]),
+                     __builtin_bit_cast(float, sq.mx[1]));
+      // Give-up rule: when more than 3/4 of the sample partitions left after the k largest hold a
+      // row that clears thr_q, the int8 sweep would emit a large share of the corpus (a bound too
+      // loose for this query, e.g. a dominant channel) and overflow anyway.  The query then emits
+      // nothing and its shard-0 counter is set past the capacity, so the merge flags it and the
+      // caller answers it through FLAT: only the speed depends on this rule, never the answer.
+      // Applied with at least 64 partitions left (k near P says nothing about the density).
+      const uint32_t rest = (uint32_t)(P > k ? P - k : 0);
+      uint32_t above = 0u;
+#pragma unroll
+      for (int i = 0; i < RF_SAMPLE_WGS / 64; ++i) above += (uint32_t)__popcll(__ballot(v[i] >= t));
+      if (rest >= 64u && above * 4u > rest * 3u) {
+        give_up = true;
+        t = INFINITY;
+      }
+    }
   }
   if (lane == 0) {
     thr[qi] = t;
-    eps_out[qi] = eps;
+    eps_out[qi] = (sq.mx && qi < B) ? rf_sq8_delta(sq.nq[qi], sq.fq[qi], __builtin_bit_cast(float, sq.mx[0]),
+                                                   __builtin_bit_cast(float, sq.mx[1]))
+                                    : eps;
   }
   uint32_t appended = 0u;  // wave-uniform; entry g goes to shard g % RF_CAND_SHARDS
   if (folding) {
@@ -212,7 +242,9 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
       }
     }
   }
-  if (lane < RF_CAND_SHARDS) cand_cnt[qi * RF_CAND_SHARDS + lane] = (appended + RF_CAND_SHARDS - 1u - lane) / RF_CAND_SHARDS;
+  if (lane < RF_CAND_SHARDS)
+    cand_cnt[qi * RF_CAND_SHARDS + lane] = (give_up && lane == 0) ? (uint32_t)RF_SHARD_CAP + 1u
+                                                                 : (appended + RF_CAND_SHARDS - 1u - lane) / RF_CAND_SHARDS;
 }
 
 // ---- candidate merge + exact rescoring --------------------------------------------
@@ -661,8 +693,15 @@ __global__ void __launch_bounds__(EX_THREADS) k_merge_shards(
 
 // ---- host side --------------------------------------------------------------------------
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
-                        const rf_workspace& ws, hipStream_t st, const rf_fold* fold) {
+                        const rf_workspace& ws, hipStream_t st, const rf_fold* fold,
+                        const rf_sq8_ws* sq8) {
   ThrFold fd{};
+  ThrSq8 sq{};
+  if (sq8) {
+    sq.nq = sq8->nq;
+    sq.fq = sq8->fq;
+    sq.mx = ix->sq8_max;
+  }
   if (fold && fold->n_samp > 0u && P > 0 && B <= RF_QCHUNK) {
     fd.lists = ws.fold;
     fd.rmask = ws.rmask;
@@ -677,7 +716,7 @@ int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
   }
   // one wave per query slot of the sweep (64, or up to RF_QWIDE for a wide sweep)
   hipLaunchKernelGGL(k_threshold, dim3(B > RF_QCHUNK ? RF_QWIDE : RF_QCHUNK), dim3(64), 0, st, (const _Float16*)q, B, ix->dim,
-                     k, ws.pmax, P, ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd);
+                     k, ws.pmax, P, ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd, sq);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }

@@ -34,6 +34,11 @@ struct rf_index {
   uint32_t* max_norm2; // device: bits of max squared row norm (float >= 0)
   size_t storage_bytes;
   int num_cus;         // compute units of `device`
+  // SQ8 shadow (sq8.hip): a caller-owned int8 copy of the rows, nullptr while none is attached
+  uint4* sq8_tiles;    // device: capacity_blocks * KS8 * 64 uint4 (KS8 = dim / 32)
+  float* sq8_scale;    // device: [capacity_blocks][32] s_r, in accumulator order (rf_sq8_slot)
+  float* sq8_err;      // device: [capacity_blocks][32] e_r, same order
+  uint32_t* sq8_max;   // device: {bits of N' = max ||s_r c^_r||, bits of E = max e_r}
 };
 // An index is immutable during searches (no mutable host state: any number of threads may
 // search one index concurrently, each with its own workspace and stream); rf_index_add_f16 /
@@ -184,9 +189,25 @@ int rf_wide_supported(const rf_index* ix);
 int rf_launch_wide_sample(const rf_index* ix, const void* q, int B, const rf_workspace& ws, int* P_out,
                           hipStream_t st);
 int rf_launch_wide_emit(const rf_index* ix, const void* q, int B, const rf_workspace& ws, hipStream_t st);
+// sq8.hip: the SQ8 shadow (include/ragfin.h, "SQ8 index").  Per-query quantization of a sweep,
+// written by rf_launch_sq8_queries into the workspace area after the FLAT carve.
+struct rf_sq8_ws {
+  int8_t* q8;          // [64][dim] q^
+  float* tq;           // [64] query scale t_q
+  float* nq;           // [64] ||q||, rounded up
+  float* fq;           // [64] ||q - t_q q^||, rounded up
+};
+// quantize rows [row0, 32 * ceil(row1 / 32)) of the fp16 tiles into the shadow (pad rows give 0)
+int rf_sq8_quantize_rows(rf_index* ix, int64_t row0, int64_t row1, hipStream_t st);
+int rf_launch_sq8_queries(const rf_index* ix, const void* q, int B, const rf_sq8_ws& sw, hipStream_t st);
+int rf_launch_sq8_emit(const rf_index* ix, int B, int JB, const rf_workspace& ws, const rf_sq8_ws& sw,
+                       hipStream_t st);
+int rf_launch_sq8_debug(const rf_index* ix, int B, int64_t n, const rf_sq8_ws& sw, float* out, float* delta,
+                        hipStream_t st);
 // merge.hip
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
-                        const rf_workspace& ws, hipStream_t st, const rf_fold* fold = nullptr);
+                        const rf_workspace& ws, hipStream_t st, const rf_fold* fold = nullptr,
+                        const rf_sq8_ws* sq8 = nullptr);
 int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                     const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                     uint32_t* flags, hipStream_t st);

@@ -128,6 +128,18 @@ class ShardedCorpusStore(CorpusStore):
             self._id_map = torch.empty(0, dtype=torch.int64, device=self.index.device)
             self._searcher = None
 
+    # -- index type ---------------------------------------------------------------------------------
+    def create_index(self, field_name: str, index_params: dict | None = None, **kwargs) -> None:
+        """FLAT and IVF_FLAT (served as FLAT) are accepted; SQ8 is not implemented for the sharded
+        search (NotImplementedError).  Local bookkeeping only: every rank makes the same call."""
+        itype, metric = self._check_index_params(field_name, dict(index_params or {}))
+        if itype == "SQ8":
+            raise NotImplementedError("SQ8 is not supported by ShardedCorpusStore (single-GPU CorpusStore only)")
+        with self._rw.write():
+            self.index_type = "FLAT"
+            self._index_params = {"index_type": itype, "metric_type": metric,
+                                  "params": dict((index_params or {}).get("params") or {})}
+
     # -- mutation (COLLECTIVE) ----------------------------------------------------------------------
     # Every rank holds the full columns, so every rank computes the same global keep mask without
     # talking to the others; each compacts its own shard (its local rows whose global id survives)

@@ -80,10 +80,13 @@ class GpuIndex:
                                                 self.device.index))
             self.handle = handle
             ws = self.lib.rf_search_workspace_bytes(self.handle)
-            self.workspace = torch.zeros(ws, dtype=torch.uint8, device=self.device)
+            # one workspace serves both paths: the SQ8 one is the FLAT one plus its query area
+            self.sq8_workspace_bytes = self.lib.rf_search_sq8_workspace_bytes(self.handle)
+            self.workspace = torch.zeros(max(ws, self.sq8_workspace_bytes), dtype=torch.uint8, device=self.device)
             self.workspace_bytes = ws
         self._lock = threading.Lock()
         self._host_bufs = {}
+        self._sq8_storage = None   # the SQ8 shadow (enable_sq8), a separate allocation
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -164,21 +167,101 @@ class GpuIndex:
                                                       _lib.current_stream_ptr()))
         return out
 
+    # -- SQ8 shadow (include/ragfin.h, "SQ8 index") ----------------------------------------
+    @property
+    def sq8(self) -> bool:
+        """True while an int8 shadow is attached (rf_search_sq8 can run)."""
+        return self._sq8_storage is not None
+
+    def enable_sq8(self) -> None:
+        """Attach an int8 shadow (dim + 8 bytes per row of capacity) and quantize every row; adds,
+        compactions and resets keep it current from then on.  Needs dim % 32 == 0."""
+        torch = _torch()
+        if self._sq8_storage is not None:
+            return
+        nbytes = self.lib.rf_sq8_storage_bytes(self.dim, self.capacity)
+        if nbytes == 0:
+            raise _lib.RagfinError(-2, f"SQ8 needs dim % 32 == 0 (dim {self.dim})")
+        with self._lock, torch.cuda.device(self.device):
+            storage = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rf_index_attach_sq8(self.handle, c_void_p(storage.data_ptr()), nbytes,
+                                                    _lib.current_stream_ptr()))
+            self._sq8_storage = storage
+
+    def disable_sq8(self) -> None:
+        torch = _torch()
+        if self._sq8_storage is None:
+            return
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_index_detach_sq8(self.handle))
+            # freed in stream order: a search already enqueued on this stream still reads it
+            self._sq8_storage = None
+
+    def get_rows_sq8(self, row_ids):
+        """rf_index_get_rows_sq8: (int8 [n, dim], s_r fp32 [n], e_r fp32 [n]) on the device."""
+        torch = _torch()
+        ids = torch.as_tensor(row_ids, dtype=torch.int64).to(self.device).contiguous()
+        n = ids.numel()
+        out = torch.empty((n, self.dim), dtype=torch.int8, device=self.device)
+        sc = torch.empty((n,), dtype=torch.float32, device=self.device)
+        er = torch.empty((n,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_index_get_rows_sq8(self.handle, c_void_p(ids.data_ptr()), n,
+                                                      c_void_p(out.data_ptr()), c_void_p(sc.data_ptr()),
+                                                      c_void_p(er.data_ptr()), _lib.current_stream_ptr()))
+        return out, sc, er
+
+    def debug_scores_sq8(self, q16, n: int | None = None):
+        """rf_debug_scores_sq8: (a~ fp32 [B, n], delta_q fp32 [B])."""
+        torch = _torch()
+        n = self.size if n is None else n
+        q16 = q16.to(self.device).contiguous()
+        B = q16.shape[0]
+        out = torch.empty((B, n), dtype=torch.float32, device=self.device)
+        delta = torch.empty((B,), dtype=torch.float32, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_debug_scores_sq8(self.handle, c_void_p(q16.data_ptr()), B, n,
+                                                    c_void_p(out.data_ptr()), c_void_p(delta.data_ptr()),
+                                                    c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
+                                                    _lib.current_stream_ptr()))
+        return out, delta
+
+    def search_sq8_profile(self, q16, k: int):
+        """rf_search_sq8_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
+        torch = _torch()
+        q16 = q16.to(self.device).contiguous()
+        B = min(q16.shape[0], _lib.RF_QCHUNK)
+        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ms = (ctypes.c_float * 5)()
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_search_sq8_profile(
+                self.handle, c_void_p(q16.data_ptr()), B, k, 0, c_void_p(scores.data_ptr()),
+                c_void_p(ids.data_ptr()), None, c_void_p(flags.data_ptr()),
+                c_void_p(self.workspace.data_ptr()), self.workspace.numel(), _lib.current_stream_ptr(), ms))
+        return {"quantize": ms[0], "sample": ms[1], "threshold": ms[2], "emit": ms[3], "merge": ms[4]}
+
     # -- search --------------------------------------------------------------
     def new_workspace(self):
         """An extra search workspace: one per batch in flight when several streams
-        search the same (immutable) index concurrently."""
+        search the same (immutable) index concurrently.  Large enough for SQ8 too."""
         torch = _torch()
-        return torch.zeros(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+        return torch.zeros(max(self.workspace_bytes, self.sq8_workspace_bytes), dtype=torch.uint8,
+                           device=self.device)
 
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None, filt=None):
+                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
         hipStream_t of this device); no host sync.  Returns
         (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
         filt: a filter buffer built for this index (CorpusStore.build_filter / rf_filter_eval):
-        rf_search_filtered, the same outputs over the passing rows only."""
+        rf_search_filtered, the same outputs over the passing rows only.
+        sq8: rf_search_sq8 (needs enable_sq8; not with filt).  A workspace passed in must hold
+        sq8_workspace_bytes (new_workspace does)."""
         torch = _torch()
+        if sq8 and filt is not None:
+            raise ValueError("SQ8 search has no filtered form")
         if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
             raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
         if not q16.is_contiguous() or q16.device != self.device:
@@ -195,9 +278,12 @@ class GpuIndex:
                 c_void_p(ids.data_ptr()), c_void_p(exact.data_ptr()) if exact is not None else None,
                 c_void_p(flags.data_ptr()),
                 c_void_p((workspace if workspace is not None else self.workspace).data_ptr()),
-                self.workspace_bytes, stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
+                self.sq8_workspace_bytes if sq8 else self.workspace_bytes,
+                stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
         with torch.cuda.device(self.device):
-            if filt is None:
+            if sq8:
+                _lib.check(self.lib.rf_search_sq8(self.handle, *args))
+            elif filt is None:
                 _lib.check(self.lib.rf_search(self.handle, *args))
             else:
                 _lib.check(self.lib.rf_search_filtered(self.handle, c_void_p(filt.data_ptr()), *args))
@@ -298,14 +384,24 @@ class GpuIndex:
         out = (torch.cat(scores, 1)[:, :k].contiguous(), torch.cat(ids, 1)[:, :k].contiguous())
         return out + (torch.cat(exacts, 1)[:, :k].contiguous(),) if want_exact else out
 
-    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
+    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False):
         """rf_search, then re-run any query the fused path could not prove exact
         (flags != 0) through the exhaustive fp64 kernel.  Serialised: the index
-        workspace is shared (SURVEY.md 8b threading row).  filt: over the passing rows."""
+        workspace is shared (SURVEY.md 8b threading row).  filt: over the passing rows.
+        sq8: rf_search_sq8 first; a query it flags is re-run through FLAT rf_search, and only one
+        that flags there too goes to the exhaustive kernel ("fallback")."""
         torch = _torch()
         with self._lock:
-            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt)
+            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8)
             bad = torch.nonzero(flags != 0).flatten()
+            if sq8 and bad.numel() > 0:
+                qb = q16.to(self.device)[bad].contiguous()
+                s2, i2, e2, f2 = self.search_raw(qb, k, id_base, want_exact)
+                scores[bad] = s2
+                ids[bad] = i2
+                if exact is not None:
+                    exact[bad] = e2
+                bad = bad[f2 != 0]
             if bad.numel() > 0:
                 qb = q16.to(self.device)[bad].contiguous()
                 s2, i2, e2 = self.search_exhaustive(qb, k, id_base, want_exact, filt=filt)
@@ -317,10 +413,11 @@ class GpuIndex:
 
     ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
 
-    def search_host(self, q16, k: int, filt=None):
+    def search_host(self, q16, k: int, filt=None, sq8: bool = False):
         """search() whose results land on the host with ONE synchronisation: scores, ids and
         flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
-        ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows."""
+        ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows.
+        sq8: rf_search_sq8, with search()'s two-step fallback for flagged queries."""
         torch = _torch()
         with self._lock:
             B = q16.shape[0]
@@ -334,19 +431,26 @@ class GpuIndex:
                 # query-sized results: the merge kernel stores straight into the pinned host buffers
                 # (host-coherent memory, mapped at the same address on the device) -- no copy commands,
                 # only the synchronisation
-                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]), filt=filt)
+                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]), filt=filt, sq8=sq8)
             else:
-                scores, ids, _, flags = self.search_raw(q16, k, filt=filt)
+                scores, ids, _, flags = self.search_raw(q16, k, filt=filt, sq8=sq8)
                 bufs[0].copy_(scores, non_blocking=True)
                 bufs[1].copy_(ids, non_blocking=True)
                 bufs[2].copy_(flags, non_blocking=True)
             torch.cuda.current_stream(self.device).synchronize()
             if bool(bufs[2].any()):
                 bad = torch.nonzero(bufs[2] != 0).flatten()
-                qb = q16.to(self.device)[bad.to(self.device)].contiguous()
-                s2, i2, _ = self.search_exhaustive(qb, k, filt=filt)
-                bufs[0][bad] = s2.cpu()
-                bufs[1][bad] = i2.cpu()
+                if sq8:   # flagged by SQ8: FLAT first, the exhaustive kernel only for what FLAT flags
+                    qb = q16.to(self.device)[bad.to(self.device)].contiguous()
+                    s2, i2, _, f2 = self.search_raw(qb, k)
+                    bufs[0][bad] = s2.cpu()
+                    bufs[1][bad] = i2.cpu()
+                    bad = bad[(f2 != 0).cpu()]
+                if bad.numel() > 0:
+                    qb = q16.to(self.device)[bad.to(self.device)].contiguous()
+                    s2, i2, _ = self.search_exhaustive(qb, k, filt=filt)
+                    bufs[0][bad] = s2.cpu()
+                    bufs[1][bad] = i2.cpu()
             # private copies, taken while the lock is still held: the pinned buffers are shared by every caller with
             # this (B, k) and the next search's merge kernel stores straight into them
             return bufs[0].numpy().copy(), bufs[1].numpy().copy()
@@ -579,6 +683,8 @@ class CorpusStore:
         # numbers and then reads the host columns at those rows (search_large over several pages):
         # a delete in between would pin another row's entity on a hit.
         self._rw = _RWLock()
+        self.index_type = "FLAT"            # create_index: "FLAT" (IVF_FLAT is served as FLAT) or "SQ8"
+        self._index_params = None           # what create_index was given (None: no create_index call)
 
     # -- pymilvus-shaped lifecycle ---------------------------------------------
     def flush(self) -> None:
@@ -611,7 +717,57 @@ class CorpusStore:
         step = 1 << 18
         for s in range(0, n, step):
             new.add(old.get_rows(np.arange(s, min(n, s + step), dtype=np.int64)))
+        if getattr(old, "sq8", False):
+            new.enable_sq8()   # re-attach: quantizes the copied rows
         self.index = new
+
+    # -- index type: Collection.create_index / drop_index / has_index --------------------------
+    INDEX_TYPES = ("FLAT", "IVF_FLAT", "SQ8")
+
+    def create_index(self, field_name: str, index_params: dict | None = None, **kwargs) -> None:
+        """pymilvus-shaped create_index ("chunking_storing (1).py":29).  index_type "FLAT" (the
+        default), "IVF_FLAT" (served as FLAT: exact, `params` such as nlist are ignored) or "SQ8"
+        (an int8 shadow of the vectors: fewer bytes per search, same exact answers; dim % 32 == 0).
+        Any other type, a metric_type other than the collection's or a field other than
+        "embedding" raises ValueError."""
+        params = dict(index_params or {})
+        itype, metric = self._check_index_params(field_name, params)
+        with self._rw.write():
+            if itype == "SQ8":
+                self.index.enable_sq8()
+            elif getattr(self.index, "sq8", False):
+                self.index.disable_sq8()
+            self.index_type = "SQ8" if itype == "SQ8" else "FLAT"
+            self._index_params = {"index_type": itype, "metric_type": metric, "params": dict(params.get("params") or {})}
+
+    def _check_index_params(self, field_name, params):
+        if field_name != "embedding":
+            raise ValueError(f"create_index: unknown vector field {field_name!r} (only 'embedding')")
+        itype = str(params.get("index_type", "FLAT")).upper()
+        if itype not in self.INDEX_TYPES:
+            raise ValueError(f"create_index: index_type {itype!r} not supported (one of {', '.join(self.INDEX_TYPES)})")
+        metric = str(params.get("metric_type", self.metric_type)).upper()
+        if metric != self.metric_type:
+            raise ValueError(f"create_index: collection was built for {self.metric_type}, index asked for {metric}")
+        p = params.get("params")
+        if p is not None and not isinstance(p, dict):
+            raise ValueError("create_index: params must be a dict")
+        return itype, metric
+
+    def drop_index(self, **kwargs) -> None:
+        """Back to FLAT (the shadow of SQ8 is freed)."""
+        with self._rw.write():
+            if getattr(self.index, "sq8", False):
+                self.index.disable_sq8()
+            self.index_type = "FLAT"
+            self._index_params = None
+
+    def has_index(self, **kwargs) -> bool:
+        return self._index_params is not None
+
+    def _use_sq8(self, B: int, limit: int) -> bool:
+        # the routing rule (INTEGRATION §2): unfiltered, limit <= RF_MAX_K, B <= one 64-query sweep
+        return self.index_type == "SQ8" and limit <= _lib.RF_MAX_K and B <= _lib.RF_QCHUNK
 
     # -- ingest ------------------------------------------------------------------
     def add(self, ids: Sequence, texts: Sequence[str], embeddings, periods: Sequence[str],
@@ -777,6 +933,8 @@ class CorpusStore:
             scores, rows = self.index.search_large(q16, limit, **kw)   # paged, exhaustive beyond 64
             kk = min(limit, self.num_entities)
             return scores[:, :kk].cpu().numpy(), rows[:, :kk].cpu().numpy()
+        if filt is None and self._use_sq8(int(q16.shape[0]), limit):
+            kw["sq8"] = True
         scores, rows = self.index.search_host(q16, limit, **kw)   # one synchronisation for the whole download
         kk = min(limit, self.num_entities)
         return scores[:, :kk], rows[:, :kk]
@@ -836,6 +994,8 @@ class CorpusStore:
         os.replace(tmp, os.path.join(path, "vectors.f16"))
         meta = {"format": "ragfin-corpus-v1", "name": self.name, "dim": self.dim,
                 "metric_type": self.metric_type, "n": n, "columns": self.columns}
+        if self.index_type != "FLAT":   # FLAT directories stay exactly as before
+            meta["index_type"] = self.index_type
         tmp = os.path.join(path, "columns.json.tmp")
         with open(tmp, "w", encoding="utf-8") as f:
             json.dump(meta, f, ensure_ascii=False)
@@ -870,6 +1030,9 @@ class CorpusStore:
             raise ValueError(f"{path}: column lengths do not match n={n}")
         st.columns = {f: list(cols[f]) for f in SCALAR_FIELDS}
         st._pk_row = {pk: i for i, pk in enumerate(st.columns["id"])}
+        itype = meta.get("index_type", "FLAT")   # a missing key means FLAT
+        if itype != "FLAT":
+            st.create_index("embedding", {"index_type": itype, "metric_type": st.metric_type})
         return st
 
     # -- filters -------------------------------------------------------------------------
