@@ -5,65 +5,78 @@
 #include <stdlib.h>
 #include <string.h>
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-static size_t carve(unsigned char* base, rf_workspace* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    unsigned char* p = base ? base + off : nullptr;
-    off = align_up(off + bytes, 256);
+// ---- workspace layout ---------------------------------------------------------------------------
+// Arrays carved off a caller's buffer in order, each 256-byte aligned (base == nullptr: sizes only).
+struct rf_arena {
+  unsigned char* base;
+  size_t off;
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off = (off + count * sizeof(T) + 255) / 256 * 256;
     return p;
-  };
-  float* thr = (float*)take(RF_QWIDE * sizeof(float));
-  float* eps = (float*)take(RF_QWIDE * sizeof(float));
-  uint32_t* cnt = (uint32_t*)take((size_t)RF_QWIDE * RF_CAND_SHARDS * sizeof(uint32_t));
-  float* pmax = (float*)take((size_t)RF_QWIDE * RF_SAMPLE_WGS * sizeof(float));
-  uint2* cand = (uint2*)take((size_t)RF_QWIDE * RF_CAND_SHARDS * RF_SHARD_CAP * sizeof(uint2));
-  uint4* fold = (uint4*)take((size_t)RF_FOLD_WAVES * RF_QCHUNK * sizeof(uint4));
-  unsigned long long* rmask = (unsigned long long*)take((size_t)RF_FOLD_WAVES * sizeof(unsigned long long));
-  uint32_t* rlist = (uint32_t*)take((size_t)RF_FOLD_BLOCKS * sizeof(uint32_t));
-  uint32_t* rcnt = (uint32_t*)take(sizeof(uint32_t));
-  double* exs = (double*)take((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K * sizeof(double));
-  int64_t* exr = (int64_t*)take((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K * sizeof(int64_t));
-  if (ws) {
-    ws->thr = thr;
-    ws->eps = eps;
-    ws->cand_cnt = cnt;
-    ws->pmax = pmax;
-    ws->cand = cand;
-    ws->fold = fold;
-    ws->rmask = rmask;
-    ws->rlist = rlist;
-    ws->rcnt = rcnt;
-    ws->ex_score = exs;
-    ws->ex_row = exr;
   }
-  return off;
+};
+
+static rf_workspace carve(rf_arena& a) {
+  rf_workspace ws;
+  ws.thr = a.take<float>(RF_QWIDE);
+  ws.eps = a.take<float>(RF_QWIDE);
+  ws.cand_cnt = a.take<uint32_t>((size_t)RF_QWIDE * RF_CAND_SHARDS);
+  ws.pmax = a.take<float>((size_t)RF_QWIDE * RF_SAMPLE_WGS);
+  ws.cand = a.take<uint2>((size_t)RF_QWIDE * RF_CAND_SHARDS * RF_SHARD_CAP);
+  ws.fold = a.take<uint4>((size_t)RF_FOLD_WAVES * RF_QCHUNK);
+  ws.rmask = a.take<unsigned long long>(RF_FOLD_WAVES);
+  ws.rlist = a.take<uint32_t>(RF_FOLD_BLOCKS);
+  ws.rcnt = a.take<uint32_t>(1);
+  ws.ex_score = a.take<double>((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K);
+  ws.ex_row = a.take<int64_t>((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K);
+  return ws;
+}
+
+// The SQ8 workspace is the FLAT one followed by the per-sweep query quantization (q^ for 64 queries
+// of up to 1024 dims, then t_q, n_q, f_q).
+static rf_sq8_ws carve_sq8(rf_arena& a, rf_workspace* ws) {
+  const rf_workspace flat = carve(a);
+  if (ws) *ws = flat;
+  rf_sq8_ws sw;
+  sw.q8 = a.take<int8_t>((size_t)RF_QCHUNK * 1024);
+  sw.tq = a.take<float>(RF_QCHUNK);
+  sw.nq = a.take<float>(RF_QCHUNK);
+  sw.fq = a.take<float>(RF_QCHUNK);
+  return sw;
 }
 
 #ifdef RF_EXPERIMENTS
 // Diagnostic hook: byte offset of a named workspace array ("pmax", "cand", "thr", "eps", "cand_cnt",
 // "rmask", "rcnt").
 extern "C" size_t rf_debug_workspace_offset(const char* field) {
-  unsigned char* base = (unsigned char*)(uintptr_t)4096;   // never dereferenced
-  rf_workspace ws;
-  carve(base, &ws);
-  if (field && !strcmp(field, "pmax")) return (size_t)((unsigned char*)ws.pmax - base);
-  if (field && !strcmp(field, "cand")) return (size_t)((unsigned char*)ws.cand - base);
-  if (field && !strcmp(field, "thr")) return (size_t)((unsigned char*)ws.thr - base);
-  if (field && !strcmp(field, "eps")) return (size_t)((unsigned char*)ws.eps - base);
-  if (field && !strcmp(field, "cand_cnt")) return (size_t)((unsigned char*)ws.cand_cnt - base);
-  if (field && !strcmp(field, "rmask")) return (size_t)((unsigned char*)ws.rmask - base);
-  if (field && !strcmp(field, "rcnt")) return (size_t)((unsigned char*)ws.rcnt - base);
+  rf_arena a{(unsigned char*)(uintptr_t)4096, 0};   // never dereferenced
+  const rf_workspace ws = carve(a);
+  const struct { const char* name; const void* at; } fields[] = {
+      {"pmax", ws.pmax}, {"cand", ws.cand},   {"thr", ws.thr},  {"eps", ws.eps},
+      {"cand_cnt", ws.cand_cnt}, {"rmask", ws.rmask}, {"rcnt", ws.rcnt}};
+  for (const auto& f : fields)
+    if (field && !strcmp(field, f.name)) return (size_t)((const unsigned char*)f.at - a.base);
   return (size_t)-1;
 }
 #endif
 
 extern "C" size_t rf_search_workspace_bytes(const rf_index_t* ix) {
   (void)ix;
-  return carve(nullptr, nullptr);
+  rf_arena a{nullptr, 0};
+  carve(a);
+  return a.off;
 }
 
+extern "C" size_t rf_search_sq8_workspace_bytes(const rf_index_t* ix) {
+  (void)ix;
+  rf_arena a{nullptr, 0};
+  carve_sq8(a, nullptr);
+  return a.off;
+}
+
+// ---- argument checks ----------------------------------------------------------------------------
 static int check_search_args(const char* fn, const rf_index_t* ix, const void* q, int B, int k,
                              const void* scores, const void* ids, const void* ws, size_t ws_bytes) {
   if (!ix || !q || !scores || !ids || !ws) {
@@ -90,125 +103,6 @@ static int check_search_args(const char* fn, const rf_index_t* ix, const void* q
   return RF_OK;
 }
 
-static void fill_empty(int B, int k, float* scores, int64_t* ids, double* exact, uint32_t* flags,
-                       hipStream_t st);
-
-__global__ void k_fill_empty(int n, int B, float* scores, int64_t* ids, double* exact,
-                             uint32_t* flags) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    scores[i] = -INFINITY;
-    ids[i] = -1;
-    if (exact) exact[i] = -INFINITY;
-  }
-  if (flags && i < B) flags[i] = 0u;
-}
-
-static void fill_empty(int B, int k, float* scores, int64_t* ids, double* exact, uint32_t* flags,
-                       hipStream_t st) {
-  const int n = B * k;
-  hipLaunchKernelGGL(k_fill_empty, dim3((n + 255) / 256), dim3(256), 0, st, n, B, scores, ids,
-                     exact, flags);
-}
-
-static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, float* scores_dev,
-                          int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
-                          hipStream_t st, const rf_filter_view* filt = nullptr);
-
-// More than one 64-query sweep left and dim 384: one wide sweep of up to 256 queries.
-// Small corpora -- every row a candidate -- stay on the 64-query kernel (its inline flushes take
-// any hit density, the wide kernel's bounded staging would flag every query), and so do large k
-// (the k-th of ~64 partition maxima is a weak threshold) and k-dense searches of mid-sized
-// corpora (expected hits per wave and phase ~ 2^15 k / N against room for 96).
-static bool take_wide(const rf_index_t* ix, int left, int k) {
-  return rf_wide_supported(ix) && left > RF_QCHUNK && ix->size > RF_SMALL_ROWS && k <= 16 &&
-         ix->size >= (int64_t)k * 1024;
-}
-
-extern "C" int rf_search(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
-                         float* scores_dev, int64_t* ids_dev, double* exact_dev,
-                         uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes,
-                         void* stream) {
-  int rc = check_search_args("rf_search", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
-                             workspace_bytes);
-  if (rc != RF_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  return search_enqueue(ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, workspace_dev, st);
-}
-
-// filt: the masked sweep of filtered search (never the wide sweep: B > 64 runs as 64-query sweeps)
-static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, float* scores_dev,
-                          int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
-                          hipStream_t st, const rf_filter_view* filt) {
-  int rc = RF_OK;
-  if (ix->size == 0) {
-    fill_empty(B, k, scores_dev, ids_dev, exact_dev, flags_dev, st);
-    RF_HIP(hipGetLastError());
-    return RF_OK;
-  }
-  rf_workspace ws;
-  carve((unsigned char*)workspace_dev, &ws);
-  const int dim = ix->dim;
-  for (int q0 = 0; q0 < B;) {
-    const int left = B - q0;
-    const bool wide = !filt && take_wide(ix, left, k);
-    const int nb = wide ? (left < RF_QWIDE ? left : RF_QWIDE) : (left < RF_QCHUNK ? left : RF_QCHUNK);
-    const int JB = nb <= 32 ? 1 : 2;
-    const _Float16* qc = (const _Float16*)q_dev + (size_t)q0 * dim;
-    if (wide) {
-      int P = 0;
-      if (ix->size > RF_SMALL_ROWS) {
-        rc = rf_launch_wide_sample(ix, qc, nb, ws, &P, st);
-        if (rc != RF_OK) return rc;
-      }
-      rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st);
-      if (rc != RF_OK) return rc;
-      rc = rf_launch_wide_emit(ix, qc, nb, ws, st);
-      if (rc != RF_OK) return rc;
-    } else {
-      int P = 0;
-      rf_fold fold{};  // n_samp = 0 unless the sample pass keeps its lists
-      if (ix->size > RF_SMALL_ROWS) {
-        rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st, filt, &fold);
-        if (rc != RF_OK) return rc;
-      }
-      rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, &fold);
-      if (rc != RF_OK) return rc;
-      rc = rf_launch_emit(ix, qc, nb, JB, ws, st, filt, &fold);
-      if (rc != RF_OK) return rc;
-    }
-    rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, scores_dev + (size_t)q0 * k,
-                         ids_dev + (size_t)q0 * k, exact_dev ? exact_dev + (size_t)q0 * k : nullptr,
-                         flags_dev ? flags_dev + q0 : nullptr, st);
-    if (rc != RF_OK) return rc;
-    q0 += nb;
-  }
-  return RF_OK;
-}
-
-// ---- SQ8 (include/ragfin.h, "SQ8 index") ------------------------------------------------------------
-// The SQ8 workspace is the FLAT one followed by the per-sweep query quantization (q^ for 64 queries
-// of up to 1024 dims, then t_q, n_q, f_q).
-static size_t carve_sq8(unsigned char* base, rf_workspace* ws, rf_sq8_ws* sw) {
-  size_t off = carve(base, ws);
-  auto take = [&](size_t bytes) {
-    unsigned char* p = base ? base + off : nullptr;
-    off = align_up(off + bytes, 256);
-    return p;
-  };
-  int8_t* q8 = (int8_t*)take((size_t)RF_QCHUNK * 1024);
-  float* tq = (float*)take(RF_QCHUNK * sizeof(float));
-  float* nq = (float*)take(RF_QCHUNK * sizeof(float));
-  float* fq = (float*)take(RF_QCHUNK * sizeof(float));
-  if (sw) *sw = rf_sq8_ws{q8, tq, nq, fq};
-  return off;
-}
-
-extern "C" size_t rf_search_sq8_workspace_bytes(const rf_index_t* ix) {
-  (void)ix;
-  return carve_sq8(nullptr, nullptr, nullptr);
-}
-
 static int check_sq8(const char* fn, const rf_index_t* ix, size_t ws_bytes) {
   if (!ix->sq8_tiles) {
     rf_set_error("%s: no SQ8 shadow attached (rf_index_attach_sq8)", fn);
@@ -221,28 +115,184 @@ static int check_sq8(const char* fn, const rf_index_t* ix, size_t ws_bytes) {
   return RF_OK;
 }
 
-// One 64-query sweep: quantize the queries, the fp16 sample pass (no fold), the threshold with its
-// SQ8 argument, the int8 emit sweep, the unchanged merge.  stage_ev: nullable, 6 events around the
-// five stages.
-static int sq8_sweep(const rf_index_t* ix, const _Float16* qc, int nb, int k, int64_t id_base, float* scores,
-                     int64_t* ids, double* exact, uint32_t* flags, const rf_workspace& ws, const rf_sq8_ws& sw,
-                     hipStream_t st, hipEvent_t* ev) {
+static int check_filter_arg(const char* fn, const void* filter_dev) {
+  if (!filter_dev || (((uintptr_t)filter_dev) & 15)) {
+    rf_set_error("%s: filter buffer null or not 16-byte aligned", fn);
+    return RF_ERR_INVALID;
+  }
+  return RF_OK;
+}
+
+__global__ void k_fill_empty(int n, int B, float* scores, int64_t* ids, double* exact,
+                             uint32_t* flags) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    scores[i] = -INFINITY;
+    ids[i] = -1;
+    if (exact) exact[i] = -INFINITY;
+  }
+  if (flags && i < B) flags[i] = 0u;
+}
+
+// ---- the chunk walk -----------------------------------------------------------------------------
+// Per-query outputs of a batch, [B, k] each (flags: [B]); any of them may be absent.
+struct rf_out {
+  float* scores;
+  int64_t* ids;
+  double* exact;
+  uint32_t* flags;
+};
+
+static int fill_empty(int B, int k, const rf_out& o, hipStream_t st) {
+  const int n = B * k;
+  hipLaunchKernelGGL(k_fill_empty, dim3((n + 255) / 256), dim3(256), 0, st, n, B, o.scores, o.ids,
+                     o.exact, o.flags);
+  RF_HIP(hipGetLastError());
+  return RF_OK;
+}
+
+// More than one 64-query sweep left and dim 384: one wide sweep of up to 256 queries.
+// Small corpora -- every row a candidate -- stay on the 64-query kernel (its inline flushes take
+// any hit density, the wide kernel's bounded staging would flag every query), and so do large k
+// (the k-th of ~64 partition maxima is a weak threshold) and k-dense searches of mid-sized
+// corpora (expected hits per wave and phase ~ 2^15 k / N against room for 96).
+static bool take_wide(const rf_index_t* ix, int left, int k) {
+  return rf_wide_supported(ix) && left > RF_QCHUNK && ix->size > RF_SMALL_ROWS && k <= 16 &&
+         ix->size >= (int64_t)k * 1024;
+}
+
+// Queries of the next sweep when `left` remain; widen: the caller's chain has a wide form.
+static int chunk_width(const rf_index_t* ix, int left, int k, bool widen, bool* wide) {
+  *wide = widen && take_wide(ix, left, k);
+  const int cap = *wide ? RF_QWIDE : RF_QCHUNK;
+  return left < cap ? left : cap;
+}
+
+template <class T>
+static T* at(T* p, size_t off) { return p ? p + off : nullptr; }
+
+// Walks a batch in sweeps: body(q0, nb, wide, q of the chunk, outputs of the chunk), with `row`
+// output elements per query.  Anything else a body offsets (bounds, deltas) it offsets by q0.
+template <class F>
+static int for_chunks(const rf_index_t* ix, const void* q_dev, int B, int k, size_t row, bool widen,
+                      const rf_out& o, F&& body) {
+  for (int q0 = 0; q0 < B;) {
+    bool wide;
+    const int nb = chunk_width(ix, B - q0, k, widen, &wide);
+    const size_t r0 = (size_t)q0 * row;
+    const int rc = body(q0, nb, wide, (const _Float16*)q_dev + (size_t)q0 * ix->dim,
+                        rf_out{at(o.scores, r0), at(o.ids, r0), at(o.exact, r0), at(o.flags, (size_t)q0)});
+    if (rc != RF_OK) return rc;
+    q0 += nb;
+  }
+  return RF_OK;
+}
+
+// ---- the search chain ---------------------------------------------------------------------------
+// Which form of the chain a sweep runs.  filt: the masked sweep of filtered search (never wide:
+// B > 64 runs as 64-query sweeps).  sq8: the int8 emit over the shadow, after quantizing the
+// queries into *sq8 (64-query sweeps only, no filtered form).  wide: the 256-query kernels.
+struct rf_variant {
+  const rf_filter_view* filt;
+  const rf_sq8_ws* sq8;
+  bool wide;
+};
+
+static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
+  if (ev) RF_HIP(hipEventRecord(ev[(*n)++], st));
+  return RF_OK;
+}
+
+// One sweep of nb <= RF_QWIDE queries: (SQ8: quantize the queries ->) sample -> threshold -> emit ->
+// merge.  ev: nullable; one event before the first stage and one after each (5, with SQ8 6).
+static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, int nb, int k, int64_t id_base,
+                 const rf_workspace& ws, const rf_out& o, hipStream_t st, hipEvent_t* ev) {
   const int JB = nb <= 32 ? 1 : 2;
-  int P = 0;
-  if (ev) RF_HIP(hipEventRecord(ev[0], st));
-  int rc = rf_launch_sq8_queries(ix, qc, nb, sw, st);
-  if (ev) RF_HIP(hipEventRecord(ev[1], st));
-  if (rc == RF_OK) rc = rf_launch_sample(ix, qc, nb, JB, ws, &P, st);
-  if (ev) RF_HIP(hipEventRecord(ev[2], st));
-  if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, nullptr, &sw);
-  if (ev) RF_HIP(hipEventRecord(ev[3], st));
-  if (rc == RF_OK) rc = rf_launch_sq8_emit(ix, nb, JB, ws, sw, st);
-  if (ev) RF_HIP(hipEventRecord(ev[4], st));
-  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, scores, ids, exact, flags, st);
-  if (ev) RF_HIP(hipEventRecord(ev[5], st));
+  int P = 0, n_ev = 0;
+  // the unfiltered 64-query FLAT sweep folds the sample into the emit; n_samp stays 0 unless the
+  // sample pass keeps its lists
+  rf_fold kept{};
+  rf_fold* fold = (v.wide || v.sq8 || v.filt) ? nullptr : &kept;
+  int rc = mark(ev, &n_ev, st);
+  if (v.sq8) {
+    if (rc == RF_OK) rc = rf_launch_sq8_queries(ix, qc, nb, *v.sq8, st);
+    if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  }
+  if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
+    rc = v.wide ? rf_launch_wide_sample(ix, qc, nb, ws, &P, st)
+                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK)
+    rc = v.wide  ? rf_launch_wide_emit(ix, qc, nb, ws, st)
+         : v.sq8 ? rf_launch_sq8_emit(ix, nb, JB, ws, *v.sq8, st)
+                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   return rc;
 }
 
+// Every search entry point below: the whole batch (stage_ms == nullptr), or its first sweep alone
+// with HIP events around the stages, whose times in ms go to stage_ms (4 floats, with SQ8 5).
+// sq8 on a small corpus runs the FLAT chain: every row is a candidate there anyway (no sample pass
+// to gain from).
+static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, const rf_out& o,
+                          void* workspace_dev, hipStream_t st, const rf_filter_view* filt, bool sq8,
+                          float* stage_ms = nullptr) {
+  if (ix->size == 0) return fill_empty(B, k, o, st);
+  rf_arena a{(unsigned char*)workspace_dev, 0};
+  rf_workspace ws;
+  const rf_sq8_ws sw = carve_sq8(a, &ws);   // (the SQ8 area is only touched by an SQ8 sweep)
+  const rf_sq8_ws* sq = sq8 && ix->size > RF_SMALL_ROWS ? &sw : nullptr;
+  const bool widen = !filt && !sq;
+  if (!stage_ms)
+    return for_chunks(ix, q_dev, B, k, (size_t)k, widen, o,
+                      [&](int, int nb, bool wide, const _Float16* qc, const rf_out& oc) {
+                        return sweep(ix, rf_variant{filt, sq, wide}, qc, nb, k, id_base, ws, oc, st, nullptr);
+                      });
+  bool wide;
+  const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
+  const int stages = sq ? 5 : 4;
+  hipEvent_t ev[6];
+  for (int i = 0; i <= stages; ++i) RF_HIP(hipEventCreate(&ev[i]));
+  int rc = sweep(ix, rf_variant{filt, sq, wide}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
+  if (rc == RF_OK) {
+    RF_HIP(hipEventSynchronize(ev[stages]));
+    for (int i = 0; i < stages; ++i) RF_HIP(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
+  }
+  for (int i = 0; i <= stages; ++i) (void)hipEventDestroy(ev[i]);
+  return rc;
+}
+
+extern "C" int rf_search(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                         float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                         uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes,
+                         void* stream) {
+  int rc = check_search_args("rf_search", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc != RF_OK) return rc;
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, nullptr, false);
+}
+
+extern "C" int rf_search_profile(const rf_index_t* ix, const void* q_dev, int B, int k,
+                                 int64_t id_base, float* scores_dev, int64_t* ids_dev,
+                                 double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream, float* stage_ms_host) {
+  int rc = check_search_args("rf_search_profile", ix, q_dev, B, k, scores_dev, ids_dev,
+                             workspace_dev, workspace_bytes);
+  if (rc != RF_OK) return rc;
+  if (!stage_ms_host || ix->size == 0) {
+    rf_set_error("rf_search_profile: null stage buffer or empty index");
+    return RF_ERR_INVALID;
+  }
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, nullptr, false, stage_ms_host);
+}
+
+// ---- SQ8 (include/ragfin.h, "SQ8 index") ------------------------------------------------------------
 extern "C" int rf_search_sq8(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
                              float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
                              void* workspace_dev, size_t workspace_bytes, void* stream) {
@@ -251,21 +301,8 @@ extern "C" int rf_search_sq8(const rf_index_t* ix, const void* q_dev, int B, int
   if (rc != RF_OK) return rc;
   rc = check_sq8("rf_search_sq8", ix, workspace_bytes);
   if (rc != RF_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  // small corpora: every row is a candidate on the FLAT path anyway (no sample pass to gain from)
-  if (ix->size <= RF_SMALL_ROWS)
-    return search_enqueue(ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, workspace_dev, st);
-  rf_workspace ws;
-  rf_sq8_ws sw;
-  carve_sq8((unsigned char*)workspace_dev, &ws, &sw);
-  for (int q0 = 0; q0 < B; q0 += RF_QCHUNK) {
-    const int nb = (B - q0) < RF_QCHUNK ? (B - q0) : RF_QCHUNK;
-    rc = sq8_sweep(ix, (const _Float16*)q_dev + (size_t)q0 * ix->dim, nb, k, id_base, scores_dev + (size_t)q0 * k,
-                   ids_dev + (size_t)q0 * k, exact_dev ? exact_dev + (size_t)q0 * k : nullptr,
-                   flags_dev ? flags_dev + q0 : nullptr, ws, sw, st, nullptr);
-    if (rc != RF_OK) return rc;
-  }
-  return RF_OK;
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, nullptr, true);
 }
 
 extern "C" int rf_search_sq8_profile(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
@@ -281,21 +318,8 @@ extern "C" int rf_search_sq8_profile(const rf_index_t* ix, const void* q_dev, in
     rf_set_error("rf_search_sq8_profile: null stage buffer or a corpus of <= %d rows", RF_SMALL_ROWS);
     return RF_ERR_INVALID;
   }
-  hipStream_t st = (hipStream_t)stream;
-  rf_workspace ws;
-  rf_sq8_ws sw;
-  carve_sq8((unsigned char*)workspace_dev, &ws, &sw);
-  hipEvent_t ev[6];
-  for (int i = 0; i < 6; ++i) RF_HIP(hipEventCreate(&ev[i]));
-  const int nb = B < RF_QCHUNK ? B : RF_QCHUNK;
-  rc = sq8_sweep(ix, (const _Float16*)q_dev, nb, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, ws, sw, st,
-                 ev);
-  if (rc == RF_OK) {
-    RF_HIP(hipEventSynchronize(ev[5]));
-    for (int i = 0; i < 5; ++i) RF_HIP(hipEventElapsedTime(&stage_ms_host[i], ev[i], ev[i + 1]));
-  }
-  for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, nullptr, true, stage_ms_host);
 }
 
 extern "C" int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int B, int64_t n, float* out_dev,
@@ -307,54 +331,14 @@ extern "C" int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int 
   int rc = check_sq8("rf_debug_scores_sq8", ix, workspace_bytes);
   if (rc != RF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  rf_sq8_ws sw;
-  carve_sq8((unsigned char*)workspace_dev, nullptr, &sw);
-  for (int q0 = 0; q0 < B; q0 += RF_QCHUNK) {
-    const int nb = (B - q0) < RF_QCHUNK ? (B - q0) : RF_QCHUNK;
-    rc = rf_launch_sq8_queries(ix, (const _Float16*)q_dev + (size_t)q0 * ix->dim, nb, sw, st);
-    if (rc == RF_OK)
-      rc = rf_launch_sq8_debug(ix, nb, n, sw, out_dev + (size_t)q0 * n, delta_dev ? delta_dev + q0 : nullptr, st);
-    if (rc != RF_OK) return rc;
-  }
-  return RF_OK;
-}
-
-extern "C" int rf_search_profile(const rf_index_t* ix, const void* q_dev, int B, int k,
-                                 int64_t id_base, float* scores_dev, int64_t* ids_dev,
-                                 double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
-                                 size_t workspace_bytes, void* stream, float* stage_ms_host) {
-  int rc = check_search_args("rf_search_profile", ix, q_dev, B, k, scores_dev, ids_dev,
-                             workspace_dev, workspace_bytes);
-  if (rc != RF_OK) return rc;
-  if (!stage_ms_host || ix->size == 0) {
-    rf_set_error("rf_search_profile: null stage buffer or empty index");
-    return RF_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  hipEvent_t ev[5];
-  for (int i = 0; i < 5; ++i) RF_HIP(hipEventCreate(&ev[i]));
-  rf_workspace ws;
-  carve((unsigned char*)workspace_dev, &ws);
-  const bool wide = take_wide(ix, B, k);   // the first sweep rf_search would run for this batch
-  const int nb = wide ? (B < RF_QWIDE ? B : RF_QWIDE) : (B < RF_QCHUNK ? B : RF_QCHUNK);
-  const int JB = nb <= 32 ? 1 : 2;
-  int P = 0;
-  rf_fold fold{};  // the chain rf_search runs: the 64-query sweep folds the sample into the emit
-  RF_HIP(hipEventRecord(ev[0], st));
-  if (ix->size > RF_SMALL_ROWS)
-    rc = wide ? rf_launch_wide_sample(ix, q_dev, nb, ws, &P, st) : rf_launch_sample(ix, q_dev, nb, JB, ws, &P, st, nullptr, &fold);
-  RF_HIP(hipEventRecord(ev[1], st));
-  if (rc == RF_OK) rc = rf_launch_threshold(ix, q_dev, nb, k, P, ws, st, wide ? nullptr : &fold);
-  RF_HIP(hipEventRecord(ev[2], st));
-  if (rc == RF_OK) rc = wide ? rf_launch_wide_emit(ix, q_dev, nb, ws, st) : rf_launch_emit(ix, q_dev, nb, JB, ws, st, nullptr, &fold);
-  RF_HIP(hipEventRecord(ev[3], st));
-  if (rc == RF_OK)
-    rc = rf_launch_merge(ix, q_dev, nb, k, id_base, ws, scores_dev, ids_dev, exact_dev, flags_dev, st);
-  RF_HIP(hipEventRecord(ev[4], st));
-  RF_HIP(hipEventSynchronize(ev[4]));
-  for (int i = 0; i < 4; ++i) RF_HIP(hipEventElapsedTime(&stage_ms_host[i], ev[i], ev[i + 1]));
-  for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
+  rf_arena a{(unsigned char*)workspace_dev, 0};
+  const rf_sq8_ws sw = carve_sq8(a, nullptr);
+  // (n scores per query: the walk offsets out_dev as a [B, n] output)
+  return for_chunks(ix, q_dev, B, 0, (size_t)n, false, rf_out{out_dev, nullptr, nullptr, nullptr},
+                    [&](int q0, int nb, bool, const _Float16* qc, const rf_out& oc) {
+                      const int rc = rf_launch_sq8_queries(ix, qc, nb, sw, st);
+                      return rc != RF_OK ? rc : rf_launch_sq8_debug(ix, nb, n, sw, oc.scores, at(delta_dev, (size_t)q0), st);
+                    });
 }
 
 static int exhaustive_impl(const char* fn, const rf_index_t* ix, const void* q_dev, int B, int k,
@@ -364,22 +348,15 @@ static int exhaustive_impl(const char* fn, const rf_index_t* ix, const void* q_d
   int rc = check_search_args(fn, ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev, workspace_bytes);
   if (rc != RF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (ix->size == 0) {
-    fill_empty(B, k, scores_dev, ids_dev, exact_dev, nullptr, st);
-    RF_HIP(hipGetLastError());
-    return RF_OK;
-  }
-  rf_workspace ws;
-  carve((unsigned char*)workspace_dev, &ws);
-  for (int q0 = 0; q0 < B; q0 += RF_QCHUNK) {
-    const int nb = (B - q0) < RF_QCHUNK ? (B - q0) : RF_QCHUNK;
-    rc = rf_launch_exhaustive(ix, (const _Float16*)q_dev + (size_t)q0 * ix->dim, nb, k, id_base, ws,
-                              scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k,
-                              exact_dev ? exact_dev + (size_t)q0 * k : nullptr,
-                              after_s ? after_s + q0 : nullptr, after_r ? after_r + q0 : nullptr, st, mask);
-    if (rc != RF_OK) return rc;
-  }
-  return RF_OK;
+  const rf_out o{scores_dev, ids_dev, exact_dev, nullptr};
+  if (ix->size == 0) return fill_empty(B, k, o, st);
+  rf_arena a{(unsigned char*)workspace_dev, 0};
+  const rf_workspace ws = carve(a);
+  return for_chunks(ix, q_dev, B, k, (size_t)k, false, o,
+                    [&](int q0, int nb, bool, const _Float16* qc, const rf_out& oc) {
+                      return rf_launch_exhaustive(ix, qc, nb, k, id_base, ws, oc.scores, oc.ids, oc.exact,
+                                                  at(after_s, (size_t)q0), at(after_r, (size_t)q0), st, mask);
+                    });
 }
 
 extern "C" int rf_search_exhaustive(const rf_index_t* ix, const void* q_dev, int B, int k,
@@ -404,14 +381,6 @@ extern "C" int rf_search_exhaustive_after(const rf_index_t* ix, const void* q_de
 }
 
 // ---- filtered search (include/ragfin.h, "filtered search") ---------------------------------------
-static int check_filter_arg(const char* fn, const void* filter_dev) {
-  if (!filter_dev || (((uintptr_t)filter_dev) & 15)) {
-    rf_set_error("%s: filter buffer null or not 16-byte aligned", fn);
-    return RF_ERR_INVALID;
-  }
-  return RF_OK;
-}
-
 extern "C" int rf_search_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
                                   int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
                                   uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
@@ -421,8 +390,8 @@ extern "C" int rf_search_filtered(const rf_index_t* ix, const void* filter_dev, 
   rc = check_filter_arg("rf_search_filtered", filter_dev);
   if (rc != RF_OK) return rc;
   const rf_filter_view f = rf_filter_carve(filter_dev, ix->size);
-  return search_enqueue(ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev, flags_dev, workspace_dev,
-                        (hipStream_t)stream, &f);
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, &f, false);
 }
 
 extern "C" int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev,

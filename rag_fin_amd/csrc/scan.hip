@@ -438,13 +438,19 @@ extern "C" int rf_set_tuning(const char* key, int value) {
 }
 #endif
 
+// The JB = 1 / JB = 2 pair of one (KS, ring depth, waves) shape.
+template <int KS, int R, int WAVES, int MODE, class PT>
+static int launch_scan_jb(int JB, const PT& p, int grid, hipStream_t st) {
+  return JB == 1 ? launch_scan<KS, R, 1, WAVES, MODE>(p, grid, st) : launch_scan<KS, R, 2, WAVES, MODE>(p, grid, st);
+}
+
+#define RF_CASE(ks, r, waves, grid) \
+  case ks:                          \
+    return launch_scan_jb<ks, r, waves, MODE>(JB, p, grid, st);
+
 template <int MODE, class PT>
 static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
                          hipStream_t st) {
-#define RF_CASE(ks, r, waves, grid)                                              \
-  case ks:                                                                       \
-    return JB == 1 ? launch_scan<ks, r, 1, waves, MODE>(p, grid, st)             \
-                   : launch_scan<ks, r, 2, waves, MODE>(p, grid, st);
   // dim 384: the emit sweep runs best with a SHALLOW ring (8 fragments = 8 KiB per
   // wave in flight: 119 us vs 124 us at 24 -- deeper queues only add latency once
   // HBM is saturated), the short sample pass with the full-block ring (16 vs 21 us:
@@ -455,21 +461,16 @@ static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
     const int ring = (p.n_work < 6u * 4u * (uint32_t)grid4) ? 24 : rf_knob_ring24;
     switch (ring) {
       case 8:
-        return JB == 1 ? launch_scan<24, 8, 1, 4, MODE>(p, grid4, st) : launch_scan<24, 8, 2, 4, MODE>(p, grid4, st);
+        return launch_scan_jb<24, 8, 4, MODE>(JB, p, grid4, st);
 #ifdef RF_EXPERIMENTS
       case 6:
-        return JB == 1 ? launch_scan<24, 6, 1, 4, MODE>(p, grid4, st) : launch_scan<24, 6, 2, 4, MODE>(p, grid4, st);
+        return launch_scan_jb<24, 6, 4, MODE>(JB, p, grid4, st);
       case 12:
-        return JB == 1 ? launch_scan<24, 12, 1, 4, MODE>(p, grid4, st) : launch_scan<24, 12, 2, 4, MODE>(p, grid4, st);
+        return launch_scan_jb<24, 12, 4, MODE>(JB, p, grid4, st);
 #endif
-      default:
+      default:   // 24: the table's entry
         break;
     }
-#undef RF_CASE
-#define RF_CASE(ks, r, waves, grid)                                              \
-  case ks:                                                                       \
-    return JB == 1 ? launch_scan<ks, r, 1, waves, MODE>(p, grid, st)             \
-                   : launch_scan<ks, r, 2, waves, MODE>(p, grid, st);
   }
   switch (KS) {
     RF_CASE(4, 4, 4, grid4)
@@ -482,10 +483,10 @@ static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
     default:
       break;
   }
-#undef RF_CASE
   rf_set_error("no scan kernel for dim %d", KS * 16);
   return RF_ERR_UNSUPPORTED;
 }
+#undef RF_CASE
 
 int rf_scan_supported_dim(int dim) {
   switch (dim) {

@@ -60,8 +60,48 @@ def require_gpu(device=None):
     return torch.device("cuda", idx)
 
 
+def rerun_flagged(q16, k: int, id_base: int, flags, sq8: bool, filt, flat, exhaustive):
+    """The flagged-query ladder ("fallback"): a query the first pass could not prove
+    exact (flags != 0) is re-run one tier down.  A query flagged by an SQ8 first pass (`sq8`) goes
+    through the FLAT chain, and only one that flags there too goes to the exhaustive kernel; one
+    flagged by a FLAT or filtered (`filt`) first pass goes straight to the exhaustive kernel, over
+    the same passing rows.  The tiers are callables, on whatever device their tensors live:
+      flat(q, k, id_base)             -> (scores, ids, exact | None, flags)
+      exhaustive(q, k, id_base, filt) -> (scores, ids, exact | None)
+    -> (bad, rows): the indices of the re-run queries (on the device of `flags`) and their
+    replacement [scores, ids, exact | None], each row from the last tier that ran it; rows is
+    None when nothing was flagged.  The caller patches its own destination."""
+    torch = _torch()
+    bad = torch.nonzero(flags != 0).flatten()
+    if bad.numel() == 0:
+        return bad, None
+    qb = q16[bad.to(q16.device)].contiguous()
+    if not sq8:
+        return bad, list(exhaustive(qb, k, id_base, filt))
+    *rows, f2 = flat(qb, k, id_base)
+    again = torch.nonzero(f2 != 0).flatten()
+    if again.numel() > 0:
+        for dst, src in zip(rows, exhaustive(qb[again].contiguous(), k, id_base, filt)):
+            if dst is not None:
+                dst[again] = src
+    return bad, rows
+
+
+def _ptr(t):
+    return c_void_p(t.data_ptr()) if t is not None else None
+
+
 class GpuIndex:
-    """Thin object wrapper over rf_index_* / rf_search (include/ragfin.h)."""
+    """Thin object wrapper over rf_index_* / rf_search (include/ragfin.h).
+
+    Locking: the index's own workspace (`self.workspace`) is shared by every caller that does not
+    bring one.  A method that uses it holds `self._lock` while it enqueues and until the results
+    it patches from are read; so do the methods that change the index under a search (compact,
+    enable_sq8, disable_sq8).  A method given a caller's workspace does not lock.  The two
+    exceptions are `search_raw(workspace=None)` and `enqueue_search`: the benchmark and the
+    sharded lanes call them on streams of their own, and the caller serialises.  The lock is not
+    re-entrant: public locked methods call the private unlocked ones (`_exhaustive`,
+    `_rerun_flagged`), never each other."""
 
     def __init__(self, dim: int, capacity: int, device=None):
         torch = _torch()
@@ -228,19 +268,19 @@ class GpuIndex:
 
     def search_sq8_profile(self, q16, k: int):
         """rf_search_sq8_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
+        return self._profile(self.lib.rf_search_sq8_profile, q16, min(q16.shape[0], _lib.RF_QCHUNK), k,
+                             self.workspace.numel(), ("quantize", "sample", "threshold", "emit", "merge"))
+
+    def _profile(self, fn, q16, B: int, k: int, workspace_bytes: int, stages):
+        """The first sweep of a B-query batch through a *_profile entry point -> {stage: ms}."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
-        B = min(q16.shape[0], _lib.RF_QCHUNK)
-        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
-        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
-        ms = (ctypes.c_float * 5)()
+        scores, ids, _, flags = self._outputs(B, k)
+        ms = (ctypes.c_float * len(stages))()
         with self._lock, torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_search_sq8_profile(
-                self.handle, c_void_p(q16.data_ptr()), B, k, 0, c_void_p(scores.data_ptr()),
-                c_void_p(ids.data_ptr()), None, c_void_p(flags.data_ptr()),
-                c_void_p(self.workspace.data_ptr()), self.workspace.numel(), _lib.current_stream_ptr(), ms))
-        return {"quantize": ms[0], "sample": ms[1], "threshold": ms[2], "emit": ms[3], "merge": ms[4]}
+            _lib.check(fn(self.handle, _ptr(q16), B, k, 0, _ptr(scores), _ptr(ids), None, _ptr(flags),
+                          _ptr(self.workspace), workspace_bytes, _lib.current_stream_ptr(), ms))
+        return dict(zip(stages, ms))
 
     # -- search --------------------------------------------------------------
     def new_workspace(self):
@@ -250,6 +290,17 @@ class GpuIndex:
         return torch.zeros(max(self.workspace_bytes, self.sq8_workspace_bytes), dtype=torch.uint8,
                            device=self.device)
 
+    def _outputs(self, B: int, k: int, want_exact: bool = False, flags: bool = True, out=None):
+        """The output tuple of a search: `out` when the caller brings one, else fresh device tensors
+        (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags i32 [B] | None)."""
+        if out is not None:
+            return out
+        torch = _torch()
+        return (torch.empty((B, k), dtype=torch.float32, device=self.device),
+                torch.empty((B, k), dtype=torch.int64, device=self.device),
+                torch.empty((B, k), dtype=torch.float64, device=self.device) if want_exact else None,
+                torch.empty((B,), dtype=torch.int32, device=self.device) if flags else None)
+
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
                    workspace=None, stream_ptr=None, filt=None, sq8: bool = False):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
@@ -258,7 +309,9 @@ class GpuIndex:
         filt: a filter buffer built for this index (CorpusStore.build_filter / rf_filter_eval):
         rf_search_filtered, the same outputs over the passing rows only.
         sq8: rf_search_sq8 (needs enable_sq8; not with filt).  A workspace passed in must hold
-        sq8_workspace_bytes (new_workspace does)."""
+        sq8_workspace_bytes (new_workspace does).
+        Takes no lock, with or without a workspace of the caller's: the benchmark and the sharded
+        lanes call it on their own streams, and whoever shares the index's workspace serialises."""
         torch = _torch()
         if sq8 and filt is not None:
             raise ValueError("SQ8 search has no filtered form")
@@ -267,17 +320,9 @@ class GpuIndex:
         if not q16.is_contiguous() or q16.device != self.device:
             q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
-        if out is None:
-            scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
-            ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
-            exact = torch.empty((B, k), dtype=torch.float64, device=self.device) if want_exact else None
-            flags = torch.empty((B,), dtype=torch.int32, device=self.device)
-        else:
-            scores, ids, exact, flags = out
-        args = (c_void_p(q16.data_ptr()), B, k, id_base, c_void_p(scores.data_ptr()),
-                c_void_p(ids.data_ptr()), c_void_p(exact.data_ptr()) if exact is not None else None,
-                c_void_p(flags.data_ptr()),
-                c_void_p((workspace if workspace is not None else self.workspace).data_ptr()),
+        scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
+        args = (_ptr(q16), B, k, id_base, _ptr(scores), _ptr(ids), _ptr(exact), _ptr(flags),
+                _ptr(workspace if workspace is not None else self.workspace),
                 self.sq8_workspace_bytes if sq8 else self.workspace_bytes,
                 stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
         with torch.cuda.device(self.device):
@@ -286,14 +331,15 @@ class GpuIndex:
             elif filt is None:
                 _lib.check(self.lib.rf_search(self.handle, *args))
             else:
-                _lib.check(self.lib.rf_search_filtered(self.handle, c_void_p(filt.data_ptr()), *args))
+                _lib.check(self.lib.rf_search_filtered(self.handle, _ptr(filt), *args))
         return scores, ids, exact, flags
 
     def enqueue_search(self, q_ptr: int, B: int, k: int, id_base: int, scores_ptr: int, ids_ptr: int,
                        exact_ptr: int, flags_ptr: int, workspace_ptr: int, stream_ptr):
         """The bare rf_search enqueue for callers that own every buffer (the sharded step: no
         tensor checks, no allocations, no stream / device context).  The caller guarantees that
-        this index's device is the thread's current HIP device."""
+        this index's device is the thread's current HIP device, and serialises the use of
+        the workspace it passes: no lock is taken here."""
         rc = self.lib.rf_search(self.handle, q_ptr, B, k, id_base, scores_ptr, ids_ptr, exact_ptr, flags_ptr,
                                 workspace_ptr, self.workspace_bytes, stream_ptr)
         if rc:
@@ -301,49 +347,42 @@ class GpuIndex:
 
     def search_profile(self, q16, k: int):
         """rf_search_profile: per-stage HIP-event times in ms (synchronises)."""
-        torch = _torch()
-        q16 = q16.to(self.device).contiguous()
-        B = min(q16.shape[0], 256)      # the first sweep: 64 queries, or up to 256 on the wide path
-        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
-        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
-        ms = (ctypes.c_float * 4)()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_search_profile(
-                self.handle, c_void_p(q16.data_ptr()), B, k, 0, c_void_p(scores.data_ptr()),
-                c_void_p(ids.data_ptr()), None, c_void_p(flags.data_ptr()),
-                c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
-                _lib.current_stream_ptr(), ms))
-        return {"sample": ms[0], "threshold": ms[1], "emit": ms[2], "merge": ms[3]}
+        # the first sweep: 64 queries, or up to 256 on the wide path
+        return self._profile(self.lib.rf_search_profile, q16, min(q16.shape[0], 256), k, self.workspace_bytes,
+                             ("sample", "threshold", "emit", "merge"))
 
-    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
+    def _exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, after=None):
+        """The exhaustive fp64 kernel through whichever entry point the arguments need.  filt: over
+        the passing rows.  after: (fp64 scores [B], i64 ids [B]), only the hits ranked strictly after
+        that bound per query.  Uses the index workspace: the caller holds the lock."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
-        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
-        ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
-        exact = torch.empty((B, k), dtype=torch.float64, device=self.device) if want_exact else None
+        scores, ids, exact, _ = self._outputs(B, k, want_exact, flags=False)
+        query = (_ptr(q16), B, k, id_base)
+        bounds = (None, None) if after is None else (_ptr(after[0]), _ptr(after[1]))
+        outs = (_ptr(scores), _ptr(ids), _ptr(exact), _ptr(self.workspace), self.workspace_bytes,
+                _lib.current_stream_ptr())
         with torch.cuda.device(self.device):
-            if filt is None:
-                _lib.check(self.lib.rf_search_exhaustive(
-                    self.handle, c_void_p(q16.data_ptr()), B, k, id_base, c_void_p(scores.data_ptr()),
-                    c_void_p(ids.data_ptr()), c_void_p(exact.data_ptr()) if exact is not None else None,
-                    c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
-                    _lib.current_stream_ptr()))
+            if filt is not None:
+                rc = self.lib.rf_search_exhaustive_filtered(self.handle, _ptr(filt), *query, *bounds, *outs)
+            elif after is not None:
+                rc = self.lib.rf_search_exhaustive_after(self.handle, *query, *bounds, *outs)
             else:
-                _lib.check(self.lib.rf_search_exhaustive_filtered(
-                    self.handle, c_void_p(filt.data_ptr()), c_void_p(q16.data_ptr()), B, k, id_base, None, None,
-                    c_void_p(scores.data_ptr()), c_void_p(ids.data_ptr()),
-                    c_void_p(exact.data_ptr()) if exact is not None else None,
-                    c_void_p(self.workspace.data_ptr()), self.workspace_bytes, _lib.current_stream_ptr()))
+                rc = self.lib.rf_search_exhaustive(self.handle, *query, *outs)
+        _lib.check(rc)
         return scores, ids, exact
+
+    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
+        with self._lock:
+            return self._exhaustive(q16, k, id_base, want_exact, filt)
 
     def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
         """Limits above RF_MAX_K: the first page through the fused path, further pages
-        of RF_MAX_K through rf_search_exhaustive_after (each page = the hits ranked
+        of RF_MAX_K through the exhaustive kernel with a bound (each page = the hits ranked
         strictly after the previous page's last hit).  Returns (scores, ids) [B, k]
         (+ the fp64 ranking scores with want_exact: what a cross-shard merge ranks by).
-        filt: the same over the passing rows (rf_search_exhaustive_filtered pages)."""
+        filt: the same over the passing rows."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
@@ -353,25 +392,11 @@ class GpuIndex:
         last_s, last_i = e0[:, -1].contiguous(), i0[:, -1].contiguous()
         got = page
         while got < k and bool((last_i >= 0).any()):
-            s = torch.empty((B, page), dtype=torch.float32, device=self.device)
-            i = torch.empty((B, page), dtype=torch.int64, device=self.device)
-            e = torch.empty((B, page), dtype=torch.float64, device=self.device)
             # exhausted queries keep a bound nothing can follow
             bs = torch.where(last_i >= 0, last_s, torch.full_like(last_s, float("-inf")))
             bi = torch.where(last_i >= 0, last_i, torch.full_like(last_i, 2 ** 62))
-            with self._lock, torch.cuda.device(self.device):
-                if filt is None:
-                    _lib.check(self.lib.rf_search_exhaustive_after(
-                        self.handle, c_void_p(q16.data_ptr()), B, page, id_base, c_void_p(bs.data_ptr()),
-                        c_void_p(bi.data_ptr()), c_void_p(s.data_ptr()), c_void_p(i.data_ptr()),
-                        c_void_p(e.data_ptr()), c_void_p(self.workspace.data_ptr()), self.workspace_bytes,
-                        _lib.current_stream_ptr()))
-                else:
-                    _lib.check(self.lib.rf_search_exhaustive_filtered(
-                        self.handle, c_void_p(filt.data_ptr()), c_void_p(q16.data_ptr()), B, page, id_base,
-                        c_void_p(bs.data_ptr()), c_void_p(bi.data_ptr()), c_void_p(s.data_ptr()),
-                        c_void_p(i.data_ptr()), c_void_p(e.data_ptr()), c_void_p(self.workspace.data_ptr()),
-                        self.workspace_bytes, _lib.current_stream_ptr()))
+            with self._lock:
+                s, i, e = self._exhaustive(q16, page, id_base, True, filt, after=(bs, bi))
             scores.append(s)
             ids.append(i)
             exacts.append(e)
@@ -384,31 +409,22 @@ class GpuIndex:
         out = (torch.cat(scores, 1)[:, :k].contiguous(), torch.cat(ids, 1)[:, :k].contiguous())
         return out + (torch.cat(exacts, 1)[:, :k].contiguous(),) if want_exact else out
 
+    def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt):
+        """rerun_flagged with this index's tiers.  The caller holds the lock."""
+        return rerun_flagged(q16, k, id_base, flags, sq8, filt,
+                             lambda q, k, base: self.search_raw(q, k, base, want_exact),
+                             lambda q, k, base, f: self._exhaustive(q, k, base, want_exact, f))
+
     def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False):
-        """rf_search, then re-run any query the fused path could not prove exact
-        (flags != 0) through the exhaustive fp64 kernel.  Serialised: the index
-        workspace is shared (SURVEY.md 8b threading row).  filt: over the passing rows.
-        sq8: rf_search_sq8 first; a query it flags is re-run through FLAT rf_search, and only one
-        that flags there too goes to the exhaustive kernel ("fallback")."""
-        torch = _torch()
+        """rf_search, then the flagged-query ladder (rerun_flagged) for any query the fused path
+        could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first."""
         with self._lock:
             scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8)
-            bad = torch.nonzero(flags != 0).flatten()
-            if sq8 and bad.numel() > 0:
-                qb = q16.to(self.device)[bad].contiguous()
-                s2, i2, e2, f2 = self.search_raw(qb, k, id_base, want_exact)
-                scores[bad] = s2
-                ids[bad] = i2
-                if exact is not None:
-                    exact[bad] = e2
-                bad = bad[f2 != 0]
-            if bad.numel() > 0:
-                qb = q16.to(self.device)[bad].contiguous()
-                s2, i2, e2 = self.search_exhaustive(qb, k, id_base, want_exact, filt=filt)
-                scores[bad] = s2
-                ids[bad] = i2
-                if exact is not None:
-                    exact[bad] = e2
+            bad, rows = self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt)
+            if rows is not None:
+                for dst, src in zip((scores, ids, exact), rows):
+                    if dst is not None:
+                        dst[bad] = src
         return scores, ids, exact
 
     ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
@@ -417,7 +433,7 @@ class GpuIndex:
         """search() whose results land on the host with ONE synchronisation: scores, ids and
         flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
         ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows.
-        sq8: rf_search_sq8, with search()'s two-step fallback for flagged queries."""
+        sq8: rf_search_sq8 first, as in search()."""
         torch = _torch()
         with self._lock:
             B = q16.shape[0]
@@ -439,18 +455,9 @@ class GpuIndex:
                 bufs[2].copy_(flags, non_blocking=True)
             torch.cuda.current_stream(self.device).synchronize()
             if bool(bufs[2].any()):
-                bad = torch.nonzero(bufs[2] != 0).flatten()
-                if sq8:   # flagged by SQ8: FLAT first, the exhaustive kernel only for what FLAT flags
-                    qb = q16.to(self.device)[bad.to(self.device)].contiguous()
-                    s2, i2, _, f2 = self.search_raw(qb, k)
-                    bufs[0][bad] = s2.cpu()
-                    bufs[1][bad] = i2.cpu()
-                    bad = bad[(f2 != 0).cpu()]
-                if bad.numel() > 0:
-                    qb = q16.to(self.device)[bad.to(self.device)].contiguous()
-                    s2, i2, _ = self.search_exhaustive(qb, k, filt=filt)
-                    bufs[0][bad] = s2.cpu()
-                    bufs[1][bad] = i2.cpu()
+                bad, rows = self._rerun_flagged(q16, k, 0, False, bufs[2], sq8, filt)
+                bufs[0][bad] = rows[0].cpu()
+                bufs[1][bad] = rows[1].cpu()
             # private copies, taken while the lock is still held: the pinned buffers are shared by every caller with
             # this (B, k) and the next search's merge kernel stores straight into them
             return bufs[0].numpy().copy(), bufs[1].numpy().copy()

@@ -188,3 +188,80 @@ def test_sq8_symbols_exported_and_host_checks():
     assert lib.rf_index_get_rows_sq8(None, None, 0, None, None, None, None) == -1
     assert lib.rf_debug_scores_sq8(None, None, 1, 1, None, None, None, 0, None) == -1
     assert lib.rf_search_sq8(None, None, 1, 10, 0, None, None, None, None, None, 0, None) == -1
+
+
+# ---- the flagged-query ladder with stand-in tiers (store.rerun_flagged; DESIGN §4.4b, "fallback") ----
+class Tiers:
+    """Stand-ins for the FLAT chain and the exhaustive kernel: each records the queries it was given
+    (a query is the row [j, j, ...]) and answers with its own mark, FLAT flagging `flat_flags`."""
+
+    def __init__(self, flat_flags=()):
+        self.flat_flags = set(flat_flags)
+        self.flat_ran, self.exhaustive_ran, self.filters = [], [], []
+
+    @staticmethod
+    def rows(q, k, mark):
+        n = q.shape[0]
+        qi = q[:, 0].to(torch.int64)
+        return (torch.full((n, k), float(mark), dtype=torch.float32) + qi[:, None].float(),
+                torch.full((n, k), mark, dtype=torch.int64) + qi[:, None],
+                torch.full((n, k), float(mark), dtype=torch.float64) + qi[:, None].double())
+
+    def flat(self, q, k, id_base):
+        qi = [int(v) for v in q[:, 0]]
+        self.flat_ran.append(qi)
+        flags = torch.tensor([1 if j in self.flat_flags else 0 for j in qi], dtype=torch.int32)
+        return self.rows(q, k, 1000) + (flags,)
+
+    def exhaustive(self, q, k, id_base, filt):
+        self.exhaustive_ran.append([int(v) for v in q[:, 0]])
+        self.filters.append(filt)
+        return self.rows(q, k, 2000)
+
+
+def ladder(flags, sq8, filt, tiers, k=3):
+    from rag_fin_amd.store import rerun_flagged
+    q = torch.arange(8, dtype=torch.float16)[:, None].repeat(1, 4)
+    out = [torch.zeros((8, k), dtype=torch.float32), torch.zeros((8, k), dtype=torch.int64),
+           torch.zeros((8, k), dtype=torch.float64)]
+    f = torch.zeros(8, dtype=torch.int32)
+    f[list(flags)] = 1
+    bad, rows = rerun_flagged(q, k, 0, f, sq8, filt, tiers.flat, tiers.exhaustive)
+    if rows is not None:
+        for dst, src in zip(out, rows):
+            dst[bad] = src
+    return bad, rows, out
+
+
+def test_ladder_sq8_first_pass_goes_through_flat_then_exhaustive():
+    t = Tiers(flat_flags={4})
+    bad, rows, (s, i, e) = ladder({1, 4, 6}, True, None, t)
+    assert bad.tolist() == [1, 4, 6]
+    assert t.flat_ran == [[1, 4, 6]]                 # FLAT ran on exactly the SQ8-flagged queries
+    assert t.exhaustive_ran == [[4]]                 # the exhaustive kernel on exactly what FLAT flagged too
+    for r in (0, 2, 3, 5, 7):                        # untouched
+        assert not s[r].any() and not i[r].any() and not e[r].any()
+    # each patched row holds the value of the last tier that ran it
+    for r, mark in ((1, 1000), (4, 2000), (6, 1000)):
+        assert i[r].tolist() == [mark + r] * 3
+        assert s[r].tolist() == [float(mark + r)] * 3 and e[r].tolist() == [float(mark + r)] * 3
+
+
+@pytest.mark.parametrize("filt", [None, "the-filter"])
+def test_ladder_flat_or_filtered_first_pass_goes_straight_to_exhaustive(filt):
+    t = Tiers()
+    bad, rows, (s, i, e) = ladder({2}, False, filt, t)
+    assert bad.tolist() == [2]
+    assert t.flat_ran == [] and t.exhaustive_ran == [[2]]
+    assert t.filters == [filt]                       # the exhaustive tier receives the filter
+    assert i[2].tolist() == [2002] * 3 and s[2].tolist() == [2002.0] * 3
+    assert not i[[0, 1, 3, 4, 5, 6, 7]].any()
+
+
+@pytest.mark.parametrize("sq8", [False, True])
+def test_ladder_without_flags_runs_no_tier(sq8):
+    t = Tiers()
+    bad, rows, (s, i, e) = ladder((), sq8, None, t)
+    assert bad.numel() == 0 and rows is None
+    assert t.flat_ran == [] and t.exhaustive_ran == []
+    assert not s.any() and not i.any() and not e.any()

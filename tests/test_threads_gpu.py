@@ -133,3 +133,45 @@ def test_raw_searches_from_threads_with_own_workspaces_and_streams(gpu_device):
     for t in threads:
         t.join()
     assert not errors, errors[:3]
+
+
+def test_locked_entry_points_share_the_index_workspace(gpu_device):
+    """GpuIndex's locking rule: every method that uses the index's own workspace holds the index
+    lock.  Four threads on ONE index and its workspace -- two in search, one in search_profile, one
+    in search_exhaustive -- and every search / search_exhaustive result must be byte-equal to the
+    single-threaded answer taken before the threads start."""
+    import torch
+    from rag_fin_amd.store import GpuIndex
+    c = osearch.synth_unit_rows(30_000, 384, 3)
+    ix = GpuIndex(384, 30_000, gpu_device)
+    ix.add(torch.from_numpy(c).to(gpu_device))
+    q = torch.from_numpy(osearch.synth_unit_rows(64, 384, 13)).to(gpu_device)
+    q_ex = q[:8].contiguous()
+
+    def host(out):
+        torch.cuda.synchronize(gpu_device)
+        return [t.cpu().numpy().tobytes() for t in out]
+
+    want_search = host(ix.search(q, 10, want_exact=True))
+    want_ex = host(ix.search_exhaustive(q_ex, 10, want_exact=True))
+    errors, rounds = [], 20
+
+    def worker(tid):
+        try:
+            for r in range(rounds):
+                if tid < 2:
+                    assert host(ix.search(q, 10, want_exact=True)) == want_search, ("search", tid, r)
+                elif tid == 2:
+                    st = ix.search_profile(q, 10)
+                    assert set(st) == {"sample", "threshold", "emit", "merge"}
+                else:
+                    assert host(ix.search_exhaustive(q_ex, 10, want_exact=True)) == want_ex, ("exhaustive", tid, r)
+        except BaseException as e:      # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors[:3]
