@@ -229,6 +229,39 @@ int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* filter_dev, 
                                   const int64_t* after_id_dev, float* scores_dev, int64_t* ids_dev,
                                   double* exact_dev, void* workspace_dev, size_t workspace_bytes,
                                   void* stream);
+/* ---- range search: Collection.search(..., param={"params": {"radius": r, "range_filter": f}}) ----
+ * The best k hits whose score lies in the band  radius < score <= range_filter  (COSINE / IP:
+ * higher is better), i.e. the (score desc, row asc) ranking of rf_search with every row outside
+ * the band removed.  Band membership is decided on the contract score -- the fp64 value exact_dev
+ * receives -- against the two bounds as fp64: not on the MFMA score and not on the fp32 rounding
+ * of the score (so a returned fp32 score may EQUAL (float)radius: its fp64 value is above it).
+ * radius may be -INFINITY (a band with only a ceiling) and range_filter +INFINITY (only a floor);
+ * radius >= range_filter or a NaN returns RF_ERR_INVALID.  Fewer band rows than k: the tail is
+ * -inf / -1 and flags stay 0 (an empty band is a proven answer).
+ * filter_dev: NULL, or a filter buffer as for rf_search_filtered -- the band within the passing
+ * rows.  Otherwise the conventions of rf_search_filtered: stream-ordered, no host sync, captures
+ * into a hipGraph (the bounds travel in the launch arguments), outputs may be pinned host memory,
+ * flags 0 = proven equal to the exact ranking of the band, non-zero (RF_FLAG_*) = answer that
+ * query through rf_search_exhaustive_range.  Workspace: rf_search_workspace_bytes.
+ * What runs: 64-query sweeps whatever B is (no wide band kernel); the sample pass clips at the
+ * ceiling, the threshold has the floor of the band under it, the emit appends only rows between
+ * the two, and the merge drops what the fp64 scores put outside the band.  No
+ * sample fold and no SQ8 form: an index with an SQ8 shadow answers a range search from its fp16
+ * rows.  Corpora of <= 8192 rows skip the sample pass as in rf_search (every row at or above
+ * the floor and at or below the ceiling is a candidate).
+ * rf_search_exhaustive_range: the fp64 kernel with the eligibility test radius < a <=
+ * range_filter; after_score_dev / after_id_dev are both NULL, or both set for paging above
+ * RF_MAX_K as in rf_search_exhaustive_after.  No flags: its answer is exact by construction.
+ * New in this build; the reference calls Milvus without range parameters on this path. */
+int rf_search_range(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                    int64_t id_base, double radius, double range_filter, float* scores_dev,
+                    int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
+                    size_t workspace_bytes, void* stream);
+int rf_search_exhaustive_range(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B,
+                               int k, int64_t id_base, double radius, double range_filter,
+                               const double* after_score_dev, const int64_t* after_id_dev,
+                               float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

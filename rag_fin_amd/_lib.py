@@ -88,6 +88,11 @@ SIGNATURES = {
     "rf_search_exhaustive_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
+    "rf_search_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_search_exhaustive_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
     "rf_packed_shard_words": (c_size_t, [c_int, c_int]),

@@ -35,14 +35,18 @@ class SearchRequest(BaseModel):
     top_k: int = Field(default=3, ge=1, le=20)
     # boolean expression over the scalar fields (rag_fin_amd.filter_expr); new, not in the reference
     filter: Optional[str] = None
+    # score cut-offs (range search: min_score < score <= max_score); new, not in the reference
+    min_score: Optional[float] = None
+    max_score: Optional[float] = None
 
 
 def search_args(req: SearchRequest) -> dict:
-    """Tool arguments of POST /search: `filter` only when it was given, so the reference's
-    payload {"query", "top_k"} is unchanged."""
+    """Tool arguments of POST /search: `filter`, `min_score` and `max_score` only when they were
+    given, so the reference's payload {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
-    if req.filter is not None:
-        args["filter"] = req.filter
+    for name in ("filter", "min_score", "max_score"):
+        if getattr(req, name) is not None:
+            args[name] = getattr(req, name)
     return args
 
 

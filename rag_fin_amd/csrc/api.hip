@@ -192,10 +192,15 @@ static int for_chunks(const rf_index_t* ix, const void* q_dev, int B, int k, siz
 // Which form of the chain a sweep runs.  filt: the masked sweep of filtered search (never wide:
 // B > 64 runs as 64-query sweeps).  sq8: the int8 emit over the shadow, after quantizing the
 // queries into *sq8 (64-query sweeps only, no filtered form).  wide: the 256-query kernels.
+// band: range search (with or without filt; never SQ8, never wide, no sample fold): the sample
+// pass clips at the ceiling by the eps a pre-kernel writes, the threshold has the floor of the
+// band under it, the emit clips at the ceiling and the merge drops what the fp64 scores put
+// outside the band.
 struct rf_variant {
   const rf_filter_view* filt;
   const rf_sq8_ws* sq8;
   bool wide;
+  const rf_band* band;
 };
 
 static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
@@ -212,24 +217,25 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   // the unfiltered 64-query FLAT sweep folds the sample into the emit; n_samp stays 0 unless the
   // sample pass keeps its lists
   rf_fold kept{};
-  rf_fold* fold = (v.wide || v.sq8 || v.filt) ? nullptr : &kept;
+  rf_fold* fold = (v.wide || v.sq8 || v.filt || v.band) ? nullptr : &kept;
   int rc = mark(ev, &n_ev, st);
   if (v.sq8) {
     if (rc == RF_OK) rc = rf_launch_sq8_queries(ix, qc, nb, *v.sq8, st);
     if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   }
+  if (rc == RF_OK && ix->size > RF_SMALL_ROWS && v.band) rc = rf_launch_band_eps(ix, qc, nb, ws, st);
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
     rc = v.wide ? rf_launch_wide_sample(ix, qc, nb, ws, &P, st)
-                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold);
+                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
-  if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8);
+  if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK)
     rc = v.wide  ? rf_launch_wide_emit(ix, qc, nb, ws, st)
          : v.sq8 ? rf_launch_sq8_emit(ix, nb, JB, ws, *v.sq8, st)
-                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold);
+                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
-  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st);
+  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   return rc;
 }
@@ -240,24 +246,24 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
 // to gain from).
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, const rf_out& o,
                           void* workspace_dev, hipStream_t st, const rf_filter_view* filt, bool sq8,
-                          float* stage_ms = nullptr) {
+                          float* stage_ms = nullptr, const rf_band* band = nullptr) {
   if (ix->size == 0) return fill_empty(B, k, o, st);
   rf_arena a{(unsigned char*)workspace_dev, 0};
   rf_workspace ws;
   const rf_sq8_ws sw = carve_sq8(a, &ws);   // (the SQ8 area is only touched by an SQ8 sweep)
   const rf_sq8_ws* sq = sq8 && ix->size > RF_SMALL_ROWS ? &sw : nullptr;
-  const bool widen = !filt && !sq;
+  const bool widen = !filt && !sq && !band;
   if (!stage_ms)
     return for_chunks(ix, q_dev, B, k, (size_t)k, widen, o,
                       [&](int, int nb, bool wide, const _Float16* qc, const rf_out& oc) {
-                        return sweep(ix, rf_variant{filt, sq, wide}, qc, nb, k, id_base, ws, oc, st, nullptr);
+                        return sweep(ix, rf_variant{filt, sq, wide, band}, qc, nb, k, id_base, ws, oc, st, nullptr);
                       });
   bool wide;
   const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
   const int stages = sq ? 5 : 4;
   hipEvent_t ev[6];
   for (int i = 0; i <= stages; ++i) RF_HIP(hipEventCreate(&ev[i]));
-  int rc = sweep(ix, rf_variant{filt, sq, wide}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
+  int rc = sweep(ix, rf_variant{filt, sq, wide, band}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
   if (rc == RF_OK) {
     RF_HIP(hipEventSynchronize(ev[stages]));
     for (int i = 0; i < stages; ++i) RF_HIP(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
@@ -344,7 +350,8 @@ extern "C" int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int 
 static int exhaustive_impl(const char* fn, const rf_index_t* ix, const void* q_dev, int B, int k,
                            int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
                            const double* after_s, const int64_t* after_r, void* workspace_dev,
-                           size_t workspace_bytes, void* stream, const uint32_t* mask = nullptr) {
+                           size_t workspace_bytes, void* stream, const uint32_t* mask = nullptr,
+                           const rf_band* band = nullptr) {
   int rc = check_search_args(fn, ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev, workspace_bytes);
   if (rc != RF_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
@@ -355,7 +362,7 @@ static int exhaustive_impl(const char* fn, const rf_index_t* ix, const void* q_d
   return for_chunks(ix, q_dev, B, k, (size_t)k, false, o,
                     [&](int q0, int nb, bool, const _Float16* qc, const rf_out& oc) {
                       return rf_launch_exhaustive(ix, qc, nb, k, id_base, ws, oc.scores, oc.ids, oc.exact,
-                                                  at(after_s, (size_t)q0), at(after_r, (size_t)q0), st, mask);
+                                                  at(after_s, (size_t)q0), at(after_r, (size_t)q0), st, mask, band);
                     });
 }
 
@@ -410,6 +417,49 @@ extern "C" int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* f
   const rf_filter_view f = rf_filter_carve(filter_dev, ix ? ix->size : 0);
   return exhaustive_impl("rf_search_exhaustive_filtered", ix, q_dev, B, k, id_base, scores_dev, ids_dev,
                          exact_dev, after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream, f.mask);
+}
+
+// ---- range search (include/ragfin.h, "range search") ----------------------------------------------
+static int check_band(const char* fn, double radius, double range_filter) {
+  if (!(radius < range_filter)) {   // also catches a NaN on either side
+    rf_set_error("%s: need radius < range_filter (got %g, %g)", fn, radius, range_filter);
+    return RF_ERR_INVALID;
+  }
+  return RF_OK;
+}
+
+extern "C" int rf_search_range(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                               int64_t id_base, double radius, double range_filter, float* scores_dev,
+                               int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
+                               size_t workspace_bytes, void* stream) {
+  int rc = check_search_args("rf_search_range", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc == RF_OK) rc = check_band("rf_search_range", radius, range_filter);
+  if (rc == RF_OK && filter_dev) rc = check_filter_arg("rf_search_range", filter_dev);
+  if (rc != RF_OK) return rc;
+  const rf_band band{radius, range_filter};
+  const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix->size) : rf_filter_view{};
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, filter_dev ? &f : nullptr, false, nullptr, &band);
+}
+
+extern "C" int rf_search_exhaustive_range(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B,
+                                          int k, int64_t id_base, double radius, double range_filter,
+                                          const double* after_score_dev, const int64_t* after_id_dev,
+                                          float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                                          void* workspace_dev, size_t workspace_bytes, void* stream) {
+  int rc = check_band("rf_search_exhaustive_range", radius, range_filter);
+  if (rc == RF_OK && filter_dev) rc = check_filter_arg("rf_search_exhaustive_range", filter_dev);
+  if (rc != RF_OK) return rc;
+  if ((after_score_dev == nullptr) != (after_id_dev == nullptr)) {
+    rf_set_error("rf_search_exhaustive_range: give both bound arrays or neither");
+    return RF_ERR_INVALID;
+  }
+  const rf_band band{radius, range_filter};
+  const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix ? ix->size : 0) : rf_filter_view{};
+  return exhaustive_impl("rf_search_exhaustive_range", ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev,
+                         after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream,
+                         filter_dev ? f.mask : nullptr, &band);
 }
 
 extern "C" int rf_merge_shards(const double* exact_dev, const int64_t* ids_dev, int W, int B, int k,

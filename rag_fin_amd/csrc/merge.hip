@@ -111,11 +111,40 @@ struct ThrSq8 {
   const float* fq;
   const uint32_t* mx;         // {N', E} bits
 };
+// eps of query qi (the bound above), the same value in every lane of the wave
+__device__ __forceinline__ float query_eps(const _Float16* __restrict__ q, int qi, int B, int dim, int lane,
+                                           const uint32_t* __restrict__ max_norm2) {
+  float s = 0.f;
+  if (qi < B)
+    for (int d = lane; d < dim; d += 64) {
+      const float x = (float)q[(size_t)qi * dim + d];
+      s = fmaf(x, x, s);
+    }
+  s = wave_sum_f(s);
+  const float cmax2 = __builtin_bit_cast(float, *max_norm2);
+  return 1.25f * (float)dim * 1.1920929e-7f * sqrtf(s) * sqrtf(cmax2);
+}
+
+// Range search: the sample pass of a band sweep clips by eps before k_threshold has run, so this
+// one-wave-per-query kernel writes it first (k_threshold writes the same value again).
+__global__ void __launch_bounds__(64) k_band_eps(const _Float16* __restrict__ q, int B, int dim,
+                                                 const uint32_t* __restrict__ max_norm2,
+                                                 float* __restrict__ eps_out) {
+  const float eps = query_eps(q, blockIdx.x, B, dim, threadIdx.x, max_norm2);
+  if (threadIdx.x == 0) eps_out[blockIdx.x] = eps;
+}
+
+// BAND (range search, rf_band {lo, hi}): pmax holds the partition maxima over the rows with
+// score <= hi - eps (scan.hip), and thr = max(m_k - 2 eps, lo - eps): with fewer than k such
+// maxima, or a k-th below the floor of the band, every row that can have a > lo is emitted
+// (DESIGN 4.4c).  No fold and no SQ8 in this form.
+template <bool BAND>
 __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q, int B, int dim,
                                                   int k, const float* __restrict__ pmax, int P,
                                                   const uint32_t* __restrict__ max_norm2,
                                                   float* __restrict__ thr, float* __restrict__ eps_out,
-                                                  uint32_t* __restrict__ cand_cnt, ThrFold fd, ThrSq8 sq) {
+                                                  uint32_t* __restrict__ cand_cnt, ThrFold fd, ThrSq8 sq,
+                                                  rf_band bd) {
   const int qi = blockIdx.x;
   const int lane = threadIdx.x;
   // kept lists per lane and chunk: the first chunk (1024 sample waves, all of a 4-wave sample
@@ -138,15 +167,7 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
     }
   };
   load_lists(0u);
-  float s = 0.f;
-  if (qi < B)
-    for (int d = lane; d < dim; d += 64) {
-      const float x = (float)q[(size_t)qi * dim + d];
-      s = fmaf(x, x, s);
-    }
-  s = wave_sum_f(s);
-  const float cmax2 = __builtin_bit_cast(float, *max_norm2);
-  const float eps = 1.25f * (float)dim * 1.1920929e-7f * sqrtf(s) * sqrtf(cmax2);
+  const float eps = query_eps(q, qi, B, dim, lane, max_norm2);
 
   float t;
   bool give_up = false;  // SQ8 only: the query is left to FLAT (see below)
@@ -201,6 +222,7 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
       }
     }
   }
+  if (BAND && qi < B) t = fmaxf(t, rf_band_floor(bd.lo - (double)eps));
   if (lane == 0) {
     thr[qi] = t;
     eps_out[qi] = (sq.mx && qi < B) ? rf_sq8_delta(sq.nq[qi], sq.fq[qi], __builtin_bit_cast(float, sq.mx[0]),
@@ -278,12 +300,18 @@ static size_t merge_lds_bytes(int dim) {
          RF_RESCORE_CAP * 4 + 64 + (size_t)dim * 8 + (size_t)MERGE_STAGE_ROWS * (dim * 2 + 16);
 }
 
+// BAND (range search): the candidates reach up to hi + eps.  The k-th largest is taken among
+// those with score <= hi - eps only (rows that are certainly not above the band; fewer than k of
+// them: no cut), R keeps everything at or above the cut -- the fringe (hi - eps, hi + eps]
+// included --, and after the fp64 chains every row of R with a > hi or a <= lo is dropped before
+// the ranking.
+template <bool BAND>
 __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
     int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
     uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
     int64_t* __restrict__ ids, double* __restrict__ exact, uint32_t* __restrict__ flags,
-    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt) {
+    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt, rf_band bd) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned long long* skeys = (unsigned long long*)lds;                       // [1024]
   unsigned long long* wtop = skeys + MERGE_RANK_MAX;                          // [4][RF_MAX_K]
@@ -291,6 +319,8 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   uint32_t* r_row = (uint32_t*)(r_exact + RF_RESCORE_CAP);                    // [RESCORE_CAP]
   uint32_t* r_cnt = r_row + RF_RESCORE_CAP;                                   // misc: 16 words
   float* t_cut = (float*)(r_cnt + 1);
+  uint32_t* n_elig = r_cnt + 2;                                               // BAND: candidates <= hi - eps
+  uint32_t* n_band = r_cnt + 3;                                               // BAND: rows of R inside the band
   double* qd = (double*)(r_cnt + 16);                                         // [dim]
   uint4* srows = (uint4*)(qd + dim);                                          // [32][2 KS + 1]
   const int srow_stride = 2 * KS + 1;
@@ -315,7 +345,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   if (total > RF_CAND_CAP) fl = RF_FLAG_CAND_OVERFLOW;
   const uint32_t c = total < RF_CAND_CAP ? total : RF_CAND_CAP;
   const int kk = (uint32_t)k < c ? k : (int)c;
-  const bool have_cut = kk > 0 && (uint32_t)k <= c;  // fewer than k candidates: rescore all
+  bool have_cut = kk > 0 && (uint32_t)k <= c;  // fewer than k candidates: rescore all
   const uint2* lists = cand + (size_t)qi * RF_CAND_SHARDS * cap;
   auto cand_at = [&](uint32_t g) -> uint2 {
     int s = 0;
@@ -333,10 +363,20 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     return e;
   };
   const float eps2 = 2.f * eps_in[qi];
+  // BAND: a key takes part in the k-th selection only if its score is <= hs
+  const float hs = BAND ? rf_band_floor(bd.hi - (double)eps_in[qi]) : INFINITY;
   if (tid == 0) {
     *r_cnt = 0u;
     *t_cut = -INFINITY;
+    if (BAND) *n_elig = *n_band = 0u;
   }
+  if (BAND) __syncthreads();
+  // counts the eligible keys of the block; every thread calls it once
+  auto count_eligible = [&](uint32_t mine) -> uint32_t {
+    if (mine) atomicAdd(n_elig, mine);
+    __syncthreads();
+    return *n_elig;
+  };
   for (int d = tid; d < dim; d += MERGE_THREADS) ((_Float16*)qd)[d] = q[(size_t)qi * dim + d];
 
   if (c <= MERGE_RANK_MAX) {
@@ -346,7 +386,14 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     for (int i = 0; i < MERGE_RANK_MAX / MERGE_THREADS; ++i) {
       const uint32_t idx = (uint32_t)tid + MERGE_THREADS * i;
       key[i] = idx < c ? cand_key(cand_at(idx)) : 0ull;
-      skeys[idx] = key[i];  // zero padding never outranks a real key
+      skeys[idx] = (BAND && !(key_score(key[i]) <= hs)) ? 0ull : key[i];  // zero padding never outranks a real key
+    }
+    if (BAND) {
+      uint32_t mine = 0u;
+#pragma unroll
+      for (int i = 0; i < MERGE_RANK_MAX / MERGE_THREADS; ++i)
+        mine += (key[i] != 0ull && key_score(key[i]) <= hs) ? 1u : 0u;
+      have_cut = count_eligible(mine) >= (uint32_t)k;
     }
     __syncthreads();
     if (have_cut) {
@@ -364,7 +411,8 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
       }
 #pragma unroll
       for (int i = 0; i < MERGE_RANK_MAX / MERGE_THREADS; ++i)
-        if (key[i] != 0ull && rank[i] == (uint32_t)(kk - 1)) *t_cut = key_score(key[i]) - eps2;
+        if (key[i] != 0ull && rank[i] == (uint32_t)(kk - 1) && (!BAND || key_score(key[i]) <= hs))
+          *t_cut = key_score(key[i]) - eps2;
     }
     __syncthreads();
     // ---- pass 2a: compact R from the LDS keys -----------------------------------
@@ -383,6 +431,13 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     for (int i = 0; i < MERGE_PER_THREAD; ++i) {
       const uint32_t idx = (uint32_t)tid + MERGE_THREADS * i;
       key[i] = idx < c ? cand_key(cand_at(idx)) : 0ull;
+      if (BAND && !(key_score(key[i]) <= hs)) key[i] = 0ull;
+    }
+    if (BAND) {
+      uint32_t mine = 0u;
+#pragma unroll
+      for (int i = 0; i < MERGE_PER_THREAD; ++i) mine += key[i] != 0ull ? 1u : 0u;
+      have_cut = count_eligible(mine) >= (uint32_t)k;
     }
     for (int r = 0; r < kk; ++r) {
       unsigned long long m = key[0];
@@ -466,9 +521,24 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   }
 
   // ---- pass 4: rank by (exact desc, row asc) and write --------------------------------
+  uint32_t n_in = R;
+  if (BAND) {
+    // rows outside the band leave R: they rank after every row inside it (-inf < lo < a) and
+    // are never written
+    uint32_t mine = 0u;
+    for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
+      const double s = r_exact[i];
+      if (s > bd.lo && s <= bd.hi) ++mine;
+      else r_exact[i] = -INFINITY;
+    }
+    if (mine) atomicAdd(n_band, mine);
+    __syncthreads();
+    n_in = *n_band;
+  }
   for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
     const double s = r_exact[i];
     const uint32_t row = r_row[i];
+    if (BAND && s == -INFINITY) continue;
     uint32_t rank = 0;
     for (uint32_t j = 0; j < R; ++j) rank += ranks_before(r_exact[j], r_row[j], s, row) ? 1u : 0u;
     if (rank < (uint32_t)k) {
@@ -478,7 +548,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
       if (exact) exact[o] = s;
     }
   }
-  const uint32_t filled = R < (uint32_t)k ? R : (uint32_t)k;
+  const uint32_t filled = n_in < (uint32_t)k ? n_in : (uint32_t)k;
   for (uint32_t j = filled + tid; j < (uint32_t)k; j += MERGE_THREADS) {
     const size_t o = (size_t)qi * k + j;
     scores[o] = -INFINITY;
@@ -603,6 +673,44 @@ __global__ void __launch_bounds__(EX_THREADS) k_exhaustive_scan_masked(
   }
 }
 
+// The exhaustive scan of range search: a row is eligible only if lo < a <= hi on its fp64 score
+// (and, MASKED, if its filter bit is set), beside the paging bound.  Kernels of their own for the
+// same reason as above.
+template <bool MASKED>
+__global__ void __launch_bounds__(EX_THREADS) k_exhaustive_scan_band(
+    const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int64_t n_rows,
+    int k, double* __restrict__ out_s, int64_t* __restrict__ out_r,
+    const double* __restrict__ after_s, const int64_t* __restrict__ after_r, int64_t id_base,
+    const uint32_t* __restrict__ mask, rf_band bd) {
+  __shared__ ExList L;
+  __shared__ double t_s[RF_MAX_K + EX_THREADS];
+  __shared__ int64_t t_r[RF_MAX_K + EX_THREADS];
+  __shared__ int t_n;
+  const int tid = threadIdx.x;
+  const int qi = blockIdx.y;
+  if (tid == 0) L.n = 0;
+  __syncthreads();
+  const _Float16* qrow = q + (size_t)qi * dim;
+  const bool paged = after_s != nullptr;
+  const double bs = paged ? after_s[qi] : 0.0;
+  const int64_t br = paged ? after_r[qi] - id_base : 0;
+  const int64_t step = (int64_t)gridDim.x * EX_THREADS;
+  for (int64_t base = (int64_t)blockIdx.x * EX_THREADS; base < n_rows; base += step) {
+    const int64_t row = base + tid;
+    bool valid = row < n_rows;
+    if (MASKED) valid = valid && ((mask[row >> 5] >> (row & 31)) & 1u) != 0u;
+    const double s = valid ? exact_dot(qrow, tiles, row, KS) : 0.0;
+    valid = valid && s > bd.lo && s <= bd.hi;
+    if (paged) valid = valid && ranks_before(bs, br, s, row);
+    exlist_update(&L, t_s, t_r, &t_n, k, s, row, valid, tid);
+  }
+  const size_t o = ((size_t)qi * gridDim.x + blockIdx.x) * RF_MAX_K;
+  if (tid < RF_MAX_K) {
+    out_s[o + tid] = tid < L.n ? L.s[tid] : -INFINITY;
+    out_r[o + tid] = tid < L.n ? L.r[tid] : -1;
+  }
+}
+
 __global__ void __launch_bounds__(EX_THREADS) k_exhaustive_final(
     const double* __restrict__ in_s, const int64_t* __restrict__ in_r, int lists, int k,
     int64_t id_base, float* __restrict__ scores, int64_t* __restrict__ ids,
@@ -694,7 +802,7 @@ __global__ void __launch_bounds__(EX_THREADS) k_merge_shards(
 // ---- host side --------------------------------------------------------------------------
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
                         const rf_workspace& ws, hipStream_t st, const rf_fold* fold,
-                        const rf_sq8_ws* sq8) {
+                        const rf_sq8_ws* sq8, const rf_band* band) {
   ThrFold fd{};
   ThrSq8 sq{};
   if (sq8) {
@@ -715,21 +823,42 @@ int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
     fd.force = rf_knob_fold_dbg & 1;
   }
   // one wave per query slot of the sweep (64, or up to RF_QWIDE for a wide sweep)
-  hipLaunchKernelGGL(k_threshold, dim3(B > RF_QCHUNK ? RF_QWIDE : RF_QCHUNK), dim3(64), 0, st, (const _Float16*)q, B, ix->dim,
-                     k, ws.pmax, P, ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd, sq);
+  const dim3 grid(B > RF_QCHUNK ? RF_QWIDE : RF_QCHUNK);
+  if (band)
+    hipLaunchKernelGGL(k_threshold<true>, grid, dim3(64), 0, st, (const _Float16*)q, B, ix->dim, k, ws.pmax, P,
+                       ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd, sq, *band);
+  else
+    hipLaunchKernelGGL(k_threshold<false>, grid, dim3(64), 0, st, (const _Float16*)q, B, ix->dim, k, ws.pmax, P,
+                       ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd, sq, rf_band{});
+  RF_HIP(hipGetLastError());
+  return RF_OK;
+}
+
+int rf_launch_band_eps(const rf_index* ix, const void* q, int B, const rf_workspace& ws, hipStream_t st) {
+  // every query slot of the 64-query sweep: the sample pass reads the eps of all 64 lanes
+  hipLaunchKernelGGL(k_band_eps, dim3(RF_QCHUNK), dim3(64), 0, st, (const _Float16*)q, B, ix->dim, ix->max_norm2,
+                     ws.eps);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }
 
 int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                     const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
-                    uint32_t* flags, hipStream_t st) {
+                    uint32_t* flags, hipStream_t st, const rf_band* band) {
   const size_t lds = merge_lds_bytes(ix->dim);
-  static rf_lds_attr lds_attr;
-  RF_HIP(rf_ensure_lds(lds_attr, (const void*)k_merge, lds));
-  hipLaunchKernelGGL(k_merge, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim,
-                     ix->KS, ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP,
-                     ws.eps, scores, ids, exact, flags, ws.cand_cnt, (uint32_t)ix->size, (rf_knob_fold_dbg & 2) ? 1 : 0);
+  static rf_lds_attr lds_attr, lds_attr_band;
+  if (band) {
+    RF_HIP(rf_ensure_lds(lds_attr_band, (const void*)k_merge<true>, lds));
+    hipLaunchKernelGGL(k_merge<true>, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim,
+                       ix->KS, ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP,
+                       ws.eps, scores, ids, exact, flags, ws.cand_cnt, (uint32_t)ix->size, 0, *band);
+  } else {
+    RF_HIP(rf_ensure_lds(lds_attr, (const void*)k_merge<false>, lds));
+    hipLaunchKernelGGL(k_merge<false>, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim,
+                       ix->KS, ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP,
+                       ws.eps, scores, ids, exact, flags, ws.cand_cnt, (uint32_t)ix->size,
+                       (rf_knob_fold_dbg & 2) ? 1 : 0, rf_band{});
+  }
   RF_HIP(hipGetLastError());
   return RF_OK;
 }
@@ -737,10 +866,18 @@ int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_
 int rf_launch_exhaustive(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                          const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                          const double* after_s, const int64_t* after_r, hipStream_t st,
-                         const uint32_t* mask) {
+                         const uint32_t* mask, const rf_band* band) {
   int64_t need = (ix->size + EX_THREADS - 1) / EX_THREADS;
   int lists = (int)(need < RF_EX_WGS ? (need < 1 ? 1 : need) : RF_EX_WGS);
-  if (mask)
+  if (band && mask)
+    hipLaunchKernelGGL(k_exhaustive_scan_band<true>, dim3(lists, B), dim3(EX_THREADS), 0, st,
+                       (const _Float16*)q, ix->dim, ix->KS, ix->tiles, ix->size, k, ws.ex_score,
+                       ws.ex_row, after_s, after_r, id_base, mask, *band);
+  else if (band)
+    hipLaunchKernelGGL(k_exhaustive_scan_band<false>, dim3(lists, B), dim3(EX_THREADS), 0, st,
+                       (const _Float16*)q, ix->dim, ix->KS, ix->tiles, ix->size, k, ws.ex_score,
+                       ws.ex_row, after_s, after_r, id_base, (const uint32_t*)nullptr, *band);
+  else if (mask)
     hipLaunchKernelGGL(k_exhaustive_scan_masked, dim3(lists, B), dim3(EX_THREADS), 0, st,
                        (const _Float16*)q, ix->dim, ix->KS, ix->tiles, ix->size, k, ws.ex_score,
                        ws.ex_row, after_s, after_r, id_base, mask);

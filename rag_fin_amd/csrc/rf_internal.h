@@ -173,14 +173,23 @@ struct rf_fold {
   uint32_t bstride;  // block stride of the sample
   uint32_t W;        // waves of the sample pass
 };
+// Range search (include/ragfin.h, "range search"): the band radius < a <= range_filter on the
+// contract score a, both bounds as fp64 (lo = -inf / hi = +inf: open on that side).  The sweep
+// tests MFMA scores against float bounds derived from them and the query's eps; the derivation is
+// shared by every kernel (rf_band_floor / rf_band_ceil below).
+struct rf_band {
+  double lo, hi;
+};
 // scan.hip (filt: nullptr = every row; otherwise the masked sweep over the filter's blocks)
+// band: nullptr = no band; otherwise the band form of the sweep (never with a fold)
 // fold: rf_launch_sample fills it (the fold is off for a filtered sweep and with the knob off);
 // rf_launch_threshold and rf_launch_emit take what it filled, nullptr = no fold
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr,
-                     rf_fold* fold = nullptr);
+                     rf_fold* fold = nullptr, const rf_band* band = nullptr);
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr);
+                   hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr,
+                   const rf_band* band = nullptr);
 int rf_launch_debug_scores(const rf_index* ix, const void* q, int B, int64_t n, float* out,
                            hipStream_t st);
 int rf_scan_supported_dim(int dim);
@@ -207,14 +216,16 @@ int rf_launch_sq8_debug(const rf_index* ix, int B, int64_t n, const rf_sq8_ws& s
 // merge.hip
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
                         const rf_workspace& ws, hipStream_t st, const rf_fold* fold = nullptr,
-                        const rf_sq8_ws* sq8 = nullptr);
+                        const rf_sq8_ws* sq8 = nullptr, const rf_band* band = nullptr);
+// the per-query eps of k_threshold into ws.eps, ahead of a band sample pass (which clips by it)
+int rf_launch_band_eps(const rf_index* ix, const void* q, int B, const rf_workspace& ws, hipStream_t st);
 int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                     const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
-                    uint32_t* flags, hipStream_t st);
+                    uint32_t* flags, hipStream_t st, const rf_band* band = nullptr);
 int rf_launch_exhaustive(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                          const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                          const double* after_s, const int64_t* after_r, hipStream_t st,
-                         const uint32_t* mask = nullptr);
+                         const uint32_t* mask = nullptr, const rf_band* band = nullptr);
 int rf_launch_merge_shards(const double* exact, const int64_t* ids, size_t shard_stride, int W, int B, int k,
                            float* scores_out, int64_t* ids_out, const uint32_t* flags_in, size_t flag_stride,
                            uint32_t* flags_out, hipStream_t st);
@@ -227,4 +238,15 @@ __host__ __device__ inline uint32_t rf_f2ord(float f) {
 __host__ __device__ inline float rf_ord2f(uint32_t o) {
   uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
   return __builtin_bit_cast(float, u);
+}
+
+// Range search: the float at or just below / at or just above a double (never on the wrong side
+// of it; +-inf pass through), by one step in the ordered encoding.
+__host__ __device__ inline float rf_band_floor(double x) {
+  const float f = (float)x;
+  return (double)f > x ? rf_ord2f(rf_f2ord(f) - 1u) : f;
+}
+__host__ __device__ inline float rf_band_ceil(double x) {
+  const float f = (float)x;
+  return (double)f < x ? rf_ord2f(rf_f2ord(f) + 1u) : f;
 }

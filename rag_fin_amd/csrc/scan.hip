@@ -62,13 +62,18 @@ __device__ __forceinline__ void fold_top2(const f32x16& a, uint32_t rbase, float
   m1 = c ? b1 : m1;
 }
 
-template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false>
+// BAND (range search): tc is the lane's ceiling -- hi - eps in the sample pass (rows above it
+// leave the maximum, like rows a filter rejects), hi + eps in the emit (rows above it are no
+// candidates; the block prefilter tests thr <= score <= ceiling per row -- two compares whose
+// lane masks combine on the scalar unit, no clipped copy of the accumulators -- so a block whose
+// only rows >= thr lie above the ceiling never reaches emit_slow).
+template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false, bool BAND = false>
 __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
                                            const uint4* nxt, const u32x4* smemQ, int lane,
                                            uint32_t row0, const float (&th)[JB], float (&pm)[JB],
                                            float (&m1)[JB], uint32_t (&r1)[JB], float (&m2)[JB],
                                            EmitState& es, const ScanParams& p,
-                                           uint32_t mword = 0u) {
+                                           uint32_t mword = 0u, const float* tc = nullptr) {
   static_assert(KS % R == 0, "ring must divide the block");
   // keep the query-fragment LDS reads inside the block: hoisted out of the
   // block loop they would pin JB*KS*4 registers and spill
@@ -114,6 +119,12 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
         for (int i = 0; i < 16; ++i)
           if (row0 + acc_row(i, h) >= p.n_rows) acc[jb][i] = -INFINITY;
     }
+    if (BAND) {
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[jb][i] = acc[jb][i] <= tc[jb] ? acc[jb][i] : -INFINITY;
+    }
     if (MODE == MODE_FOLD) {
 #pragma unroll
       for (int jb = 0; jb < JB; ++jb) fold_top2(acc[jb], row0 + 4u * (uint32_t)(lane >> 5), m1[jb], r1[jb], m2[jb]);
@@ -123,16 +134,24 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
     }
   } else {
     bool hit = false;
+    if (BAND) {
 #pragma unroll
-    for (int jb = 0; jb < JB; ++jb) hit |= (max16(acc[jb]) >= th[jb]);
-    if (__ballot(hit) != 0ull) emit_slow<JB, ScanParams, FILTER>(acc, th, row0, lane, es, p, mword);
+      for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) hit |= (acc[jb][i] >= th[jb]) & (acc[jb][i] <= tc[jb]);
+    } else {
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) hit |= (max16(acc[jb]) >= th[jb]);
+    }
+    if (__ballot(hit) != 0ull) emit_slow<JB, ScanParams, FILTER, BAND>(acc, th, row0, lane, es, p, mword, tc);
   }
 }
 
 // FILTER (filtered search, p is a ScanParamsF): the work items are the filter's pass blocks
 // (sample pass: every bstride-th of them), counted on the device; see scan_common.h.
-template <int KS, int R, int JB, int WAVES, int MODE, bool FILTER, class PT>
+template <int KS, int R, int JB, int WAVES, int MODE, bool FILTER, bool BAND, class PT>
 __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
+  static_assert(!BAND || MODE != MODE_FOLD, "the band sweep has no sample fold");
   u32x4* smemQ = (u32x4*)smem_raw;                                   // JB*KS*64 uint4
   unsigned char* tail = smem_raw + (size_t)JB * KS * RF_FRAG_BYTES;  // per-mode scratch
 
@@ -146,8 +165,15 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   float m1[JB];     // MODE_FOLD: best score (the partition maximum), its row, second best score
   uint32_t r1[JB];
   float m2[JB];
+  float tc[JB];     // BAND: the lane's ceiling (block_step)
 #pragma unroll
   for (int jb = 0; jb < JB; ++jb) {
+    if (BAND) {
+      const double e = (double)p.eps[jb * 32 + (lane & 31)];
+      tc[jb] = (MODE == MODE_EMIT) ? rf_band_ceil(p.band_hi + e) : rf_band_floor(p.band_hi - e);
+    } else {
+      tc[jb] = INFINITY;
+    }
     pm[jb] = -INFINITY;
     m1[jb] = -INFINITY;
     r1[jb] = 0xFFFFFFFFu;
@@ -191,7 +217,8 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   // is rlist[j].  Dense items keep every wave busy: skipping the sampled blocks inside the plain
   // round-robin would idle the waves whose blocks are the sample's (W is a multiple of s_bs).
   // With s_n = 0 item i is block i.
-  const bool folded = !FILTER && MODE == MODE_EMIT && p.s_n > 0u;  // wave-uniform
+  // (a band sweep never folds: its emit is the plain walk over every block)
+  const bool folded = !FILTER && !BAND && MODE == MODE_EMIT && p.s_n > 0u;  // wave-uniform
   const uint32_t M = folded ? p.n_work - p.s_n : p.n_work;
   const uint32_t L = folded ? p.s_n * (p.s_bs - 1u) : 0u;
   uint32_t n_res = 0u;
@@ -213,7 +240,7 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   if (FILTER ? gw < p.n_work : gw < M) {
     const uint4* src;
     if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[gw * p.bstride] * (KS * 64) + lane;
-    else if constexpr (MODE == MODE_EMIT) src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
+    else if constexpr (MODE == MODE_EMIT && !BAND) src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
     else src = p.corpus + (size_t)gw * p.bstride * (KS * 64) + lane;
 #pragma unroll
     for (int s = 0; s < R; ++s) ring[s] = ld_frag(src + s * 64);
@@ -235,7 +262,7 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   __syncthreads();
   const uint32_t n_items = M + n_res;
   const uint32_t cnt = (n_items > gw) ? (n_items - gw + W - 1) / W : 0u;
-  if (!FILTER && cnt > 0 && gw >= M) {  // the wave's first item is a rescan (a corpus of few blocks)
+  if (!FILTER && !BAND && cnt > 0 && gw >= M) {  // the wave's first item is a rescan (a corpus of few blocks)
     const uint4* src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
 #pragma unroll
     for (int s = 0; s < R; ++s) ring[s] = ld_frag(src + s * 64);
@@ -252,15 +279,15 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
         const uint32_t mw = p.mask[b];
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
         const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, false, true>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw);
+        block_step<KS, R, JB, MODE, false, true, BAND>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw, tc);
         b = bn;
       }
       {
         const uint32_t mw = p.mask[b];
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, true, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw);
+        block_step<KS, R, JB, MODE, true, true, BAND>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw, tc);
       }
-    } else if constexpr (MODE == MODE_EMIT) {
+    } else if constexpr (MODE == MODE_EMIT && !BAND) {
       // a rescanned block (item >= M) appends only for the queries its sample wave marked:
       // the others' rows of it came from k_threshold (an MFMA score is finite, never >= +inf)
       auto item_th = [&](uint32_t i, uint32_t b, float (&te)[JB]) {
@@ -281,26 +308,26 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
         const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
         float te[JB];
         item_th(w, b, te);
-        block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, te, pm, m1, r1, m2, es, p);
+        block_step<KS, R, JB, MODE, false, false, BAND>(ring, cur, nxt, smemQ, lane, b * 32u, te, pm, m1, r1, m2, es, p, 0u, tc);
         b = bn;
       }
       {
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
         float te[JB];
         item_th(w, b, te);
-        block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, te, pm, m1, r1, m2, es, p);
+        block_step<KS, R, JB, MODE, true, false, BAND>(ring, cur, cur, smemQ, lane, b * 32u, te, pm, m1, r1, m2, es, p, 0u, tc);
       }
     } else {
       for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
         const uint32_t b = w * p.bstride;
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
         const uint4* nxt = p.corpus + (size_t)(b + W * p.bstride) * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, false>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p);
+        block_step<KS, R, JB, MODE, false, false, BAND>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, 0u, tc);
       }
       {
         const uint32_t b = w * p.bstride;
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-        block_step<KS, R, JB, MODE, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p);
+        block_step<KS, R, JB, MODE, true, false, BAND>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, 0u, tc);
       }
     }
   }
@@ -345,16 +372,16 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   }
 }
 
-template <int KS, int R, int JB, int WAVES, int MODE>
+template <int KS, int R, int JB, int WAVES, int MODE, bool BAND = false>
 __global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  scan_body<KS, R, JB, WAVES, MODE, false>(p, smem_raw);
+  scan_body<KS, R, JB, WAVES, MODE, false, BAND>(p, smem_raw);
 }
 
-template <int KS, int R, int JB, int WAVES, int MODE>
+template <int KS, int R, int JB, int WAVES, int MODE, bool BAND = false>
 __global__ void __launch_bounds__(WAVES * 64, 2) k_scan_filtered(ScanParamsF p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  scan_body<KS, R, JB, WAVES, MODE, true>(p, smem_raw);
+  scan_body<KS, R, JB, WAVES, MODE, true, BAND>(p, smem_raw);
 }
 
 // ---- raw score dump (test hook) ---------------------------------------------
@@ -386,14 +413,14 @@ __global__ void __launch_bounds__(64) k_debug_scores(const uint4* corpus, const 
 }
 
 // ---- host side ----------------------------------------------------------------
-template <int KS, int R, int JB, int WAVES, int MODE, class PT>
+template <int KS, int R, int JB, int WAVES, int MODE, bool BAND, class PT>
 static int launch_scan(const PT& p, int grid, hipStream_t st) {
   size_t lds = (size_t)JB * KS * RF_FRAG_BYTES;
   if (MODE == MODE_EMIT) lds += (size_t)3 * WAVES * SCAP * 4;
   else lds += (size_t)WAVES * 2 * JB * 32 * 4;
   auto kern = [] {
-    if constexpr (std::is_same<PT, ScanParamsF>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE>;
-    else return k_scan<KS, R, JB, WAVES, MODE>;
+    if constexpr (std::is_same<PT, ScanParamsF>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE, BAND>;
+    else return k_scan<KS, R, JB, WAVES, MODE, BAND>;
   }();
   static rf_lds_attr attr;  // per instantiation, per device
   RF_HIP(rf_ensure_lds(attr, (const void*)kern, lds));
@@ -439,16 +466,17 @@ extern "C" int rf_set_tuning(const char* key, int value) {
 #endif
 
 // The JB = 1 / JB = 2 pair of one (KS, ring depth, waves) shape.
-template <int KS, int R, int WAVES, int MODE, class PT>
+template <int KS, int R, int WAVES, int MODE, bool BAND, class PT>
 static int launch_scan_jb(int JB, const PT& p, int grid, hipStream_t st) {
-  return JB == 1 ? launch_scan<KS, R, 1, WAVES, MODE>(p, grid, st) : launch_scan<KS, R, 2, WAVES, MODE>(p, grid, st);
+  return JB == 1 ? launch_scan<KS, R, 1, WAVES, MODE, BAND>(p, grid, st)
+                 : launch_scan<KS, R, 2, WAVES, MODE, BAND>(p, grid, st);
 }
 
 #define RF_CASE(ks, r, waves, grid) \
   case ks:                          \
-    return launch_scan_jb<ks, r, waves, MODE>(JB, p, grid, st);
+    return launch_scan_jb<ks, r, waves, MODE, BAND>(JB, p, grid, st);
 
-template <int MODE, class PT>
+template <int MODE, bool BAND = false, class PT>
 static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
                          hipStream_t st) {
   // dim 384: the emit sweep runs best with a SHALLOW ring (8 fragments = 8 KiB per
@@ -461,12 +489,12 @@ static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
     const int ring = (p.n_work < 6u * 4u * (uint32_t)grid4) ? 24 : rf_knob_ring24;
     switch (ring) {
       case 8:
-        return launch_scan_jb<24, 8, 4, MODE>(JB, p, grid4, st);
+        return launch_scan_jb<24, 8, 4, MODE, BAND>(JB, p, grid4, st);
 #ifdef RF_EXPERIMENTS
       case 6:
-        return launch_scan_jb<24, 6, 4, MODE>(JB, p, grid4, st);
+        return launch_scan_jb<24, 6, 4, MODE, BAND>(JB, p, grid4, st);
       case 12:
-        return launch_scan_jb<24, 12, 4, MODE>(JB, p, grid4, st);
+        return launch_scan_jb<24, 12, 4, MODE, BAND>(JB, p, grid4, st);
 #endif
       default:   // 24: the table's entry
         break;
@@ -501,7 +529,8 @@ static inline int waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
 static inline int wgs_per_cu(int KS) { return KS >= 48 ? 1 : 2; }
 
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                     int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold) {
+                     int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold,
+                     const rf_band* band) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = waves_per_wg(KS);
@@ -532,6 +561,10 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
   p.P = grid;
   *P_out = grid;
   if (fold) *fold = rf_fold{0u, 1u, 1u};
+  if (band) {  // the clip reads the eps rf_launch_band_eps wrote; no fold in this form
+    p.eps = ws.eps;
+    p.band_hi = band->hi;
+  }
   if (filt) {
     // the grid (= partitions) is sized from the whole corpus; the kernel derives the sampled
     // count and stride from the filter's device count of pass blocks, within the same bounds
@@ -543,8 +576,10 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
     f.n_blocks = nblk;
     f.work_lo = lo;
     f.work_hi = hi;
-    return dispatch_scan<MODE_SAMPLE>(KS, JB, f, grid, grid, st);
+    return band ? dispatch_scan<MODE_SAMPLE, true>(KS, JB, f, grid, grid, st)
+                : dispatch_scan<MODE_SAMPLE>(KS, JB, f, grid, grid, st);
   }
+  if (band) return dispatch_scan<MODE_SAMPLE, true>(KS, JB, p, grid, grid, st);
   if (fold && rf_knob_sample_fold && B <= RF_QCHUNK && n_work <= (uint32_t)RF_FOLD_BLOCKS &&
       (uint32_t)grid * WAVES <= (uint32_t)RF_FOLD_WAVES) {
     p.fold = ws.fold;
@@ -557,7 +592,7 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
 }
 
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st, const rf_filter_view* filt, const rf_fold* fold) {
+                   hipStream_t st, const rf_filter_view* filt, const rf_fold* fold, const rf_band* band) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = waves_per_wg(KS);
@@ -577,7 +612,11 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
   p.cand_cnt = ws.cand_cnt;
   p.cand = ws.cand;
   p.cap = RF_SHARD_CAP;
-  if (fold && fold->n_samp > 0u && !filt) {
+  if (band) {  // eps: what k_threshold wrote
+    p.eps = ws.eps;
+    p.band_hi = band->hi;
+  }
+  if (fold && fold->n_samp > 0u && !filt && !band) {
     // the sweep skips the sampled blocks (scan_body): the grid and the ring depth stay those of
     // the whole corpus
     p.rmask = ws.rmask;
@@ -595,9 +634,11 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
     f.mask = filt->mask;
     f.blocks = filt->blocks;
     f.n_blocks = nblk;
-    return dispatch_scan<MODE_EMIT>(KS, JB, f, grid, grid, st);
+    return band ? dispatch_scan<MODE_EMIT, true>(KS, JB, f, grid, grid, st)
+                : dispatch_scan<MODE_EMIT>(KS, JB, f, grid, grid, st);
   }
-  return dispatch_scan<MODE_EMIT>(KS, JB, p, grid, grid, st);
+  return band ? dispatch_scan<MODE_EMIT, true>(KS, JB, p, grid, grid, st)
+              : dispatch_scan<MODE_EMIT>(KS, JB, p, grid, grid, st);
 }
 
 int rf_launch_debug_scores(const rf_index* ix, const void* q, int B, int64_t n, float* out,

@@ -33,6 +33,11 @@ struct ScanParams {
   uint32_t* rlist;
   uint32_t* rcnt;
   uint32_t s_n, s_bs, s_W;       // sampled blocks, their stride, sample waves
+  // range search (the BAND instantiations only): the ceiling of the band and the per-query eps.
+  // MODE_SAMPLE keeps a row out of the maximum unless score <= hi - eps (then a <= hi for
+  // certain), MODE_EMIT appends a row only if score <= hi + eps (any row with a <= hi)
+  const float* eps;              // [64]
+  double band_hi;
 };
 
 // The masked sweep (filtered search): work item w is block blocks[w * bstride] of the filter's
@@ -104,10 +109,11 @@ __device__ __forceinline__ void emit_flush(EmitState& es, const P& p, int lane) 
 // FILTER: `mword` is the block's filter word; a row whose bit is clear is never a candidate,
 // whatever its score (an explicit test: the threshold may be -inf, so masking by writing -inf
 // into the accumulators would not keep rejected rows out).
-template <int JB, class P, bool FILTER = false>
+// BAND: `tc` is the per-lane ceiling of the emit (hi + eps); a row above it is no candidate.
+template <int JB, class P, bool FILTER = false, bool BAND = false>
 __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (&th)[JB],
                                           uint32_t row0, int lane, EmitState& es, const P& p,
-                                          uint32_t mword = 0u) {
+                                          uint32_t mword = 0u, const float* tc = nullptr) {
   const int h = lane >> 5;
   const uint32_t lim = p.n_rows - row0;  // rows of this block that exist (>= 32 except the last block)
   uint32_t bits = 0u;
@@ -116,7 +122,8 @@ __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (
 #pragma unroll
     for (int i = 0; i < 16; ++i)
       bits |= ((acc[jb][i] >= th[jb]) && (acc_row(i, h) < lim) &&
-               (!FILTER || ((mword >> acc_row(i, h)) & 1u) != 0u)) ? (1u << (jb * 16 + i)) : 0u;
+               (!FILTER || ((mword >> acc_row(i, h)) & 1u) != 0u) &&
+               (!BAND || acc[jb][i] <= tc[jb])) ? (1u << (jb * 16 + i)) : 0u;
   unsigned long long mask;
   while ((mask = __ballot(bits != 0u)) != 0ull) {
     const bool pass = bits != 0u;

@@ -55,11 +55,17 @@ def _searcher():
     return _batcher
 
 
-def search_vectors(query: str, top_k: int = 3, filter: str = ""):
+def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
+                   max_score: float | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
-    scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax)."""
+    scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
+    min_score / max_score: optional score cut-offs, min_score < score <= max_score."""
     try:
-        if filter and filter.strip():
+        if min_score is not None or max_score is not None:
+            # like filtered calls, banded calls bypass the micro-batcher: one batch shares one band
+            contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
+                                        min_score=min_score, max_score=max_score)
+        elif filter and filter.strip():
             # filtered calls bypass the micro-batcher: one batch shares one filter
             contexts = get_rag().search(query, top_k, expr=filter)
         else:
@@ -70,10 +76,11 @@ def search_vectors(query: str, top_k: int = 3, filter: str = ""):
         return {"status": "error", "message": str(e), "query": query}
 
 
-def answer_question(question: str, top_k: int = 3):
-    """Answer question using RAG"""
+def answer_question(question: str, top_k: int = 3, min_score: float | None = None):
+    """Answer question using RAG.  min_score: only chunks scoring above it are used."""
     try:
-        result = get_rag().search_and_answer(question, top_k)
+        result = get_rag().search_and_answer(question, top_k) if min_score is None else \
+            get_rag().search_and_answer(question, top_k, min_score=min_score)
         return {"status": "success", "question": question, **result}
     except Exception as e:
         return {"status": "error", "message": str(e), "question": question}

@@ -52,12 +52,26 @@ class VectorRAG:
                  "primary_value": h.entity.primary_value, "score": float(h.score)}
                 for i, h in enumerate(hits)]
 
-    def search(self, query: str, top_k: int = 3, expr: str | None = None) -> list[dict]:
+    @staticmethod
+    def _search_param(min_score, max_score) -> dict:
+        """The pymilvus search param: a score cut-off becomes range search (radius = min_score,
+        range_filter = max_score; max_score alone: a band with only a ceiling)."""
+        param = {"metric_type": "COSINE"}
+        if min_score is not None or max_score is not None:
+            param["params"] = {"radius": float("-inf") if min_score is None else min_score}
+            if max_score is not None:
+                param["params"]["range_filter"] = max_score
+        return param
+
+    def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
+               max_score: float | None = None) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
-        over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'."""
+        over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
+        min_score / max_score: only chunks with min_score < score <= max_score (range search;
+        the list may be shorter than top_k, or empty)."""
         q = self._embed([query])
-        results = self.collection.search(q, "embedding", {"metric_type": "COSINE"}, top_k, expr=expr,
-                                         output_fields=OUTPUT_FIELDS)
+        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
+                                         expr=expr, output_fields=OUTPUT_FIELDS)
         return self._contexts(results[0])
 
     def _embed(self, texts):
@@ -69,15 +83,16 @@ class VectorRAG:
 
     retrieve = search  # BASELINE.json's "retrieve(query, k)" name for the same call
 
-    def search_batch(self, queries: Sequence[str], top_k: int = 3,
-                     expr: str | None = None) -> list[list[dict]]:
+    def search_batch(self, queries: Sequence[str], top_k: int = 3, expr: str | None = None,
+                     min_score: float | None = None, max_score: float | None = None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
-        is strictly one query per call); expr: one filter for the whole batch."""
+        is strictly one query per call); expr, min_score / max_score: one filter and one score
+        band for the whole batch."""
         if not queries:
             return []
         q = self._embed(list(queries))
-        results = self.collection.search(q, "embedding", {"metric_type": "COSINE"}, top_k, expr=expr,
-                                         output_fields=OUTPUT_FIELDS)
+        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
+                                         expr=expr, output_fields=OUTPUT_FIELDS)
         return [self._contexts(r) for r in results]
 
     # -- generation (out of scope; interface kept) -----------------------------------------
@@ -86,8 +101,11 @@ class VectorRAG:
                           for i, c in enumerate(contexts))
         return self.prompt_template.format(question=question, context=ctx)
 
-    def search_and_answer(self, question: str, top_k: int = 3) -> dict:
-        contexts = self.search(question, top_k)
+    def search_and_answer(self, question: str, top_k: int = 3, min_score: float | None = None) -> dict:
+        """min_score: only chunks scoring above it reach the prompt (possibly none: the prompt is
+        then built from zero contexts and the payload keeps its keys)."""
+        contexts = self.search(question, top_k) if min_score is None else \
+            self.search(question, top_k, min_score=min_score)
         prompt = self.build_prompt(question, contexts)
         try:
             if self.generator is None:

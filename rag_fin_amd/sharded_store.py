@@ -305,6 +305,8 @@ class ShardedCorpusStore(CorpusStore):
                output_fields=None):
         if not filter_expr.is_empty(expr):
             raise NotImplementedError("filtered search is not implemented for the sharded store")
+        if self._band_of(param) is not None:
+            raise NotImplementedError("range search (radius / range_filter) is not implemented for the sharded store")
         return super().search(data, anns_field, param, limit, expr, output_fields)
 
     def _expr_rows(self, expr):

@@ -91,6 +91,27 @@ def _ptr(t):
     return c_void_p(t.data_ptr()) if t is not None else None
 
 
+def check_band(radius, range_filter=None):
+    """Range-search bounds -> the band (radius, range_filter) as two floats, or None when neither is
+    given.  A hit has radius < score <= range_filter (higher is better), compared as fp64 on the
+    fp64 ranking score.  range_filter without radius, a bound that is no real number (NaN, a string,
+    a bool) or radius >= range_filter raises ValueError; range_filter defaults to +inf."""
+    import math
+    import numbers
+    if radius is None and range_filter is None:
+        return None
+    if radius is None:
+        raise ValueError("range search: range_filter needs radius (radius switches range search on)")
+    out = []
+    for name, v in (("radius", radius), ("range_filter", math.inf if range_filter is None else range_filter)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or math.isnan(float(v)):
+            raise ValueError(f"range search: {name} must be a real number, got {v!r}")
+        out.append(float(v))
+    if not out[0] < out[1]:
+        raise ValueError(f"range search: need radius < range_filter, got {out[0]!r} and {out[1]!r}")
+    return out[0], out[1]
+
+
 class GpuIndex:
     """Thin object wrapper over rf_index_* / rf_search (include/ragfin.h).
 
@@ -302,7 +323,7 @@ class GpuIndex:
                 torch.empty((B,), dtype=torch.int32, device=self.device) if flags else None)
 
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False):
+                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
         hipStream_t of this device); no host sync.  Returns
         (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
@@ -310,11 +331,13 @@ class GpuIndex:
         rf_search_filtered, the same outputs over the passing rows only.
         sq8: rf_search_sq8 (needs enable_sq8; not with filt).  A workspace passed in must hold
         sq8_workspace_bytes (new_workspace does).
+        band: (radius, range_filter) -- rf_search_range: the best k rows with
+        radius < fp64 score <= range_filter (within the passing rows with filt; not with sq8).
         Takes no lock, with or without a workspace of the caller's: the benchmark and the sharded
         lanes call it on their own streams, and whoever shares the index's workspace serialises."""
         torch = _torch()
-        if sq8 and filt is not None:
-            raise ValueError("SQ8 search has no filtered form")
+        if sq8 and (filt is not None or band is not None):
+            raise ValueError("SQ8 search has no filtered and no range form")
         if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
             raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
         if not q16.is_contiguous() or q16.device != self.device:
@@ -326,7 +349,10 @@ class GpuIndex:
                 self.sq8_workspace_bytes if sq8 else self.workspace_bytes,
                 stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
         with torch.cuda.device(self.device):
-            if sq8:
+            if band is not None:
+                _lib.check(self.lib.rf_search_range(self.handle, _ptr(filt), *args[:4], float(band[0]), float(band[1]),
+                                                    *args[4:]))
+            elif sq8:
                 _lib.check(self.lib.rf_search_sq8(self.handle, *args))
             elif filt is None:
                 _lib.check(self.lib.rf_search(self.handle, *args))
@@ -351,10 +377,12 @@ class GpuIndex:
         return self._profile(self.lib.rf_search_profile, q16, min(q16.shape[0], 256), k, self.workspace_bytes,
                              ("sample", "threshold", "emit", "merge"))
 
-    def _exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, after=None):
+    def _exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, after=None,
+                    band=None):
         """The exhaustive fp64 kernel through whichever entry point the arguments need.  filt: over
         the passing rows.  after: (fp64 scores [B], i64 ids [B]), only the hits ranked strictly after
-        that bound per query.  Uses the index workspace: the caller holds the lock."""
+        that bound per query.  band: (radius, range_filter), only rows inside it
+        (rf_search_exhaustive_range).  Uses the index workspace: the caller holds the lock."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
@@ -364,7 +392,10 @@ class GpuIndex:
         outs = (_ptr(scores), _ptr(ids), _ptr(exact), _ptr(self.workspace), self.workspace_bytes,
                 _lib.current_stream_ptr())
         with torch.cuda.device(self.device):
-            if filt is not None:
+            if band is not None:
+                rc = self.lib.rf_search_exhaustive_range(self.handle, _ptr(filt), *query, float(band[0]),
+                                                         float(band[1]), *bounds, *outs)
+            elif filt is not None:
                 rc = self.lib.rf_search_exhaustive_filtered(self.handle, _ptr(filt), *query, *bounds, *outs)
             elif after is not None:
                 rc = self.lib.rf_search_exhaustive_after(self.handle, *query, *bounds, *outs)
@@ -373,21 +404,23 @@ class GpuIndex:
         _lib.check(rc)
         return scores, ids, exact
 
-    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
+    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, band=None):
         with self._lock:
-            return self._exhaustive(q16, k, id_base, want_exact, filt)
+            return self._exhaustive(q16, k, id_base, want_exact, filt, band=band)
 
-    def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None):
+    def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, band=None):
         """Limits above RF_MAX_K: the first page through the fused path, further pages
         of RF_MAX_K through the exhaustive kernel with a bound (each page = the hits ranked
         strictly after the previous page's last hit).  Returns (scores, ids) [B, k]
         (+ the fp64 ranking scores with want_exact: what a cross-shard merge ranks by).
-        filt: the same over the passing rows."""
+        filt: the same over the passing rows.  band: (radius, range_filter) -- the same within the
+        band: the first page through rf_search_range, later pages through the exhaustive band
+        kernel; the walk ends with the first page that the band does not fill."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
         page = _lib.RF_MAX_K
-        s0, i0, e0 = self.search(q16, page, id_base, want_exact=True, filt=filt)
+        s0, i0, e0 = self.search(q16, page, id_base, want_exact=True, filt=filt, band=band)
         scores, ids, exacts = [s0], [i0], [e0]
         last_s, last_i = e0[:, -1].contiguous(), i0[:, -1].contiguous()
         got = page
@@ -396,7 +429,7 @@ class GpuIndex:
             bs = torch.where(last_i >= 0, last_s, torch.full_like(last_s, float("-inf")))
             bi = torch.where(last_i >= 0, last_i, torch.full_like(last_i, 2 ** 62))
             with self._lock:
-                s, i, e = self._exhaustive(q16, page, id_base, True, filt, after=(bs, bi))
+                s, i, e = self._exhaustive(q16, page, id_base, True, filt, after=(bs, bi), band=band)
             scores.append(s)
             ids.append(i)
             exacts.append(e)
@@ -409,18 +442,22 @@ class GpuIndex:
         out = (torch.cat(scores, 1)[:, :k].contiguous(), torch.cat(ids, 1)[:, :k].contiguous())
         return out + (torch.cat(exacts, 1)[:, :k].contiguous(),) if want_exact else out
 
-    def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt):
-        """rerun_flagged with this index's tiers.  The caller holds the lock."""
+    def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt, band=None):
+        """rerun_flagged with this index's tiers (the band of a range search rides in them).  The
+        caller holds the lock."""
         return rerun_flagged(q16, k, id_base, flags, sq8, filt,
-                             lambda q, k, base: self.search_raw(q, k, base, want_exact),
-                             lambda q, k, base, f: self._exhaustive(q, k, base, want_exact, f))
+                             lambda q, k, base: self.search_raw(q, k, base, want_exact, band=band),
+                             lambda q, k, base, f: self._exhaustive(q, k, base, want_exact, f, band=band))
 
-    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False):
+    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False,
+               band=None):
         """rf_search, then the flagged-query ladder (rerun_flagged) for any query the fused path
-        could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first."""
+        could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first.
+        band: (radius, range_filter) -- rf_search_range, flagged queries through the exhaustive
+        band kernel."""
         with self._lock:
-            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8)
-            bad, rows = self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt)
+            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8, band=band)
+            bad, rows = self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt, band)
             if rows is not None:
                 for dst, src in zip((scores, ids, exact), rows):
                     if dst is not None:
@@ -429,11 +466,11 @@ class GpuIndex:
 
     ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
 
-    def search_host(self, q16, k: int, filt=None, sq8: bool = False):
+    def search_host(self, q16, k: int, filt=None, sq8: bool = False, band=None):
         """search() whose results land on the host with ONE synchronisation: scores, ids and
         flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
         ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows.
-        sq8: rf_search_sq8 first, as in search()."""
+        sq8: rf_search_sq8 first, as in search().  band: (radius, range_filter), as in search()."""
         torch = _torch()
         with self._lock:
             B = q16.shape[0]
@@ -447,15 +484,15 @@ class GpuIndex:
                 # query-sized results: the merge kernel stores straight into the pinned host buffers
                 # (host-coherent memory, mapped at the same address on the device) -- no copy commands,
                 # only the synchronisation
-                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]), filt=filt, sq8=sq8)
+                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]), filt=filt, sq8=sq8, band=band)
             else:
-                scores, ids, _, flags = self.search_raw(q16, k, filt=filt, sq8=sq8)
+                scores, ids, _, flags = self.search_raw(q16, k, filt=filt, sq8=sq8, band=band)
                 bufs[0].copy_(scores, non_blocking=True)
                 bufs[1].copy_(ids, non_blocking=True)
                 bufs[2].copy_(flags, non_blocking=True)
             torch.cuda.current_stream(self.device).synchronize()
             if bool(bufs[2].any()):
-                bad, rows = self._rerun_flagged(q16, k, 0, False, bufs[2], sq8, filt)
+                bad, rows = self._rerun_flagged(q16, k, 0, False, bufs[2], sq8, filt, band)
                 bufs[0][bad] = rows[0].cpu()
                 bufs[1][bad] = rows[1].cpu()
             # private copies, taken while the lock is still held: the pinned buffers are shared by every caller with
@@ -772,9 +809,10 @@ class CorpusStore:
     def has_index(self, **kwargs) -> bool:
         return self._index_params is not None
 
-    def _use_sq8(self, B: int, limit: int) -> bool:
-        # the routing rule: unfiltered, limit <= RF_MAX_K, B <= one 64-query sweep
-        return self.index_type == "SQ8" and limit <= _lib.RF_MAX_K and B <= _lib.RF_QCHUNK
+    def _use_sq8(self, B: int, limit: int, band=None) -> bool:
+        # the routing rule: unfiltered, no range parameters, limit <= RF_MAX_K,
+        # B <= one 64-query sweep
+        return self.index_type == "SQ8" and band is None and limit <= _lib.RF_MAX_K and B <= _lib.RF_QCHUNK
 
     # -- ingest ------------------------------------------------------------------
     def add(self, ids: Sequence, texts: Sequence[str], embeddings, periods: Sequence[str],
@@ -925,22 +963,28 @@ class CorpusStore:
             q = q[None, :]
         return self.index.to_fp16(q, normalize=self.metric_type == "COSINE")
 
-    def search_rows(self, data, limit: int, filt=None):
+    def search_rows(self, data, limit: int, filt=None, band=None):
         """(scores f32 [B,k'], rows i64 [B,k']) as host numpy, k' = min(limit, N).  filt: a
-        filter buffer (build_filter): the top-k of the passing rows, padded with -1 rows."""
+        filter buffer (build_filter): the top-k of the passing rows, padded with -1 rows.
+        band: (radius, range_filter) -- range search: the top-k of the rows with
+        radius < fp64 score <= range_filter, padded with -1 rows."""
         if limit < 1:
             raise ValueError("limit must be >= 1")
+        if band is not None:
+            band = check_band(*band)
         with self._rw.read():
-            return self._search_rows(data, limit, filt)
+            return self._search_rows(data, limit, filt, band)
 
-    def _search_rows(self, data, limit: int, filt=None):
+    def _search_rows(self, data, limit: int, filt=None, band=None):
         q16 = self._prepare_queries(data)
         kw = {} if filt is None else {"filt": filt}
+        if band is not None:
+            kw["band"] = band
         if limit > _lib.RF_MAX_K:
             scores, rows = self.index.search_large(q16, limit, **kw)   # paged, exhaustive beyond 64
             kk = min(limit, self.num_entities)
             return scores[:, :kk].cpu().numpy(), rows[:, :kk].cpu().numpy()
-        if filt is None and self._use_sq8(int(q16.shape[0]), limit):
+        if filt is None and self._use_sq8(int(q16.shape[0]), limit, band):
             kw["sq8"] = True
         scores, rows = self.index.search_host(q16, limit, **kw)   # one synchronisation for the whole download
         kk = min(limit, self.num_entities)
@@ -948,7 +992,12 @@ class CorpusStore:
 
     def search(self, data, anns_field: str = "embedding", param: dict | None = None,
                limit: int = 3, expr=None, output_fields: Iterable[str] | None = None):
-        """pymilvus-shaped search: one list of hits per query vector, best first."""
+        """pymilvus-shaped search: one list of hits per query vector, best first.
+        param["params"] may hold the range-search bounds `radius` and, optionally, `range_filter`:
+        the best `limit` hits with radius < score <= range_filter (a query may return []); the
+        comparison is made in fp64 on the fp64 ranking score, so a hit's fp32 `score` may equal
+        float32(radius).  range_filter without radius, a bound that is no real number, NaN or
+        radius >= range_filter raises ValueError.  Other keys of params (nprobe, ...) are ignored."""
         with self._rw.read():   # the rows handed back are marshalled below: no delete in between
             return self._search(data, anns_field, param, limit, expr, output_fields)
 
@@ -962,10 +1011,12 @@ class CorpusStore:
         for f in fields:
             if f not in self.columns:
                 raise KeyError(f"unknown output field {f!r}")
+        band = self._band_of(param)
+        kw = {} if band is None else {"band": band}
         if filter_expr.is_empty(expr):
-            scores, rows = self.search_rows(data, limit)
+            scores, rows = self.search_rows(data, limit, **kw)
         else:
-            scores, rows = self.search_rows(data, limit, filt=self.build_filter(expr))
+            scores, rows = self.search_rows(data, limit, filt=self.build_filter(expr), **kw)
         out = []
         for b in range(rows.shape[0]):
             hits = []
@@ -977,6 +1028,16 @@ class CorpusStore:
                                 {f: self.columns[f][r] for f in fields}))
             out.append(hits)
         return out
+
+    @staticmethod
+    def _band_of(param):
+        """The range-search band of a pymilvus search `param`, or None."""
+        params = (param or {}).get("params")
+        if params is None:
+            return None
+        if not isinstance(params, dict):
+            raise ValueError("search: param['params'] must be a dict")
+        return check_band(params.get("radius"), params.get("range_filter"))
 
     # -- persistence (SURVEY.md 8f rank 1) -------------------------------------------------
     # The reference leans on the Milvus server for durability and re-creates the
