@@ -262,6 +262,53 @@ int rf_search_exhaustive_range(const rf_index_t* ix, const void* filter_dev, con
                                const double* after_score_dev, const int64_t* after_id_dev,
                                float* scores_dev, int64_t* ids_dev, double* exact_dev,
                                void* workspace_dev, size_t workspace_bytes, void* stream);
+/* ---- grouping search: Collection.search(..., group_by_field=f, group_size=s) -----------------------
+ * The best n_groups GROUPS instead of the best k rows: a group is the set of rows that share a
+ * code (the caller's int32 dictionary code of the group-by field, one per row), its rows are ranked
+ * by (fp64 contract score desc, row asc) as everywhere else and it keeps its first
+ * min(group_size, rows of the group); groups are ranked by their best row under the same rule.
+ *   group_codes_dev  int32 [rf_index_size(ix)] on the device.  A code outside [0, n_codes) is a row
+ *                    without a group: it is never returned.
+ *   n_codes          size of the dictionary, 1..RF_GROUP_MAX_CODES for this fused path; above it
+ *                    RF_ERR_UNSUPPORTED (the caller answers group by group through
+ *                    rf_search_exhaustive_filtered).  The cap comes from the LDS budget of the sweep
+ *                    at dim 1024: 128 KiB of query fragments + a 64-code x 64-query fp32 table
+ *                    (16 KiB) + 6 KiB of staging, of 160 KiB.
+ *   n_groups, group_size   n_groups * group_size <= RF_MAX_K and both >= 1, else RF_ERR_INVALID
+ *                    (so is a null group_codes_dev).
+ *   filter_dev       NULL, or a filter buffer as for rf_search_filtered: groups are formed among the
+ *                    passing rows only (a group without a passing row does not exist).
+ * Outputs are [B, n_groups * group_size] (flags: [B]): the group of rank j occupies slots
+ * [j * group_size, (j + 1) * group_size), best row first; a short group and missing groups are
+ * padded with -inf / -1.  flags 0 = proven equal to the exact grouped ranking; non-zero (RF_FLAG_*)
+ * = answer that query group by group through the exhaustive kernel.
+ * Otherwise the conventions of rf_search_filtered: stream-ordered, no host sync, captures into a
+ * hipGraph, outputs may be pinned host memory, 64-query sweeps whatever B is.
+ * What runs per sweep: a sweep of every (passing) block that keeps the maximum MFMA
+ * score per (query, code) and workgroup, a threshold per (query, code) -- +inf for a group that
+ * cannot be among the first n_groups --, the same sweep again appending every row that reaches
+ * the threshold of its own group, and a merge that rescored in fp64.  The corpus is read twice,
+ * whatever its size (no small-corpus shortcut, no sample fold, no SQ8 form: an index with an SQ8
+ * shadow answers from its fp16 rows).  workspace_bytes >= rf_search_grouped_workspace_bytes
+ * (> rf_search_sq8_workspace_bytes; its leading part is the rf_search workspace).
+ * rf_search_grouped_profile: the first sweep with HIP events: stage_ms_host (host) receives
+ * {group-maximum sweep, threshold, emit sweep, merge} in ms; SYNCHRONISES.
+ * rf_debug_grouped_counters_offset: test hook -- byte offset in the workspace of the uint32
+ * [64][8] candidate counters, which a grouped search leaves as its last sweep wrote them (list
+ * capacity 2048 each).
+ * New in this build; the reference calls Milvus without group_by_field on this path. */
+#define RF_GROUP_MAX_CODES 64
+size_t rf_search_grouped_workspace_bytes(const rf_index_t* ix);
+int rf_search_grouped(const rf_index_t* ix, const void* filter_dev, const int32_t* group_codes_dev, int n_codes,
+                      const void* q_dev, int B, int n_groups, int group_size, int64_t id_base,
+                      float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+int rf_search_grouped_profile(const rf_index_t* ix, const void* filter_dev, const int32_t* group_codes_dev,
+                              int n_codes, const void* q_dev, int B, int n_groups, int group_size,
+                              int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                              uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream,
+                              float* stage_ms_host);
+size_t rf_debug_grouped_counters_offset(void);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

@@ -17,6 +17,7 @@ RF_MAX_K = 64
 RF_QCHUNK = 64
 RF_FLAG_CAND_OVERFLOW = 1
 RF_FLAG_TIE_OVERFLOW = 2
+RF_GROUP_MAX_CODES = 64   # dictionary size the fused grouped path serves (include/ragfin.h)
 
 
 class RagfinError(RuntimeError):
@@ -93,6 +94,13 @@ SIGNATURES = {
     "rf_search_exhaustive_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                            c_void_p]),
+    "rf_search_grouped_workspace_bytes": (c_size_t, [c_void_p]),
+    "rf_search_grouped": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_search_grouped_profile": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int64,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
+                                          POINTER(c_float)]),
+    "rf_debug_grouped_counters_offset": (c_size_t, []),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
     "rf_packed_shard_words": (c_size_t, [c_int, c_int]),

@@ -38,13 +38,16 @@ class SearchRequest(BaseModel):
     # score cut-offs (range search: min_score < score <= max_score); new, not in the reference
     min_score: Optional[float] = None
     max_score: Optional[float] = None
+    # grouping search (the best top_k groups by a scalar field, group_size chunks each); new
+    group_by: Optional[str] = None
+    group_size: Optional[int] = Field(default=None, ge=1)
 
 
 def search_args(req: SearchRequest) -> dict:
-    """Tool arguments of POST /search: `filter`, `min_score` and `max_score` only when they were
-    given, so the reference's payload {"query", "top_k"} is unchanged."""
+    """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by` and
+    `group_size` only when they were given, so the reference's payload {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
-    for name in ("filter", "min_score", "max_score"):
+    for name in ("filter", "min_score", "max_score", "group_by", "group_size"):
         if getattr(req, name) is not None:
             args[name] = getattr(req, name)
     return args

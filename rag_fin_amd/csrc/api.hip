@@ -47,6 +47,16 @@ static rf_sq8_ws carve_sq8(rf_arena& a, rf_workspace* ws) {
   return sw;
 }
 
+// The grouped workspace is the SQ8 one followed by the partition maxima and the thresholds per
+// (query, code) of a sweep.
+static rf_grouped_ws carve_grouped(rf_arena& a, rf_workspace* ws) {
+  carve_sq8(a, ws);
+  rf_grouped_ws gw;
+  gw.gpmax = a.take<float>((size_t)RF_GROUP_PARTS * RF_QCHUNK * RF_GROUP_MAX_CODES);
+  gw.gthr = a.take<float>((size_t)RF_QCHUNK * RF_GROUP_MAX_CODES);
+  return gw;
+}
+
 #ifdef RF_EXPERIMENTS
 // Diagnostic hook: byte offset of a named workspace array ("pmax", "cand", "thr", "eps", "cand_cnt",
 // "rmask", "rcnt").
@@ -460,6 +470,115 @@ extern "C" int rf_search_exhaustive_range(const rf_index_t* ix, const void* filt
   return exhaustive_impl("rf_search_exhaustive_range", ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev,
                          after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream,
                          filter_dev ? f.mask : nullptr, &band);
+}
+
+// ---- grouping search (include/ragfin.h, "grouping search") ----------------------------------------
+extern "C" size_t rf_search_grouped_workspace_bytes(const rf_index_t* ix) {
+  (void)ix;
+  rf_arena a{nullptr, 0};
+  carve_grouped(a, nullptr);
+  return a.off;
+}
+
+extern "C" size_t rf_debug_grouped_counters_offset(void) {
+  rf_arena a{(unsigned char*)(uintptr_t)4096, 0};   // never dereferenced
+  const rf_workspace ws = carve(a);
+  return (size_t)((const unsigned char*)ws.cand_cnt - a.base);
+}
+
+// One grouped sweep of nb <= 64 queries: eps -> group-maximum sweep -> thresholds -> emit -> merge.
+// ev: nullable, 5 events.
+static int sweep_grouped(const rf_index_t* ix, const rf_filter_view* filt, const rf_group& g, const _Float16* qc,
+                         int nb, int64_t id_base, const rf_workspace& ws, const rf_grouped_ws& gws,
+                         const rf_out& o, hipStream_t st, hipEvent_t* ev) {
+  const int JB = nb <= 32 ? 1 : 2;
+  int P = 0, n_ev = 0;
+  int rc = rf_launch_band_eps(ix, qc, nb, ws, st);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK) rc = rf_launch_group_max(ix, qc, nb, JB, g, ws, gws, &P, st, filt);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK) rc = rf_launch_group_threshold(nb, g, P, ws, gws, st);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK) rc = rf_launch_group_emit(ix, qc, nb, JB, g, ws, gws, st, filt);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  if (rc == RF_OK) rc = rf_launch_merge_grouped(ix, qc, nb, g, id_base, ws, o.scores, o.ids, o.exact, o.flags, st);
+  if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+  return rc;
+}
+
+static int grouped_impl(const char* fn, const rf_index_t* ix, const void* filter_dev, const int32_t* codes,
+                        int n_codes, const void* q_dev, int B, int n_groups, int group_size, int64_t id_base,
+                        const rf_out& o, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
+                        float* stage_ms) {
+  if (!codes || n_groups < 1 || group_size < 1 || n_codes < 1 ||
+      (int64_t)n_groups * group_size > RF_MAX_K) {
+    rf_set_error("%s: null codes, or n_codes / n_groups / group_size < 1, or n_groups * group_size > %d", fn,
+                 RF_MAX_K);
+    return RF_ERR_INVALID;
+  }
+  if (n_codes > RF_GROUP_MAX_CODES) {
+    rf_set_error("%s: n_codes = %d above the fused path's %d", fn, n_codes, RF_GROUP_MAX_CODES);
+    return RF_ERR_UNSUPPORTED;
+  }
+  const int k = n_groups * group_size;
+  int rc = check_search_args(fn, ix, q_dev, B, k, o.scores, o.ids, workspace_dev, workspace_bytes);
+  if (rc == RF_OK && filter_dev) rc = check_filter_arg(fn, filter_dev);
+  if (rc != RF_OK) return rc;
+  if (workspace_bytes < rf_search_grouped_workspace_bytes(ix)) {
+    rf_set_error("%s: workspace %zu B < required %zu B", fn, workspace_bytes, rf_search_grouped_workspace_bytes(ix));
+    return RF_ERR_CAPACITY;
+  }
+  if (ix->size == 0) {
+    if (stage_ms) {
+      rf_set_error("%s: empty index", fn);
+      return RF_ERR_INVALID;
+    }
+    return fill_empty(B, k, o, st);
+  }
+  rf_arena a{(unsigned char*)workspace_dev, 0};
+  rf_workspace ws;
+  const rf_grouped_ws gws = carve_grouped(a, &ws);
+  const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix->size) : rf_filter_view{};
+  const rf_filter_view* filt = filter_dev ? &f : nullptr;
+  const rf_group g{codes, n_codes, n_groups, group_size};
+  if (!stage_ms)
+    return for_chunks(ix, q_dev, B, k, (size_t)k, false, o,
+                      [&](int, int nb, bool, const _Float16* qc, const rf_out& oc) {
+                        return sweep_grouped(ix, filt, g, qc, nb, id_base, ws, gws, oc, st, nullptr);
+                      });
+  hipEvent_t ev[5];
+  for (int i = 0; i < 5; ++i) RF_HIP(hipEventCreate(&ev[i]));
+  rc = sweep_grouped(ix, filt, g, (const _Float16*)q_dev, B < RF_QCHUNK ? B : RF_QCHUNK, id_base, ws, gws, o, st, ev);
+  if (rc == RF_OK) {
+    RF_HIP(hipEventSynchronize(ev[4]));
+    for (int i = 0; i < 4; ++i) RF_HIP(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
+  }
+  for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]);
+  return rc;
+}
+
+extern "C" int rf_search_grouped(const rf_index_t* ix, const void* filter_dev, const int32_t* group_codes_dev,
+                                 int n_codes, const void* q_dev, int B, int n_groups, int group_size,
+                                 int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                                 uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return grouped_impl("rf_search_grouped", ix, filter_dev, group_codes_dev, n_codes, q_dev, B, n_groups, group_size,
+                      id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev, workspace_bytes,
+                      (hipStream_t)stream, nullptr);
+}
+
+extern "C" int rf_search_grouped_profile(const rf_index_t* ix, const void* filter_dev,
+                                         const int32_t* group_codes_dev, int n_codes, const void* q_dev, int B,
+                                         int n_groups, int group_size, int64_t id_base, float* scores_dev,
+                                         int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                                         void* workspace_dev, size_t workspace_bytes, void* stream,
+                                         float* stage_ms_host) {
+  if (!stage_ms_host) {
+    rf_set_error("rf_search_grouped_profile: null stage buffer");
+    return RF_ERR_INVALID;
+  }
+  return grouped_impl("rf_search_grouped_profile", ix, filter_dev, group_codes_dev, n_codes, q_dev, B, n_groups,
+                      group_size, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                      workspace_bytes, (hipStream_t)stream, stage_ms_host);
 }
 
 extern "C" int rf_merge_shards(const double* exact_dev, const int64_t* ids_dev, int W, int B, int k,

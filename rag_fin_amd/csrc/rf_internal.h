@@ -226,6 +226,31 @@ int rf_launch_exhaustive(const rf_index* ix, const void* q, int B, int k, int64_
                          const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                          const double* after_s, const int64_t* after_r, hipStream_t st,
                          const uint32_t* mask = nullptr, const rf_band* band = nullptr);
+// grouped.hip (include/ragfin.h, "grouping search"): one code per row, the best n_groups groups by
+// their best group_size rows.  The sweeps write one partition of group maxima per workgroup.
+#define RF_GROUP_PARTS 512   // partitions (workgroups) of the group-maximum sweep, at most
+struct rf_group {
+  const int32_t* codes;  // device [n_rows]; a code outside [0, n_codes) = a row without a group
+  int n_codes;           // <= RF_GROUP_MAX_CODES
+  int n_groups;          // groups returned per query
+  int group_size;        // rows returned per group
+};
+struct rf_grouped_ws {
+  float* gpmax;          // [RF_GROUP_PARTS][64][n_codes] partition maxima per (query, code)
+  float* gthr;           // [64][RF_GROUP_MAX_CODES] emit threshold per (query, code)
+};
+// (eps: rf_launch_band_eps writes it ahead of the chain)
+int rf_launch_group_max(const rf_index* ix, const void* q, int B, int JB, const rf_group& g,
+                        const rf_workspace& ws, const rf_grouped_ws& gws, int* P_out, hipStream_t st,
+                        const rf_filter_view* filt);
+int rf_launch_group_threshold(int B, const rf_group& g, int P, const rf_workspace& ws,
+                              const rf_grouped_ws& gws, hipStream_t st);
+int rf_launch_group_emit(const rf_index* ix, const void* q, int B, int JB, const rf_group& g,
+                         const rf_workspace& ws, const rf_grouped_ws& gws, hipStream_t st,
+                         const rf_filter_view* filt);
+int rf_launch_merge_grouped(const rf_index* ix, const void* q, int B, const rf_group& g, int64_t id_base,
+                            const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
+                            uint32_t* flags, hipStream_t st);
 int rf_launch_merge_shards(const double* exact, const int64_t* ids, size_t shard_stride, int W, int B, int k,
                            float* scores_out, int64_t* ids_out, const uint32_t* flags_in, size_t flag_stride,
                            uint32_t* flags_out, hipStream_t st);

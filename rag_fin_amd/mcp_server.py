@@ -56,12 +56,20 @@ def _searcher():
 
 
 def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
-                   max_score: float | None = None):
+                   max_score: float | None = None, group_by: str | None = None, group_size: int = 1):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
-    min_score / max_score: optional score cut-offs, min_score < score <= max_score."""
+    min_score / max_score: optional score cut-offs, min_score < score <= max_score.
+    group_by: optional grouping field (period, chunk_type, statement_type): the best top_k groups,
+    each by its best group_size chunks, as one flat ranked list."""
     try:
-        if min_score is not None or max_score is not None:
+        if group_by is not None:
+            # grouped calls bypass the micro-batcher like filtered ones: one batch shares one grouping
+            kw = {"group_by": group_by, "group_size": group_size}
+            if min_score is not None or max_score is not None:
+                kw.update(min_score=min_score, max_score=max_score)   # (the store refuses the combination)
+            contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None, **kw)
+        elif min_score is not None or max_score is not None:
             # like filtered calls, banded calls bypass the micro-batcher: one batch shares one band
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
                                         min_score=min_score, max_score=max_score)

@@ -63,15 +63,24 @@ class VectorRAG:
                 param["params"]["range_filter"] = max_score
         return param
 
+    @staticmethod
+    def _group_args(group_by, group_size) -> dict:
+        """The store's grouping arguments; nothing when group_by is absent (the call of before)."""
+        return {} if group_by is None else {"group_by_field": group_by, "group_size": group_size}
+
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
-               max_score: float | None = None) -> list[dict]:
+               max_score: float | None = None, group_by: str | None = None, group_size: int = 1) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
-        the list may be shorter than top_k, or empty)."""
+        the list may be shorter than top_k, or empty).
+        group_by ("period", "chunk_type", "statement_type"): grouping search -- the best top_k
+        groups by that field, each by its best group_size chunks, as one flat list (group after
+        group, `rank` = the 1-based position in it); every dict carries the field already."""
         q = self._embed([query])
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
-                                         expr=expr, output_fields=OUTPUT_FIELDS)
+                                         expr=expr, output_fields=OUTPUT_FIELDS,
+                                         **self._group_args(group_by, group_size))
         return self._contexts(results[0])
 
     def _embed(self, texts):
@@ -84,15 +93,17 @@ class VectorRAG:
     retrieve = search  # BASELINE.json's "retrieve(query, k)" name for the same call
 
     def search_batch(self, queries: Sequence[str], top_k: int = 3, expr: str | None = None,
-                     min_score: float | None = None, max_score: float | None = None) -> list[list[dict]]:
+                     min_score: float | None = None, max_score: float | None = None,
+                     group_by: str | None = None, group_size: int = 1) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
-        is strictly one query per call); expr, min_score / max_score: one filter and one score
-        band for the whole batch."""
+        is strictly one query per call); expr, min_score / max_score, group_by / group_size: one
+        filter, one score band and one grouping for the whole batch."""
         if not queries:
             return []
         q = self._embed(list(queries))
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
-                                         expr=expr, output_fields=OUTPUT_FIELDS)
+                                         expr=expr, output_fields=OUTPUT_FIELDS,
+                                         **self._group_args(group_by, group_size))
         return [self._contexts(r) for r in results]
 
     # -- generation (out of scope; interface kept) -----------------------------------------

@@ -302,7 +302,9 @@ class ShardedCorpusStore(CorpusStore):
 
     # -- filters: not over shards (yet) -----------------------------------------------------------------
     def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
-               output_fields=None):
+               output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False):
+        if group_by_field is not None:
+            raise NotImplementedError("grouping search (group_by_field) is not implemented for the sharded store")
         if not filter_expr.is_empty(expr):
             raise NotImplementedError("filtered search is not implemented for the sharded store")
         if self._band_of(param) is not None:

@@ -87,6 +87,57 @@ def rerun_flagged(q16, k: int, id_base: int, flags, sq8: bool, filt, flat, exhau
     return bad, rows
 
 
+def mask_words(bits):
+    """bool [n] (device) -> the filter mask words int32 [ceil(n / 32)]: bit r of word b = row 32 b + r."""
+    torch = _torch()
+    n = bits.numel()
+    nblk = (n + 31) // 32
+    pad = torch.zeros(nblk * 32, dtype=torch.int64, device=bits.device)
+    pad[:n] = bits.to(torch.int64)
+    w = (pad.view(nblk, 32) << torch.arange(32, dtype=torch.int64, device=bits.device)).sum(1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def words_mask(words, n: int):
+    """The inverse of mask_words: int32 words (device) -> bool [n]."""
+    torch = _torch()
+    sh = torch.arange(32, dtype=torch.int64, device=words.device)
+    return (((words.to(torch.int64).unsqueeze(1) >> sh) & 1) != 0).flatten()[:n]
+
+
+def grouped_exhaustive(q16, group, pass_bits, exhaustive_masked):
+    """The flagged-query ladder of a grouping search, and the path of a dictionary
+    above RF_GROUP_MAX_CODES: per group code g that has a row, the exhaustive fp64 kernel with
+    k = group_size over "code == g AND the user's filter", then the groups ranked on their fp64
+    best (score desc, row asc).  Costs one fp64 pass per group, for the given queries only.
+      group = (codes int32 [n] on the device, n_codes, n_groups, group_size)
+      pass_bits: bool [n] on the device (the user's filter), or None
+      exhaustive_masked(q16, k, words) -> (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k]) over
+      the rows of the mask `words` (mask_words), ids WITHOUT an id base
+    -> (scores, rows, exact) in the padded slot form [B, n_groups * group_size], host numpy."""
+    torch = _torch()
+    codes, n_codes, n, s = group
+    B = q16.shape[0]
+    ok = (codes >= 0) & (codes < n_codes)
+    if pass_bits is not None:
+        ok = ok & pass_bits
+    per = []
+    for g in torch.unique(codes[ok]).tolist():
+        sc, ids, ex = exhaustive_masked(q16, s, mask_words(ok & (codes == g)))
+        per.append((sc.cpu().numpy(), ids.cpu().numpy(), ex.cpu().numpy()))
+    scores = np.full((B, n * s), -np.inf, dtype=np.float32)
+    rows = np.full((B, n * s), -1, dtype=np.int64)
+    exact = np.full((B, n * s), -np.inf, dtype=np.float64)
+    for b in range(B):
+        live = [p for p in per if p[1][b, 0] >= 0]
+        live.sort(key=lambda p: (-p[2][b, 0], p[1][b, 0]))
+        for j, (sc, ids, ex) in enumerate(live[:n]):
+            scores[b, j * s:(j + 1) * s] = sc[b]
+            rows[b, j * s:(j + 1) * s] = ids[b]
+            exact[b, j * s:(j + 1) * s] = ex[b]
+    return scores, rows, exact
+
+
 def _ptr(t):
     return c_void_p(t.data_ptr()) if t is not None else None
 
@@ -143,7 +194,10 @@ class GpuIndex:
             ws = self.lib.rf_search_workspace_bytes(self.handle)
             # one workspace serves both paths: the SQ8 one is the FLAT one plus its query area
             self.sq8_workspace_bytes = self.lib.rf_search_sq8_workspace_bytes(self.handle)
-            self.workspace = torch.zeros(max(ws, self.sq8_workspace_bytes), dtype=torch.uint8, device=self.device)
+            # ... and the grouped one is the SQ8 one plus its per-(query, group) tables
+            self.grouped_workspace_bytes = self.lib.rf_search_grouped_workspace_bytes(self.handle)
+            self.workspace = torch.zeros(max(ws, self.sq8_workspace_bytes, self.grouped_workspace_bytes),
+                                         dtype=torch.uint8, device=self.device)
             self.workspace_bytes = ws
         self._lock = threading.Lock()
         self._host_bufs = {}
@@ -308,8 +362,8 @@ class GpuIndex:
         """An extra search workspace: one per batch in flight when several streams
         search the same (immutable) index concurrently.  Large enough for SQ8 too."""
         torch = _torch()
-        return torch.zeros(max(self.workspace_bytes, self.sq8_workspace_bytes), dtype=torch.uint8,
-                           device=self.device)
+        return torch.zeros(max(self.workspace_bytes, self.sq8_workspace_bytes, self.grouped_workspace_bytes),
+                           dtype=torch.uint8, device=self.device)
 
     def _outputs(self, B: int, k: int, want_exact: bool = False, flags: bool = True, out=None):
         """The output tuple of a search: `out` when the caller brings one, else fresh device tensors
@@ -323,7 +377,7 @@ class GpuIndex:
                 torch.empty((B,), dtype=torch.int32, device=self.device) if flags else None)
 
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None):
+                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None, group=None):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
         hipStream_t of this device); no host sync.  Returns
         (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
@@ -333,11 +387,19 @@ class GpuIndex:
         sq8_workspace_bytes (new_workspace does).
         band: (radius, range_filter) -- rf_search_range: the best k rows with
         radius < fp64 score <= range_filter (within the passing rows with filt; not with sq8).
+        group: (codes int32 [size] on this device, n_codes, n_groups, group_size) -- rf_search_grouped:
+        the best n_groups groups of rows sharing a code, each by its best group_size rows (within
+        the passing rows with filt; not with sq8 or band).  k must be n_groups * group_size; the
+        outputs are in the padded slot form (group of rank j in slots [j s, (j + 1) s)).
         Takes no lock, with or without a workspace of the caller's: the benchmark and the sharded
         lanes call it on their own streams, and whoever shares the index's workspace serialises."""
         torch = _torch()
-        if sq8 and (filt is not None or band is not None):
-            raise ValueError("SQ8 search has no filtered and no range form")
+        if sq8 and (filt is not None or band is not None or group is not None):
+            raise ValueError("SQ8 search has no filtered, no range and no grouped form")
+        if group is not None:
+            if band is not None:
+                raise ValueError("grouping search has no range form")
+            self._check_group(group, k)
         if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
             raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
         if not q16.is_contiguous() or q16.device != self.device:
@@ -346,10 +408,14 @@ class GpuIndex:
         scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
         args = (_ptr(q16), B, k, id_base, _ptr(scores), _ptr(ids), _ptr(exact), _ptr(flags),
                 _ptr(workspace if workspace is not None else self.workspace),
+                self.grouped_workspace_bytes if group is not None else
                 self.sq8_workspace_bytes if sq8 else self.workspace_bytes,
                 stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
         with torch.cuda.device(self.device):
-            if band is not None:
+            if group is not None:
+                _lib.check(self.lib.rf_search_grouped(self.handle, _ptr(filt), _ptr(group[0]), int(group[1]),
+                                                      args[0], B, int(group[2]), int(group[3]), *args[3:]))
+            elif band is not None:
                 _lib.check(self.lib.rf_search_range(self.handle, _ptr(filt), *args[:4], float(band[0]), float(band[1]),
                                                     *args[4:]))
             elif sq8:
@@ -359,6 +425,32 @@ class GpuIndex:
             else:
                 _lib.check(self.lib.rf_search_filtered(self.handle, _ptr(filt), *args))
         return scores, ids, exact, flags
+
+    def _check_group(self, group, k: int) -> None:
+        torch = _torch()
+        codes, n_codes, n, s = group
+        if not torch.is_tensor(codes) or codes.dtype != torch.int32 or codes.dim() != 1 or \
+                codes.numel() != self.size or codes.device != self.device or not codes.is_contiguous():
+            raise ValueError(f"group codes must be a contiguous int32 [{self.size}] tensor on {self.device}")
+        if n < 1 or s < 1 or n * s > _lib.RF_MAX_K or n * s != k:
+            raise ValueError(f"grouping search: need n_groups, group_size >= 1 and k == n_groups * group_size <= "
+                             f"{_lib.RF_MAX_K} (got {n}, {s}, k = {k})")
+
+    def search_grouped_profile(self, q16, group, filt=None):
+        """rf_search_grouped_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
+        torch = _torch()
+        q16 = q16.to(self.device).contiguous()
+        B = min(q16.shape[0], _lib.RF_QCHUNK)
+        k = int(group[2]) * int(group[3])
+        self._check_group(group, k)
+        scores, ids, _, flags = self._outputs(B, k)
+        ms = (ctypes.c_float * 4)()
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_search_grouped_profile(
+                self.handle, _ptr(filt), _ptr(group[0]), int(group[1]), _ptr(q16), B, int(group[2]), int(group[3]), 0,
+                _ptr(scores), _ptr(ids), None, _ptr(flags), _ptr(self.workspace), self.grouped_workspace_bytes,
+                _lib.current_stream_ptr(), ms))
+        return dict(zip(("group_max", "threshold", "emit", "merge"), ms))
 
     def enqueue_search(self, q_ptr: int, B: int, k: int, id_base: int, scores_ptr: int, ids_ptr: int,
                        exact_ptr: int, flags_ptr: int, workspace_ptr: int, stream_ptr):
@@ -442,22 +534,61 @@ class GpuIndex:
         out = (torch.cat(scores, 1)[:, :k].contiguous(), torch.cat(ids, 1)[:, :k].contiguous())
         return out + (torch.cat(exacts, 1)[:, :k].contiguous(),) if want_exact else out
 
-    def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt, band=None):
-        """rerun_flagged with this index's tiers (the band of a range search rides in them).  The
-        caller holds the lock."""
+    def _grouped_exhaustive(self, q16, group, id_base: int, want_exact: bool, filt):
+        """grouped_exhaustive with this index's exhaustive kernel -> device tensors.  The caller
+        holds the lock."""
+        torch = _torch()
+        n_rows = self.size
+        nblk = (n_rows + 31) // 32
+        bits = None if filt is None else words_mask(filt[16:16 + 4 * nblk].view(torch.int32), n_rows)
+
+        def masked(q, k, words):
+            buf = torch.empty(self.lib.rf_filter_bytes(n_rows), dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.rf_filter_from_mask(_ptr(words), n_rows, _ptr(buf), _lib.current_stream_ptr()))
+            return self._exhaustive(q, k, 0, True, buf)
+
+        scores, rows, exact = grouped_exhaustive(q16.to(self.device).contiguous(), group, bits, masked)
+        rows = np.where(rows >= 0, rows + id_base, rows)
+        return (torch.from_numpy(scores).to(self.device), torch.from_numpy(rows).to(self.device),
+                torch.from_numpy(exact).to(self.device) if want_exact else None)
+
+    def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt, band=None,
+                       group=None):
+        """rerun_flagged with this index's tiers (the band of a range search rides in them; a
+        grouping search re-runs group by group).  The caller holds the lock."""
+        if group is not None:
+            return rerun_flagged(q16, k, id_base, flags, False, filt, None,
+                                 lambda q, k, base, f: self._grouped_exhaustive(q, group, base, want_exact, f))
         return rerun_flagged(q16, k, id_base, flags, sq8, filt,
                              lambda q, k, base: self.search_raw(q, k, base, want_exact, band=band),
                              lambda q, k, base, f: self._exhaustive(q, k, base, want_exact, f, band=band))
 
+    def _grouped_first_pass(self, q16, k: int, id_base: int, want_exact: bool, filt, group, out=None):
+        """search_raw(group=...), or -- a dictionary above RF_GROUP_MAX_CODES -- outputs whose every
+        query is flagged, so that the ladder answers the whole batch."""
+        if int(group[1]) <= _lib.RF_GROUP_MAX_CODES:
+            return self.search_raw(q16, k, id_base, want_exact, out=out, filt=filt, group=group)
+        self._check_group(group, k)
+        res = self._outputs(q16.shape[0], k, want_exact, out=out)
+        res[3].fill_(_lib.RF_FLAG_CAND_OVERFLOW)
+        return res
+
     def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False,
-               band=None):
+               band=None, group=None):
         """rf_search, then the flagged-query ladder (rerun_flagged) for any query the fused path
         could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first.
         band: (radius, range_filter) -- rf_search_range, flagged queries through the exhaustive
-        band kernel."""
+        band kernel.  group: as in search_raw -- rf_search_grouped, flagged queries (and every query
+        of a dictionary above RF_GROUP_MAX_CODES) group by group through the exhaustive kernel."""
         with self._lock:
-            scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8, band=band)
-            bad, rows = self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt, band)
+            if group is not None:
+                if sq8 or band is not None:
+                    raise ValueError("grouping search has no SQ8 and no range form")
+                scores, ids, exact, flags = self._grouped_first_pass(q16, k, id_base, want_exact, filt, group)
+            else:
+                scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8, band=band)
+            bad, rows = self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt, band, group)
             if rows is not None:
                 for dst, src in zip((scores, ids, exact), rows):
                     if dst is not None:
@@ -466,12 +597,23 @@ class GpuIndex:
 
     ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
 
-    def search_host(self, q16, k: int, filt=None, sq8: bool = False, band=None):
+    def search_host(self, q16, k: int, filt=None, sq8: bool = False, band=None, group=None):
         """search() whose results land on the host with ONE synchronisation: scores, ids and
         flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
         ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows.
-        sq8: rf_search_sq8 first, as in search().  band: (radius, range_filter), as in search()."""
+        sq8: rf_search_sq8 first, as in search().  band: (radius, range_filter), as in search().
+        group: as in search(); k = n_groups * group_size, the padded slot form."""
         torch = _torch()
+        if group is not None:
+            if sq8 or band is not None:
+                raise ValueError("grouping search has no SQ8 and no range form")
+            with self._lock:
+                scores, ids, _, flags = self._grouped_first_pass(q16, k, 0, False, filt, group)
+                bad, rows = self._rerun_flagged(q16, k, 0, False, flags, False, filt, None, group)
+                if rows is not None:
+                    scores[bad] = rows[0]
+                    ids[bad] = rows[1]
+                return scores.cpu().numpy(), ids.cpu().numpy()
         with self._lock:
             B = q16.shape[0]
             key = (B, k)
@@ -975,8 +1117,24 @@ class CorpusStore:
         with self._rw.read():
             return self._search_rows(data, limit, filt, band)
 
-    def _search_rows(self, data, limit: int, filt=None, band=None):
+    GROUP_BY_FIELDS = filter_expr.VARCHAR_FIELDS   # period, chunk_type, statement_type ("id": the plain search)
+
+    def _group_codes(self, field: str):
+        """(codes int32 [n] on the device, n_codes) of a group-by field, from the device mirror."""
+        with self._filter_lock:
+            if self._dcols is None:
+                self._dcols = _DeviceColumns(self.index.device)
+            self._dcols.sync(self.columns, self.num_entities)
+            return self._dcols.codes[field].contiguous(), len(self._dcols.dicts[field])
+
+    def _search_rows(self, data, limit: int, filt=None, band=None, group=None):
         q16 = self._prepare_queries(data)
+        if group is not None:
+            # (field, group_size): the padded [B, limit * group_size] block; never SQ8, never paged
+            field, gsize = group
+            kw = {} if filt is None else {"filt": filt}
+            codes, n_codes = self._group_codes(field)
+            return self.index.search_host(q16, limit * gsize, group=(codes, n_codes, limit, gsize), **kw)
         kw = {} if filt is None else {"filt": filt}
         if band is not None:
             kw["band"] = band
@@ -991,17 +1149,46 @@ class CorpusStore:
         return scores[:, :kk], rows[:, :kk]
 
     def search(self, data, anns_field: str = "embedding", param: dict | None = None,
-               limit: int = 3, expr=None, output_fields: Iterable[str] | None = None):
+               limit: int = 3, expr=None, output_fields: Iterable[str] | None = None,
+               group_by_field: str | None = None, group_size: int = 1, strict_group_size: bool = False):
         """pymilvus-shaped search: one list of hits per query vector, best first.
+        group_by_field ("period", "chunk_type", "statement_type"; "id" is the plain search): the best
+        `limit` GROUPS of rows sharing that field's value, each by its best min(group_size, rows of
+        the group) rows.  One flat hit list per query: group after group in group rank order (a
+        group ranks by its best row), the rows of a group best first; every hit carries the group
+        value, hit.entity.get(group_by_field).  With expr, groups are formed among the passing
+        rows.  limit * group_size <= 64; not together with radius / range_filter;
+        strict_group_size is accepted and ignored (the search is exact: every group already
+        returns as many rows as it has, up to group_size).
         param["params"] may hold the range-search bounds `radius` and, optionally, `range_filter`:
         the best `limit` hits with radius < score <= range_filter (a query may return []); the
         comparison is made in fp64 on the fp64 ranking score, so a hit's fp32 `score` may equal
         float32(radius).  range_filter without radius, a bound that is no real number, NaN or
         radius >= range_filter raises ValueError.  Other keys of params (nprobe, ...) are ignored."""
         with self._rw.read():   # the rows handed back are marshalled below: no delete in between
-            return self._search(data, anns_field, param, limit, expr, output_fields)
+            if group_by_field is None:
+                return self._search(data, anns_field, param, limit, expr, output_fields)
+            return self._search(data, anns_field, param, limit, expr, output_fields,
+                                self._check_group_by(group_by_field, group_size, limit, param))
 
-    def _search(self, data, anns_field, param, limit, expr, output_fields):
+    def _check_group_by(self, field, group_size, limit, param):
+        """-> (field, group_size), or None for "id" (every row its own group: the plain search)."""
+        if field != "id" and field not in self.GROUP_BY_FIELDS:
+            raise ValueError(f"group_by_field {field!r}: only {', '.join(self.GROUP_BY_FIELDS)} (or id) can be grouped by")
+        if isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or group_size < 1:
+            raise ValueError(f"group_size must be an integer >= 1, got {group_size!r}")
+        if limit < 1:
+            raise ValueError("limit must be >= 1")
+        if self._band_of(param) is not None:
+            raise ValueError("group_by_field cannot be combined with range search (radius / range_filter)")
+        if field == "id":
+            return None
+        if limit * group_size > _lib.RF_MAX_K:
+            raise ValueError(f"grouping search: limit * group_size = {limit * group_size} > {_lib.RF_MAX_K} "
+                             "(grouped results are not paged)")
+        return field, int(group_size)
+
+    def _search(self, data, anns_field, param, limit, expr, output_fields, group=None):
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         metric = (param or {}).get("metric_type", self.metric_type).upper()
@@ -1013,7 +1200,13 @@ class CorpusStore:
                 raise KeyError(f"unknown output field {f!r}")
         band = self._band_of(param)
         kw = {} if band is None else {"band": band}
-        if filter_expr.is_empty(expr):
+        if group is not None:
+            # the padded [B, limit * group_size] block; short and missing groups leave -1 slots
+            filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
+            scores, rows = self._search_rows(data, limit, filt, group=group)
+            if group[0] not in fields:
+                fields = fields + [group[0]]
+        elif filter_expr.is_empty(expr):
             scores, rows = self.search_rows(data, limit, **kw)
         else:
             scores, rows = self.search_rows(data, limit, filt=self.build_filter(expr), **kw)
@@ -1023,6 +1216,8 @@ class CorpusStore:
             for j in range(rows.shape[1]):
                 r = int(rows[b, j])
                 if r < 0:
+                    if group is not None:
+                        continue
                     break
                 hits.append(Hit(r, self.columns["id"][r], float(scores[b, j]),
                                 {f: self.columns[f][r] for f in fields}))

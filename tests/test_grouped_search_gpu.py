@@ -1,0 +1,416 @@
+"""Grouping search on the GPU: rf_search_grouped and everything above it against a CPU oracle.
+
+The oracle (here, because oracle/ holds none): osearch.exact_scores for the full fp64 score matrix;
+masked rows and rows whose code lies outside [0, n_codes) removed; per query the rows ordered by
+(-score, row); a walk down that order that keeps the first s rows of each code and the first n codes
+met; laid out in the padded slot form (group of rank j in slots [j s, (j + 1) s), -inf / -1 where a
+group is short or missing).  `grouped_oracle` computes the same thing group-wise (top s of each
+code, codes ordered by their best row) and `test_the_oracle_is_the_walk` checks it against the
+literal walk.  Bar: ids, ranks and fp64 scores bit-identical, fp32 scores == float32(oracle), flags
+0 on the raw path unless the case is about overflow."""
+import os
+
+import numpy as np
+import pytest
+
+from oracle import encoder as oenc, search as osearch
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+
+_CACHE = {}
+
+
+def scored(n, d, B, cseed=1234, qseed=5678):
+    """(corpus fp16, queries fp16, oracle score matrix f64 [B, n]); one large case kept at a time."""
+    key = (n, d, B, cseed, qseed)
+    if key not in _CACHE:
+        _CACHE.clear()
+        c16 = osearch.synth_unit_rows(n, d, cseed)
+        q16 = osearch.synth_unit_rows(B, d, qseed)
+        _CACHE[key] = (c16, q16, osearch.exact_scores(q16, c16))
+    return _CACHE[key]
+
+
+def make_index(c16, device):
+    import torch
+    from rag_fin_amd.store import GpuIndex
+    ix = GpuIndex(c16.shape[1], max(c16.shape[0], 1), device)
+    ix.add(torch.from_numpy(c16).to(device))
+    return ix
+
+
+def coding(n, G, kind):
+    """interleaved: row mod G; contiguous: G equal runs."""
+    r = np.arange(n)
+    return (r % G if kind == "interleaved" else np.minimum(r * G // n, G - 1)).astype(np.int32)
+
+
+def grouped_oracle(S, codes, n_codes, n, s, mask=None):
+    B, N = S.shape
+    ok = (codes >= 0) & (codes < n_codes)
+    if mask is not None:
+        ok &= mask
+    per = []
+    for g in np.unique(codes[ok]):
+        rows = np.flatnonzero(ok & (codes == g))                  # ascending: local order == row order
+        gs, gi = osearch.topk_from_scores(S[:, rows], s)
+        per.append((gs, np.where(gi >= 0, rows[np.maximum(gi, 0)], -1)))
+    es = np.full((B, n * s), -np.inf)
+    ei = np.full((B, n * s), -1, dtype=np.int64)
+    for b in range(B):
+        order = sorted(range(len(per)), key=lambda j: (-per[j][0][b, 0], per[j][1][b, 0]))
+        for j, g in enumerate(order[:n]):
+            es[b, j * s:(j + 1) * s] = per[g][0][b]
+            ei[b, j * s:(j + 1) * s] = per[g][1][b]
+    return es, ei
+
+
+def walk_oracle(S, codes, n_codes, n, s, mask=None):
+    """The literal walk (slow: small cases only)."""
+    B, N = S.shape
+    es = np.full((B, n * s), -np.inf)
+    ei = np.full((B, n * s), -1, dtype=np.int64)
+    for b in range(B):
+        slot_of, taken = {}, {}
+        for r in np.lexsort((np.arange(N), -S[b])):
+            c = int(codes[r])
+            if c < 0 or c >= n_codes or (mask is not None and not mask[r]):
+                continue
+            if c not in slot_of:
+                if len(slot_of) == n:
+                    continue
+                slot_of[c], taken[c] = len(slot_of), 0
+            if taken[c] < s:
+                o = slot_of[c] * s + taken[c]
+                es[b, o], ei[b, o] = S[b, r], r
+                taken[c] += 1
+    return es, ei
+
+
+def check_equal(scores, ids, exact, es, ei):
+    ids = ids.cpu().numpy()
+    assert np.array_equal(ids, ei), f"ids differ at {np.argwhere(ids != ei)[:5]}"
+    assert np.array_equal(exact.cpu().numpy(), es)
+    assert np.array_equal(scores.cpu().numpy(), es.astype(np.float32))
+
+
+def check_grouped(ix, q16, S, codes, n_codes, n, s, device, mask=None, filt=None, raw=True, both=True):
+    import torch
+    q = torch.from_numpy(q16).to(device)
+    cd = torch.from_numpy(codes).to(device)
+    es, ei = grouped_oracle(S, codes, n_codes, n, s, mask)
+    group = (cd, n_codes, n, s)
+    if raw:
+        scores, ids, exact, flags = ix.search_raw(q, n * s, want_exact=True, filt=filt, group=group)
+        torch.cuda.synchronize()
+        assert int(flags.abs().sum()) == 0, f"flags set: {np.flatnonzero(flags.cpu().numpy())[:8]}"
+        check_equal(scores, ids, exact, es, ei)
+    if both or not raw:
+        scores, ids, exact = ix.search(q, n * s, want_exact=True, filt=filt, group=group)
+        check_equal(scores, ids, exact, es, ei)
+    return es, ei
+
+
+def mask_filter(ix, mask, device):
+    """A filter buffer from a host bool mask (rf_filter_from_mask)."""
+    import torch
+    from rag_fin_amd import _lib
+    from rag_fin_amd.store import mask_words, _ptr
+    n = mask.size
+    words = mask_words(torch.from_numpy(mask).to(device))
+    buf = torch.empty(ix.lib.rf_filter_bytes(n), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(ix.lib.rf_filter_from_mask(_ptr(words), n, _ptr(buf), _lib.current_stream_ptr()))
+    return buf
+
+
+def test_the_oracle_is_the_walk():
+    rng = np.random.default_rng(3)
+    S = rng.standard_normal((5, 300)).round(1)            # rounded: plenty of exact ties
+    codes = rng.integers(-1, 7, 300).astype(np.int32)     # -1 and 6 are out of range for n_codes = 6
+    mask = rng.random(300) < 0.7
+    for n, s in ((3, 1), (4, 3), (8, 2), (2, 60)):
+        for m in (None, mask):
+            a, b = grouped_oracle(S, codes, 6, n, s, m), walk_oracle(S, codes, 6, n, s, m)
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+
+
+# ---- parity on random unit corpora ------------------------------------------------------------------
+CONFIGS = [(4, 4, 1), (4, 10, 1), (16, 8, 1), (16, 8, 4), (64, 10, 1), (64, 16, 4)]
+SHAPES = [(n, d, B) for n, d in ((100_000, 384), (20_000, 768)) for B in (1, 64, 100)]
+
+
+def assert_not_vacuous(S, es, ei, n, s):
+    """On the oracle alone: the grouped ids differ from the plain top-(n s) ids for >= 1/4 of the queries."""
+    ps, pi = osearch.topk_from_scores(S, n * s)
+    differ = sum(set(pi[b].tolist()) != set(ei[b][ei[b] >= 0].tolist()) for b in range(S.shape[0]))
+    print(f"grouped != plain top-{n * s} for {differ} of {S.shape[0]} queries")
+    assert differ * 4 >= S.shape[0], (differ, S.shape[0])
+
+
+@pytest.mark.parametrize("kind", ["interleaved", "contiguous"])
+@pytest.mark.parametrize("G,n,s", CONFIGS)
+@pytest.mark.parametrize("N,d,B", SHAPES)
+def test_grouped_equals_oracle(gpu_device, N, d, B, G, n, s, kind):
+    c16, q16, S = scored(N, d, B)
+    codes = coding(N, G, kind)
+    key = ("ix", N, d)
+    if key not in _CACHE:
+        _CACHE[key] = make_index(c16, gpu_device)
+    es, ei = check_grouped(_CACHE[key], q16, S, codes, G, n, s, gpu_device)
+    if B == 64 and n <= G:
+        assert_not_vacuous(S, es, ei, n, s)
+
+
+def test_small_corpus(gpu_device):
+    c16, q16, S = scored(5_000, 384, 64)
+    ix = make_index(c16, gpu_device)
+    for G, n, s in ((4, 4, 1), (16, 8, 4), (64, 10, 1)):
+        for kind in ("interleaved", "contiguous"):
+            check_grouped(ix, q16, S, coding(5_000, G, kind), G, n, s, gpu_device)
+
+
+# ---- skew: the case a per-query threshold cannot serve ---------------------------------------------
+def test_skew_fills_no_candidate_list(gpu_device):
+    import torch
+    from rag_fin_amd import _lib
+    N, B = 100_000, 64
+    c16, q16, S = scored(N, 384, B)
+    rng = np.random.default_rng(11)
+    codes = np.where(rng.random(N) < 0.9, 0, 1 + rng.integers(0, 15, N)).astype(np.int32)
+    ix = make_index(c16, gpu_device)
+    es, ei = check_grouped(ix, q16, S, codes, 16, 8, 1, gpu_device, both=False)
+    assert_not_vacuous(S, es, ei, 8, 1)
+    off = ix.lib.rf_debug_grouped_counters_offset()
+    cnt = ix.workspace[off:off + 64 * 8 * 4].view(torch.int32).cpu().numpy().reshape(64, 8)
+    print("candidates per query: max", int(cnt.sum(1).max()), "largest list", int(cnt.max()))
+    assert cnt.max() <= 2048 and cnt.sum(1).min() >= 8
+    check_grouped(ix, q16, S, codes, 16, 8, 1, gpu_device, raw=False)
+    assert _lib.RF_GROUP_MAX_CODES >= 64
+
+
+# ---- with a filter ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["interleaved", "contiguous"])
+def test_grouped_with_filters(gpu_device, kind):
+    N, B, G = 100_000, 64, 16
+    c16, q16, S = scored(N, 384, B)
+    ix = make_index(c16, gpu_device)
+    codes = coding(N, G, kind)
+    r = np.arange(N)
+    masks = {"round robin 1/8": r % 8 == 3,                       # (interleaved coding: only odd codes pass)
+             "contiguous 1/8": (r >= N // 2) & (r < N // 2 + N // 8),
+             "one group removed": codes != 5,
+             "nothing passes": np.zeros(N, dtype=bool)}
+    for name, mask in masks.items():
+        filt = mask_filter(ix, mask, gpu_device)
+        es, ei = check_grouped(ix, q16, S, codes, G, 8, 2, gpu_device, mask=mask, filt=filt)
+        got = ei[ei >= 0]
+        assert mask[got].all(), name
+        if name == "one group removed":
+            assert not (codes[got] == 5).any() and (ei >= 0).all()
+        if name == "nothing passes":
+            assert (ei == -1).all() and np.isneginf(es).all()
+
+
+# ---- short groups, missing groups, rows without a group -------------------------------------------
+def test_short_and_missing_groups(gpu_device):
+    N, B = 50_000, 64
+    c16, q16, S = scored(N, 384, B)
+    ix = make_index(c16, gpu_device)
+    s = 4
+    codes = (np.arange(N) % 3).astype(np.int32)            # codes 0..2 are large
+    codes[777] = 3                                          # one row
+    codes[[5, 30_001, 44_444]] = 4                          # group_size - 1 rows
+    codes[[9, 10, 11]] = 99                                 # out of range: never returned
+    codes[[12, 13]] = -7
+    # code 5 has no row; n_codes = 7 and limit 8: fewer distinct codes than the limit
+    es, ei = check_grouped(ix, q16, S, codes, 7, 8, s, gpu_device)
+    assert (ei[:, 5 * s:] == -1).all() and (ei[:, :5 * s:s] >= 0).all()
+    got = ei[ei >= 0]
+    assert not np.isin(got, [9, 10, 11, 12, 13]).any()
+    assert ((ei >= 0).sum(1) == 3 * s + 1 + 3).all()
+    # a limit below the number of groups drops the weakest groups whole
+    check_grouped(ix, q16, S, codes, 7, 2, s, gpu_device)
+
+
+# ---- ties and the ladder ---------------------------------------------------------------------------
+def test_identical_corpus_goes_through_the_ladder(gpu_device):
+    import torch
+    N, B = 20_000, 4
+    row = osearch.synth_unit_rows(1, 384, 7)
+    c16 = np.repeat(row, N, axis=0)
+    q16 = osearch.synth_unit_rows(B, 384, 8)
+    S = osearch.exact_scores(q16, c16)
+    ix = make_index(c16, gpu_device)
+    codes = np.full(N, 3, dtype=np.int32)
+    codes[100:] = (np.arange(N - 100) % 3).astype(np.int32)      # code 3 first, then 0, 1, 2 by their first rows
+    q = torch.from_numpy(q16).to(gpu_device)
+    cd = torch.from_numpy(codes).to(gpu_device)
+    flags = ix.search_raw(q, 8, group=(cd, 4, 4, 2))[3]
+    torch.cuda.synchronize()
+    assert (flags.cpu().numpy() != 0).all()
+    es, ei = check_grouped(ix, q16, S, codes, 4, 4, 2, gpu_device, raw=False)
+    assert ei[0].tolist() == [0, 1, 100, 103, 101, 104, 102, 105]
+
+
+def test_engineered_ties_between_group_bests(gpu_device):
+    N, B = 30_000, 16
+    c16 = osearch.synth_unit_rows(N, 384, 21).copy()
+    q16 = osearch.synth_unit_rows(B, 384, 22)
+    codes = coding(N, 8, "interleaved")
+    S0 = osearch.exact_scores(q16, c16)
+    # the best row of query 0 is copied into the rows of two other groups: three groups tie on their best
+    best = int(np.argmax(S0[0]))
+    targets = [r for r in (best + 1, best + 2) if r < N] or [best - 1, best - 2]
+    for r in targets:
+        c16[r] = c16[best]
+    S = osearch.exact_scores(q16, c16)
+    assert S[0, targets[0]] == S[0, best] == S[0, targets[1]]
+    ix = make_index(c16, gpu_device)
+    es, ei = check_grouped(ix, q16, S, codes, 8, 4, 2, gpu_device)
+    assert ei[0, 0::2][:3].tolist() == sorted([best] + targets)
+
+
+def test_a_dictionary_above_the_cap_is_answered_by_the_ladder(gpu_device):
+    import torch
+    from rag_fin_amd import _lib
+    N, B, G = 20_000, 8, 100
+    c16, q16, S = scored(N, 384, B)
+    ix = make_index(c16, gpu_device)
+    codes = coding(N, G, "interleaved")
+    q = torch.from_numpy(q16).to(gpu_device)
+    with pytest.raises(_lib.RagfinError) as e:
+        ix.search_raw(q, 5, group=(torch.from_numpy(codes).to(gpu_device), G, 5, 1))
+    assert e.value.code == -2
+    check_grouped(ix, q16, S, codes, G, 5, 1, gpu_device, raw=False)
+
+
+# ---- hipGraph ------------------------------------------------------------------------------------------
+def test_graph_capture_and_replay(gpu_device):
+    import torch
+    c16, q16, S = scored(100_000, 384, 64)
+    ix = make_index(c16, gpu_device)
+    codes = coding(100_000, 16, "interleaved")
+    q = torch.from_numpy(q16).to(gpu_device)
+    group = (torch.from_numpy(codes).to(gpu_device), 16, 8, 2)
+    eager = ix.search_raw(q, 16, want_exact=True, group=group)
+    torch.cuda.synchronize()
+    out = ix._outputs(64, 16, want_exact=True)
+    ws = ix.new_workspace()
+    g = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream(gpu_device)
+    side.wait_stream(torch.cuda.current_stream(gpu_device))
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(g, stream=side):
+            ix.search_raw(q, 16, want_exact=True, out=out, workspace=ws, group=group)
+    torch.cuda.current_stream(gpu_device).wait_stream(side)
+    for _ in range(2):
+        for t in out:
+            t.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        for x, y in zip(eager, out):
+            assert torch.equal(x, y)
+    check_equal(out[0], out[1], out[2], *grouped_oracle(S, codes, 16, 8, 2))
+
+
+# ---- CorpusStore: marshalling, expr, delete / upsert, SQ8 ---------------------------------------------
+def _store(c16, device, periods, ctypes_):
+    import torch
+    from rag_fin_amd.store import CorpusStore
+    n = c16.shape[0]
+    st = CorpusStore("grp", dim=c16.shape[1], capacity=n, device=device, metric_type="IP")
+    st.add(list(range(n)), [f"t{i}" for i in range(n)], torch.from_numpy(c16).to(device), periods, ctypes_,
+           ["s"] * n, [float(i % 10) for i in range(n)])
+    return st
+
+
+def _expect_hits(S, ids, values, limit, s, mask=None):
+    """Flat (id, score, group value) lists from the oracle; `values`: the group value per row."""
+    uniq = {v: i for i, v in enumerate(dict.fromkeys(values))}
+    codes = np.array([uniq[v] for v in values], dtype=np.int32)
+    es, ei = grouped_oracle(S, codes, len(uniq), limit, s, mask)
+    return [[(ids[r], np.float32(es[b, j]), values[r]) for j, r in enumerate(ei[b]) if r >= 0]
+            for b in range(S.shape[0])]
+
+
+def test_store_grouping_with_expr_delete_upsert_and_sq8(gpu_device):
+    import torch
+    n, d, B = 20_000, 384, 8
+    c16 = osearch.synth_unit_rows(n, d, 1234)
+    q16 = osearch.synth_unit_rows(B, d, 5678)
+    S = osearch.exact_scores(q16, c16)
+    periods = [f"Q{1 + i % 4}_FY{2023 + (i // 4) % 2}" for i in range(n)]
+    ctypes_ = [("summary", "profitability_analysis", "notes")[min(i * 3 // n, 2)] for i in range(n)]
+    st = _store(c16, gpu_device, periods, ctypes_)
+    q = torch.from_numpy(q16).to(gpu_device)
+    ids = list(range(n))
+
+    def hits(res, field):
+        return [[(h.id, np.float32(h.score), h.entity.get(field)) for h in row] for row in res]
+
+    res = st.search(q, "embedding", {"metric_type": "IP"}, limit=5, group_by_field="period", group_size=3,
+                    output_fields=["text"])
+    assert hits(res, "period") == _expect_hits(S, ids, periods, 5, 3)
+    assert res[0][0].entity.get("text") == f"t{res[0][0].id}"
+    res = st.search(q, "embedding", {"metric_type": "IP"}, limit=3, group_by_field="chunk_type", group_size=2,
+                    expr="primary_value < 2", strict_group_size=True)
+    mask = np.array([i % 10 < 2 for i in range(n)])
+    assert hits(res, "chunk_type") == _expect_hits(S, ids, ctypes_, 3, 2, mask)
+    # "id": every row its own group -- the plain search
+    assert [[h.id for h in row] for row in st.search(q, "embedding", {"metric_type": "IP"}, limit=5, group_by_field="id")] == \
+           [[h.id for h in row] for row in st.search(q, "embedding", {"metric_type": "IP"}, limit=5)]
+    # SQ8 collection: answers from the fp16 rows, stays SQ8
+    st.create_index("embedding", {"index_type": "SQ8", "metric_type": "IP"})
+    res = st.search(q, "embedding", {"metric_type": "IP"}, limit=5, group_by_field="period", group_size=3)
+    assert hits(res, "period") == _expect_hits(S, ids, periods, 5, 3) and st.index_type == "SQ8"
+    st.drop_index()
+    # delete one whole period and every second row, upsert 100 rows into a NEW period
+    st.delete('period == "Q1_FY2023"')
+    st.delete("primary_value == 7")
+    keep = [i for i in range(n) if periods[i] != "Q1_FY2023" and i % 10 != 7]
+    up = keep[:100]
+    st.upsert([up, [f"u{i}" for i in up], torch.from_numpy(c16[up]).to(gpu_device), ["Q9_FY2030"] * 100,
+               [ctypes_[i] for i in up], ["s"] * 100, [1.0] * 100])
+    order = keep[100:] + up
+    per2 = [periods[i] for i in keep[100:]] + ["Q9_FY2030"] * 100
+    res = st.search(q, "embedding", {"metric_type": "IP"}, limit=8, group_by_field="period", group_size=2)
+    want = _expect_hits(S[:, order], order, per2, 8, 2)
+    assert hits(res, "period") == want
+    assert all(h[2] != "Q1_FY2023" for row in want for h in row) and any(h[2] == "Q9_FY2030" for row in want for h in row)
+
+
+# ---- end to end on the golden chunks -------------------------------------------------------------------
+def test_one_hit_of_every_period_on_the_golden_chunks(gpu_device):
+    from rag_fin_amd import chunker
+    from rag_fin_amd.embedder import Embedder
+    from rag_fin_amd.rag import VectorRAG
+    from rag_fin_amd.service import ingest
+    from rag_fin_amd.store import CorpusStore
+    from rag_fin_amd.tokenizer import WordPieceTokenizer
+    questions = ["What was ICICI's Q1 net profit and profitability?", "How did net profit develop over the year?",
+                 "Which segment contributed the most revenue?"]
+    chunks = chunker.build_all_chunks(os.path.join(GOLD, "extract_data"))
+    probe = WordPieceTokenizer(["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"])
+    words = sorted({w for t in [c["text"] for c in chunks] + questions for w in probe.basic_tokens(t)})
+    vocab = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + words + \
+            [ch for ch in "abcdefghijklmnopqrstuvwxyz0123456789"] + ["##" + ch for ch in "abcdefghijklmnopqrstuvwxyz0123456789"]
+    tok = WordPieceTokenizer(list(dict.fromkeys(vocab)))
+    cfg = dict(oenc.MINILM_L6, vocab_size=len(tok.vocab))
+    emb = Embedder(oenc.random_weights(cfg, 42), cfg, tokenizer=tok, device=gpu_device)
+    store = CorpusStore("fin_chunks", dim=384, capacity=16, device=gpu_device)
+    assert ingest(store, emb, chunks) == 16
+    rag = VectorRAG("no-key", "fin_chunks", embedder=emb, store=store)
+    periods = store.columns["period"]
+    assert len(set(periods)) == 4
+    c16 = store.index.get_rows(np.arange(16)).cpu().numpy()
+    for question in questions:
+        q16 = store._prepare_queries(emb.encode([question]))
+        S = osearch.exact_scores(q16.cpu().numpy(), c16)
+        want = _expect_hits(S, store.columns["id"], periods, 4, 1)[0]
+        got = rag.search(question, top_k=4, group_by="period")
+        assert [c["rank"] for c in got] == [1, 2, 3, 4]
+        assert sorted(c["period"] for c in got) == sorted(set(periods))
+        assert [c["period"] for c in got] == [w[2] for w in want]
+        assert [np.float32(c["score"]) for c in got] == [w[1] for w in want]
