@@ -218,6 +218,21 @@ static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
   return RF_OK;
 }
 
+// Time the stages of one sweep: run(ev) records `marks` events, one before the first stage and one
+// after each; the marks - 1 stage times in ms go to stage_ms.
+template <class F>
+static int time_stages(int marks, float* stage_ms, F run) {
+  hipEvent_t ev[6];
+  for (int i = 0; i < marks; ++i) RF_HIP(hipEventCreate(&ev[i]));
+  const int rc = run(ev);
+  if (rc == RF_OK) {
+    RF_HIP(hipEventSynchronize(ev[marks - 1]));
+    for (int i = 0; i + 1 < marks; ++i) RF_HIP(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
+  }
+  for (int i = 0; i < marks; ++i) (void)hipEventDestroy(ev[i]);
+  return rc;
+}
+
 // One sweep of nb <= RF_QWIDE queries: (SQ8: quantize the queries ->) sample -> threshold -> emit ->
 // merge.  ev: nullable; one event before the first stage and one after each (5, with SQ8 6).
 static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, int nb, int k, int64_t id_base,
@@ -270,16 +285,9 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
                       });
   bool wide;
   const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
-  const int stages = sq ? 5 : 4;
-  hipEvent_t ev[6];
-  for (int i = 0; i <= stages; ++i) RF_HIP(hipEventCreate(&ev[i]));
-  int rc = sweep(ix, rf_variant{filt, sq, wide, band}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
-  if (rc == RF_OK) {
-    RF_HIP(hipEventSynchronize(ev[stages]));
-    for (int i = 0; i < stages; ++i) RF_HIP(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
-  }
-  for (int i = 0; i <= stages; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
+  return time_stages(sq ? 6 : 5, stage_ms, [&](hipEvent_t* ev) {
+    return sweep(ix, rf_variant{filt, sq, wide, band}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
+  });
 }
 
 extern "C" int rf_search(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
@@ -546,15 +554,9 @@ static int grouped_impl(const char* fn, const rf_index_t* ix, const void* filter
                       [&](int, int nb, bool, const _Float16* qc, const rf_out& oc) {
                         return sweep_grouped(ix, filt, g, qc, nb, id_base, ws, gws, oc, st, nullptr);
                       });
-  hipEvent_t ev[5];
-  for (int i = 0; i < 5; ++i) RF_HIP(hipEventCreate(&ev[i]));
-  rc = sweep_grouped(ix, filt, g, (const _Float16*)q_dev, B < RF_QCHUNK ? B : RF_QCHUNK, id_base, ws, gws, o, st, ev);
-  if (rc == RF_OK) {
-    RF_HIP(hipEventSynchronize(ev[4]));
-    for (int i = 0; i < 4; ++i) RF_HIP(hipEventElapsedTime(&stage_ms[i], ev[i], ev[i + 1]));
-  }
-  for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]);
-  return rc;
+  return time_stages(5, stage_ms, [&](hipEvent_t* ev) {
+    return sweep_grouped(ix, filt, g, (const _Float16*)q_dev, B < RF_QCHUNK ? B : RF_QCHUNK, id_base, ws, gws, o, st, ev);
+  });
 }
 
 extern "C" int rf_search_grouped(const rf_index_t* ix, const void* filter_dev, const int32_t* group_codes_dev,

@@ -16,6 +16,9 @@
 //                         their best row
 // Why the answer is exact: DESIGN.md 4.4d.
 #include "rf_internal.h"
+#include <algorithm>
+
+#include "merge_common.h"
 #include "scan_common.h"
 
 enum { GMODE_MAX = 0, GMODE_EMIT = 1 };
@@ -41,66 +44,12 @@ struct GroupParams {
   uint32_t n_blocks;
 };
 
-// The MFMA chain of one block with the register ring re-armed for the next (scan.hip, block_step).
-template <int KS, int R, int JB, bool LAST>
-__device__ __forceinline__ void group_mfma(u32x4 (&ring)[R], const uint4* cur, const uint4* nxt,
-                                           const u32x4* smemQ, int lane, f32x16 (&acc)[JB]) {
-  static_assert(KS % R == 0, "ring must divide the block");
-  asm volatile("" ::: "memory");
-#pragma unroll
-  for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[jb][i] = 0.f;
-#pragma unroll
-  for (int kk = 0; kk < KS; ++kk) {
-    const half8 a = __builtin_bit_cast(half8, ring[kk % R]);
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb) {
-      const half8 b = __builtin_bit_cast(half8, smemQ[(jb * KS + kk) * 64 + lane]);
-      acc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[jb], 0, 0, 0);
-    }
-    if (kk + R < KS) {
-      ring[kk % R] = ld_frag(cur + (kk + R) * 64);
-    } else if (!LAST) {
-      ring[kk % R] = ld_frag(nxt + (kk + R - KS) * 64);
-    }
-  }
-}
-
 // gmax[idx] = max(gmax[idx], x) on the order-preserving encoding; the LDS atomic is issued only
 // on improvement (a plain read first).  A NaN stays out.
 __device__ __forceinline__ void gmax_update(uint32_t* tab, uint32_t idx, float x) {
   if (x == x) {
     const uint32_t o = rf_f2ord(x);
     if (o > tab[idx]) atomicMax(&tab[idx], o);
-  }
-}
-
-// The append loop of emit_slow (scan_common.h) for a hit mask the caller built (bit jb*16+i).
-template <int JB, class P>
-__device__ __forceinline__ void group_append(const f32x16 (&acc)[JB], uint32_t bits, uint32_t row0, int lane,
-                                             EmitState& es, const P& p) {
-  const int h = lane >> 5;
-  unsigned long long mask;
-  while ((mask = __ballot(bits != 0u)) != 0ull) {
-    const bool pass = bits != 0u;
-    const int b = __ffs((int)bits) - 1;
-    float s = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s = (b == jb * 16 + i) ? acc[jb][i] : s;
-    const uint32_t n = (uint32_t)__popcll(mask);
-    if (es.cnt + n > SCAP) emit_flush(es, p, lane);
-    if (pass) {
-      const int i = b & 15;
-      const uint32_t slot = es.cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      es.s_row[slot] = row0 + acc_row(i, h);
-      es.s_score[slot] = s;
-      es.s_q[slot] = (uint32_t)((b >> 4) * 32 + (lane & 31));
-    }
-    es.cnt += n;
-    bits &= bits - 1u;
   }
 }
 
@@ -161,7 +110,7 @@ __device__ __forceinline__ void group_block(const f32x16 (&acc)[JB], int cv, uin
           bits |= (ci >= 0 && acc[jb][i] >= thr[at + jb * 32]) ? (1u << (jb * 16 + i)) : 0u;
       }
     }
-    if (__ballot(bits != 0u) != 0ull) group_append<JB>(acc, bits, row0, lane, es, p);
+    if (__ballot(bits != 0u) != 0ull) emit_append<JB>(acc, bits, row0, lane, es, [&] { emit_flush(es, p, lane); });
   }
 }
 
@@ -175,20 +124,11 @@ __global__ void __launch_bounds__(WAVES * 64) k_group_sweep(GroupParams p) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int dim = KS * 16;
 
-  EmitState es;
-  es.cnt = 0;
-  es.q_base = 0;
-  es.s_row = stage + wave * SCAP;
-  es.s_score = (float*)(stage + WAVES * SCAP) + wave * SCAP;
-  es.s_q = stage + 2 * WAVES * SCAP + wave * SCAP;
+  EmitState es = emit_state(stage, wave, WAVES, SCAP);
 
   uint32_t n_work = p.n_work;
-  if constexpr (FILTER) {   // a header built for another row count passes nothing
-    n_work = p.hdr[0] == p.n_rows ? p.hdr[2] : 0u;
-    n_work = n_work < p.n_blocks ? n_work : p.n_blocks;
-  }
+  if constexpr (FILTER) n_work = filter_pass_blocks(p.hdr, p.n_rows, p.n_blocks);
   const uint32_t W = gridDim.x * WAVES;
   const uint32_t gw = blockIdx.x * WAVES + wave;
   const uint32_t cnt = n_work > gw ? (n_work - gw + W - 1) / W : 0u;
@@ -209,15 +149,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_group_sweep(GroupParams p) {
 #pragma unroll
     for (int s = 0; s < R; ++s) ring[s] = ld_frag(src + s * 64);
   }
-  for (int idx = tid; idx < JB * KS * 64; idx += WAVES * 64) {
-    const int l = idx & 63;
-    const int kk = (idx >> 6) % KS;
-    const int jb = idx / (64 * KS);
-    const int qi = jb * 32 + (l & 31);
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (qi < p.B) v = *(const u32x4*)(p.q + (size_t)qi * dim + kk * 16 + (l >> 5) * 8);
-    smemQ[idx] = v;
-  }
+  stage_queries<KS, JB, WAVES>(smemQ, p.q, p.B);
   for (int idx = tid; idx < GTAB; idx += WAVES * 64) {
     // GMAX: 0 is below the encoding of every float; GEMIT: the (query, code) thresholds, transposed
     if (MODE == GMODE_MAX) tab[idx] = 0u;
@@ -244,14 +176,14 @@ __global__ void __launch_bounds__(WAVES * 64) k_group_sweep(GroupParams p) {
       const int cv = code_of(b);
       const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
       const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
-      group_mfma<KS, R, JB, false>(ring, cur, nxt, smemQ, lane, acc);
+      mfma_block<KS, R, JB, false>(ring, cur, nxt, smemQ, lane, acc);
       group_block<JB, MODE>(acc, cv, b * 32u, lane, tab, es, p);
       b = bn;
     }
     {
       const int cv = code_of(b);
       const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
-      group_mfma<KS, R, JB, true>(ring, cur, cur, smemQ, lane, acc);
+      mfma_block<KS, R, JB, true>(ring, cur, cur, smemQ, lane, acc);
       group_block<JB, MODE>(acc, cv, b * 32u, lane, tab, es, p);
     }
   }
@@ -272,11 +204,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_group_sweep(GroupParams p) {
 }
 
 // ---- per-(query, group) thresholds ------------------------------------------------------------
-__device__ __forceinline__ float gwave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
 // One workgroup of four waves per query slot; wave w takes the codes g = w, w + 4, ...
 // M_g = the maximum over the P partitions (the exact maximum MFMA score of the group: the sweep
 // was complete), m_{g,s} = the s-th largest partition maximum (-inf with fewer than s finite ones).
@@ -310,7 +237,7 @@ __global__ void __launch_bounds__(256) k_group_threshold(int B, int n_codes, int
         float m = v[0];
 #pragma unroll
         for (int i = 1; i < GTHR_V; ++i) m = fmaxf(m, v[i]);
-        const float wm = gwave_max(m);
+        const float wm = wave_max_xor(m);
         if (r == 0) M = wm;
         kth = wm;
         if (wm == -INFINITY) break;
@@ -339,7 +266,7 @@ __global__ void __launch_bounds__(256) k_group_threshold(int B, int n_codes, int
       const float mine = lane < n_codes ? sM[lane] : -INFINITY;
       float x = mine, Mn = -INFINITY;
       for (int r = 0; r < n_groups; ++r) {
-        const float wm = gwave_max(x);
+        const float wm = wave_max_xor(x);
         Mn = wm;
         if (wm == -INFINITY) break;
         const unsigned long long who = __ballot(x == wm);
@@ -361,25 +288,15 @@ __global__ void __launch_bounds__(256) k_group_threshold(int B, int n_codes, int
 //   3. R = the candidates at or above their group's cut; fp64 chains of the contract for R;
 //   4. per group the top s by (exact desc, row asc), groups ranked by their best row; slot
 //      j * s + i receives row i of the group of rank j, everything else is padded.
-#define GM_THREADS 256
-#define GM_STAGE_ROWS 32
 #define GM_NONE 0xFFFFFFFFu
 
-__device__ __forceinline__ unsigned long long gcand_key(uint2 e) {
-  return ((unsigned long long)rf_f2ord(__builtin_bit_cast(float, e.y)) << 32) |
-         (unsigned long long)(0xFFFFFFFFu - e.x);
-}
-__device__ __forceinline__ bool granks_before(double s1, uint32_t r1, double s2, uint32_t r2) {
-  return (s1 > s2) || (s1 == s2 && r1 < r2);
-}
-
 static size_t gmerge_lds_bytes(int dim) {
-  return (size_t)RF_CAND_CAP * 8 + (size_t)GM_STAGE_ROWS * (dim * 2 + 16) + RF_RESCORE_CAP * 8 +
+  return (size_t)RF_CAND_CAP * 8 + (size_t)MERGE_STAGE_ROWS * (dim * 2 + 16) + RF_RESCORE_CAP * 8 +
          RF_GROUP_MAX_CODES * 8 + (size_t)3 * RF_RESCORE_CAP * 4 + (size_t)4 * RF_GROUP_MAX_CODES * 4 + 16 +
          (size_t)dim * 2 + RF_CAND_CAP;
 }
 
-__global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
+__global__ void __launch_bounds__(MERGE_THREADS) k_merge_grouped(
     const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles,
     const int32_t* __restrict__ codes, int n_codes, int n_groups, int gsize, int64_t id_base,
     const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand, uint32_t cap,
@@ -389,7 +306,7 @@ __global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
   const int srow_stride = 2 * KS + 1;
   unsigned long long* skeys = (unsigned long long*)lds;                 // [RF_CAND_CAP]
   uint4* srows = (uint4*)(skeys + RF_CAND_CAP);                         // [32][2 KS + 1]
-  double* r_exact = (double*)(srows + GM_STAGE_ROWS * srow_stride);     // [RESCORE_CAP]
+  double* r_exact = (double*)(srows + MERGE_STAGE_ROWS * srow_stride);     // [RESCORE_CAP]
   double* g_bs = r_exact + RF_RESCORE_CAP;                              // [codes] best fp64 score of the group
   uint32_t* r_row = (uint32_t*)(g_bs + RF_GROUP_MAX_CODES);             // [RESCORE_CAP]
   uint32_t* r_code = r_row + RF_RESCORE_CAP;
@@ -408,36 +325,18 @@ __global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
   const uint32_t s = (uint32_t)gsize;
   const int K = n_groups * gsize;
   bool bad_row = false;
-  uint32_t off[RF_CAND_SHARDS + 1];
-  uint32_t fl = 0u;
-  off[0] = 0u;
-#pragma unroll
-  for (int t = 0; t < RF_CAND_SHARDS; ++t) {
-    const uint32_t n = cand_cnt[qi * RF_CAND_SHARDS + t];
-    if (n > cap) fl = RF_FLAG_CAND_OVERFLOW;
-    off[t + 1] = off[t] + (n < cap ? n : cap);
-  }
-  const uint32_t total = off[RF_CAND_SHARDS];
-  if (total > RF_CAND_CAP) fl = RF_FLAG_CAND_OVERFLOW;
-  const uint32_t c = total < RF_CAND_CAP ? total : RF_CAND_CAP;
-  const uint2* lists = cand + (size_t)qi * RF_CAND_SHARDS * cap;
+  CandLists L;
+  uint32_t fl = cand_lists(L, cand_cnt, cand, cap, qi);
+  const uint32_t c = L.c;
   const float eps2 = 2.f * eps_in[qi];
 
   // ---- 1: gather -----------------------------------------------------------------------------
-  for (uint32_t g = tid; g < c; g += GM_THREADS) {
-    int t = 0;
-#pragma unroll
-    for (int u = 1; u < RF_CAND_SHARDS; ++u) t += g >= off[u] ? 1 : 0;
-    uint2 e = lists[(size_t)t * cap + (g - off[t])];
-    int code = -1;
-    if (e.x >= n_rows) {   // cannot come from the sweep (see k_merge): never gathered, flagged
-      e.x = 0u;
-      e.y = 0xFF800000u;
-      bad_row = true;
-    } else {
-      code = codes[e.x];
-    }
-    skeys[g] = gcand_key(e);
+  for (uint32_t g = tid; g < c; g += MERGE_THREADS) {
+    bool bad = false;
+    const uint2 e = cand_at(L, g, n_rows, bad);
+    const int code = bad ? -1 : codes[e.x];   // a bad row has no group: it takes part in nothing
+    bad_row |= bad;
+    skeys[g] = cand_key(e);
     scode[g] = (uint32_t)code < (uint32_t)n_codes ? (unsigned char)code : (unsigned char)0xFF;
   }
   if (tid < RF_GROUP_MAX_CODES) {
@@ -447,28 +346,28 @@ __global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
     filled[tid] = 0u;
   }
   if (tid == 0) *r_cnt = 0u;
-  for (int d = tid; d < dim; d += GM_THREADS) qh[d] = q[(size_t)qi * dim + d];
+  for (int d = tid; d < dim; d += MERGE_THREADS) qh[d] = q[(size_t)qi * dim + d];
   __syncthreads();
 
   // ---- 2: the s-th largest candidate of every group --------------------------------------------
-  for (uint32_t g = tid; g < c; g += GM_THREADS) {
+  for (uint32_t g = tid; g < c; g += MERGE_THREADS) {
     const unsigned long long key = skeys[g];
     const unsigned char code = scode[g];
     if (code == 0xFF) continue;
     uint32_t rank = 0u;
     for (uint32_t j = 0; j < c; ++j) rank += (scode[j] == code && skeys[j] > key) ? 1u : 0u;
-    if (rank == s - 1u) g_cut[code] = rf_ord2f((uint32_t)(key >> 32)) - eps2;   // one candidate per group has this rank
+    if (rank == s - 1u) g_cut[code] = key_score(key) - eps2;   // one candidate per group has this rank
   }
   __syncthreads();
   // ---- 3: R, then the fp64 chains ----------------------------------------------------------------
-  for (uint32_t g = tid; g < c; g += GM_THREADS) {
+  for (uint32_t g = tid; g < c; g += MERGE_THREADS) {
     const unsigned long long key = skeys[g];
     const unsigned char code = scode[g];
     if (code == 0xFF) continue;
-    if (rf_ord2f((uint32_t)(key >> 32)) >= g_cut[code]) {
+    if (key_score(key) >= g_cut[code]) {
       const uint32_t slot = atomicAdd(r_cnt, 1u);
       if (slot < RF_RESCORE_CAP) {
-        r_row[slot] = 0xFFFFFFFFu - (uint32_t)key;
+        r_row[slot] = key_row(key);
         r_code[slot] = code;
       }
     }
@@ -479,36 +378,14 @@ __global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
     fl |= RF_FLAG_TIE_OVERFLOW;
     R = RF_RESCORE_CAP;
   }
-  const int chunks = 2 * KS;
-  for (uint32_t base = 0; base < R; base += GM_STAGE_ROWS) {
-    const uint32_t nb = (R - base) < GM_STAGE_ROWS ? (R - base) : GM_STAGE_ROWS;
-    for (uint32_t idx = tid; idx < nb * (uint32_t)chunks; idx += GM_THREADS) {
-      const uint32_t r = idx / chunks, ch = idx % chunks;
-      srows[r * srow_stride + ch] = tiles[rf_chunk_index((int64_t)r_row[base + r], (int)ch, KS)];
-    }
-    __syncthreads();
-    {
-      // 8 lanes per row: lane j owns chain j (dims j, j + 8, ...), combined by the contract's tree
-      const uint32_t r = (uint32_t)tid >> 3;
-      const int j = tid & 7;
-      const _Float16* row = (const _Float16*)(srows + (r < nb ? r : 0) * srow_stride);
-      double a = 0.0;
-#pragma unroll 8
-      for (int ch = 0; ch < chunks; ++ch) a = fma((double)qh[8 * ch + j], (double)row[8 * ch + j], a);
-      a += __shfl_xor(a, 1);
-      a += __shfl_xor(a, 2);
-      a += __shfl_xor(a, 4);
-      if (j == 0 && r < nb) r_exact[base + r] = a;
-    }
-    __syncthreads();
-  }
+  rescore_rows(r_row, R, tiles, KS, qh, srows, r_exact);
 
   // ---- 4: top s per group, groups by their best row ----------------------------------------------
-  for (uint32_t i = tid; i < R; i += GM_THREADS) {
+  for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
     const double si = r_exact[i];
     const uint32_t ri = r_row[i], ci = r_code[i];
     uint32_t rank = 0u;
-    for (uint32_t j = 0; j < R; ++j) rank += (r_code[j] == ci && granks_before(r_exact[j], r_row[j], si, ri)) ? 1u : 0u;
+    for (uint32_t j = 0; j < R; ++j) rank += (r_code[j] == ci && ranks_before(r_exact[j], r_row[j], si, ri)) ? 1u : 0u;
     r_in[i] = rank;
     if (rank == 0u) {
       g_bs[ci] = si;
@@ -519,11 +396,11 @@ __global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
   if (tid < RF_GROUP_MAX_CODES && g_br[tid] != GM_NONE) {
     uint32_t rank = 0u;
     for (int g = 0; g < RF_GROUP_MAX_CODES; ++g)
-      rank += (g_br[g] != GM_NONE && granks_before(g_bs[g], g_br[g], g_bs[tid], g_br[tid])) ? 1u : 0u;
+      rank += (g_br[g] != GM_NONE && ranks_before(g_bs[g], g_br[g], g_bs[tid], g_br[tid])) ? 1u : 0u;
     g_rank[tid] = rank;
   }
   __syncthreads();
-  for (uint32_t i = tid; i < R; i += GM_THREADS) {
+  for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
     const uint32_t gr = g_rank[r_code[i]];
     if (r_in[i] < s && gr < (uint32_t)n_groups) {
       const uint32_t slot = gr * s + r_in[i];
@@ -536,7 +413,7 @@ __global__ void __launch_bounds__(GM_THREADS) k_merge_grouped(
     }
   }
   __syncthreads();
-  for (int j = tid; j < K; j += GM_THREADS) {
+  for (int j = tid; j < K; j += MERGE_THREADS) {
     if (filled[j]) continue;
     const size_t o = (size_t)qi * K + j;
     scores[o] = -INFINITY;
@@ -587,19 +464,6 @@ static int dispatch_group_sweep(int KS, int JB, bool filtered, const GroupParams
   return RF_ERR_UNSUPPORTED;
 }
 
-// One partition per workgroup: the grid of the emit sweep (CUs x workgroups per CU), at most
-// RF_GROUP_PARTS, at most one wave per block.
-static int group_grid(const rf_index* ix) {
-  const int KS = ix->KS;
-  const int WAVES = KS >= 48 ? 8 : 4;
-  const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
-  int grid = ix->num_cus * (KS >= 48 ? 1 : 2);
-  const uint32_t need = (nblk + WAVES - 1) / WAVES;
-  if ((uint32_t)grid > need) grid = (int)need;
-  if (grid > RF_GROUP_PARTS) grid = RF_GROUP_PARTS;
-  return grid < 1 ? 1 : grid;
-}
-
 static GroupParams group_params(const rf_index* ix, const void* q, int B, const rf_group& g,
                                 const rf_workspace& ws, const rf_grouped_ws& gws, const rf_filter_view* filt) {
   GroupParams p{};
@@ -627,7 +491,8 @@ static GroupParams group_params(const rf_index* ix, const void* q, int B, const 
 int rf_launch_group_max(const rf_index* ix, const void* q, int B, int JB, const rf_group& g,
                         const rf_workspace& ws, const rf_grouped_ws& gws, int* P_out, hipStream_t st,
                         const rf_filter_view* filt) {
-  const int grid = group_grid(ix);
+  // one partition per workgroup: the emit grid of the dim (no knob), at most RF_GROUP_PARTS
+  const int grid = std::min(rf_emit_grid(ix, 0), RF_GROUP_PARTS);
   *P_out = grid;
   return dispatch_group_sweep<GMODE_MAX>(ix->KS, JB, filt != nullptr, group_params(ix, q, B, g, ws, gws, filt), grid, st);
 }
@@ -644,7 +509,7 @@ int rf_launch_group_emit(const rf_index* ix, const void* q, int B, int JB, const
                          const rf_workspace& ws, const rf_grouped_ws& gws, hipStream_t st,
                          const rf_filter_view* filt) {
   return dispatch_group_sweep<GMODE_EMIT>(ix->KS, JB, filt != nullptr, group_params(ix, q, B, g, ws, gws, filt),
-                                          group_grid(ix), st);
+                                          std::min(rf_emit_grid(ix, 0), RF_GROUP_PARTS), st);
 }
 
 int rf_launch_merge_grouped(const rf_index* ix, const void* q, int B, const rf_group& g, int64_t id_base,
@@ -653,7 +518,7 @@ int rf_launch_merge_grouped(const rf_index* ix, const void* q, int B, const rf_g
   const size_t lds = gmerge_lds_bytes(ix->dim);
   static rf_lds_attr attr;
   RF_HIP(rf_ensure_lds(attr, (const void*)k_merge_grouped, lds));
-  hipLaunchKernelGGL(k_merge_grouped, dim3(B), dim3(GM_THREADS), lds, st, (const _Float16*)q, ix->dim, ix->KS,
+  hipLaunchKernelGGL(k_merge_grouped, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim, ix->KS,
                      ix->tiles, g.codes, g.n_codes, g.n_groups, g.group_size, id_base, ws.cand_cnt, ws.cand,
                      (uint32_t)RF_SHARD_CAP, ws.eps, scores, ids, exact, flags, (uint32_t)ix->size);
   RF_HIP(hipGetLastError());

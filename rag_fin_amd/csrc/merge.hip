@@ -11,6 +11,7 @@
 // The MFMA scan only nominates candidates; every returned score comes from the
 // fp64 chain, so ids and ranks are bit-reproducible on the CPU.
 #include "rf_internal.h"
+#include "merge_common.h"
 #include "sq8.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -71,11 +72,6 @@ __device__ __forceinline__ double exact_dot(const _Float16* __restrict__ qrow,
     for (int j = 0; j < 8; ++j) p[j] = fma((double)qh[j], (double)ch[j], p[j]);
   }
   return tree8(p);
-}
-
-// (score desc, row asc): is (s1, r1) ranked strictly before (s2, r2)?
-__device__ __forceinline__ bool ranks_before(double s1, int64_t r1, double s2, int64_t r2) {
-  return (s1 > s2) || (s1 == s2 && r1 < r2);
 }
 
 // ---- emit threshold -------------------------------------------------------------
@@ -278,22 +274,8 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
 //   3. stage the rows of R in LDS with all 256 threads (one HBM latency instead
 //      of one per 16-byte chunk), then one thread per row runs the fp64 chain;
 //   4. rank R by (exact desc, row asc) and write the top-k.
-#define MERGE_THREADS 256
 #define MERGE_PER_THREAD (RF_CAND_CAP / MERGE_THREADS)
 #define MERGE_RANK_MAX 1024
-#define MERGE_STAGE_ROWS 32
-
-__device__ __forceinline__ unsigned long long cand_key(uint2 e) {
-  // larger key <=> (higher score, then lower row)
-  return ((unsigned long long)rf_f2ord(__builtin_bit_cast(float, e.y)) << 32) |
-         (unsigned long long)(0xFFFFFFFFu - e.x);
-}
-__device__ __forceinline__ float key_score(unsigned long long key) {
-  return rf_ord2f((uint32_t)(key >> 32));
-}
-__device__ __forceinline__ uint32_t key_row(unsigned long long key) {
-  return 0xFFFFFFFFu - (uint32_t)key;
-}
 
 static size_t merge_lds_bytes(int dim) {
   return (size_t)MERGE_RANK_MAX * 8 + (MERGE_THREADS / 64) * RF_MAX_K * 8 + RF_RESCORE_CAP * 8 +
@@ -323,45 +305,17 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   uint32_t* n_band = r_cnt + 3;                                               // BAND: rows of R inside the band
   double* qd = (double*)(r_cnt + 16);                                         // [dim]
   uint4* srows = (uint4*)(qd + dim);                                          // [32][2 KS + 1]
-  const int srow_stride = 2 * KS + 1;
 
   const int qi = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   bool bad_row = false;
-  // candidate lists of this query: RF_CAND_SHARDS lists of up to `cap` entries;
-  // global candidate index g -> (list s, entry g - off[s])
-  uint32_t off[RF_CAND_SHARDS + 1];
-  uint32_t fl = 0u;
-  off[0] = 0u;
-#pragma unroll
-  for (int s = 0; s < RF_CAND_SHARDS; ++s) {
-    const uint32_t n = cand_cnt[qi * RF_CAND_SHARDS + s];
-    if (n > cap) fl = RF_FLAG_CAND_OVERFLOW;
-    off[s + 1] = off[s] + (n < cap ? n : cap);
-  }
-  const uint32_t total = off[RF_CAND_SHARDS];
-  if (total > RF_CAND_CAP) fl = RF_FLAG_CAND_OVERFLOW;
-  const uint32_t c = total < RF_CAND_CAP ? total : RF_CAND_CAP;
+  CandLists L;
+  uint32_t fl = cand_lists(L, cand_cnt, cand, cap, qi);
+  const uint32_t c = L.c;
   const int kk = (uint32_t)k < c ? k : (int)c;
   bool have_cut = kk > 0 && (uint32_t)k <= c;  // fewer than k candidates: rescore all
-  const uint2* lists = cand + (size_t)qi * RF_CAND_SHARDS * cap;
-  auto cand_at = [&](uint32_t g) -> uint2 {
-    int s = 0;
-#pragma unroll
-    for (int t = 1; t < RF_CAND_SHARDS; ++t) s += g >= off[t] ? 1 : 0;
-    uint2 e = lists[(size_t)s * cap + (g - off[s])];
-    // a row id past the corpus cannot come from the sweep (k_threshold zeroes the counters of
-    // every search); should one appear (a caller sharing one workspace between concurrent
-    // searches), never let it reach the row gather -- make it the worst candidate and flag
-    if (e.x >= n_rows) {
-      e.x = 0u;
-      e.y = 0xFF800000u;  // -inf
-      bad_row = true;
-    }
-    return e;
-  };
   const float eps2 = 2.f * eps_in[qi];
   // BAND: a key takes part in the k-th selection only if its score is <= hs
   const float hs = BAND ? rf_band_floor(bd.hi - (double)eps_in[qi]) : INFINITY;
@@ -385,7 +339,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
 #pragma unroll
     for (int i = 0; i < MERGE_RANK_MAX / MERGE_THREADS; ++i) {
       const uint32_t idx = (uint32_t)tid + MERGE_THREADS * i;
-      key[i] = idx < c ? cand_key(cand_at(idx)) : 0ull;
+      key[i] = idx < c ? cand_key(cand_at(L, idx, n_rows, bad_row)) : 0ull;
       skeys[idx] = (BAND && !(key_score(key[i]) <= hs)) ? 0ull : key[i];  // zero padding never outranks a real key
     }
     if (BAND) {
@@ -430,7 +384,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
 #pragma unroll
     for (int i = 0; i < MERGE_PER_THREAD; ++i) {
       const uint32_t idx = (uint32_t)tid + MERGE_THREADS * i;
-      key[i] = idx < c ? cand_key(cand_at(idx)) : 0ull;
+      key[i] = idx < c ? cand_key(cand_at(L, idx, n_rows, bad_row)) : 0ull;
       if (BAND && !(key_score(key[i]) <= hs)) key[i] = 0ull;
     }
     if (BAND) {
@@ -479,7 +433,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     // ---- pass 2b: compact R from global ------------------------------------------
     const float cut = *t_cut;
     for (uint32_t idx = tid; idx < c; idx += MERGE_THREADS) {
-      const uint2 e = cand_at(idx);
+      const uint2 e = cand_at(L, idx, n_rows, bad_row);
       if (__builtin_bit_cast(float, e.y) >= cut) {
         const uint32_t slot = atomicAdd(r_cnt, 1u);
         if (slot < RF_RESCORE_CAP) r_row[slot] = e.x;
@@ -494,31 +448,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   }
 
   // ---- pass 3: exact fp64 scores, rows staged through LDS ---------------------------
-  // 8 lanes per candidate: lane j owns chain j (dims j, j+8, ...); xor-shuffle tree.
-  const int chunks = 2 * KS;
-  const _Float16* qh = (const _Float16*)qd;  // query row as fp16 in LDS
-  for (uint32_t base = 0; base < R; base += MERGE_STAGE_ROWS) {
-    const uint32_t nb = (R - base) < MERGE_STAGE_ROWS ? (R - base) : MERGE_STAGE_ROWS;
-    for (uint32_t idx = tid; idx < nb * (uint32_t)chunks; idx += MERGE_THREADS) {
-      const uint32_t r = idx / chunks, ch = idx % chunks;
-      srows[r * srow_stride + ch] = tiles[rf_chunk_index((int64_t)r_row[base + r], (int)ch, KS)];
-    }
-    __syncthreads();
-    {
-      const uint32_t r = (uint32_t)tid >> 3;   // 32 candidates x 8 lanes = 256 threads
-      const int j = tid & 7;
-      const _Float16* row = (const _Float16*)(srows + (r < nb ? r : 0) * srow_stride);
-      double acc = 0.0;
-#pragma unroll 8
-      for (int ch = 0; ch < chunks; ++ch)
-        acc = fma((double)qh[8 * ch + j], (double)row[8 * ch + j], acc);
-      acc += __shfl_xor(acc, 1);
-      acc += __shfl_xor(acc, 2);
-      acc += __shfl_xor(acc, 4);
-      if (j == 0 && r < nb) r_exact[base + r] = acc;
-    }
-    __syncthreads();
-  }
+  rescore_rows(r_row, R, tiles, KS, (const _Float16*)qd, srows, r_exact);   // (qd: the query row as fp16)
 
   // ---- pass 4: rank by (exact desc, row asc) and write --------------------------------
   uint32_t n_in = R;

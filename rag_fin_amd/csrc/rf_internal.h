@@ -190,6 +190,17 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                    hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr,
                    const rf_band* band = nullptr);
+// Shape of the 64-query sweeps (scan.hip, grouped.hip): waves per workgroup by dim, and the emit
+// grid = CUs x workgroups per CU (0 = the default of the dim), at most one wave per 32-row block.
+static inline int rf_waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
+static inline int rf_emit_grid(const rf_index* ix, int wgs_per_cu) {
+  const int WAVES = rf_waves_per_wg(ix->KS);
+  const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
+  int grid = ix->num_cus * (wgs_per_cu > 0 ? wgs_per_cu : (ix->KS >= 48 ? 1 : 2));
+  const uint32_t need = (nblk + WAVES - 1) / WAVES;
+  if ((uint32_t)grid > need) grid = (int)need;
+  return grid < 1 ? 1 : grid;
+}
 int rf_launch_debug_scores(const rf_index* ix, const void* q, int B, int64_t n, float* out,
                            hipStream_t st);
 int rf_scan_supported_dim(int dim);

@@ -74,31 +74,8 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
                                            float (&m1)[JB], uint32_t (&r1)[JB], float (&m2)[JB],
                                            EmitState& es, const ScanParams& p,
                                            uint32_t mword = 0u, const float* tc = nullptr) {
-  static_assert(KS % R == 0, "ring must divide the block");
-  // keep the query-fragment LDS reads inside the block: hoisted out of the
-  // block loop they would pin JB*KS*4 registers and spill
-  asm volatile("" ::: "memory");
   f32x16 acc[JB];
-#pragma unroll
-  for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[jb][i] = 0.f;
-
-#pragma unroll
-  for (int kk = 0; kk < KS; ++kk) {
-    const half8 a = __builtin_bit_cast(half8, ring[kk % R]);
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb) {
-      const half8 b = __builtin_bit_cast(half8, smemQ[(jb * KS + kk) * 64 + lane]);
-      acc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[jb], 0, 0, 0);
-    }
-    // re-arm this ring slot with the fragment R steps ahead
-    if (kk + R < KS) {
-      ring[kk % R] = ld_frag(cur + (kk + R) * 64);
-    } else if (!LAST) {
-      ring[kk % R] = ld_frag(nxt + (kk + R - KS) * 64);
-    }
-  }
+  mfma_block<KS, R, JB, LAST>(ring, cur, nxt, smemQ, lane, acc);
 
   if (MODE != MODE_EMIT) {
     if (FILTER) {
@@ -158,7 +135,6 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int dim = KS * 16;
 
   float th[JB];
   float pm[JB];
@@ -180,26 +156,13 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
     m2[jb] = -INFINITY;
     th[jb] = (MODE == MODE_EMIT) ? p.thr[jb * 32 + (lane & 31)] : 0.f;
   }
-  EmitState es;
-  es.cnt = 0;
-  es.q_base = 0;
-  if (MODE == MODE_EMIT) {
-    es.s_row = (uint32_t*)tail + wave * SCAP;
-    es.s_score = (float*)((uint32_t*)tail + WAVES * SCAP) + wave * SCAP;
-    es.s_q = (uint32_t*)tail + 2 * WAVES * SCAP + wave * SCAP;
-  } else {
-    es.s_row = nullptr;
-    es.s_score = nullptr;
-    es.s_q = nullptr;
-  }
+  EmitState es = emit_state((uint32_t*)tail, wave, WAVES, SCAP);  // (touched by MODE_EMIT only)
 
   // work items w = gw, gw + W, ...  (one item = one 32-row block)
   const uint32_t W = gridDim.x * WAVES;
   const uint32_t gw = blockIdx.x * WAVES + wave;
   if constexpr (FILTER) {
-    // pass blocks of the filter (a header built for another row count passes nothing)
-    uint32_t npb = p.hdr[0] == p.n_rows ? p.hdr[2] : 0u;
-    npb = npb < p.n_blocks ? npb : p.n_blocks;
+    const uint32_t npb = filter_pass_blocks(p.hdr, p.n_rows, p.n_blocks);
     if (MODE == MODE_SAMPLE) {  // ~1/16 of the pass blocks, spread evenly (rf_launch_sample)
       uint32_t n = npb / 16;
       n = n < p.work_lo ? p.work_lo : n;
@@ -247,18 +210,7 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   }
   // (the corpus stream starts BEFORE the queries are staged: the first HBM round trip runs
   // under the staging loop and its barrier instead of after them)
-  // stage the queries in B-fragment order: lane (j = l & 31, h = l >> 5) of
-  // fragment (jb, kk) holds q[32 jb + j][16 kk + 8 h .. +8)
-  for (int idx = tid; idx < JB * KS * 64; idx += WAVES * 64) {
-    const int l = idx & 63;
-    const int kk = (idx >> 6) % KS;
-    const int jb = idx / (64 * KS);
-    const int qi = jb * 32 + (l & 31);
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (qi < p.B) v = *(const u32x4*)(p.q + (size_t)qi * dim + kk * 16 + (l >> 5) * 8);
-    smemQ[idx] = v;
-  }
-
+  stage_queries<KS, JB, WAVES>(smemQ, p.q, p.B);
   __syncthreads();
   const uint32_t n_items = M + n_res;
   const uint32_t cnt = (n_items > gw) ? (n_items - gw + W - 1) / W : 0u;
@@ -525,15 +477,12 @@ int rf_scan_supported_dim(int dim) {
   }
 }
 
-static inline int waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
-static inline int wgs_per_cu(int KS) { return KS >= 48 ? 1 : 2; }
-
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold,
                      const rf_band* band) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
-  const int WAVES = waves_per_wg(KS);
+  const int WAVES = rf_waves_per_wg(KS);
   // Sample ~1/16 of the corpus, spread evenly: candidates per query ~ k * N / n_sample
   // stay ~16 k whatever N is, and a small corpus does not pay a sample pass as long as
   // its scan.  At least 64 workgroups (partitions) so the k-th largest exists for
@@ -595,12 +544,7 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
                    hipStream_t st, const rf_filter_view* filt, const rf_fold* fold, const rf_band* band) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
-  const int WAVES = waves_per_wg(KS);
-  const int wgs_env = rf_knob_emit_wgs_per_cu;
-  int grid = ix->num_cus * (wgs_env > 0 ? wgs_env : wgs_per_cu(KS));
-  const uint32_t need = (nblk + WAVES - 1) / WAVES;
-  if ((uint32_t)grid > need) grid = (int)need;
-  if (grid < 1) grid = 1;
+  const int grid = rf_emit_grid(ix, rf_knob_emit_wgs_per_cu);
   ScanParams p{};
   p.corpus = ix->tiles;
   p.q = (const _Float16*)q;

@@ -1,4 +1,4 @@
-// Device helpers shared by scan.hip (sample / emit kernels) and scan_fused.hip.
+// Device helpers shared by the sweeps: scan.hip, scan_wide.hip, sq8.hip and grouped.hip.
 #pragma once
 #include "rf_internal.h"
 
@@ -77,16 +77,93 @@ __device__ __forceinline__ uint32_t acc_row(int i, int h) {
   return (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h);
 }
 
+// (a maximum is exact in any order; the wave sums stay with their kernels: their order is their bits)
+__device__ __forceinline__ float wave_max_xor(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+// The MFMA chain of one 32-row block against the JB query groups in LDS: acc = scores, and the
+// register ring re-armed for the next block (fragment t + R is requested right after fragment t
+// has been consumed; LAST: nothing follows).
+template <int KS, int R, int JB, bool LAST>
+__device__ __forceinline__ void mfma_block(u32x4 (&ring)[R], const uint4* cur, const uint4* nxt,
+                                           const u32x4* smemQ, int lane, f32x16 (&acc)[JB]) {
+  static_assert(KS % R == 0, "ring must divide the block");
+  // keep the query-fragment LDS reads inside the block: hoisted out of the
+  // block loop they would pin JB*KS*4 registers and spill
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[jb][i] = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < KS; ++kk) {
+    const half8 a = __builtin_bit_cast(half8, ring[kk % R]);
+#pragma unroll
+    for (int jb = 0; jb < JB; ++jb) {
+      const half8 b = __builtin_bit_cast(half8, smemQ[(jb * KS + kk) * 64 + lane]);
+      acc[jb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[jb], 0, 0, 0);
+    }
+    // re-arm this ring slot with the fragment R steps ahead
+    if (kk + R < KS) {
+      ring[kk % R] = ld_frag(cur + (kk + R) * 64);
+    } else if (!LAST) {
+      ring[kk % R] = ld_frag(nxt + (kk + R - KS) * 64);
+    }
+  }
+}
+
+// The queries of a sweep into LDS in B-fragment order: a row is KF fragments' worth of 32 bytes
+// (fp16: KF = KS, 16 dims; int8: KF = KS8, 32 dims), and lane (j = l & 31, h = l >> 5) of fragment
+// (jb, kk) holds the 16 bytes at 32 kk + 16 h of query 32 jb + j.  Query slots past B read as zero.
+template <int KF, int JB, int WAVES>
+__device__ __forceinline__ void stage_queries(u32x4* smemQ, const void* q_bytes, int B) {
+  for (int idx = threadIdx.x; idx < JB * KF * 64; idx += WAVES * 64) {
+    const int l = idx & 63;
+    const int kk = (idx >> 6) % KF;
+    const int jb = idx / (64 * KF);
+    const int qi = jb * 32 + (l & 31);
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (qi < B) v = *(const u32x4*)((const unsigned char*)q_bytes + (size_t)qi * (KF * 32) + kk * 32 + (l >> 5) * 16);
+    smemQ[idx] = v;
+  }
+}
+
+// Work items of a masked sweep: the pass blocks of the filter, zero if its header was built for
+// another row count, clamped to the blocks of the index.
+__device__ __forceinline__ uint32_t filter_pass_blocks(const uint32_t* hdr, uint32_t n_rows, uint32_t n_blocks) {
+  const uint32_t npb = hdr[0] == n_rows ? hdr[2] : 0u;
+  return npb < n_blocks ? npb : n_blocks;
+}
+
 struct EmitState {
-  uint32_t* s_row;     // [SCAP] per wave (LDS)
-  float* s_score;      // [SCAP]
-  uint32_t* s_q;       // [SCAP]
+  uint32_t* s_row;     // [entries] per wave (LDS)
+  float* s_score;      // [entries]
+  uint32_t* s_q;       // [entries]
   uint32_t cnt;        // wave-uniform
   uint32_t q_base;     // query index of this wave's column 0 (wide sweep: 32 * wave)
 };
 
-template <class P>
-__device__ __forceinline__ void emit_flush(EmitState& es, const P& p, int lane) {
+// The staging area of a workgroup is three arrays [waves][entries]: rows, scores, queries.
+__device__ __forceinline__ EmitState emit_state(uint32_t* stage, int wave, int waves, int entries) {
+  EmitState es;
+  es.s_row = stage + wave * entries;
+  es.s_score = (float*)(stage + waves * entries) + wave * entries;
+  es.s_q = stage + 2 * waves * entries + wave * entries;
+  es.cnt = 0;
+  es.q_base = 0;
+  return es;
+}
+
+struct EmitListFull {   // emit_flush: nothing to do for a query whose list is full
+  __device__ __forceinline__ void operator()(uint32_t) const {}
+};
+
+// on_full(q): called for every entry that found the list of its query q full (the merge flags
+// such a query whatever else is appended).
+template <class P, class F = EmitListFull>
+__device__ __forceinline__ void emit_flush(EmitState& es, const P& p, int lane, F on_full = F()) {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   for (uint32_t i = lane; i < es.cnt; i += 64) {
     const uint32_t q = es.s_q[i];
@@ -97,14 +174,45 @@ __device__ __forceinline__ void emit_flush(EmitState& es, const P& p, int lane) 
     if (slot < p.cap)
       p.cand[(size_t)list * p.cap + slot] =
           make_uint2(es.s_row[i], __builtin_bit_cast(uint32_t, es.s_score[i]));
+    else
+      on_full(q);
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   es.cnt = 0;
 }
 
+// The append loop over a per-lane hit mask the caller built (bit jb*16+i: register i of query
+// group jb; `sc` holds the scores that are appended).  The wave retires each lane's lowest set
+// bit per iteration and ballot-compacts the hits into the staging area; flush() empties it when
+// the round would not fit.
+template <int JB, class F>
+__device__ __forceinline__ void emit_append(const f32x16 (&sc)[JB], uint32_t bits, uint32_t row0, int lane,
+                                            EmitState& es, F flush) {
+  const int h = lane >> 5;
+  unsigned long long mask;
+  while ((mask = __ballot(bits != 0u)) != 0ull) {
+    const bool pass = bits != 0u;
+    const int b = __ffs((int)bits) - 1;  // -1 when !pass (unused then)
+    float s = 0.f;
+#pragma unroll
+    for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s = (b == jb * 16 + i) ? sc[jb][i] : s;
+    const uint32_t n = (uint32_t)__popcll(mask);
+    if (es.cnt + n > SCAP) flush();
+    if (pass) {
+      const uint32_t slot = es.cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+      es.s_row[slot] = row0 + acc_row(b & 15, h);
+      es.s_score[slot] = s;
+      es.s_q[slot] = es.q_base + (uint32_t)((b >> 4) * 32 + (lane & 31));
+    }
+    es.cnt += n;
+    bits &= bits - 1u;
+  }
+}
+
 // Slow path of the filter (some lane holds a score >= its query's threshold).
-// Branch-free build of a per-lane 32-bit hit mask (bit jb*16+i), then a wave loop
-// that retires each lane's lowest set bit per iteration: the usual case (one or two
+// Branch-free build of a per-lane 32-bit hit mask, then emit_append: the usual case (one or two
 // hits in the whole wave) costs one iteration instead of 32 ballot+branch rounds.
 // FILTER: `mword` is the block's filter word; a row whose bit is clear is never a candidate,
 // whatever its score (an explicit test: the threshold may be -inf, so masking by writing -inf
@@ -124,27 +232,7 @@ __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (
       bits |= ((acc[jb][i] >= th[jb]) && (acc_row(i, h) < lim) &&
                (!FILTER || ((mword >> acc_row(i, h)) & 1u) != 0u) &&
                (!BAND || acc[jb][i] <= tc[jb])) ? (1u << (jb * 16 + i)) : 0u;
-  unsigned long long mask;
-  while ((mask = __ballot(bits != 0u)) != 0ull) {
-    const bool pass = bits != 0u;
-    const int b = __ffs((int)bits) - 1;  // -1 when !pass (unused then)
-    float s = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s = (b == jb * 16 + i) ? acc[jb][i] : s;
-    const uint32_t n = (uint32_t)__popcll(mask);
-    if (es.cnt + n > SCAP) emit_flush(es, p, lane);
-    if (pass) {
-      const int i = b & 15;
-      const uint32_t slot = es.cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      es.s_row[slot] = row0 + (uint32_t)((i & 3) + 8 * (i >> 2) + 4 * h);
-      es.s_score[slot] = s;
-      es.s_q[slot] = es.q_base + (uint32_t)((b >> 4) * 32 + (lane & 31));
-    }
-    es.cnt += n;
-    bits &= bits - 1u;
-  }
+  emit_append<JB>(acc, bits, row0, lane, es, [&] { emit_flush(es, p, lane); });
 }
 
 // Slow path, second form (wide sweep): one ballot per accumulator register instead of a

@@ -184,12 +184,8 @@ __global__ void __launch_bounds__(NW * 64, 1) k_scan_ldsdma(WideParams p) {
   float pm[JBW];
 #pragma unroll
   for (int jb = 0; jb < JBW; ++jb) pm[jb] = -INFINITY;
-  EmitState es;
-  es.cnt = 0;
+  EmitState es = emit_state(stage, wave, NW, CAP);
   es.q_base = (uint32_t)(wave * JBW * 32);
-  es.s_row = stage + wave * CAP;
-  es.s_score = (float*)(stage + NW * CAP) + wave * CAP;
-  es.s_q = stage + 2 * NW * CAP + wave * CAP;
 
   // Score filter of one 32-row block (all query blocks of the wave).  Sample: running maximum
   // per lane (= per query); emit: any score >= the query's threshold sends the wave down the

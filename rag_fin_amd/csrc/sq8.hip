@@ -28,10 +28,6 @@ typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
 static inline int64_t sq8_blocks(int64_t rows) { return (rows + RF_BLOCK_ROWS - 1) / RF_BLOCK_ROWS; }
 
 // ---- quantization ---------------------------------------------------------------------------
-__device__ __forceinline__ float wave_max_xor(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 __device__ __forceinline__ double wave_sum_xor(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
@@ -155,52 +151,12 @@ struct Sq8Params {
   uint32_t cap;
 };
 
-// emit_flush (scan_common.h) that also records the queries whose list is full: an append past the
-// capacity means the merge flags the query (RF_FLAG_CAND_OVERFLOW) whatever else is appended, so the
-// workgroup stops testing it (`sat`, LDS).
-__device__ __forceinline__ void sq8_flush(EmitState& es, const Sq8Params& p, int lane, unsigned long long* sat) {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  for (uint32_t i = lane; i < es.cnt; i += 64) {
-    const uint32_t q = es.s_q[i];
-    const uint32_t list = q * RF_CAND_SHARDS + (blockIdx.x & (RF_CAND_SHARDS - 1));
-    const uint32_t slot = atomicAdd(&p.cand_cnt[list], 1u);
-    if (slot < p.cap)
-      p.cand[(size_t)list * p.cap + slot] = make_uint2(es.s_row[i], __builtin_bit_cast(uint32_t, es.s_score[i]));
-    else
-      atomicOr(sat, 1ull << q);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  es.cnt = 0;
-}
-
-// emit_slow (scan_common.h) with the per-lane hit mask given: the test of a row depends on its own
-// e_r, so the mask is built by the caller; `sc` holds the a~ that are appended.
-template <int JB>
-__device__ __forceinline__ void emit_bits(const f32x16 (&sc)[JB], uint32_t bits, uint32_t row0, int lane,
-                                          EmitState& es, const Sq8Params& p, unsigned long long* sat) {
-  const int h = lane >> 5;
-  unsigned long long mask;
-  while ((mask = __ballot(bits != 0u)) != 0ull) {
-    const bool pass = bits != 0u;
-    const int b = __ffs((int)bits) - 1;
-    float s = 0.f;
-#pragma unroll
-    for (int jb = 0; jb < JB; ++jb)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s = (b == jb * 16 + i) ? sc[jb][i] : s;
-    const uint32_t n = (uint32_t)__popcll(mask);
-    if (es.cnt + n > SCAP) sq8_flush(es, p, lane, sat);
-    if (pass) {
-      const int i = b & 15;
-      const uint32_t slot = es.cnt + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      es.s_row[slot] = row0 + acc_row(i, h);
-      es.s_score[slot] = s;
-      es.s_q[slot] = es.q_base + (uint32_t)((b >> 4) * 32 + (lane & 31));
-    }
-    es.cnt += n;
-    bits &= bits - 1u;
-  }
-}
+// emit_flush's hook: an append past the capacity means the merge flags the query
+// (RF_FLAG_CAND_OVERFLOW) whatever else is appended, so the workgroup stops testing it (`sat`, LDS).
+struct Sq8ListFull {
+  unsigned long long* sat;
+  __device__ __forceinline__ void operator()(uint32_t q) const { atomicOr(sat, 1ull << q); }
+};
 
 struct Sq8Meta {
   float4 s[4], e[4];   // s_r / e_r of the 16 accumulator rows of this lane half
@@ -268,7 +224,8 @@ __device__ __forceinline__ void sq8_step(u32x4 (&ring)[R], Sq8Meta& meta, uint32
                       ((full >> (jb * 32 + (lane & 31))) & 1ull) == 0ull;
       bits |= ok ? (1u << (jb * 16 + i)) : 0u;
     }
-  if (__ballot(bits != 0u) != 0ull) emit_bits<JB>(sc, bits, row0, lane, es, p, sat);
+  // the test of a row depends on its own e_r, so the mask is built here; the a~ are what is appended
+  if (__ballot(bits != 0u) != 0ull) emit_append<JB>(sc, bits, row0, lane, es, [&] { emit_flush(es, p, lane, Sq8ListFull{sat}); });
   if (!LAST) meta = next;
 }
 
@@ -292,12 +249,7 @@ __global__ void __launch_bounds__(256, 2) k_sq8_emit(Sq8Params p) {
     tq[jb] = p.tq[qi];
     nq[jb] = p.nq[qi];
   }
-  EmitState es;
-  es.cnt = 0;
-  es.q_base = 0;
-  es.s_row = (uint32_t*)tail + wave * SCAP;
-  es.s_score = (float*)((uint32_t*)tail + WAVES * SCAP) + wave * SCAP;
-  es.s_q = (uint32_t*)tail + 2 * WAVES * SCAP + wave * SCAP;
+  EmitState es = emit_state((uint32_t*)tail, wave, WAVES, SCAP);
   const uint32_t W = gridDim.x * WAVES;
   const uint32_t gw = blockIdx.x * WAVES + wave;
   u32x4 ring[R];
@@ -309,17 +261,7 @@ __global__ void __launch_bounds__(256, 2) k_sq8_emit(Sq8Params p) {
     load_meta(meta, p, gw, h);
   }
   if (tid == 0) sat = 0ull;
-  // stage q^ in B-fragment order: lane (j = l & 31, h = l >> 5) of fragment (jb, kk) holds
-  // q^[32 jb + j][32 kk + 16 h .. +16)
-  for (int idx = tid; idx < JB * KS8 * 64; idx += WAVES * 64) {
-    const int l = idx & 63;
-    const int kk = (idx >> 6) % KS8;
-    const int jb = idx / (64 * KS8);
-    const int qi = jb * 32 + (l & 31);
-    u32x4 v = {0u, 0u, 0u, 0u};
-    if (qi < p.B) v = *(const u32x4*)(p.q8 + (size_t)qi * p.dim + kk * 32 + (l >> 5) * 16);
-    smemQ[idx] = v;
-  }
+  stage_queries<KS8, JB, WAVES>(smemQ, p.q8, p.B);   // q^[32 jb + j][32 kk + 16 h .. +16)
   __syncthreads();
   const uint32_t cnt = (p.n_work > gw) ? (p.n_work - gw + W - 1) / W : 0u;
   if (cnt > 0) {
@@ -328,7 +270,7 @@ __global__ void __launch_bounds__(256, 2) k_sq8_emit(Sq8Params p) {
       sq8_step<KS8, R, JB, false>(ring, meta, b, b + W, smemQ, lane, th, tq, nq, es, p, &sat);
     sq8_step<KS8, R, JB, true>(ring, meta, b, b, smemQ, lane, th, tq, nq, es, p, &sat);
   }
-  if (es.cnt > 0) sq8_flush(es, p, lane, &sat);
+  if (es.cnt > 0) emit_flush(es, p, lane, Sq8ListFull{&sat});
 }
 
 // ---- test hooks -------------------------------------------------------------------------------
