@@ -419,8 +419,10 @@ int rf_index_get_rows_sq8(const rf_index_t* ix, const int64_t* rows_dev, int64_t
  * The shipped library has no run-time tuning surface: the knobs are compile-time constants
  * (csrc/rf_internal.h).  In the experiments build they are process-wide ints, NOT thread-safe
  * against concurrent searches.  Keys: "ring24" (6|8|12|24), "emit_wgs_per_cu" (0..4),
- * "sample_bpw" (1..8), "wide_sample_pairs" (1..8), "wide_dbg"; encoder: "linear_dma" (0..3),
- * "linear_small", "encode_graph" (0|1), "k384_ntb", "ffn2_ntb" (2|4), "linear_dbg", "debug_epi". */
+ * "sample_bpw" (1..8), "sample_fold" (0|1), "fold_dbg", "wide_sample_pairs" (1..8), "wide_dbg",
+ * "wide_ne"; encoder: "linear_dma" (0..3), "linear_small", "encode_graph", "one_query",
+ * "post_block", "post_qkv" (0|1), "linear_dbg", "post_dbg", "debug_epi" (0|2|5).  The list with
+ * defaults and ranges is RF_KNOBS in csrc/rf_internal.h; any other key is an error. */
 int rf_set_tuning(const char* key, int value);
 /* byte offset of a named array ("pmax", "cand", "thr", "eps", "cand_cnt", "rmask", "rcnt") inside a
  * search workspace (the same in an SQ8 workspace, whose query area follows the FLAT arrays) */

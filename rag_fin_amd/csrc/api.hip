@@ -70,6 +70,34 @@ extern "C" size_t rf_debug_workspace_offset(const char* field) {
     if (field && !strcmp(field, f.name)) return (size_t)((const unsigned char*)f.at - a.base);
   return (size_t)-1;
 }
+
+// The tuning knobs (rf_internal.h, RF_KNOBS) as process-wide ints behind rf_set_tuning.
+#define RF_KNOB_DEF(name, dflt, lo, hi) int rf_knob_##name = dflt;
+RF_KNOBS(RF_KNOB_DEF)
+#undef RF_KNOB_DEF
+int rf_tuning_generation = 0;
+void* rf_debug_buffer = nullptr;
+extern "C" int rf_debug_set_buffer(void* dev_ptr) {
+  rf_debug_buffer = dev_ptr;
+  return RF_OK;
+}
+extern "C" int rf_set_tuning(const char* key, int value) {
+  if (!key) return RF_ERR_INVALID;
+  ++rf_tuning_generation;   // cached encode graphs were captured under the old settings
+  const struct { const char* name; int* var; int lo, hi; } keys[] = {
+#define RF_KNOB_KEY(name, dflt, lo, hi) {#name, &rf_knob_##name, lo, hi},
+      RF_KNOBS(RF_KNOB_KEY)
+#undef RF_KNOB_KEY
+  };
+  for (const auto& k : keys)
+    if (!strcmp(key, k.name) && value >= k.lo && value <= k.hi) {
+      if (k.var == &rf_knob_ring24 && value != 6 && value != 8 && value != 12 && value != 24) break;
+      *k.var = value;
+      return RF_OK;
+    }
+  rf_set_error("rf_set_tuning: unknown key or bad value (%s = %d)", key, value);
+  return RF_ERR_INVALID;
+}
 #endif
 
 extern "C" size_t rf_search_workspace_bytes(const rf_index_t* ix) {

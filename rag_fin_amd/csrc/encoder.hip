@@ -15,14 +15,14 @@
 //   k_tok_offsets   lens -> packed row offsets
 //   k_embed_ln      word + position + type embedding gather, LayerNorm        (K1)
 //   the Linears     Y^T = W X^T on the matrix cores with the epilogues fused -- bias (QKV, K2) | bias + GELU
-//                   (K5) | bias + residual + LayerNorm (K4, K6) -- in one of four forms chosen by the batch's
+//                   (K5) | bias + residual + LayerNorm (K4, K6) -- in one of three forms chosen by the batch's
 //                   token slots (launch_linear):
 //     k_linear_small  <= 1024 slots (queries): output features spread over the chip, LayerNorm as k_ln_rows
-//     k_linear        < 8192: a workgroup owns 32 or 64 tokens x 384 features, operands straight from L1/L2
-//     k_linear_dma    >= 8192, QKV and FFN1: the wave's 32 tokens resident in registers, weights through an
+//     k_linear        < 8192: a workgroup owns 64 tokens x 384 features, operands straight from L1/L2
+//     k_linear_dma    >= 8192, layer 0's QKV: the wave's 32 tokens resident in registers, weights through an
 //                     LDS-DMA ring, the epilogue of block b deferred into the MFMA stream of block b + 1
-//     k_gemm_tile     >= 8192, out-projection and FFN2 (LayerNorm epilogues): both operands through a 4-slot
-//                     LDS-DMA ring, 128 tokens x 384 features per workgroup
+//   k_post_block    >= 8192: out-projection, MLP and the next layer's QKV of a layer in one launch
+//                   (encoder_post.hip)
 //   k_attention_mfma softmax(Q K^T / sqrt(32)) V per (sequence, head) on the matrix cores
 //                   for T <= 256 (K3); k_attention = vector-ALU online-softmax form
 //                   kept for longer sequences
@@ -519,7 +519,7 @@ __global__ void __launch_bounds__(256) k_linear(
   }
 }
 
-// ---- K = 384 GEMMs with plain epilogues (QKV, FFN1): weights through an LDS-DMA ring -------
+// ---- the K = 384 GEMM with the bias epilogue (QKV): weights through an LDS-DMA ring --------
 // k_linear above loads BOTH operands of every k-step straight from L1/L2 into registers, per
 // wave: 5 KiB of fragment loads per 6 MFMAs, and the texture-addresser path, not the matrix
 // pipe, sets its pace (~1.7 x the MFMA time).  This form is the batch-256 corpus sweep
@@ -531,8 +531,8 @@ __global__ void __launch_bounds__(256) k_linear(
 //     all eight waves of the workgroup read it from LDS (inline-asm ds_read_b128, lds_ring.h),
 //     so a weight byte crosses the load path once per 128 tokens instead of once per wave;
 //   * workgroup = 128 tokens x ALL N features: waves w and w + 4 share a token block and a
-//     SIMD and take the even / odd feature block of each phase, so one's epilogue (bias, GELU,
-//     fp16 stores) runs under the other's MFMAs;
+//     SIMD and take the even / odd feature block of each phase, so one's epilogue (fp16
+//     stores) runs under the other's MFMAs;
 //   * the bias vector sits in LDS and is read with inline-asm ds_read_b64 (an ordinary global
 //     load in the loop would make hipcc wait vmcnt(0) and drain the ring).
 #define LD_TOK 128
@@ -544,34 +544,10 @@ __global__ void __launch_bounds__(256) k_linear(
 // two feature blocks; WIDE = 1: 256 tokens per workgroup, every wave owns a token block and takes
 // BOTH feature blocks of a phase (the per-wave fixed costs -- six LDS-DMA issues, a barrier --
 // are paid once per 48 MFMAs instead of once per 24, and a weight byte serves 256 tokens).
-// GELU for the deferred epilogue below: plain (unpacked) fp32 only.  Measured on gfx950
-// (tools/ubench/mfma_valu.hip): v_fma_f32 issues under the MFMAs of either wave of the SIMD at
-// almost no cost (8 MFMA + 32 v_fma_f32 in one wave: 276 cycles against 264 for the MFMAs alone),
-// v_pk_fma_f32 does not (484 cycles) -- the packed form is only worth its two lanes where no MFMA
-// is in flight.  h(y) = y (1/2 + yc Q(t)), yc = y clamped to +-3.2 sqrt 2, t = yc^2 / 3.2^2 - 1:
-// the erf polynomial of gelu_erf2 with 1/(2 sqrt 2) folded into its coefficients; 16 VALU
-// operations per value (bias add included), same error (2e-5 absolute at the clamp).
-__device__ __forceinline__ float gelu_erf_s(float y) {
-  constexpr float CP = 4.52548360824585f;   // 3.2 sqrt 2
-  const float yc = __builtin_amdgcn_fmed3f(y, -CP, CP);
-  const float t = __builtin_fmaf(yc * yc, 0.09765625f, -1.f);
-  float p = __builtin_fmaf(t, 8.469007444e-04f, -2.387454268e-03f);
-  p = __builtin_fmaf(t, p, 3.280109027e-03f);
-  p = __builtin_fmaf(t, p, -5.588355009e-03f);
-  p = __builtin_fmaf(t, p, 1.136882324e-02f);
-  p = __builtin_fmaf(t, p, -1.921003498e-02f);
-  p = __builtin_fmaf(t, p, 2.861942165e-02f);
-  p = __builtin_fmaf(t, p, -4.021260887e-02f);
-  p = __builtin_fmaf(t, p, 5.456056446e-02f);
-  p = __builtin_fmaf(t, p, -7.682786137e-02f);
-  p = __builtin_fmaf(t, p, 1.560353935e-01f);
-  return y * __builtin_fmaf(yc, p, 0.5f);
-}
-
 // ABL: ablations for tools/bench_encode.py --linear-dbg (experiments build only; results wrong):
 // 1 = every LDS-DMA piece re-reads one cached KiB, 2 = no LDS-DMA in the loop, 4 = no epilogue,
 // 8 = every workgroup stores into one L2-resident window, 16 = no LDS fragment reads, 32 = no MFMAs.
-template <int EPI, int WIDE, int ABL>
+template <int WIDE, int ABL>
 __global__ void __launch_bounds__(LD_WAVES * 64, 1) RF_NO_PACKED_FP32 k_linear_dma(
     const _Float16* __restrict__ X, const uint4* __restrict__ Wt, const _Float16* __restrict__ bias,
     _Float16* __restrict__ out, int N, const int32_t* __restrict__ m_ptr, float* __restrict__ dbg) {
@@ -680,10 +656,6 @@ __global__ void __launch_bounds__(LD_WAVES * 64, 1) RF_NO_PACKED_FP32 k_linear_d
     float y[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) y[j] = acc[4 * g + j];
-    if (EPI == EPI_BIAS_GELU) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = gelu_erf_s(y[j]);
-    }
     const half4 o = {(_Float16)y[0], (_Float16)y[1], (_Float16)y[2], (_Float16)y[3]};
     const uint2 pk = __builtin_bit_cast(uint2, o);
     if (!(g & 1)) {
@@ -797,329 +769,6 @@ __global__ void __launch_bounds__(LD_WAVES * 64, 1) RF_NO_PACKED_FP32 k_linear_d
     o[2] = (float)(ts_loop - ts_entry);                             // cycles before the loop
     o[3] = (float)t_wait;                                           // cycles in vmcnt wait + barrier
     o[4] = (float)n_ph;
-  }
-}
-
-// ---- tiled GEMM with both operands through an LDS-DMA ring (round 2) ----------------------------
-// Y[128 tokens, 384 features] per workgroup, any K: the form for the GEMMs whose activations do
-// not fit a wave's registers (FFN2: K = 1536) and for the LayerNorm epilogues, which need all 384
-// features of a token inside one workgroup.  k_linear (above) loads both operands per wave
-// straight from L1/L2 -- 5 KiB of fragment loads per 6 MFMAs per wave, texture-addresser-bound at
-// ~1.7 x its MFMA time (round-1 counters: matrix pipe busy 28 % for FFN2, 13 % for the
-// out-projection).  Here a K-step of 32 is brought ONCE per workgroup by LDS-DMA -- 4 token blocks
-// and 12 feature blocks of two 1-KiB fragments each, 32 KiB, HBM/L2 order == LDS order because the
-// fragment image is lane-linear -- into a 4-slot ring with three stages in flight behind a counted
-// vmcnt and one raw s_barrier per stage; the 8 waves (2 token halves x 4 feature quarters) read
-// their 4 + 6 operand tiles with the permuted, conflict-free ds_read_b128 of the batch-256 sweep
-// (scan_wide.hip) and run 24 v_mfma_f32_16x16x32_f16 per stage: 10 LDS reads per 24 MFMAs.
-// A = weights (16 features x 32 k), B = activations (16 tokens x 32 k): the accumulator holds the
-// TOKEN on the lane and 4 consecutive FEATURES in registers, as in the other GEMMs, so bias, GELU,
-// residual add, the LayerNorm statistics and the 8-byte stores into the tiled layout are lane-local
-// plus one LDS exchange between the four feature quarters.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define GT_TOK 128
-#define GT_SLOTS 4
-#define GT_STAGE_FRAGS 32                  // 1-KiB fragments per stage: 4 x 2 (activations) + 12 x 2 (weights)
-template <int EPI, int KS, int DMODE>      // KS = K / 16 (24 | 96); DMODE: who issues the LDS-DMA pieces (below)
-__global__ void __launch_bounds__(512, 1) k_gemm_tile(
-    const _Float16* __restrict__ X, const uint4* __restrict__ Wt, const _Float16* __restrict__ bias,
-    _Float16* __restrict__ out, int ldo, const int32_t* __restrict__ m_ptr, const _Float16* __restrict__ res,
-    const _Float16* __restrict__ gamma, const _Float16* __restrict__ beta, float eps, float* __restrict__ dbg) {
-  constexpr int NST = KS / 2;              // stages (k-steps of 32)
-  // diagnostic run only (dbg != nullptr, tools/bench_encode.py --stamps --stamp-epi 3 | 4): clock stamps per wave
-  const uint64_t ts_entry = dbg ? __builtin_amdgcn_s_memtime() : 0;
-  uint64_t ts_loop = 0, ts_epi = 0, t_wait = 0;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  rf_u32x4* slots = (rf_u32x4*)smem_raw;                           // [GT_SLOTS][32 frags][64 lanes]
-  rf_u32x4* const dump = slots + GT_SLOTS * GT_STAGE_FRAGS * 64;   // 1 KiB: pieces issued past the last stage
-  float* red = (float*)(dump + 64);                               // [2][4 quarters][128 tokens] LayerNorm partial sums
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int c16 = lane & 15, g = lane >> 4;
-  const int wm = wave >> 2, wn = wave & 3;                         // token half, feature quarter
-  const int t0 = blockIdx.x * GT_TOK;
-  const int n0 = blockIdx.y * 384;
-
-  // LDS-DMA issue is stall-prone (60-185 cycles per piece): were every wave to issue its share at the
-  // same point of every stage, both waves of a SIMD would stall together and the matrix pipe would idle.
-  // The halves of the workgroup (waves 0-3 / 4-7: the two waves of each SIMD) therefore take TURNS: the
-  // stage t is brought, three stages ahead, by half (t + 1) & 1 alone -- 8 pieces per wave, every other
-  // stage -- so in every stage one wave per SIMD goes straight to its MFMAs.  Piece p = 8 w' + j
-  // (w' = wave & 3): p < 8: activation block p >> 1, fragment p & 1; p >= 8: weight block (p - 8) >> 1.
-  // A wave's outstanding pieces at the wait in front of stage t are then either {t, t + 2} (its half
-  // brought t) or {t + 1}: `vmcnt(8)` is right for both.
-  // DMODE 1: EVERY wave brings 4 pieces of every stage, one after each sixth MFMA of the stage before
-  // (mfma_stage): 8 pieces in a burst ahead of the MFMAs cost the issuing wave ~1 200 cycles, during which the
-  // stage's barrier holds everybody else -- spread, the stalls of a piece sit on top of six queued MFMAs.
-  const int half = wave >> 2;
-  constexpr int NP = DMODE == 1 ? 4 : 8;    // pieces per wave per issue
-  const int p0 = DMODE == 1 ? wave * 4 : (wave & 3) * 8;
-  // a piece's source = a wave-uniform base (scalar registers) + the lane's 16 bytes: nothing of it lives in
-  // vector registers across the MFMAs it is issued between
-  const char* const my_base = (p0 < 8) ? (const char*)X + ((size_t)((t0 >> 5) + (p0 >> 1)) * KS) * 1024
-                                       : (const char*)Wt + ((size_t)((n0 >> 5) + ((p0 - 8) >> 1)) * KS) * 1024;
-  const uint32_t lane_off = (uint32_t)lane * 16u;
-  auto issue_piece = [&](int s, int j) __attribute__((always_inline)) {   // j = 2 b + f: block b of mine, fragment f
-    const bool live = s < NST;
-    const char* src = my_base + ((size_t)(j >> 1) * KS + (size_t)(live ? 2 * s : 0) + (j & 1)) * 1024;
-    rf_u32x4* dst = live ? slots + ((s % GT_SLOTS) * GT_STAGE_FRAGS + p0 + j) * 64 : dump;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane_off),
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-  };
-  auto issue_stage = [&](int s) __attribute__((always_inline)) {   // all of my pieces of stage s, live or not (uniform vmcnt arithmetic)
-    if (DMODE == 2 && s >= 3) return;   // ablation (experiments build; results wrong): no LDS-DMA in the stage loop
-    if (DMODE != 1 && ((s + 1) & 1) != half) return;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) issue_piece(s, j);
-  };
-  issue_stage(0);
-  issue_stage(1);
-  issue_stage(2);
-  const int M = *m_ptr;
-  if (t0 >= M) {   // whole workgroup; its LDS-DMA pieces must land before the LDS is handed on
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return;
-  }
-
-  f32x4 acc[6][4];   // [feature tile ft][token tile tt]: lane = token 16 tt + c16, features 16 ft + 4 g + j
-#pragma unroll
-  for (int ft = 0; ft < 6; ++ft)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) acc[ft][tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // operand tile addresses inside a stage: activation block b at fragment 2 b, weight block b at 8 + 2 b;
-  // lane's bytes = ((g >> 1) * 64 + (g & 1) * 32 + 16 rg + c16) * 16 (see k_scan_w16)
-  const uint32_t lane_a = (uint32_t)(((g >> 1) * 64 + (g & 1) * 32 + c16) * 16);
-  const uint32_t xa = lane_a + (uint32_t)((2 * wm) * 2048);             // my first token block
-  const uint32_t wa = lane_a + (uint32_t)(8 * 1024 + (3 * wn) * 2048);  // my first feature block
-  // Software pipeline by one stage: after barrier(s) the operands of stage s are READ into one register set
-  // while the MFMAs of stage s-1 run on the other -- the LDS latency (and the LDS-DMA issues of stage s+3)
-  // sit under 24 MFMAs instead of in front of them.
-  auto read_stage = [&](int s, rf_u32x4 (&xb)[4], rf_u32x4 (&wf)[6]) __attribute__((always_inline)) {
-    const uint32_t sb = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)(slots + (s % GT_SLOTS) * GT_STAGE_FRAGS * 64);
-    // tile tt of my tokens = block tt >> 1, row group tt & 1; tile ft of my features likewise
-    asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(xb[0]) : "v"(sb + xa));
-    asm volatile("ds_read_b128 %0, %1 offset:256" : "=v"(xb[1]) : "v"(sb + xa));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(xb[2]) : "v"(sb + xa));
-    asm volatile("ds_read_b128 %0, %1 offset:2304" : "=v"(xb[3]) : "v"(sb + xa));
-    asm volatile("ds_read_b128 %0, %1 offset:0" : "=v"(wf[0]) : "v"(sb + wa));
-    asm volatile("ds_read_b128 %0, %1 offset:256" : "=v"(wf[1]) : "v"(sb + wa));
-    asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(wf[2]) : "v"(sb + wa));
-    asm volatile("ds_read_b128 %0, %1 offset:2304" : "=v"(wf[3]) : "v"(sb + wa));
-    asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(wf[4]) : "v"(sb + wa));
-    asm volatile("ds_read_b128 %0, %1 offset:4352" : "=v"(wf[5]) : "v"(sb + wa));
-  };
-  // nxt (DMODE 1): the stage whose pieces this wave issues between the MFMAs
-  auto mfma_stage = [&](rf_u32x4 (&xb)[4], rf_u32x4 (&wf)[6], int nxt) __attribute__((always_inline)) {
-    if (DMODE != 1) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ft = 0; ft < 6; ++ft) {
-#pragma unroll
-      for (int tt = 0; tt < 4; ++tt)
-        acc[ft][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, wf[ft]), __builtin_bit_cast(half8, xb[tt]),
-                                                             acc[ft][tt], 0, 0, 0);
-      if (DMODE == 1 && ft >= 1 && ft <= 4) {
-        __builtin_amdgcn_sched_barrier(0);
-        issue_piece(nxt, ft - 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (DMODE != 1) __builtin_amdgcn_s_setprio(0);
-  };
-  auto sync_stage = [&]() __attribute__((always_inline)) {
-    uint64_t ts0 = 0;
-    if (dbg) ts0 = __builtin_amdgcn_s_memtime();
-    // my pieces of the stage have landed (those of the next two stages may stay in flight) ...
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    // ... after the barrier everybody's have, and everybody has READ the previous stage (its slot is free)
-    __builtin_amdgcn_s_barrier();
-    if (dbg) t_wait += __builtin_amdgcn_s_memtime() - ts0;
-  };
-  rf_u32x4 xb0[4], wf0[6], xb1[4], wf1[6];
-  static_assert(NST % 2 == 0, "stages are processed in pairs");
-  if (dbg) ts_loop = __builtin_amdgcn_s_memtime();
-  // vmcnt arithmetic of DMODE 1: the pieces of stage t + 3 go out under the MFMAs of stage t - 1, i.e. after the
-  // barrier of stage t (the slot they overwrite, that of stage t - 1, has been read by everybody by then); at
-  // the wait in front of stage t a wave has therefore issued, after its pieces of stage t, those of t + 1 and
-  // t + 2 (4 each): vmcnt(8), the same constant as in the other mode.
-  sync_stage();
-  read_stage(0, xb0, wf0);
-  issue_stage(3);
-#pragma unroll 1
-  for (int s = 1; s < NST; s += 2) {
-    // odd stage s: read into set 1, compute stage s-1 from set 0
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xb0[0]), "+v"(xb0[1]), "+v"(xb0[2]), "+v"(xb0[3]), "+v"(wf0[0]), "+v"(wf0[1]),
-                 "+v"(wf0[2]), "+v"(wf0[3]), "+v"(wf0[4]), "+v"(wf0[5]));
-    sync_stage();
-    read_stage(s, xb1, wf1);
-    if (DMODE != 1) issue_stage(s + 3);
-    mfma_stage(xb0, wf0, s + 3);          // (DMODE 1) under the MFMAs of stage s-1: the pieces of stage s+3
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xb1[0]), "+v"(xb1[1]), "+v"(xb1[2]), "+v"(xb1[3]), "+v"(wf1[0]), "+v"(wf1[1]),
-                 "+v"(wf1[2]), "+v"(wf1[3]), "+v"(wf1[4]), "+v"(wf1[5]));
-    if (s + 1 < NST) {   // even stage s+1: read into set 0, compute stage s from set 1
-      sync_stage();
-      read_stage(s + 1, xb0, wf0);
-      if (DMODE != 1) issue_stage(s + 4);
-    }
-    mfma_stage(xb1, wf1, s + 4);          // (in the last trip: pieces past the last stage, into the dump slot)
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the dump pieces must land before the LDS is handed on
-  if (dbg) ts_epi = __builtin_amdgcn_s_memtime();
-
-  // ---- epilogue: acc[ft][tt][j] = Y[t0 + 64 wm + 16 tt + c16][n0 + 96 wn + 16 ft + 4 g + j] ----------------
-  const int fbase = n0 + 96 * wn + 4 * g;
-  float mu[4], rstd[4];
-  // every global load of the epilogue -- bias, residual, LayerNorm scale and shift -- is issued HERE, ahead of
-  // the first use: spread through the epilogue (the scale and shift behind the LayerNorm's barriers) they were
-  // three to four memory round trips in a row, most of the epilogue's 15-17 k cycles (stamps)
-  half4 bvs[6], gvs[6], bes[6];
-  uint4 rrs[6][2];
-#pragma unroll
-  for (int ft = 0; ft < 6; ++ft) {
-    bvs[ft] = *(const half4*)(bias + fbase + 16 * ft);
-    if (EPI == EPI_BIAS_RES_LN) {
-      gvs[ft] = *(const half4*)(gamma + fbase + 16 * ft);
-      bes[ft] = *(const half4*)(beta + fbase + 16 * ft);
-      // residual: ONE 16-byte lane-linear load per pair of token tiles (the fragment of token block
-      // 2 wm + tp, feature group 6 wn + ft, whole); the half exchange of the stores below, backwards, follows
-#pragma unroll
-      for (int tp = 0; tp < 2; ++tp)
-        rrs[ft][tp] = *(const uint4*)(res + ((size_t)((t0 >> 5) + 2 * wm + tp) * (HID / 16) + (n0 >> 4) + 6 * wn + ft) * 512 + lane * 8);
-    }
-  }
-#pragma unroll
-  for (int ft = 0; ft < 6; ++ft) {
-    const half4 bv = bvs[ft];
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      if (EPI == EPI_BIAS_GELU) {
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-          f32x2 y;
-          y[0] = acc[ft][tt][j] + (float)bv[j];
-          y[1] = acc[ft][tt][j + 1] + (float)bv[j + 1];
-          y = gelu_erf2(y);
-          acc[ft][tt][j] = y[0];
-          acc[ft][tt][j + 1] = y[1];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[ft][tt][j] += (float)bv[j];
-      }
-    }
-    if (EPI == EPI_BIAS_RES_LN) {
-#pragma unroll
-      for (int tp = 0; tp < 2; ++tp) {
-        const uint4 r = rrs[ft][tp];
-        const auto sx = __builtin_amdgcn_permlane16_swap(r.x, r.z, false, false);
-        const auto sy = __builtin_amdgcn_permlane16_swap(r.y, r.w, false, false);
-        const uint2 lo = make_uint2(sx[0], sy[0]), hi = make_uint2(sx[1], sy[1]);
-        const half4 r0 = __builtin_bit_cast(half4, lo), r1 = __builtin_bit_cast(half4, hi);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[ft][2 * tp][j] += (float)r0[j];
-          acc[ft][2 * tp + 1][j] += (float)r1[j];
-        }
-      }
-    }
-  }
-  uint64_t ts_e1 = 0, ts_e2 = 0;
-  if (dbg) {
-    asm volatile("" : "+v"(acc[0][0]), "+v"(acc[5][3]));
-    ts_e1 = __builtin_amdgcn_s_memtime();   // bias + residual added: the epilogue's loads have arrived
-  }
-  if (EPI == EPI_BIAS_RES_LN) {
-    // LayerNorm over the 384 features of a token: 24 per lane, x 4 lane groups (g), x 4 feature quarters.  Sum and
-    // sum of squares in ONE sweep and ONE exchange through LDS (variance = E[x^2] - mean^2 in fp32: the inputs
-    // are residual-stream values of order 1 with |mean| << spread, the cancellation costs ~1e-6 relative): the
-    // two-sweep form had a second barrier and a second LDS round trip on every workgroup's critical path.
-    // (The cross-lane sums stay __shfl_xor: as v_permlane16/32_swap pair sums they measured 4 600 against 5 000
-    // cycles for this block -- and the BUILTIN fed one value twice is folded by hipcc 7.2 into x + x, wrong
-    // statistics with no diagnostic; only the inline-asm form is usable for that.)
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int ft = 0; ft < 6; ++ft)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float v = acc[ft][tt][j];
-          s1 += v;
-          s2 = fmaf(v, v, s2);
-        }
-      s1 += __shfl_xor(s1, 16);
-      s2 += __shfl_xor(s2, 16);
-      s1 += __shfl_xor(s1, 32);
-      s2 += __shfl_xor(s2, 32);
-      if (g == 0) {
-        red[(0 * 4 + wn) * GT_TOK + 64 * wm + 16 * tt + c16] = s1;
-        red[(1 * 4 + wn) * GT_TOK + 64 * wm + 16 * tt + c16] = s2;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt) {
-      const int tk = 64 * wm + 16 * tt + c16;
-      const float t1 = (red[(0 * 4 + 0) * GT_TOK + tk] + red[(0 * 4 + 1) * GT_TOK + tk]) +
-                       (red[(0 * 4 + 2) * GT_TOK + tk] + red[(0 * 4 + 3) * GT_TOK + tk]);
-      const float t2 = (red[(1 * 4 + 0) * GT_TOK + tk] + red[(1 * 4 + 1) * GT_TOK + tk]) +
-                       (red[(1 * 4 + 2) * GT_TOK + tk] + red[(1 * 4 + 3) * GT_TOK + tk]);
-      mu[tt] = t1 * (1.f / HID);
-      rstd[tt] = rsqrtf(fmaxf(t2 * (1.f / HID) - mu[tt] * mu[tt], 0.f) + eps);
-    }
-  }
-  if (dbg) {
-    asm volatile("" : "+v"(mu[0]), "+v"(rstd[3]));
-    ts_e2 = __builtin_amdgcn_s_memtime();   // LayerNorm statistics known
-  }
-  // Stores: 16 bytes per lane.  A lane holds 4 consecutive features (8 bytes) of each token tile; the 16-byte slot
-  // (token, 8 features) of the tiled layout is split between lanes g and g ^ 1.  v_permlane16_swap between the
-  // packed values of tile 2 tp (vdst) and tile 2 tp + 1 (src) leaves lanes with g even holding the whole slot of
-  // THEIR token of tile 2 tp and lanes with g odd that of tile 2 tp + 1 -- and the wave's 64 slots are then one
-  // whole fragment, lane-linear: 12 global_store_dwordx4 per wave instead of 24 dwordx2 (cdna_hip_programming.md
-  // T21; here worth little by itself -- the epilogue's 12-13 k cycles per tile are a memory round trip for the
-  // residual (4-5 k), the LayerNorm statistics with their shuffles, LDS exchange and barrier (5 k) and the
-  // normalise + store pass (3 k): stamps).
-#pragma unroll
-  for (int ft = 0; ft < 6; ++ft) {
-    const half4 gv = gvs[ft], be = bes[ft];
-#pragma unroll
-    for (int tp = 0; tp < 2; ++tp) {
-      uint2 pk[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int tt = 2 * tp + u;
-        half4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float v = acc[ft][tt][j];
-          if (EPI == EPI_BIAS_RES_LN) v = (v - mu[tt]) * rstd[tt] * (float)gv[j] + (float)be[j];
-          o[j] = (_Float16)v;
-        }
-        pk[u] = __builtin_bit_cast(uint2, o);
-      }
-      const auto sx = __builtin_amdgcn_permlane16_swap(pk[0].x, pk[1].x, false, false);
-      const auto sy = __builtin_amdgcn_permlane16_swap(pk[0].y, pk[1].y, false, false);
-      const int token = t0 + 64 * wm + 16 * (2 * tp + (g & 1)) + c16;   // the token whose slot this lane now holds
-      if (token < M)
-        *(uint4*)(out + ((size_t)((t0 >> 5) + 2 * wm + tp) * (ldo / 16) + (n0 >> 4) + 6 * wn + ft) * 512 + lane * 8) =
-            make_uint4(sx[0], sy[0], sx[1], sy[1]);
-    }
-  }
-  if (dbg && lane == 0) {
-    const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (wg < 512) {   // the buffer holds 4096 waves x 8 floats
-      float* d = dbg + (wg * 8 + wave) * 8;
-      const uint64_t te = __builtin_amdgcn_s_memtime();
-      d[0] = (float)(te - ts_entry);        // cycles, whole wave
-      d[1] = (float)(ts_loop - ts_entry);   // prologue (first three stages' pieces, first wait)
-      d[2] = (float)(ts_epi - ts_loop);     // the stage loop
-      d[3] = (float)t_wait;                 // of it: vmcnt wait + barrier
-      d[4] = (float)(te - ts_epi);          // epilogue
-      d[5] = (float)NST;
-      d[6] = (float)(ts_e1 - ts_epi);       // of the epilogue: until bias + residual are in
-      d[7] = (float)(ts_e2 - ts_e1);        // ... the LayerNorm statistics (the rest: normalise + store)
-    }
   }
 }
 
@@ -1404,7 +1053,7 @@ __device__ __forceinline__ float att_max3(float a, float b, float c) {
 // scores of a (query block, head) item stay in registers between the two products -- 16 KB registers -- and
 // the kernel is latency-bound (10 % matrix pipe busy), so short batches (the ingest buckets are sorted by
 // length) take an instantiation with fewer registers and more waves per SIMD instead of the T = 256 one.
-template <int KB, int WPS, int NH, int NHALF>   // NH = heads per workgroup (1 | 2); NHALF = groups the key blocks are taken in
+template <int KB, int WPS, int NH, int NHALF>   // NH = heads per workgroup (1: the only instantiation); NHALF = groups the key blocks are taken in
 __global__ void __launch_bounds__(256, WPS) k_attention_mfma(const _Float16* __restrict__ qkv,
                                                         const int32_t* __restrict__ tok_off,
                                                         _Float16* __restrict__ ctx, float* __restrict__ dbg) {
@@ -1415,7 +1064,7 @@ __global__ void __launch_bounds__(256, WPS) k_attention_mfma(const _Float16* __r
   // a workgroup serves NH heads of one sequence: the (head, query block) items are dealt round-robin to the 4
   // waves.  NH = 1 is the product's choice: half the LDS per workgroup lets a third workgroup share the CU at
   // T = 256 (3 waves per SIMD), and the kernel's time is waiting -- staging latency, LDS and MFMA drains -- not
-  // issue: +2 % on the whole encoder against NH = 2 (A/B in one process, tools/bench_encode.py --tune att_heads=).
+  // issue: +2 % on the whole encoder against NH = 2 (only NH = 1 is instantiated).
   const int b = blockIdx.x, head0 = blockIdx.y * NH;
   const int r0 = tok_off[b];
   const int n = tok_off[b + 1] - r0;
@@ -1819,103 +1468,83 @@ __global__ void __launch_bounds__(256) k_pool_norm(const _Float16* __restrict__ 
   }
 }
 
+// The instantiations of k_attention_mfma: <key blocks, minimum waves per SIMD the register budget must allow,
+// one head per workgroup, groups of key blocks>
+struct AttKernel {
+  void (*fn)(const _Float16*, const int32_t*, _Float16*, float*);
+  rf_lds_attr* attr;   // per instantiation, per device
+};
+static AttKernel attention_kernel(int key_blocks) {
+  switch (key_blocks) {
+#define RF_ATT_CASE(KB_, WPS, NHF)                          \
+  case KB_: {                                               \
+    static rf_lds_attr a_;                                  \
+    return {k_attention_mfma<KB_, WPS, 1, NHF>, &a_};       \
+  }
+    RF_ATT_CASE(1, 6, 1)
+    RF_ATT_CASE(2, 6, 1)
+    RF_ATT_CASE(4, 4, 1)
+    RF_ATT_CASE(6, 4, 2)
+    default: RF_ATT_CASE(8, 4, 2)
+#undef RF_ATT_CASE
+  }
+}
+
 // ---- forward pass -----------------------------------------------------------------------
-// the LayerNorm-fused GEMMs have only 384 output features (one feature group), so
-// they take 32-token tiles to put twice as many workgroups on the chip
-template <int EPI>
-static void launch_linear(const _Float16* X, int K, const uint4* Wt, const _Float16* bias,
-                          _Float16* out, int N, int tokens, const int32_t* m_ptr, const _Float16* res,
-                          const _Float16* g, const _Float16* b, float eps, float* pre, hipStream_t st) {
-  constexpr int NTB = 2;
-  const int tiles = (tokens + 32 * NTB - 1) / (32 * NTB);
+// One launcher per (epilogue, K) pair of the layer: only the pairs that occur are instantiated.
+template <int EPI, int KS>   // KS = K / 16: 24 (QKV, out-projection, FFN1) | 96 (FFN2)
+static void launch_linear(const _Float16* X, const uint4* Wt, const _Float16* bias, _Float16* out, int N, int tokens,
+                          const int32_t* m_ptr, const _Float16* res, const _Float16* g, const _Float16* b, float eps,
+                          float* pre, hipStream_t st) {
   if (tokens <= SM_MAX_TOK && rf_knob_linear_small) {
     // small batches: output features spread over the chip (k_linear_small), LayerNorm as its own launch
     const dim3 grid(N / 32, (tokens + SM_TOK - 1) / SM_TOK);
     constexpr int E = (EPI == EPI_BIAS_RES_LN) ? (int)EPI_PRE_LN : (int)EPI;
-    if (K == 384)
-      hipLaunchKernelGGL((k_linear_small<E, 24>), grid, dim3(256), 0, st, X, Wt, bias, out, pre, N, m_ptr, res);
-    else
-      hipLaunchKernelGGL((k_linear_small<E, 96>), grid, dim3(256), 0, st, X, Wt, bias, out, pre, N, m_ptr, res);
+    hipLaunchKernelGGL((k_linear_small<E, KS>), grid, dim3(256), 0, st, X, Wt, bias, out, pre, N, m_ptr, res);
     if (EPI == EPI_BIAS_RES_LN)
       hipLaunchKernelGGL(k_ln_rows, dim3((tokens + 3) / 4), dim3(256), 0, st, pre, m_ptr, g, b, eps, out);
     return;
   }
-  // bit per GEMM of a layer: 1 = FFN2 + LayerNorm (K 1536), 2 = out-projection + LayerNorm, 4 = QKV, 8 = FFN1
-  const int gt_bit = (K != 384) ? 1 : (EPI == EPI_BIAS_RES_LN ? 2 : (EPI == EPI_BIAS ? 4 : 8));
-  if ((rf_knob_gemm_tile & gt_bit) && tokens >= 8192) {
-    const size_t lds = (size_t)GT_SLOTS * GT_STAGE_FRAGS * RF_FRAG_BYTES + RF_FRAG_BYTES + (size_t)2 * 4 * GT_TOK * 4;
-    const dim3 grid((tokens + GT_TOK - 1) / GT_TOK, N / 384);
-#define RF_GT_LAUNCH(KS_, D_)                                                                                   \
-  do {                                                                                                         \
-    static rf_lds_attr attr_;                                                                                  \
-    (void)rf_ensure_lds(attr_, (const void*)k_gemm_tile<EPI, KS_, D_>, lds);                                   \
-    hipLaunchKernelGGL((k_gemm_tile<EPI, KS_, D_>), grid, dim3(512), lds, st, X, Wt, bias, out, N, m_ptr, res, g, b, eps, gt_dbg); \
-  } while (0)
-    // clock stamps (experiments build): debug_epi 3 = the K = 1536 GEMM (FFN2), 4 = the K = 384 one (out-projection)
-    float* const gt_dbg = (rf_knob_debug_epi == (K == 384 ? 4 : 3)) ? (float*)rf_debug_buffer : nullptr;
-#ifdef RF_EXPERIMENTS
-    if (rf_knob_gemm_tile_dma == 2) {
-      if (K == 384) RF_GT_LAUNCH(24, 2);
-      else RF_GT_LAUNCH(96, 2);
-    } else
-#endif
-    if (rf_knob_gemm_tile_dma == 1) {
-      if (K == 384) RF_GT_LAUNCH(24, 1);
-      else RF_GT_LAUNCH(96, 1);
-    } else {
-      if (K == 384) RF_GT_LAUNCH(24, 0);
-      else RF_GT_LAUNCH(96, 0);
-    }
-#undef RF_GT_LAUNCH
-    return;
-  }
-  if (K == 384 && EPI != EPI_BIAS_RES_LN && rf_knob_linear_dma && tokens >= 8192) {
-    const size_t lds = (size_t)LD_SLOTS * LD_FRAGS * RF_FRAG_BYTES + RF_FRAG_BYTES + (size_t)N * 4;   // ring + dump + fp32 bias
-    constexpr int E = (EPI == EPI_BIAS_GELU ? EPI_BIAS_GELU : EPI_BIAS);
-    // 256-token workgroups once they still fill the chip (>= 256 of them would need 64 k tokens;
-    // from ~48 k the halved weight traffic and per-wave overhead outweigh the idle CUs)
-    const bool wide = rf_knob_linear_dma == 2 || (rf_knob_linear_dma == 1 && tokens >= 49152);   // 3: never
-    float* dbgp = (rf_knob_debug_epi == (int)EPI) ? (float*)rf_debug_buffer : nullptr;
-    const dim3 grid_w((tokens + 2 * LD_TOK - 1) / (2 * LD_TOK)), grid_n((tokens + LD_TOK - 1) / LD_TOK), block(LD_WAVES * 64);
+  if constexpr (EPI == EPI_BIAS && KS == HID / 16) {
+    if (rf_knob_linear_dma && tokens >= 8192) {
+      const size_t lds = (size_t)LD_SLOTS * LD_FRAGS * RF_FRAG_BYTES + RF_FRAG_BYTES + (size_t)N * 4;   // ring + dump + fp32 bias
+      // 256-token workgroups once they still fill the chip (>= 256 of them would need 64 k tokens;
+      // from ~48 k the halved weight traffic and per-wave overhead outweigh the idle CUs)
+      const bool wide = rf_knob_linear_dma == 2 || (rf_knob_linear_dma == 1 && tokens >= 49152);   // 3: never
+      float* dbgp = (rf_knob_debug_epi == 0) ? (float*)rf_debug_buffer : nullptr;   // clock stamps (experiments build)
+      const dim3 grid_w((tokens + 2 * LD_TOK - 1) / (2 * LD_TOK)), grid_n((tokens + LD_TOK - 1) / LD_TOK), block(LD_WAVES * 64);
 #define RF_LD_LAUNCH(W, A)                                                                                     \
   do {                                                                                                         \
     static rf_lds_attr attr_;   /* per instantiation, per device */                                            \
-    (void)rf_ensure_lds(attr_, (const void*)k_linear_dma<E, W, A>, lds);                                       \
-    hipLaunchKernelGGL((k_linear_dma<E, W, A>), (W) ? grid_w : grid_n, block, lds, st, X, Wt, bias, out, N, m_ptr, dbgp); \
+    (void)rf_ensure_lds(attr_, (const void*)k_linear_dma<W, A>, lds);                                          \
+    hipLaunchKernelGGL((k_linear_dma<W, A>), (W) ? grid_w : grid_n, block, lds, st, X, Wt, bias, out, N, m_ptr, dbgp); \
   } while (0)
 #ifdef RF_EXPERIMENTS
-    if (wide && rf_knob_linear_dbg) {   // ablations of the wide form (results wrong)
-      switch (rf_knob_linear_dbg) {
-        case 1: RF_LD_LAUNCH(1, 1); return;
-        case 2: RF_LD_LAUNCH(1, 2); return;
-        case 4: RF_LD_LAUNCH(1, 4); return;
-        case 8: RF_LD_LAUNCH(1, 8); return;
-        case 12: RF_LD_LAUNCH(1, 12); return;
-        case 16: RF_LD_LAUNCH(1, 16); return;
-        case 32: RF_LD_LAUNCH(1, 32); return;
-        case 48: RF_LD_LAUNCH(1, 48); return;
-        case 50: RF_LD_LAUNCH(1, 50); return;
-        default: break;
+      if (wide && rf_knob_linear_dbg) {   // ablations of the wide form (results wrong)
+        switch (rf_knob_linear_dbg) {
+          case 1: RF_LD_LAUNCH(1, 1); return;
+          case 2: RF_LD_LAUNCH(1, 2); return;
+          case 4: RF_LD_LAUNCH(1, 4); return;
+          case 8: RF_LD_LAUNCH(1, 8); return;
+          case 12: RF_LD_LAUNCH(1, 12); return;
+          case 16: RF_LD_LAUNCH(1, 16); return;
+          case 32: RF_LD_LAUNCH(1, 32); return;
+          case 48: RF_LD_LAUNCH(1, 48); return;
+          case 50: RF_LD_LAUNCH(1, 50); return;
+          default: break;
+        }
       }
-    }
 #endif
-    if (wide) RF_LD_LAUNCH(1, 0);
-    else RF_LD_LAUNCH(0, 0);
+      if (wide) RF_LD_LAUNCH(1, 0);
+      else RF_LD_LAUNCH(0, 0);
 #undef RF_LD_LAUNCH
-    return;
+      return;
+    }
   }
-  if (K == 384 && rf_knob_k384_ntb == 4 && tokens >= 8192)   // 128-token tiles
-    hipLaunchKernelGGL((k_linear<EPI, 4, 24>), dim3((tokens + 127) / 128, N / 384), dim3(256), 0, st, X, K, Wt, bias,
-                       out, N, m_ptr, res, g, b, eps);
-  else if (K == 384)
-    hipLaunchKernelGGL((k_linear<EPI, NTB, 24>), dim3(tiles, N / 384), dim3(256), 0, st, X, K, Wt, bias, out,
-                       N, m_ptr, res, g, b, eps);
-  else if (rf_knob_ffn2_ntb == 4 && tokens >= 8192)   // experiment: 128-token tiles for the K = 1536 GEMM
-    hipLaunchKernelGGL((k_linear<EPI, 4, 96>), dim3((tokens + 127) / 128, N / 384), dim3(256), 0, st, X, K, Wt, bias,
-                       out, N, m_ptr, res, g, b, eps);
-  else   // K == 1536 (checked by rf_encoder_create: intermediate == 4 * hidden is the only other K)
-    hipLaunchKernelGGL((k_linear<EPI, NTB, 96>), dim3(tiles, N / 384), dim3(256), 0, st, X, K, Wt, bias, out,
-                       N, m_ptr, res, g, b, eps);
+  constexpr int NTB = 2;   // 64-token tiles
+  const int tiles = (tokens + 32 * NTB - 1) / (32 * NTB);
+  hipLaunchKernelGGL((k_linear<EPI, NTB, KS>), dim3(tiles, N / 384), dim3(256), 0, st, X, KS * 16, Wt, bias, out, N,
+                     m_ptr, res, g, b, eps);
 }
 
 static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
@@ -2051,32 +1680,12 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
   const size_t attn_lds = (size_t)T * 2 * HEAD_DIM * 2;
   static rf_lds_attr attn_attr;
   if (T > 32 * ATT_MAX_KB) RF_HIP(rf_ensure_lds(attn_attr, (const void*)k_attention, attn_lds));
-  // instantiation by the batch's width: <key blocks, minimum waves per SIMD the register budget must allow, heads
-  // per workgroup>
+  // instantiation by the batch's width
   const int att_kb = T <= 32 ? 1 : (T <= 64 ? 2 : (T <= 128 ? 4 : (T <= 192 ? 6 : 8)));   // a query is one key block
-  const int att_nh = rf_knob_att_heads;
   const size_t att_tp = (size_t)att_kb * 32;   // the kernel's LDS image has the instantiation's shape
-  const size_t mfma_lds = att_nh * (att_tp * 80 + (size_t)32 * (att_tp + 4) * 2);  // 37 KB per head at T = 256
-#define RF_ATT_CASE(KB_, W2, W1, NHF)                                                                                \
-  case KB_: {                                                                                                    \
-    static rf_lds_attr a2_, a1_;   /* per instantiation, per device */                                           \
-    if (att_nh == 2) {                                                                                           \
-      RF_HIP(rf_ensure_lds(a2_, (const void*)k_attention_mfma<KB_, W2, 2, NHF>, mfma_lds));                           \
-    } else {                                                                                                     \
-      RF_HIP(rf_ensure_lds(a1_, (const void*)k_attention_mfma<KB_, W1, 1, NHF>, mfma_lds));                           \
-    }                                                                                                            \
-  } break;
-  if (T <= 32 * ATT_MAX_KB) {
-    switch (att_kb) {
-      RF_ATT_CASE(1, 4, 6, 1)
-      RF_ATT_CASE(2, 4, 6, 1)
-      RF_ATT_CASE(4, 3, 4, 1)
-      RF_ATT_CASE(6, 3, 4, 2)
-      RF_ATT_CASE(8, 3, 4, 2)
-      default: break;
-    }
-  }
-#undef RF_ATT_CASE
+  const size_t mfma_lds = att_tp * 80 + (size_t)32 * (att_tp + 4) * 2;  // 37 KB at T = 256
+  const AttKernel att = attention_kernel(att_kb);
+  if (T <= 32 * ATT_MAX_KB) RF_HIP(rf_ensure_lds(*att.attr, (const void*)att.fn, mfma_lds));
   float* const att_dbg = (rf_knob_debug_epi == 2) ? (float*)rf_debug_buffer : nullptr;   // clock stamps (experiments build)
   const bool one_query = rf_knob_one_query && B == 1 && T <= 32 && rf_knob_linear_small;
   _Float16* x = ws.x;
@@ -2091,27 +1700,10 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
                          (const _Float16*)w.qkv_b + (size_t)l * 3 * HID, m_ptr, ws.ctx);
     } else {
     if (!(l > 0 && rf_knob_post_block && rf_knob_post_qkv && tiles >= 8192))   // else: written by the previous layer's k_post_block
-    launch_linear<EPI_BIAS>(x, HID, qkv_t, (const _Float16*)w.qkv_b + (size_t)l * 3 * HID, ws.qkv,
-                            3 * HID, tiles, m_ptr, nullptr, nullptr, nullptr, 0.f, ws.pre, st);
-    if (T <= 32 * ATT_MAX_KB) {
-      const dim3 ag(B, c.heads / att_nh);
-#define RF_ATT_CASE(KB_, W2, W1, NHF)                                                                                        \
-  case KB_:                                                                                                              \
-    if (att_nh == 2)                                                                                                     \
-      hipLaunchKernelGGL((k_attention_mfma<KB_, W2, 2, NHF>), ag, dim3(256), mfma_lds, st, ws.qkv, ws.tok_off, ws.ctx, att_dbg); \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((k_attention_mfma<KB_, W1, 1, NHF>), ag, dim3(256), mfma_lds, st, ws.qkv, ws.tok_off, ws.ctx, att_dbg); \
-    break;
-      switch (att_kb) {
-        RF_ATT_CASE(1, 4, 6, 1)
-        RF_ATT_CASE(2, 4, 6, 1)
-        RF_ATT_CASE(4, 3, 4, 1)
-        RF_ATT_CASE(6, 3, 4, 2)
-        RF_ATT_CASE(8, 3, 4, 2)
-        default: break;
-      }
-#undef RF_ATT_CASE
-    }
+    launch_linear<EPI_BIAS, HID / 16>(x, qkv_t, (const _Float16*)w.qkv_b + (size_t)l * 3 * HID, ws.qkv,
+                                      3 * HID, tiles, m_ptr, nullptr, nullptr, nullptr, 0.f, ws.pre, st);
+    if (T <= 32 * ATT_MAX_KB)
+      hipLaunchKernelGGL(att.fn, dim3(B, c.heads), dim3(256), mfma_lds, st, ws.qkv, ws.tok_off, ws.ctx, att_dbg);
     else
       hipLaunchKernelGGL(k_attention, dim3(B, c.heads), dim3(256), attn_lds, st, ws.qkv, ws.tok_off,
                          ws.ctx);
@@ -2135,14 +1727,14 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
       y = t_;
       continue;
     }
-    launch_linear<EPI_BIAS_RES_LN>(ws.ctx, HID, ao_t, (const _Float16*)w.ao_b + (size_t)l * HID, y, HID,
-                                   tiles, m_ptr, x, (const _Float16*)w.ln1_g + (size_t)l * HID,
-                                   (const _Float16*)w.ln1_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
-    launch_linear<EPI_BIAS_GELU>(y, HID, ff1_t, (const _Float16*)w.ff1_b + (size_t)l * I, ws.ff, I,
-                                 tiles, m_ptr, nullptr, nullptr, nullptr, 0.f, ws.pre, st);
-    launch_linear<EPI_BIAS_RES_LN>(ws.ff, I, ff2_t, (const _Float16*)w.ff2_b + (size_t)l * HID, x, HID,
-                                   tiles, m_ptr, y, (const _Float16*)w.ln2_g + (size_t)l * HID,
-                                   (const _Float16*)w.ln2_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
+    launch_linear<EPI_BIAS_RES_LN, HID / 16>(ws.ctx, ao_t, (const _Float16*)w.ao_b + (size_t)l * HID, y, HID,
+                                             tiles, m_ptr, x, (const _Float16*)w.ln1_g + (size_t)l * HID,
+                                             (const _Float16*)w.ln1_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
+    launch_linear<EPI_BIAS_GELU, HID / 16>(y, ff1_t, (const _Float16*)w.ff1_b + (size_t)l * I, ws.ff, I,
+                                           tiles, m_ptr, nullptr, nullptr, nullptr, 0.f, ws.pre, st);
+    launch_linear<EPI_BIAS_RES_LN, 4 * HID / 16>(ws.ff, ff2_t, (const _Float16*)w.ff2_b + (size_t)l * HID, x, HID,
+                                                 tiles, m_ptr, y, (const _Float16*)w.ln2_g + (size_t)l * HID,
+                                                 (const _Float16*)w.ln2_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
   }
   hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(256), 0, st, x, ws.tok_off, (_Float16*)out_f16_dev,
                      out_f32_dev);

@@ -410,7 +410,7 @@ __global__ void __launch_bounds__(PB_WAVES * 64, 1) RF_NO_PACKED_FP32 k_post_blo
     t1 += __shfl_xor(t1, 32);
     t2 += __shfl_xor(t2, 32);
     const float mu = t1 * inv_h;
-    // E[v^2] - mu^2 in fp32: residual-stream values of order 1 with |mu| << spread (as k_gemm_tile)
+    // E[v^2] - mu^2 in fp32: residual-stream values of order 1 with |mu| << spread
     sc = rsqrtf(fmaxf(t2 * inv_h - mu * mu, 0.f) + a.eps);
     sh = -mu * sc;
   };

@@ -49,36 +49,34 @@ struct rf_index {
 // The shipped library has NO run-time tuning surface: every knob below is a compile-time
 // constant.  Built with -DRF_EXPERIMENTS (python -m rag_fin_amd.build --experiments ->
 // libragfin_hip_exp.so, used by tools/ only) the same names are process-wide ints set through
-// rf_set_tuning, for A/B runs in one process.
+// rf_set_tuning (api.hip), for A/B runs in one process.  ONE list: X(name, default, low, high)
+// gives the constant rf_knob_<name> here, and the variable and the rf_set_tuning key "<name>"
+// with its range in api.hip.
+#define RF_KNOBS(X)                                                                                                  \
+  X(ring24, 8, 6, 24)            /* register-ring depth (fragments) of the dim-384 emit sweep: 6 | 8 | 12 | 24 */    \
+  X(emit_wgs_per_cu, 0, 0, 4)    /* emit grid = CUs x this (0 = default for the dim) */                              \
+  X(sample_bpw, 2, 1, 8)         /* sample blocks per wave */                                                        \
+  X(sample_fold, 1, 0, 1)        /* 64-query sweep: the emit skips the sampled blocks (k_threshold appends what the sample kept) */ \
+  X(fold_dbg, 0, 0, 3)           /* sample fold diagnostics: 1 = every kept list counts as incomplete (all rescanned), 2 = k_merge leaves the candidate counters */ \
+  X(wide_sample_pairs, 4, 1, 8)  /* wide sample pass: block pairs per workgroup, at most */                          \
+  X(wide_dbg, 0, 0, 63)          /* wide sweep diagnostic bits (clock stamps, ablations: scan_wide.hip, dispatch_w16) */ \
+  X(wide_ne, 0, 0, 112)          /* wide sweep: LDS-DMA pieces per phase of waves 0-3 (0 = the product's split) */   \
+  X(linear_dma, 1, 0, 3)         /* encoder: layer 0's QKV GEMM through the LDS-DMA ring at >= 8192 token slots (0 off, 1 auto, 2 always 256-token, 3 never 256-token) */ \
+  X(linear_small, 1, 0, 1)       /* encoder: feature-split GEMMs + separate LayerNorm at <= 1024 token slots */      \
+  X(encode_graph, 1, 0, 1)       /* encoder: query-sized forwards replay a cached hipGraph */                        \
+  X(linear_dbg, 0, 0, 63)        /* encoder: k_linear_dma ablation bits (results wrong) */                           \
+  X(debug_epi, 0, 0, 5)          /* encoder: which kernel writes clock stamps (0 QKV k_linear_dma, 2 attention, 5 post block; 1, 3, 4 stamped kernels that are gone and select none) */ \
+  X(one_query, 1, 0, 1)          /* encoder: a single sequence of <= 32 tokens takes the fused QKV + attention launch */ \
+  X(post_block, 1, 0, 1)         /* encoder: out-projection + MLP of a layer as one launch at >= 8192 token slots (encoder_post.hip) */ \
+  X(post_qkv, 1, 0, 1)           /* encoder: k_post_block also computes the next layer's QKV projection */           \
+  X(post_dbg, 0, 0, 511)         /* encoder: k_post_block ablation bits (results wrong) */
 #ifdef RF_EXPERIMENTS
-#define RF_KNOB(name, dflt) extern int name;
+#define RF_KNOB_DECL(name, dflt, lo, hi) extern int rf_knob_##name;
 #else
-#define RF_KNOB(name, dflt) static constexpr int name = dflt;
+#define RF_KNOB_DECL(name, dflt, lo, hi) static constexpr int rf_knob_##name = dflt;
 #endif
-RF_KNOB(rf_knob_ring24, 8)             // register-ring depth (fragments) of the dim-384 emit sweep: 6 | 8 | 12 | 24
-RF_KNOB(rf_knob_emit_wgs_per_cu, 0)    // emit grid = CUs x this (0 = default for the dim)
-RF_KNOB(rf_knob_sample_bpw, 2)         // sample blocks per wave
-RF_KNOB(rf_knob_sample_fold, 1)        // 64-query sweep: the emit skips the sampled blocks (k_threshold appends what the sample kept)
-RF_KNOB(rf_knob_fold_dbg, 0)           // sample fold diagnostics: 1 = every kept list counts as incomplete (all rescanned), 2 = k_merge leaves the candidate counters
-RF_KNOB(rf_knob_wide_sample_pairs, 4)  // wide sample pass: block pairs per workgroup, at most
-RF_KNOB(rf_knob_wide_dbg, 0)           // wide sweep diagnostic bits (clock stamps, cached-KiB ablation)
-RF_KNOB(rf_knob_wide_form, 0)          // wide sweep kernel: 0 = eight waves x 32 queries (k_scan_w16), 1 = four waves x 64 queries (k_scan_w64)
-RF_KNOB(rf_knob_wide_ne, 0)            // wide sweep: LDS-DMA pieces per phase of waves 0-3 (0 = the product's split)
-RF_KNOB(rf_knob_linear_dma, 1)         // encoder: K = 384 plain-epilogue GEMMs through the LDS-DMA ring (0 off, 1 auto, 2 always 256-token, 3 never 256-token)
-RF_KNOB(rf_knob_linear_small, 1)       // encoder: feature-split GEMMs + separate LayerNorm at <= 1024 token slots
-RF_KNOB(rf_knob_k384_ntb, 4)           // encoder: token blocks per workgroup of the K = 384 LayerNorm GEMM at large batch
-RF_KNOB(rf_knob_ffn2_ntb, 4)           // encoder: the same for the K = 1536 LayerNorm GEMM
-RF_KNOB(rf_knob_gemm_tile, 3)          // encoder: GEMMs on k_gemm_tile (both operands through the LDS-DMA ring): 1 FFN2, 2 out-proj, 4 QKV, 8 FFN1
-RF_KNOB(rf_knob_encode_graph, 1)       // encoder: query-sized forwards replay a cached hipGraph
-RF_KNOB(rf_knob_linear_dbg, 0)         // encoder: k_linear_dma ablation bits (results wrong)
-RF_KNOB(rf_knob_debug_epi, 1)          // encoder: which kernel writes clock stamps (0 QKV, 1 FFN1, 2 attention, 3 FFN2, 4 out-projection, 5 post block)
-RF_KNOB(rf_knob_att_heads, 1)          // encoder: heads per attention workgroup (1 | 2)
-RF_KNOB(rf_knob_one_query, 1)          // encoder: a single sequence of <= 32 tokens takes the fused QKV + attention launch
-RF_KNOB(rf_knob_post_block, 1)         // encoder: out-projection + MLP of a layer as one launch at >= 8192 token slots (encoder_post.hip)
-RF_KNOB(rf_knob_post_qkv, 1)           // encoder: k_post_block also computes the next layer's QKV projection
-RF_KNOB(rf_knob_post_dbg, 0)           // encoder: k_post_block ablation bits (results wrong)
-RF_KNOB(rf_knob_gemm_tile_dma, 0)      // encoder: k_gemm_tile LDS-DMA issue: 0 = halves take turns, 8 pieces in a burst (product); 1 = every wave 4 pieces between its MFMAs; 2 = none (ablation)
-#undef RF_KNOB
+RF_KNOBS(RF_KNOB_DECL)
+#undef RF_KNOB_DECL
 #ifdef RF_EXPERIMENTS
 extern int rf_tuning_generation;   // bumped by rf_set_tuning: cached encode graphs of older settings are not replayed
 extern void* rf_debug_buffer;      // rf_debug_set_buffer: clock stamps of the diagnostic runs

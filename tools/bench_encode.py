@@ -22,10 +22,10 @@ def main():
     ap.add_argument("--batch-tokens", type=int, default=65536)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--fixed-len", type=int, default=0)
-    ap.add_argument("--tune", default="", help="rf_set_tuning pairs, e.g. ffn2_ntb=4,linear_dma=0")
+    ap.add_argument("--tune", default="", help="rf_set_tuning pairs, e.g. post_block=0,linear_dma=0")
     ap.add_argument("--texts", action="store_true", help="also time the text -> tokenizer -> encoder path")
     ap.add_argument("--stamps", action="store_true", help="clock stamps of the last k_linear_dma launch")
-    ap.add_argument("--stamp-epi", type=int, default=1, help="0 = QKV, 1 = FFN1, 2 = attention, 3 = FFN2, 4 = out-projection, 5 = post block")
+    ap.add_argument("--stamp-epi", type=int, default=0, choices=(0, 2, 5), help="0 = QKV (k_linear_dma), 2 = attention, 5 = post block")
     ap.add_argument("--linear-dbg", type=int, default=0, help="ablation bits of k_linear_dma (results wrong)")
     args = ap.parse_args()
     import torch
@@ -108,21 +108,10 @@ def main():
                       (name, ok.sum(), np.median(tot / ticks) * 0.1, np.median(tot), np.median(pro), np.median(pa), np.median(pa) / 6, np.median(l1),
                        np.median(pb), np.median(pb) / 50, np.median(l2), np.median(wait) / 56))
             return
-        if args.stamp_epi in (3, 4):   # k_gemm_tile: [workgroup][wave] x {cycles, prologue, loop, wait in loop, epilogue, stages}
-            st = buf.view(512, 8, 8).cpu().numpy()
-            ok = st[..., 0] > 0
-            tot, pro, loop, wait, epi, nst, e1, e2 = (st[..., i][ok] for i in range(8))
-            print("k_gemm_tile stamps (last launch of the %s GEMM, %d waves): wave %.0f cycles = prologue %.0f + %d stages x %.0f "
-                  "(of which vmcnt wait + barrier %.0f) + epilogue %.0f (loads + bias + residual %.0f, LayerNorm statistics %.0f, "
-                  "normalise + store %.0f)" %
-                  ("K = 1536" if args.stamp_epi == 3 else "K = 384", ok.sum(), np.median(tot), np.median(pro), int(nst.max()),
-                   np.median(loop / nst), np.median(wait / nst), np.median(epi), np.median(e1), np.median(e2),
-                   np.median(epi - e1 - e2)))
-            return
         st = buf.view(512, 8, 8).cpu().numpy()
         ok = st[..., 1] > 0
         cyc, ticks, pre, wait, nph = (st[..., i][ok] for i in range(5))
-        print("stamps (last k_linear_dma launch of the chosen epilogue, %d waves): clock %.2f GHz; kernel %.1f us; "
+        print("stamps (last k_linear_dma launch, %d waves): clock %.2f GHz; kernel %.1f us; "
               "prologue %.0f cycles; loop %.0f cycles/phase (%d phases); wait+barrier share %.1f %%" %
               (ok.sum(), np.median(cyc / ticks) * 0.1, np.median(ticks) / 100.0, np.median(pre),
                np.median((cyc - pre) / nph), int(nph.max()), 100.0 * np.median(wait / cyc)))

@@ -1,7 +1,7 @@
 // Micro-benchmark (diagnostic, not product): cycles per v_mfma_f32_32x32x16_f16 by the register file each operand
 // sits in -- accumulator (C / D) in the vector half or the accumulator half, B in the vector half or the accumulator
 // half; A always fresh from LDS (ds_read_b128), four rotating accumulation chains, one wave per SIMD.
-// (k_scan_w64 keeps its B operands -- the queries -- in the accumulator half and its accumulators in the vector half.)
+// (The removed k_scan_w64 kept its B operands -- the queries -- in the accumulator half and its accumulators in the vector half.)
 //   hipcc --offload-arch=gfx950 -O3 -o mfma_regfile tools/ubench/mfma_regfile.hip && ./mfma_regfile
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -1,4 +1,4 @@
-// Micro-benchmark (diagnostic, not product): the inner loop of k_scan_w64 (csrc/scan_wide.hip) taken apart.  One wave per
+// Micro-benchmark (diagnostic, not product): the inner loop of k_scan_w64 taken apart (the kernel was removed from csrc/scan_wide.hip; DESIGN.md 4.1b, git history).  One wave per
 // SIMD, 192 resident query registers in the accumulator half, the corpus slot in LDS read through run_step's pair ring
 // (csrc/lds_ring.h), per fragment two inline-asm MFMAs on four rotating vector-register accumulators.  Variants add
 // the pieces of the real loop one at a time: V0 MFMAs + reads only | V1 + a barrier per phase | V2 + the filter's 64
@@ -128,7 +128,7 @@ int main() {
   (void)hipMemcpy(w, hw.data(), nw * 16, hipMemcpyHostToDevice);
   (void)hipMemcpy(x, hx.data(), nx * 16, hipMemcpyHostToDevice);
   const int phases = 4000;
-  printf("%s, %d CUs: the k_scan_w64 loop piece by piece (96 MFMAs per phase and wave)\n", p.gcnArchName, cus);
+  printf("%s, %d CUs: the four-wave x 64-query sweep loop (removed k_scan_w64) piece by piece (96 MFMAs per phase and wave)\n", p.gcnArchName, cus);
   run<0>("V0 MFMAs + pair-ring LDS reads", w, x, out, stamps, cus, phases);
   run<1>("V1 + barrier per phase", w, x, out, stamps, cus, phases);
   run<2>("V2 + 64 v_max3 per phase", w, x, out, stamps, cus, phases);
