@@ -182,15 +182,19 @@ class ShardedSearcher:
         else:
             self.dist.all_gather_into_tensor(outp, inp, group=self.group)
 
+    def _lane(self, key, B: int, k: int):
+        """The preallocated buffers of (key, B, k), made on first use; key: the workspace's address,
+        0 for the index's own."""
+        lane = self._lanes.get((key, B, k))
+        if lane is None:
+            lane = self._lanes[(key, B, k)] = self.backend.new_lane(B, k, self.world)
+        return lane
+
     def _search_lane(self, q16, k: int, workspace):
         """Product path (HipShardBackend): per-(workspace, B, k) preallocated buffers; the
         returned tensors are those buffers -- consume them before the same lane searches
         again.  Three enqueues per step: rf_search, all-gather, merge."""
-        B = q16.shape[0]
-        key = (workspace.data_ptr() if workspace is not None else 0, B, k)
-        lane = self._lanes.get(key)
-        if lane is None:
-            lane = self._lanes[key] = self.backend.new_lane(B, k, self.world)
+        lane = self._lane(workspace.data_ptr() if workspace is not None else 0, q16.shape[0], k)
         self.backend.local_topk_into(q16, k, 0 if self.id_map is not None else self.row_base, lane, workspace)
         if self.id_map is not None:
             self._map_ids_(lane["local_ids"])
@@ -279,10 +283,7 @@ class ShardedSearcher:
         every rank learns of the failure from the merged flags."""
         import torch
         if hasattr(self.backend, "local_topk_into"):
-            key = (0, B, k)
-            lane = self._lanes.get(key)
-            if lane is None:
-                lane = self._lanes[key] = self.backend.new_lane(B, k, self.world)
+            lane = self._lane(0, B, k)
             lane["exact"].fill_(float("-inf"))
             lane["local_ids"].fill_(-1)
             lane["local_flags"].fill_(SHARD_FAILED)

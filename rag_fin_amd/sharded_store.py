@@ -30,7 +30,7 @@ import threading
 
 from . import _lib, filter_expr
 from .sharded import HipShardBackend, ShardedSearcher
-from .store import SCALAR_FIELDS, CorpusStore, MutationResult, _id_in_keys
+from .store import CorpusStore, MutationResult, _id_in_keys
 
 
 logger = logging.getLogger(__name__)
@@ -76,50 +76,30 @@ class ShardedCorpusStore(CorpusStore):
         batch [n, dim] (each rank keeps its slice), or with local=True only this rank's slice
         [hi - lo, dim] where (lo, hi) = ShardedSearcher.shard_bounds(n, world, rank) -- the
         encoder runs as replicas, each rank embedding its own rows."""
-        with self._rw.write():
-            return self._add_sharded(ids, texts, embeddings, periods, chunk_types, statement_types,
-                                     primary_values, local)
-
-    def _add_sharded(self, ids, texts, embeddings, periods, chunk_types, statement_types, primary_values,
-                     local: bool) -> int:
-        torch = _torch()
-        n = len(ids)
         cols = (texts, periods, chunk_types, statement_types, primary_values)
-        if any(len(c) != n for c in cols):
-            raise ValueError("insert columns differ in length")
-        for pk in ids:
-            if pk in self._pk_row:
-                raise ValueError(f"duplicate primary key {pk!r}")
-        if len(set(ids)) != n:
-            raise ValueError("duplicate primary keys in insert")
-        lo, hi = ShardedSearcher.shard_bounds(n, self.world, self.rank)
-        m = hi - lo
-        if torch.is_tensor(embeddings) and embeddings.dtype == torch.float16:
-            vec = embeddings if local else embeddings[lo:hi]
-        else:
-            emb = embeddings if torch.is_tensor(embeddings) else np.asarray(embeddings, dtype=np.float32)
-            emb = emb if local else emb[lo:hi]
-            vec = self.index.to_fp16(emb, normalize=self.metric_type == "COSINE") if m else \
-                torch.empty((0, self.dim), dtype=torch.float16, device=self.index.device)
-        if tuple(vec.shape) != (m, self.dim):
-            raise ValueError(f"rank {self.rank}: embeddings must be [{m if local else n}, {self.dim}]")
-        if m:
-            if self.index.size + m > self.index.capacity:
-                self._grow(self.index.size + m)
-            self.index.add(vec.to(self.index.device).contiguous())
-        base = self.num_entities
-        self._id_map = torch.cat([self._id_map,
-                                  torch.arange(base + lo, base + hi, dtype=torch.int64, device=self._id_map.device)])
+        with self._rw.write():
+            vec, lo = self._check_slice(ids, cols, embeddings, local, "insert")
+            self._store_vectors(vec, lo)
+            self._append_rows(ids, cols)
+        return len(ids)
+
+    def _check_slice(self, ids, cols, embeddings, local: bool, what: str):
+        """_check_batch with this rank's slice [lo, hi) of the batch's vectors -> (fp16 rows, lo).
+        A whole column (local=False) must be [n, dim] before it is cut: all ranks refuse it, or none."""
+        lo, hi = ShardedSearcher.shard_bounds(len(ids), self.world, self.rank)
+        if not local:
+            embeddings = self._embedding_rows(embeddings, len(ids))[lo:hi]
+        return self._check_batch(ids, cols, embeddings, hi - lo, what), lo
+
+    def _store_vectors(self, vec, lo: int = 0) -> None:
+        """vec: this rank's rows, rows lo onward of a batch that is about to be appended."""
+        torch = _torch()
+        if vec.shape[0]:
+            super()._store_vectors(vec)
+        first = self.num_entities + lo
+        self._id_map = torch.cat([self._id_map, torch.arange(first, first + vec.shape[0], dtype=torch.int64,
+                                                             device=self._id_map.device)])
         self._searcher = None        # id_map changed (and _grow may have replaced the index)
-        for j, pk in enumerate(ids):
-            self._pk_row[pk] = base + j
-        self.columns["id"].extend(ids)
-        self.columns["text"].extend(texts)
-        self.columns["period"].extend(periods)
-        self.columns["chunk_type"].extend(chunk_types)
-        self.columns["statement_type"].extend(statement_types)
-        self.columns["primary_value"].extend(float(v) for v in primary_values)
-        return n
 
     def drop(self) -> None:
         torch = _torch()
@@ -160,25 +140,15 @@ class ShardedCorpusStore(CorpusStore):
     def upsert(self, data, local: bool = False) -> MutationResult:
         """COLLECTIVE.  As CorpusStore.upsert; `local` as for add (the embedding column holds
         only this rank's slice of the batch)."""
-        if len(data) != 7:
-            raise ValueError("upsert expects 7 columns: id, text, embedding, period, chunk_type, "
-                             "statement_type, primary_value")
-        ids, texts, emb, periods, ctypes_, stypes, pvals = data
+        ids, cols, emb = self._split_columns(data, "upsert")
         ids = list(ids)
-        n = len(ids)
-        if any(len(c) != n for c in (texts, periods, ctypes_, stypes, pvals)):
-            raise ValueError("upsert columns differ in length")
-        if len(set(ids)) != n:
-            raise ValueError("duplicate primary keys in upsert")
-        lo, hi = ShardedSearcher.shard_bounds(n, self.world, self.rank)
-        want = (hi - lo if local else n, self.dim)
-        if tuple(emb.shape if hasattr(emb, "shape") else np.asarray(emb).shape) != want:
-            raise ValueError(f"rank {self.rank}: embeddings must be {list(want)}")
         with self._rw.write(), self._coll_lock:
             self._check_not_leading()
+            vec, lo = self._check_slice(ids, cols, emb, local, "upsert")   # before any row goes
             self._delete_mask(self._pk_mask(ids))
-            self.add(ids, texts, emb, periods, ctypes_, stypes, pvals, local=local)
-            return MutationResult(ids, insert_count=n, upsert_count=n)
+            self._store_vectors(vec, lo)
+            self._append_rows(ids, cols)
+        return MutationResult(ids, insert_count=len(ids), upsert_count=len(ids))
 
     def _check_not_leading(self) -> None:
         if self._leading:
@@ -353,7 +323,6 @@ class ShardedCorpusStore(CorpusStore):
             self._save(path, chunk_rows)
 
     def _save(self, path: str, chunk_rows: int) -> None:
-        import json
         import os
         n = self.num_entities
         vec_path = os.path.join(path, "vectors.f16")
@@ -372,12 +341,7 @@ class ShardedCorpusStore(CorpusStore):
             del mm
         self.dist.barrier(group=self.group)
         if self.rank == 0:
-            meta = {"format": "ragfin-corpus-v1", "name": self.name, "dim": self.dim,
-                    "metric_type": self.metric_type, "n": n, "columns": self.columns}
-            tmp = os.path.join(path, "columns.json.tmp")
-            with open(tmp, "w", encoding="utf-8") as f:
-                json.dump(meta, f, ensure_ascii=False)
-            os.replace(tmp, os.path.join(path, "columns.json"))
+            self._write_meta(path, n)
         self.dist.barrier(group=self.group)
 
     @classmethod
@@ -385,35 +349,16 @@ class ShardedCorpusStore(CorpusStore):
                   index_factory=None, backend=None) -> "ShardedCorpusStore":
         """COLLECTIVE.  Rank r memory-maps vectors.f16 and streams rows
         shard_bounds(n, world, r) into its HBM; the columns are read by every rank."""
-        import json
-        import os
         import torch.distributed as dist
         torch = _torch()
-        with open(os.path.join(path, "columns.json"), encoding="utf-8") as f:
-            meta = json.load(f)
-        if meta.get("format") != "ragfin-corpus-v1":
-            raise ValueError(f"{path}: not a ragfin corpus directory")
-        n, dim = int(meta["n"]), int(meta["dim"])
+        meta, n, dim = cls._read_meta(path)
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         lo, hi = ShardedSearcher.shard_bounds(n, world, rank)
         cap = max(capacity or 0, hi - lo, 1)
         index = index_factory(dim, cap, device) if index_factory is not None else None
         st = cls(meta["name"], dim=dim, capacity=cap, device=device, metric_type=meta["metric_type"], group=group,
                  index=index, backend=backend)
-        if n:
-            expect = n * dim * 2
-            got = os.path.getsize(os.path.join(path, "vectors.f16"))
-            if got != expect:
-                raise ValueError(f"{path}/vectors.f16 holds {got} bytes, expected {expect}")
-            mm = np.memmap(os.path.join(path, "vectors.f16"), dtype=np.float16, mode="r", shape=(n, dim))
-            for s0 in range(lo, hi, chunk_rows):
-                s1 = min(hi, s0 + chunk_rows)
-                st.index.add(torch.from_numpy(np.ascontiguousarray(mm[s0:s1])).to(st.index.device))
-            del mm
+        st._load_rows(path, n, lo, hi, chunk_rows)
         st._id_map = torch.arange(lo, hi, dtype=torch.int64, device=st.index.device)
-        cols = meta["columns"]
-        if any(len(cols[f]) != n for f in SCALAR_FIELDS):
-            raise ValueError(f"{path}: column lengths do not match n={n}")
-        st.columns = {f: list(cols[f]) for f in SCALAR_FIELDS}
-        st._pk_row = {pk: i for i, pk in enumerate(st.columns["id"])}
+        st._adopt_columns(path, meta, n)
         return st

@@ -21,11 +21,11 @@ CPU path.
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import itertools
+import json
+import os
 import re
 import threading
-from ctypes import c_void_p
 from typing import Any, Iterable, Sequence
 
 import numpy as np
@@ -33,113 +33,17 @@ import numpy as np
 from . import _lib
 from . import filter_expr
 
-import os as _os
-# RAGFIN_ZERO_COPY=0: search_host copies results with async memcpys instead of letting the merge kernel
-# store into the pinned host buffers (A/B switch)
-_ZERO_COPY = _os.environ.get("RAGFIN_ZERO_COPY", "1") != "0"
+from .index import (GpuIndex, _ptr, eval_filter, filter_mask_bits, grouped_exhaustive, mask_words,  # noqa: F401
+                    require_gpu, rerun_flagged, words_mask)
+
 
 SCALAR_FIELDS = ("id", "text", "period", "chunk_type", "statement_type", "primary_value")
+FORMAT = "ragfin-corpus-v1"   # columns.json "format"
 
 
 def _torch():
     import torch
     return torch
-
-
-def require_gpu(device=None):
-    """Fail loudly when there is no MI355X to run on."""
-    torch = _torch()
-    if not torch.cuda.is_available():
-        raise RuntimeError("rag_fin_amd needs a ROCm GPU (gfx950); torch.cuda.is_available() is "
-                           "False and there is no CPU fallback")
-    dev = torch.device(device if device is not None else "cuda:0")
-    if dev.type != "cuda":
-        raise RuntimeError(f"device {dev} is not a GPU")
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    _lib.check(_lib.load_library().rf_device_check(idx))
-    return torch.device("cuda", idx)
-
-
-def rerun_flagged(q16, k: int, id_base: int, flags, sq8: bool, filt, flat, exhaustive):
-    """The flagged-query ladder ("fallback"): a query the first pass could not prove
-    exact (flags != 0) is re-run one tier down.  A query flagged by an SQ8 first pass (`sq8`) goes
-    through the FLAT chain, and only one that flags there too goes to the exhaustive kernel; one
-    flagged by a FLAT or filtered (`filt`) first pass goes straight to the exhaustive kernel, over
-    the same passing rows.  The tiers are callables, on whatever device their tensors live:
-      flat(q, k, id_base)             -> (scores, ids, exact | None, flags)
-      exhaustive(q, k, id_base, filt) -> (scores, ids, exact | None)
-    -> (bad, rows): the indices of the re-run queries (on the device of `flags`) and their
-    replacement [scores, ids, exact | None], each row from the last tier that ran it; rows is
-    None when nothing was flagged.  The caller patches its own destination."""
-    torch = _torch()
-    bad = torch.nonzero(flags != 0).flatten()
-    if bad.numel() == 0:
-        return bad, None
-    qb = q16[bad.to(q16.device)].contiguous()
-    if not sq8:
-        return bad, list(exhaustive(qb, k, id_base, filt))
-    *rows, f2 = flat(qb, k, id_base)
-    again = torch.nonzero(f2 != 0).flatten()
-    if again.numel() > 0:
-        for dst, src in zip(rows, exhaustive(qb[again].contiguous(), k, id_base, filt)):
-            if dst is not None:
-                dst[again] = src
-    return bad, rows
-
-
-def mask_words(bits):
-    """bool [n] (device) -> the filter mask words int32 [ceil(n / 32)]: bit r of word b = row 32 b + r."""
-    torch = _torch()
-    n = bits.numel()
-    nblk = (n + 31) // 32
-    pad = torch.zeros(nblk * 32, dtype=torch.int64, device=bits.device)
-    pad[:n] = bits.to(torch.int64)
-    w = (pad.view(nblk, 32) << torch.arange(32, dtype=torch.int64, device=bits.device)).sum(1)
-    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
-
-
-def words_mask(words, n: int):
-    """The inverse of mask_words: int32 words (device) -> bool [n]."""
-    torch = _torch()
-    sh = torch.arange(32, dtype=torch.int64, device=words.device)
-    return (((words.to(torch.int64).unsqueeze(1) >> sh) & 1) != 0).flatten()[:n]
-
-
-def grouped_exhaustive(q16, group, pass_bits, exhaustive_masked):
-    """The flagged-query ladder of a grouping search, and the path of a dictionary
-    above RF_GROUP_MAX_CODES: per group code g that has a row, the exhaustive fp64 kernel with
-    k = group_size over "code == g AND the user's filter", then the groups ranked on their fp64
-    best (score desc, row asc).  Costs one fp64 pass per group, for the given queries only.
-      group = (codes int32 [n] on the device, n_codes, n_groups, group_size)
-      pass_bits: bool [n] on the device (the user's filter), or None
-      exhaustive_masked(q16, k, words) -> (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k]) over
-      the rows of the mask `words` (mask_words), ids WITHOUT an id base
-    -> (scores, rows, exact) in the padded slot form [B, n_groups * group_size], host numpy."""
-    torch = _torch()
-    codes, n_codes, n, s = group
-    B = q16.shape[0]
-    ok = (codes >= 0) & (codes < n_codes)
-    if pass_bits is not None:
-        ok = ok & pass_bits
-    per = []
-    for g in torch.unique(codes[ok]).tolist():
-        sc, ids, ex = exhaustive_masked(q16, s, mask_words(ok & (codes == g)))
-        per.append((sc.cpu().numpy(), ids.cpu().numpy(), ex.cpu().numpy()))
-    scores = np.full((B, n * s), -np.inf, dtype=np.float32)
-    rows = np.full((B, n * s), -1, dtype=np.int64)
-    exact = np.full((B, n * s), -np.inf, dtype=np.float64)
-    for b in range(B):
-        live = [p for p in per if p[1][b, 0] >= 0]
-        live.sort(key=lambda p: (-p[2][b, 0], p[1][b, 0]))
-        for j, (sc, ids, ex) in enumerate(live[:n]):
-            scores[b, j * s:(j + 1) * s] = sc[b]
-            rows[b, j * s:(j + 1) * s] = ids[b]
-            exact[b, j * s:(j + 1) * s] = ex[b]
-    return scores, rows, exact
-
-
-def _ptr(t):
-    return c_void_p(t.data_ptr()) if t is not None else None
 
 
 def check_band(radius, range_filter=None):
@@ -161,524 +65,6 @@ def check_band(radius, range_filter=None):
     if not out[0] < out[1]:
         raise ValueError(f"range search: need radius < range_filter, got {out[0]!r} and {out[1]!r}")
     return out[0], out[1]
-
-
-class GpuIndex:
-    """Thin object wrapper over rf_index_* / rf_search (include/ragfin.h).
-
-    Locking: the index's own workspace (`self.workspace`) is shared by every caller that does not
-    bring one.  A method that uses it holds `self._lock` while it enqueues and until the results
-    it patches from are read; so do the methods that change the index under a search (compact,
-    enable_sq8, disable_sq8).  A method given a caller's workspace does not lock.  The two
-    exceptions are `search_raw(workspace=None)` and `enqueue_search`: the benchmark and the
-    sharded lanes call them on streams of their own, and the caller serialises.  The lock is not
-    re-entrant: public locked methods call the private unlocked ones (`_exhaustive`,
-    `_rerun_flagged`), never each other."""
-
-    def __init__(self, dim: int, capacity: int, device=None):
-        torch = _torch()
-        self.device = require_gpu(device)
-        self.lib = _lib.load_library()
-        self.dim = int(dim)
-        self.capacity = int(capacity)
-        nbytes = self.lib.rf_index_storage_bytes(self.dim, self.capacity)
-        if nbytes == 0:
-            raise _lib.RagfinError(-1, f"unsupported index shape dim={dim} capacity={capacity}")
-        with torch.cuda.device(self.device):
-            self.storage = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            handle = c_void_p()
-            _lib.check(self.lib.rf_index_create(ctypes.byref(handle), self.dim, self.capacity,
-                                                c_void_p(self.storage.data_ptr()), nbytes,
-                                                self.device.index))
-            self.handle = handle
-            ws = self.lib.rf_search_workspace_bytes(self.handle)
-            # one workspace serves both paths: the SQ8 one is the FLAT one plus its query area
-            self.sq8_workspace_bytes = self.lib.rf_search_sq8_workspace_bytes(self.handle)
-            # ... and the grouped one is the SQ8 one plus its per-(query, group) tables
-            self.grouped_workspace_bytes = self.lib.rf_search_grouped_workspace_bytes(self.handle)
-            self.workspace = torch.zeros(max(ws, self.sq8_workspace_bytes, self.grouped_workspace_bytes),
-                                         dtype=torch.uint8, device=self.device)
-            self.workspace_bytes = ws
-        self._lock = threading.Lock()
-        self._host_bufs = {}
-        self._sq8_storage = None   # the SQ8 shadow (enable_sq8), a separate allocation
-
-    def __del__(self):
-        h = getattr(self, "handle", None)
-        if h:
-            self.lib.rf_index_destroy(h)
-            self.handle = None
-
-    @property
-    def size(self) -> int:
-        return int(self.lib.rf_index_size(self.handle))
-
-    def reset(self) -> None:
-        torch = _torch()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_index_reset(self.handle, _lib.current_stream_ptr()))
-
-    # -- ingest --------------------------------------------------------------
-    def add(self, rows) -> None:
-        """rows: fp16 [n, dim] tensor on this device (row-major, contiguous)."""
-        torch = _torch()
-        if rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != self.dim:
-            raise ValueError(f"add expects fp16 [n, {self.dim}], got {rows.dtype} {tuple(rows.shape)}")
-        rows = rows.to(self.device).contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_index_add_f16(self.handle, c_void_p(rows.data_ptr()),
-                                                 rows.shape[0], _lib.current_stream_ptr()))
-
-    def to_fp16(self, rows_f32, normalize: bool = True):
-        """fp32 [n, dim] -> (L2-normalised) fp16 on device, via rf_normalize_f32_to_f16."""
-        torch = _torch()
-        x = torch.as_tensor(rows_f32, dtype=torch.float32).to(self.device).contiguous()
-        if x.dim() != 2 or x.shape[1] != self.dim:
-            raise ValueError(f"expected [n, {self.dim}] vectors, got {tuple(x.shape)}")
-        out = torch.empty(x.shape, dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_normalize_f32_to_f16(c_void_p(x.data_ptr()), x.shape[0], self.dim,
-                                                        1 if normalize else 0,
-                                                        c_void_p(out.data_ptr()),
-                                                        _lib.current_stream_ptr()))
-        return out
-
-    COMPACT_WINDOW_ROWS = 1 << 16   # rows per rf_index_compact window (scratch = rows * dim * 2 bytes)
-
-    def compact(self, keep_rows, window_rows: int | None = None) -> None:
-        """Keep rows `keep_rows` (strictly ascending row numbers) in that order and drop the rest,
-        in place (rf_index_compact): the index then equals a fresh one given the survivors.
-        window_rows: rows per compaction window (a multiple of 32; default COMPACT_WINDOW_ROWS).
-        Takes the index lock, so it cannot interleave with search / search_host / a page of
-        search_large."""
-        torch = _torch()
-        keep = np.asarray(keep_rows, dtype=np.int64).reshape(-1)
-        n = keep.size
-        size = self.size
-        if n and (keep[0] < 0 or keep[-1] >= size or (n > 1 and bool((np.diff(keep) <= 0).any()))):
-            raise ValueError(f"keep_rows must be strictly ascending row numbers in [0, {size})")
-        w = self.COMPACT_WINDOW_ROWS if window_rows is None else int(window_rows)
-        if w < 32 or w % 32:
-            raise ValueError("window_rows must be a positive multiple of 32")
-        w = min(w, max(32, (n + 31) // 32 * 32))
-        with self._lock, torch.cuda.device(self.device):
-            if n == 0:
-                _lib.check(self.lib.rf_index_compact(self.handle, None, 0, None, 0, _lib.current_stream_ptr()))
-                return
-            keep_d = torch.from_numpy(keep).to(self.device)
-            scratch = torch.empty(w * self.dim * 2, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rf_index_compact(self.handle, c_void_p(keep_d.data_ptr()), n,
-                                                 c_void_p(scratch.data_ptr()), scratch.numel(),
-                                                 _lib.current_stream_ptr()))
-        # keep_d / scratch are released in stream order (caching allocator): no sync needed
-
-    def get_rows(self, row_ids):
-        torch = _torch()
-        ids = torch.as_tensor(row_ids, dtype=torch.int64).to(self.device).contiguous()
-        out = torch.empty((ids.numel(), self.dim), dtype=torch.float16, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_index_get_rows_f16(self.handle, c_void_p(ids.data_ptr()),
-                                                      ids.numel(), c_void_p(out.data_ptr()),
-                                                      _lib.current_stream_ptr()))
-        return out
-
-    # -- SQ8 shadow (include/ragfin.h, "SQ8 index") ----------------------------------------
-    @property
-    def sq8(self) -> bool:
-        """True while an int8 shadow is attached (rf_search_sq8 can run)."""
-        return self._sq8_storage is not None
-
-    def enable_sq8(self) -> None:
-        """Attach an int8 shadow (dim + 8 bytes per row of capacity) and quantize every row; adds,
-        compactions and resets keep it current from then on.  Needs dim % 32 == 0."""
-        torch = _torch()
-        if self._sq8_storage is not None:
-            return
-        nbytes = self.lib.rf_sq8_storage_bytes(self.dim, self.capacity)
-        if nbytes == 0:
-            raise _lib.RagfinError(-2, f"SQ8 needs dim % 32 == 0 (dim {self.dim})")
-        with self._lock, torch.cuda.device(self.device):
-            storage = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.rf_index_attach_sq8(self.handle, c_void_p(storage.data_ptr()), nbytes,
-                                                    _lib.current_stream_ptr()))
-            self._sq8_storage = storage
-
-    def disable_sq8(self) -> None:
-        torch = _torch()
-        if self._sq8_storage is None:
-            return
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_index_detach_sq8(self.handle))
-            # freed in stream order: a search already enqueued on this stream still reads it
-            self._sq8_storage = None
-
-    def get_rows_sq8(self, row_ids):
-        """rf_index_get_rows_sq8: (int8 [n, dim], s_r fp32 [n], e_r fp32 [n]) on the device."""
-        torch = _torch()
-        ids = torch.as_tensor(row_ids, dtype=torch.int64).to(self.device).contiguous()
-        n = ids.numel()
-        out = torch.empty((n, self.dim), dtype=torch.int8, device=self.device)
-        sc = torch.empty((n,), dtype=torch.float32, device=self.device)
-        er = torch.empty((n,), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_index_get_rows_sq8(self.handle, c_void_p(ids.data_ptr()), n,
-                                                      c_void_p(out.data_ptr()), c_void_p(sc.data_ptr()),
-                                                      c_void_p(er.data_ptr()), _lib.current_stream_ptr()))
-        return out, sc, er
-
-    def debug_scores_sq8(self, q16, n: int | None = None):
-        """rf_debug_scores_sq8: (a~ fp32 [B, n], delta_q fp32 [B])."""
-        torch = _torch()
-        n = self.size if n is None else n
-        q16 = q16.to(self.device).contiguous()
-        B = q16.shape[0]
-        out = torch.empty((B, n), dtype=torch.float32, device=self.device)
-        delta = torch.empty((B,), dtype=torch.float32, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_debug_scores_sq8(self.handle, c_void_p(q16.data_ptr()), B, n,
-                                                    c_void_p(out.data_ptr()), c_void_p(delta.data_ptr()),
-                                                    c_void_p(self.workspace.data_ptr()), self.workspace.numel(),
-                                                    _lib.current_stream_ptr()))
-        return out, delta
-
-    def search_sq8_profile(self, q16, k: int):
-        """rf_search_sq8_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
-        return self._profile(self.lib.rf_search_sq8_profile, q16, min(q16.shape[0], _lib.RF_QCHUNK), k,
-                             self.workspace.numel(), ("quantize", "sample", "threshold", "emit", "merge"))
-
-    def _profile(self, fn, q16, B: int, k: int, workspace_bytes: int, stages):
-        """The first sweep of a B-query batch through a *_profile entry point -> {stage: ms}."""
-        torch = _torch()
-        q16 = q16.to(self.device).contiguous()
-        scores, ids, _, flags = self._outputs(B, k)
-        ms = (ctypes.c_float * len(stages))()
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(fn(self.handle, _ptr(q16), B, k, 0, _ptr(scores), _ptr(ids), None, _ptr(flags),
-                          _ptr(self.workspace), workspace_bytes, _lib.current_stream_ptr(), ms))
-        return dict(zip(stages, ms))
-
-    # -- search --------------------------------------------------------------
-    def new_workspace(self):
-        """An extra search workspace: one per batch in flight when several streams
-        search the same (immutable) index concurrently.  Large enough for SQ8 too."""
-        torch = _torch()
-        return torch.zeros(max(self.workspace_bytes, self.sq8_workspace_bytes, self.grouped_workspace_bytes),
-                           dtype=torch.uint8, device=self.device)
-
-    def _outputs(self, B: int, k: int, want_exact: bool = False, flags: bool = True, out=None):
-        """The output tuple of a search: `out` when the caller brings one, else fresh device tensors
-        (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags i32 [B] | None)."""
-        if out is not None:
-            return out
-        torch = _torch()
-        return (torch.empty((B, k), dtype=torch.float32, device=self.device),
-                torch.empty((B, k), dtype=torch.int64, device=self.device),
-                torch.empty((B, k), dtype=torch.float64, device=self.device) if want_exact else None,
-                torch.empty((B,), dtype=torch.int32, device=self.device) if flags else None)
-
-    def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None, group=None):
-        """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
-        hipStream_t of this device); no host sync.  Returns
-        (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
-        filt: a filter buffer built for this index (CorpusStore.build_filter / rf_filter_eval):
-        rf_search_filtered, the same outputs over the passing rows only.
-        sq8: rf_search_sq8 (needs enable_sq8; not with filt).  A workspace passed in must hold
-        sq8_workspace_bytes (new_workspace does).
-        band: (radius, range_filter) -- rf_search_range: the best k rows with
-        radius < fp64 score <= range_filter (within the passing rows with filt; not with sq8).
-        group: (codes int32 [size] on this device, n_codes, n_groups, group_size) -- rf_search_grouped:
-        the best n_groups groups of rows sharing a code, each by its best group_size rows (within
-        the passing rows with filt; not with sq8 or band).  k must be n_groups * group_size; the
-        outputs are in the padded slot form (group of rank j in slots [j s, (j + 1) s)).
-        Takes no lock, with or without a workspace of the caller's: the benchmark and the sharded
-        lanes call it on their own streams, and whoever shares the index's workspace serialises."""
-        torch = _torch()
-        if sq8 and (filt is not None or band is not None or group is not None):
-            raise ValueError("SQ8 search has no filtered, no range and no grouped form")
-        if group is not None:
-            if band is not None:
-                raise ValueError("grouping search has no range form")
-            self._check_group(group, k)
-        if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
-            raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
-        if not q16.is_contiguous() or q16.device != self.device:
-            q16 = q16.to(self.device).contiguous()
-        B = q16.shape[0]
-        scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
-        args = (_ptr(q16), B, k, id_base, _ptr(scores), _ptr(ids), _ptr(exact), _ptr(flags),
-                _ptr(workspace if workspace is not None else self.workspace),
-                self.grouped_workspace_bytes if group is not None else
-                self.sq8_workspace_bytes if sq8 else self.workspace_bytes,
-                stream_ptr if stream_ptr is not None else _lib.current_stream_ptr())
-        with torch.cuda.device(self.device):
-            if group is not None:
-                _lib.check(self.lib.rf_search_grouped(self.handle, _ptr(filt), _ptr(group[0]), int(group[1]),
-                                                      args[0], B, int(group[2]), int(group[3]), *args[3:]))
-            elif band is not None:
-                _lib.check(self.lib.rf_search_range(self.handle, _ptr(filt), *args[:4], float(band[0]), float(band[1]),
-                                                    *args[4:]))
-            elif sq8:
-                _lib.check(self.lib.rf_search_sq8(self.handle, *args))
-            elif filt is None:
-                _lib.check(self.lib.rf_search(self.handle, *args))
-            else:
-                _lib.check(self.lib.rf_search_filtered(self.handle, _ptr(filt), *args))
-        return scores, ids, exact, flags
-
-    def _check_group(self, group, k: int) -> None:
-        torch = _torch()
-        codes, n_codes, n, s = group
-        if not torch.is_tensor(codes) or codes.dtype != torch.int32 or codes.dim() != 1 or \
-                codes.numel() != self.size or codes.device != self.device or not codes.is_contiguous():
-            raise ValueError(f"group codes must be a contiguous int32 [{self.size}] tensor on {self.device}")
-        if n < 1 or s < 1 or n * s > _lib.RF_MAX_K or n * s != k:
-            raise ValueError(f"grouping search: need n_groups, group_size >= 1 and k == n_groups * group_size <= "
-                             f"{_lib.RF_MAX_K} (got {n}, {s}, k = {k})")
-
-    def search_grouped_profile(self, q16, group, filt=None):
-        """rf_search_grouped_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
-        torch = _torch()
-        q16 = q16.to(self.device).contiguous()
-        B = min(q16.shape[0], _lib.RF_QCHUNK)
-        k = int(group[2]) * int(group[3])
-        self._check_group(group, k)
-        scores, ids, _, flags = self._outputs(B, k)
-        ms = (ctypes.c_float * 4)()
-        with self._lock, torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_search_grouped_profile(
-                self.handle, _ptr(filt), _ptr(group[0]), int(group[1]), _ptr(q16), B, int(group[2]), int(group[3]), 0,
-                _ptr(scores), _ptr(ids), None, _ptr(flags), _ptr(self.workspace), self.grouped_workspace_bytes,
-                _lib.current_stream_ptr(), ms))
-        return dict(zip(("group_max", "threshold", "emit", "merge"), ms))
-
-    def enqueue_search(self, q_ptr: int, B: int, k: int, id_base: int, scores_ptr: int, ids_ptr: int,
-                       exact_ptr: int, flags_ptr: int, workspace_ptr: int, stream_ptr):
-        """The bare rf_search enqueue for callers that own every buffer (the sharded step: no
-        tensor checks, no allocations, no stream / device context).  The caller guarantees that
-        this index's device is the thread's current HIP device, and serialises the use of
-        the workspace it passes: no lock is taken here."""
-        rc = self.lib.rf_search(self.handle, q_ptr, B, k, id_base, scores_ptr, ids_ptr, exact_ptr, flags_ptr,
-                                workspace_ptr, self.workspace_bytes, stream_ptr)
-        if rc:
-            _lib.check(rc)
-
-    def search_profile(self, q16, k: int):
-        """rf_search_profile: per-stage HIP-event times in ms (synchronises)."""
-        # the first sweep: 64 queries, or up to 256 on the wide path
-        return self._profile(self.lib.rf_search_profile, q16, min(q16.shape[0], 256), k, self.workspace_bytes,
-                             ("sample", "threshold", "emit", "merge"))
-
-    def _exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, after=None,
-                    band=None):
-        """The exhaustive fp64 kernel through whichever entry point the arguments need.  filt: over
-        the passing rows.  after: (fp64 scores [B], i64 ids [B]), only the hits ranked strictly after
-        that bound per query.  band: (radius, range_filter), only rows inside it
-        (rf_search_exhaustive_range).  Uses the index workspace: the caller holds the lock."""
-        torch = _torch()
-        q16 = q16.to(self.device).contiguous()
-        B = q16.shape[0]
-        scores, ids, exact, _ = self._outputs(B, k, want_exact, flags=False)
-        query = (_ptr(q16), B, k, id_base)
-        bounds = (None, None) if after is None else (_ptr(after[0]), _ptr(after[1]))
-        outs = (_ptr(scores), _ptr(ids), _ptr(exact), _ptr(self.workspace), self.workspace_bytes,
-                _lib.current_stream_ptr())
-        with torch.cuda.device(self.device):
-            if band is not None:
-                rc = self.lib.rf_search_exhaustive_range(self.handle, _ptr(filt), *query, float(band[0]),
-                                                         float(band[1]), *bounds, *outs)
-            elif filt is not None:
-                rc = self.lib.rf_search_exhaustive_filtered(self.handle, _ptr(filt), *query, *bounds, *outs)
-            elif after is not None:
-                rc = self.lib.rf_search_exhaustive_after(self.handle, *query, *bounds, *outs)
-            else:
-                rc = self.lib.rf_search_exhaustive(self.handle, *query, *outs)
-        _lib.check(rc)
-        return scores, ids, exact
-
-    def search_exhaustive(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, band=None):
-        with self._lock:
-            return self._exhaustive(q16, k, id_base, want_exact, filt, band=band)
-
-    def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, band=None):
-        """Limits above RF_MAX_K: the first page through the fused path, further pages
-        of RF_MAX_K through the exhaustive kernel with a bound (each page = the hits ranked
-        strictly after the previous page's last hit).  Returns (scores, ids) [B, k]
-        (+ the fp64 ranking scores with want_exact: what a cross-shard merge ranks by).
-        filt: the same over the passing rows.  band: (radius, range_filter) -- the same within the
-        band: the first page through rf_search_range, later pages through the exhaustive band
-        kernel; the walk ends with the first page that the band does not fill."""
-        torch = _torch()
-        q16 = q16.to(self.device).contiguous()
-        B = q16.shape[0]
-        page = _lib.RF_MAX_K
-        s0, i0, e0 = self.search(q16, page, id_base, want_exact=True, filt=filt, band=band)
-        scores, ids, exacts = [s0], [i0], [e0]
-        last_s, last_i = e0[:, -1].contiguous(), i0[:, -1].contiguous()
-        got = page
-        while got < k and bool((last_i >= 0).any()):
-            # exhausted queries keep a bound nothing can follow
-            bs = torch.where(last_i >= 0, last_s, torch.full_like(last_s, float("-inf")))
-            bi = torch.where(last_i >= 0, last_i, torch.full_like(last_i, 2 ** 62))
-            with self._lock:
-                s, i, e = self._exhaustive(q16, page, id_base, True, filt, after=(bs, bi), band=band)
-            scores.append(s)
-            ids.append(i)
-            exacts.append(e)
-            last_s, last_i = e[:, -1].contiguous(), i[:, -1].contiguous()
-            got += page
-        if got < k:   # corpus exhausted before k hits: pad like rf_search does
-            scores.append(torch.full((B, k - got), float("-inf"), dtype=torch.float32, device=self.device))
-            ids.append(torch.full((B, k - got), -1, dtype=torch.int64, device=self.device))
-            exacts.append(torch.full((B, k - got), float("-inf"), dtype=torch.float64, device=self.device))
-        out = (torch.cat(scores, 1)[:, :k].contiguous(), torch.cat(ids, 1)[:, :k].contiguous())
-        return out + (torch.cat(exacts, 1)[:, :k].contiguous(),) if want_exact else out
-
-    def _grouped_exhaustive(self, q16, group, id_base: int, want_exact: bool, filt):
-        """grouped_exhaustive with this index's exhaustive kernel -> device tensors.  The caller
-        holds the lock."""
-        torch = _torch()
-        n_rows = self.size
-        nblk = (n_rows + 31) // 32
-        bits = None if filt is None else words_mask(filt[16:16 + 4 * nblk].view(torch.int32), n_rows)
-
-        def masked(q, k, words):
-            buf = torch.empty(self.lib.rf_filter_bytes(n_rows), dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                _lib.check(self.lib.rf_filter_from_mask(_ptr(words), n_rows, _ptr(buf), _lib.current_stream_ptr()))
-            return self._exhaustive(q, k, 0, True, buf)
-
-        scores, rows, exact = grouped_exhaustive(q16.to(self.device).contiguous(), group, bits, masked)
-        rows = np.where(rows >= 0, rows + id_base, rows)
-        return (torch.from_numpy(scores).to(self.device), torch.from_numpy(rows).to(self.device),
-                torch.from_numpy(exact).to(self.device) if want_exact else None)
-
-    def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt, band=None,
-                       group=None):
-        """rerun_flagged with this index's tiers (the band of a range search rides in them; a
-        grouping search re-runs group by group).  The caller holds the lock."""
-        if group is not None:
-            return rerun_flagged(q16, k, id_base, flags, False, filt, None,
-                                 lambda q, k, base, f: self._grouped_exhaustive(q, group, base, want_exact, f))
-        return rerun_flagged(q16, k, id_base, flags, sq8, filt,
-                             lambda q, k, base: self.search_raw(q, k, base, want_exact, band=band),
-                             lambda q, k, base, f: self._exhaustive(q, k, base, want_exact, f, band=band))
-
-    def _grouped_first_pass(self, q16, k: int, id_base: int, want_exact: bool, filt, group, out=None):
-        """search_raw(group=...), or -- a dictionary above RF_GROUP_MAX_CODES -- outputs whose every
-        query is flagged, so that the ladder answers the whole batch."""
-        if int(group[1]) <= _lib.RF_GROUP_MAX_CODES:
-            return self.search_raw(q16, k, id_base, want_exact, out=out, filt=filt, group=group)
-        self._check_group(group, k)
-        res = self._outputs(q16.shape[0], k, want_exact, out=out)
-        res[3].fill_(_lib.RF_FLAG_CAND_OVERFLOW)
-        return res
-
-    def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False,
-               band=None, group=None):
-        """rf_search, then the flagged-query ladder (rerun_flagged) for any query the fused path
-        could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first.
-        band: (radius, range_filter) -- rf_search_range, flagged queries through the exhaustive
-        band kernel.  group: as in search_raw -- rf_search_grouped, flagged queries (and every query
-        of a dictionary above RF_GROUP_MAX_CODES) group by group through the exhaustive kernel."""
-        with self._lock:
-            if group is not None:
-                if sq8 or band is not None:
-                    raise ValueError("grouping search has no SQ8 and no range form")
-                scores, ids, exact, flags = self._grouped_first_pass(q16, k, id_base, want_exact, filt, group)
-            else:
-                scores, ids, exact, flags = self.search_raw(q16, k, id_base, want_exact, filt=filt, sq8=sq8, band=band)
-            bad, rows = self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt, band, group)
-            if rows is not None:
-                for dst, src in zip((scores, ids, exact), rows):
-                    if dst is not None:
-                        dst[bad] = src
-        return scores, ids, exact
-
-    ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
-
-    def search_host(self, q16, k: int, filt=None, sq8: bool = False, band=None, group=None):
-        """search() whose results land on the host with ONE synchronisation: scores, ids and
-        flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
-        ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows.
-        sq8: rf_search_sq8 first, as in search().  band: (radius, range_filter), as in search().
-        group: as in search(); k = n_groups * group_size, the padded slot form."""
-        torch = _torch()
-        if group is not None:
-            if sq8 or band is not None:
-                raise ValueError("grouping search has no SQ8 and no range form")
-            with self._lock:
-                scores, ids, _, flags = self._grouped_first_pass(q16, k, 0, False, filt, group)
-                bad, rows = self._rerun_flagged(q16, k, 0, False, flags, False, filt, None, group)
-                if rows is not None:
-                    scores[bad] = rows[0]
-                    ids[bad] = rows[1]
-                return scores.cpu().numpy(), ids.cpu().numpy()
-        with self._lock:
-            B = q16.shape[0]
-            key = (B, k)
-            bufs = self._host_bufs.get(key)
-            if bufs is None:
-                bufs = self._host_bufs[key] = (torch.empty((B, k), dtype=torch.float32, pin_memory=True),
-                                               torch.empty((B, k), dtype=torch.int64, pin_memory=True),
-                                               torch.empty((B,), dtype=torch.int32, pin_memory=True))
-            if B * k <= self.ZERO_COPY_MAX and _ZERO_COPY:
-                # query-sized results: the merge kernel stores straight into the pinned host buffers
-                # (host-coherent memory, mapped at the same address on the device) -- no copy commands,
-                # only the synchronisation
-                self.search_raw(q16, k, out=(bufs[0], bufs[1], None, bufs[2]), filt=filt, sq8=sq8, band=band)
-            else:
-                scores, ids, _, flags = self.search_raw(q16, k, filt=filt, sq8=sq8, band=band)
-                bufs[0].copy_(scores, non_blocking=True)
-                bufs[1].copy_(ids, non_blocking=True)
-                bufs[2].copy_(flags, non_blocking=True)
-            torch.cuda.current_stream(self.device).synchronize()
-            if bool(bufs[2].any()):
-                bad, rows = self._rerun_flagged(q16, k, 0, False, bufs[2], sq8, filt, band)
-                bufs[0][bad] = rows[0].cpu()
-                bufs[1][bad] = rows[1].cpu()
-            # private copies, taken while the lock is still held: the pinned buffers are shared by every caller with
-            # this (B, k) and the next search's merge kernel stores straight into them
-            return bufs[0].numpy().copy(), bufs[1].numpy().copy()
-
-    def debug_scores(self, q16, n: int | None = None):
-        torch = _torch()
-        n = self.size if n is None else n
-        q16 = q16.to(self.device).contiguous()
-        out = torch.empty((q16.shape[0], n), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.rf_debug_scores(self.handle, c_void_p(q16.data_ptr()), q16.shape[0], n,
-                                                c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
-        return out
-
-
-def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int):
-    """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
-    rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors
-    {period, chunk_type, statement_type codes int32 [n_rows], primary_value fp64 [n_rows]}."""
-    torch = _torch()
-    lib = _lib.load_library()
-    cs, rl = filter_expr.program_arrays(program)
-    with torch.cuda.device(device):
-        buf = torch.empty(lib.rf_filter_bytes(n_rows), dtype=torch.uint8, device=device)
-        cs_d = torch.from_numpy(cs.view(np.int32)).to(device) if cs.size else None
-        rl_d = torch.from_numpy(rl.view(np.int32)).to(device) if rl.size else None
-        ptrs = (c_void_p * _lib.RF_FILTER_COLUMNS)(*[c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-                                                     for t in columns])
-        ops = program.ops_ctypes()
-        _lib.check(lib.rf_filter_eval(ops, len(ops), c_void_p(cs_d.data_ptr()) if cs_d is not None else None,
-                                      c_void_p(rl_d.data_ptr()) if rl_d is not None else None, ptrs, n_rows,
-                                      c_void_p(buf.data_ptr()), _lib.current_stream_ptr()))
-    # (cs_d / rl_d may be freed now: the caching allocator reuses their memory in stream order)
-    return buf
-
-
-def filter_mask_bits(buf, n_rows: int):
-    """The row mask of a filter buffer as a host bool array [n_rows] (synchronises)."""
-    nblk = (n_rows + 31) // 32
-    words = buf[16:16 + 4 * nblk].cpu().numpy().view(np.uint32)
-    bits = np.unpackbits(words.view(np.uint8), bitorder="little").astype(bool)
-    return bits[:n_rows]
 
 
 class _DeviceColumns:
@@ -903,9 +289,14 @@ class CorpusStore:
         step = 1 << 18
         for s in range(0, n, step):
             new.add(old.get_rows(np.arange(s, min(n, s + step), dtype=np.int64)))
-        if getattr(old, "sq8", False):
+        if self._has_sq8:
             new.enable_sq8()   # re-attach: quantizes the copied rows
         self.index = new
+
+    @property
+    def _has_sq8(self) -> bool:
+        """The index carries an int8 shadow (a CPU double of GpuIndex has no such attribute)."""
+        return getattr(self.index, "sq8", False)
 
     # -- index type: Collection.create_index / drop_index / has_index --------------------------
     INDEX_TYPES = ("FLAT", "IVF_FLAT", "SQ8")
@@ -921,7 +312,7 @@ class CorpusStore:
         with self._rw.write():
             if itype == "SQ8":
                 self.index.enable_sq8()
-            elif getattr(self.index, "sq8", False):
+            elif self._has_sq8:
                 self.index.disable_sq8()
             self.index_type = "SQ8" if itype == "SQ8" else "FLAT"
             self._index_params = {"index_type": itype, "metric_type": metric, "params": dict(params.get("params") or {})}
@@ -943,7 +334,7 @@ class CorpusStore:
     def drop_index(self, **kwargs) -> None:
         """Back to FLAT (the shadow of SQ8 is freed)."""
         with self._rw.write():
-            if getattr(self.index, "sq8", False):
+            if self._has_sq8:
                 self.index.disable_sq8()
             self.index_type = "FLAT"
             self._index_params = None
@@ -960,33 +351,51 @@ class CorpusStore:
     def add(self, ids: Sequence, texts: Sequence[str], embeddings, periods: Sequence[str],
             chunk_types: Sequence[str], statement_types: Sequence[str],
             primary_values: Sequence[float]) -> int:
+        cols = (texts, periods, chunk_types, statement_types, primary_values)
         with self._rw.write():
-            return self._add(ids, texts, embeddings, periods, chunk_types, statement_types, primary_values)
+            self._store_vectors(self._check_batch(ids, cols, embeddings, len(ids), "insert"))
+            self._append_rows(ids, cols)
+        return len(ids)
 
-    def _add(self, ids, texts, embeddings, periods, chunk_types, statement_types, primary_values) -> int:
+    def _check_batch(self, ids, cols, embeddings, n_vec_rows: int, what: str):
+        """Everything an insert / upsert (`what`) refuses, checked before anything changes; returns
+        the fp16 rows to store.  cols: the five scalar columns after id.  embeddings: n_vec_rows rows
+        (the sharded store: this rank's slice); fp16 is embedder output and stays, else to_fp16."""
         torch = _torch()
         n = len(ids)
-        cols = (texts, periods, chunk_types, statement_types, primary_values)
         if any(len(c) != n for c in cols):
-            raise ValueError("insert columns differ in length")
-        if torch.is_tensor(embeddings) and embeddings.dtype == torch.float16:
-            vec = embeddings  # already normalised fp16 (embedder output)
-            if vec.shape != (n, self.dim):
-                raise ValueError(f"embeddings must be [{n}, {self.dim}]")
-        else:
-            emb = np.asarray(embeddings, dtype=np.float32) if not torch.is_tensor(embeddings) else embeddings
-            if tuple(emb.shape) != (n, self.dim):
-                raise ValueError(f"embeddings must be [{n}, {self.dim}], got {tuple(emb.shape)}")
-            vec = self.index.to_fp16(emb, normalize=self.metric_type == "COSINE")
-        for pk in ids:
-            if pk in self._pk_row:
-                raise ValueError(f"duplicate primary key {pk!r}")
+            raise ValueError(f"{what} columns differ in length")
+        if what == "insert":   # (an upsert replaces the rows of its existing keys)
+            for pk in ids:
+                if pk in self._pk_row:
+                    raise ValueError(f"duplicate primary key {pk!r}")
         if len(set(ids)) != n:
-            raise ValueError("duplicate primary keys in insert")
-        if self.index.size + n > self.index.capacity:
-            self._grow(self.index.size + n)
-        base = self.index.size
+            raise ValueError(f"duplicate primary keys in {what}")
+        emb = self._embedding_rows(embeddings, n_vec_rows)
+        if torch.is_tensor(emb) and emb.dtype == torch.float16:
+            return emb
+        if n_vec_rows == 0:
+            return torch.empty((0, self.dim), dtype=torch.float16, device=self.index.device)
+        return self.index.to_fp16(emb, normalize=self.metric_type == "COSINE")
+
+    def _embedding_rows(self, embeddings, n_rows: int):
+        """embeddings as they came when a tensor, else as an fp32 array; ValueError unless [n_rows, dim]."""
+        emb = embeddings if _torch().is_tensor(embeddings) else np.asarray(embeddings, dtype=np.float32)
+        if tuple(emb.shape) != (n_rows, self.dim):
+            raise ValueError(f"embeddings must be [{n_rows}, {self.dim}], got {tuple(emb.shape)}")
+        return emb
+
+    def _store_vectors(self, vec) -> None:
+        """Append the checked fp16 rows to the index, growing it first when they do not fit."""
+        need = self.index.size + vec.shape[0]
+        if need > self.index.capacity:
+            self._grow(need)
         self.index.add(vec)
+
+    def _append_rows(self, ids, cols) -> None:
+        """The host side of an append: the pk map and the six scalar columns."""
+        texts, periods, chunk_types, statement_types, primary_values = cols
+        base = self.num_entities
         for j, pk in enumerate(ids):
             self._pk_row[pk] = base + j
         self.columns["id"].extend(ids)
@@ -995,16 +404,21 @@ class CorpusStore:
         self.columns["chunk_type"].extend(chunk_types)
         self.columns["statement_type"].extend(statement_types)
         self.columns["primary_value"].extend(float(v) for v in primary_values)
-        return n
+
+    @staticmethod
+    def _split_columns(data, what: str):
+        """Column-major `data` in the reference's order -> (ids, the five scalar columns, embeddings)."""
+        if len(data) != 7:
+            raise ValueError(f"{what} expects 7 columns: id, text, embedding, period, chunk_type, "
+                             "statement_type, primary_value")
+        ids, texts, emb, periods, ctypes_, stypes, pvals = data
+        return ids, (texts, periods, ctypes_, stypes, pvals), emb
 
     def insert(self, data: Sequence[Sequence]) -> int:
         """Column-major insert in the reference's order
         [id, text, embedding, period, chunk_type, statement_type, primary_value]."""
-        if len(data) != 7:
-            raise ValueError("insert expects 7 columns: id, text, embedding, period, chunk_type, "
-                             "statement_type, primary_value")
-        ids, texts, emb, periods, ctypes_, stypes, pvals = data
-        return self.add(ids, texts, emb, periods, ctypes_, stypes, pvals)
+        ids, cols, emb = self._split_columns(data, "insert")
+        return self.add(ids, cols[0], emb, *cols[1:])
 
     # -- mutation: Collection.delete(expr) / Collection.upsert(data) -----------------------
     # Deletes compact eagerly: the index, the host columns, the pk map and the device filter
@@ -1024,34 +438,14 @@ class CorpusStore:
         row is appended in the given order: a replaced row moves to the END of the collection (so
         on an exact score tie -- ranked by score desc, then row asc -- it ranks after older rows).
         Duplicate keys inside one batch raise ValueError, as insert does."""
-        if len(data) != 7:
-            raise ValueError("upsert expects 7 columns: id, text, embedding, period, chunk_type, "
-                             "statement_type, primary_value")
-        ids, texts, emb, periods, ctypes_, stypes, pvals = data
+        ids, cols, emb = self._split_columns(data, "upsert")
         ids = list(ids)
         with self._rw.write():
-            emb = self._check_upsert(ids, (texts, periods, ctypes_, stypes, pvals), emb)
+            vec = self._check_batch(ids, cols, emb, len(ids), "upsert")   # before any row goes
             self._delete_mask(self._pk_mask(ids))
-            n = self.add(ids, texts, emb, periods, ctypes_, stypes, pvals)
-            return MutationResult(ids, insert_count=n, upsert_count=n)
-
-    def _check_upsert(self, ids, cols, emb):
-        """Everything add() would refuse, checked BEFORE the old rows go; returns the batch's
-        vectors as the fp16 rows add() stores."""
-        torch = _torch()
-        n = len(ids)
-        if any(len(c) != n for c in cols):
-            raise ValueError("upsert columns differ in length")
-        if len(set(ids)) != n:
-            raise ValueError("duplicate primary keys in upsert")
-        if torch.is_tensor(emb) and emb.dtype == torch.float16:
-            if tuple(emb.shape) != (n, self.dim):
-                raise ValueError(f"embeddings must be [{n}, {self.dim}]")
-            return emb
-        e = np.asarray(emb, dtype=np.float32) if not torch.is_tensor(emb) else emb
-        if tuple(e.shape) != (n, self.dim):
-            raise ValueError(f"embeddings must be [{n}, {self.dim}], got {tuple(e.shape)}")
-        return self.index.to_fp16(e, normalize=self.metric_type == "COSINE")
+            self._store_vectors(vec)
+            self._append_rows(ids, cols)
+        return MutationResult(ids, insert_count=len(ids), upsert_count=len(ids))
 
     def _match_mask(self, expr: str) -> np.ndarray:
         """bool [num_entities]: the rows `expr` matches, evaluated on the device."""
@@ -1129,13 +523,12 @@ class CorpusStore:
 
     def _search_rows(self, data, limit: int, filt=None, band=None, group=None):
         q16 = self._prepare_queries(data)
+        kw = {} if filt is None else {"filt": filt}   # the index is given a keyword only when it is set
         if group is not None:
             # (field, group_size): the padded [B, limit * group_size] block; never SQ8, never paged
             field, gsize = group
-            kw = {} if filt is None else {"filt": filt}
             codes, n_codes = self._group_codes(field)
             return self.index.search_host(q16, limit * gsize, group=(codes, n_codes, limit, gsize), **kw)
-        kw = {} if filt is None else {"filt": filt}
         if band is not None:
             kw["band"] = band
         if limit > _lib.RF_MAX_K:
@@ -1245,8 +638,6 @@ class CorpusStore:
             self._save(path, chunk_rows)
 
     def _save(self, path: str, chunk_rows: int) -> None:
-        import json
-        import os
         os.makedirs(path, exist_ok=True)
         n = self.num_entities
         tmp = os.path.join(path, "vectors.f16.tmp")
@@ -1255,7 +646,11 @@ class CorpusStore:
                 rows = np.arange(s0, min(n, s0 + chunk_rows), dtype=np.int64)
                 f.write(self.index.get_rows(rows).cpu().numpy().tobytes())
         os.replace(tmp, os.path.join(path, "vectors.f16"))
-        meta = {"format": "ragfin-corpus-v1", "name": self.name, "dim": self.dim,
+        self._write_meta(path, n)
+
+    def _write_meta(self, path: str, n: int) -> None:
+        """columns.json, written to a temporary file and moved into place."""
+        meta = {"format": FORMAT, "name": self.name, "dim": self.dim,
                 "metric_type": self.metric_type, "n": n, "columns": self.columns}
         if self.index_type != "FLAT":   # FLAT directories stay exactly as before
             meta["index_type"] = self.index_type
@@ -1264,35 +659,48 @@ class CorpusStore:
             json.dump(meta, f, ensure_ascii=False)
         os.replace(tmp, os.path.join(path, "columns.json"))
 
+    @staticmethod
+    def _read_meta(path: str):
+        """columns.json of a corpus directory -> (meta, n, dim)."""
+        with open(os.path.join(path, "columns.json"), encoding="utf-8") as f:
+            meta = json.load(f)
+        if meta.get("format") != FORMAT:
+            raise ValueError(f"{path}: not a ragfin corpus directory")
+        return meta, int(meta["n"]), int(meta["dim"])
+
+    def _load_rows(self, path: str, n: int, lo: int, hi: int, chunk_rows: int) -> None:
+        """Memory-map vectors.f16 (n rows); stream rows [lo, hi) into the index chunk by chunk."""
+        torch = _torch()
+        if not n:
+            return
+        expect = n * self.dim * 2
+        got = os.path.getsize(os.path.join(path, "vectors.f16"))
+        if got != expect:
+            raise ValueError(f"{path}/vectors.f16 holds {got} bytes, expected {expect}")
+        mm = np.memmap(os.path.join(path, "vectors.f16"), dtype=np.float16, mode="r", shape=(n, self.dim))
+        for s0 in range(lo, hi, chunk_rows):
+            s1 = min(hi, s0 + chunk_rows)
+            self.index.add(torch.from_numpy(np.ascontiguousarray(mm[s0:s1])).to(self.index.device))
+        del mm
+
+    def _adopt_columns(self, path: str, meta: dict, n: int) -> None:
+        """The scalar columns of a loaded columns.json become this store's; the pk map is rebuilt."""
+        cols = meta["columns"]
+        if any(len(cols[f]) != n for f in SCALAR_FIELDS):
+            raise ValueError(f"{path}: column lengths do not match n={n}")
+        self.columns = {f: list(cols[f]) for f in SCALAR_FIELDS}
+        self._pk_row = {pk: i for i, pk in enumerate(self.columns["id"])}
+
     @classmethod
     def load_from(cls, path: str, device=None, capacity: int | None = None,
                   chunk_rows: int = 1 << 18) -> "CorpusStore":
         """Memory-map vectors.f16 and stream it into HBM in chunks (never the whole file
         in host RAM)."""
-        import json
-        import os
-        torch = _torch()
-        with open(os.path.join(path, "columns.json"), encoding="utf-8") as f:
-            meta = json.load(f)
-        if meta.get("format") != "ragfin-corpus-v1":
-            raise ValueError(f"{path}: not a ragfin corpus directory")
-        n, dim = int(meta["n"]), int(meta["dim"])
+        meta, n, dim = cls._read_meta(path)
         st = cls(meta["name"], dim=dim, capacity=max(capacity or 0, n, 1), device=device,
                  metric_type=meta["metric_type"])
-        if n:
-            expect = n * dim * 2
-            got = os.path.getsize(os.path.join(path, "vectors.f16"))
-            if got != expect:
-                raise ValueError(f"{path}/vectors.f16 holds {got} bytes, expected {expect}")
-            mm = np.memmap(os.path.join(path, "vectors.f16"), dtype=np.float16, mode="r", shape=(n, dim))
-            for s0 in range(0, n, chunk_rows):
-                st.index.add(torch.from_numpy(np.ascontiguousarray(mm[s0:s0 + chunk_rows])).to(st.index.device))
-            del mm
-        cols = meta["columns"]
-        if any(len(cols[f]) != n for f in SCALAR_FIELDS):
-            raise ValueError(f"{path}: column lengths do not match n={n}")
-        st.columns = {f: list(cols[f]) for f in SCALAR_FIELDS}
-        st._pk_row = {pk: i for i, pk in enumerate(st.columns["id"])}
+        st._load_rows(path, n, 0, n, chunk_rows)
+        st._adopt_columns(path, meta, n)
         itype = meta.get("index_type", "FLAT")   # a missing key means FLAT
         if itype != "FLAT":
             st.create_index("embedding", {"index_type": itype, "metric_type": st.metric_type})

@@ -414,3 +414,36 @@ def test_one_hit_of_every_period_on_the_golden_chunks(gpu_device):
         assert sorted(c["period"] for c in got) == sorted(set(periods))
         assert [c["period"] for c in got] == [w[2] for w in want]
         assert [np.float32(c["score"]) for c in got] == [w[1] for w in want]
+
+
+# ---- search_host: the same first pass and ladder as search, then the download -------------------------
+@pytest.mark.parametrize("filtered", [False, True])
+@pytest.mark.parametrize("G", [70, 16])
+def test_search_host_is_search_moved_to_the_host(gpu_device, G, filtered):
+    """70 codes is above RF_GROUP_MAX_CODES: every query is flagged and the whole batch goes down
+    the ladder; with 16 codes no query is flagged."""
+    import torch
+    from rag_fin_amd import _lib
+    N, d, B, n, s = 300, 64, 3, 4, 2
+    c16 = osearch.synth_unit_rows(N, d, 31)
+    q16 = osearch.synth_unit_rows(B, d, 32)
+    S = osearch.exact_scores(q16, c16)
+    ix = make_index(c16, gpu_device)
+    codes = coding(N, G, "interleaved")
+    mask = np.random.default_rng(33).random(N) < 0.5 if filtered else None
+    filt = mask_filter(ix, mask, gpu_device) if filtered else None
+    q = torch.from_numpy(q16).to(gpu_device)
+    group = (torch.from_numpy(codes).to(gpu_device), G, n, s)
+    if G > _lib.RF_GROUP_MAX_CODES:
+        with pytest.raises(_lib.RagfinError):       # no first pass of its own: the ladder answers every query
+            ix.search_raw(q, n * s, filt=filt, group=group)
+    else:
+        flags = ix.search_raw(q, n * s, filt=filt, group=group)[3]
+        assert int(flags.abs().sum()) == 0
+    scores, ids, exact = ix.search(q, n * s, want_exact=True, filt=filt, group=group)
+    check_equal(scores, ids, exact, *grouped_oracle(S, codes, G, n, s, mask))
+    host_scores, host_ids = ix.search_host(q, n * s, filt=filt, group=group)
+    assert isinstance(host_scores, np.ndarray) and host_scores.dtype == np.float32 and host_ids.dtype == np.int64
+    assert np.array_equal(host_ids, ids.cpu().numpy())
+    assert np.array_equal(host_scores.view(np.uint32), scores.cpu().numpy().view(np.uint32))
+    assert (host_ids >= 0).sum() > B * s                 # not vacuous: more than one group per query

@@ -485,3 +485,135 @@ def test_sharded_delete_and_upsert_equal_a_single_store(tmp_path, world):
     # the saved corpus is the single-GPU format, in global row order
     mm = np.fromfile(tmp_path / "corpus" / "vectors.f16", dtype=np.float16).reshape(-1, D_SH)
     assert np.array_equal(mm.view(np.uint16), c16.view(np.uint16))
+
+
+# ---- one ingest check: a bad batch is refused whole, by either store, for insert and upsert --------------
+D_BAD = 32
+
+
+def _plain_store():
+    return CorpusStore("t", dim=D_BAD, capacity=16, index=CpuIndex(D_BAD, 16))
+
+
+def _sharded_store_world_1(tmp_path):
+    from rag_fin_amd.sharded_store import ShardedCorpusStore
+    dist.init_process_group("gloo", init_method=f"file://{tmp_path}/pg", rank=0, world_size=1)
+    return ShardedCorpusStore("t", dim=D_BAD, capacity=16, index=CpuIndex(D_BAD, 16))
+
+
+def _bad_batch(case, what):
+    """Batches of 3 for a store that holds k0 .. k4; an upsert batch replaces k1, so a delete made
+    before the refusal would show."""
+    keys = ["k5", "k6", "k7"] if what == "insert" else ["k1", "k5", "k6"]
+    if case == "a key twice in the batch":
+        keys[2] = keys[0]
+    if case == "a key already present":
+        keys[1] = "k3"
+    n_vec, d_vec = (2 if case == "embeddings [n - 1, dim]" else 3), (D_BAD + 1 if case == "embeddings [n, dim + 1]" else D_BAD)
+    b = batch(keys, vecs(n_vec, d_vec, 41))
+    if case == "a column one short":
+        b[3] = b[3][:-1]
+    return b[:6] if case == "6 columns" else b
+
+
+BAD_CASES = ["a column one short", "a key twice in the batch", "embeddings [n, dim + 1]", "embeddings [n - 1, dim]",
+             "6 columns"]
+
+
+BAD_PARAMS = [(w, c) for w in ("insert", "upsert") for c in BAD_CASES] + [("insert", "a key already present")]
+
+
+@pytest.mark.parametrize("what,case", BAD_PARAMS)
+@pytest.mark.parametrize("kind", ["CorpusStore", "ShardedCorpusStore"])
+def test_a_bad_batch_is_refused_and_changes_nothing(tmp_path, kind, what, case):
+    try:
+        st = _plain_store() if kind == "CorpusStore" else _sharded_store_world_1(tmp_path)
+        st.insert(batch([f"k{i}" for i in range(5)], vecs(5, D_BAD, 40)))
+        before = ({f: list(c) for f, c in st.columns.items()}, dict(st._pk_row), st.index.rows.copy())
+        with pytest.raises(ValueError):
+            getattr(st, what)(_bad_batch(case, what))
+        assert st.num_entities == 5 == st.index.size
+        assert st.columns == before[0] and all(len(c) == 5 for c in st.columns.values())
+        assert st._pk_row == before[1] == {f"k{i}": i for i in range(5)}
+        assert np.array_equal(st.index.rows.view(np.uint16), before[2].view(np.uint16)) and st.index.compactions == []
+        if kind == "ShardedCorpusStore":
+            assert st._id_map.tolist() == list(range(5))
+        # the batch without its fault goes through
+        getattr(st, what)(_bad_batch(None, what))
+        assert st.num_entities == (8 if what == "insert" else 7) == st.index.size
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def _bad_batch_worker(rank, world, port, out_dir):
+    from rag_fin_amd.sharded_store import ShardedCorpusStore
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        st = ShardedCorpusStore("t", dim=D_BAD, capacity=16, index=CpuIndex(D_BAD, 16))
+        st.insert(batch([f"k{i}" for i in range(5)], vecs(5, D_BAD, 40)))
+        rows0, refused, unchanged = st.index.rows.copy(), [], []
+        for what, case in BAD_PARAMS:
+            try:
+                getattr(st, what)(_bad_batch(case, what))
+                refused.append(False)
+            except ValueError:
+                refused.append(True)
+            unchanged.append(st.columns["id"] == [f"k{i}" for i in range(5)] and
+                             all(len(c) == 5 for c in st.columns.values()) and
+                             st._pk_row == {f"k{i}": i for i in range(5)} and st.index.compactions == [] and
+                             np.array_equal(st.index.rows.view(np.uint16), rows0.view(np.uint16)))
+        np.savez(os.path.join(out_dir, f"bad{rank}.npz"), refused=np.array(refused), unchanged=np.array(unchanged),
+                 id_map=st._id_map.numpy())
+    finally:
+        dist.destroy_process_group()
+
+
+def test_a_bad_batch_is_refused_by_every_rank_of_a_sharded_store(tmp_path):
+    """World 2, batches of 3: rank 0 owns rows [0, 2) of a batch and rank 1 row 2, so a whole
+    embedding column that is one row short would pass a check of rank 0's slice alone.  Every rank
+    must refuse every case, or the ranks' columns and id maps part ways."""
+    mp.spawn(_bad_batch_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    maps = []
+    for r in range(2):
+        z = np.load(tmp_path / f"bad{r}.npz")
+        assert z["refused"].all(), (r, [p for p, ok in zip(BAD_PARAMS, z["refused"]) if not ok])
+        assert z["unchanged"].all(), (r, [p for p, ok in zip(BAD_PARAMS, z["unchanged"]) if not ok])
+        maps.append(z["id_map"].tolist())
+    assert maps == [[0, 1, 2], [3, 4]]
+
+
+# ---- one loader, one metadata writer: the directory is the one the format's first version wrote ----------
+GOLD_STORE = os.path.join(os.path.dirname(__file__), "golden", "store_v1")
+
+
+class LoadableHostStore(HostStore):
+    """HostStore with the constructor signature load_from calls."""
+
+    def __init__(self, name="t", dim=32, capacity=16, device=None, metric_type="COSINE"):
+        CorpusStore.__init__(self, name, dim=dim, capacity=capacity, metric_type=metric_type,
+                             index=CpuIndex(dim, capacity))
+
+
+def golden_store():
+    """The 5-row, dim-32 store whose saved directory is tests/golden/store_v1."""
+    st = LoadableHostStore()
+    st.insert(batch([f"k{i}" for i in range(5)], vecs(5, 32, 50), tag="gold"))
+    return st
+
+
+def test_save_load_save_is_byte_identical_to_the_recorded_directory(tmp_path):
+    def files(path):
+        return {name: open(os.path.join(path, name), "rb").read() for name in ("vectors.f16", "columns.json")}
+    want = files(GOLD_STORE)
+    assert len(want["vectors.f16"]) == 5 * 32 * 2
+    st = golden_store()
+    st.save(str(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["columns.json", "vectors.f16"]
+    assert files(tmp_path / "a") == want
+    st2 = LoadableHostStore.load_from(str(tmp_path / "a"))
+    assert st2.columns == st.columns and st2._pk_row == st._pk_row and st2.name == "t" and st2.index_type == "FLAT"
+    assert np.array_equal(st2.index.rows.view(np.uint16), st.index.rows.view(np.uint16))
+    st2.save(str(tmp_path / "b"))
+    assert files(tmp_path / "b") == want
