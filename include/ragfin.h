@@ -309,6 +309,35 @@ int rf_search_grouped_profile(const rf_index_t* ix, const void* filter_dev, cons
                               uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream,
                               float* stage_ms_host);
 size_t rf_debug_grouped_counters_offset(void);
+/* ---- diversified search: maximal-marginal-relevance re-ranking of a search's answer ----------------
+ * What RAG clients do after Collection.search (LangChain's max_marginal_relevance_search: search
+ * fetch_k hits, query() their vectors back, a numpy loop), as one stage on the device: it picks k
+ * of the fetch_k candidates of a search, trading relevance against similarity to what is already
+ * picked.  The candidates are the [B, fetch_k] outputs of ANY search entry point above for
+ * k = fetch_k (plain, filtered, range, SQ8, exhaustive): their ids (id_base included, -1 padded)
+ * and their fp64 ranking scores (exact_dev), in that search's order.
+ * Definition, per query (1 <= k <= fetch_k <= RF_MAX_K, lambda in [0, 1],
+ * mu = 1.0 - lambda in fp64): candidate i has the score s_i; g(i, j) is the contract dot product of
+ * the fp16 rows of candidates i and j (the cosine for normalised rows); m_i = -inf.  Each round
+ * computes v_i = (lambda * s_i) - pen_i for every unselected i, pen_i = 0.0 in the first round and
+ * mu * m_i afterwards, the two products and the subtraction each rounded to fp64 on its own (no
+ * fma); the pick is the largest v_i, the smallest i on a tie; then m_i = max(m_i, g(i, pick)).
+ * min(k, real candidates) rounds.  Output slot t holds the t-th pick: (float(s), id, s) -- the
+ * RELEVANCE score, in MMR order; the remaining slots are -inf / -1.  lambda = 1 reproduces the
+ * first k candidates; the first pick is always the best hit.  An id that is negative or whose row
+ * (id - id_base) is not in the index is treated as absent.  Non-finite candidate scores:
+ * unspecified.
+ * Conventions of rf_search: stream-ordered, no host sync, no allocation, no workspace, captures
+ * into a hipGraph, outputs may be pinned host memory.  RF_ERR_INVALID: a null pointer (exact_dev
+ * may be NULL), B < 1, k < 1, k > fetch_k, fetch_k > RF_MAX_K, lambda outside [0, 1] or NaN --
+ * checked on the host before any device call.  The flags of the candidate search still decide
+ * whether a query's candidates are proven exact: re-run a flagged query, then this stage on it.
+ * One workgroup per query; the candidate rows are staged once in LDS (fetch_k x (dim * 2 + 16)
+ * bytes, 129 KiB at dim 1024 and fetch_k 64), the rounds read LDS only.
+ * New in this build; the reference has no re-ranking stage. */
+int rf_mmr_select(const rf_index_t* ix, int B, int fetch_k, int k, double lambda, int64_t id_base,
+                  const double* cand_exact_dev, const int64_t* cand_ids_dev, float* scores_dev,
+                  int64_t* ids_dev, double* exact_dev, void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

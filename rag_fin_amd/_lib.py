@@ -101,6 +101,8 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                           POINTER(c_float)]),
     "rf_debug_grouped_counters_offset": (c_size_t, []),
+    "rf_mmr_select": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
     "rf_packed_shard_words": (c_size_t, [c_int, c_int]),

@@ -41,13 +41,17 @@ class SearchRequest(BaseModel):
     # grouping search (the best top_k groups by a scalar field, group_size chunks each); new
     group_by: Optional[str] = None
     group_size: Optional[int] = Field(default=None, ge=1)
+    # diversified search (maximal marginal relevance over the best fetch_k chunks); new
+    mmr_lambda: Optional[float] = Field(default=None, ge=0.0, le=1.0)
+    fetch_k: Optional[int] = Field(default=None, ge=1, le=64)
 
 
 def search_args(req: SearchRequest) -> dict:
-    """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by` and
-    `group_size` only when they were given, so the reference's payload {"query", "top_k"} is unchanged."""
+    """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by`, `group_size`,
+    `mmr_lambda` and `fetch_k` only when they were given, so the reference's payload
+    {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
-    for name in ("filter", "min_score", "max_score", "group_by", "group_size"):
+    for name in ("filter", "min_score", "max_score", "group_by", "group_size", "mmr_lambda", "fetch_k"):
         if getattr(req, name) is not None:
             args[name] = getattr(req, name)
     return args

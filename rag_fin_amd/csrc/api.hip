@@ -611,6 +611,27 @@ extern "C" int rf_search_grouped_profile(const rf_index_t* ix, const void* filte
                       workspace_bytes, (hipStream_t)stream, stage_ms_host);
 }
 
+// ---- diversified search (include/ragfin.h, "diversified search") ----------------------------------
+extern "C" int rf_mmr_select(const rf_index_t* ix, int B, int fetch_k, int k, double lambda, int64_t id_base,
+                             const double* cand_exact_dev, const int64_t* cand_ids_dev, float* scores_dev,
+                             int64_t* ids_dev, double* exact_dev, void* stream) {
+  if (!ix || !cand_exact_dev || !cand_ids_dev || !scores_dev || !ids_dev) {
+    rf_set_error("rf_mmr_select: null argument");
+    return RF_ERR_INVALID;
+  }
+  if (B < 1 || k < 1 || k > fetch_k || fetch_k > RF_MAX_K) {
+    rf_set_error("rf_mmr_select: need B >= 1 and 1 <= k <= fetch_k <= %d (got B = %d, k = %d, fetch_k = %d)",
+                 RF_MAX_K, B, k, fetch_k);
+    return RF_ERR_INVALID;
+  }
+  if (!(lambda >= 0.0 && lambda <= 1.0)) {   // also catches a NaN
+    rf_set_error("rf_mmr_select: lambda = %g outside [0, 1]", lambda);
+    return RF_ERR_INVALID;
+  }
+  return rf_launch_mmr(ix, B, fetch_k, k, lambda, id_base, cand_exact_dev, cand_ids_dev, scores_dev, ids_dev,
+                       exact_dev, (hipStream_t)stream);
+}
+
 extern "C" int rf_merge_shards(const double* exact_dev, const int64_t* ids_dev, int W, int B, int k,
                                float* scores_out_dev, int64_t* ids_out_dev, void* stream) {
   if (!exact_dev || !ids_dev || !scores_out_dev || !ids_out_dev || W <= 0 || B <= 0 || k <= 0) {

@@ -1,6 +1,7 @@
-// Device helpers shared by the candidate merges: k_merge (merge.hip) and k_merge_grouped
-// (grouped.hip).  The candidate order and the rescoring stage are the exactness contract
-// (mirrored by oracle/search.py): both merges take them from here.
+// Device helpers shared by the candidate merges, k_merge (merge.hip) and k_merge_grouped
+// (grouped.hip), and by the MMR stage k_mmr (mmr.hip).  The candidate order, the contract dot and
+// the rescoring stage are the exactness contract (mirrored by oracle/search.py): all
+// three take them from here.
 #pragma once
 #include "rf_internal.h"
 
@@ -74,11 +75,26 @@ __device__ __forceinline__ uint2 cand_at(const CandLists& L, uint32_t g, uint32_
   return e;
 }
 
+// The contract dot product of two fp16 rows of `chunks` 16-byte chunks in LDS, by 8 adjacent
+// lanes (an aligned group of 8; every lane of the wave calls it): lane j owns chain j of the
+// contract (dims j, j + 8, ... ascending, one fma per step; the product of two fp16 values is
+// exact in fp64, so the result does not depend on which row is `a`), combined by the xor tree
+// 1, 2, 4 = ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)).  Every lane of the group returns the dot.
+__device__ __forceinline__ double contract_dot8(const _Float16* a, const _Float16* b, int chunks, int j) {
+  double acc = 0.0;
+#pragma unroll 8
+  for (int ch = 0; ch < chunks; ++ch)
+    acc = fma((double)a[8 * ch + j], (double)b[8 * ch + j], acc);
+  acc += __shfl_xor(acc, 1);
+  acc += __shfl_xor(acc, 2);
+  acc += __shfl_xor(acc, 4);
+  return acc;
+}
+
 // The fp64 ranking scores of the rows r_row[0..R) into r_exact, by all MERGE_THREADS threads:
 // the rows pass through LDS MERGE_STAGE_ROWS at a time (srows: [32][2 KS + 1] uint4; one HBM
-// latency per stage instead of one per 16-byte chunk), then 8 lanes per row: lane j owns chain j
-// of the contract (dims j, j + 8, ... ascending, one fma per step), combined by the xor tree
-// 1, 2, 4 = ((p0+p1)+(p2+p3))+((p4+p5)+(p6+p7)).  qh: the query row as fp16 in LDS.
+// latency per stage instead of one per 16-byte chunk), then 8 lanes per row run contract_dot8
+// against the query.  qh: the query row as fp16 in LDS.
 __device__ __forceinline__ void rescore_rows(const uint32_t* r_row, uint32_t R, const uint4* __restrict__ tiles,
                                              int KS, const _Float16* qh, uint4* srows, double* r_exact) {
   const int tid = threadIdx.x;
@@ -95,13 +111,7 @@ __device__ __forceinline__ void rescore_rows(const uint32_t* r_row, uint32_t R, 
       const uint32_t r = (uint32_t)tid >> 3;   // 32 rows x 8 lanes = 256 threads
       const int j = tid & 7;
       const _Float16* row = (const _Float16*)(srows + (r < nb ? r : 0) * srow_stride);
-      double acc = 0.0;
-#pragma unroll 8
-      for (int ch = 0; ch < chunks; ++ch)
-        acc = fma((double)qh[8 * ch + j], (double)row[8 * ch + j], acc);
-      acc += __shfl_xor(acc, 1);
-      acc += __shfl_xor(acc, 2);
-      acc += __shfl_xor(acc, 4);
+      const double acc = contract_dot8(qh, row, chunks, j);
       if (j == 0 && r < nb) r_exact[base + r] = acc;
     }
     __syncthreads();

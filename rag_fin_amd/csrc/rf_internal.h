@@ -263,6 +263,11 @@ int rf_launch_merge_grouped(const rf_index* ix, const void* q, int B, const rf_g
 int rf_launch_merge_shards(const double* exact, const int64_t* ids, size_t shard_stride, int W, int B, int k,
                            float* scores_out, int64_t* ids_out, const uint32_t* flags_in, size_t flag_stride,
                            uint32_t* flags_out, hipStream_t st);
+// mmr.hip (include/ragfin.h, "diversified search"): MMR selection of k of the fetch_k candidates
+// per query, one workgroup per query; the arguments are checked by the caller
+int rf_launch_mmr(const rf_index* ix, int B, int fetch_k, int k, double lambda, int64_t id_base,
+                  const double* cand_exact, const int64_t* cand_ids, float* scores, int64_t* ids,
+                  double* exact, hipStream_t st);
 
 // order-preserving map float -> uint32 (larger float <=> larger uint)
 __host__ __device__ inline uint32_t rf_f2ord(float f) {

@@ -335,7 +335,7 @@ class GpuIndex:
                 torch.empty((B,), dtype=torch.int32, device=self.device) if flags else None)
 
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None, group=None):
+                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None, group=None, mmr=None):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
         hipStream_t of this device); no host sync.  Returns
         (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
@@ -349,15 +349,30 @@ class GpuIndex:
         the best n_groups groups of rows sharing a code, each by its best group_size rows (within
         the passing rows with filt; not with sq8 or band).  k must be n_groups * group_size; the
         outputs are in the padded slot form (group of rank j in slots [j s, (j + 1) s)).
+        mmr: (fetch_k, lam) -- diversified search: the search above runs with the limit fetch_k (into
+        device tensors of its own, with the fp64 scores), then rf_mmr_select picks k of its hits by
+        maximal marginal relevance with lambda = lam (1 = relevance only) into the outputs, on the
+        same stream.  With filt, band or sq8; not with group.  The scores returned are the relevance
+        scores, in MMR order; the flags are those of the candidate search.  (The candidate tensors
+        come from torch's allocator on the current stream: with a stream_ptr of another stream the
+        caller keeps that stream ahead of their reuse, as for every tensor it passes in.)
         Takes no lock, with or without a workspace of the caller's: the benchmark and the sharded
         lanes call it on their own streams, and whoever shares the index's workspace serialises."""
         torch = _torch()
-        self._check_variant(filt, sq8, band, group, k)
+        self._check_variant(filt, sq8, band, group, k, mmr)
         if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
             raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
         if not q16.is_contiguous() or q16.device != self.device:
             q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
+        if mmr is not None:
+            # the candidate search (its flags land in the caller's), then the MMR stage behind it
+            res = self._outputs(B, k, want_exact, out=out)
+            _, cand_ids, cand_exact, _ = self.search_raw(
+                q16, int(mmr[0]), id_base, True, out=self._outputs(B, int(mmr[0]), True, flags=False)[:3] + (res[3],),
+                workspace=workspace, stream_ptr=stream_ptr, filt=filt, sq8=sq8, band=band)
+            self._mmr_select(cand_exact, cand_ids, k, mmr, id_base, res, stream_ptr)
+            return res
         scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
         args = (_ptr(q16), B, k, id_base, _ptr(scores), _ptr(ids), _ptr(exact), _ptr(flags),
                 _ptr(workspace if workspace is not None else self.workspace),
@@ -379,8 +394,29 @@ class GpuIndex:
                 _lib.check(self.lib.rf_search_filtered(self.handle, _ptr(filt), *args))
         return scores, ids, exact, flags
 
-    def _check_variant(self, filt, sq8: bool, band, group, k: int) -> None:
-        """Which of filt / sq8 / band / group go together, for every search method."""
+    def _mmr_select(self, cand_exact, cand_ids, k: int, mmr, id_base: int, out, stream_ptr=None):
+        """Enqueue rf_mmr_select over the candidates (fp64 scores, ids: device tensors [B, fetch_k])
+        into out = (scores, ids, exact | None, ...); no host sync."""
+        torch = _torch()
+        B, fetch_k = cand_ids.shape
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_mmr_select(self.handle, B, fetch_k, k, float(mmr[1]), id_base, _ptr(cand_exact),
+                                              _ptr(cand_ids), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                              stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+
+    def _check_variant(self, filt, sq8: bool, band, group, k: int, mmr=None) -> None:
+        """Which of filt / sq8 / band / group / mmr go together, for every search method."""
+        if mmr is not None:
+            if group is not None:
+                raise ValueError("diversified search (mmr) has no grouping form")
+            fetch_k, lam = mmr
+            if isinstance(fetch_k, bool) or not isinstance(fetch_k, (int, np.integer)) or \
+                    not 1 <= k <= fetch_k <= _lib.RF_MAX_K:
+                raise ValueError(f"diversified search: need 1 <= k <= fetch_k <= {_lib.RF_MAX_K} "
+                                 f"(got k = {k}, fetch_k = {fetch_k!r})")
+            if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or \
+                    not 0.0 <= float(lam) <= 1.0:
+                raise ValueError(f"diversified search: lambda must be a real number in [0, 1], got {lam!r}")
         if group is not None:
             if sq8 or band is not None:
                 raise ValueError("grouping search has no SQ8 and no range form")
@@ -530,32 +566,45 @@ class GpuIndex:
         return res
 
     def _search_ladder(self, q16, k: int, id_base: int, want_exact: bool, filt, sq8: bool, band, group, out=None,
-                       landed=None):
+                       landed=None, mmr=None):
         """The first pass (search_raw, or _grouped_first_pass for a grouping search), then the
         flagged-query ladder -> ((scores, ids, exact, flags), bad, rows): the first pass's outputs
         and what _rerun_flagged gives; the caller patches rows `bad` of its own destination when
         rows is not None.  out: as in search_raw.  landed(outputs) -> flags: called between the two
-        by search_host, which reads the flags on the host once it has synchronised.  Caller locks."""
+        by search_host, which reads the flags on the host once it has synchronised.  Caller locks.
+        mmr: as in search_raw; the first pass enqueues the candidate search and the MMR stage back to
+        back, and a flagged query gets its fetch_k candidates from the ladder and the MMR stage again:
+        its first-pass row is always replaced."""
         if group is not None:
             res = self._grouped_first_pass(q16, k, id_base, want_exact, filt, sq8, band, group, out)
         else:
-            res = self.search_raw(q16, k, id_base, want_exact, out=out, filt=filt, sq8=sq8, band=band)
+            res = self.search_raw(q16, k, id_base, want_exact, out=out, filt=filt, sq8=sq8, band=band, mmr=mmr)
         flags = res[3]
         if landed is not None:
             flags = landed(res)
             if not bool(flags.any()):
                 return res, None, None
-        return (res,) + self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt, band, group)
+        if mmr is None:
+            return (res,) + self._rerun_flagged(q16, k, id_base, want_exact, flags, sq8, filt, band, group)
+        bad, cand = self._rerun_flagged(q16, int(mmr[0]), id_base, True, flags, sq8, filt, band)
+        if cand is None:
+            return res, bad, None
+        rows = self._outputs(cand[1].shape[0], k, want_exact, flags=False)[:3]
+        self._mmr_select(cand[2].contiguous(), cand[1].contiguous(), k, mmr, id_base, rows)
+        return res, bad, list(rows)
 
     def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False,
-               band=None, group=None):
+               band=None, group=None, mmr=None):
         """rf_search, then the flagged-query ladder (rerun_flagged) for any query the fused path
         could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first.
         band: (radius, range_filter) -- rf_search_range, flagged queries through the exhaustive
         band kernel.  group: as in search_raw -- rf_search_grouped, flagged queries (and every query
-        of a dictionary above RF_GROUP_MAX_CODES) group by group through the exhaustive kernel."""
+        of a dictionary above RF_GROUP_MAX_CODES) group by group through the exhaustive kernel.
+        mmr: (fetch_k, lam), as in search_raw -- k of the best fetch_k hits by maximal marginal
+        relevance; flagged queries get their candidates from the ladder and are selected again."""
         with self._lock:
-            (scores, ids, exact, _), bad, rows = self._search_ladder(q16, k, id_base, want_exact, filt, sq8, band, group)
+            (scores, ids, exact, _), bad, rows = self._search_ladder(q16, k, id_base, want_exact, filt, sq8, band, group,
+                                                                     mmr=mmr)
             if rows is not None:
                 for dst, src in zip((scores, ids, exact), rows):
                     if dst is not None:
@@ -564,12 +613,13 @@ class GpuIndex:
 
     ZERO_COPY_MAX = 4096   # B * k up to which search_host lets the kernel write into host memory
 
-    def search_host(self, q16, k: int, filt=None, sq8: bool = False, band=None, group=None):
+    def search_host(self, q16, k: int, filt=None, sq8: bool = False, band=None, group=None, mmr=None):
         """search() whose results land on the host with ONE synchronisation: scores, ids and
         flags are copied into cached pinned buffers asynchronously.  -> (scores f32 [B,k],
         ids i64 [B,k]) numpy arrays (the caller's own copies).  filt: over the passing rows.
         sq8: rf_search_sq8 first, as in search().  band: (radius, range_filter), as in search().
-        group: as in search(); k = n_groups * group_size, the padded slot form."""
+        group: as in search(); k = n_groups * group_size, the padded slot form.
+        mmr: (fetch_k, lam), as in search(); still one synchronisation unless a query is flagged."""
         torch = _torch()
         with self._lock:
             B = q16.shape[0]
@@ -592,7 +642,7 @@ class GpuIndex:
                 return bufs[2]
 
             _, bad, rows = self._search_ladder(q16, k, 0, False, filt, sq8, band, group,
-                                               (bufs[0], bufs[1], None, bufs[2]) if zero_copy else None, landed)
+                                               (bufs[0], bufs[1], None, bufs[2]) if zero_copy else None, landed, mmr)
             if rows is not None:
                 bufs[0][bad] = rows[0].cpu()
                 bufs[1][bad] = rows[1].cpu()

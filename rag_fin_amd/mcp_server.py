@@ -56,26 +56,34 @@ def _searcher():
 
 
 def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
-                   max_score: float | None = None, group_by: str | None = None, group_size: int = 1):
+                   max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
+                   mmr_lambda: float | None = None, fetch_k: int | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
     group_by: optional grouping field (period, chunk_type, statement_type): the best top_k groups,
-    each by its best group_size chunks, as one flat ranked list."""
+    each by its best group_size chunks, as one flat ranked list.
+    mmr_lambda: optional diversification, 0..1 (maximal marginal relevance: 1 = relevance only, lower
+    values trade relevance for chunks unlike those already returned); fetch_k: how many best chunks
+    the top_k are picked from (at most 64)."""
     try:
+        # (only what was given travels on; diversified calls bypass the micro-batcher as well)
+        mmr = {name: v for name, v in (("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k)) if v is not None}
         if group_by is not None:
             # grouped calls bypass the micro-batcher like filtered ones: one batch shares one grouping
             kw = {"group_by": group_by, "group_size": group_size}
             if min_score is not None or max_score is not None:
                 kw.update(min_score=min_score, max_score=max_score)   # (the store refuses the combination)
-            contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None, **kw)
+            contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None, **kw, **mmr)
         elif min_score is not None or max_score is not None:
             # like filtered calls, banded calls bypass the micro-batcher: one batch shares one band
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
-                                        min_score=min_score, max_score=max_score)
+                                        min_score=min_score, max_score=max_score, **mmr)
         elif filter and filter.strip():
             # filtered calls bypass the micro-batcher: one batch shares one filter
-            contexts = get_rag().search(query, top_k, expr=filter)
+            contexts = get_rag().search(query, top_k, expr=filter, **mmr)
+        elif mmr:
+            contexts = get_rag().search(query, top_k, **mmr)
         else:
             contexts = _searcher().search(query, top_k)
         return {"status": "success", "query": query, "results": contexts,

@@ -68,19 +68,29 @@ class VectorRAG:
         """The store's grouping arguments; nothing when group_by is absent (the call of before)."""
         return {} if group_by is None else {"group_by_field": group_by, "group_size": group_size}
 
+    @staticmethod
+    def _mmr_args(mmr_lambda, fetch_k) -> dict:
+        """The store's diversified-search arguments, each only when it was given."""
+        return {name: v for name, v in (("mmr_lambda", mmr_lambda), ("mmr_fetch_k", fetch_k)) if v is not None}
+
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
-               max_score: float | None = None, group_by: str | None = None, group_size: int = 1) -> list[dict]:
+               max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
+               mmr_lambda: float | None = None, fetch_k: int | None = None) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
         the list may be shorter than top_k, or empty).
         group_by ("period", "chunk_type", "statement_type"): grouping search -- the best top_k
         groups by that field, each by its best group_size chunks, as one flat list (group after
-        group, `rank` = the 1-based position in it); every dict carries the field already."""
+        group, `rank` = the 1-based position in it); every dict carries the field already.
+        mmr_lambda (0..1): diversified search -- the top_k chunks are picked from the best fetch_k
+        (default min(64, max(20, 4 top_k))) by maximal marginal relevance, so near-copies of one
+        chunk do not crowd out the rest; `rank` is the MMR order, `score` stays the relevance."""
         q = self._embed([query])
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
-                                         **self._group_args(group_by, group_size))
+                                         **self._group_args(group_by, group_size),
+                                         **self._mmr_args(mmr_lambda, fetch_k))
         return self._contexts(results[0])
 
     def _embed(self, texts):
@@ -94,16 +104,19 @@ class VectorRAG:
 
     def search_batch(self, queries: Sequence[str], top_k: int = 3, expr: str | None = None,
                      min_score: float | None = None, max_score: float | None = None,
-                     group_by: str | None = None, group_size: int = 1) -> list[list[dict]]:
+                     group_by: str | None = None, group_size: int = 1,
+                     mmr_lambda: float | None = None, fetch_k: int | None = None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
-        is strictly one query per call); expr, min_score / max_score, group_by / group_size: one
-        filter, one score band and one grouping for the whole batch."""
+        is strictly one query per call); expr, min_score / max_score, group_by / group_size,
+        mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
+        the whole batch."""
         if not queries:
             return []
         q = self._embed(list(queries))
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
-                                         **self._group_args(group_by, group_size))
+                                         **self._group_args(group_by, group_size),
+                                         **self._mmr_args(mmr_lambda, fetch_k))
         return [self._contexts(r) for r in results]
 
     # -- generation (out of scope; interface kept) -----------------------------------------

@@ -272,7 +272,11 @@ class ShardedCorpusStore(CorpusStore):
 
     # -- filters: not over shards (yet) -----------------------------------------------------------------
     def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
-               output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False):
+               output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False,
+               mmr_lambda=None, mmr_fetch_k=None):
+        if mmr_lambda is not None or mmr_fetch_k is not None:
+            # (the candidate vectors live on different ranks)
+            raise NotImplementedError("diversified search (mmr_lambda) is not implemented for the sharded store")
         if group_by_field is not None:
             raise NotImplementedError("grouping search (group_by_field) is not implemented for the sharded store")
         if not filter_expr.is_empty(expr):

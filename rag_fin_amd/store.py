@@ -67,6 +67,38 @@ def check_band(radius, range_filter=None):
     return out[0], out[1]
 
 
+MMR_MAX_FETCH_K = _lib.RF_MAX_K
+
+
+def check_mmr(mmr_lambda, mmr_fetch_k, limit: int):
+    """Diversified-search arguments -> (fetch_k, lambda), or None when neither is given.  lambda
+    weighs relevance against redundancy (1 = the plain ranking, 0 = diversity only after the best
+    hit); fetch_k is the number of best hits the `limit` results are picked from, by default
+    min(64, max(20, 4 * limit)).  mmr_fetch_k without mmr_lambda, a lambda that is no real number in
+    [0, 1] (NaN, a string, a bool), a fetch_k that is no integer, limit > fetch_k or fetch_k > 64
+    raises ValueError."""
+    import math
+    import numbers
+    if mmr_lambda is None:
+        if mmr_fetch_k is not None:
+            raise ValueError("diversified search: mmr_fetch_k needs mmr_lambda (mmr_lambda switches MMR on)")
+        return None
+    if isinstance(mmr_lambda, bool) or not isinstance(mmr_lambda, numbers.Real) or math.isnan(float(mmr_lambda)) \
+            or not 0.0 <= float(mmr_lambda) <= 1.0:
+        raise ValueError(f"diversified search: mmr_lambda must be a real number in [0, 1], got {mmr_lambda!r}")
+    if limit < 1:
+        raise ValueError("limit must be >= 1")
+    if mmr_fetch_k is None:
+        mmr_fetch_k = min(MMR_MAX_FETCH_K, max(20, 4 * limit))
+    if isinstance(mmr_fetch_k, bool) or not isinstance(mmr_fetch_k, numbers.Integral):
+        raise ValueError(f"diversified search: mmr_fetch_k must be an integer, got {mmr_fetch_k!r}")
+    if mmr_fetch_k > MMR_MAX_FETCH_K:
+        raise ValueError(f"diversified search: mmr_fetch_k = {mmr_fetch_k} > {MMR_MAX_FETCH_K}")
+    if limit > mmr_fetch_k:
+        raise ValueError(f"diversified search: limit = {limit} > mmr_fetch_k = {mmr_fetch_k}")
+    return int(mmr_fetch_k), float(mmr_lambda)
+
+
 class _DeviceColumns:
     """The device mirror of the four filterable scalar columns: period / chunk_type /
     statement_type as int32 codes into append-only dictionaries, primary_value as fp64.
@@ -499,17 +531,21 @@ class CorpusStore:
             q = q[None, :]
         return self.index.to_fp16(q, normalize=self.metric_type == "COSINE")
 
-    def search_rows(self, data, limit: int, filt=None, band=None):
+    def search_rows(self, data, limit: int, filt=None, band=None, mmr=None):
         """(scores f32 [B,k'], rows i64 [B,k']) as host numpy, k' = min(limit, N).  filt: a
         filter buffer (build_filter): the top-k of the passing rows, padded with -1 rows.
         band: (radius, range_filter) -- range search: the top-k of the rows with
-        radius < fp64 score <= range_filter, padded with -1 rows."""
+        radius < fp64 score <= range_filter, padded with -1 rows.
+        mmr: (fetch_k, lambda) -- diversified search: `limit` of the best fetch_k such hits by
+        maximal marginal relevance, in MMR order (check_mmr)."""
         if limit < 1:
             raise ValueError("limit must be >= 1")
         if band is not None:
             band = check_band(*band)
+        if mmr is not None:
+            mmr = check_mmr(mmr[1], mmr[0], limit)
         with self._rw.read():
-            return self._search_rows(data, limit, filt, band)
+            return self._search_rows(data, limit, filt, band, mmr=mmr)
 
     GROUP_BY_FIELDS = filter_expr.VARCHAR_FIELDS   # period, chunk_type, statement_type ("id": the plain search)
 
@@ -521,7 +557,7 @@ class CorpusStore:
             self._dcols.sync(self.columns, self.num_entities)
             return self._dcols.codes[field].contiguous(), len(self._dcols.dicts[field])
 
-    def _search_rows(self, data, limit: int, filt=None, band=None, group=None):
+    def _search_rows(self, data, limit: int, filt=None, band=None, group=None, mmr=None):
         q16 = self._prepare_queries(data)
         kw = {} if filt is None else {"filt": filt}   # the index is given a keyword only when it is set
         if group is not None:
@@ -531,6 +567,8 @@ class CorpusStore:
             return self.index.search_host(q16, limit * gsize, group=(codes, n_codes, limit, gsize), **kw)
         if band is not None:
             kw["band"] = band
+        if mmr is not None:
+            kw["mmr"] = mmr   # (limit <= fetch_k <= RF_MAX_K: never paged)
         if limit > _lib.RF_MAX_K:
             scores, rows = self.index.search_large(q16, limit, **kw)   # paged, exhaustive beyond 64
             kk = min(limit, self.num_entities)
@@ -543,7 +581,8 @@ class CorpusStore:
 
     def search(self, data, anns_field: str = "embedding", param: dict | None = None,
                limit: int = 3, expr=None, output_fields: Iterable[str] | None = None,
-               group_by_field: str | None = None, group_size: int = 1, strict_group_size: bool = False):
+               group_by_field: str | None = None, group_size: int = 1, strict_group_size: bool = False,
+               mmr_lambda=None, mmr_fetch_k=None):
         """pymilvus-shaped search: one list of hits per query vector, best first.
         group_by_field ("period", "chunk_type", "statement_type"; "id" is the plain search): the best
         `limit` GROUPS of rows sharing that field's value, each by its best min(group_size, rows of
@@ -557,10 +596,20 @@ class CorpusStore:
         the best `limit` hits with radius < score <= range_filter (a query may return []); the
         comparison is made in fp64 on the fp64 ranking score, so a hit's fp32 `score` may equal
         float32(radius).  range_filter without radius, a bound that is no real number, NaN or
-        radius >= range_filter raises ValueError.  Other keys of params (nprobe, ...) are ignored."""
+        radius >= range_filter raises ValueError.  Other keys of params (nprobe, ...) are ignored.
+        mmr_lambda (a real number in [0, 1]): diversified search -- the `limit` hits are picked from
+        the best mmr_fetch_k (default min(64, max(20, 4 * limit)), at most 64) by maximal marginal
+        relevance on the GPU: each pick maximises lambda * score - (1 - lambda) * (largest similarity
+        to a hit already picked).  The hits come in MMR order, the first is always the best hit and
+        hit.score stays the relevance score; 1 gives the plain ranking.  With expr, range search and
+        an SQ8 index; not with group_by_field (ValueError, as are mmr_fetch_k without mmr_lambda,
+        limit > mmr_fetch_k and mmr_fetch_k > 64)."""
+        mmr = check_mmr(mmr_lambda, mmr_fetch_k, limit)
+        if mmr is not None and group_by_field is not None:
+            raise ValueError("diversified search (mmr_lambda) cannot be combined with group_by_field")
         with self._rw.read():   # the rows handed back are marshalled below: no delete in between
             if group_by_field is None:
-                return self._search(data, anns_field, param, limit, expr, output_fields)
+                return self._search(data, anns_field, param, limit, expr, output_fields, mmr=mmr)
             return self._search(data, anns_field, param, limit, expr, output_fields,
                                 self._check_group_by(group_by_field, group_size, limit, param))
 
@@ -581,7 +630,7 @@ class CorpusStore:
                              "(grouped results are not paged)")
         return field, int(group_size)
 
-    def _search(self, data, anns_field, param, limit, expr, output_fields, group=None):
+    def _search(self, data, anns_field, param, limit, expr, output_fields, group=None, mmr=None):
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         metric = (param or {}).get("metric_type", self.metric_type).upper()
@@ -593,6 +642,8 @@ class CorpusStore:
                 raise KeyError(f"unknown output field {f!r}")
         band = self._band_of(param)
         kw = {} if band is None else {"band": band}
+        if mmr is not None:
+            kw["mmr"] = mmr
         if group is not None:
             # the padded [B, limit * group_size] block; short and missing groups leave -1 slots
             filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
