@@ -522,6 +522,32 @@ int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* le
               int B, int T, void* out_f16_dev, float* out_f32_dev,
               void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Cross-encoder reranking: one relevance logit per (query, chunk) pair from a
+ * BertForSequenceClassification checkpoint of the same family (cross-encoder/ms-marco-MiniLM-L-6-v2,
+ * -L-12-v2): the encoder handle holds the BertModel weights, `head` the pooler and the classifier
+ * (device fp16, row-major as nn.Linear stores them; the caller keeps them alive for the call).
+ * Same conventions as rf_encode: stream-ordered, caller-owned buffers, workspace of
+ * rf_encode_workspace_bytes(enc, B, T) bytes.
+ * ids_dev int32 [B, T]: [CLS] query [SEP] chunk [SEP], padded; lens_dev int32 [B]; seg_dev int32 [B]: the
+ * index of the first token of the second segment (token_type_ids = 1 from there on; seg >= len: the row
+ * has no second segment).  logits_dev fp32 [B]:
+ *   logit = cls_w . tanh(pool_w x + pool_b) + cls_b,  x = the last hidden state of the row's [CLS] token,
+ * accumulated in fp32 in a fixed order (csrc/rerank.hip), so a pair's logit has the same bits wherever the
+ * pair sits in a batch; a row with lens < 1 has no [CLS] token and gets -inf.  No activation is applied.
+ * The layers are rf_encode's (all its paths by B and T); these calls are always plain launches and never
+ * touch rf_encode's cached hipGraphs.
+ * RF_ERR_UNSUPPORTED: num_labels != 1, an encoder with type_vocab < 2, T > max_position. */
+typedef struct rf_pair_head {
+  const void* pool_w;   /* [H, H]  bert.pooler.dense.weight (16-byte aligned) */
+  const void* pool_b;   /* [H] */
+  const void* cls_w;    /* [1, H]  classifier.weight */
+  const void* cls_b;    /* [1] */
+  int32_t num_labels;
+} rf_pair_head;
+int rf_score_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev,
+                   const int32_t* seg_dev, int B, int T, const rf_pair_head* head, float* logits_dev,
+                   void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- tokenizer: the text -> token-id stage in front of rf_encode ------------------------
  * Reference: the WordPiece tokenizer SentenceTransformer('all-MiniLM-L6-v2') loads by name
  * (vector_rag_mcp/main.py:41,50; "chunking_storing (1).py":8,380).  Host code, multi-threaded.

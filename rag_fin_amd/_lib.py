@@ -55,6 +55,12 @@ class EncoderWeights(Structure):
     _fields_ = [(n, c_void_p) for n in ENCODER_WEIGHT_FIELDS]
 
 
+class PairHead(Structure):
+    """rf_pair_head: the pooler and classifier of a cross-encoder (device fp16 pointers)."""
+    _fields_ = [("pool_w", c_void_p), ("pool_b", c_void_p), ("cls_w", c_void_p), ("cls_b", c_void_p),
+                ("num_labels", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/ragfin.h declares
 SIGNATURES = {
     "rf_version": (c_int, []),
@@ -141,6 +147,8 @@ SIGNATURES = {
     "rf_encode_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rf_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                           c_size_t, c_void_p]),
+    "rf_score_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(PairHead), c_void_p,
+                               c_void_p, c_size_t, c_void_p]),
 }
 
 # present only in the experiments build (libragfin_hip_exp.so, tools/): bound when exported

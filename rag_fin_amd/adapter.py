@@ -3,7 +3,7 @@
 Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
   GET /            service card                         (:121-132)
   GET /health      {"status": "healthy", "mcp": ...} | {"status": "unhealthy", "mcp": "unavailable"}
-  POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional)}
+  POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional), rerank: bool (optional)}
                                                                -> tool search_vectors
   POST /answer     {question: str >= 5 chars, top_k: 1..10 = 3} -> tool answer_question
   GET /stats       -> tool get_collection_stats
@@ -44,16 +44,20 @@ class SearchRequest(BaseModel):
     # diversified search (maximal marginal relevance over the best fetch_k chunks); new
     mmr_lambda: Optional[float] = Field(default=None, ge=0.0, le=1.0)
     fetch_k: Optional[int] = Field(default=None, ge=1, le=64)
+    # two-stage search (the best fetch_k chunks re-scored by the cross-encoder); new
+    rerank: bool = False
 
 
 def search_args(req: SearchRequest) -> dict:
     """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by`, `group_size`,
-    `mmr_lambda` and `fetch_k` only when they were given, so the reference's payload
-    {"query", "top_k"} is unchanged."""
+    `mmr_lambda` and `fetch_k` only when they were given and `rerank` only when it is set, so the
+    reference's payload {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
     for name in ("filter", "min_score", "max_score", "group_by", "group_size", "mmr_lambda", "fetch_k"):
         if getattr(req, name) is not None:
             args[name] = getattr(req, name)
+    if req.rerank:
+        args["rerank"] = True
     return args
 
 

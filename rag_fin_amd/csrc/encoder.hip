@@ -28,6 +28,7 @@
 //                   kept for longer sequences
 //   k_qkv_attn_one  a single sequence of <= 32 tokens: K2 + K3 of a head in one launch
 //   k_pool_norm     mean over the sequence, L2-normalise                      (K7)
+// A cross-encoder forward (rf_score_pairs) runs the same layers between the two kernels of rerank.hip.
 #include "encoder_internal.h"
 #include <mutex>
 #include <new>
@@ -221,88 +222,14 @@ __global__ void __launch_bounds__(256) k_tok_offsets(const int32_t* __restrict__
   }
 }
 
-// One workgroup per 32 consecutive positions of one sequence, lane = (position c, feature half h); its four
-// waves take six of the 24 16-feature groups each.  The wave's stores are runs of whole 16-byte slots of the
-// tiled activations (a token's slot of fragment f is next to its neighbour's: 512 contiguous bytes per half,
-// split at most once by a token-block boundary) instead of 48 slots 1 KiB apart per token; every load of a
-// wave (18 x 16 bytes per lane) is in flight at once and its 48 sums stay in registers; the LayerNorm sums are
-// lane-local plus one xor-32 exchange and one trip through LDS between the four waves.  The per-sequence
-// scalars (length, packed offset) are wave-uniform scalar loads.  (Round-2 history: one wave per token, four
-// tokens per wave in a row, each a chain of three dependent vector loads: 49 us per 64 k-token batch; one wave
-// per 32 positions with two sweeps over the rows: 56 us -- 8 waves per CU cannot hide the latency.)
+// K1: the body is embed_ln_rows() of encoder_internal.h (shared with the pair form in rerank.hip); every position
+// takes type row 0 here.
 __global__ void __launch_bounds__(256) k_embed_ln(
     const int32_t* __restrict__ ids, const int32_t* __restrict__ lens,
     int32_t* __restrict__ tok_off, int B, int T, int vocab, const _Float16* __restrict__ word,
     const _Float16* __restrict__ pos, const _Float16* __restrict__ type, const _Float16* __restrict__ g,
     const _Float16* __restrict__ b, float eps, _Float16* __restrict__ out) {
-  __shared__ float red[2][4][32];
-  constexpr int FW = HID / 16 / 4;                             // feature groups per wave (6)
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int c = lane & 31, h = lane >> 5;
-  const int cpr = (T + 31) >> 5;                               // 32-position chunks per sequence row
-  const int bi = blockIdx.x / cpr, p0 = (blockIdx.x % cpr) * 32;
-  const int len = min(max(lens[bi], 0), T);
-  // ONE sequence (a query): the packed offsets are {0, len} -- written here, so that the launch of k_tok_offsets
-  // (a dependent kernel boundary, ~4.5 us of the query's latency) is not needed
-  if (B == 1 && blockIdx.x == 0 && threadIdx.x == 0) {
-    tok_off[0] = 0;
-    tok_off[1] = len;
-  }
-  if (p0 >= len) return;                                       // workgroup-uniform
-  const int p = p0 + c;
-  const bool live = p < len;
-  int id = live ? ids[(size_t)bi * T + p] : 0;
-  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-  const int f0 = 16 * FW * wave + 8 * h;                       // the lane's first feature
-  const _Float16* wrow = word + (size_t)id * HID + f0;
-  const _Float16* prow = pos + (size_t)(live ? p : 0) * HID + f0;
-  const _Float16* trow = type + f0;
-  half8 a[FW], cc[FW], d[FW];
-#pragma unroll
-  for (int f = 0; f < FW; ++f) {
-    a[f] = *(const half8*)(wrow + 16 * f);
-    cc[f] = *(const half8*)(prow + 16 * f);
-    d[f] = *(const half8*)(trow + 16 * f);
-  }
-  float v[FW][8];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int f = 0; f < FW; ++f)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      v[f][j] = (float)a[f][j] + (float)cc[f][j] + (float)d[f][j];
-      s1 += v[f][j];
-      s2 = fmaf(v[f][j], v[f][j], s2);
-    }
-  s1 += __shfl_xor(s1, 32);
-  s2 += __shfl_xor(s2, 32);
-  if (h == 0) {
-    red[0][wave][c] = s1;
-    red[1][wave][c] = s2;
-  }
-  // the scale and shift are not needed before the statistics: their round trip sits under the exchange
-  half8 gg[FW], bb[FW];
-#pragma unroll
-  for (int f = 0; f < FW; ++f) {
-    gg[f] = *(const half8*)(g + f0 + 16 * f);
-    bb[f] = *(const half8*)(b + f0 + 16 * f);
-  }
-  __syncthreads();
-  const float t1 = (red[0][0][c] + red[0][1][c]) + (red[0][2][c] + red[0][3][c]);
-  const float t2 = (red[1][0][c] + red[1][1][c]) + (red[1][2][c] + red[1][3][c]);
-  const float mu = t1 * (1.f / HID);
-  // E[v^2] - mu^2 in fp32 over 384 values of order 1 with |mu| << 1: the cancellation is ~1e-6 relative
-  const float rstd = rsqrtf(fmaxf(t2 * (1.f / HID) - mu * mu, 0.f) + eps);
-  const int token = (B == 1 ? 0 : tok_off[bi]) + p;
-  _Float16* orow = out + ((size_t)(token >> 5) * (HID / 16) * 64 + (size_t)h * 32 + (token & 31)) * 8 + (size_t)(FW * wave) * 512;
-#pragma unroll
-  for (int f = 0; f < FW; ++f) {
-    half8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (_Float16)((v[f][j] - mu) * rstd * (float)gg[f][j] + (float)bb[f][j]);
-    if (live) *(half8*)(orow + (size_t)f * 512) = o;
-  }
+  embed_ln_rows<false>(ids, lens, nullptr, tok_off, B, T, vocab, word, pos, type, g, b, eps, out);
 }
 
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RES_LN = 2 };
@@ -1548,7 +1475,8 @@ static void launch_linear(const _Float16* X, const uint4* Wt, const _Float16* bi
 }
 
 static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
-                          void* out_f16_dev, float* out_f32_dev, void* workspace_dev, hipStream_t st);
+                          void* out_f16_dev, float* out_f32_dev, void* workspace_dev, hipStream_t st,
+                          const rf_pair_ends* ends = nullptr);
 
 // First call with a (shape, buffers) key: plain launches.  Second: the same launch sequence is
 // captured on a private stream, instantiated and replayed on the caller's stream; later calls
@@ -1632,6 +1560,23 @@ static int encode_graphed(const rf_encoder_t* enc, const int32_t* ids, const int
   return RF_OK;
 }
 
+// the shape and workspace checks of a forward (the callers have checked their pointers)
+static int encode_check(const char* who, const rf_encoder_t* enc, int B, int T, void* workspace_dev, size_t workspace_bytes) {
+  if (B <= 0 || T <= 0 || T > enc->cfg.max_position) {
+    rf_set_error("%s: B=%d T=%d out of range (max_position %d)", who, B, T, enc->cfg.max_position);
+    return RF_ERR_INVALID;
+  }
+  if ((size_t)T * 2 * HEAD_DIM * 2 > 160 * 1024) {
+    rf_set_error("%s: T=%d does not fit the attention kernel's LDS", who, T);
+    return RF_ERR_UNSUPPORTED;
+  }
+  if (workspace_bytes < rf_encode_workspace_bytes(enc, B, T) || ((uintptr_t)workspace_dev & 15)) {
+    rf_set_error("%s: workspace too small or misaligned", who);
+    return RF_ERR_CAPACITY;
+  }
+  return RF_OK;
+}
+
 extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev,
                          int B, int T, void* out_f16_dev, float* out_f32_dev, void* workspace_dev,
                          size_t workspace_bytes, void* stream) {
@@ -1639,18 +1584,8 @@ extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const 
     rf_set_error("rf_encode: null argument");
     return RF_ERR_INVALID;
   }
-  if (B <= 0 || T <= 0 || T > enc->cfg.max_position) {
-    rf_set_error("rf_encode: B=%d T=%d out of range (max_position %d)", B, T, enc->cfg.max_position);
-    return RF_ERR_INVALID;
-  }
-  if ((size_t)T * 2 * HEAD_DIM * 2 > 160 * 1024) {
-    rf_set_error("rf_encode: T=%d does not fit the attention kernel's LDS", T);
-    return RF_ERR_UNSUPPORTED;
-  }
-  if (workspace_bytes < rf_encode_workspace_bytes(enc, B, T) || ((uintptr_t)workspace_dev & 15)) {
-    rf_set_error("rf_encode: workspace too small or misaligned");
-    return RF_ERR_CAPACITY;
-  }
+  const int crc = encode_check("rf_encode", enc, B, T, workspace_dev, workspace_bytes);
+  if (crc != RF_OK) return crc;
   hipStream_t st = (hipStream_t)stream;
   if ((size_t)B * T <= SM_MAX_TOK && rf_knob_encode_graph) {
     const int rc = encode_graphed(enc, ids_dev, lens_dev, B, T, out_f16_dev, out_f32_dev, workspace_dev, st);
@@ -1659,8 +1594,26 @@ extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const 
   return encode_enqueue(enc, ids_dev, lens_dev, B, T, out_f16_dev, out_f32_dev, workspace_dev, st);
 }
 
+// rf_score_pairs (rerank.hip) behind its pointer checks.  Always the plain launches: the cached hipGraphs are
+// rf_encode's alone, so a pair forward can never replay an embedding graph, nor the other way round.
+int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
+                    const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st) {
+  if (enc->cfg.type_vocab < 2) {
+    rf_set_error("rf_score_pairs: the encoder has %d token-type row(s); a pair needs 2", enc->cfg.type_vocab);
+    return RF_ERR_UNSUPPORTED;
+  }
+  if (T > enc->cfg.max_position) {
+    rf_set_error("rf_score_pairs: T=%d exceeds max_position %d", T, enc->cfg.max_position);
+    return RF_ERR_UNSUPPORTED;
+  }
+  const int crc = encode_check("rf_score_pairs", enc, B, T, workspace_dev, workspace_bytes);
+  if (crc != RF_OK) return crc;
+  return encode_enqueue(enc, ids_dev, lens_dev, B, T, nullptr, nullptr, workspace_dev, st, &ends);
+}
+
 static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
-                          void* out_f16_dev, float* out_f32_dev, void* workspace_dev, hipStream_t st) {
+                          void* out_f16_dev, float* out_f32_dev, void* workspace_dev, hipStream_t st,
+                          const rf_pair_ends* ends) {
   const rf_encoder_config& c = enc->cfg;
   const rf_encoder_weights& w = enc->w;
   const int I = c.intermediate, L = c.layers;
@@ -1669,8 +1622,10 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
   const int tiles = B * T;   // token slots; launch_linear turns them into tiles
   const int32_t* m_ptr = ws.tok_off + B;
 
-  if (B > 1) hipLaunchKernelGGL(k_tok_offsets, dim3(1), dim3(256), 0, st, lens_dev, B, T, ws.tok_off);   // B == 1: k_embed_ln writes them
-  {
+  if (B > 1) hipLaunchKernelGGL(k_tok_offsets, dim3(1), dim3(256), 0, st, lens_dev, B, T, ws.tok_off);   // B == 1: the embedding launch writes them
+  if (ends) {
+    rf_launch_embed_pair(ids_dev, lens_dev, ends->seg, ws.tok_off, B, T, c, w, ws.x, st);
+  } else {
     const int chunks = B * ((T + 31) / 32);   // one workgroup per 32 positions of a row
     hipLaunchKernelGGL(k_embed_ln, dim3(chunks), dim3(256), 0, st, ids_dev, lens_dev, ws.tok_off, B, T,
                        c.vocab_size, (const _Float16*)w.word_emb, (const _Float16*)w.pos_emb,
@@ -1736,8 +1691,10 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
                                                  tiles, m_ptr, y, (const _Float16*)w.ln2_g + (size_t)l * HID,
                                                  (const _Float16*)w.ln2_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
   }
-  hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(256), 0, st, x, ws.tok_off, (_Float16*)out_f16_dev,
-                     out_f32_dev);
+  if (ends)
+    rf_launch_cls_head(x, ws.tok_off, B, *ends->head, ends->logits, st);
+  else
+    hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(256), 0, st, x, ws.tok_off, (_Float16*)out_f16_dev, out_f32_dev);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }

@@ -22,6 +22,96 @@ __device__ __forceinline__ size_t toff(int t, int f, int KSf) {
   return (((size_t)(t >> 5) * KSf + (f >> 4)) * 64 + (size_t)(((f >> 3) & 1) * 32 + (t & 31))) * 8 + (f & 7);
 }
 
+// ---- the embedding launch that opens a forward (k_embed_ln in encoder.hip, k_embed_pair_ln in rerank.hip) ----
+// One workgroup per 32 consecutive positions of one sequence, lane = (position c, feature half h); its four
+// waves take six of the 24 16-feature groups each.  The wave's stores are runs of whole 16-byte slots of the
+// tiled activations (a token's slot of fragment f is next to its neighbour's: 512 contiguous bytes per half,
+// split at most once by a token-block boundary) instead of 48 slots 1 KiB apart per token; every load of a
+// wave (18 x 16 bytes per lane) is in flight at once and its 48 sums stay in registers; the LayerNorm sums are
+// lane-local plus one xor-32 exchange and one trip through LDS between the four waves.  The per-sequence
+// scalars (length, packed offset) are wave-uniform scalar loads.  (Round-2 history: one wave per token, four
+// tokens per wave in a row, each a chain of three dependent vector loads: 49 us per 64 k-token batch; one wave
+// per 32 positions with two sweeps over the rows: 56 us -- 8 waves per CU cannot hide the latency.)
+template <bool PAIR>   // PAIR: seg[b] = index of the first segment-1 position of sequence b (>= its length: none)
+__device__ __forceinline__ void embed_ln_rows(
+    const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, const int32_t* __restrict__ seg,
+    int32_t* __restrict__ tok_off, int B, int T, int vocab, const _Float16* __restrict__ word,
+    const _Float16* __restrict__ pos, const _Float16* __restrict__ type, const _Float16* __restrict__ g,
+    const _Float16* __restrict__ b, float eps, _Float16* __restrict__ out) {
+  __shared__ float red[2][4][32];
+  constexpr int FW = HID / 16 / 4;                             // feature groups per wave (6)
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int c = lane & 31, h = lane >> 5;
+  const int cpr = (T + 31) >> 5;                               // 32-position chunks per sequence row
+  const int bi = blockIdx.x / cpr, p0 = (blockIdx.x % cpr) * 32;
+  const int len = min(max(lens[bi], 0), T);
+  // ONE sequence (a query): the packed offsets are {0, len} -- written here, so that the launch of k_tok_offsets
+  // (a dependent kernel boundary, ~4.5 us of the query's latency) is not needed
+  if (B == 1 && blockIdx.x == 0 && threadIdx.x == 0) {
+    tok_off[0] = 0;
+    tok_off[1] = len;
+  }
+  if (p0 >= len) return;                                       // workgroup-uniform
+  const int p = p0 + c;
+  const bool live = p < len;
+  int id = live ? ids[(size_t)bi * T + p] : 0;
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  const int f0 = 16 * FW * wave + 8 * h;                       // the lane's first feature
+  const _Float16* wrow = word + (size_t)id * HID + f0;
+  const _Float16* prow = pos + (size_t)(live ? p : 0) * HID + f0;
+  // PAIR: positions from seg[bi] on belong to the second segment and take type row 1 (a per-lane choice
+  // between two rows; the arithmetic below is the same)
+  const _Float16* trow = type + f0;
+  if constexpr (PAIR) trow += (p >= seg[bi]) ? HID : 0;
+  half8 a[FW], cc[FW], d[FW];
+#pragma unroll
+  for (int f = 0; f < FW; ++f) {
+    a[f] = *(const half8*)(wrow + 16 * f);
+    cc[f] = *(const half8*)(prow + 16 * f);
+    d[f] = *(const half8*)(trow + 16 * f);
+  }
+  float v[FW][8];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int f = 0; f < FW; ++f)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      v[f][j] = (float)a[f][j] + (float)cc[f][j] + (float)d[f][j];
+      s1 += v[f][j];
+      s2 = fmaf(v[f][j], v[f][j], s2);
+    }
+  s1 += __shfl_xor(s1, 32);
+  s2 += __shfl_xor(s2, 32);
+  if (h == 0) {
+    red[0][wave][c] = s1;
+    red[1][wave][c] = s2;
+  }
+  // the scale and shift are not needed before the statistics: their round trip sits under the exchange
+  half8 gg[FW], bb[FW];
+#pragma unroll
+  for (int f = 0; f < FW; ++f) {
+    gg[f] = *(const half8*)(g + f0 + 16 * f);
+    bb[f] = *(const half8*)(b + f0 + 16 * f);
+  }
+  __syncthreads();
+  const float t1 = (red[0][0][c] + red[0][1][c]) + (red[0][2][c] + red[0][3][c]);
+  const float t2 = (red[1][0][c] + red[1][1][c]) + (red[1][2][c] + red[1][3][c]);
+  const float mu = t1 * (1.f / HID);
+  // E[v^2] - mu^2 in fp32 over 384 values of order 1 with |mu| << 1: the cancellation is ~1e-6 relative
+  const float rstd = rsqrtf(fmaxf(t2 * (1.f / HID) - mu * mu, 0.f) + eps);
+  const int token = (B == 1 ? 0 : tok_off[bi]) + p;
+  _Float16* orow = out + ((size_t)(token >> 5) * (HID / 16) * 64 + (size_t)h * 32 + (token & 31)) * 8 + (size_t)(FW * wave) * 512;
+#pragma unroll
+  for (int f = 0; f < FW; ++f) {
+    half8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = (_Float16)((v[f][j] - mu) * rstd * (float)gg[f][j] + (float)bb[f][j]);
+    if (live) *(half8*)(orow + (size_t)f * 512) = o;
+  }
+}
+
+
 // (the attribute means something in the device pass only; the host pass of the same source would warn)
 #ifdef __HIP_DEVICE_COMPILE__
 #define RF_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
@@ -57,3 +147,20 @@ struct rf_post_args {
   int abl;                  // ablation bits (experiments build; results wrong): see k_post_block
 };
 int rf_launch_post_block(const rf_post_args& a, int token_slots, hipStream_t st);
+
+// ---- rerank.hip: a cross-encoder forward = the same layers between two other launches -----------------
+// encode_enqueue's option: which embedding launch opens the forward and which launch closes it.  nullptr is
+// the sentence embedder (k_embed_ln ... k_pool_norm); with it the forward opens with k_embed_pair_ln (segment
+// ids) and closes with k_cls_head (pooler + classifier on the [CLS] row) instead.  The layer loop is the same.
+struct rf_pair_ends {
+  const int32_t* seg;         // [B] first segment-1 position per sequence
+  const rf_pair_head* head;   // device pointers of the classification head
+  float* logits;              // [B]
+};
+void rf_launch_embed_pair(const int32_t* ids, const int32_t* lens, const int32_t* seg, int32_t* tok_off, int B, int T,
+                          const rf_encoder_config& c, const rf_encoder_weights& w, _Float16* out, hipStream_t st);
+void rf_launch_cls_head(const _Float16* x, const int32_t* tok_off, int B, const rf_pair_head& head, float* logits,
+                        hipStream_t st);
+// encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph)
+int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
+                    const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st);

@@ -67,6 +67,43 @@ def stack_hf_state_dict(sd: dict, cfg: dict) -> dict:
     }
 
 
+def stack_hf_pair_head(sd: dict) -> dict:
+    """The classification head of a Hugging Face BertForSequenceClassification state dict -> the tensors of
+    rf_pair_head: the pooler (dense + tanh on the [CLS] row) and the classifier on top of it."""
+    def get(name):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name} (not a BertForSequenceClassification?)")
+        return np.asarray(sd[name], dtype=np.float32)
+    return {"pool_w": get("bert.pooler.dense.weight"), "pool_b": get("bert.pooler.dense.bias"),
+            "cls_w": get("classifier.weight"), "cls_b": get("classifier.bias")}
+
+
+def hf_encoder_config(hc: dict) -> dict:
+    """config.json of a BERT checkpoint -> the fields of rf_encoder_config."""
+    if hc.get("hidden_act", "gelu") != "gelu":
+        raise _lib.RagfinError(-2, f"activation {hc.get('hidden_act')} is not supported (gelu only)")
+    return dict(vocab_size=hc["vocab_size"], hidden=hc["hidden_size"], layers=hc["num_hidden_layers"],
+                heads=hc["num_attention_heads"], intermediate=hc["intermediate_size"],
+                max_position=hc["max_position_embeddings"], type_vocab=hc.get("type_vocab_size", 2),
+                ln_eps=hc.get("layer_norm_eps", 1e-12))
+
+
+def random_weights(cfg: dict, seed: int = 0, scale: float = 0.05) -> dict:
+    """Seeded random weights of the named architecture (no checkpoint exists offline): same generator as the
+    test oracle so both sides can be rebuilt from the seed alone."""
+    rng = np.random.default_rng(seed)
+    H, L, I = cfg["hidden"], cfg["layers"], cfg["intermediate"]
+
+    def mat(*shape, s=scale):
+        return (rng.standard_normal(shape, dtype=np.float32) * s).astype(np.float32)
+    return {"word_emb": mat(cfg["vocab_size"], H), "pos_emb": mat(cfg["max_position"], H),
+            "type_emb": mat(cfg["type_vocab"], H), "emb_ln_g": 1 + mat(H, s=0.1), "emb_ln_b": mat(H, s=0.1),
+            "qkv_w": mat(L, 3 * H, H), "qkv_b": mat(L, 3 * H, s=0.02), "ao_w": mat(L, H, H),
+            "ao_b": mat(L, H, s=0.02), "ln1_g": 1 + mat(L, H, s=0.1), "ln1_b": mat(L, H, s=0.1),
+            "ff1_w": mat(L, I, H), "ff1_b": mat(L, I, s=0.02), "ff2_w": mat(L, H, I),
+            "ff2_b": mat(L, H, s=0.02), "ln2_g": 1 + mat(L, H, s=0.1), "ln2_b": mat(L, H, s=0.1)}
+
+
 class Embedder:
     """`encode(list[str]) -> np.float32 [n, 384]`, unit-norm rows."""
 
@@ -129,12 +166,7 @@ class Embedder:
         from safetensors.numpy import load_file
         with open(os.path.join(path, "config.json")) as f:
             hc = json.load(f)
-        cfg = dict(vocab_size=hc["vocab_size"], hidden=hc["hidden_size"], layers=hc["num_hidden_layers"],
-                   heads=hc["num_attention_heads"], intermediate=hc["intermediate_size"],
-                   max_position=hc["max_position_embeddings"], type_vocab=hc.get("type_vocab_size", 2),
-                   ln_eps=hc.get("layer_norm_eps", 1e-12))
-        if hc.get("hidden_act", "gelu") != "gelu":
-            raise _lib.RagfinError(-2, f"activation {hc.get('hidden_act')} is not supported (gelu only)")
+        cfg = hf_encoder_config(hc)
         sd = load_file(os.path.join(path, "model.safetensors"))
         tok = WordPieceTokenizer.from_vocab_file(os.path.join(path, "vocab.txt"))
         msl = max_seq_length
@@ -151,17 +183,7 @@ class Embedder:
         offline): same generator as the test oracle so both sides can be rebuilt
         from the seed alone."""
         cfg = dict(cfg or MINILM_L6)
-        rng = np.random.default_rng(seed)
-        H, L, I = cfg["hidden"], cfg["layers"], cfg["intermediate"]
-
-        def mat(*shape, s=scale):
-            return (rng.standard_normal(shape, dtype=np.float32) * s).astype(np.float32)
-        w = {"word_emb": mat(cfg["vocab_size"], H), "pos_emb": mat(cfg["max_position"], H),
-             "type_emb": mat(cfg["type_vocab"], H), "emb_ln_g": 1 + mat(H, s=0.1), "emb_ln_b": mat(H, s=0.1),
-             "qkv_w": mat(L, 3 * H, H), "qkv_b": mat(L, 3 * H, s=0.02), "ao_w": mat(L, H, H),
-             "ao_b": mat(L, H, s=0.02), "ln1_g": 1 + mat(L, H, s=0.1), "ln1_b": mat(L, H, s=0.1),
-             "ff1_w": mat(L, I, H), "ff1_b": mat(L, I, s=0.02), "ff2_w": mat(L, H, I),
-             "ff2_b": mat(L, H, s=0.02), "ln2_g": 1 + mat(L, H, s=0.1), "ln2_b": mat(L, H, s=0.1)}
+        w = random_weights(cfg, seed, scale)
         return cls(w, cfg, tokenizer, device)
 
     # -- forward ------------------------------------------------------------------------

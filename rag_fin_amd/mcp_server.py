@@ -57,7 +57,7 @@ def _searcher():
 
 def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
-                   mmr_lambda: float | None = None, fetch_k: int | None = None):
+                   mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -65,10 +65,14 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     each by its best group_size chunks, as one flat ranked list.
     mmr_lambda: optional diversification, 0..1 (maximal marginal relevance: 1 = relevance only, lower
     values trade relevance for chunks unlike those already returned); fetch_k: how many best chunks
-    the top_k are picked from (at most 64)."""
+    the top_k are picked from (at most 64).
+    rerank: optional second stage -- the best fetch_k chunks are re-scored as (query, text) pairs by the
+    cross-encoder and the best top_k of them returned, each with a rerank_score."""
     try:
-        # (only what was given travels on; diversified calls bypass the micro-batcher as well)
+        # (only what was given travels on; diversified and reranked calls bypass the micro-batcher as well)
         mmr = {name: v for name, v in (("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k)) if v is not None}
+        if rerank:
+            mmr["rerank"] = True
         if group_by is not None:
             # grouped calls bypass the micro-batcher like filtered ones: one batch shares one grouping
             kw = {"group_by": group_by, "group_size": group_size}

@@ -27,14 +27,17 @@ DEFAULT_PROMPT = "Question: {question}\n\nRetrieved contexts:\n{context}\n\nAnsw
 class VectorRAG:
     def __init__(self, gemini_api_key: str | None = None, collection_name: str = "fin_chunks", *,
                  embedder=None, store=None, generator: Callable[[str], str] | None = None,
-                 llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT):
+                 llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None):
         """embedder: .encode(list[str]) -> [n, dim] (rag_fin_amd.embedder.Embedder);
         store: rag_fin_amd.store.CorpusStore.  `gemini_api_key` is accepted for
-        signature compatibility and only handed to `generator` factories upstream."""
+        signature compatibility and only handed to `generator` factories upstream.
+        reranker: .predict(list[(query, text)]) -> [n] scores (rag_fin_amd.reranker.CrossEncoder), the
+        second stage of search(..., rerank=True)."""
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
         self.similarity_model = embedder
+        self.reranker = reranker
         self.collection = store
         self.collection_name = collection_name
         self.generator = generator
@@ -75,7 +78,7 @@ class VectorRAG:
 
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
-               mmr_lambda: float | None = None, fetch_k: int | None = None) -> list[dict]:
+               mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -85,7 +88,12 @@ class VectorRAG:
         group, `rank` = the 1-based position in it); every dict carries the field already.
         mmr_lambda (0..1): diversified search -- the top_k chunks are picked from the best fetch_k
         (default min(64, max(20, 4 top_k))) by maximal marginal relevance, so near-copies of one
-        chunk do not crowd out the rest; `rank` is the MMR order, `score` stays the relevance."""
+        chunk do not crowd out the rest; `rank` is the MMR order, `score` stays the relevance.
+        rerank: two-stage search -- the best fetch_k chunks (same default) are scored as (query, text)
+        pairs by the cross-encoder and the best top_k of them are kept; `rank` is the rerank order,
+        `score` stays the cosine and `rerank_score` (only here) is the cross-encoder's."""
+        if rerank:
+            return self._search_reranked([query], top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k)[0]
         q = self._embed([query])
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
@@ -100,18 +108,51 @@ class VectorRAG:
         to_dev = getattr(self.similarity_model, "encode_to_device", None)
         return to_dev(texts) if to_dev is not None else self.similarity_model.encode(texts)
 
+    def _search_reranked(self, queries, top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k):
+        if self.reranker is None:
+            raise ValueError("rerank=True needs a reranker (VectorRAG(..., reranker=CrossEncoder.from_local(dir)))")
+        if mmr_lambda is not None:
+            raise ValueError("rerank and mmr_lambda both re-order the best fetch_k chunks: give one of them")
+        if group_by is not None:
+            raise ValueError("rerank does not combine with group_by")
+        fk = min(64, max(20, 4 * top_k)) if fetch_k is None else fetch_k
+        if fk < top_k:
+            raise ValueError(f"fetch_k={fk} is less than top_k={top_k}")
+        q = self._embed(list(queries))
+        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
+                                         expr=expr, output_fields=OUTPUT_FIELDS)
+        hits = [list(r) for r in results]
+        # every query's candidates in ONE cross-encoder call
+        pairs = [(query, h.entity.text) for query, r in zip(queries, hits) for h in r]
+        scores = self.reranker.predict(pairs) if pairs else []
+        out, at = [], 0
+        for r in hits:
+            s = [float(v) for v in scores[at:at + len(r)]]
+            at += len(r)
+            # best rerank score first; equal scores keep the retrieval order
+            keep = sorted(range(len(r)), key=lambda i: (-s[i], i))[:top_k]
+            ctx = self._contexts([r[i] for i in keep])
+            for c, i in zip(ctx, keep):
+                c["rerank_score"] = s[i]
+            out.append(ctx)
+        return out
+
     retrieve = search  # BASELINE.json's "retrieve(query, k)" name for the same call
 
     def search_batch(self, queries: Sequence[str], top_k: int = 3, expr: str | None = None,
                      min_score: float | None = None, max_score: float | None = None,
                      group_by: str | None = None, group_size: int = 1,
-                     mmr_lambda: float | None = None, fetch_k: int | None = None) -> list[list[dict]]:
+                     mmr_lambda: float | None = None, fetch_k: int | None = None,
+                     rerank: bool = False) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
-        the whole batch."""
+        the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call."""
         if not queries:
             return []
+        if rerank:
+            return self._search_reranked(list(queries), top_k, expr, min_score, max_score, group_by, mmr_lambda,
+                                         fetch_k)
         q = self._embed(list(queries))
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,

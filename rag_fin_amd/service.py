@@ -3,6 +3,8 @@
 Environment (dotenv-style names):
   RAGFIN_MODEL_DIR     local all-MiniLM-L6-v2 directory (config.json, vocab.txt,
                        model.safetensors).  Required: nothing is fetched by name.
+  RERANKER_MODEL_DIR   optional local cross-encoder directory (e.g. ms-marco-MiniLM-L-6-v2, same three
+                       files): enables search(..., rerank=True)
   RAGFIN_DATA_DIR      folder with icici_q{1..4}_2023/*.json (default: extract_data)
   RAGFIN_DEVICE        torch device string (default cuda:0)
   WORLD_SIZE / RANK / LOCAL_RANK (torch.distributed.run): with WORLD_SIZE > 1 the corpus is
@@ -34,15 +36,23 @@ def ingest(store, embedder, chunks, upsert: bool = False) -> int:
     return n
 
 
+def _load_reranker(reranker_dir, device):
+    if not reranker_dir:
+        return None
+    from .reranker import CrossEncoder
+    return CrossEncoder.from_local(reranker_dir, device=device)
+
+
 def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
-              collection_name: str = "fin_chunks", generator=None):
+              collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None):
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
     embedder = Embedder.from_local(model_dir, device=device)
     store = CorpusStore(collection_name, dim=embedder.dim, device=device)
     ingest(store, embedder, chunker.build_all_chunks(data_dir))
-    return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator)
+    return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
+                     reranker=_load_reranker(reranker_dir, device))
 
 
 def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
@@ -66,7 +76,8 @@ def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
 
 
 def build_sharded_rag(model_dir: str, data_dir: str = "extract_data", local_rank: int = 0,
-                      collection_name: str = "fin_chunks", generator=None, backend: str = "nccl"):
+                      collection_name: str = "fin_chunks", generator=None, backend: str = "nccl",
+                      reranker_dir: str | None = None):
     """One process per GPU (launched by torch.distributed.run): every rank builds an embedder
     replica and its shard of the store.  Returns the VectorRAG on EVERY rank; a serving
     deployment then calls `rag.collection.start_workers()` on all ranks -- rank 0 comes back and
@@ -84,7 +95,9 @@ def build_sharded_rag(model_dir: str, data_dir: str = "extract_data", local_rank
     embedder = Embedder.from_local(model_dir, device=dev)
     store = ShardedCorpusStore(collection_name, dim=embedder.dim, device=dev)
     ingest_sharded(store, embedder, chunker.build_all_chunks(data_dir))
-    return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator)
+    # (the serving rank reranks; the others only hold a replica like the embedder's)
+    return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
+                     reranker=_load_reranker(reranker_dir, dev))
 
 
 def build_rag_from_env():
@@ -93,8 +106,11 @@ def build_rag_from_env():
         raise RuntimeError("RAGFIN_MODEL_DIR is not set: point it at a local all-MiniLM-L6-v2 "
                            "directory (the reference fetches the model by name; this build never "
                            "touches the network)")
+    reranker_dir = os.getenv("RERANKER_MODEL_DIR") or None
     if int(os.getenv("WORLD_SIZE", "1")) > 1:
         return build_sharded_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
-                                 int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"))
+                                 int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
+                                 reranker_dir=reranker_dir)
     return build_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
-                     os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"))
+                     os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
+                     reranker_dir=reranker_dir)

@@ -101,6 +101,50 @@ def _simple_tables():
     return _SIMPLE
 
 
+def assemble_pairs(q_ids, q_lens, d_ids, d_lens, max_length: int, cls_id: int, sep_id: int, pad_id: int):
+    """[CLS] q [SEP] d [SEP] rows of a cross-encoder from token ids WITHOUT specials (q_ids [n, Tq], d_ids
+    [n, Td] int32, padded; q_lens, d_lens [n] token counts -- they may exceed the arrays' widths, which need
+    only hold the first max_length - 3 tokens of a side), truncated to max_length by the `longest_first` rule
+    of Hugging Face's tokenizers library (BertTokenizerFast, what AutoTokenizer and with it sentence-transformers'
+    CrossEncoder load).  With budget = max_length - 3 and a pair that exceeds it:
+      * the shorter side (the query on a tie) is kept whole and the longer one cut to budget - shorter, as long
+        as that leaves the longer side at least as long as the shorter;
+      * otherwise both are cut: the shorter side to budget // 2 tokens, the longer side to the rest (one more
+        when the budget is odd).
+    -> (ids int32 [n, T] padded, lens int32 [n], seg int32 [n]); seg = index of the document's first token
+    (token_type_ids are 0 before it and 1 from it on, the closing [SEP] included)."""
+    import numpy as np
+    budget = max_length - 3
+    if budget < 0:
+        raise ValueError(f"max_length {max_length} leaves no room for [CLS] [SEP] [SEP]")
+    lq, ld = np.asarray(q_lens, dtype=np.int64), np.asarray(d_lens, dtype=np.int64)
+    short = np.minimum(lq, ld)
+    long_keep = np.where(short > budget, short, np.maximum(short, budget - short))
+    both = short + long_keep > budget
+    short_keep = np.where(both, budget // 2, short)
+    long_keep = np.where(both, budget - budget // 2, long_keep)
+    fits, q_longer = lq + ld <= budget, lq > ld
+    kq = np.where(fits, lq, np.where(q_longer, long_keep, short_keep))
+    kd = np.where(fits, ld, np.where(q_longer, short_keep, long_keep))
+    n = len(lq)
+    lens = (kq + kd + 3).astype(np.int32)
+    T = max(int(lens.max()), 1) if n else 1
+    ids = np.full((n, T), pad_id, dtype=np.int32)
+    pos = np.arange(T, dtype=np.int64)[None, :]
+    kq_, kd_ = kq[:, None], kd[:, None]
+    in_q = (pos >= 1) & (pos <= kq_)
+    in_d = (pos >= kq_ + 2) & (pos < kq_ + 2 + kd_)
+    q_ids, d_ids = np.asarray(q_ids), np.asarray(d_ids)
+    rows = np.broadcast_to(np.arange(n)[:, None], (n, T))
+    ids[in_q] = q_ids[rows[in_q], np.broadcast_to(pos - 1, (n, T))[in_q]]
+    ids[in_d] = d_ids[rows[in_d], (pos - kq_ - 2)[in_d]]
+    if n:
+        ids[:, 0] = cls_id
+        ids[np.arange(n), kq + 1] = sep_id
+        ids[np.arange(n), kq + kd + 2] = sep_id
+    return ids, lens, (kq + 2).astype(np.int32)
+
+
 class WordPieceTokenizer:
     def __init__(self, vocab: dict[str, int] | Iterable[str], do_lower_case: bool = True,
                  unk_token: str = "[UNK]", cls_token: str = "[CLS]", sep_token: str = "[SEP]",
@@ -327,6 +371,31 @@ class WordPieceTokenizer:
             lens[i] = len(row)
         T = max(int(lens.max()), 1)
         return np.ascontiguousarray(ids[:, :T]), lens
+
+    def batch_pairs(self, queries: list[str], documents: list[str], max_length: int = 512):
+        """(query, document) pairs of a cross-encoder -> (ids int32 [n, T], lens int32 [n], seg int32 [n]):
+        both sides through batch_native, their [CLS] / [SEP] dropped, then assemble_pairs().  Neither side can
+        keep more than budget = max_length - 3 tokens, so the native call stops a text at budget + 1 -- enough
+        to tell which side is longer unless BOTH run into that cap; those rare rows are counted in full (a text
+        has at most one token per character).  A query that repeats (one query against many documents) is
+        tokenised once."""
+        import numpy as np
+        if len(queries) != len(documents):
+            raise ValueError("batch_pairs expects as many queries as documents")
+        budget = max(max_length - 3, 0)
+        uniq = {}
+        which = np.fromiter((uniq.setdefault(q, len(uniq)) for q in queries), dtype=np.int64, count=len(queries))
+        uq = list(uniq)
+        q_ids, q_lens = self.batch_native(uq, budget + 3)
+        d_ids, d_lens = self.batch_native(list(documents), budget + 3)
+        # a native row is [CLS] tokens [SEP]: the tokens are columns 1 .. len - 2
+        q_lens, d_lens = (q_lens - 2).astype(np.int64)[which], (d_lens - 2).astype(np.int64)
+        capped = np.flatnonzero((q_lens > budget) & (d_lens > budget))
+        if capped.size:
+            for lens_, texts in ((q_lens, [uq[which[i]] for i in capped]), (d_lens, [documents[i] for i in capped])):
+                lens_[capped] = self.batch_native(texts, max(map(len, texts)) + 2)[1] - 2
+        return assemble_pairs(q_ids[which, 1:], q_lens, d_ids[:, 1:], d_lens, max_length,
+                              self.cls_id, self.sep_id, self.pad_id)
 
     def batch(self, texts: list[str], max_length: int = 256):
         """-> (ids int32 [B, T] padded with [PAD], lens int32 [B]), T = longest row."""
