@@ -338,6 +338,62 @@ size_t rf_debug_grouped_counters_offset(void);
 int rf_mmr_select(const rf_index_t* ix, int B, int fetch_k, int k, double lambda, int64_t id_base,
                   const double* cand_exact_dev, const int64_t* cand_ids_dev, float* scores_dev,
                   int64_t* ids_dev, double* exact_dev, void* stream);
+/* ---- lexical search: BM25 over posting lists, and reciprocal-rank fusion of several searches --------
+ * What RAG stacks put beside the dense retriever (Milvus: a BM25 sparse field, hybrid_search with
+ * RRFRanker; LangChain: EnsembleRetriever).  The caller builds the postings on the host
+ * (rag_fin_amd/lexical.py) and owns the device arrays, like the index storage:
+ *   post_off  int64  [n_terms + 1]  term t's postings are [post_off[t], post_off[t + 1])
+ *   post_row  uint32 [nnz]          rows holding the term, ASCENDING within a term
+ *   post_imp  fp32   [nnz]          the BM25 impact of (term, row): idf * tf-saturation, computed in
+ *                                   fp64 on the host and rounded to fp32 once; positive and normal
+ * A batch of queries is CSR on the device: q_off int32 [B + 1], q_term int32 (a query's distinct term
+ * ids, ascending), q_weight fp32 (the count of the term in the query); at most RF_SPARSE_MAX_TERMS
+ * terms per query (the kernel reads no more than that of a longer one).
+ * Score of row r:  acc = 0.0f; for the query's terms in order, if the term is in r:
+ * acc = acc + (w * imp), the product and the sum each rounded to fp32 on its own (no fma).  A row is
+ * a hit iff it holds a query term (acc > 0) and its bit is set in the filter, if one is given.
+ * Ranking (score desc, row asc); outputs as rf_search: scores_dev fp32 [B, k], ids_dev int64 [B, k]
+ * (row + id_base), exact_dev fp64 [B, k] (nullable) = (double)score, padded with -inf / -1.  No flags
+ * and no fallback: the summation order is fixed, so the answer is exact by construction and has the
+ * same bits on every run and for every B.
+ *   rf_sparse_create    host-side handle over the caller's arrays (checked on the host: non-null,
+ *                       16-byte aligned, 1 <= n_rows < 2^31, n_terms >= 1, nnz >= 1); no device call
+ *   rf_sparse_search    stream-ordered, no host sync, no allocation, captures into a hipGraph,
+ *                       1 <= k <= RF_MAX_K, 1 <= B <= 65535; RF_ERR_INVALID before any device call.
+ *                       filter_dev: NULL or a filter buffer as for rf_search_filtered (mask bits only;
+ *                       a header built for another row count passes no row).
+ *                       workspace_bytes >= rf_sparse_search_workspace_bytes(sp, B, k).
+ * What runs: grid (row tiles, B); a workgroup owns RF_SPARSE_TILE_ROWS consecutive rows as fp32
+ * accumulators in LDS, finds each term's slice of postings inside its tile by binary search, adds
+ * term after term with a barrier in between (rows within a term are distinct: plain read-modify-
+ * writes, no atomics), and selects its own top k into the workspace; a second launch, one workgroup
+ * per query, merges the tiles' lists.  A posting whose row is outside the tile or the index is
+ * skipped: malformed postings give wrong scores, never an out-of-range access.
+ *
+ * rf_fuse_rrf: weighted reciprocal-rank fusion of A <= RF_FUSE_MAX_ARMS answers.  ids_dev int64
+ * [A, B, F]: arm a's ids for query b in that search's order (-1 = padding), F <= RF_MAX_K.
+ *   fused(d) = sum over the arms a, in arm order, that hold d of  weights[a] / (rrf_k + rank_a(d)),
+ * rank_a(d) 1-based (the first occurrence, should an arm repeat an id), each division rounded to fp64
+ * on its own, the sum in fp64.  weights_host: A doubles in HOST memory (they travel in the launch
+ * arguments), finite and >= 0, NULL = all 1.0; rrf_k finite and > 0.  The best k distinct ids by
+ * (fused desc, id asc) go out as (float(fused), id, fused), padded with -inf / -1; 1 <= k <= RF_MAX_K.
+ * One workgroup per query, the A F <= 256 candidates deduplicated in LDS; no workspace.
+ * New in this build; the reference has no lexical arm and no fusion stage. */
+#define RF_SPARSE_MAX_TERMS 64
+#define RF_SPARSE_TILE_ROWS 8192
+#define RF_FUSE_MAX_ARMS 4
+typedef struct rf_sparse rf_sparse_t;
+int rf_sparse_create(rf_sparse_t** out, int64_t n_rows, int64_t n_terms, int64_t nnz,
+                     const int64_t* post_off_dev, const uint32_t* post_row_dev, const float* post_imp_dev,
+                     int device);
+int rf_sparse_destroy(rf_sparse_t* sp);
+size_t rf_sparse_search_workspace_bytes(const rf_sparse_t* sp, int B, int k);
+int rf_sparse_search(const rf_sparse_t* sp, const void* filter_dev, const int32_t* q_off_dev,
+                     const int32_t* q_term_dev, const float* q_weight_dev, int B, int k, int64_t id_base,
+                     float* scores_dev, int64_t* ids_dev, double* exact_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+int rf_fuse_rrf(int A, const int64_t* ids_dev, int F, const double* weights_host, double rrf_k, int B, int k,
+                float* scores_dev, int64_t* ids_dev_out, double* exact_dev, void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

@@ -18,6 +18,10 @@ RF_QCHUNK = 64
 RF_FLAG_CAND_OVERFLOW = 1
 RF_FLAG_TIE_OVERFLOW = 2
 RF_GROUP_MAX_CODES = 64   # dictionary size the fused grouped path serves (include/ragfin.h)
+# lexical search (include/ragfin.h, "lexical search")
+RF_SPARSE_MAX_TERMS = 64     # distinct known terms of one query
+RF_SPARSE_TILE_ROWS = 8192   # rows a workgroup of the posting scan accumulates in LDS
+RF_FUSE_MAX_ARMS = 4         # answers rf_fuse_rrf fuses
 
 
 class RagfinError(RuntimeError):
@@ -109,6 +113,13 @@ SIGNATURES = {
     "rf_debug_grouped_counters_offset": (c_size_t, []),
     "rf_mmr_select": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_int64, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p]),
+    "rf_sparse_create": (c_int, [POINTER(c_void_p), c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int]),
+    "rf_sparse_destroy": (c_int, [c_void_p]),
+    "rf_sparse_search_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rf_sparse_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_fuse_rrf": (c_int, [c_int, c_void_p, c_int, POINTER(c_double), c_double, c_int, c_int, c_void_p, c_void_p,
+                            c_void_p, c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p]),
     "rf_packed_shard_words": (c_size_t, [c_int, c_int]),

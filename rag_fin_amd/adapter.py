@@ -3,7 +3,8 @@
 Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
   GET /            service card                         (:121-132)
   GET /health      {"status": "healthy", "mcp": ...} | {"status": "unhealthy", "mcp": "unavailable"}
-  POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional), rerank: bool (optional)}
+  POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional), rerank: bool (optional),
+                   hybrid: bool (optional)}
                                                                -> tool search_vectors
   POST /answer     {question: str >= 5 chars, top_k: 1..10 = 3} -> tool answer_question
   GET /stats       -> tool get_collection_stats
@@ -46,11 +47,13 @@ class SearchRequest(BaseModel):
     fetch_k: Optional[int] = Field(default=None, ge=1, le=64)
     # two-stage search (the best fetch_k chunks re-scored by the cross-encoder); new
     rerank: bool = False
+    # hybrid search (the dense and a BM25 arm fused by reciprocal rank); new
+    hybrid: bool = False
 
 
 def search_args(req: SearchRequest) -> dict:
     """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by`, `group_size`,
-    `mmr_lambda` and `fetch_k` only when they were given and `rerank` only when it is set, so the
+    `mmr_lambda` and `fetch_k` only when they were given, `rerank` and `hybrid` only when set, so the
     reference's payload {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
     for name in ("filter", "min_score", "max_score", "group_by", "group_size", "mmr_lambda", "fetch_k"):
@@ -58,6 +61,8 @@ def search_args(req: SearchRequest) -> dict:
             args[name] = getattr(req, name)
     if req.rerank:
         args["rerank"] = True
+    if req.hybrid:
+        args["hybrid"] = True
     return args
 
 

@@ -1,6 +1,7 @@
 """The device layer under rag_fin_amd/store.py (which re-exports these names): `GpuIndex` over
 rf_index_* / rf_search (include/ragfin.h), the flagged-query ladder, the filter-mask helpers and
-rf_filter_eval.  All arithmetic goes through libragfin_hip.so; there is no CPU path."""
+rf_filter_eval; `SparseIndex` over rf_sparse_* (BM25 posting lists) and `fuse_rrf` over rf_fuse_rrf.
+All arithmetic goes through libragfin_hip.so; there is no CPU path."""
 from __future__ import annotations
 
 import ctypes
@@ -659,6 +660,92 @@ class GpuIndex:
             _lib.check(self.lib.rf_debug_scores(self.handle, c_void_p(q16.data_ptr()), q16.shape[0], n,
                                                 c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
         return out
+
+
+class SparseIndex:
+    """Thin object wrapper over rf_sparse_* (include/ragfin.h, "lexical search"): the posting arrays
+    of a `lexical.Postings` on the device, the handle over them and a search workspace.
+
+    Locking: as in GpuIndex, the workspace is shared by every caller, so `search` holds
+    `self._lock` while it sizes the workspace and enqueues; the results are the caller's own
+    tensors.  The postings are immutable: a changed corpus gets a new SparseIndex."""
+
+    def __init__(self, postings, device=None):
+        torch = _torch()
+        self.device = require_gpu(device)
+        self.lib = _lib.load_library()
+        self.n_rows, self.n_terms, self.nnz = postings.n_rows, postings.n_terms, postings.nnz
+        with torch.cuda.device(self.device):
+            self.post_off = torch.from_numpy(np.ascontiguousarray(postings.post_off, dtype=np.int64)).to(self.device)
+            # (uint32 rows travel as their int32 bit patterns)
+            self.post_row = torch.from_numpy(np.ascontiguousarray(postings.post_row, dtype=np.uint32).view(np.int32)
+                                             ).to(self.device)
+            self.post_imp = torch.from_numpy(np.ascontiguousarray(postings.post_imp, dtype=np.float32)).to(self.device)
+            handle = c_void_p()
+            _lib.check(self.lib.rf_sparse_create(ctypes.byref(handle), self.n_rows, self.n_terms, self.nnz,
+                                                 _ptr(self.post_off), _ptr(self.post_row), _ptr(self.post_imp),
+                                                 self.device.index))
+        self.handle = handle
+        self.workspace = None
+        self._lock = threading.Lock()
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            self.lib.rf_sparse_destroy(h)
+            self.handle = None
+
+    def search(self, q_off, q_term, q_weight, k: int, id_base: int = 0, filt=None, want_exact: bool = True):
+        """Enqueue rf_sparse_search on the current stream; no host sync.  q_off int32 [B + 1], q_term
+        int32, q_weight fp32: the CSR batch of lexical.encode_queries (numpy or tensors).  filt: a
+        filter buffer built for n_rows rows.  -> (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None)
+        on the device, padded with -inf / -1."""
+        torch = _torch()
+        if not 1 <= k <= _lib.RF_MAX_K:
+            raise ValueError(f"BM25 search: need 1 <= k <= {_lib.RF_MAX_K}, got {k}")
+        q_off = torch.as_tensor(q_off, dtype=torch.int32).to(self.device).contiguous()
+        # (an empty batch of terms still needs a pointer: one spare entry)
+        q_term = torch.cat([torch.as_tensor(q_term, dtype=torch.int32), torch.zeros(1, dtype=torch.int32)]
+                           ).to(self.device)
+        q_weight = torch.cat([torch.as_tensor(q_weight, dtype=torch.float32), torch.zeros(1, dtype=torch.float32)]
+                             ).to(self.device)
+        B = q_off.numel() - 1
+        scores = torch.empty((B, k), dtype=torch.float32, device=self.device)
+        ids = torch.empty((B, k), dtype=torch.int64, device=self.device)
+        exact = torch.empty((B, k), dtype=torch.float64, device=self.device) if want_exact else None
+        with self._lock, torch.cuda.device(self.device):
+            need = self.lib.rf_sparse_search_workspace_bytes(self.handle, B, k)
+            if need == 0:
+                raise ValueError(f"BM25 search: batch of {B} queries with k = {k} is out of range")
+            if self.workspace is None or self.workspace.numel() < need:
+                # (the old one is released in stream order: a search already enqueued still owns it)
+                self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rf_sparse_search(self.handle, _ptr(filt), _ptr(q_off), _ptr(q_term), _ptr(q_weight),
+                                                 B, k, id_base, _ptr(scores), _ptr(ids), _ptr(exact),
+                                                 _ptr(self.workspace), self.workspace.numel(),
+                                                 _lib.current_stream_ptr()))
+        return scores, ids, exact
+
+
+def fuse_rrf(arm_ids, k: int, weights=None, rrf_k: float = 60.0):
+    """Enqueue rf_fuse_rrf on the current stream: arm_ids int64 [A, B, F] on the device (-1 =
+    padding) -> (scores f32 [B,k], ids i64 [B,k], fused f64 [B,k]) on the device."""
+    torch = _torch()
+    if arm_ids.dim() != 3 or arm_ids.dtype != torch.int64:
+        raise ValueError("fuse_rrf expects int64 [A, B, F] ids")
+    arm_ids = arm_ids.contiguous()
+    A, B, F = arm_ids.shape
+    if weights is not None and len(weights) != A:
+        raise ValueError(f"fuse_rrf: {len(weights)} weights for {A} arms")
+    w = None if weights is None else (ctypes.c_double * A)(*[float(x) for x in weights])
+    dev = arm_ids.device
+    scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+    ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+    fused = torch.empty((B, k), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load_library().rf_fuse_rrf(A, _ptr(arm_ids), F, w, float(rrf_k), B, k, _ptr(scores), _ptr(ids),
+                                                   _ptr(fused), _lib.current_stream_ptr()))
+    return scores, ids, fused
 
 
 def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int):

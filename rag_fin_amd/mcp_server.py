@@ -57,7 +57,8 @@ def _searcher():
 
 def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
-                   mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False):
+                   mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
+                   hybrid: bool = False):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -67,12 +68,18 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     values trade relevance for chunks unlike those already returned); fetch_k: how many best chunks
     the top_k are picked from (at most 64).
     rerank: optional second stage -- the best fetch_k chunks are re-scored as (query, text) pairs by the
-    cross-encoder and the best top_k of them returned, each with a rerank_score."""
+    cross-encoder and the best top_k of them returned, each with a rerank_score.
+    hybrid: optional lexical arm -- the semantic search and a BM25 search of the chunk texts run at
+    fetch_k each and are fused by reciprocal rank; `score` is then the fused score.  With filter and
+    rerank; not with min_score / max_score, group_by or mmr_lambda.  Needs the store's lexical index
+    (LEXICAL_INDEX=1 at ingest)."""
     try:
-        # (only what was given travels on; diversified and reranked calls bypass the micro-batcher as well)
+        # (only what was given travels on; diversified, reranked and hybrid calls bypass the micro-batcher as well)
         mmr = {name: v for name, v in (("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k)) if v is not None}
         if rerank:
             mmr["rerank"] = True
+        if hybrid:
+            mmr["hybrid"] = True
         if group_by is not None:
             # grouped calls bypass the micro-batcher like filtered ones: one batch shares one grouping
             kw = {"group_by": group_by, "group_size": group_size}

@@ -78,7 +78,8 @@ class VectorRAG:
 
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
-               mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False) -> list[dict]:
+               mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
+               hybrid: bool = False) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -91,9 +92,20 @@ class VectorRAG:
         chunk do not crowd out the rest; `rank` is the MMR order, `score` stays the relevance.
         rerank: two-stage search -- the best fetch_k chunks (same default) are scored as (query, text)
         pairs by the cross-encoder and the best top_k of them are kept; `rank` is the rerank order,
-        `score` stays the cosine and `rerank_score` (only here) is the cross-encoder's."""
+        `score` stays the cosine and `rerank_score` (only here) is the cross-encoder's.
+        hybrid: the dense search and a BM25 search of the chunk texts (the store needs its lexical
+        index: create_index("sparse", ...), service.build_rag(..., hybrid=True)) run at fetch_k each
+        (same default), their lists are fused by reciprocal rank (RRF, k = 60) and the best top_k are
+        kept; `score` is the fused score.  With expr (both arms) and with rerank (the cross-encoder
+        scores the fused candidates); not with min_score / max_score, group_by or mmr_lambda
+        (ValueError)."""
+        if hybrid:
+            self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if rerank:
-            return self._search_reranked([query], top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k)[0]
+            return self._search_reranked([query], top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
+                                         hybrid)[0]
+        if hybrid:
+            return self._contexts(self._search_hybrid([query], top_k, top_k, expr, fetch_k)[0])
         q = self._embed([query])
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
@@ -108,19 +120,48 @@ class VectorRAG:
         to_dev = getattr(self.similarity_model, "encode_to_device", None)
         return to_dev(texts) if to_dev is not None else self.similarity_model.encode(texts)
 
-    def _search_reranked(self, queries, top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k):
+    @staticmethod
+    def _default_fetch_k(top_k: int) -> int:
+        return min(64, max(20, 4 * top_k))
+
+    @staticmethod
+    def _check_hybrid(min_score, max_score, group_by, mmr_lambda) -> None:
+        if min_score is not None or max_score is not None:
+            raise ValueError("hybrid search ranks by a fused score: it takes no min_score / max_score")
+        if group_by is not None:
+            raise ValueError("hybrid search does not combine with group_by")
+        if mmr_lambda is not None:
+            raise ValueError("hybrid search does not combine with mmr_lambda")
+
+    def _search_hybrid(self, queries, top_k, limit, expr, fetch_k):
+        """The dense and the BM25 arm at fetch_k each, fused by RRF -> `limit` hits per query."""
+        from .hybrid import AnnSearchRequest, RRFRanker
+        fk = self._default_fetch_k(top_k) if fetch_k is None else fetch_k
+        if isinstance(fk, bool) or not isinstance(fk, int) or not 1 <= fk <= 64:
+            raise ValueError(f"hybrid search: fetch_k must be an integer in 1..64, got {fk!r}")
+        if not 1 <= limit <= fk:
+            raise ValueError(f"hybrid search: need 1 <= top_k <= fetch_k (got top_k = {limit}, fetch_k = {fk})")
+        reqs = [AnnSearchRequest(self._embed(list(queries)), "embedding", {"metric_type": "COSINE"}, fk, expr),
+                AnnSearchRequest(list(queries), "sparse", {"metric_type": "BM25"}, fk, expr)]
+        return self.collection.hybrid_search(reqs, RRFRanker(), limit, output_fields=OUTPUT_FIELDS)
+
+    def _search_reranked(self, queries, top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
+                         hybrid: bool = False):
         if self.reranker is None:
             raise ValueError("rerank=True needs a reranker (VectorRAG(..., reranker=CrossEncoder.from_local(dir)))")
         if mmr_lambda is not None:
             raise ValueError("rerank and mmr_lambda both re-order the best fetch_k chunks: give one of them")
         if group_by is not None:
             raise ValueError("rerank does not combine with group_by")
-        fk = min(64, max(20, 4 * top_k)) if fetch_k is None else fetch_k
+        fk = self._default_fetch_k(top_k) if fetch_k is None else fetch_k
         if fk < top_k:
             raise ValueError(f"fetch_k={fk} is less than top_k={top_k}")
-        q = self._embed(list(queries))
-        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
-                                         expr=expr, output_fields=OUTPUT_FIELDS)
+        if hybrid:   # the fused candidates: `score` is then the fused score
+            results = self._search_hybrid(queries, top_k, fk, expr, fk)
+        else:
+            q = self._embed(list(queries))
+            results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
+                                             expr=expr, output_fields=OUTPUT_FIELDS)
         hits = [list(r) for r in results]
         # every query's candidates in ONE cross-encoder call
         pairs = [(query, h.entity.text) for query, r in zip(queries, hits) for h in r]
@@ -143,16 +184,21 @@ class VectorRAG:
                      min_score: float | None = None, max_score: float | None = None,
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
-                     rerank: bool = False) -> list[list[dict]]:
+                     rerank: bool = False, hybrid: bool = False) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
-        the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call."""
+        the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call; hybrid:
+        dense + BM25 fused by reciprocal rank for every query, as in search()."""
+        if hybrid:
+            self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if not queries:
             return []
         if rerank:
             return self._search_reranked(list(queries), top_k, expr, min_score, max_score, group_by, mmr_lambda,
-                                         fetch_k)
+                                         fetch_k, hybrid)
+        if hybrid:
+            return [self._contexts(r) for r in self._search_hybrid(list(queries), top_k, top_k, expr, fetch_k)]
         q = self._embed(list(queries))
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,

@@ -5,6 +5,7 @@ Environment (dotenv-style names):
                        model.safetensors).  Required: nothing is fetched by name.
   RERANKER_MODEL_DIR   optional local cross-encoder directory (e.g. ms-marco-MiniLM-L-6-v2, same three
                        files): enables search(..., rerank=True)
+  LEXICAL_INDEX        1: declare the lexical (BM25) index at ingest: enables search(..., hybrid=True)
   RAGFIN_DATA_DIR      folder with icici_q{1..4}_2023/*.json (default: extract_data)
   RAGFIN_DEVICE        torch device string (default cuda:0)
   WORLD_SIZE / RANK / LOCAL_RANK (torch.distributed.run): with WORLD_SIZE > 1 the corpus is
@@ -44,13 +45,18 @@ def _load_reranker(reranker_dir, device):
 
 
 def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
-              collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None):
+              collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
+              hybrid: bool = False):
+    """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
+    can run; its posting lists are built by the first such search."""
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
     embedder = Embedder.from_local(model_dir, device=device)
     store = CorpusStore(collection_name, dim=embedder.dim, device=device)
     ingest(store, embedder, chunker.build_all_chunks(data_dir))
+    if hybrid:
+        store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
                      reranker=_load_reranker(reranker_dir, device))
 
@@ -113,4 +119,4 @@ def build_rag_from_env():
                                  reranker_dir=reranker_dir)
     return build_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                      os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
-                     reranker_dir=reranker_dir)
+                     reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1")

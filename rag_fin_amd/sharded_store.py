@@ -111,7 +111,11 @@ class ShardedCorpusStore(CorpusStore):
     # -- index type ---------------------------------------------------------------------------------
     def create_index(self, field_name: str, index_params: dict | None = None, **kwargs) -> None:
         """FLAT and IVF_FLAT (served as FLAT) are accepted; SQ8 is not implemented for the sharded
-        search (NotImplementedError).  Local bookkeeping only: every rank makes the same call."""
+        search (NotImplementedError), and neither is the lexical index of the "sparse" field.  Local
+        bookkeeping only: every rank makes the same call."""
+        if field_name == "sparse":
+            raise NotImplementedError("the lexical (BM25) index is not implemented for the sharded store "
+                                      "(single-GPU CorpusStore only)")
         itype, metric = self._check_index_params(field_name, dict(index_params or {}))
         if itype == "SQ8":
             raise NotImplementedError("SQ8 is not supported by ShardedCorpusStore (single-GPU CorpusStore only)")
@@ -274,6 +278,9 @@ class ShardedCorpusStore(CorpusStore):
     def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
                output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False,
                mmr_lambda=None, mmr_fetch_k=None):
+        if anns_field == "sparse":
+            # (the texts are replicated, but no rank holds posting lists)
+            raise NotImplementedError("BM25 search (anns_field='sparse') is not implemented for the sharded store")
         if mmr_lambda is not None or mmr_fetch_k is not None:
             # (the candidate vectors live on different ranks)
             raise NotImplementedError("diversified search (mmr_lambda) is not implemented for the sharded store")
@@ -284,6 +291,9 @@ class ShardedCorpusStore(CorpusStore):
         if self._band_of(param) is not None:
             raise NotImplementedError("range search (radius / range_filter) is not implemented for the sharded store")
         return super().search(data, anns_field, param, limit, expr, output_fields)
+
+    def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields=None):
+        raise NotImplementedError("hybrid search (hybrid_search) is not implemented for the sharded store")
 
     def _expr_rows(self, expr):
         raise NotImplementedError(f"query expression {expr!r}: the sharded store supports '' and 'id in [...]' only")

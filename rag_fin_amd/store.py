@@ -17,6 +17,10 @@ columns stay in host Python lists, and the four a filter can test are mirrored o
 device on demand (filtered search: `search(..., expr=...)`, `query(expr=...)`,
 rag_fin_amd/filter_expr.py).  All arithmetic goes through libragfin_hip.so; there is no
 CPU path.
+
+Beyond the reference: a lexical index over the `text` column (create_index("sparse", ...),
+search(["query text"], anns_field="sparse", ...): BM25 on the GPU) and `hybrid_search`, which fuses
+dense and BM25 arms by reciprocal rank (rag_fin_amd/lexical.py, rag_fin_amd/hybrid.py).
 """
 from __future__ import annotations
 
@@ -32,9 +36,11 @@ import numpy as np
 
 from . import _lib
 from . import filter_expr
+from . import lexical
+from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, _ptr, eval_filter, filter_mask_bits, grouped_exhaustive, mask_words,  # noqa: F401
-                    require_gpu, rerun_flagged, words_mask)
+from .index import (GpuIndex, SparseIndex, _ptr, eval_filter, filter_mask_bits, fuse_rrf, grouped_exhaustive,  # noqa: F401
+                    mask_words, require_gpu, rerun_flagged, words_mask)
 
 
 SCALAR_FIELDS = ("id", "text", "period", "chunk_type", "statement_type", "primary_value")
@@ -289,6 +295,12 @@ class CorpusStore:
         self._rw = _RWLock()
         self.index_type = "FLAT"            # create_index: "FLAT" (IVF_FLAT is served as FLAT) or "SQ8"
         self._index_params = None           # what create_index was given (None: no create_index call)
+        # the lexical index (create_index("sparse", ...)): its parameters, and the SparseIndex built from
+        # the text column by the first BM25 search after a change of the rows (None: to be built)
+        self._sparse_params = None
+        self._sparse = None
+        self._sparse_lock = threading.Lock()
+        self.analyzer = None                # list[str] -> list[list[str]]; None: lexical.analyze
 
     # -- pymilvus-shaped lifecycle ---------------------------------------------
     def flush(self) -> None:
@@ -308,6 +320,7 @@ class CorpusStore:
                 col.clear()
             self._pk_row.clear()
             self._dcols = None
+            self._sparse = None
 
     @property
     def num_entities(self) -> int:
@@ -338,8 +351,19 @@ class CorpusStore:
         default), "IVF_FLAT" (served as FLAT: exact, `params` such as nlist are ignored) or "SQ8"
         (an int8 shadow of the vectors: fewer bytes per search, same exact answers; dim % 32 == 0).
         Any other type, a metric_type other than the collection's or a field other than
-        "embedding" raises ValueError."""
+        "embedding" / "sparse" raises ValueError.
+        field_name "sparse" with {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25",
+        "params": {"bm25_k1": 1.2, "bm25_b": 0.75}} declares the lexical index over the `text` column
+        and leaves the vector index as it is.  The posting lists are built from the texts by the first
+        BM25 search and rebuilt, whole, by the first one after any add / insert / upsert / delete
+        (there is no incremental maintenance)."""
         params = dict(index_params or {})
+        if field_name == "sparse":
+            sparse = self._check_sparse_params(params)
+            with self._rw.write():
+                self._sparse_params = sparse
+                self._sparse = None
+            return
         itype, metric = self._check_index_params(field_name, params)
         with self._rw.write():
             if itype == "SQ8":
@@ -363,8 +387,33 @@ class CorpusStore:
             raise ValueError("create_index: params must be a dict")
         return itype, metric
 
+    @staticmethod
+    def _check_sparse_params(params) -> dict:
+        itype = str(params.get("index_type", "SPARSE_INVERTED_INDEX")).upper()
+        if itype != "SPARSE_INVERTED_INDEX":
+            raise ValueError(f"create_index: the sparse field takes index_type SPARSE_INVERTED_INDEX, got {itype!r}")
+        metric = str(params.get("metric_type", "BM25")).upper()
+        if metric != "BM25":
+            raise ValueError(f"create_index: the sparse field takes metric_type BM25, got {metric!r}")
+        p = params.get("params")
+        if p is not None and not isinstance(p, dict):
+            raise ValueError("create_index: params must be a dict")
+        k1, b = lexical.check_bm25_params((p or {}).get("bm25_k1", lexical.DEFAULT_K1),
+                                          (p or {}).get("bm25_b", lexical.DEFAULT_B))
+        return {"bm25_k1": k1, "bm25_b": b}
+
+    @staticmethod
+    def _is_sparse_field(kwargs) -> bool:
+        return "sparse" in (kwargs.get("field_name"), kwargs.get("index_name"))
+
     def drop_index(self, **kwargs) -> None:
-        """Back to FLAT (the shadow of SQ8 is freed)."""
+        """Back to FLAT (the shadow of SQ8 is freed).  field_name="sparse" (or index_name="sparse"):
+        drop the lexical index instead and leave the vector index alone."""
+        if self._is_sparse_field(kwargs):
+            with self._rw.write():
+                self._sparse_params = None
+                self._sparse = None
+            return
         with self._rw.write():
             if self._has_sq8:
                 self.index.disable_sq8()
@@ -372,6 +421,9 @@ class CorpusStore:
             self._index_params = None
 
     def has_index(self, **kwargs) -> bool:
+        """field_name="sparse" (or index_name="sparse") asks about the lexical index."""
+        if self._is_sparse_field(kwargs):
+            return self._sparse_params is not None
         return self._index_params is not None
 
     def _use_sq8(self, B: int, limit: int, band=None) -> bool:
@@ -427,6 +479,7 @@ class CorpusStore:
     def _append_rows(self, ids, cols) -> None:
         """The host side of an append: the pk map and the six scalar columns."""
         texts, periods, chunk_types, statement_types, primary_values = cols
+        self._sparse = None   # the lexical index is rebuilt by the next BM25 search
         base = self.num_entities
         for j, pk in enumerate(ids):
             self._pk_row[pk] = base + j
@@ -504,6 +557,7 @@ class CorpusStore:
         keep_mask = ~mask
         keep = np.flatnonzero(keep_mask)
         n_old = self.num_entities
+        self._sparse = None   # the lexical index is rebuilt by the next BM25 search
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
         for f in SCALAR_FIELDS:
@@ -603,7 +657,20 @@ class CorpusStore:
         to a hit already picked).  The hits come in MMR order, the first is always the best hit and
         hit.score stays the relevance score; 1 gives the plain ranking.  With expr, range search and
         an SQ8 index; not with group_by_field (ValueError, as are mmr_fetch_k without mmr_lambda,
-        limit > mmr_fetch_k and mmr_fetch_k > 64)."""
+        limit > mmr_fetch_k and mmr_fetch_k > 64).
+        anns_field "sparse": BM25 search of the `text` column (create_index("sparse", ...) first).
+        data is a list of query STRINGS, param {"metric_type": "BM25"}, limit <= 64; a hit is a row
+        that holds at least one query term (and passes expr), hit.score its BM25 score, so a list
+        may be shorter than limit, or empty.  Exact and bit-reproducible.  No range,
+        grouping or MMR arguments (ValueError); vectors for "sparse" or strings for "embedding"
+        raise ValueError too.  To combine the two fields see hybrid_search."""
+        if anns_field == "sparse":
+            if group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
+                raise ValueError("BM25 search (anns_field='sparse') has no grouping and no MMR form")
+            texts = self._check_sparse_search(data, param, limit)
+            fields = self._check_output_fields(output_fields)
+            with self._rw.read():
+                return self._search_sparse(texts, limit, expr, fields)
         mmr = check_mmr(mmr_lambda, mmr_fetch_k, limit)
         if mmr is not None and group_by_field is not None:
             raise ValueError("diversified search (mmr_lambda) cannot be combined with group_by_field")
@@ -630,9 +697,158 @@ class CorpusStore:
                              "(grouped results are not paged)")
         return field, int(group_size)
 
+    # -- lexical and hybrid search (rag_fin_amd/lexical.py, rag_fin_amd/hybrid.py) --------
+    @staticmethod
+    def _is_text(data) -> bool:
+        return isinstance(data, str) or (isinstance(data, (list, tuple)) and len(data) > 0
+                                         and all(isinstance(t, str) for t in data))
+
+    def _check_output_fields(self, output_fields) -> list:
+        fields = list(output_fields or [])
+        for f in fields:
+            if f not in self.columns:
+                raise KeyError(f"unknown output field {f!r}")
+        return fields
+
+    def _check_sparse_search(self, data, param, limit) -> list:
+        """Everything a BM25 search refuses -> the query strings."""
+        if self._sparse_params is None:
+            raise ValueError("no sparse index: call create_index('sparse', {'index_type': 'SPARSE_INVERTED_INDEX', "
+                             "'metric_type': 'BM25'}) first")
+        if not self._is_text(data):
+            raise ValueError("the sparse field is searched with query strings (a list of str), not with vectors")
+        metric = str((param or {}).get("metric_type", "BM25")).upper()
+        if metric != "BM25":
+            raise ValueError(f"the sparse field is searched with metric_type BM25, search asked for {metric}")
+        params = (param or {}).get("params")
+        if params is not None and not isinstance(params, dict):
+            raise ValueError("search: param['params'] must be a dict")
+        if params and (params.get("radius") is not None or params.get("range_filter") is not None):
+            raise ValueError("BM25 search (anns_field='sparse') has no range form (radius / range_filter)")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
+            raise ValueError("limit must be an integer >= 1")
+        if limit > _lib.RF_MAX_K:
+            raise ValueError(f"BM25 search: limit = {limit} > {_lib.RF_MAX_K} (the sparse arm is not paged)")
+        return [data] if isinstance(data, str) else list(data)
+
+    def _sparse_index(self):
+        """(postings, SparseIndex | None) over the current text column, built when a mutation (or
+        create_index) has invalidated the last one.  None: no row holds a term.  Caller holds the
+        read lock."""
+        with self._sparse_lock:
+            if self._sparse is None:
+                p = self._sparse_params
+                postings = lexical.build_postings(self.columns["text"], p["bm25_k1"], p["bm25_b"], self.analyzer)
+                self._sparse = (postings, SparseIndex(postings, self.index.device) if postings.nnz else None)
+            return self._sparse
+
+    def _sparse_arm(self, texts, limit: int, expr):
+        """The BM25 arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors, or None
+        when nothing can hit (no row holds a term)."""
+        postings, sp = self._sparse_index()
+        if sp is None:
+            return None
+        q_off, q_term, q_weight = lexical.encode_queries(postings, texts, self.analyzer)
+        kw = {} if filter_expr.is_empty(expr) else {"filt": self.build_filter(expr)}
+        scores, rows, _ = sp.search(q_off, q_term, q_weight, limit, want_exact=False, **kw)
+        return scores, rows
+
+    def _search_sparse(self, texts, limit, expr, fields):
+        res = self._sparse_arm(texts, limit, expr)
+        if res is None:
+            return [[] for _ in texts]
+        scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
+        return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
+
+    def _hits(self, rows, scores, fields) -> list:
+        """The Hit list of one query from its row numbers (best first, -1 ends it) and scores."""
+        hits = []
+        for r, s in zip(rows.tolist(), scores.tolist()):
+            if r < 0:
+                break
+            hits.append(Hit(r, self.columns["id"][r], float(s), {f: self.columns[f][r] for f in fields}))
+        return hits
+
+    def _dense_arm(self, q16, limit: int, expr):
+        """The dense arm of a hybrid search on the device -> rows i64 [B, limit]: the existing ladder
+        (SQ8 first when the index has a shadow), so a flagged query is patched before the fusion."""
+        kw = {}
+        if not filter_expr.is_empty(expr):
+            kw["filt"] = self.build_filter(expr)
+        elif self._use_sq8(int(q16.shape[0]), limit):
+            kw["sq8"] = True
+        return self.index.search(q16, limit, **kw)[1]
+
+    def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields: Iterable[str] | None = None):
+        """pymilvus-shaped hybrid search: every AnnSearchRequest of `reqs` (1..4; anns_field "embedding"
+        with query vectors, or "sparse" with query strings) runs on the GPU with its own limit (<= 64)
+        and its own expr, and `rerank` -- an RRFRanker -- fuses the arms' ranked lists per query:
+        fused(d) = sum over the arms holding d of weight / (k + rank), the best `limit` (<= 64) rows by
+        (fused desc, row asc).  One list of hits per query; hit.score is the fused score.  The fusion
+        runs on the device (rf_fuse_rrf) and the call downloads once.  All arms must carry the same
+        number of queries; range, grouping and MMR arguments have no hybrid form.  A score-normalising
+        ranker is not offered (WeightedRanker raises NotImplementedError; weigh by RRFRanker(weights=...))."""
+        torch = _torch()
+        reqs = list(reqs)
+        if not 1 <= len(reqs) <= MAX_ARMS or not all(isinstance(r, AnnSearchRequest) for r in reqs):
+            raise ValueError(f"hybrid_search takes 1..{MAX_ARMS} AnnSearchRequest objects")
+        if not isinstance(rerank, RRFRanker):
+            raise ValueError("hybrid_search: rerank must be an RRFRanker (score-normalising rankers are not "
+                             "supported; use RRFRanker(weights=...))")
+        weights = rerank.arm_weights(len(reqs))
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= limit <= _lib.RF_MAX_K:
+            raise ValueError(f"hybrid_search: limit must be an integer in 1..{_lib.RF_MAX_K}, got {limit!r}")
+        fields = self._check_output_fields(output_fields)
+        with self._rw.read():
+            # every arm is checked before any runs
+            prepared = []
+            for r in reqs:
+                if r.limit > _lib.RF_MAX_K:
+                    raise ValueError(f"hybrid_search: an arm's limit is at most {_lib.RF_MAX_K}, got {r.limit}")
+                if r.anns_field == "sparse":
+                    q = self._check_sparse_search(r.data, r.param, r.limit)
+                    prepared.append((r, q, len(q)))
+                elif r.anns_field == "embedding":
+                    if self._is_text(r.data):
+                        raise ValueError("the embedding field is searched with vectors, not with strings")
+                    metric = str(r.param.get("metric_type", self.metric_type)).upper()
+                    if metric != self.metric_type:
+                        raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
+                    if self._band_of(r.param) is not None:
+                        raise ValueError("hybrid_search: an arm takes no range parameters (radius / range_filter)")
+                    q = self._prepare_queries(r.data)
+                    prepared.append((r, q, int(q.shape[0])))
+                else:
+                    raise ValueError(f"unknown vector field {r.anns_field!r}")
+            B = prepared[0][2]
+            if any(n != B for _, _, n in prepared):
+                raise ValueError(f"hybrid_search: the arms carry {[n for _, _, n in prepared]} queries; all must "
+                                 "carry the same number")
+            if self.num_entities == 0 or B == 0:
+                return [[] for _ in range(B)]
+            F = max(r.limit for r in reqs)
+            device = self.index.device
+            arms = []
+            for r, q, _ in prepared:
+                if r.anns_field == "sparse":
+                    res = self._sparse_arm(q, r.limit, r.expr)
+                    rows = None if res is None else res[1]
+                else:
+                    rows = self._dense_arm(q, r.limit, r.expr)
+                block = torch.full((B, F), -1, dtype=torch.int64, device=device)
+                if rows is not None:
+                    block[:, :r.limit] = rows
+                arms.append(block)
+            _, rows, fused = fuse_rrf(torch.stack(arms), int(limit), weights, rerank.k)
+            packed = torch.stack([rows, fused.view(torch.int64)]).cpu().numpy()   # the one download
+            rows, fused = packed[0], packed[1].view(np.float64)
+            return [self._hits(rows[b], fused[b], fields) for b in range(B)]
+
     def _search(self, data, anns_field, param, limit, expr, output_fields, group=None, mmr=None):
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
+        if self._is_text(data):
+            raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
         metric = (param or {}).get("metric_type", self.metric_type).upper()
         if metric != self.metric_type:
             raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
@@ -705,6 +921,8 @@ class CorpusStore:
                 "metric_type": self.metric_type, "n": n, "columns": self.columns}
         if self.index_type != "FLAT":   # FLAT directories stay exactly as before
             meta["index_type"] = self.index_type
+        if self._sparse_params is not None:   # (and so do directories without a lexical index)
+            meta["sparse_index"] = dict(self._sparse_params)
         tmp = os.path.join(path, "columns.json.tmp")
         with open(tmp, "w", encoding="utf-8") as f:
             json.dump(meta, f, ensure_ascii=False)
@@ -755,7 +973,14 @@ class CorpusStore:
         itype = meta.get("index_type", "FLAT")   # a missing key means FLAT
         if itype != "FLAT":
             st.create_index("embedding", {"index_type": itype, "metric_type": st.metric_type})
+        st._adopt_sparse(meta)
         return st
+
+    def _adopt_sparse(self, meta: dict) -> None:
+        """Re-declare the lexical index a saved store had (the postings are rebuilt on first use)."""
+        if meta.get("sparse_index") is not None:
+            self.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25",
+                                         "params": dict(meta["sparse_index"])})
 
     # -- filters -------------------------------------------------------------------------
     def build_filter(self, expr: str):
