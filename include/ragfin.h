@@ -176,12 +176,16 @@ int rf_search_exhaustive_after(const rf_index_t* ix, const void* q_dev, int B, i
  *                   inclusive; IEEE comparisons, so a NaN value fails
  *   RF_FOP_ROWLIST  the row number is in row_lists_dev[off .. off + len) (sorted ascending,
  *                   binary search)
+ *   RF_FOP_BITMAP   (rf_filter_eval_bitmaps only) row r passes iff (r >> 5) < len and bit r & 31 of
+ *                   bitmaps_dev[off + (r >> 5)] is set: a row bitmap some earlier call on the same
+ *                   stream wrote, such as rf_text_match ("keyword filters" below)
  *   RF_FOP_TRUE / RF_FOP_FALSE
  * and RF_FOP_AND / RF_FOP_OR (two operands) / RF_FOP_NOT (one).
  * columns: HOST array of RF_FILTER_COLUMNS device pointers {int32 period codes [n_rows],
  * int32 chunk_type codes, int32 statement_type codes, fp64 primary_value [n_rows]}; an entry
  * the program does not read may be NULL.  code_sets_dev / row_lists_dev may be NULL when the
- * program has no leaf of that kind.
+ * program has no leaf of that kind.  rf_filter_eval is rf_filter_eval_bitmaps with bitmaps_dev =
+ * NULL; a RF_FOP_BITMAP leaf with a NULL bitmaps_dev is RF_ERR_INVALID before any device call.
  * rf_filter_from_mask: the same buffer from a caller's own row mask (mask_dev uint32 [nblk],
  * same bit layout; bits past n_rows are ignored) -- compaction only.
  *
@@ -205,13 +209,15 @@ int rf_search_exhaustive_after(const rf_index_t* ix, const void* q_dev, int B, i
 #define RF_FOP_AND 6
 #define RF_FOP_OR 7
 #define RF_FOP_NOT 8
+#define RF_FOP_BITMAP 9      /* row r passes iff (r >> 5) < len and bit (r & 31) of bitmaps_dev[off + (r >> 5)] is set */
 #define RF_FRANGE_LO_INCL 1
 #define RF_FRANGE_HI_INCL 2
 typedef struct rf_filter_op {
   int32_t op;      /* RF_FOP_* */
   int32_t column;  /* CODESET: 0..2; RANGE: 3 */
-  int32_t off;     /* CODESET: first word in code_sets_dev; ROWLIST: first entry in row_lists_dev */
-  int32_t len;     /* CODESET: words; ROWLIST: entries */
+  int32_t off;     /* CODESET: first word in code_sets_dev; ROWLIST: first entry in row_lists_dev;
+                      BITMAP: first word in bitmaps_dev */
+  int32_t len;     /* CODESET, BITMAP: words; ROWLIST: entries */
   int32_t flags;   /* RANGE: RF_FRANGE_* bits */
   int32_t pad;
   double lo, hi;   /* RANGE bounds */
@@ -220,6 +226,9 @@ size_t rf_filter_bytes(int64_t n_rows);
 int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
                    const uint32_t* row_lists_dev, const void* const* columns, int64_t n_rows,
                    void* filter_dev, void* stream);
+int rf_filter_eval_bitmaps(const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
+                           const uint32_t* row_lists_dev, const uint32_t* bitmaps_dev,
+                           const void* const* columns, int64_t n_rows, void* filter_dev, void* stream);
 int rf_filter_from_mask(const uint32_t* mask_dev, int64_t n_rows, void* filter_dev, void* stream);
 int rf_search_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
                        int64_t id_base, float* scores_dev, int64_t* ids_dev, double* exact_dev,
@@ -394,6 +403,50 @@ int rf_sparse_search(const rf_sparse_t* sp, const void* filter_dev, const int32_
                      size_t workspace_bytes, void* stream);
 int rf_fuse_rrf(int A, const int64_t* ids_dev, int F, const double* weights_host, double rrf_k, int B, int k,
                 float* scores_dev, int64_t* ids_dev_out, double* exact_dev, void* stream);
+/* ---- keyword filters: TEXT_MATCH / PHRASE_MATCH as leaves of a filter expression ------------------
+ * Milvus pairs its BM25 field with TEXT_MATCH(field, 'terms' [, minimum_should_match=N]) and
+ * PHRASE_MATCH(field, 'a b c') in `expr`.  rf_text_match turns the posting lists of an rf_sparse_t
+ * into one row bitmap per leaf, which a RF_FOP_BITMAP leaf of rf_filter_eval_bitmaps then reads
+ * (the definition in numpy: rag_fin_amd/lexical.py, text_match_reference).
+ *   RF_TEXT_MATCH   terms: DISTINCT term ids, ascending.  Row r passes iff at least min_match of
+ *                   them have a posting for r.
+ *   RF_TEXT_PHRASE  terms: the phrase p_0 .. p_{m-1} in order, repeats allowed (min_match is not
+ *                   read).  Row r passes iff some position j has term p_i at position j + i of r for
+ *                   every i.  Needs the positions: for posting q (in post_row order), the ASCENDING
+ *                   token positions pos[pos_off[q] .. pos_off[q + 1]) of that term in that row
+ *                   (pos_off int64 [nnz + 1], pos uint32 [n_pos], caller-owned device memory, attached
+ *                   once by rf_sparse_attach_positions: host-checked, no device call).
+ * A term id outside [0, n_terms) has no postings.  leaves_host: n_leaves (1..RF_TEXT_MAX_LEAVES)
+ * leaves in HOST memory (they travel in the launch arguments); leaf l reads terms_dev[term_off ..
+ * term_off + n_terms), 1 <= n_terms <= RF_SPARSE_MAX_TERMS, inside [0, n_terms_total), and writes
+ * EVERY word of bitmaps_dev[l * words_per_leaf .. (l + 1) * words_per_leaf), words_per_leaf >=
+ * ceil(n_rows / 32); bits past n_rows are zero.  Stream-ordered, no host sync, no allocation;
+ * workspace_bytes >= rf_text_match_workspace_bytes(sp, n_leaves) (0 = n_leaves out of range).
+ * RF_ERR_INVALID before any device call: n_leaves, a leaf's kind, n_terms, term range or min_match
+ * (< 1) out of range, a PHRASE leaf on a handle without positions, a workspace that is too small, a
+ * NULL pointer, bitmaps_dev / workspace_dev not 16-byte aligned, terms_dev not 4-byte aligned.
+ * What runs: one small launch clamps every term's posting range and marks the repeats of a term;
+ * then grid (row tiles of RF_SPARSE_TILE_ROWS, leaves): a workgroup counts, per tile row in LDS, the
+ * leaf's distinct terms that hold the row (term after term with a barrier in between, rows within
+ * a term are distinct: no atomics on a counter), a PHRASE leaf then verifies adjacency for the rows
+ * that hold every term (binary searches in the position lists), and each wave ballots 64 rows into
+ * two words.  Integers only: the same bits on every run.  Offsets and rows are clamped as in
+ * rf_sparse_search: malformed postings give wrong bits, never an out-of-range access.
+ * New in this build; the reference filters on no text. */
+#define RF_TEXT_MATCH 1
+#define RF_TEXT_PHRASE 2
+#define RF_TEXT_MAX_LEAVES 16
+typedef struct rf_text_leaf {
+  int32_t kind;       /* RF_TEXT_MATCH | RF_TEXT_PHRASE */
+  int32_t term_off;   /* first entry in terms_dev */
+  int32_t n_terms;    /* 1..RF_SPARSE_MAX_TERMS */
+  int32_t min_match;  /* MATCH: >= 1; PHRASE: >= 1, not read */
+} rf_text_leaf;
+int rf_sparse_attach_positions(rf_sparse_t* sp, const int64_t* pos_off_dev, const uint32_t* pos_dev, int64_t n_pos);
+size_t rf_text_match_workspace_bytes(const rf_sparse_t* sp, int n_leaves);
+int rf_text_match(const rf_sparse_t* sp, const rf_text_leaf* leaves_host, int n_leaves, const int32_t* terms_dev,
+                  int64_t n_terms_total, uint32_t* bitmaps_dev, int64_t words_per_leaf, void* workspace_dev,
+                  size_t workspace_bytes, void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

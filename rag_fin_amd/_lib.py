@@ -22,6 +22,10 @@ RF_GROUP_MAX_CODES = 64   # dictionary size the fused grouped path serves (inclu
 RF_SPARSE_MAX_TERMS = 64     # distinct known terms of one query
 RF_SPARSE_TILE_ROWS = 8192   # rows a workgroup of the posting scan accumulates in LDS
 RF_FUSE_MAX_ARMS = 4         # answers rf_fuse_rrf fuses
+# keyword filters (include/ragfin.h, "keyword filters")
+RF_TEXT_MATCH = 1
+RF_TEXT_PHRASE = 2
+RF_TEXT_MAX_LEAVES = 16      # text leaves one rf_text_match call (one filter expression) holds
 
 
 class RagfinError(RuntimeError):
@@ -41,6 +45,7 @@ RF_FILTER_MAX_OPS = 64
 RF_FILTER_MAX_DEPTH = 32
 RF_FILTER_COLUMNS = 4
 RF_FOP_CODESET, RF_FOP_RANGE, RF_FOP_ROWLIST, RF_FOP_TRUE, RF_FOP_FALSE, RF_FOP_AND, RF_FOP_OR, RF_FOP_NOT = range(1, 9)
+RF_FOP_BITMAP = 9
 RF_FRANGE_LO_INCL = 1
 RF_FRANGE_HI_INCL = 2
 
@@ -48,6 +53,10 @@ RF_FRANGE_HI_INCL = 2
 class FilterOp(Structure):
     _fields_ = [("op", c_int32), ("column", c_int32), ("off", c_int32), ("len", c_int32),
                 ("flags", c_int32), ("pad", c_int32), ("lo", c_double), ("hi", c_double)]
+
+
+class TextLeaf(Structure):
+    _fields_ = [("kind", c_int32), ("term_off", c_int32), ("n_terms", c_int32), ("min_match", c_int32)]
 
 
 ENCODER_WEIGHT_FIELDS = ["word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b", "qkv_w",
@@ -93,6 +102,8 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_filter_bytes": (c_size_t, [c_int64]),
     "rf_filter_eval": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rf_filter_eval_bitmaps": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                       c_void_p]),
     "rf_filter_from_mask": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_search_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -118,6 +129,10 @@ SIGNATURES = {
     "rf_sparse_search_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "rf_sparse_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_sparse_attach_positions": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
+    "rf_text_match_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "rf_text_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
+                              c_void_p]),
     "rf_fuse_rrf": (c_int, [c_int, c_void_p, c_int, POINTER(c_double), c_double, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,

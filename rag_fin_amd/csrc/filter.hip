@@ -71,6 +71,7 @@ struct FilterProg {
   const double* value;         // primary_value
   const uint32_t* code_sets;
   const uint32_t* row_lists;
+  const uint32_t* bitmaps;
   uint32_t* mask;
   uint32_t* tile_cnt;          // [n_tiles][2] {non-empty blocks, passing rows}
   uint32_t n_rows, nblk, tile_words, n_ops;
@@ -115,6 +116,9 @@ __device__ __forceinline__ bool eval_row(const FilterProg& P, uint32_t row) {
         }
       }
       v = lo < (uint32_t)o.len && L[lo] == row;
+    } else if (op == RF_FOP_BITMAP) {
+      const uint32_t w = row >> 5;
+      v = w < (uint32_t)o.len && ((P.bitmaps[(uint32_t)o.off + w] >> (row & 31u)) & 1u) != 0u;
     } else {
       v = op == RF_FOP_TRUE;
     }
@@ -279,10 +283,9 @@ static int check_filter_buffer(const char* fn, int64_t n_rows, const void* filte
   return RF_OK;
 }
 
-extern "C" int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
-                              const uint32_t* row_lists_dev, const void* const* columns, int64_t n_rows,
-                              void* filter_dev, void* stream) {
-  static const char* fn = "rf_filter_eval";
+static int filter_eval(const char* fn, const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
+                       const uint32_t* row_lists_dev, const uint32_t* bitmaps_dev, const void* const* columns,
+                       int64_t n_rows, void* filter_dev, void* stream) {
   if (!ops || !columns) {
     rf_set_error("%s: null program or column table", fn);
     return RF_ERR_INVALID;
@@ -316,6 +319,14 @@ extern "C" int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t
       case RF_FOP_ROWLIST:
         if (o.off < 0 || o.len < 0 || (o.len > 0 && !row_lists_dev)) {
           rf_set_error("%s: op %d: bad row-list leaf (off %d, len %d)", fn, i, o.off, o.len);
+          return RF_ERR_INVALID;
+        }
+        ++depth;
+        break;
+      case RF_FOP_BITMAP:
+        if (o.off < 0 || o.len < 0 || !bitmaps_dev) {
+          rf_set_error("%s: op %d: bad bitmap leaf (off %d, len %d%s)", fn, i, o.off, o.len,
+                       bitmaps_dev ? "" : ", no bitmaps given");
           return RF_ERR_INVALID;
         }
         ++depth;
@@ -361,6 +372,7 @@ extern "C" int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t
   P.value = (const double*)columns[3];
   P.code_sets = code_sets_dev;
   P.row_lists = row_lists_dev;
+  P.bitmaps = bitmaps_dev;
   P.mask = (uint32_t*)(base + mo);
   P.tile_cnt = (uint32_t*)(base + to);
   P.n_rows = (uint32_t)n_rows;
@@ -372,6 +384,20 @@ extern "C" int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t
     RF_HIP(hipGetLastError());
   }
   return launch_compact(filter_dev, n_rows, tp, st);
+}
+
+extern "C" int rf_filter_eval(const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
+                              const uint32_t* row_lists_dev, const void* const* columns, int64_t n_rows,
+                              void* filter_dev, void* stream) {
+  return filter_eval("rf_filter_eval", ops, n_ops, code_sets_dev, row_lists_dev, nullptr, columns, n_rows, filter_dev,
+                     stream);
+}
+
+extern "C" int rf_filter_eval_bitmaps(const rf_filter_op* ops, int n_ops, const uint32_t* code_sets_dev,
+                                      const uint32_t* row_lists_dev, const uint32_t* bitmaps_dev,
+                                      const void* const* columns, int64_t n_rows, void* filter_dev, void* stream) {
+  return filter_eval("rf_filter_eval_bitmaps", ops, n_ops, code_sets_dev, row_lists_dev, bitmaps_dev, columns, n_rows,
+                     filter_dev, stream);
 }
 
 extern "C" int rf_filter_from_mask(const uint32_t* mask_dev, int64_t n_rows, void* filter_dev, void* stream) {

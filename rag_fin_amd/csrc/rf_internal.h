@@ -269,6 +269,19 @@ int rf_launch_mmr(const rf_index* ix, int B, int fetch_k, int k, double lambda, 
                   const double* cand_exact, const int64_t* cand_ids, float* scores, int64_t* ids,
                   double* exact, hipStream_t st);
 
+// sparse.hip, text_match.hip: the handle over the caller's posting arrays (include/ragfin.h, "lexical
+// search"), and the token positions of every posting once rf_sparse_attach_positions gave them
+struct rf_sparse {
+  int64_t n_rows, n_terms, nnz;
+  const int64_t* post_off;
+  const uint32_t* post_row;
+  const float* post_imp;
+  int device;
+  const int64_t* pos_off;   // [nnz + 1], nullptr while no positions are attached
+  const uint32_t* pos;      // [n_pos]
+  int64_t n_pos;
+};
+
 // order-preserving map float -> uint32 (larger float <=> larger uint)
 __host__ __device__ inline uint32_t rf_f2ord(float f) {
   uint32_t u = __builtin_bit_cast(uint32_t, f);

@@ -21,14 +21,6 @@ static_assert(RF_SPARSE_TILE_ROWS % SPARSE_THREADS == 0, "a thread owns whole st
 static_assert(RF_SPARSE_MAX_TERMS <= SPARSE_THREADS, "one lane per query term in the slice search");
 static_assert(RF_FUSE_MAX_ARMS * RF_MAX_K <= FUSE_THREADS, "one lane per fusion candidate");
 
-struct rf_sparse {
-  int64_t n_rows, n_terms, nnz;
-  const int64_t* post_off;
-  const uint32_t* post_row;
-  const float* post_imp;
-  int device;
-};
-
 // A hit as one word: larger key <=> (higher score, then lower row).  Scores of hits are positive
 // floats, whose bit patterns order as unsigned integers; 0 is "no hit".
 __device__ __forceinline__ unsigned long long sparse_key(float score, uint32_t row) {

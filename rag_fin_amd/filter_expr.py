@@ -12,6 +12,8 @@ Grammar (keywords case-insensitive; precedence not > and > or)::
     unary   := ("not" | "!") unary | "(" expr ")" | compare
     compare := FIELD CMP literal | literal CMP FIELD [CMP literal]
              | FIELD ["not"] "in" "[" [literal ("," literal)*] "]" | FIELD "like" STRING
+             | FUNC "(" "text" "," STRING ["," (NAME "=" NUM | NUM)] ")"
+    FUNC    := "TEXT_MATCH" | "PHRASE_MATCH"
 
 Fields and what they accept:
   period, chunk_type, statement_type (VARCHAR)  == != < <= > >= (code-point order), in / not in,
@@ -20,14 +22,28 @@ Fields and what they accept:
                                                 in / not in; IEEE semantics: NaN fails every
                                                 comparison except !=
   id (primary key)                              == != in / not in
+  text (VARCHAR with the lexical index)         TEXT_MATCH(text, 'terms' [, minimum_should_match=N]),
+                                                PHRASE_MATCH(text, 'a b c' [, slop=0]); nothing else
+Keyword filters (Milvus TEXT_MATCH / PHRASE_MATCH).  The terms of a string are those of
+the analyzer the caller gives `parse` (the store's), else `lexical.analyze`: punctuation characters
+are terms of their own, so 'Q1_FY2024' is the three terms q1, _, fy2024.
+  TEXT_MATCH    Q = the distinct terms of the string; a row passes iff it holds at least N of them
+                (N an integer >= 1, default 1 = OR).  N > |Q| and an empty Q pass no row; more than
+                64 distinct terms raise ValueError.
+  PHRASE_MATCH  p_0 .. p_{m-1} = the terms in order (repeats allowed, m <= 64); a row with the term
+                sequence d passes iff some j has d[j + i] == p_i for every i.  Only slop 0 (exact
+                adjacency) is offered; m = 0 passes no row.
+Both need the lexical index (create_index("sparse", ...)): compiling one without it raises ValueError.
 String literals take single or double quotes (backslash escapes the next character).  Anything
-else -- an unknown field, `text` or `embedding`, a type mismatch such as `period > 3` or
+else -- an unknown field, `embedding`, `text` outside the two functions, a type mismatch such as `period > 3` or
 `primary_value == "x"`, a syntax error -- raises ValueError naming the token and its position.
 
 Compilation.  A VARCHAR leaf is evaluated once against the column's dictionary (every distinct
 string, in first-seen order = its code) and becomes a set of codes, so a literal that is not in
 the dictionary matches nothing; numeric leaves become interval tests; id leaves become a sorted
-list of row numbers; and / or / not become stack operations.
+list of row numbers; a keyword leaf becomes the ids of its terms in the lexical index's dictionary
+(`Program.text_leaves`, which rf_text_match turns into a row bitmap) and an RF_FOP_BITMAP leaf that
+reads the bitmap; and / or / not become stack operations.
 """
 from __future__ import annotations
 
@@ -38,7 +54,7 @@ from typing import Any, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, lexical
 
 VARCHAR_FIELDS = ("period", "chunk_type", "statement_type")   # device columns 0, 1, 2
 DOUBLE_FIELDS = ("primary_value",)                             # device column 3
@@ -47,6 +63,10 @@ UNFILTERABLE = ("text", "embedding")
 COLUMN_OF = {"period": 0, "chunk_type": 1, "statement_type": 2, "primary_value": 3}
 
 _CMP = ("==", "!=", "<", "<=", ">", ">=")
+TEXT_FUNCS = ("text_match", "phrase_match")
+TEXT_FIELD = "text"
+NO_LEXICAL_INDEX = ("TEXT_MATCH / PHRASE_MATCH need the lexical index over the text column: call "
+                    "create_index('sparse', {'index_type': 'SPARSE_INVERTED_INDEX', 'metric_type': 'BM25'}) first")
 _FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<=", "==": "==", "!=": "!="}
 
 
@@ -68,7 +88,7 @@ _TOKEN = re.compile(r"""
     (?P<ws>\s+)
   | (?P<num>(?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?)
   | (?P<name>[A-Za-z_][A-Za-z0-9_]*)
-  | (?P<op>==|!=|<=|>=|&&|\|\||[<>()\[\],!+-])
+  | (?P<op>==|!=|<=|>=|&&|\|\||=|[<>()\[\],!+-])
 """, re.X)
 
 
@@ -150,6 +170,46 @@ class Like(Node):
         return like_match(row[self.field], self.pattern)
 
 
+def _terms_of(analyzer, text: str) -> list:
+    return list((analyzer or lexical.analyze)([text])[0])
+
+
+@dataclass
+class TextMatch(Node):
+    """TEXT_MATCH(text, query, minimum_should_match=min_match).  analyzer: list[str] -> list[list[str]],
+    None = lexical.analyze."""
+    field: str
+    query: str
+    min_match: int = 1
+    analyzer: Any = None
+
+    def terms(self) -> list:
+        """The distinct terms of the query, sorted."""
+        return sorted(set(_terms_of(self.analyzer, self.query)))
+
+    def eval(self, row):
+        return len(set(self.terms()) & set(_terms_of(self.analyzer, row[self.field]))) >= self.min_match
+
+
+@dataclass
+class PhraseMatch(Node):
+    """PHRASE_MATCH(text, query): the query's terms, adjacent and in order."""
+    field: str
+    query: str
+    slop: int = 0
+    analyzer: Any = None
+
+    def terms(self) -> list:
+        """The terms of the phrase in order."""
+        return _terms_of(self.analyzer, self.query)
+
+    def eval(self, row):
+        p = self.terms()
+        d = _terms_of(self.analyzer, row[self.field])
+        m = len(p)
+        return m > 0 and any(d[j:j + m] == p for j in range(len(d) - m + 1))
+
+
 @dataclass
 class And(Node):
     a: Node
@@ -205,9 +265,10 @@ def like_match(s: str, pattern: str) -> bool:
 
 # ---- parser ------------------------------------------------------------------------------------
 class _Parser:
-    def __init__(self, text: str):
+    def __init__(self, text: str, analyzer=None):
         self.toks = tokenize(text)
         self.i = 0
+        self.analyzer = analyzer
 
     def peek(self, k: int = 0) -> Tok:
         return self.toks[min(self.i + k, len(self.toks) - 1)]
@@ -306,6 +367,8 @@ class _Parser:
                 return left
             lit2, lt2 = self.literal()
             return And(left, self._leaf_cmp(name, ft, o2.value, lit2, lt2, o2))
+        if t.kind == "name" and t.value.lower() in TEXT_FUNCS and self.op("(", 1):
+            return self.text_func()
         name, ft = self.field()
         o = self.cmp_op()
         if o is not None:
@@ -329,6 +392,51 @@ class _Parser:
                 raise _err("'like' supports 'p%', '%s' and '%i%' only", pt)
             return Like(name, pt.value)
         raise _err("expected a comparison, 'in' or 'like'", self.peek())
+
+    def text_func(self) -> Node:
+        """The keyword leaf of the grammar: FUNC ( text , STRING [, NAME = NUM | , NUM] )."""
+        ft = self.take()
+        func = ft.value.upper()
+        phrase = func == "PHRASE_MATCH"
+        self.take()   # "("
+        t = self.take()
+        if t.kind != "name":
+            raise _err(f"{func} expects the field name first", t)
+        if t.value != TEXT_FIELD:
+            raise _err(f"{func} takes the field {TEXT_FIELD!r} only, not {t.value!r}", t)
+        if not self.op(","):
+            raise _err("expected ','", self.peek())
+        self.take()
+        st = self.take()
+        if st.kind != "str":
+            raise _err(f"{func} expects a string of terms", st)
+        option, arg = ("slop", 0) if phrase else ("minimum_should_match", 1)
+        if self.op(","):
+            self.take()
+            if self.peek().kind == "name":
+                nt = self.take()
+                if nt.value.lower() != option:
+                    raise _err(f"{func} takes the option {option} only", nt)
+                if not self.op("="):
+                    raise _err("expected '='", self.peek())
+                self.take()
+            vt = self.take()
+            if vt.kind != "num" or not isinstance(vt.value, int):
+                raise _err(f"{option} must be an integer" + ("" if phrase else " >= 1"), vt)
+            if phrase and vt.value != 0:
+                raise _err("PHRASE_MATCH offers exact adjacency only (slop 0)", vt)
+            if not phrase and vt.value < 1:
+                raise _err("minimum_should_match must be an integer >= 1", vt)
+            arg = vt.value
+        if not self.op(")"):
+            raise _err("expected ')'", self.peek())
+        self.take()
+        node = (PhraseMatch if phrase else TextMatch)(TEXT_FIELD, st.value, arg, self.analyzer)
+        n_terms = len(node.terms())
+        if n_terms > lexical.MAX_QUERY_TERMS:
+            raise _err(f"{func}: {n_terms} {'terms in the phrase' if phrase else 'distinct terms'}, at most "
+                       f"{lexical.MAX_QUERY_TERMS} are taken", st)
+        return node
 
     def _list(self, name: str, kt: Tok) -> list:
         if not self.op("["):
@@ -366,24 +474,40 @@ def _check_type(name: str, lit, tok: Tok):
     return lit   # id: int or str keys, as inserted
 
 
-def parse(text: str) -> Node:
+def parse(text: str, analyzer=None) -> Node:
+    """analyzer: what the keyword leaves analyse their strings with (None = lexical.analyze)."""
     if not isinstance(text, str):
         raise ValueError(f"filter expression must be a string, got {type(text).__name__}")
-    return _Parser(text).parse()
+    return _Parser(text, analyzer).parse()
+
+
+def text_leaves(node: Node) -> list:
+    """The TextMatch / PhraseMatch leaves of a tree, in evaluation order."""
+    if isinstance(node, (And, Or)):
+        return text_leaves(node.a) + text_leaves(node.b)
+    if isinstance(node, Not):
+        return text_leaves(node.a)
+    return [node] if isinstance(node, (TextMatch, PhraseMatch)) else []
 
 
 # ---- compilation -------------------------------------------------------------------------------
 @dataclass
 class Program:
     """The postfix program of rf_filter_eval: ops (tuples op, column, off, len, flags, lo, hi),
-    the code-set bitmap words and the sorted row lists the leaves point into."""
+    the code-set bitmap words and the sorted row lists the leaves point into.  text_leaves: the
+    keyword leaves as (kind RF_TEXT_*, term ids, min_match), the input of rf_text_match; the
+    RF_FOP_BITMAP op of leaf l carries l in `off`, and ops_ctypes turns it into the leaf's word range
+    once the caller knows how many words a leaf's bitmap has."""
     ops: list = field(default_factory=list)
     code_sets: list = field(default_factory=list)
     row_lists: list = field(default_factory=list)
+    text_leaves: list = field(default_factory=list)
 
-    def ops_ctypes(self):
+    def ops_ctypes(self, words_per_leaf: int = 0):
         arr = (_lib.FilterOp * len(self.ops))()
         for i, (op, col, off, ln, flags, lo, hi) in enumerate(self.ops):
+            if op == _lib.RF_FOP_BITMAP:
+                off, ln = off * words_per_leaf, words_per_leaf
             arr[i].op, arr[i].column, arr[i].off, arr[i].len = op, col, off, ln
             arr[i].flags, arr[i].lo, arr[i].hi = flags, lo, hi
         return arr
@@ -391,15 +515,16 @@ class Program:
     def max_depth(self) -> int:
         d = m = 0
         for o in self.ops:
-            d += 1 if o[0] <= _lib.RF_FOP_FALSE else (-1 if o[0] in (_lib.RF_FOP_AND, _lib.RF_FOP_OR) else 0)
+            d += 1 if o[0] <= _lib.RF_FOP_FALSE or o[0] == _lib.RF_FOP_BITMAP else (-1 if o[0] in (_lib.RF_FOP_AND, _lib.RF_FOP_OR) else 0)
             m = max(m, d)
         return m
 
 
 class _Compiler:
-    def __init__(self, dicts: dict[str, Sequence[str]], pk_row: dict):
+    def __init__(self, dicts: dict[str, Sequence[str]], pk_row: dict, term_id: dict | None = None):
         self.dicts = dicts
         self.pk_row = pk_row
+        self.term_id = term_id
         self.p = Program()
 
     def leaf(self, op, col=0, off=0, ln=0, flags=0, lo=0.0, hi=0.0):
@@ -413,12 +538,35 @@ class _Compiler:
         elif isinstance(n, Not):
             self.emit(n.a)
             self.leaf(_lib.RF_FOP_NOT)
+        elif isinstance(n, (TextMatch, PhraseMatch)):
+            self.text(n)
         elif n.field in VARCHAR_FIELDS:
             self.codeset(n)
         elif n.field in DOUBLE_FIELDS:
             self.numeric(n)
         else:
             self.pk(n)
+
+    def text(self, n: Node) -> None:
+        if self.term_id is None:
+            raise ValueError("filter expression: " + NO_LEXICAL_INDEX)
+        terms = n.terms()
+        ids = [self.term_id.get(t) for t in terms]
+        if isinstance(n, TextMatch):
+            # a term no row holds matches nothing: dropped; fewer than N left can never reach N
+            ids = sorted(i for i in ids if i is not None)
+            kind, need = _lib.RF_TEXT_MATCH, n.min_match
+            dead = len(ids) < need
+        else:
+            kind, need = _lib.RF_TEXT_PHRASE, 1
+            dead = not ids or any(i is None for i in ids)
+        if dead:
+            self.leaf(_lib.RF_FOP_FALSE)
+            return
+        if len(self.p.text_leaves) == _lib.RF_TEXT_MAX_LEAVES:
+            raise ValueError(f"filter expression: more than {_lib.RF_TEXT_MAX_LEAVES} TEXT_MATCH / PHRASE_MATCH leaves")
+        self.leaf(_lib.RF_FOP_BITMAP, 0, len(self.p.text_leaves))
+        self.p.text_leaves.append((kind, ids, need))
 
     def codeset(self, n: Node) -> None:
         d = self.dicts.get(n.field, ())
@@ -479,12 +627,14 @@ def _hashable(k) -> bool:
         return False
 
 
-def compile_expr(node: Node | str, dicts: dict[str, Sequence[str]], pk_row: dict) -> Program:
+def compile_expr(node: Node | str, dicts: dict[str, Sequence[str]], pk_row: dict,
+                 term_id: dict | None = None) -> Program:
     """AST (or expression text) -> Program.  dicts: VARCHAR field -> its dictionary (code i =
-    dicts[field][i]); pk_row: primary key -> row number."""
+    dicts[field][i]); pk_row: primary key -> row number; term_id: term -> id in the lexical index's
+    dictionary (`Postings.term_id`), None = no lexical index: a keyword leaf raises ValueError."""
     if isinstance(node, str):
         node = parse(node)
-    c = _Compiler(dicts, pk_row)
+    c = _Compiler(dicts, pk_row, term_id)
     c.emit(node)
     p = c.p
     if len(p.ops) > _lib.RF_FILTER_MAX_OPS:
@@ -493,6 +643,16 @@ def compile_expr(node: Node | str, dicts: dict[str, Sequence[str]], pk_row: dict
     if p.max_depth() > _lib.RF_FILTER_MAX_DEPTH:
         raise ValueError(f"filter expression: nests deeper than {_lib.RF_FILTER_MAX_DEPTH} operands")
     return p
+
+
+def text_leaf_arrays(p: Program):
+    """(rf_text_leaf array, the leaves' term ids int32 back to back) of p.text_leaves."""
+    arr = (_lib.TextLeaf * len(p.text_leaves))()
+    terms: list = []
+    for i, (kind, ids, need) in enumerate(p.text_leaves):
+        arr[i].kind, arr[i].term_off, arr[i].n_terms, arr[i].min_match = kind, len(terms), len(ids), need
+        terms.extend(ids)
+    return arr, np.asarray(terms, dtype=np.int32).reshape(-1)
 
 
 def program_arrays(p: Program) -> tuple[np.ndarray, np.ndarray]:

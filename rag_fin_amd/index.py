@@ -666,9 +666,11 @@ class SparseIndex:
     """Thin object wrapper over rf_sparse_* (include/ragfin.h, "lexical search"): the posting arrays
     of a `lexical.Postings` on the device, the handle over them and a search workspace.
 
-    Locking: as in GpuIndex, the workspace is shared by every caller, so `search` holds
-    `self._lock` while it sizes the workspace and enqueues; the results are the caller's own
-    tensors.  The postings are immutable: a changed corpus gets a new SparseIndex."""
+    Locking: as in GpuIndex, the workspaces are shared by every caller, so `search` and `text_match`
+    hold `self._lock` while they size a workspace and enqueue; the results are the caller's own
+    tensors.  The postings are immutable: a changed corpus gets a new SparseIndex.  The token
+    positions (`attach_positions`) are given once, by whoever needs a phrase first; the caller
+    serialises that against `text_match` (CorpusStore: under its `_sparse_lock`)."""
 
     def __init__(self, postings, device=None):
         torch = _torch()
@@ -687,6 +689,8 @@ class SparseIndex:
                                                  self.device.index))
         self.handle = handle
         self.workspace = None
+        self.text_workspace = None
+        self.positions = None   # (pos_off, pos) device tensors once attach_positions has run
         self._lock = threading.Lock()
 
     def __del__(self):
@@ -694,6 +698,40 @@ class SparseIndex:
         if h:
             self.lib.rf_sparse_destroy(h)
             self.handle = None
+
+    def attach_positions(self, pos_off, pos) -> None:
+        """rf_sparse_attach_positions: the pair of lexical.build_positions (host numpy), copied to the
+        device and kept alive with the handle.  PHRASE leaves of text_match need it."""
+        torch = _torch()
+        with torch.cuda.device(self.device):
+            off_d = torch.from_numpy(np.ascontiguousarray(pos_off, dtype=np.int64)).to(self.device)
+            pos_d = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.uint32).view(np.int32)).to(self.device)
+            _lib.check(self.lib.rf_sparse_attach_positions(self.handle, _ptr(off_d), _ptr(pos_d), pos_d.numel()))
+        self.positions = (off_d, pos_d)
+
+    def text_match(self, leaves):
+        """Enqueue rf_text_match on the current stream; no host sync.  leaves: (kind, term ids,
+        min_match) as in filter_expr.Program.text_leaves, 1..RF_TEXT_MAX_LEAVES of them.  -> the row
+        bitmaps, an int32 device tensor [L, words_per_leaf] of uint32 bit patterns: bit r & 31 of word
+        r >> 5 of row l = row r passes leaf l; words_per_leaf = ceil(n_rows / 32) rounded up to 4 (a
+        leaf's words start 16-byte aligned), every word written, bits past n_rows zero."""
+        torch = _torch()
+        prog = filter_expr.Program(text_leaves=list(leaves))
+        arr, terms = filter_expr.text_leaf_arrays(prog)
+        L = len(arr)
+        words = ((self.n_rows + 31) // 32 + 3) // 4 * 4
+        terms_d = torch.from_numpy(np.concatenate([terms, np.zeros(1, dtype=np.int32)])).to(self.device)
+        out = torch.empty((L, words), dtype=torch.int32, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            need = self.lib.rf_text_match_workspace_bytes(self.handle, L)
+            if need == 0:
+                raise ValueError(f"text_match: {L} leaves, need 1..{_lib.RF_TEXT_MAX_LEAVES}")
+            if self.text_workspace is None or self.text_workspace.numel() < need:
+                self.text_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rf_text_match(self.handle, arr, L, _ptr(terms_d), int(terms.size), _ptr(out), words,
+                                              _ptr(self.text_workspace), self.text_workspace.numel(),
+                                              _lib.current_stream_ptr()))
+        return out
 
     def search(self, q_off, q_term, q_weight, k: int, id_base: int = 0, filt=None, want_exact: bool = True):
         """Enqueue rf_sparse_search on the current stream; no host sync.  q_off int32 [B + 1], q_term
@@ -748,10 +786,12 @@ def fuse_rrf(arm_ids, k: int, weights=None, rrf_k: float = 60.0):
     return scores, ids, fused
 
 
-def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int):
+def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None):
     """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
     rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors
-    {period, chunk_type, statement_type codes int32 [n_rows], primary_value fp64 [n_rows]}."""
+    {period, chunk_type, statement_type codes int32 [n_rows], primary_value fp64 [n_rows]}.
+    bitmaps: SparseIndex.text_match(program.text_leaves), enqueued on the same stream, when the
+    program has keyword leaves (rf_filter_eval_bitmaps)."""
     torch = _torch()
     lib = _lib.load_library()
     cs, rl = filter_expr.program_arrays(program)
@@ -761,10 +801,10 @@ def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int):
         rl_d = torch.from_numpy(rl.view(np.int32)).to(device) if rl.size else None
         ptrs = (c_void_p * _lib.RF_FILTER_COLUMNS)(*[c_void_p(t.data_ptr()) if t is not None and t.numel() else None
                                                      for t in columns])
-        ops = program.ops_ctypes()
-        _lib.check(lib.rf_filter_eval(ops, len(ops), c_void_p(cs_d.data_ptr()) if cs_d is not None else None,
-                                      c_void_p(rl_d.data_ptr()) if rl_d is not None else None, ptrs, n_rows,
-                                      c_void_p(buf.data_ptr()), _lib.current_stream_ptr()))
+        ops = program.ops_ctypes(0 if bitmaps is None else int(bitmaps.shape[1]))
+        _lib.check(lib.rf_filter_eval_bitmaps(ops, len(ops), c_void_p(cs_d.data_ptr()) if cs_d is not None else None,
+                                              c_void_p(rl_d.data_ptr()) if rl_d is not None else None, _ptr(bitmaps),
+                                              ptrs, n_rows, c_void_p(buf.data_ptr()), _lib.current_stream_ptr()))
     # (cs_d / rl_d may be freed now: the caching allocator reuses their memory in stream order)
     return buf
 

@@ -19,6 +19,10 @@ Definition
   score     acc = 0.0f; for i = 1..m, if t_i in r: acc = acc + (w_i * imp[t_i, r]), the product and
             the sum each rounded to fp32.  A row is a hit iff it holds a query term (and passes the
             filter); ranking (score desc, row asc).
+  keyword   (TEXT_MATCH / PHRASE_MATCH filters) positions[q] = the ascending token
+            positions of posting q's term in its row (build_positions).  A MATCH leaf passes the rows
+            that hold at least min_match of its distinct terms; a PHRASE leaf p_0 .. p_{m-1} passes row
+            r iff some j has p_i at position j + i of r for every i (text_match_reference).
   fusion    fused(d) = sum over the arms a, in arm order, that hold d of weight_a / (rrf_k + rank_a(d)),
             rank 1-based, in fp64; the best k distinct ids by (fused desc, id asc).
 """
@@ -185,6 +189,73 @@ def encode_queries(postings: Postings, texts: Sequence[str], analyzer: Analyzer 
         off.append(len(terms))
     return (np.asarray(off, dtype=np.int32), np.asarray(terms, dtype=np.int32),
             np.asarray(weights, dtype=np.float32))
+
+
+def build_positions(postings: Postings, texts: Sequence[str], analyzer: Analyzer | None = None):
+    """Token positions of every posting -> (pos_off int64 [nnz + 1], pos uint32 [n_tokens]): posting q,
+    that is (term, row) in post_row order, owns pos[pos_off[q] : pos_off[q + 1]], the ascending
+    positions of the term in the row's term sequence.  texts / analyzer: what build_postings was given.
+    Only PHRASE_MATCH reads positions, so they are built apart from the postings, when first needed."""
+    docs = (analyzer or analyze)(list(texts))
+    n = len(docs)
+    if n != postings.n_rows:
+        raise ValueError(f"build_positions: {n} texts for postings over {postings.n_rows} rows")
+    dl = np.asarray([len(d) for d in docs], dtype=np.int64)
+    total = int(dl.sum())
+    flat = np.fromiter((postings.term_id[t] for d in docs for t in d), dtype=np.int64, count=total)
+    rows = np.repeat(np.arange(n, dtype=np.int64), dl)
+    starts = np.zeros(n, dtype=np.int64)
+    np.cumsum(dl[:-1], out=starts[1:])
+    position = np.arange(total, dtype=np.int64) - np.repeat(starts, dl)
+    keys = flat * max(n, 1) + rows
+    order = np.argsort(keys, kind="stable")   # (term, row), and within one the tokens stay in text order
+    _, counts = np.unique(keys, return_counts=True)
+    if counts.size != postings.nnz:
+        raise ValueError("build_positions: the texts do not give the postings' (term, row) pairs")
+    pos_off = np.zeros(postings.nnz + 1, dtype=np.int64)
+    np.cumsum(counts, out=pos_off[1:])
+    return pos_off, position[order].astype(np.uint32)
+
+
+def _term_slice(postings: Postings, t: int) -> tuple[int, int]:
+    if not 0 <= t < postings.n_terms:
+        return 0, 0
+    return int(postings.post_off[t]), int(postings.post_off[t + 1])
+
+
+def text_match_reference(postings: Postings, positions, leaves, n_rows: int) -> np.ndarray:
+    """The definition of rf_text_match in numpy -> uint32 [L, ceil(n_rows / 32)], bit r & 31 of word
+    r >> 5 = row r passes; bits past n_rows are zero.  leaves: (kind, term ids, min_match) as in
+    filter_expr.Program.text_leaves, kind 1 = MATCH (distinct ids), 2 = PHRASE (ids in phrase order);
+    an id outside the dictionary has no postings.  positions: build_positions' pair (None when no
+    leaf is a phrase).  For tests and tools only."""
+    words = (n_rows + 31) // 32
+    out = np.zeros((len(leaves), words), dtype=np.uint32)
+    for li, (kind, ids, min_match) in enumerate(leaves):
+        ids = [int(t) for t in ids]
+        count = np.zeros(n_rows, dtype=np.int64)
+        for t in sorted(set(ids)):
+            lo, hi = _term_slice(postings, t)
+            count[postings.post_row[lo:hi].astype(np.int64)] += 1
+        if kind == 1:
+            passing = count >= int(min_match)
+        else:
+            pos_off, pos = positions
+            starts = None   # (row << 32 | start position) of the occurrences of p_0 .. p_i found so far
+            for i, t in enumerate(ids):
+                lo, hi = _term_slice(postings, t)
+                rows = np.repeat(postings.post_row[lo:hi].astype(np.int64), np.diff(pos_off[lo:hi + 1]))
+                at = pos[int(pos_off[lo]):int(pos_off[hi])].astype(np.int64) if hi > lo else np.zeros(0, dtype=np.int64)
+                keep = at >= i
+                key = (rows[keep] << 32) | (at[keep] - i)
+                starts = key if starts is None else np.intersect1d(starts, key)
+            passing = np.zeros(n_rows, dtype=bool)
+            if starts is not None:
+                passing[np.unique(starts >> 32)] = True
+        bits = np.zeros(words * 32, dtype=np.uint8)
+        bits[:n_rows] = passing
+        out[li] = np.packbits(bits, bitorder="little").view(np.uint32)
+    return out
 
 
 def bm25_scores(postings: Postings, terms, weights, reverse: bool = False) -> np.ndarray:

@@ -299,6 +299,8 @@ class CorpusStore:
         # the text column by the first BM25 search after a change of the rows (None: to be built)
         self._sparse_params = None
         self._sparse = None
+        # (the token positions a PHRASE_MATCH filter needs live on that SparseIndex: attached once,
+        # by the first such filter, and gone with it on any mutation)
         self._sparse_lock = threading.Lock()
         self.analyzer = None                # list[str] -> list[list[str]]; None: lexical.analyze
 
@@ -537,7 +539,9 @@ class CorpusStore:
         n = self.num_entities
         if n == 0:
             with self._filter_lock:   # still reject a bad expression
-                filter_expr.compile_expr(filter_expr.parse(expr), {f: [] for f in filter_expr.VARCHAR_FIELDS}, {})
+                filter_expr.compile_expr(filter_expr.parse(expr, self.analyzer),
+                                         {f: [] for f in filter_expr.VARCHAR_FIELDS}, {},
+                                         None if self._sparse_params is None else {})
             return np.zeros(0, dtype=bool)
         return filter_mask_bits(self.build_filter(expr), n)
 
@@ -986,15 +990,41 @@ class CorpusStore:
     def build_filter(self, expr: str):
         """Parse + compile `expr` (rag_fin_amd.filter_expr; ValueError on a bad expression) and
         evaluate it on the device into a fresh filter buffer for this collection's rows.  One
-        buffer per call: concurrent searches with different filters do not share one."""
-        node = filter_expr.parse(expr)
+        buffer per call: concurrent searches with different filters do not share one.
+        TEXT_MATCH / PHRASE_MATCH leaves read the lexical index (create_index("sparse", ...) first:
+        ValueError without it): rf_text_match turns their posting lists into row bitmaps and the
+        filter program reads those, both on the current stream.  The first PHRASE_MATCH after a
+        change of the rows also builds the token positions (lexical.build_positions), once.
+
+        Lock order: the read/write lock (held by the caller: search, query and delete take it; delete
+        holds the WRITE side, so nothing here may ask for it again), then `_sparse_lock` (inside
+        _sparse_index and _text_index, released before the next), then `_filter_lock`, then the
+        SparseIndex's own `_lock` (inside text_match).  No path takes them the other way round."""
+        node = filter_expr.parse(expr, self.analyzer)
+        term_id, sp = self._text_index(filter_expr.text_leaves(node))
         with self._filter_lock:
             n = self.num_entities
             if self._dcols is None:
                 self._dcols = _DeviceColumns(self.index.device)
             self._dcols.sync(self.columns, n)
-            prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row)
-            return eval_filter(self.index.device, prog, self._dcols.tensors(), n)
+            prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row, term_id)
+            bitmaps = sp.text_match(prog.text_leaves) if prog.text_leaves else None
+            return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps)
+
+    def _text_index(self, leaves):
+        """What the keyword leaves of a filter need -> (term -> id map, SparseIndex), (None, None)
+        without such leaves.  No postings at all (no row holds a term): an empty map and no index,
+        so every leaf compiles to RF_FOP_FALSE."""
+        if not leaves:
+            return None, None
+        if self._sparse_params is None:
+            raise ValueError("filter expression: " + filter_expr.NO_LEXICAL_INDEX)
+        postings, sp = self._sparse_index()
+        if sp is not None and any(isinstance(n, filter_expr.PhraseMatch) for n in leaves):
+            with self._sparse_lock:
+                if sp.positions is None:
+                    sp.attach_positions(*lexical.build_positions(postings, self.columns["text"], self.analyzer))
+        return postings.term_id, sp
 
     def filter_rows(self, expr: str) -> np.ndarray:
         """Row numbers (ascending) that pass `expr`."""
