@@ -1,7 +1,7 @@
 """Filter expressions on the host: parser, AST semantics, compiled postfix program (CPU only).
 
-The compiled program is run by a numpy interpreter of the device program's semantics
-(include/ragfin.h, "filtered search") and compared with an evaluator written here, over random
+The compiled program is run by the numpy interpreter of the device program's semantics
+(oracle/filter_program.py; include/ragfin.h, "filtered search") and compared with an evaluator written here, over random
 expressions and random columns (duplicate strings, NaN, +-0.0, empty strings)."""
 import math
 
@@ -9,50 +9,13 @@ import numpy as np
 import pytest
 from hypothesis import given, settings, strategies as st
 
+from oracle.filter_program import run_program
 from rag_fin_amd import _lib, filter_expr as fe
 
 STRS = ["", "Q1_FY2024", "Q2_FY2024", "Q1", "a", "ab", "b", "key_ratios", "ratios_key", "Z"]
 NUMS = [0.0, -0.0, 1.0, -1.5, 2.5, 3.0, 1e6, float("nan"), float("inf"), float("-inf")]
 LITS = [0.0, 1.0, -1.5, 2.5, 3, -3, 1e6]
 VARCHAR = ["period", "chunk_type", "statement_type"]
-
-
-# ---- numpy interpreter of the postfix program ----------------------------------------------------
-def run_program(prog, codes, values, n):
-    """codes: {column index: int32 [n]}, values: fp64 [n].  Mirrors k_filter_eval."""
-    cs = np.asarray(prog.code_sets, dtype=np.uint32)
-    rl = np.asarray(prog.row_lists, dtype=np.uint32)
-    rows = np.arange(n, dtype=np.uint32)
-    stack = []
-    for op, col, off, ln, flags, lo, hi in prog.ops:
-        if op == _lib.RF_FOP_AND:
-            b, a = stack.pop(), stack.pop()
-            stack.append(a & b)
-        elif op == _lib.RF_FOP_OR:
-            b, a = stack.pop(), stack.pop()
-            stack.append(a | b)
-        elif op == _lib.RF_FOP_NOT:
-            stack.append(~stack.pop())
-        elif op == _lib.RF_FOP_CODESET:
-            c = codes[col].astype(np.int64)
-            ok = (c >= 0) & (c < 32 * ln)
-            w = cs[off + np.clip(c >> 5, 0, max(ln - 1, 0))] if ln else np.zeros(n, np.uint32)
-            stack.append(ok & (((w >> (c & 31).astype(np.uint32)) & 1) == 1))
-        elif op == _lib.RF_FOP_RANGE:
-            with np.errstate(invalid="ignore"):
-                a = values >= lo if flags & _lib.RF_FRANGE_LO_INCL else values > lo
-                b = values <= hi if flags & _lib.RF_FRANGE_HI_INCL else values < hi
-            stack.append(a & b)
-        elif op == _lib.RF_FOP_ROWLIST:
-            stack.append(np.isin(rows, rl[off:off + ln]))
-        elif op == _lib.RF_FOP_TRUE:
-            stack.append(np.ones(n, bool))
-        elif op == _lib.RF_FOP_FALSE:
-            stack.append(np.zeros(n, bool))
-        else:
-            raise AssertionError(op)
-    assert len(stack) == 1
-    return stack[0]
 
 
 def compile_on(table, expr):

@@ -137,6 +137,12 @@ def test_filter_abi_argument_checks():
     assert lib.rf_filter_bytes(-1) == 0 and lib.rf_filter_bytes(1 << 33) == 0
     assert lib.rf_filter_bytes(0) == 16 + 2 * 4 * 1024
     assert lib.rf_filter_bytes(1_000_000) == 16 + 2 * 125_008 + 2 * 4 * 1024   # two 31 250-word arrays, 16-byte aligned
+    # the sizes at which the tile plan changes regime (tests/test_filter_scale_gpu.py): header, two
+    # nblk-word arrays padded to 16 bytes, then {blocks, rows} counts of 1024 tiles whatever the plan is
+    for n in (1_048_576, 1_048_577, 8_388_641, 33_554_465):
+        nblk = (n + 31) // 32
+        assert lib.rf_filter_bytes(n) == 16 + 2 * ((4 * nblk + 15) // 16 * 16) + 2 * 4 * 1024
+    assert lib.rf_filter_bytes(1_048_577) == 16 + 2 * 131_088 + 8192 and lib.rf_filter_bytes(33_554_465) == 16 + 2 * 4_194_320 + 8192
     fake = ctypes.c_void_p(4096)    # never dereferenced: every case below fails its checks first
     cols = (ctypes.c_void_p * 4)(4096, 4096, 4096, 8192)
 
