@@ -271,6 +271,45 @@ int rf_search_exhaustive_range(const rf_index_t* ix, const void* filter_dev, con
                                const double* after_score_dev, const int64_t* after_id_dev,
                                float* scores_dev, int64_t* ids_dev, double* exact_dev,
                                void* workspace_dev, size_t workspace_bytes, void* stream);
+/* ---- paged search: Collection.search(..., offset=o) / Collection.search_iterator(...) -------------
+ * "The next k hits after hit X": per query b the best k rows by (fp64 contract score desc, row asc)
+ * among the rows that
+ *   - pass filter_dev (NULL: every row),
+ *   - lie in the band  radius < a <= range_filter  (-INFINITY / +INFINITY leave a side open; both
+ *     open: no band), decided on the fp64 score as in rf_search_range, and
+ *   - rank strictly AFTER the bound: a < after_score_dev[b], or a == after_score_dev[b] and
+ *     row + id_base > after_id_dev[b] -- the rule of rf_search_exhaustive_after.
+ * after_score_dev fp64 [B], after_id_dev int64 [B] (ids WITH the id base), device memory, read by
+ * the kernels in stream order (the previous page's last hit can feed them without a host sync).
+ * A bound score of +inf makes every row eligible (the answer of rf_search_range / rf_search); a
+ * bound (-inf, any id) makes none eligible: all padding (-inf / -1), flags 0.  A NaN bound gives
+ * an unspecified page (never an out-of-range access).
+ * Conventions of rf_search_range: stream-ordered, no host sync, no allocation, outputs may be
+ * pinned host memory, workspace rf_search_workspace_bytes, 64-query sweeps whatever B is (no wide
+ * sweep, no sample fold, no SQ8 form; for B > 64 each sweep reads its own 64 bounds), flags 0 =
+ * proven equal to the exact ranking of the eligible rows, non-zero (RF_FLAG_*) = answer that query
+ * through rf_search_exhaustive_range / _filtered / _after with the same filter, band and bound.
+ * More than 256 rows tied at the bound's score (within the sweep's error bound) raise
+ * RF_FLAG_TIE_OVERFLOW.
+ * RF_ERR_INVALID before any device call: a NULL bound array, radius >= range_filter or a NaN, k
+ * outside 1..RF_MAX_K, and the argument errors of rf_search.
+ * What runs: the band chain of rf_search_range with a per-query ceiling min(range_filter, bound
+ * score); the sample pass and the merge's k-th cut count only rows strictly below the bound score,
+ * and the merge drops every rescored row at or before the bound by the fp64 (score, id) rule
+ * (DESIGN 4.4i).  A page costs one sweep of the corpus whatever its depth.
+ * rf_search_after_profile: the first sweep alone with HIP events around its stages (4 floats:
+ * sample, threshold, emit, merge; synchronises).
+ * New in this build; the reference pages through Milvus (offset / search_iterator). */
+int rf_search_after(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                    int64_t id_base, double radius, double range_filter,
+                    const double* after_score_dev, const int64_t* after_id_dev,
+                    float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+int rf_search_after_profile(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                            int64_t id_base, double radius, double range_filter,
+                            const double* after_score_dev, const int64_t* after_id_dev,
+                            float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                            void* workspace_dev, size_t workspace_bytes, void* stream, float* stage_ms_host);
 /* ---- grouping search: Collection.search(..., group_by_field=f, group_size=s) -----------------------
  * The best n_groups GROUPS instead of the best k rows: a group is the set of rows that share a
  * code (the caller's int32 dictionary code of the group-by field, one per row), its rows are ranked

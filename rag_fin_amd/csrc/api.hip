@@ -234,11 +234,15 @@ static int for_chunks(const rf_index_t* ix, const void* q_dev, int B, int k, siz
 // pass clips at the ceiling by the eps a pre-kernel writes, the threshold has the floor of the
 // band under it, the emit clips at the ceiling and the merge drops what the fp64 scores put
 // outside the band.
+// after: search-after (always with band, both sides open when the caller gave none): the band
+// chain with the ceiling of each query read from its bound in device memory; the merge also drops
+// what the fp64 (score, id) rule puts at or before the bound.
 struct rf_variant {
   const rf_filter_view* filt;
   const rf_sq8_ws* sq8;
   bool wide;
   const rf_band* band;
+  const rf_after* after;
 };
 
 static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
@@ -279,16 +283,16 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS && v.band) rc = rf_launch_band_eps(ix, qc, nb, ws, st);
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
     rc = v.wide ? rf_launch_wide_sample(ix, qc, nb, ws, &P, st)
-                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band);
+                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band, v.after);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK)
     rc = v.wide  ? rf_launch_wide_emit(ix, qc, nb, ws, st)
          : v.sq8 ? rf_launch_sq8_emit(ix, nb, JB, ws, *v.sq8, st)
-                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band);
+                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band, v.after);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
-  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band);
+  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band, v.after);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   return rc;
 }
@@ -299,7 +303,8 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
 // to gain from).
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, const rf_out& o,
                           void* workspace_dev, hipStream_t st, const rf_filter_view* filt, bool sq8,
-                          float* stage_ms = nullptr, const rf_band* band = nullptr) {
+                          float* stage_ms = nullptr, const rf_band* band = nullptr,
+                          const rf_after* after = nullptr) {
   if (ix->size == 0) return fill_empty(B, k, o, st);
   rf_arena a{(unsigned char*)workspace_dev, 0};
   rf_workspace ws;
@@ -308,13 +313,15 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
   const bool widen = !filt && !sq && !band;
   if (!stage_ms)
     return for_chunks(ix, q_dev, B, k, (size_t)k, widen, o,
-                      [&](int, int nb, bool wide, const _Float16* qc, const rf_out& oc) {
-                        return sweep(ix, rf_variant{filt, sq, wide, band}, qc, nb, k, id_base, ws, oc, st, nullptr);
+                      [&](int q0, int nb, bool wide, const _Float16* qc, const rf_out& oc) {
+                        const rf_after ac{after ? after->score + q0 : nullptr, after ? after->id + q0 : nullptr};
+                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr}, qc, nb, k, id_base, ws,
+                                     oc, st, nullptr);
                       });
   bool wide;
   const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
   return time_stages(sq ? 6 : 5, stage_ms, [&](hipEvent_t* ev) {
-    return sweep(ix, rf_variant{filt, sq, wide, band}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
+    return sweep(ix, rf_variant{filt, sq, wide, band, after}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
   });
 }
 
@@ -506,6 +513,53 @@ extern "C" int rf_search_exhaustive_range(const rf_index_t* ix, const void* filt
   return exhaustive_impl("rf_search_exhaustive_range", ix, q_dev, B, k, id_base, scores_dev, ids_dev, exact_dev,
                          after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream,
                          filter_dev ? f.mask : nullptr, &band);
+}
+
+// ---- paged search (include/ragfin.h, "paged search") ----------------------------------------------
+static int search_after_impl(const char* fn, const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B,
+                             int k, int64_t id_base, double radius, double range_filter,
+                             const double* after_score_dev, const int64_t* after_id_dev, const rf_out& o,
+                             void* workspace_dev, size_t workspace_bytes, void* stream, float* stage_ms) {
+  if (!after_score_dev || !after_id_dev) {
+    rf_set_error("%s: null bound arrays", fn);
+    return RF_ERR_INVALID;
+  }
+  if (k > RF_MAX_K) {   // (no larger sweep exists to be "unsupported" here: a page is at most RF_MAX_K hits)
+    rf_set_error("%s: k = %d outside 1..%d", fn, k, RF_MAX_K);
+    return RF_ERR_INVALID;
+  }
+  int rc = check_search_args(fn, ix, q_dev, B, k, o.scores, o.ids, workspace_dev, workspace_bytes);
+  if (rc == RF_OK) rc = check_band(fn, radius, range_filter);
+  if (rc == RF_OK && filter_dev) rc = check_filter_arg(fn, filter_dev);
+  if (rc != RF_OK) return rc;
+  const rf_band band{radius, range_filter};
+  const rf_after after{after_score_dev, after_id_dev};
+  const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix->size) : rf_filter_view{};
+  return search_enqueue(ix, q_dev, B, k, id_base, o, workspace_dev, (hipStream_t)stream, filter_dev ? &f : nullptr,
+                        false, stage_ms, &band, &after);
+}
+
+extern "C" int rf_search_after(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                               int64_t id_base, double radius, double range_filter, const double* after_score_dev,
+                               const int64_t* after_id_dev, float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                               uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return search_after_impl("rf_search_after", ix, filter_dev, q_dev, B, k, id_base, radius, range_filter,
+                           after_score_dev, after_id_dev, rf_out{scores_dev, ids_dev, exact_dev, flags_dev},
+                           workspace_dev, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int rf_search_after_profile(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,
+                                       int64_t id_base, double radius, double range_filter,
+                                       const double* after_score_dev, const int64_t* after_id_dev, float* scores_dev,
+                                       int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev, void* workspace_dev,
+                                       size_t workspace_bytes, void* stream, float* stage_ms_host) {
+  if (!stage_ms_host || !ix || ix->size == 0) {
+    rf_set_error("rf_search_after_profile: null stage buffer, null or empty index");
+    return RF_ERR_INVALID;
+  }
+  return search_after_impl("rf_search_after_profile", ix, filter_dev, q_dev, B, k, id_base, radius, range_filter,
+                           after_score_dev, after_id_dev, rf_out{scores_dev, ids_dev, exact_dev, flags_dev},
+                           workspace_dev, workspace_bytes, stream, stage_ms_host);
 }
 
 // ---- grouping search (include/ragfin.h, "grouping search") ----------------------------------------

@@ -287,14 +287,19 @@ static size_t merge_lds_bytes(int dim) {
 // them: no cut), R keeps everything at or above the cut -- the fringe (hi - eps, hi + eps]
 // included --, and after the fp64 chains every row of R with a > hi or a <= lo is dropped before
 // the ranking.
-template <bool BAND>
-__global__ void __launch_bounds__(MERGE_THREADS) k_merge(
-    const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
+// AFTER (search-after, always with BAND): the ceiling of the k-th selection is the
+// strict per-query one (rf_after_ceiling: a key at or below it is eligible whatever its row), and a
+// row of R also leaves unless it ranks strictly after the bound (after_s[qi], after_r[qi]) by the
+// fp64 (score, id) rule.
+template <bool BAND, bool AFTER>
+__device__ __forceinline__ void merge_body(
+    unsigned char* lds, const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
     int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
     uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
     int64_t* __restrict__ ids, double* __restrict__ exact, uint32_t* __restrict__ flags,
-    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt, rf_band bd) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt, rf_band bd,
+    const double* __restrict__ after_s, const int64_t* __restrict__ after_r) {
+  static_assert(!AFTER || BAND, "a search-after merge is a band merge");
   unsigned long long* skeys = (unsigned long long*)lds;                       // [1024]
   unsigned long long* wtop = skeys + MERGE_RANK_MAX;                          // [4][RF_MAX_K]
   double* r_exact = (double*)(wtop + (MERGE_THREADS / 64) * RF_MAX_K);        // [RESCORE_CAP]
@@ -318,7 +323,11 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   bool have_cut = kk > 0 && (uint32_t)k <= c;  // fewer than k candidates: rescore all
   const float eps2 = 2.f * eps_in[qi];
   // BAND: a key takes part in the k-th selection only if its score is <= hs
-  const float hs = BAND ? rf_band_floor(bd.hi - (double)eps_in[qi]) : INFINITY;
+  const double bound_s = AFTER ? after_s[qi] : 0.0;
+  const int64_t bound_r = AFTER ? after_r[qi] - id_base : 0;
+  const float hs = AFTER  ? rf_band_floor(rf_after_ceiling(bd.hi, bound_s, true) - (double)eps_in[qi])
+                   : BAND ? rf_band_floor(bd.hi - (double)eps_in[qi])
+                          : INFINITY;
   if (tid == 0) {
     *r_cnt = 0u;
     *t_cut = -INFINITY;
@@ -458,7 +467,7 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
     uint32_t mine = 0u;
     for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
       const double s = r_exact[i];
-      if (s > bd.lo && s <= bd.hi) ++mine;
+      if (s > bd.lo && s <= bd.hi && (!AFTER || ranks_before(bound_s, bound_r, s, (int64_t)r_row[i]))) ++mine;
       else r_exact[i] = -INFINITY;
     }
     if (mine) atomicAdd(n_band, mine);
@@ -491,6 +500,31 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge(
   // above); k_threshold zeroes them again at the start of every search, so a search never
   // depends on what an earlier one -- or an error return mid-pipeline -- left behind
   if (tid < RF_CAND_SHARDS && !keep_cnt) cand_cnt_rw[qi * RF_CAND_SHARDS + tid] = 0u;
+}
+
+template <bool BAND>
+__global__ void __launch_bounds__(MERGE_THREADS) k_merge(
+    const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
+    int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
+    uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
+    int64_t* __restrict__ ids, double* __restrict__ exact, uint32_t* __restrict__ flags,
+    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt, rf_band bd) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  merge_body<BAND, false>(lds, q, dim, KS, tiles, k, id_base, cand_cnt, cand, cap, eps_in, scores, ids, exact, flags,
+                          cand_cnt_rw, n_rows, keep_cnt, bd, nullptr, nullptr);
+}
+
+// (a kernel of its own, so that the arguments of the other two stay what they are)
+__global__ void __launch_bounds__(MERGE_THREADS) k_merge_after(
+    const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
+    int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
+    uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
+    int64_t* __restrict__ ids, double* __restrict__ exact, uint32_t* __restrict__ flags,
+    uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, rf_band bd,
+    const double* __restrict__ after_s, const int64_t* __restrict__ after_r) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  merge_body<true, true>(lds, q, dim, KS, tiles, k, id_base, cand_cnt, cand, cap, eps_in, scores, ids, exact, flags,
+                         cand_cnt_rw, n_rows, 0, bd, after_s, after_r);
 }
 // ---- exhaustive exact path ----------------------------------------------------------
 // Workgroup-level running top-k list (sorted, in LDS) updated 256 entries at a
@@ -774,10 +808,16 @@ int rf_launch_band_eps(const rf_index* ix, const void* q, int B, const rf_worksp
 
 int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                     const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
-                    uint32_t* flags, hipStream_t st, const rf_band* band) {
+                    uint32_t* flags, hipStream_t st, const rf_band* band, const rf_after* after) {
   const size_t lds = merge_lds_bytes(ix->dim);
-  static rf_lds_attr lds_attr, lds_attr_band;
-  if (band) {
+  static rf_lds_attr lds_attr, lds_attr_band, lds_attr_after;
+  if (band && after) {
+    RF_HIP(rf_ensure_lds(lds_attr_after, (const void*)k_merge_after, lds));
+    hipLaunchKernelGGL(k_merge_after, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim,
+                       ix->KS, ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP,
+                       ws.eps, scores, ids, exact, flags, ws.cand_cnt, (uint32_t)ix->size, *band,
+                       after->score, after->id);
+  } else if (band) {
     RF_HIP(rf_ensure_lds(lds_attr_band, (const void*)k_merge<true>, lds));
     hipLaunchKernelGGL(k_merge<true>, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim,
                        ix->KS, ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP,

@@ -178,16 +178,24 @@ struct rf_fold {
 struct rf_band {
   double lo, hi;
 };
+// Search-after (include/ragfin.h, "paged search"): per query of the batch, the (fp64 score, id) of
+// the hit the page follows, in device memory.  A sweep with a bound is a band sweep (rf_band, both
+// sides open without a band of the caller's) whose ceiling is per query: rf_after_ceiling below.
+struct rf_after {
+  const double* score;   // [B]
+  const int64_t* id;     // [B], with the id base
+};
 // scan.hip (filt: nullptr = every row; otherwise the masked sweep over the filter's blocks)
 // band: nullptr = no band; otherwise the band form of the sweep (never with a fold)
+// after: nullptr = no bound; otherwise the search-after form (always with a band)
 // fold: rf_launch_sample fills it (the fold is off for a filtered sweep and with the knob off);
 // rf_launch_threshold and rf_launch_emit take what it filled, nullptr = no fold
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr,
-                     rf_fold* fold = nullptr, const rf_band* band = nullptr);
+                     rf_fold* fold = nullptr, const rf_band* band = nullptr, const rf_after* after = nullptr);
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                    hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr,
-                   const rf_band* band = nullptr);
+                   const rf_band* band = nullptr, const rf_after* after = nullptr);
 // Shape of the 64-query sweeps (scan.hip, grouped.hip): waves per workgroup by dim, and the emit
 // grid = CUs x workgroups per CU (0 = the default of the dim), at most one wave per 32-row block.
 static inline int rf_waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
@@ -230,7 +238,8 @@ int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
 int rf_launch_band_eps(const rf_index* ix, const void* q, int B, const rf_workspace& ws, hipStream_t st);
 int rf_launch_merge(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                     const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
-                    uint32_t* flags, hipStream_t st, const rf_band* band = nullptr);
+                    uint32_t* flags, hipStream_t st, const rf_band* band = nullptr,
+                    const rf_after* after = nullptr);
 int rf_launch_exhaustive(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
                          const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                          const double* after_s, const int64_t* after_r, hipStream_t st,
@@ -301,4 +310,22 @@ __host__ __device__ inline float rf_band_floor(double x) {
 __host__ __device__ inline float rf_band_ceil(double x) {
   const float f = (float)x;
   return (double)f < x ? rf_ord2f(rf_f2ord(f) + 1u) : f;
+}
+
+// Search-after: the largest double below x (+-inf and a NaN pass through).
+__host__ __device__ inline double rf_next_below(double x) {
+  if (!(x > -INFINITY && x < INFINITY)) return x;
+  uint64_t u = __builtin_bit_cast(uint64_t, x);
+  if (x > 0.0) u -= 1u;
+  else if (x == 0.0) u = 0x8000000000000001ull;   // below +-0: the negative subnormal
+  else u += 1u;
+  return __builtin_bit_cast(double, u);
+}
+// The fp64 ceiling of a query whose page follows a hit of score `after` inside a band up to hi.
+// Plain: min(hi, after) -- no eligible row scores above it.  strict: a row at or below it is
+// eligible whatever its id, i.e. it scores strictly below the bound when the bound is the tighter
+// (or an equal) side.  A NaN bound leaves hi (the merge's (score, id) rule then drops every row).
+__host__ __device__ inline double rf_after_ceiling(double hi, double after, bool strict) {
+  if (!(after <= hi)) return hi;
+  return strict ? rf_next_below(after) : after;
 }

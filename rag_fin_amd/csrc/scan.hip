@@ -126,9 +126,12 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
 
 // FILTER (filtered search, p is a ScanParamsF): the work items are the filter's pass blocks
 // (sample pass: every bstride-th of them), counted on the device; see scan_common.h.
-template <int KS, int R, int JB, int WAVES, int MODE, bool FILTER, bool BAND, class PT>
+// AFTER (search-after, always with BAND): the ceiling is per query, from the bound's score in
+// device memory (rf_after_ceiling); everything after the set-up of tc is the band sweep.
+template <int KS, int R, int JB, int WAVES, int MODE, bool FILTER, bool BAND, bool AFTER, class PT>
 __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   static_assert(!BAND || MODE != MODE_FOLD, "the band sweep has no sample fold");
+  static_assert(!AFTER || BAND, "a search-after sweep is a band sweep");
   u32x4* smemQ = (u32x4*)smem_raw;                                   // JB*KS*64 uint4
   unsigned char* tail = smem_raw + (size_t)JB * KS * RF_FRAG_BYTES;  // per-mode scratch
 
@@ -145,8 +148,13 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
 #pragma unroll
   for (int jb = 0; jb < JB; ++jb) {
     if (BAND) {
-      const double e = (double)p.eps[jb * 32 + (lane & 31)];
-      tc[jb] = (MODE == MODE_EMIT) ? rf_band_ceil(p.band_hi + e) : rf_band_floor(p.band_hi - e);
+      const int ql = jb * 32 + (lane & 31);
+      const double e = (double)p.eps[ql];
+      double hi = p.band_hi;
+      if constexpr (AFTER) {
+        if (ql < p.B) hi = rf_after_ceiling(hi, p.after_s[ql], MODE != MODE_EMIT);  // (slots past B have no bound)
+      }
+      tc[jb] = (MODE == MODE_EMIT) ? rf_band_ceil(hi + e) : rf_band_floor(hi - e);
     } else {
       tc[jb] = INFINITY;
     }
@@ -327,13 +335,26 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
 template <int KS, int R, int JB, int WAVES, int MODE, bool BAND = false>
 __global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  scan_body<KS, R, JB, WAVES, MODE, false, BAND>(p, smem_raw);
+  scan_body<KS, R, JB, WAVES, MODE, false, BAND, false>(p, smem_raw);
 }
 
 template <int KS, int R, int JB, int WAVES, int MODE, bool BAND = false>
 __global__ void __launch_bounds__(WAVES * 64, 2) k_scan_filtered(ScanParamsF p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  scan_body<KS, R, JB, WAVES, MODE, true, BAND>(p, smem_raw);
+  scan_body<KS, R, JB, WAVES, MODE, true, BAND, false>(p, smem_raw);
+}
+
+// The search-after sweeps: the band sweeps above with the per-query ceiling.
+template <int KS, int R, int JB, int WAVES, int MODE>
+__global__ void __launch_bounds__(WAVES * 64, 2) k_scan_after(ScanParamsA p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  scan_body<KS, R, JB, WAVES, MODE, false, true, true>(p, smem_raw);
+}
+
+template <int KS, int R, int JB, int WAVES, int MODE>
+__global__ void __launch_bounds__(WAVES * 64, 2) k_scan_filtered_after(ScanParamsFA p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  scan_body<KS, R, JB, WAVES, MODE, true, true, true>(p, smem_raw);
 }
 
 // ---- raw score dump (test hook) ---------------------------------------------
@@ -372,6 +393,8 @@ static int launch_scan(const PT& p, int grid, hipStream_t st) {
   else lds += (size_t)WAVES * 2 * JB * 32 * 4;
   auto kern = [] {
     if constexpr (std::is_same<PT, ScanParamsF>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE, BAND>;
+    else if constexpr (std::is_same<PT, ScanParamsFA>::value) return k_scan_filtered_after<KS, R, JB, WAVES, MODE>;
+    else if constexpr (std::is_same<PT, ScanParamsA>::value) return k_scan_after<KS, R, JB, WAVES, MODE>;
     else return k_scan<KS, R, JB, WAVES, MODE, BAND>;
   }();
   static rf_lds_attr attr;  // per instantiation, per device
@@ -392,6 +415,7 @@ static int launch_scan_jb(int JB, const PT& p, int grid, hipStream_t st) {
   case ks:                          \
     return launch_scan_jb<ks, r, waves, MODE, BAND>(JB, p, grid, st);
 
+// (PT = ScanParamsA / ScanParamsFA: the search-after kernels, BAND = true)
 template <int MODE, bool BAND = false, class PT>
 static int dispatch_scan(int KS, int JB, const PT& p, int grid4, int grid8,
                          hipStream_t st) {
@@ -443,7 +467,7 @@ int rf_scan_supported_dim(int dim) {
 
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold,
-                     const rf_band* band) {
+                     const rf_band* band, const rf_after* after) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = rf_waves_per_wg(KS);
@@ -489,8 +513,20 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
     f.n_blocks = nblk;
     f.work_lo = lo;
     f.work_hi = hi;
+    if (band && after) {
+      ScanParamsFA fa{};
+      static_cast<ScanParamsF&>(fa) = f;
+      fa.after_s = after->score;
+      return dispatch_scan<MODE_SAMPLE, true>(KS, JB, fa, grid, grid, st);
+    }
     return band ? dispatch_scan<MODE_SAMPLE, true>(KS, JB, f, grid, grid, st)
                 : dispatch_scan<MODE_SAMPLE>(KS, JB, f, grid, grid, st);
+  }
+  if (band && after) {
+    ScanParamsA pa{};
+    static_cast<ScanParams&>(pa) = p;
+    pa.after_s = after->score;
+    return dispatch_scan<MODE_SAMPLE, true>(KS, JB, pa, grid, grid, st);
   }
   if (band) return dispatch_scan<MODE_SAMPLE, true>(KS, JB, p, grid, grid, st);
   if (fold && rf_knob_sample_fold && B <= RF_QCHUNK && n_work <= (uint32_t)RF_FOLD_BLOCKS &&
@@ -505,7 +541,8 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
 }
 
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
-                   hipStream_t st, const rf_filter_view* filt, const rf_fold* fold, const rf_band* band) {
+                   hipStream_t st, const rf_filter_view* filt, const rf_fold* fold, const rf_band* band,
+                   const rf_after* after) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int grid = rf_emit_grid(ix, rf_knob_emit_wgs_per_cu);
@@ -542,8 +579,20 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
     f.mask = filt->mask;
     f.blocks = filt->blocks;
     f.n_blocks = nblk;
+    if (band && after) {
+      ScanParamsFA fa{};
+      static_cast<ScanParamsF&>(fa) = f;
+      fa.after_s = after->score;
+      return dispatch_scan<MODE_EMIT, true>(KS, JB, fa, grid, grid, st);
+    }
     return band ? dispatch_scan<MODE_EMIT, true>(KS, JB, f, grid, grid, st)
                 : dispatch_scan<MODE_EMIT>(KS, JB, f, grid, grid, st);
+  }
+  if (band && after) {
+    ScanParamsA pa{};
+    static_cast<ScanParams&>(pa) = p;
+    pa.after_s = after->score;
+    return dispatch_scan<MODE_EMIT, true>(KS, JB, pa, grid, grid, st);
   }
   return band ? dispatch_scan<MODE_EMIT, true>(KS, JB, p, grid, grid, st)
               : dispatch_scan<MODE_EMIT>(KS, JB, p, grid, grid, st);

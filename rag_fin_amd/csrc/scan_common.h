@@ -52,6 +52,17 @@ struct ScanParamsF : ScanParams {
   uint32_t work_lo, work_hi;  // sample pass: bounds of the sampled block count (n_work is unused)
 };
 
+// Search-after (k_scan_after / k_scan_filtered_after, always the band form): the fp64 score of each
+// query's bound.  The ceiling of query b is rf_after_ceiling(band_hi, after_s[b], ...) instead of
+// band_hi: min(hi, bound) in the emit, the strict one in the sample pass.  Types of
+// their own, so that the arguments of the other sweeps stay what they are.
+struct ScanParamsA : ScanParams {
+  const double* after_s;   // [B]
+};
+struct ScanParamsFA : ScanParamsF {
+  const double* after_s;   // [B]
+};
+
 #ifndef RF_RING24
 #define RF_RING24 24
 #endif

@@ -491,33 +491,124 @@ class GpuIndex:
         with self._lock:
             return self._exhaustive(q16, k, id_base, want_exact, filt, band=band)
 
+    def search_after_raw(self, q16, k: int, after, id_base: int = 0, want_exact: bool = False, out=None,
+                         workspace=None, stream_ptr=None, filt=None, band=None):
+        """Enqueue rf_search_after (include/ragfin.h, "paged search"); no host sync, no lock (as
+        search_raw).  after: (fp64 scores [B], int64 ids [B]) device tensors -- per query the best k
+        hits ranked strictly after that (score, id), within filt / band when given.  Returns
+        (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B])."""
+        torch = _torch()
+        if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
+            raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
+        if not q16.is_contiguous() or q16.device != self.device:
+            q16 = q16.to(self.device).contiguous()
+        B = q16.shape[0]
+        bs, bi = after
+        if not torch.is_tensor(bs) or not torch.is_tensor(bi) or bs.dtype != torch.float64 or \
+                bi.dtype != torch.int64 or tuple(bs.shape) != (B,) or tuple(bi.shape) != (B,):
+            raise ValueError(f"search_after expects the bound as (float64 [{B}], int64 [{B}]) tensors")
+        bs, bi = bs.to(self.device).contiguous(), bi.to(self.device).contiguous()
+        lo, hi = (float("-inf"), float("inf")) if band is None else (float(band[0]), float(band[1]))
+        scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_search_after(
+                self.handle, _ptr(filt), _ptr(q16), B, k, id_base, lo, hi, _ptr(bs), _ptr(bi), _ptr(scores), _ptr(ids),
+                _ptr(exact), _ptr(flags), _ptr(workspace if workspace is not None else self.workspace),
+                self.workspace_bytes, stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+        return scores, ids, exact, flags
+
+    def search_after_profile(self, q16, k: int, after, filt=None, band=None):
+        """rf_search_after_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
+        lo, hi = (float("-inf"), float("inf")) if band is None else (float(band[0]), float(band[1]))
+        B = min(q16.shape[0], _lib.RF_QCHUNK)
+        bs, bi = after[0][:B].contiguous(), after[1][:B].contiguous()
+        torch = _torch()
+        q16 = q16.to(self.device).contiguous()
+        scores, ids, _, flags = self._outputs(B, k)
+        ms = (ctypes.c_float * 4)()
+        with self._lock, torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_search_after_profile(
+                self.handle, _ptr(filt), _ptr(q16), B, k, 0, lo, hi, _ptr(bs), _ptr(bi), _ptr(scores), _ptr(ids), None,
+                _ptr(flags), _ptr(self.workspace), self.workspace_bytes, _lib.current_stream_ptr(), ms))
+        return dict(zip(("sample", "threshold", "emit", "merge"), ms))
+
+    def _search_after(self, q16, k: int, after, id_base: int, want_exact: bool, filt, band):
+        """search_after_raw, then the flagged queries again through the exhaustive kernel with the
+        same filter, band and bound -> ((scores, ids, exact),).  The caller holds the lock."""
+        torch = _torch()
+        scores, ids, exact, flags = self.search_after_raw(q16, k, after, id_base, want_exact, filt=filt, band=band)
+        bad = torch.nonzero(flags != 0).flatten()
+        if bad.numel() > 0:
+            q16 = q16.to(self.device)
+            rows = self._exhaustive(q16[bad].contiguous(), k, id_base, want_exact, filt,
+                                    after=(after[0].to(self.device)[bad].contiguous(),
+                                           after[1].to(self.device)[bad].contiguous()), band=band)
+            for dst, src in zip((scores, ids, exact), rows):
+                if dst is not None:
+                    dst[bad] = src
+        return ((scores, ids, exact),)
+
+    def search_after(self, q16, k: int, after, id_base: int = 0, want_exact: bool = False, filt=None, band=None):
+        """The best k (<= RF_MAX_K) hits per query ranked strictly after the bound `after` = (fp64
+        scores [B], int64 ids [B], device tensors; ids with id_base): one sweep of the corpus
+        through rf_search_after whatever the depth, then the flagged-query ladder (a flagged query
+        through _exhaustive(..., after=...)).  filt: over the passing rows.  band: (radius,
+        range_filter), within the band.  A bound score of +inf is the first page; (-inf, any id)
+        gives all padding.  -> (scores, ids, exact | None) on the device."""
+        with self._lock:
+            return self._search_after(q16, k, after, id_base, want_exact, filt, band)[0]
+
+    PAGES_PER_SYNC = 16   # search_large: pages enqueued back to back before their flags are read
+
+    @staticmethod
+    def _bound_after(exact, ids):
+        """The bound of the next page: the last hit of this one; a query whose page is not full is
+        exhausted and keeps a bound nothing can follow.  Device tensors, no sync."""
+        torch = _torch()
+        last_s, last_i = exact[:, -1], ids[:, -1]
+        return (torch.where(last_i >= 0, last_s, torch.full_like(last_s, float("-inf"))).contiguous(),
+                torch.where(last_i >= 0, last_i, torch.full_like(last_i, 2 ** 62)).contiguous())
+
     def search_large(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, band=None):
-        """Limits above RF_MAX_K: the first page through the fused path, further pages
-        of RF_MAX_K through the exhaustive kernel with a bound (each page = the hits ranked
-        strictly after the previous page's last hit).  Returns (scores, ids) [B, k]
-        (+ the fp64 ranking scores with want_exact: what a cross-shard merge ranks by).
-        filt: the same over the passing rows.  band: (radius, range_filter) -- the same within the
-        band: the first page through rf_search_range, later pages through the exhaustive band
-        kernel; the walk ends with the first page that the band does not fill."""
+        """Limits above RF_MAX_K: the first page through the fused path, further pages of RF_MAX_K
+        through the search-after sweep (rf_search_after: each page = the hits ranked strictly after
+        the previous page's last hit, one sweep of the corpus per page whatever its depth).  The
+        pages are enqueued back to back, PAGES_PER_SYNC at a time, each bound taken from the page
+        before on the device; their flags are read with one synchronisation, and from the first
+        page that holds a flagged query on, the pages are walked again one by one through the
+        ladder (search_after: the flagged queries through the exhaustive kernel with the same
+        bound).  Returns (scores, ids) [B, k] (+ the fp64 ranking scores with want_exact: what a
+        cross-shard merge ranks by).  filt: the same over the passing rows.  band: (radius,
+        range_filter) -- the same within the band, the first page through rf_search_range.  The
+        walk ends with the first group of pages whose last one no query fills."""
         torch = _torch()
         q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
         page = _lib.RF_MAX_K
-        s0, i0, e0 = self.search(q16, page, id_base, want_exact=True, filt=filt, band=band)
-        scores, ids, exacts = [s0], [i0], [e0]
-        last_s, last_i = e0[:, -1].contiguous(), i0[:, -1].contiguous()
+        pages = [self.search(q16, page, id_base, want_exact=True, filt=filt, band=band)]
         got = page
-        while got < k and bool((last_i >= 0).any()):
-            # exhausted queries keep a bound nothing can follow
-            bs = torch.where(last_i >= 0, last_s, torch.full_like(last_s, float("-inf")))
-            bi = torch.where(last_i >= 0, last_i, torch.full_like(last_i, 2 ** 62))
+        more = bool((pages[0][1][:, -1] >= 0).any()) if got < k else False
+        while got < k and more:
+            n_pages = min(self.PAGES_PER_SYNC, -(-(k - got) // page))
             with self._lock:
-                s, i, e = self._exhaustive(q16, page, id_base, True, filt, after=(bs, bi), band=band)
-            scores.append(s)
-            ids.append(i)
-            exacts.append(e)
-            last_s, last_i = e[:, -1].contiguous(), i[:, -1].contiguous()
-            got += page
+                flags = []
+                for _ in range(n_pages):
+                    bound = self._bound_after(pages[-1][2], pages[-1][1])
+                    *res, f = self.search_after_raw(q16, page, bound, id_base, True, filt=filt, band=band)
+                    pages.append(tuple(res))
+                    flags.append(f)
+                state = torch.cat([(torch.stack(flags) != 0).any(1), (pages[-1][1][:, -1] >= 0).any().reshape(1)]).cpu()
+                bad = torch.nonzero(state[:-1]).flatten()
+                more = bool(state[-1])
+                if bad.numel() > 0:   # unproven from page j of the group on: those again, through the ladder
+                    j = int(bad[0])
+                    del pages[len(pages) - n_pages + j:]
+                    for _ in range(j, n_pages):
+                        bound = self._bound_after(pages[-1][2], pages[-1][1])
+                        pages.append(self._search_after(q16, page, bound, id_base, True, filt, band)[0])
+                    more = bool((pages[-1][1][:, -1] >= 0).any())
+            got += n_pages * page
+        scores, ids, exacts = ([p[j] for p in pages] for j in range(3))
         if got < k:   # corpus exhausted before k hits: pad like rf_search does
             scores.append(torch.full((B, k - got), float("-inf"), dtype=torch.float32, device=self.device))
             ids.append(torch.full((B, k - got), -1, dtype=torch.int64, device=self.device))

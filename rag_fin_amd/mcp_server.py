@@ -58,7 +58,7 @@ def _searcher():
 def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                    mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
-                   hybrid: bool = False):
+                   hybrid: bool = False, offset: int | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -72,7 +72,9 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     hybrid: optional lexical arm -- the semantic search and a BM25 search of the chunk texts run at
     fetch_k each and are fused by reciprocal rank; `score` is then the fused score.  With filter and
     rerank; not with min_score / max_score, group_by or mmr_lambda.  Needs the store's lexical index
-    (LEXICAL_INDEX=1 at ingest)."""
+    (LEXICAL_INDEX=1 at ingest).
+    offset: optional paging -- skip that many of the best chunks, return the next top_k.  With filter and
+    min_score / max_score; not with rerank, hybrid, mmr_lambda or group_by."""
     try:
         # (only what was given travels on; diversified, reranked and hybrid calls bypass the micro-batcher as well)
         mmr = {name: v for name, v in (("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k)) if v is not None}
@@ -80,6 +82,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
             mmr["rerank"] = True
         if hybrid:
             mmr["hybrid"] = True
+        if offset is not None:   # (a paged call bypasses the micro-batcher too: one batch shares one offset)
+            mmr["offset"] = offset
         if group_by is not None:
             # grouped calls bypass the micro-batcher like filtered ones: one batch shares one grouping
             kw = {"group_by": group_by, "group_size": group_size}

@@ -79,7 +79,7 @@ class VectorRAG:
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
-               hybrid: bool = False) -> list[dict]:
+               hybrid: bool = False, offset: int | None = None) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -98,7 +98,11 @@ class VectorRAG:
         (same default), their lists are fused by reciprocal rank (RRF, k = 60) and the best top_k are
         kept; `score` is the fused score.  With expr (both arms) and with rerank (the cross-encoder
         scores the fused candidates); not with min_score / max_score, group_by or mmr_lambda
-        (ValueError)."""
+        (ValueError).
+        offset: skip that many of the best chunks first -- the chunks of ranks offset + 1 ...
+        offset + top_k (`rank` counts from 1 within the page); with expr and min_score / max_score,
+        not with rerank, hybrid, mmr_lambda or group_by (ValueError)."""
+        self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if rerank:
@@ -110,7 +114,7 @@ class VectorRAG:
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
                                          **self._group_args(group_by, group_size),
-                                         **self._mmr_args(mmr_lambda, fetch_k))
+                                         **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset))
         return self._contexts(results[0])
 
     def _embed(self, texts):
@@ -119,6 +123,17 @@ class VectorRAG:
         with, so the download / re-upload / re-normalise round trip of the numpy form is skipped."""
         to_dev = getattr(self.similarity_model, "encode_to_device", None)
         return to_dev(texts) if to_dev is not None else self.similarity_model.encode(texts)
+
+    @staticmethod
+    def _offset_args(offset) -> dict:
+        """The store's offset argument; nothing when it was not given (the call of before)."""
+        return {} if offset is None else {"offset": offset}
+
+    @staticmethod
+    def _check_offset(offset, rerank, hybrid, mmr_lambda, group_by) -> None:
+        if offset is not None and (rerank or hybrid or mmr_lambda is not None or group_by is not None):
+            raise ValueError("offset pages through the plain ranking: it does not combine with rerank, hybrid, "
+                             "mmr_lambda or group_by")
 
     @staticmethod
     def _default_fetch_k(top_k: int) -> int:
@@ -184,12 +199,14 @@ class VectorRAG:
                      min_score: float | None = None, max_score: float | None = None,
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
-                     rerank: bool = False, hybrid: bool = False) -> list[list[dict]]:
+                     rerank: bool = False, hybrid: bool = False, offset: int | None = None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
         the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call; hybrid:
-        dense + BM25 fused by reciprocal rank for every query, as in search()."""
+        dense + BM25 fused by reciprocal rank for every query, as in search(); offset: one for the
+        whole batch, as in search()."""
+        self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if not queries:
@@ -203,7 +220,7 @@ class VectorRAG:
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
                                          **self._group_args(group_by, group_size),
-                                         **self._mmr_args(mmr_lambda, fetch_k))
+                                         **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset))
         return [self._contexts(r) for r in results]
 
     # -- generation (out of scope; interface kept) -----------------------------------------

@@ -30,7 +30,7 @@ import threading
 
 from . import _lib, filter_expr
 from .sharded import HipShardBackend, ShardedSearcher
-from .store import CorpusStore, MutationResult, _id_in_keys
+from .store import CorpusStore, MutationResult, _id_in_keys, check_offset
 
 
 logger = logging.getLogger(__name__)
@@ -277,7 +277,10 @@ class ShardedCorpusStore(CorpusStore):
     # -- filters: not over shards (yet) -----------------------------------------------------------------
     def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
                output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False,
-               mmr_lambda=None, mmr_fetch_k=None):
+               mmr_lambda=None, mmr_fetch_k=None, offset=None):
+        if check_offset(offset, param, limit):
+            # (a page past the first 64 hits needs the search-after sweep on every shard and a merge per page)
+            raise NotImplementedError("paged search (offset) is not implemented for the sharded store")
         if anns_field == "sparse":
             # (the texts are replicated, but no rank holds posting lists)
             raise NotImplementedError("BM25 search (anns_field='sparse') is not implemented for the sharded store")
@@ -291,6 +294,9 @@ class ShardedCorpusStore(CorpusStore):
         if self._band_of(param) is not None:
             raise NotImplementedError("range search (radius / range_filter) is not implemented for the sharded store")
         return super().search(data, anns_field, param, limit, expr, output_fields)
+
+    def search_iterator(self, *args, **kwargs):
+        raise NotImplementedError("paged search (search_iterator) is not implemented for the sharded store")
 
     def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields=None):
         raise NotImplementedError("hybrid search (hybrid_search) is not implemented for the sharded store")

@@ -76,6 +76,26 @@ def check_band(radius, range_filter=None):
 MMR_MAX_FETCH_K = _lib.RF_MAX_K
 
 
+MAX_WINDOW = 16384   # Milvus' result window: offset + limit at most this
+
+
+def check_offset(offset, param, limit) -> int:
+    """The offset of a pymilvus-shaped search: the keyword, else param["offset"], else 0.  An int
+    >= 0 (no bool), and with an offset the window offset + limit <= MAX_WINDOW; else ValueError."""
+    if offset is None and isinstance(param, dict):
+        offset = param.get("offset")
+    if offset is None:
+        return 0
+    if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or offset < 0:
+        raise ValueError(f"offset must be an integer >= 0, got {offset!r}")
+    offset = int(offset)
+    if offset and (isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1
+                   or offset + limit > MAX_WINDOW):
+        raise ValueError(f"offset + limit must be an integer window of at most {MAX_WINDOW} "
+                         f"(got offset = {offset}, limit = {limit!r})")
+    return offset
+
+
 def check_mmr(mmr_lambda, mmr_fetch_k, limit: int):
     """Diversified-search arguments -> (fetch_k, lambda), or None when neither is given.  lambda
     weighs relevance against redundancy (1 = the plain ranking, 0 = diversity only after the best
@@ -270,6 +290,90 @@ class Hit:
         return f"Hit(id={self.id!r}, score={self.score:.6f})"
 
 
+class SearchIterator:
+    """What CorpusStore.search_iterator returns."""
+
+    def __init__(self, store, data, anns_field, param, batch_size, limit, expr, output_fields):
+        torch = _torch()
+        if anns_field != "embedding":
+            raise ValueError(f"search_iterator: unknown vector field {anns_field!r} (only 'embedding')")
+        if store._is_text(data):
+            raise ValueError("the embedding field is searched with vectors, not with strings")
+        metric = str((param or {}).get("metric_type", store.metric_type)).upper()
+        if metric != store.metric_type:
+            raise ValueError(f"collection was built for {store.metric_type}, search asked for {metric}")
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or \
+                not 1 <= batch_size <= MAX_WINDOW:
+            raise ValueError(f"batch_size must be an integer in 1..{MAX_WINDOW}, got {batch_size!r}")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or (limit < 1 and limit != -1):
+            raise ValueError(f"limit must be an integer >= 1, or -1 for no limit, got {limit!r}")
+        if check_offset(None, param, 1):
+            raise ValueError("search_iterator takes no offset")
+        self._fields = store._check_output_fields(output_fields)
+        self._store = store
+        self._batch = int(batch_size)
+        self._left = None if limit == -1 else int(limit)
+        self._kw = {}
+        with store._rw.read():
+            q16 = store._prepare_queries(data)
+            if q16.shape[0] != 1:
+                raise ValueError(f"search_iterator takes one query vector, got {q16.shape[0]}")
+            self._q16 = q16
+            if not filter_expr.is_empty(expr):
+                self._kw["filt"] = store.build_filter(expr)   # once, for every page
+            band = store._band_of(param)
+            if band is not None:
+                self._kw["band"] = band
+            self._gen = store._mutations
+            dev = q16.device
+            # the bound: (fp64 score, row) of the last hit handed out; +inf = before the first
+            self._bound = (torch.full((1,), float("inf"), dtype=torch.float64, device=dev),
+                           torch.full((1,), -1, dtype=torch.int64, device=dev))
+        self._done = False
+
+    def next(self) -> list:
+        torch = _torch()
+        if self._done:
+            return []
+        store = self._store
+        with store._rw.read():
+            if store._mutations != self._gen:
+                raise RuntimeError("search_iterator: the collection changed (insert / delete / upsert / drop) since "
+                                   "the iterator was made; its position is a row number and no longer valid")
+            want = self._batch if self._left is None else min(self._batch, self._left)
+            scores, rows = [], []
+            while want > 0 and not self._done and store.num_entities > 0:
+                k = min(want, _lib.RF_MAX_K)
+                s, i, e = store.index.search_after(self._q16, k, self._bound, want_exact=True, **self._kw)
+                last = i[:, -1]
+                # (the new bound stays on the device; an exhausted query keeps one nothing can follow)
+                self._bound = (torch.where(last >= 0, e[:, -1], torch.full_like(e[:, -1], float("-inf"))).contiguous(),
+                               torch.where(last >= 0, last, torch.full_like(last, 2 ** 62)).contiguous())
+                packed = torch.stack([i[0], s[0].double().view(torch.int64)]).cpu().numpy()   # the page's download
+                r = packed[0]
+                n = int((r >= 0).sum())
+                rows.append(r[:n])
+                scores.append(packed[1].view(np.float64)[:n])
+                want -= n
+                if n < k:
+                    self._done = True
+            if store.num_entities == 0:
+                self._done = True
+            if not rows:
+                self._done = True
+                return []
+            rows, scores = np.concatenate(rows), np.concatenate(scores)
+            if self._left is not None:
+                self._left -= rows.size
+                if self._left <= 0:
+                    self._done = True
+            return store._hits(rows, scores, self._fields)
+
+    def close(self) -> None:
+        self._done = True
+        self._kw = {}
+
+
 _ID_IN = re.compile(r"^\s*id\s+in\s+\[(.*)\]\s*$", re.S)
 
 
@@ -302,6 +406,9 @@ class CorpusStore:
         # (the token positions a PHRASE_MATCH filter needs live on that SparseIndex: attached once,
         # by the first such filter, and gone with it on any mutation)
         self._sparse_lock = threading.Lock()
+        # bumped by every change of the rows (insert, delete, upsert, drop): a search_iterator's
+        # bound is a row number, so it refuses to go on once this has moved
+        self._mutations = 0
         self.analyzer = None                # list[str] -> list[list[str]]; None: lexical.analyze
 
     # -- pymilvus-shaped lifecycle ---------------------------------------------
@@ -317,6 +424,7 @@ class CorpusStore:
     def drop(self) -> None:
         """utility.drop_collection + recreate ("chunking_storing (1).py":25-28)."""
         with self._rw.write():
+            self._mutations += 1
             self.index.reset()
             for col in self.columns.values():
                 col.clear()
@@ -482,6 +590,7 @@ class CorpusStore:
         """The host side of an append: the pk map and the six scalar columns."""
         texts, periods, chunk_types, statement_types, primary_values = cols
         self._sparse = None   # the lexical index is rebuilt by the next BM25 search
+        self._mutations += 1
         base = self.num_entities
         for j, pk in enumerate(ids):
             self._pk_row[pk] = base + j
@@ -562,6 +671,7 @@ class CorpusStore:
         keep = np.flatnonzero(keep_mask)
         n_old = self.num_entities
         self._sparse = None   # the lexical index is rebuilt by the next BM25 search
+        self._mutations += 1
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
         for f in SCALAR_FIELDS:
@@ -640,8 +750,16 @@ class CorpusStore:
     def search(self, data, anns_field: str = "embedding", param: dict | None = None,
                limit: int = 3, expr=None, output_fields: Iterable[str] | None = None,
                group_by_field: str | None = None, group_size: int = 1, strict_group_size: bool = False,
-               mmr_lambda=None, mmr_fetch_k=None):
+               mmr_lambda=None, mmr_fetch_k=None, offset: int | None = None):
         """pymilvus-shaped search: one list of hits per query vector, best first.
+        offset (or param["offset"], as pymilvus accepts it; the keyword wins when both are given): the
+        hits of ranks offset + 1 ... offset + limit, i.e. search(limit=offset + limit)[offset:].  An
+        int >= 0 with offset + limit <= 16384 (Milvus' window), else ValueError.  With expr, range
+        parameters and on an SQ8 collection (whose hits past rank 64 come from the fp16 rows, as for
+        any limit above 64): the first 64 ranks through the fused path, every further 64 through one
+        search-after sweep of the corpus (GpuIndex.search_large).  Not with group_by_field,
+        mmr_lambda, anns_field="sparse" or inside hybrid_search (ValueError).  To walk a long result
+        list page by page without searching from the top each time, see search_iterator.
         group_by_field ("period", "chunk_type", "statement_type"; "id" is the plain search): the best
         `limit` GROUPS of rows sharing that field's value, each by its best min(group_size, rows of
         the group) rows.  One flat hit list per query: group after group in group rank order (a
@@ -668,6 +786,10 @@ class CorpusStore:
         may be shorter than limit, or empty.  Exact and bit-reproducible.  No range,
         grouping or MMR arguments (ValueError); vectors for "sparse" or strings for "embedding"
         raise ValueError too.  To combine the two fields see hybrid_search."""
+        offset = check_offset(offset, param, limit)
+        if offset and (anns_field == "sparse" or group_by_field is not None or mmr_lambda is not None
+                       or mmr_fetch_k is not None):
+            raise ValueError("offset has no BM25 (anns_field='sparse'), grouping (group_by_field) or MMR (mmr_lambda) form")
         if anns_field == "sparse":
             if group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
                 raise ValueError("BM25 search (anns_field='sparse') has no grouping and no MMR form")
@@ -680,7 +802,7 @@ class CorpusStore:
             raise ValueError("diversified search (mmr_lambda) cannot be combined with group_by_field")
         with self._rw.read():   # the rows handed back are marshalled below: no delete in between
             if group_by_field is None:
-                return self._search(data, anns_field, param, limit, expr, output_fields, mmr=mmr)
+                return self._search(data, anns_field, param, limit, expr, output_fields, mmr=mmr, offset=offset)
             return self._search(data, anns_field, param, limit, expr, output_fields,
                                 self._check_group_by(group_by_field, group_size, limit, param))
 
@@ -820,6 +942,8 @@ class CorpusStore:
                         raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
                     if self._band_of(r.param) is not None:
                         raise ValueError("hybrid_search: an arm takes no range parameters (radius / range_filter)")
+                    if check_offset(None, r.param, r.limit):
+                        raise ValueError("hybrid_search: an arm takes no offset")
                     q = self._prepare_queries(r.data)
                     prepared.append((r, q, int(q.shape[0])))
                 else:
@@ -848,7 +972,7 @@ class CorpusStore:
             rows, fused = packed[0], packed[1].view(np.float64)
             return [self._hits(rows[b], fused[b], fields) for b in range(B)]
 
-    def _search(self, data, anns_field, param, limit, expr, output_fields, group=None, mmr=None):
+    def _search(self, data, anns_field, param, limit, expr, output_fields, group=None, mmr=None, offset: int = 0):
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         if self._is_text(data):
@@ -871,13 +995,13 @@ class CorpusStore:
             if group[0] not in fields:
                 fields = fields + [group[0]]
         elif filter_expr.is_empty(expr):
-            scores, rows = self.search_rows(data, limit, **kw)
+            scores, rows = self.search_rows(data, offset + limit, **kw)
         else:
-            scores, rows = self.search_rows(data, limit, filt=self.build_filter(expr), **kw)
+            scores, rows = self.search_rows(data, offset + limit, filt=self.build_filter(expr), **kw)
         out = []
         for b in range(rows.shape[0]):
             hits = []
-            for j in range(rows.shape[1]):
+            for j in range(offset, rows.shape[1]):
                 r = int(rows[b, j])
                 if r < 0:
                     if group is not None:
@@ -887,6 +1011,19 @@ class CorpusStore:
                                 {f: self.columns[f][r] for f in fields}))
             out.append(hits)
         return out
+
+    def search_iterator(self, data, anns_field: str = "embedding", param: dict | None = None,
+                        batch_size: int = 1000, limit: int = -1, expr=None,
+                        output_fields: Iterable[str] | None = None):
+        """pymilvus-shaped search_iterator: an object with next() -> the next batch_size hits (a list
+        of Hit, [] when done) and close().  ONE query vector (ValueError for more, as pymilvus).
+        The pages concatenated are search(limit=N): the iterator keeps the last hit's fp64 score and
+        row on the device, and a next() costs ceil(batch_size / 64) search-after sweeps of the corpus
+        (GpuIndex.search_after), not a search from the top.  expr: the filter buffer is built once.
+        param["params"] may hold radius / range_filter.  limit: hits in all (-1: until the collection
+        is exhausted).  The bound is a row number: an insert, delete, upsert or drop between two
+        next() calls makes the next one raise RuntimeError."""
+        return SearchIterator(self, data, anns_field, param, batch_size, limit, expr, output_fields)
 
     @staticmethod
     def _band_of(param):
@@ -1032,14 +1169,16 @@ class CorpusStore:
 
     # -- scalar queries ----------------------------------------------------------------
     def query(self, expr: str = "", limit: int | None = None,
-              output_fields: Iterable[str] | None = None) -> list[dict]:
+              output_fields: Iterable[str] | None = None, offset: int = 0) -> list[dict]:
         """`query(expr="id in [...]")` fetch-by-PK (key order), `query(expr="", limit=n)` scan, and
         any other filter expression (rag_fin_amd.filter_expr): the matching rows in ascending
-        row order."""
+        row order.  offset (an int >= 0, else ValueError): skip that many of the matching rows
+        first, on the host; `limit` counts from there."""
+        offset = check_offset(offset, None, 1)
         with self._rw.read():
-            return self._query(expr, limit, output_fields)
+            return self._query(expr, limit, output_fields, offset)
 
-    def _query(self, expr, limit, output_fields) -> list[dict]:
+    def _query(self, expr, limit, output_fields, offset: int = 0) -> list[dict]:
         fields = list(output_fields or ["id"])
         want_vec = "embedding" in fields
         fields = [f for f in fields if f != "embedding"]
@@ -1054,6 +1193,8 @@ class CorpusStore:
                 rows = [self._pk_row[k] for k in keys if k in self._pk_row]
             else:
                 rows = self._expr_rows(expr).tolist()
+        if offset:
+            rows = rows[offset:]
         if limit is not None:
             rows = rows[:limit]
         vecs = self.index.get_rows(np.asarray(rows, dtype=np.int64)).float().cpu().numpy() \
