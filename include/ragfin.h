@@ -238,6 +238,45 @@ int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* filter_dev, 
                                   const int64_t* after_id_dev, float* scores_dev, int64_t* ids_dev,
                                   double* exact_dev, void* workspace_dev, size_t workspace_bytes,
                                   void* stream);
+/* ---- per-query filters: one sweep for a batch whose queries differ in expr ---------------------
+ * rf_search_filtered takes one filter for the whole batch.  Here every query of the batch has a
+ * filter of its own, one of G <= RF_MULTI_MAX_FILTERS filter buffers built for the same n_rows, and
+ * the batch still costs one sweep: over the blocks of the UNION of the G filters, each query
+ * testing rows against its own filter's bits.  Query b's answer is rf_search_filtered's with filter
+ * qfilter[b], bit for bit (ids, fp64 scores, fp32 scores); same flag contract, per query.
+ *
+ * Multi-filter buffer (caller-owned device memory, rf_multi_filter_bytes(n_rows, G) bytes, 16-byte
+ * aligned; 0 for an n_rows or G out of range):
+ *   the filter buffer of the union (OR of the G masks): header, mask, ascending block list and
+ *   compaction scratch exactly as above, so the buffer can be read, or searched, as that filter
+ *   then, from the next 256-byte boundary: uint32 masks[nblk][Gp], Gp = G rounded up to a power
+ *   of two -- word [b][g] is mask word b of filter g (block-major: the words a sweep needs for one
+ *   block lie side by side); the padding columns are zero
+ * rf_multi_filter_build: filters is a HOST array of G device pointers (copied into the launch's
+ * arguments: the call captures into a hipGraph).  A filter whose header was built for another row
+ * count contributes no row.  Deterministic as the filter buffer is: no output depends on the order
+ * of atomics, and every byte of the buffer is defined (what the build has no value for -- the block
+ * list past its count, unused scratch, the alignment gap -- is zero), so equal filters give equal
+ * buffers byte for byte.  RF_ERR_INVALID before any device call for a NULL array or entry, G outside
+ * 1..RF_MULTI_MAX_FILTERS, a misaligned buffer or n_rows out of range.
+ *
+ * rf_search_multi_filtered: qfilter_dev int32 [B], the filter number of each query in [0, G)
+ * (device memory; a number outside that range reads a padding column or another filter's, never
+ * outside the buffer).  n_filters is the G the buffer was built with.  Otherwise the conventions
+ * of rf_search_filtered: any B, run as 64-query sweeps; k <= RF_MAX_K; stream-ordered, no host sync,
+ * captures into a hipGraph; the tail of a query with fewer passing rows than k is -inf / -1 with
+ * flags 0; multi_dev must have been built for n_rows == rf_index_size(ix).  A flagged query is
+ * re-run by the caller through rf_search_exhaustive_filtered with ITS filter's buffer.  No range,
+ * search-after, grouping or SQ8 form.
+ * New in this build; the reference calls Milvus one query at a time on this path. */
+#define RF_MULTI_MAX_FILTERS 64
+size_t rf_multi_filter_bytes(int64_t n_rows, int n_filters);
+int rf_multi_filter_build(const void* const* filters, int n_filters, int64_t n_rows, void* multi_dev,
+                          void* stream);
+int rf_search_multi_filtered(const rf_index_t* ix, const void* multi_dev, int n_filters,
+                             const int32_t* qfilter_dev, const void* q_dev, int B, int k, int64_t id_base,
+                             float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* stream);
 /* ---- range search: Collection.search(..., param={"params": {"radius": r, "range_filter": f}}) ----
  * The best k hits whose score lies in the band  radius < score <= range_filter  (COSINE / IP:
  * higher is better), i.e. the (score desc, row asc) ranking of rf_search with every row outside

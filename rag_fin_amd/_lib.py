@@ -110,6 +110,10 @@ SIGNATURES = {
     "rf_search_exhaustive_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
+    "rf_multi_filter_bytes": (c_size_t, [c_int64, c_int]),
+    "rf_multi_filter_build": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "rf_search_multi_filtered": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_exhaustive_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double,

@@ -6,6 +6,12 @@ GPU a corpus sweep costs the same for 1 or 64 queries, so concurrent requests ar
 worth coalescing: callers block in `search()`, a single worker thread drains the
 queue every `max_wait_ms` (or as soon as `max_batch` requests are waiting) and
 answers them with ONE `VectorRAG.search_batch` call (one embed + one sweep).
+
+A request may carry a filter expression of its own (`search(query, top_k, expr)`): the batch then
+goes out as `search_batch(queries, k, expr=[...])`, per-query filters served by one sweep over the
+union of the batch's filters, with None for the requests that have none.  The
+expression is parsed in the caller's thread before the request is queued, so a malformed filter
+fails its own request only.  A batch in which no request has a filter is the call of before.
 """
 from __future__ import annotations
 
@@ -13,12 +19,14 @@ import threading
 import time
 from collections import deque
 
+from . import filter_expr
+
 
 class _Request:
-    __slots__ = ("query", "top_k", "done", "result", "error")
+    __slots__ = ("query", "top_k", "expr", "done", "result", "error")
 
-    def __init__(self, query: str, top_k: int):
-        self.query, self.top_k = query, top_k
+    def __init__(self, query: str, top_k: int, expr=None):
+        self.query, self.top_k, self.expr = query, top_k, expr
         self.done = threading.Event()
         self.result = None
         self.error = None
@@ -38,9 +46,14 @@ class MicroBatcher:
         self._worker.start()
 
     # -- caller side -------------------------------------------------------------------
-    def search(self, query: str, top_k: int = 3):
-        """Same contract as VectorRAG.search; blocks until this request's batch is done."""
-        req = _Request(query, top_k)
+    def search(self, query: str, top_k: int = 3, expr: str | None = None):
+        """Same contract as VectorRAG.search(query, top_k, expr); blocks until this request's batch
+        is done.  A malformed expr raises ValueError here, before anything is queued."""
+        if filter_expr.is_empty(expr):
+            expr = None
+        else:
+            filter_expr.parse(expr, getattr(getattr(self.rag, "collection", None), "analyzer", None))
+        req = _Request(query, top_k, expr)
         with self._cv:
             if self._stop:
                 raise RuntimeError("MicroBatcher is closed")
@@ -84,7 +97,10 @@ class MicroBatcher:
             self.requests += len(batch)
             try:
                 k = max(r.top_k for r in batch)
-                results = self.rag.search_batch([r.query for r in batch], k)
+                if all(r.expr is None for r in batch):
+                    results = self.rag.search_batch([r.query for r in batch], k)
+                else:
+                    results = self.rag.search_batch([r.query for r in batch], k, expr=[r.expr for r in batch])
                 for r, ctx in zip(batch, results):
                     r.result = ctx[:r.top_k]
             except Exception as e:          # every waiter gets the failure, none hangs

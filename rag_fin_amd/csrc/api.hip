@@ -237,12 +237,16 @@ static int for_chunks(const rf_index_t* ix, const void* q_dev, int B, int k, siz
 // after: search-after (always with band, both sides open when the caller gave none): the band
 // chain with the ceiling of each query read from its bound in device memory; the merge also drops
 // what the fp64 (score, id) rule puts at or before the bound.
+// multi: per-query filters (always with filt, which is then the union of the batch's filters;
+// never with sq8, wide, band or after): both sweeps walk the union's blocks and test each query's
+// rows against its own filter's words; threshold and merge are per query as ever.
 struct rf_variant {
   const rf_filter_view* filt;
   const rf_sq8_ws* sq8;
   bool wide;
   const rf_band* band;
   const rf_after* after;
+  const rf_multi* multi;
 };
 
 static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
@@ -283,14 +287,14 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS && v.band) rc = rf_launch_band_eps(ix, qc, nb, ws, st);
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
     rc = v.wide ? rf_launch_wide_sample(ix, qc, nb, ws, &P, st)
-                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band, v.after);
+                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band, v.after, v.multi);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK)
     rc = v.wide  ? rf_launch_wide_emit(ix, qc, nb, ws, st)
          : v.sq8 ? rf_launch_sq8_emit(ix, nb, JB, ws, *v.sq8, st)
-                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band, v.after);
+                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band, v.after, v.multi);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band, v.after);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
@@ -304,7 +308,7 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, const rf_out& o,
                           void* workspace_dev, hipStream_t st, const rf_filter_view* filt, bool sq8,
                           float* stage_ms = nullptr, const rf_band* band = nullptr,
-                          const rf_after* after = nullptr) {
+                          const rf_after* after = nullptr, const rf_multi* multi = nullptr) {
   if (ix->size == 0) return fill_empty(B, k, o, st);
   rf_arena a{(unsigned char*)workspace_dev, 0};
   rf_workspace ws;
@@ -315,13 +319,16 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
     return for_chunks(ix, q_dev, B, k, (size_t)k, widen, o,
                       [&](int q0, int nb, bool wide, const _Float16* qc, const rf_out& oc) {
                         const rf_after ac{after ? after->score + q0 : nullptr, after ? after->id + q0 : nullptr};
-                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr}, qc, nb, k, id_base, ws,
-                                     oc, st, nullptr);
+                        const rf_multi mc{multi ? multi->masks_t : nullptr, multi ? multi->qfilter + q0 : nullptr,
+                                          multi ? multi->gp : 0u};
+                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr, multi ? &mc : nullptr},
+                                     qc, nb, k, id_base, ws, oc, st, nullptr);
                       });
   bool wide;
   const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
   return time_stages(sq ? 6 : 5, stage_ms, [&](hipEvent_t* ev) {
-    return sweep(ix, rf_variant{filt, sq, wide, band, after}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st, ev);
+    return sweep(ix, rf_variant{filt, sq, wide, band, after, multi}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st,
+                 ev);
   });
 }
 
@@ -470,6 +477,30 @@ extern "C" int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* f
   const rf_filter_view f = rf_filter_carve(filter_dev, ix ? ix->size : 0);
   return exhaustive_impl("rf_search_exhaustive_filtered", ix, q_dev, B, k, id_base, scores_dev, ids_dev,
                          exact_dev, after_score_dev, after_id_dev, workspace_dev, workspace_bytes, stream, f.mask);
+}
+
+// ---- per-query filters (include/ragfin.h, "per-query filters") -----------------------------------
+extern "C" int rf_search_multi_filtered(const rf_index_t* ix, const void* multi_dev, int n_filters,
+                                        const int32_t* qfilter_dev, const void* q_dev, int B, int k, int64_t id_base,
+                                        float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                                        void* workspace_dev, size_t workspace_bytes, void* stream) {
+  if (!qfilter_dev || n_filters < 1 || n_filters > RF_MULTI_MAX_FILTERS) {
+    rf_set_error("rf_search_multi_filtered: null qfilter, or n_filters = %d outside 1..%d", n_filters,
+                 RF_MULTI_MAX_FILTERS);
+    return RF_ERR_INVALID;
+  }
+  int rc = check_filter_arg("rf_search_multi_filtered", multi_dev);
+  if (rc != RF_OK) return rc;
+  rc = check_search_args("rf_search_multi_filtered", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                         workspace_bytes);
+  if (rc != RF_OK) return rc;
+  // the buffer starts with the union in the filter buffer format: the sweeps' work list
+  const rf_filter_view f = rf_filter_carve(multi_dev, ix->size);
+  size_t so;
+  rf_multi_layout(ix->size, n_filters, &so);
+  const rf_multi m{(const uint32_t*)((const unsigned char*)multi_dev + so), qfilter_dev, rf_multi_columns(n_filters)};
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, &f, false, nullptr, nullptr, nullptr, &m);
 }
 
 // ---- range search (include/ragfin.h, "range search") ----------------------------------------------

@@ -419,3 +419,109 @@ extern "C" int rf_filter_from_mask(const uint32_t* mask_dev, int64_t n_rows, voi
   }
   return launch_compact(filter_dev, n_rows, tp, st);
 }
+
+// ---- per-query filters (include/ragfin.h, "per-query filters") ----------------------------------
+uint32_t rf_multi_columns(int n_filters) {
+  uint32_t gp = 1u;
+  while (gp < (uint32_t)n_filters) gp <<= 1;
+  return gp;
+}
+
+size_t rf_multi_layout(int64_t n_rows, int n_filters, size_t* masks_off) {
+  const size_t m = (rf_filter_layout(n_rows, nullptr, nullptr, nullptr) + 255) / 256 * 256;
+  if (masks_off) *masks_off = m;
+  return m + (size_t)filter_blocks(n_rows) * rf_multi_columns(n_filters) * 4;
+}
+
+static bool multi_count_ok(int n_filters) { return n_filters >= 1 && n_filters <= RF_MULTI_MAX_FILTERS; }
+
+extern "C" size_t rf_multi_filter_bytes(int64_t n_rows, int n_filters) {
+  if (!filter_rows_ok(n_rows) || !multi_count_ok(n_filters)) return 0;
+  return rf_multi_layout(n_rows, n_filters, nullptr);
+}
+
+struct MultiSrc {
+  const uint32_t* hdr[RF_MULTI_MAX_FILTERS];
+  const uint32_t* mask[RF_MULTI_MAX_FILTERS];
+};
+
+// k_filter_copy with the OR of G masks as the source, which also writes the G words of every
+// block side by side (block-major).  A filter whose header was built for another row count
+// passes no row, as in the masked sweep (filter_pass_blocks).  One thread per mask word: no
+// atomics, the same filters give the same buffer bit for bit.
+__global__ void __launch_bounds__(FILTER_EVAL_THREADS) k_multi_union(MultiSrc src, uint32_t G, uint32_t gp,
+                                                                    uint32_t* __restrict__ mask,
+                                                                    uint32_t* __restrict__ masks_t,
+                                                                    uint32_t* __restrict__ tile_cnt,
+                                                                    uint32_t n_rows, uint32_t nblk,
+                                                                    uint32_t tile_words) {
+  __shared__ uint32_t red[2][FILTER_EVAL_THREADS / 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const uint32_t w0 = blockIdx.x * tile_words;
+  const uint32_t w1 = min(w0 + tile_words, nblk);
+  uint32_t nz = 0u, pc = 0u;
+  for (uint32_t w = w0 + threadIdx.x; w < w1; w += FILTER_EVAL_THREADS) {
+    const uint32_t rows = n_rows - w * 32u;   // > 0
+    const uint32_t keep = rows < 32u ? (1u << rows) - 1u : 0xFFFFFFFFu;
+    uint32_t u = 0u;
+    for (uint32_t g = 0; g < gp; ++g) {   // (g, G, gp: wave-uniform)
+      uint32_t v = 0u;
+      if (g < G && src.hdr[g][0] == n_rows) v = src.mask[g][w] & keep;
+      masks_t[(size_t)w * gp + g] = v;
+      u |= v;
+    }
+    mask[w] = u;
+    nz += u != 0u;
+    pc += (uint32_t)__popc(u);
+  }
+  nz = wave_sum_u(nz);
+  pc = wave_sum_u(pc);
+  if (lane == 0) {
+    red[0][wave] = nz;
+    red[1][wave] = pc;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    uint32_t s = 0u;
+    for (int i = 0; i < FILTER_EVAL_THREADS / 64; ++i) s += red[threadIdx.x][i];
+    tile_cnt[2 * blockIdx.x + threadIdx.x] = s;
+  }
+}
+
+extern "C" int rf_multi_filter_build(const void* const* filters, int n_filters, int64_t n_rows, void* multi_dev,
+                                     void* stream) {
+  if (!filters || !multi_count_ok(n_filters)) {
+    rf_set_error("rf_multi_filter_build: null filter array, or n_filters = %d outside 1..%d", n_filters,
+                 RF_MULTI_MAX_FILTERS);
+    return RF_ERR_INVALID;
+  }
+  int rc = check_filter_buffer("rf_multi_filter_build", n_rows, multi_dev);
+  if (rc != RF_OK) return rc;
+  MultiSrc src{};
+  for (int g = 0; g < n_filters; ++g) {
+    if (!filters[g] || (((uintptr_t)filters[g]) & 15)) {
+      rf_set_error("rf_multi_filter_build: filter %d null or not 16-byte aligned", g);
+      return RF_ERR_INVALID;
+    }
+    const rf_filter_view v = rf_filter_carve(filters[g], n_rows);
+    src.hdr[g] = v.hdr;
+    src.mask[g] = v.mask;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const TilePlan tp = plan_tiles(n_rows);
+  size_t mo, bo, to, so;
+  rf_filter_layout(n_rows, &mo, &bo, &to);
+  rf_multi_layout(n_rows, n_filters, &so);
+  unsigned char* base = (unsigned char*)multi_dev;
+  // every byte of the buffer is defined: what the kernels below do not write (the block list past
+  // the count, unused scratch, alignment gaps) is zero, so equal filters give equal buffers
+  RF_HIP(hipMemsetAsync(multi_dev, 0, rf_multi_layout(n_rows, n_filters, nullptr), st));
+  if (tp.n_tiles > 0) {
+    hipLaunchKernelGGL(k_multi_union, dim3(tp.n_tiles), dim3(FILTER_EVAL_THREADS), 0, st, src, (uint32_t)n_filters,
+                       rf_multi_columns(n_filters), (uint32_t*)(base + mo), (uint32_t*)(base + so),
+                       (uint32_t*)(base + to), (uint32_t)n_rows, tp.nblk, tp.tile_words);
+    RF_HIP(hipGetLastError());
+  }
+  return launch_compact(multi_dev, n_rows, tp, st);
+}

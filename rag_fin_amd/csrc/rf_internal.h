@@ -162,6 +162,17 @@ struct rf_filter_view {
 };
 size_t rf_filter_layout(int64_t n_rows, size_t* mask_off, size_t* blocks_off, size_t* tiles_off);
 rf_filter_view rf_filter_carve(const void* filter, int64_t n_rows);
+// Per-query filters (include/ragfin.h, "per-query filters"): the multi-filter buffer is the filter
+// buffer of the union of G filters (rf_filter_carve reads it as such), then, 256-byte aligned, the
+// G masks block-major: word [b * gp + g] is mask word b of filter g, gp = G rounded up to a power
+// of two (words of the padding columns are zero).
+struct rf_multi {
+  const uint32_t* masks_t;   // [nblk][gp]
+  const int32_t* qfilter;    // [B] filter number per query, device
+  uint32_t gp;
+};
+uint32_t rf_multi_columns(int n_filters);
+size_t rf_multi_layout(int64_t n_rows, int n_filters, size_t* masks_off);
 
 // Sample fold: the geometry of a sample pass that kept its lists (n_samp = 0: none kept; the
 // threshold appends nothing and the emit sweeps every block).  Sample wave s read blocks
@@ -190,12 +201,16 @@ struct rf_after {
 // after: nullptr = no bound; otherwise the search-after form (always with a band)
 // fold: rf_launch_sample fills it (the fold is off for a filtered sweep and with the knob off);
 // rf_launch_threshold and rf_launch_emit take what it filled, nullptr = no fold
+// multi: nullptr = one filter for the batch; otherwise per-query filters -- filt is the union of
+// the batch's filters and each query's row bits are its own filter's (never with band / after)
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr,
-                     rf_fold* fold = nullptr, const rf_band* band = nullptr, const rf_after* after = nullptr);
+                     rf_fold* fold = nullptr, const rf_band* band = nullptr, const rf_after* after = nullptr,
+                     const rf_multi* multi = nullptr);
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                    hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr,
-                   const rf_band* band = nullptr, const rf_after* after = nullptr);
+                   const rf_band* band = nullptr, const rf_after* after = nullptr,
+                   const rf_multi* multi = nullptr);
 // Shape of the 64-query sweeps (scan.hip, grouped.hip): waves per workgroup by dim, and the emit
 // grid = CUs x workgroups per CU (0 = the default of the dim), at most one wave per 32-row block.
 static inline int rf_waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }

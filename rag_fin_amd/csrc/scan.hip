@@ -67,18 +67,37 @@ __device__ __forceinline__ void fold_top2(const f32x16& a, uint32_t rbase, float
 // candidates; the block prefilter tests thr <= score <= ceiling per row -- two compares whose
 // lane masks combine on the scalar unit, no clipped copy of the accumulators -- so a block whose
 // only rows >= thr lie above the ceiling never reaches emit_slow).
-template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false, bool BAND = false>
+// MULTI (per-query filters, always with FILTER and without BAND): the filter word is per lane and
+// query group, `mwl[jb]` -- the word of the lane's own query's filter for this block -- instead of
+// the wave's `mword`.  A block of the union in which the lane's query has no row has word 0 there.
+template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false, bool BAND = false, bool MULTI = false>
 __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
                                            const uint4* nxt, const u32x4* smemQ, int lane,
                                            uint32_t row0, const float (&th)[JB], float (&pm)[JB],
                                            float (&m1)[JB], uint32_t (&r1)[JB], float (&m2)[JB],
                                            EmitState& es, const ScanParams& p,
-                                           uint32_t mword = 0u, const float* tc = nullptr) {
+                                           uint32_t mword = 0u, const float* tc = nullptr,
+                                           const uint32_t* mwl = nullptr) {
+  static_assert(!MULTI || (FILTER && !BAND && MODE != MODE_FOLD), "per-query filters: the plain masked sweep only");
   f32x16 acc[JB];
   mfma_block<KS, R, JB, LAST>(ring, cur, nxt, smemQ, lane, acc);
 
   if (MODE != MODE_EMIT) {
-    if (FILTER) {
+    if (MULTI) {
+      // rows the lane's own filter rejects leave the lane's maximum: every partition maximum of
+      // query q is taken over rows of S_q only
+      bool part = false;
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) part |= mwl[jb] != 0xFFFFFFFFu;
+      if (__ballot(part) != 0ull) {
+        const int h = lane >> 5;
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (((mwl[jb] >> acc_row(i, h)) & 1u) == 0u) acc[jb][i] = -INFINITY;
+      }
+    } else if (FILTER) {
       // rows the filter rejects (and rows past the end: their bits are zero) leave the maximum
       if (mword != 0xFFFFFFFFu) {  // wave-uniform
         const int h = lane >> 5;
@@ -120,7 +139,8 @@ __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
 #pragma unroll
       for (int jb = 0; jb < JB; ++jb) hit |= (max16(acc[jb]) >= th[jb]);
     }
-    if (__ballot(hit) != 0ull) emit_slow<JB, ScanParams, FILTER, BAND>(acc, th, row0, lane, es, p, mword, tc);
+    if (__ballot(hit) != 0ull)
+      emit_slow<JB, ScanParams, FILTER, BAND, MULTI>(acc, th, row0, lane, es, p, mword, tc, mwl);
   }
 }
 
@@ -132,7 +152,11 @@ template <int KS, int R, int JB, int WAVES, int MODE, bool FILTER, bool BAND, bo
 __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   static_assert(!BAND || MODE != MODE_FOLD, "the band sweep has no sample fold");
   static_assert(!AFTER || BAND, "a search-after sweep is a band sweep");
-  u32x4* smemQ = (u32x4*)smem_raw;                                   // JB*KS*64 uint4
+  // MULTI (p is a ScanParamsM): the work items are the pass blocks of the union of the batch's
+  // filters, the row bits per lane those of its own query's filter
+  constexpr bool MULTI = std::is_same<PT, ScanParamsM>::value;
+  static_assert(!MULTI || (FILTER && !BAND), "per-query filters: the plain masked sweep only");
+  u32x4* smemQ = (u32x4*)smem_raw;                                  // JB*KS*64 uint4
   unsigned char* tail = smem_raw + (size_t)JB * KS * RF_FRAG_BYTES;  // per-mode scratch
 
   const int tid = threadIdx.x;
@@ -168,7 +192,11 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
 
   // work items w = gw, gw + W, ...  (one item = one 32-row block)
   const uint32_t W = gridDim.x * WAVES;
-  const uint32_t gw = blockIdx.x * WAVES + wave;
+  // MULTI sample pass: the waves of a workgroup take items a whole grid apart instead of
+  // neighbours, so that a partition (= workgroup) reads blocks from all over the union.  A filter
+  // that is one contiguous 1/G of the corpus then has rows in about min(P, sampled blocks / G)
+  // partitions instead of P / G, and the k-th partition maximum of its queries exists.
+  const uint32_t gw = (MULTI && MODE == MODE_SAMPLE) ? wave * gridDim.x + blockIdx.x : blockIdx.x * WAVES + wave;
   if constexpr (FILTER) {
     const uint32_t npb = filter_pass_blocks(p.hdr, p.n_rows, p.n_blocks);
     if (MODE == MODE_SAMPLE) {  // ~1/16 of the pass blocks, spread evenly (rf_launch_sample)
@@ -207,10 +235,25 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
     return r < p.n_work ? r : 0u;  // (k_threshold lists sampled blocks only: never past the corpus)
   };
 
+  // Entry of the pass list that work item w of a masked sweep reads.  MULTI sample pass: item w
+  // steps through its stride group (entry w * bstride + w mod bstride, still below (w + 1) * bstride
+  // <= the list's length), so that the sampled blocks do not all share one residue modulo the
+  // stride: with filters interleaved row by row (row r in filter r mod G) the blocks at a fixed
+  // even stride hold rows of half the filters only, and the other half would get no threshold.
+  auto fitem = [&](uint32_t w) -> uint32_t {
+    if constexpr (FILTER) {
+      if constexpr (MULTI && MODE == MODE_SAMPLE) return w * p.bstride + w % p.bstride;
+      else return w * p.bstride;
+    } else {
+      return w;
+    }
+  };
+  (void)fitem;
+
   u32x4 ring[R];
   if (FILTER ? gw < p.n_work : gw < M) {
     const uint4* src;
-    if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[gw * p.bstride] * (KS * 64) + lane;
+    if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[fitem(gw)] * (KS * 64) + lane;
     else if constexpr (MODE == MODE_EMIT && !BAND) src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
     else src = p.corpus + (size_t)gw * p.bstride * (KS * 64) + lane;
 #pragma unroll
@@ -230,7 +273,36 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   if (cnt > 0) {
 
     uint32_t w = gw;
-    if constexpr (FILTER) {
+    if constexpr (MULTI) {
+      // the column of the lane's query's filter in masks_t (a number past the filters lands in a
+      // padding column or wraps onto a filter: never past the row of the block)
+      uint32_t gcol[JB];
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) {
+        const int ql = jb * 32 + (lane & 31);
+        gcol[jb] = ql < p.B ? ((uint32_t)p.qfilter[ql] & (p.gp - 1u)) : 0u;
+      }
+      uint32_t b = p.blocks[fitem(w)];
+      for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
+        // as below, with one vector load per query group for the lane's own mask word: issued
+        // ahead of the ring's loads of this step, consumed after the MFMA chain
+        const uint32_t bn = p.blocks[fitem(w + W)];
+        uint32_t mwl[JB];
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb) mwl[jb] = p.masks_t[(size_t)b * p.gp + gcol[jb]];
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, false, true, false, true>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, 0u, tc, mwl);
+        b = bn;
+      }
+      {
+        uint32_t mwl[JB];
+#pragma unroll
+        for (int jb = 0; jb < JB; ++jb) mwl[jb] = p.masks_t[(size_t)b * p.gp + gcol[jb]];
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, true, true, false, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, 0u, tc, mwl);
+      }
+    } else if constexpr (FILTER) {
       uint32_t b = p.blocks[w * p.bstride];
       for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
         // scalar loads at the top of the step: the next block's index is needed only when the
@@ -338,8 +410,10 @@ __global__ void __launch_bounds__(WAVES * 64, 2) k_scan(ScanParams p) {
   scan_body<KS, R, JB, WAVES, MODE, false, BAND, false>(p, smem_raw);
 }
 
-template <int KS, int R, int JB, int WAVES, int MODE, bool BAND = false>
-__global__ void __launch_bounds__(WAVES * 64, 2) k_scan_filtered(ScanParamsF p) {
+// MULTI: per-query filters (p is a ScanParamsM: the union's block list, per-lane mask words).
+template <int KS, int R, int JB, int WAVES, int MODE, bool BAND = false, bool MULTI = false>
+__global__ void __launch_bounds__(WAVES * 64, 2)
+k_scan_filtered(typename std::conditional<MULTI, ScanParamsM, ScanParamsF>::type p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   scan_body<KS, R, JB, WAVES, MODE, true, BAND, false>(p, smem_raw);
 }
@@ -393,6 +467,7 @@ static int launch_scan(const PT& p, int grid, hipStream_t st) {
   else lds += (size_t)WAVES * 2 * JB * 32 * 4;
   auto kern = [] {
     if constexpr (std::is_same<PT, ScanParamsF>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE, BAND>;
+    else if constexpr (std::is_same<PT, ScanParamsM>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE, BAND, true>;
     else if constexpr (std::is_same<PT, ScanParamsFA>::value) return k_scan_filtered_after<KS, R, JB, WAVES, MODE>;
     else if constexpr (std::is_same<PT, ScanParamsA>::value) return k_scan_after<KS, R, JB, WAVES, MODE>;
     else return k_scan<KS, R, JB, WAVES, MODE, BAND>;
@@ -465,9 +540,19 @@ int rf_scan_supported_dim(int dim) {
   }
 }
 
+// Per-query filters: the masked sweep's arguments (over the union: filt) with the per-lane words.
+static ScanParamsM multi_params(const ScanParamsF& f, const rf_multi& multi) {
+  ScanParamsM m{};
+  static_cast<ScanParamsF&>(m) = f;
+  m.masks_t = multi.masks_t;
+  m.qfilter = multi.qfilter;
+  m.gp = multi.gp;
+  return m;
+}
+
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold,
-                     const rf_band* band, const rf_after* after) {
+                     const rf_band* band, const rf_after* after, const rf_multi* multi) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = rf_waves_per_wg(KS);
@@ -513,6 +598,7 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
     f.n_blocks = nblk;
     f.work_lo = lo;
     f.work_hi = hi;
+    if (multi) return dispatch_scan<MODE_SAMPLE>(KS, JB, multi_params(f, *multi), grid, grid, st);
     if (band && after) {
       ScanParamsFA fa{};
       static_cast<ScanParamsF&>(fa) = f;
@@ -542,7 +628,7 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
 
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                    hipStream_t st, const rf_filter_view* filt, const rf_fold* fold, const rf_band* band,
-                   const rf_after* after) {
+                   const rf_after* after, const rf_multi* multi) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int grid = rf_emit_grid(ix, rf_knob_emit_wgs_per_cu);
@@ -579,6 +665,7 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
     f.mask = filt->mask;
     f.blocks = filt->blocks;
     f.n_blocks = nblk;
+    if (multi) return dispatch_scan<MODE_EMIT>(KS, JB, multi_params(f, *multi), grid, grid, st);
     if (band && after) {
       ScanParamsFA fa{};
       static_cast<ScanParamsF&>(fa) = f;

@@ -52,6 +52,16 @@ struct ScanParamsF : ScanParams {
   uint32_t work_lo, work_hi;  // sample pass: bounds of the sampled block count (n_work is unused)
 };
 
+// Per-query filters (k_scan_filtered<..., MULTI = true>): hdr / blocks are those of the union of
+// the batch's filters (`mask` is not read), and the row bits a lane tests are its own query's:
+// word masks_t[b * gp + qfilter[query of the lane]] of block b.  A type of its own, so that the
+// arguments of the other sweeps stay what they are.
+struct ScanParamsM : ScanParamsF {
+  const uint32_t* masks_t;   // [nblk][gp] the filters' mask words, block-major
+  const int32_t* qfilter;    // [B] filter number per query
+  uint32_t gp;               // words per block: a power of two >= the number of filters
+};
+
 // Search-after (k_scan_after / k_scan_filtered_after, always the band form): the fp64 score of each
 // query's bound.  The ceiling of query b is rf_after_ceiling(band_hi, after_s[b], ...) instead of
 // band_hi: min(hi, bound) in the emit, the strict one in the sample pass.  Types of
@@ -229,10 +239,13 @@ __device__ __forceinline__ void emit_append(const f32x16 (&sc)[JB], uint32_t bit
 // whatever its score (an explicit test: the threshold may be -inf, so masking by writing -inf
 // into the accumulators would not keep rejected rows out).
 // BAND: `tc` is the per-lane ceiling of the emit (hi + eps); a row above it is no candidate.
-template <int JB, class P, bool FILTER = false, bool BAND = false>
+// MULTI (per-query filters, with FILTER): the word is the lane's own per query group, `mwl[jb]`,
+// instead of the wave's `mword`; the test stays explicit for the same reason.
+template <int JB, class P, bool FILTER = false, bool BAND = false, bool MULTI = false>
 __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (&th)[JB],
                                           uint32_t row0, int lane, EmitState& es, const P& p,
-                                          uint32_t mword = 0u, const float* tc = nullptr) {
+                                          uint32_t mword = 0u, const float* tc = nullptr,
+                                          const uint32_t* mwl = nullptr) {
   const int h = lane >> 5;
   const uint32_t lim = p.n_rows - row0;  // rows of this block that exist (>= 32 except the last block)
   uint32_t bits = 0u;
@@ -241,7 +254,7 @@ __device__ __forceinline__ void emit_slow(const f32x16 (&acc)[JB], const float (
 #pragma unroll
     for (int i = 0; i < 16; ++i)
       bits |= ((acc[jb][i] >= th[jb]) && (acc_row(i, h) < lim) &&
-               (!FILTER || ((mword >> acc_row(i, h)) & 1u) != 0u) &&
+               (!FILTER || (((MULTI ? mwl[jb] : mword) >> acc_row(i, h)) & 1u) != 0u) &&
                (!BAND || acc[jb][i] <= tc[jb])) ? (1u << (jb * 16 + i)) : 0u;
   emit_append<JB>(acc, bits, row0, lane, es, [&] { emit_flush(es, p, lane); });
 }

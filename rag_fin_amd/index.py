@@ -121,6 +121,56 @@ def _ptr(t):
     return c_void_p(t.data_ptr()) if t is not None else None
 
 
+MULTI_MAX_FILTERS = 64   # filters one multi-filter buffer holds (include/ragfin.h, "per-query filters")
+
+
+class MultiFilter:
+    """The per-query filters of one batch (include/ragfin.h, "per-query filters"): G <= 64 filter
+    buffers built for the same rows, the multi-filter buffer over them (their union in the filter
+    buffer format, then their masks block-major) and, per query of the batch, the number of its
+    filter.  `GpuIndex.search_raw / search / search_host(..., filt=MultiFilter)` sweeps the union's
+    blocks once for the whole batch, each query over its own rows; a flagged query goes down the
+    ladder with its own filter buffer."""
+
+    def __init__(self, filters, qfilter, n_rows: int, device):
+        torch = _torch()
+        lib = _lib.load_library()
+        self.filters = list(filters)
+        G = len(self.filters)
+        if not 1 <= G <= MULTI_MAX_FILTERS:
+            raise ValueError(f"per-query filters: a batch holds 1..{MULTI_MAX_FILTERS} distinct filters, got {G}")
+        self.qfilter_host = np.asarray(qfilter, dtype=np.int32).reshape(-1)
+        if self.qfilter_host.size == 0 or int(self.qfilter_host.min()) < 0 or int(self.qfilter_host.max()) >= G:
+            raise ValueError(f"per-query filters: need one filter number in [0, {G}) per query")
+        self.n_rows = int(n_rows)
+        nbytes = lib.rf_multi_filter_bytes(self.n_rows, G)
+        if nbytes == 0:
+            raise ValueError(f"per-query filters: no buffer for {n_rows} rows and {G} filters")
+        with torch.cuda.device(device):
+            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self.qfilter = torch.from_numpy(self.qfilter_host).to(device)
+            ptrs = (c_void_p * G)(*[c_void_p(f.data_ptr()) for f in self.filters])
+            _lib.check(lib.rf_multi_filter_build(ptrs, G, self.n_rows, _ptr(self.buf), _lib.current_stream_ptr()))
+
+    def __len__(self) -> int:
+        return len(self.filters)
+
+
+def plan_filter_chunks(qfilter, chunk: int = _lib.RF_QCHUNK):
+    """Queries with a filter number each -> the sweeps that serve them: the queries ordered by
+    filter number (stable), cut into chunks of `chunk`, so that a chunk's union holds as few
+    filters as the order allows.  -> [(query indices int64 [nb], their filters' numbers, ascending
+    and distinct, the position of each query's filter in that list int32 [nb])]."""
+    qf = np.asarray(qfilter, dtype=np.int64).reshape(-1)
+    order = np.argsort(qf, kind="stable")
+    out = []
+    for lo in range(0, order.size, chunk):
+        idx = order[lo:lo + chunk]
+        distinct, local = np.unique(qf[idx], return_inverse=True)
+        out.append((idx, distinct.tolist(), local.astype(np.int32)))
+    return out
+
+
 class GpuIndex:
     """Thin object wrapper over rf_index_* / rf_search (include/ragfin.h).
 
@@ -341,7 +391,9 @@ class GpuIndex:
         hipStream_t of this device); no host sync.  Returns
         (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
         filt: a filter buffer built for this index (CorpusStore.build_filter / rf_filter_eval):
-        rf_search_filtered, the same outputs over the passing rows only.
+        rf_search_filtered, the same outputs over the passing rows only.  Or a MultiFilter (per-query
+        filters: rf_search_multi_filtered, query b over the passing rows of its own filter; built for
+        exactly these B queries; no sq8, band, group or mmr form: ValueError).
         sq8: rf_search_sq8 (needs enable_sq8; not with filt).  A workspace passed in must hold
         sq8_workspace_bytes (new_workspace does).
         band: (radius, range_filter) -- rf_search_range: the best k rows with
@@ -366,6 +418,17 @@ class GpuIndex:
         if not q16.is_contiguous() or q16.device != self.device:
             q16 = q16.to(self.device).contiguous()
         B = q16.shape[0]
+        if isinstance(filt, MultiFilter):
+            if filt.qfilter.numel() != B or filt.n_rows != self.size or filt.buf.device != self.device:
+                raise ValueError(f"per-query filters: built for {filt.qfilter.numel()} queries over {filt.n_rows} rows on "
+                                 f"{filt.buf.device}, searched with {B} queries over {self.size} rows on {self.device}")
+            scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.rf_search_multi_filtered(
+                    self.handle, _ptr(filt.buf), len(filt), _ptr(filt.qfilter), _ptr(q16), B, k, id_base, _ptr(scores),
+                    _ptr(ids), _ptr(exact), _ptr(flags), _ptr(workspace if workspace is not None else self.workspace),
+                    self.workspace_bytes, stream_ptr if stream_ptr is not None else _lib.current_stream_ptr()))
+            return scores, ids, exact, flags
         if mmr is not None:
             # the candidate search (its flags land in the caller's), then the MMR stage behind it
             res = self._outputs(B, k, want_exact, out=out)
@@ -407,6 +470,11 @@ class GpuIndex:
 
     def _check_variant(self, filt, sq8: bool, band, group, k: int, mmr=None) -> None:
         """Which of filt / sq8 / band / group / mmr go together, for every search method."""
+        if isinstance(filt, MultiFilter):
+            for name, on in (("SQ8", sq8), ("range (band)", band is not None), ("grouping", group is not None),
+                             ("MMR", mmr is not None)):
+                if on:
+                    raise ValueError(f"per-query filters (MultiFilter) have no {name} form")
         if mmr is not None:
             if group is not None:
                 raise ValueError("diversified search (mmr) has no grouping form")
@@ -638,7 +706,25 @@ class GpuIndex:
     def _rerun_flagged(self, q16, k: int, id_base: int, want_exact: bool, flags, sq8: bool, filt, band=None,
                        group=None):
         """rerun_flagged with this index's tiers (the band of a range search rides in them; a
-        grouping search re-runs group by group).  The caller holds the lock."""
+        grouping search re-runs group by group).  A MultiFilter re-runs filter by filter: one
+        exhaustive call serves all flagged queries of a filter, over that filter's own buffer.
+        The caller holds the lock."""
+        if isinstance(filt, MultiFilter):
+            torch = _torch()
+            bad = torch.nonzero(flags != 0).flatten()
+            if bad.numel() == 0:
+                return bad, None
+            bad_h = bad.cpu().numpy()
+            rows = list(self._outputs(bad_h.size, k, want_exact, flags=False)[:3])
+            q16 = q16.to(self.device)
+            of = filt.qfilter_host[bad_h]
+            for g in np.unique(of).tolist():
+                at = torch.from_numpy(np.flatnonzero(of == g)).to(self.device)
+                part = self._exhaustive(q16[bad.to(self.device)[at]].contiguous(), k, id_base, want_exact, filt.filters[g])
+                for dst, src in zip(rows, part):
+                    if dst is not None:
+                        dst[at] = src
+            return bad, rows
         if group is not None:
             return rerun_flagged(q16, k, id_base, flags, False, filt, None,
                                  lambda q, k, base, f: self._grouped_exhaustive(q, group, base, want_exact, f))

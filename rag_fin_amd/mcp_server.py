@@ -95,8 +95,14 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
                                         min_score=min_score, max_score=max_score, **mmr)
         elif filter and filter.strip():
-            # filtered calls bypass the micro-batcher: one batch shares one filter
-            contexts = get_rag().search(query, top_k, expr=filter, **mmr)
+            # filtered calls bypass the micro-batcher: one batch shares one filter -- unless
+            # RAGFIN_MICROBATCH_FILTERS=1 (with RAGFIN_MICROBATCH_MS > 0): a call that carries only a
+            # filter is then coalesced too, each request over its own filter in one sweep
+            batcher = _searcher() if not mmr and os.getenv("RAGFIN_MICROBATCH_FILTERS", "0") == "1" else None
+            if batcher is not None and batcher is not get_rag():
+                contexts = batcher.search(query, top_k, expr=filter)
+            else:
+                contexts = get_rag().search(query, top_k, expr=filter, **mmr)
         elif mmr:
             contexts = get_rag().search(query, top_k, **mmr)
         else:

@@ -205,7 +205,18 @@ class VectorRAG:
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
         the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call; hybrid:
         dense + BM25 fused by reciprocal rank for every query, as in search(); offset: one for the
-        whole batch, as in search()."""
+        whole batch, as in search().
+        expr may also be a list or tuple with one entry per query (a filter string, or None for "no
+        filter"): per-query filters, still one corpus sweep per 64 queries
+        (CorpusStore.search(expr=[...])).  The list form is the plain path only: with rerank, hybrid,
+        min_score / max_score, group_by, mmr_lambda or offset it raises ValueError."""
+        if isinstance(expr, (list, tuple)):
+            if rerank or hybrid or min_score is not None or max_score is not None or group_by is not None or \
+                    mmr_lambda is not None or offset is not None:
+                raise ValueError("per-query filters (a list expr) serve the plain search only: not with rerank, hybrid, "
+                                 "min_score / max_score, group_by, mmr_lambda or offset")
+            if len(expr) != len(queries):
+                raise ValueError(f"expr list: {len(expr)} entries for {len(queries)} queries (one entry per query)")
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)

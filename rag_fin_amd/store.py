@@ -39,8 +39,8 @@ from . import filter_expr
 from . import lexical
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, SparseIndex, _ptr, eval_filter, filter_mask_bits, fuse_rrf, grouped_exhaustive,  # noqa: F401
-                    mask_words, require_gpu, rerun_flagged, words_mask)
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, eval_filter, filter_mask_bits, fuse_rrf,  # noqa: F401
+                    grouped_exhaustive, mask_words, plan_filter_chunks, require_gpu, rerun_flagged, words_mask)
 
 
 SCALAR_FIELDS = ("id", "text", "period", "chunk_type", "statement_type", "primary_value")
@@ -785,7 +785,20 @@ class CorpusStore:
         that holds at least one query term (and passes expr), hit.score its BM25 score, so a list
         may be shorter than limit, or empty.  Exact and bit-reproducible.  No range,
         grouping or MMR arguments (ValueError); vectors for "sparse" or strings for "embedding"
-        raise ValueError too.  To combine the two fields see hybrid_search."""
+        raise ValueError too.  To combine the two fields see hybrid_search.
+        expr may also be a list or tuple with ONE ENTRY PER QUERY VECTOR, each a filter string or
+        None / "" (no filter for that query): per-query filters, served by one sweep of the corpus
+        per 64 queries over the union of their filters (GpuIndex.search(filt=MultiFilter)), each
+        query over its own passing rows -- the hits of query b are those of
+        search(data[b], expr=expr[b]).  Equal strings are built once; a list whose entries are all
+        equal is the plain call with that one expression; above 64 queries the queries are ordered
+        by filter internally and the results come back in the caller's order.  The list form is the
+        plain search only: limit <= 64, and no offset, radius / range_filter, group_by_field,
+        mmr_lambda / mmr_fetch_k or anns_field="sparse" (ValueError; neither search_iterator,
+        hybrid_search arms, query nor delete take a list).  These can follow later."""
+        if isinstance(expr, (list, tuple)):
+            return self._search_expr_list(data, anns_field, param, limit, expr, output_fields, group_by_field,
+                                          mmr_lambda, mmr_fetch_k, offset)
         offset = check_offset(offset, param, limit)
         if offset and (anns_field == "sparse" or group_by_field is not None or mmr_lambda is not None
                        or mmr_fetch_k is not None):
@@ -805,6 +818,89 @@ class CorpusStore:
                 return self._search(data, anns_field, param, limit, expr, output_fields, mmr=mmr, offset=offset)
             return self._search(data, anns_field, param, limit, expr, output_fields,
                                 self._check_group_by(group_by_field, group_size, limit, param))
+
+    # -- per-query filters: search(expr=[...]) ----------------------------------------
+    @staticmethod
+    def _query_count(data) -> int:
+        """How many query vectors `data` holds, without touching the device."""
+        shape = tuple(data.shape) if hasattr(data, "shape") else np.asarray(data, dtype=np.float32).shape
+        return 1 if len(shape) == 1 else int(shape[0])
+
+    def _check_expr_list(self, data, anns_field, param, limit, exprs, group_by_field, mmr_lambda, mmr_fetch_k,
+                         offset) -> list:
+        """Everything a list expr refuses, before anything runs -> one key per query: the filter
+        string, or None for "no filter"."""
+        if anns_field == "sparse":
+            raise ValueError("per-query filters (a list expr) have no BM25 form (anns_field='sparse')")
+        if self._is_text(data):
+            raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
+        if group_by_field is not None:
+            raise ValueError("per-query filters (a list expr) cannot be combined with group_by_field")
+        if mmr_lambda is not None or mmr_fetch_k is not None:
+            raise ValueError("per-query filters (a list expr) cannot be combined with mmr_lambda / mmr_fetch_k")
+        if check_offset(offset, param, limit):
+            raise ValueError("per-query filters (a list expr) take no offset")
+        if self._band_of(param) is not None:
+            raise ValueError("per-query filters (a list expr) have no range form (radius / range_filter)")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= limit <= _lib.RF_MAX_K:
+            raise ValueError(f"per-query filters (a list expr): limit must be an integer in 1..{_lib.RF_MAX_K}, "
+                             f"got {limit!r} (the list form is not paged)")
+        for j, e in enumerate(exprs):
+            if e is not None and not isinstance(e, str):
+                raise ValueError(f"expr list: entry {j} is {type(e).__name__}; every entry is a filter string or None")
+        B = self._query_count(data)
+        if len(exprs) != B:
+            raise ValueError(f"expr list: {len(exprs)} entries for {B} query vectors (one entry per query)")
+        return [None if filter_expr.is_empty(e) else e for e in exprs]
+
+    def _all_pass_filter(self):
+        """The filter buffer that passes every row: what a query without a filter uses beside
+        queries that have one."""
+        torch = _torch()
+        n = self.num_entities
+        dev = self.index.device
+        with torch.cuda.device(dev):
+            words = torch.full(((n + 31) // 32,), -1, dtype=torch.int32, device=dev)
+            buf = torch.empty(self.index.lib.rf_filter_bytes(n), dtype=torch.uint8, device=dev)
+            _lib.check(self.index.lib.rf_filter_from_mask(_ptr(words), n, _ptr(buf), _lib.current_stream_ptr()))
+        return buf
+
+    def _search_expr_list(self, data, anns_field, param, limit, exprs, output_fields, group_by_field, mmr_lambda,
+                          mmr_fetch_k, offset):
+        keys = self._check_expr_list(data, anns_field, param, limit, exprs, group_by_field, mmr_lambda, mmr_fetch_k,
+                                     offset)
+        distinct = list(dict.fromkeys(keys))
+        if len(distinct) <= 1:   # one expression for the whole batch: the existing call, the same bits
+            return self.search(data, anns_field, param, limit, expr=distinct[0] if distinct else None,
+                               output_fields=output_fields)
+        if anns_field != "embedding":
+            raise ValueError(f"unknown vector field {anns_field!r}")
+        metric = (param or {}).get("metric_type", self.metric_type).upper()
+        if metric != self.metric_type:
+            raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
+        fields = self._check_output_fields(output_fields)
+        number = {key: g for g, key in enumerate(distinct)}
+        qfilter = [number[key] for key in keys]
+        with self._rw.read():
+            B = len(keys)
+            if self.num_entities == 0:
+                return [[] for _ in range(B)]
+            # every expression is parsed and built once, before any sweep runs
+            filters = [self._all_pass_filter() if key is None else self.build_filter(key) for key in distinct]
+            q16 = self._prepare_queries(data)
+            kk = min(int(limit), self.num_entities)
+            scores = np.full((B, kk), -np.inf, dtype=np.float32)
+            rows = np.full((B, kk), -1, dtype=np.int64)
+            for idx, used, local in plan_filter_chunks(qfilter):
+                qc = q16[idx.tolist()]   # the chunk's queries, in the order of `local`
+                if len(used) == 1:   # a chunk of one filter: the single-filter sweep (or the unfiltered one)
+                    s, r = self._search_rows(qc, int(limit), None if distinct[used[0]] is None else filters[used[0]])
+                else:
+                    mf = MultiFilter([filters[g] for g in used], local, self.num_entities, self.index.device)
+                    s, r = self.index.search_host(qc, int(limit), filt=mf)
+                scores[idx] = s[:, :kk]
+                rows[idx] = r[:, :kk]
+            return [self._hits(rows[b], scores[b], fields) for b in range(B)]
 
     def _check_group_by(self, field, group_size, limit, param):
         """-> (field, group_size), or None for "id" (every row its own group: the plain search)."""
@@ -929,6 +1025,8 @@ class CorpusStore:
             # every arm is checked before any runs
             prepared = []
             for r in reqs:
+                if isinstance(r.expr, (list, tuple)):
+                    raise ValueError("hybrid_search: an arm takes one expr string, not a list (per-query filters)")
                 if r.limit > _lib.RF_MAX_K:
                     raise ValueError(f"hybrid_search: an arm's limit is at most {_lib.RF_MAX_K}, got {r.limit}")
                 if r.anns_field == "sparse":
@@ -1023,6 +1121,8 @@ class CorpusStore:
         param["params"] may hold radius / range_filter.  limit: hits in all (-1: until the collection
         is exhausted).  The bound is a row number: an insert, delete, upsert or drop between two
         next() calls makes the next one raise RuntimeError."""
+        if isinstance(expr, (list, tuple)):
+            raise ValueError("search_iterator takes one expr string, not a list (per-query filters)")
         return SearchIterator(self, data, anns_field, param, batch_size, limit, expr, output_fields)
 
     @staticmethod
@@ -1174,6 +1274,8 @@ class CorpusStore:
         any other filter expression (rag_fin_amd.filter_expr): the matching rows in ascending
         row order.  offset (an int >= 0, else ValueError): skip that many of the matching rows
         first, on the host; `limit` counts from there."""
+        if expr is not None and not isinstance(expr, str):
+            raise ValueError(f"filter expression must be a string, got {type(expr).__name__}")
         offset = check_offset(offset, None, 1)
         with self._rw.read():
             return self._query(expr, limit, output_fields, offset)
