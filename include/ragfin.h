@@ -525,6 +525,76 @@ size_t rf_text_match_workspace_bytes(const rf_sparse_t* sp, int n_leaves);
 int rf_text_match(const rf_sparse_t* sp, const rf_text_leaf* leaves_host, int n_leaves, const int32_t* terms_dev,
                   int64_t n_terms_total, uint32_t* bitmaps_dev, int64_t words_per_leaf, void* workspace_dev,
                   size_t workspace_bytes, void* stream);
+/* ---- lexical index maintenance: the postings after an append or a delete, without the old texts -------
+ * A write changes N, avgdl and df, and through them every BM25 impact -- but with the term frequencies
+ * kept beside the postings (post_tf uint32 [nnz]) everything is re-derivable: the arrays after a write
+ * are bit for bit those of a fresh build of the surviving texts (the definitions in
+ * numpy: rag_fin_amd/lexical.py, append_reference / compact_reference / impacts).
+ * rf_postings describes one set of posting arrays in caller-owned device memory, inputs and outputs
+ * alike: post_off int64 [n_terms + 1], post_row / post_tf uint32 [nnz], and, both or neither, pos_off
+ * int64 [nnz + 1] with pos uint32 [n_pos] (the token positions of "keyword filters").  Every offset is
+ * int64.  All calls are stream-ordered, allocate nothing and do not synchronise; RF_ERR_INVALID comes
+ * from host-side checks before any device call (a NULL or not 16-byte-aligned array, a negative size,
+ * n_rows >= 2^31, sizes that do not add up, a workspace that is too small).  As in rf_sparse_search, a
+ * row or an offset out of range is clamped or skipped, never dereferenced: malformed postings give
+ * wrong arrays, not an out-of-range access.  Integers only apart from the impacts, no atomics: the
+ * same bits on every run.  What runs: workgroups over chunks of RF_LEX_CHUNK postings, read lane-
+ * strided; a chunk's term range is found by two binary searches in post_off, a posting's term inside
+ * that range.
+ *   rf_sparse_impacts   post_imp[p] = float32(idf[t] * ((tf * (k1 + 1)) / (tf + k1 * ((1 - b) + b *
+ *                       (dl[row] / avgdl))))), every operation in fp64, rounded on its own (no
+ *                       contraction); (k1 + 1) and (1 - b) are formed once.  idf fp64 [n_terms] comes
+ *                       from the host (log is not correctly rounded: it must be the host's), dl int32
+ *                       [n_rows].  avgdl > 0, k1 >= 0, 0 <= b <= 1.  A row >= n_rows gets impact 0.
+ *   rf_sparse_append    merged = old followed, per merged term, by delta with rows + old->n_rows.
+ *                       delta: the postings of the appended rows alone, over their own dictionary, rows
+ *                       from 0 (nnz = 0 and n_terms = 0 are allowed; its arrays stay non-NULL).
+ *                       map_old_dev int64 [old->n_terms], map_delta_dev int64 [delta->n_terms]: the
+ *                       merged term id of every term, ascending.  merged: post_off is an INPUT (the
+ *                       host knows every df), post_row / post_tf and pos_off / pos are written, n_rows,
+ *                       nnz and n_pos are the sums of both sides.  Positions on all three or on none.
+ *                       workspace_bytes >= rf_sparse_append_workspace_bytes(n_terms old, delta).
+ *                       One small launch makes the per-term tables (where a term's postings and their
+ *                       positions go), then one launch per side moves it: every posting is read once
+ *                       and written once.
+ *   rf_sparse_compact_plan   row_map_dev int32 [old->n_rows]: the new number of a row, or < 0 for a row
+ *                       that goes.  Writes dst_post_dev int64 [nnz + 1], the exclusive scan of "posting
+ *                       p is kept" closed by the total; with positions, dst_pos_dev int64 [nnz + 1],
+ *                       the exclusive scan of the kept postings' position counts (else NULL); and
+ *                       term_dst_dev int64 [n_terms + 2]: dst_post[post_off[t]] for t = 0 .. n_terms, the
+ *                       raw term offsets (a term whose two offsets are equal is gone), then the kept
+ *                       positions.  The host reads those back, drops the dead terms and sizes the
+ *                       outputs.  workspace_bytes >= rf_sparse_compact_workspace_bytes(nnz) (0 = out of
+ *                       range).  The prefix sum is reduce-then-scan over chunks of RF_LEX_CHUNK: a sum
+ *                       per chunk, one workgroup scans the sums in tiles of RF_LEX_CHUNK with a carry,
+ *                       then every chunk scans itself from its offset.
+ *   rf_sparse_compact_apply  kept posting p goes to slot dst_post[p] with row row_map[row] and its tf; its
+ *                       positions to pos[dst_pos[p] ..), pos_off closed at slot dst_post[nnz].  out:
+ *                       post_row / post_tf / pos_off / pos are written, nnz and n_pos are capacities (a
+ *                       slot or a position past them is not written); out->post_off is not read.
+ * New in this build; the reference has no lexical index. */
+#define RF_LEX_CHUNK 1024
+typedef struct rf_postings {
+  int64_t n_rows, n_terms, nnz, n_pos;
+  int64_t* post_off;   /* [n_terms + 1] */
+  uint32_t* post_row;  /* [nnz] */
+  uint32_t* post_tf;   /* [nnz] */
+  int64_t* pos_off;    /* [nnz + 1] or NULL */
+  uint32_t* pos;       /* [n_pos] or NULL */
+} rf_postings;
+int rf_sparse_impacts(const int64_t* post_off_dev, const uint32_t* post_row_dev, const uint32_t* post_tf_dev,
+                      const double* idf_dev, const int32_t* dl_dev, int64_t n_rows, int64_t n_terms, int64_t nnz,
+                      double avgdl, double k1, double b, float* post_imp_dev, void* stream);
+size_t rf_sparse_append_workspace_bytes(int64_t n_terms_old, int64_t n_terms_delta);
+int rf_sparse_append(const rf_postings* old_p, const rf_postings* delta, const int64_t* map_old_dev,
+                     const int64_t* map_delta_dev, const rf_postings* merged, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+size_t rf_sparse_compact_workspace_bytes(int64_t nnz);
+int rf_sparse_compact_plan(const rf_postings* old_p, const int32_t* row_map_dev, int64_t* dst_post_dev,
+                           int64_t* dst_pos_dev, int64_t* term_dst_dev, void* workspace_dev, size_t workspace_bytes,
+                           void* stream);
+int rf_sparse_compact_apply(const rf_postings* old_p, const int32_t* row_map_dev, const int64_t* dst_post_dev,
+                            const int64_t* dst_pos_dev, const rf_postings* out, void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */

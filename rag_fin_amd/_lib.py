@@ -26,6 +26,8 @@ RF_FUSE_MAX_ARMS = 4         # answers rf_fuse_rrf fuses
 RF_TEXT_MATCH = 1
 RF_TEXT_PHRASE = 2
 RF_TEXT_MAX_LEAVES = 16      # text leaves one rf_text_match call (one filter expression) holds
+# lexical index maintenance (include/ragfin.h, "lexical index maintenance")
+RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
 
 
 class RagfinError(RuntimeError):
@@ -57,6 +59,13 @@ class FilterOp(Structure):
 
 class TextLeaf(Structure):
     _fields_ = [("kind", c_int32), ("term_off", c_int32), ("n_terms", c_int32), ("min_match", c_int32)]
+
+
+class Postings(Structure):
+    """rf_postings: one set of posting arrays in device memory (lexical index maintenance)."""
+    _fields_ = [("n_rows", c_int64), ("n_terms", c_int64), ("nnz", c_int64), ("n_pos", c_int64),
+                ("post_off", c_void_p), ("post_row", c_void_p), ("post_tf", c_void_p), ("pos_off", c_void_p),
+                ("pos", c_void_p)]
 
 
 ENCODER_WEIGHT_FIELDS = ["word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b", "qkv_w",
@@ -142,6 +151,15 @@ SIGNATURES = {
     "rf_text_match_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "rf_text_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
                               c_void_p]),
+    "rf_sparse_impacts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,
+                                  c_double, c_double, c_void_p, c_void_p]),
+    "rf_sparse_append_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rf_sparse_append": (c_int, [POINTER(Postings), POINTER(Postings), c_void_p, c_void_p, POINTER(Postings), c_void_p,
+                                 c_size_t, c_void_p]),
+    "rf_sparse_compact_workspace_bytes": (c_size_t, [c_int64]),
+    "rf_sparse_compact_plan": (c_int, [POINTER(Postings), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
+    "rf_sparse_compact_apply": (c_int, [POINTER(Postings), c_void_p, c_void_p, c_void_p, POINTER(Postings), c_void_p]),
     "rf_fuse_rrf": (c_int, [c_int, c_void_p, c_int, POINTER(c_double), c_double, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,

@@ -847,20 +847,37 @@ class SparseIndex:
     hold `self._lock` while they size a workspace and enqueue; the results are the caller's own
     tensors.  The postings are immutable: a changed corpus gets a new SparseIndex.  The token
     positions (`attach_positions`) are given once, by whoever needs a phrase first; the caller
-    serialises that against `text_match` (CorpusStore: under its `_sparse_lock`)."""
+    serialises that against `text_match` (CorpusStore: under its `_sparse_lock`).
+
+    Index maintenance: built from postings that carry `post_tf` and `dl`, the index also
+    holds the term frequencies and row lengths (`supports_update`), and `appended` / `compacted` return
+    a NEW SparseIndex over new tensors -- the arrays a build of the changed corpus would give, positions
+    included when attached here -- while this one stays valid for whoever still holds it."""
 
     def __init__(self, postings, device=None):
         torch = _torch()
-        self.device = require_gpu(device)
+        device = require_gpu(device)
+        tf, dl = getattr(postings, "post_tf", None), getattr(postings, "dl", None)
+        with torch.cuda.device(device):
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(device)   # noqa: E731
+            # (uint32 rows and counts travel as their int32 bit patterns)
+            self._adopt(device, postings.n_rows, postings.n_terms, up(postings.post_off, np.int64),
+                        up(np.ascontiguousarray(postings.post_row, dtype=np.uint32).view(np.int32), np.int32),
+                        up(postings.post_imp, np.float32),
+                        None if tf is None else up(np.ascontiguousarray(tf, dtype=np.uint32).view(np.int32), np.int32),
+                        None if tf is None or dl is None else up(dl, np.int32))
+
+    def _adopt(self, device, n_rows, n_terms, post_off, post_row, post_imp, post_tf, dl, positions=None):
+        """Become the index over these device tensors (the constructor's, or an update's new ones)."""
+        torch = _torch()
+        self.device = device
         self.lib = _lib.load_library()
-        self.n_rows, self.n_terms, self.nnz = postings.n_rows, postings.n_terms, postings.nnz
+        self.n_rows, self.n_terms, self.nnz = int(n_rows), int(n_terms), int(post_row.numel())
+        self.post_off, self.post_row, self.post_imp = post_off, post_row, post_imp
+        # what index maintenance needs beside the postings: the term frequencies and the row lengths
+        self.post_tf, self.dl = post_tf, dl
+        handle = c_void_p()
         with torch.cuda.device(self.device):
-            self.post_off = torch.from_numpy(np.ascontiguousarray(postings.post_off, dtype=np.int64)).to(self.device)
-            # (uint32 rows travel as their int32 bit patterns)
-            self.post_row = torch.from_numpy(np.ascontiguousarray(postings.post_row, dtype=np.uint32).view(np.int32)
-                                             ).to(self.device)
-            self.post_imp = torch.from_numpy(np.ascontiguousarray(postings.post_imp, dtype=np.float32)).to(self.device)
-            handle = c_void_p()
             _lib.check(self.lib.rf_sparse_create(ctypes.byref(handle), self.n_rows, self.n_terms, self.nnz,
                                                  _ptr(self.post_off), _ptr(self.post_row), _ptr(self.post_imp),
                                                  self.device.index))
@@ -869,6 +886,13 @@ class SparseIndex:
         self.text_workspace = None
         self.positions = None   # (pos_off, pos) device tensors once attach_positions has run
         self._lock = threading.Lock()
+        if positions is not None:
+            self._attach(*positions)
+
+    @property
+    def supports_update(self) -> bool:
+        """`appended` / `compacted` can run: the term frequencies and row lengths are on the device."""
+        return self.post_tf is not None and self.dl is not None
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -883,8 +907,140 @@ class SparseIndex:
         with torch.cuda.device(self.device):
             off_d = torch.from_numpy(np.ascontiguousarray(pos_off, dtype=np.int64)).to(self.device)
             pos_d = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.uint32).view(np.int32)).to(self.device)
+        self._attach(off_d, pos_d)
+
+    def _attach(self, off_d, pos_d) -> None:
+        with _torch().cuda.device(self.device):
             _lib.check(self.lib.rf_sparse_attach_positions(self.handle, _ptr(off_d), _ptr(pos_d), pos_d.numel()))
         self.positions = (off_d, pos_d)
+
+    # -- index maintenance (include/ragfin.h, "lexical index maintenance") -----------------
+    def _desc(self, n_rows, n_terms, post_off, post_row, post_tf, positions):
+        """rf_postings over device tensors (kept alive by the caller for the call)."""
+        d = _lib.Postings(int(n_rows), int(n_terms), int(post_row.numel()) if post_row is not None else 0,
+                          int(positions[1].numel()) if positions is not None else 0)
+        d.post_off = None if post_off is None else post_off.data_ptr()
+        d.post_row, d.post_tf = post_row.data_ptr(), post_tf.data_ptr()
+        if positions is not None:
+            d.pos_off, d.pos = positions[0].data_ptr(), positions[1].data_ptr()
+        return d
+
+    def host_array(self, name: str) -> np.ndarray:
+        """post_row / post_tf (uint32) or post_imp (fp32) as a host array (synchronises)."""
+        a = getattr(self, name).cpu().numpy()
+        return a.view(np.uint32) if name in ("post_row", "post_tf") else a
+
+    def _own_desc(self):
+        return self._desc(self.n_rows, self.n_terms, self.post_off, self.post_row, self.post_tf, self.positions)
+
+    def _updated(self, n_rows, post_off, post_row, post_tf, dl, k1, b, positions):
+        """A new SparseIndex over freshly written counts: idf from the host (numpy's log), the impacts from
+        rf_sparse_impacts.  post_off, dl: host arrays (int64); the rest device tensors.  Enqueued on the
+        current stream; nothing here waits for the device."""
+        torch = _torch()
+        from . import lexical
+        n_terms = int(post_off.size) - 1
+        idf = lexical.term_idf(int(n_rows), np.diff(post_off))
+        avgdl = float(dl.sum()) / int(n_rows)
+        with torch.cuda.device(self.device):
+            off_d = torch.from_numpy(np.ascontiguousarray(post_off, dtype=np.int64)).to(self.device)
+            idf_d = torch.from_numpy(np.ascontiguousarray(idf, dtype=np.float64)).to(self.device)
+            dl_d = torch.from_numpy(np.ascontiguousarray(dl, dtype=np.int32)).to(self.device)
+            imp = torch.empty(post_row.numel(), dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.rf_sparse_impacts(_ptr(off_d), _ptr(post_row), _ptr(post_tf), _ptr(idf_d), _ptr(dl_d),
+                                                  int(n_rows), n_terms, post_row.numel(), avgdl, float(k1), float(b),
+                                                  _ptr(imp), _lib.current_stream_ptr()))
+        new = SparseIndex.__new__(SparseIndex)
+        new._adopt(self.device, n_rows, n_terms, off_d, post_row, imp, post_tf, dl_d, positions)
+        return new
+
+    def appended(self, delta, map_old, map_delta, post_off, dl, k1: float, b: float):
+        """The index after an append (rf_sparse_append, rf_sparse_impacts) -> a NEW SparseIndex over new
+        tensors; this one stays valid.  delta: lexical.count_terms of the appended texts; map_old /
+        map_delta: lexical.merge_vocab's term maps; post_off int64 [V + 1], dl int64 [N]: the merged term
+        offsets and every row's length, host arrays.  Positions are carried when attached here."""
+        torch = _torch()
+        if not self.supports_update:
+            raise ValueError("this SparseIndex was built without term frequencies: no incremental update")
+        pos = self.positions is not None
+        n_rows = self.n_rows + int(delta.dl.size)
+        n_terms = int(post_off.size) - 1
+        nnz = self.nnz + delta.nnz
+        with self._lock, torch.cuda.device(self.device):
+            i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).to(self.device)   # noqa: E731
+            i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(self.device)   # noqa: E731
+            pad = lambda a, dt: np.concatenate([np.asarray(a, dtype=dt), np.zeros(1, dtype=dt)])   # noqa: E731  (never empty)
+            d_off, d_row, d_tf = i64(delta.post_off), i32(pad(delta.post_row, np.uint32)), i32(pad(delta.post_tf, np.uint32))
+            d_pos = (i64(delta.pos_off), i32(pad(delta.pos, np.uint32))) if pos else None
+            m_old, m_delta, off_d = i64(pad(map_old, np.int64)), i64(pad(map_delta, np.int64)), i64(post_off)
+            row = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            tf = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            positions = None
+            if pos:
+                n_pos = int(self.positions[1].numel()) + int(delta.pos.size)
+                positions = (torch.empty(nnz + 1, dtype=torch.int64, device=self.device),
+                             torch.empty(max(n_pos, 1), dtype=torch.int32, device=self.device))
+            old_desc = self._own_desc()
+            delta_desc = self._desc(delta.dl.size, len(delta.vocab), d_off, d_row, d_tf, d_pos)
+            delta_desc.nnz = delta.nnz
+            merged_desc = self._desc(n_rows, n_terms, off_d, row, tf, positions)
+            if pos:
+                delta_desc.n_pos = int(delta.pos.size)
+                merged_desc.n_pos = n_pos
+            need = self.lib.rf_sparse_append_workspace_bytes(self.n_terms, len(delta.vocab))
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.rf_sparse_append(ctypes.byref(old_desc), ctypes.byref(delta_desc), _ptr(m_old),
+                                                 _ptr(m_delta), ctypes.byref(merged_desc), _ptr(ws), ws.numel(),
+                                                 _lib.current_stream_ptr()))
+            if pos and n_pos == 0:
+                positions = (positions[0], positions[1][:0])
+        return self._updated(n_rows, post_off, row, tf, dl, k1, b, positions)
+
+    def compacted(self, row_map, dl, k1: float, b: float):
+        """The index after a delete (rf_sparse_compact_plan / _apply, rf_sparse_impacts) -> (a NEW
+        SparseIndex or None when no posting survives, alive bool [V]: the terms that keep a posting,
+        post_off int64: the surviving terms' offsets).  row_map int32 [n_rows]: the new number of every
+        row, -1 for a row that goes; dl int64: the surviving rows' lengths.  One synchronisation, to
+        read the V + 2 raw term offsets back.  This object stays valid."""
+        torch = _torch()
+        if not self.supports_update:
+            raise ValueError("this SparseIndex was built without term frequencies: no incremental update")
+        row_map = np.ascontiguousarray(row_map, dtype=np.int32)
+        if row_map.size != self.n_rows:
+            raise ValueError(f"compacted: a row map of {row_map.size} rows for an index over {self.n_rows}")
+        pos = self.positions is not None
+        with self._lock, torch.cuda.device(self.device):
+            map_d = torch.from_numpy(row_map).to(self.device)
+            dst_post = torch.empty(self.nnz + 1, dtype=torch.int64, device=self.device)
+            dst_pos = torch.empty(self.nnz + 1, dtype=torch.int64, device=self.device) if pos else None
+            term_dst = torch.empty(self.n_terms + 2, dtype=torch.int64, device=self.device)
+            need = self.lib.rf_sparse_compact_workspace_bytes(self.nnz)
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=self.device)
+            old_desc = self._own_desc()
+            _lib.check(self.lib.rf_sparse_compact_plan(ctypes.byref(old_desc), _ptr(map_d), _ptr(dst_post), _ptr(dst_pos),
+                                                       _ptr(term_dst), _ptr(ws), ws.numel(), _lib.current_stream_ptr()))
+            raw = term_dst.cpu().numpy()   # the one synchronisation
+            df = np.diff(raw[:self.n_terms + 1])
+            alive = df > 0
+            post_off = np.zeros(int(alive.sum()) + 1, dtype=np.int64)
+            np.cumsum(df[alive], out=post_off[1:])
+            nnz, n_pos = int(post_off[-1]), int(raw[self.n_terms + 1])
+            if nnz == 0 or dl.size == 0:
+                return None, alive, post_off
+            row = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            tf = torch.empty(nnz, dtype=torch.int32, device=self.device)
+            positions = None
+            if pos:
+                positions = (torch.empty(nnz + 1, dtype=torch.int64, device=self.device),
+                             torch.empty(max(n_pos, 1), dtype=torch.int32, device=self.device))
+            out_desc = self._desc(dl.size, post_off.size - 1, None, row, tf, positions)
+            if pos:
+                out_desc.n_pos = n_pos
+            _lib.check(self.lib.rf_sparse_compact_apply(ctypes.byref(old_desc), _ptr(map_d), _ptr(dst_post), _ptr(dst_pos),
+                                                        ctypes.byref(out_desc), _lib.current_stream_ptr()))
+            if pos and n_pos == 0:
+                positions = (positions[0], positions[1][:0])
+        return self._updated(dl.size, post_off, row, tf, dl, k1, b, positions), alive, post_off
 
     def text_match(self, leaves):
         """Enqueue rf_text_match on the current stream; no host sync.  leaves: (kind, term ids,

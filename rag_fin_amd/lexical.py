@@ -25,6 +25,17 @@ Definition
             r iff some j has p_i at position j + i of r for every i (text_match_reference).
   fusion    fused(d) = sum over the arms a, in arm order, that hold d of weight_a / (rrf_k + rank_a(d)),
             rank 1-based, in fp64; the best k distinct ids by (fused desc, id asc).
+  upkeep     the index after a write equals a build of the surviving texts, bit for bit.
+            With tf kept beside the postings every impact is re-derivable from N, avgdl, df and dl.
+            counts   count_terms(texts): the postings of a text list on its own (its own sorted
+                     dictionary, rows from 0, tf, dl and positions; no impacts).
+            append   rows N_old.. are new.  The dictionary is the sorted union (merge_vocab); per merged
+                     term the list is the old segment, then the delta segment with rows + N_old;
+                     positions follow their postings (append_reference).
+            compact  keep bool [N]: a posting survives iff its row does, rows are renumbered by their
+                     rank among the kept rows, a term whose df became 0 leaves the dictionary and the
+                     later ids move down; positions follow their postings (compact_reference).
+            Then idf from the new N and df (term_idf, on the host) and imp by the formula above.
 """
 from __future__ import annotations
 
@@ -90,12 +101,13 @@ def analyze(texts: Sequence[str]) -> list[list[str]]:
 class Postings:
     """What build_postings returns: the dictionary and the three posting arrays, host numpy."""
 
-    def __init__(self, vocab, post_off, post_row, post_imp, dl, k1, b):
+    def __init__(self, vocab, post_off, post_row, post_imp, dl, k1, b, post_tf=None):
         self.vocab = vocab                        # sorted distinct terms; id = position
         self.term_id = {t: i for i, t in enumerate(vocab)}
         self.post_off = post_off                  # int64 [V + 1]
         self.post_row = post_row                  # uint32 [nnz], ascending within a term
         self.post_imp = post_imp                  # fp32 [nnz]
+        self.post_tf = post_tf                    # uint32 [nnz]: the term frequencies (index maintenance)
         self.dl = dl                              # int64 [N]
         self.k1 = float(k1)
         self.b = float(b)
@@ -115,6 +127,35 @@ class Postings:
     @property
     def avgdl(self) -> float:
         return float(self.dl.sum()) / self.n_rows if self.n_rows else 0.0
+
+
+class LivePostings(Postings):
+    """The Postings of an index that is kept up to date on the device: the dictionary,
+    the term offsets and the row lengths are maintained on the host; post_row, post_imp and post_tf are
+    fetched through `fetch(name)` on first access and kept."""
+
+    def __init__(self, vocab, term_id, post_off, dl, k1, b, fetch):
+        self.vocab = vocab
+        self.term_id = term_id if term_id is not None else {t: i for i, t in enumerate(vocab)}
+        self.post_off = post_off
+        self.dl = dl
+        self.k1 = float(k1)
+        self.b = float(b)
+        self._fetch = fetch
+        self._fetched: dict = {}
+
+    def _array(self, name):
+        if name not in self._fetched:
+            self._fetched[name] = self._fetch(name)
+        return self._fetched[name]
+
+    post_row = property(lambda self: self._array("post_row"))
+    post_imp = property(lambda self: self._array("post_imp"))
+    post_tf = property(lambda self: self._array("post_tf"))
+
+    @property
+    def nnz(self) -> int:
+        return int(self.post_off[-1])
 
 
 def check_bm25_params(k1, b) -> tuple[float, float]:
@@ -145,6 +186,7 @@ def build_postings(texts: Sequence[str], k1: float = DEFAULT_K1, b: float = DEFA
     flat = np.fromiter((term_id[t] for d in docs for t in d), dtype=np.int64, count=int(dl.sum()))
     keys, tfs = np.unique(flat * max(n, 1) + np.repeat(np.arange(n, dtype=np.int64), dl), return_counts=True)
     tids, rows = keys // max(n, 1), keys % max(n, 1)
+    post_tf = tfs.astype(np.uint32)
     tfs = tfs.astype(np.float64)
     df = np.bincount(tids, minlength=len(vocab)).astype(np.float64)
     post_off = np.zeros(len(vocab) + 1, dtype=np.int64)
@@ -152,7 +194,13 @@ def build_postings(texts: Sequence[str], k1: float = DEFAULT_K1, b: float = DEFA
     imp = impacts(tfs, dl[rows].astype(np.float64), df[tids], n, float(dl.sum()) / n if n else 0.0, k1, b)
     if imp.size and not bool((imp >= np.finfo(np.float32).tiny).all() and np.isfinite(imp).all()):
         raise ValueError("BM25 impacts must be positive normal fp32 values (check bm25_k1 / bm25_b)")
-    return Postings(vocab, post_off, rows.astype(np.uint32), imp, dl, k1, b)
+    return Postings(vocab, post_off, rows.astype(np.uint32), imp, dl, k1, b, post_tf)
+
+
+def term_idf(n: int, df) -> np.ndarray:
+    """idf[t] = log(1 + (n - df + 0.5) / (df + 0.5)) in fp64 (numpy's log: the host's, never the device's)."""
+    df = np.asarray(df, dtype=np.float64)
+    return np.log(1.0 + (n - df + 0.5) / (df + 0.5))
 
 
 def impacts(tf, dl, df, n: int, avgdl: float, k1: float, b: float) -> np.ndarray:
@@ -161,7 +209,7 @@ def impacts(tf, dl, df, n: int, avgdl: float, k1: float, b: float) -> np.ndarray
     tf = np.asarray(tf, dtype=np.float64)
     dl = np.asarray(dl, dtype=np.float64)
     df = np.asarray(df, dtype=np.float64)
-    idf = np.log(1.0 + (n - df + 0.5) / (df + 0.5))
+    idf = term_idf(n, df)
     norm = (1.0 - b) + b * (dl / avgdl)
     return (idf * ((tf * (k1 + 1.0)) / (tf + k1 * norm))).astype(np.float32)
 
@@ -215,6 +263,157 @@ def build_positions(postings: Postings, texts: Sequence[str], analyzer: Analyzer
     pos_off = np.zeros(postings.nnz + 1, dtype=np.int64)
     np.cumsum(counts, out=pos_off[1:])
     return pos_off, position[order].astype(np.uint32)
+
+
+# ---- index maintenance (module docstring, "upkeep") -------------------------------------
+class TermCounts:
+    """What count_terms returns: the postings of a text list on its own, without impacts."""
+
+    def __init__(self, vocab, post_off, post_row, post_tf, dl, pos_off, pos):
+        self.vocab = vocab            # sorted distinct terms of these texts
+        self.post_off = post_off      # int64 [V + 1]
+        self.post_row = post_row      # uint32 [nnz], relative to the first text
+        self.post_tf = post_tf        # uint32 [nnz]
+        self.dl = dl                  # int64 [n]
+        self.pos_off = pos_off        # int64 [nnz + 1]
+        self.pos = pos                # uint32 [sum(dl)]
+
+    @property
+    def nnz(self) -> int:
+        return int(self.post_row.size)
+
+
+def count_terms(texts: Sequence[str], analyzer: Analyzer | None = None) -> TermCounts:
+    """The (term, row) counts and token positions of a text list: the analyzer runs once over it."""
+    docs = (analyzer or analyze)(list(texts))
+    n = len(docs)
+    if n != len(texts):
+        raise ValueError("the analyzer must return one term list per text")
+    vocab = sorted({t for d in docs for t in d})
+    term_id = {t: i for i, t in enumerate(vocab)}
+    dl = np.asarray([len(d) for d in docs], dtype=np.int64)
+    total = int(dl.sum())
+    flat = np.fromiter((term_id[t] for d in docs for t in d), dtype=np.int64, count=total)
+    rows = np.repeat(np.arange(n, dtype=np.int64), dl)
+    starts = np.zeros(n, dtype=np.int64)
+    np.cumsum(dl[:-1], out=starts[1:])
+    position = np.arange(total, dtype=np.int64) - np.repeat(starts, dl)
+    keys = flat * max(n, 1) + rows
+    order = np.argsort(keys, kind="stable")   # (term, row); the tokens of one stay in text order
+    ukeys, tfs = np.unique(keys, return_counts=True)
+    post_off = np.zeros(len(vocab) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(ukeys // max(n, 1), minlength=len(vocab)), out=post_off[1:])
+    pos_off = np.zeros(ukeys.size + 1, dtype=np.int64)
+    np.cumsum(tfs, out=pos_off[1:])
+    return TermCounts(vocab, post_off, (ukeys % max(n, 1)).astype(np.uint32), tfs.astype(np.uint32), dl, pos_off,
+                      position[order].astype(np.uint32))
+
+
+def merge_vocab(vocab: list, term_id: dict, delta_vocab: list):
+    """The sorted union of two sorted dictionaries -> (merged list, map_old int64 [V_old], map_delta
+    int64 [V_delta]): the merged id of every old and of every delta term.  O(V_old + V_delta log V_old);
+    with no new term the old list itself comes back."""
+    import bisect
+    fresh = [t for t in delta_vocab if t not in term_id]
+    at = np.asarray([bisect.bisect_left(vocab, t) for t in fresh], dtype=np.int64)   # ascending: fresh is sorted
+    map_old = np.arange(len(vocab), dtype=np.int64)
+    merged = vocab
+    if fresh:
+        map_old += np.searchsorted(at, map_old, side="right")
+        merged, last = [], 0
+        for t, i in zip(fresh, at.tolist()):
+            merged.extend(vocab[last:i])
+            merged.append(t)
+            last = i
+        merged.extend(vocab[last:])
+    fresh_id = dict(zip(fresh, (at + np.arange(at.size)).tolist()))
+    map_delta = np.asarray([fresh_id[t] if t in fresh_id else int(map_old[term_id[t]]) for t in delta_vocab],
+                           dtype=np.int64)
+    return merged, map_old, map_delta
+
+
+def merged_offsets(n_terms: int, post_off, map_old, delta_post_off, map_delta) -> np.ndarray:
+    """post_off int64 [n_terms + 1] of an append: a merged term's df is its old df plus its delta df."""
+    df = np.zeros(n_terms, dtype=np.int64)
+    df[map_old] += np.diff(post_off)
+    df[map_delta] += np.diff(delta_post_off)
+    out = np.zeros(n_terms + 1, dtype=np.int64)
+    np.cumsum(df, out=out[1:])
+    return out
+
+
+def rescored(vocab, post_off, post_row, post_tf, dl, k1: float, b: float) -> Postings:
+    """Postings over the given counts: idf and the impacts by the definition."""
+    n = int(dl.size)
+    df = np.diff(post_off)
+    imp = impacts(post_tf, dl[post_row.astype(np.int64)], np.repeat(df, df), n,
+                  float(dl.sum()) / n if n else 0.0, k1, b)
+    return Postings(vocab, post_off, post_row, imp, dl, k1, b, post_tf)
+
+
+def _segments(lo, hi):
+    """The indices of the ranges [lo[i], hi[i]) one after the other (two int64 arrays)."""
+    n = hi - lo
+    total = int(n.sum())
+    starts = np.zeros(n.size, dtype=np.int64)
+    np.cumsum(n[:-1], out=starts[1:])
+    return np.repeat(lo - starts, n) + np.arange(total, dtype=np.int64)
+
+
+def append_reference(postings: Postings, positions, delta: TermCounts):
+    """The definition of an append in numpy -> (Postings, (pos_off, pos) | None).  positions: the pair
+    of build_positions for `postings`, or None to leave positions out.  For tests and tools only."""
+    vocab, map_old, map_delta = merge_vocab(postings.vocab, postings.term_id, delta.vocab)
+    n_old = postings.n_rows
+    post_off = merged_offsets(len(vocab), postings.post_off, map_old, delta.post_off, map_delta)
+    nnz = int(post_off[-1])
+    row = np.zeros(nnz, dtype=np.uint32)
+    tf = np.zeros(nnz, dtype=np.uint32)
+    cnt = np.zeros(nnz, dtype=np.int64)
+    # where every old and every delta posting goes: the old segment first, the delta segment at the end
+    t_old = np.repeat(np.arange(len(postings.vocab)), np.diff(postings.post_off))
+    dst_old = post_off[map_old[t_old]] + (np.arange(postings.nnz) - postings.post_off[t_old])
+    t_d = np.repeat(np.arange(len(delta.vocab)), np.diff(delta.post_off))
+    dst_d = post_off[map_delta[t_d] + 1] - delta.post_off[t_d + 1] + np.arange(delta.nnz)
+    row[dst_old], tf[dst_old] = postings.post_row, postings.post_tf
+    row[dst_d], tf[dst_d] = delta.post_row + np.uint32(n_old), delta.post_tf
+    out_pos = None
+    if positions is not None:
+        pos_off_old, pos_old = positions
+        cnt[dst_old] = np.diff(pos_off_old)
+        cnt[dst_d] = np.diff(delta.pos_off)
+        pos_off = np.zeros(nnz + 1, dtype=np.int64)
+        np.cumsum(cnt, out=pos_off[1:])
+        pos = np.zeros(int(pos_off[-1]), dtype=np.uint32)
+        pos[_segments(pos_off[dst_old], pos_off[dst_old + 1])] = pos_old
+        pos[_segments(pos_off[dst_d], pos_off[dst_d + 1])] = delta.pos
+        out_pos = (pos_off, pos)
+    dl = np.concatenate([postings.dl, delta.dl])
+    return rescored(vocab, post_off, row, tf, dl, postings.k1, postings.b), out_pos
+
+
+def compact_reference(postings: Postings, positions, keep):
+    """The definition of a compaction by a keep mask (bool [N]) in numpy -> (Postings, (pos_off, pos)
+    | None).  For tests and tools only."""
+    keep = np.asarray(keep, dtype=bool)
+    row_map = np.where(keep, np.cumsum(keep) - 1, -1)
+    kept = keep[postings.post_row.astype(np.int64)]
+    term = np.repeat(np.arange(postings.n_terms), np.diff(postings.post_off))
+    df = np.bincount(term[kept], minlength=postings.n_terms)
+    alive = df > 0
+    vocab = [t for t, a in zip(postings.vocab, alive.tolist()) if a]
+    post_off = np.zeros(len(vocab) + 1, dtype=np.int64)
+    np.cumsum(df[alive], out=post_off[1:])
+    row = row_map[postings.post_row[kept].astype(np.int64)].astype(np.uint32)
+    out_pos = None
+    if positions is not None:
+        pos_off_old, pos_old = positions
+        cnt = np.diff(pos_off_old)[kept]
+        pos_off = np.zeros(cnt.size + 1, dtype=np.int64)
+        np.cumsum(cnt, out=pos_off[1:])
+        q = np.flatnonzero(kept)
+        out_pos = (pos_off, pos_old[_segments(pos_off_old[q], pos_off_old[q + 1])])
+    return rescored(vocab, post_off, row, postings.post_tf[kept], postings.dl[keep], postings.k1, postings.b), out_pos
 
 
 def _term_slice(postings: Postings, t: int) -> tuple[int, int]:

@@ -406,6 +406,12 @@ class CorpusStore:
         # (the token positions a PHRASE_MATCH filter needs live on that SparseIndex: attached once,
         # by the first such filter, and gone with it on any mutation)
         self._sparse_lock = threading.Lock()
+        # index maintenance: the last built (postings, SparseIndex, analyzer, params) and, in
+        # order, the mutations since -- ("delete", keep mask) / ("append", texts) -- which the next
+        # _sparse_index() replays through SparseIndex.compacted / .appended instead of building whole.
+        # Written under the write lock, replayed under `_sparse_lock` with the read side held.
+        self._lexical_kept = None
+        self._lexical_log: list = []
         # bumped by every change of the rows (insert, delete, upsert, drop): a search_iterator's
         # bound is a row number, so it refuses to go on once this has moved
         self._mutations = 0
@@ -431,6 +437,24 @@ class CorpusStore:
             self._pk_row.clear()
             self._dcols = None
             self._sparse = None
+            self._forget_lexical()
+
+    def _forget_lexical(self) -> None:
+        """Drop the retained lexical state: the next _sparse_index() builds whole."""
+        self._lexical_kept = None
+        self._lexical_log = []
+
+    def _log_lexical(self, kind: str, arg) -> None:
+        """Record a mutation for the next replay (caller holds the write lock).  A log longer than
+        LEXICAL_LOG_MAX is not worth replaying step by step: the state is dropped."""
+        if self._lexical_kept is None:
+            return
+        if len(self._lexical_log) >= self.LEXICAL_LOG_MAX:
+            self._forget_lexical()
+            return
+        self._lexical_log.append((kind, arg))
+
+    LEXICAL_LOG_MAX = 64
 
     @property
     def num_entities(self) -> int:
@@ -465,14 +489,19 @@ class CorpusStore:
         field_name "sparse" with {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25",
         "params": {"bm25_k1": 1.2, "bm25_b": 0.75}} declares the lexical index over the `text` column
         and leaves the vector index as it is.  The posting lists are built from the texts by the first
-        BM25 search and rebuilt, whole, by the first one after any add / insert / upsert / delete
-        (there is no incremental maintenance)."""
+        BM25 search (on the host).  After an add / insert / upsert / delete the first BM25 search or
+        keyword filter brings them up to date on the GPU: the mutations since the last build are replayed
+        through SparseIndex.appended / .compacted, which analyse only the appended texts and leave the
+        arrays bit for bit as a build of the surviving rows would.  They are built whole
+        instead after drop(), create_index / drop_index of "sparse", a changed `analyzer`, more than
+        LEXICAL_LOG_MAX pending mutations, when no row held a term, or when a replay raised."""
         params = dict(index_params or {})
         if field_name == "sparse":
             sparse = self._check_sparse_params(params)
             with self._rw.write():
                 self._sparse_params = sparse
                 self._sparse = None
+                self._forget_lexical()
             return
         itype, metric = self._check_index_params(field_name, params)
         with self._rw.write():
@@ -523,6 +552,7 @@ class CorpusStore:
             with self._rw.write():
                 self._sparse_params = None
                 self._sparse = None
+                self._forget_lexical()
             return
         with self._rw.write():
             if self._has_sq8:
@@ -589,7 +619,8 @@ class CorpusStore:
     def _append_rows(self, ids, cols) -> None:
         """The host side of an append: the pk map and the six scalar columns."""
         texts, periods, chunk_types, statement_types, primary_values = cols
-        self._sparse = None   # the lexical index is rebuilt by the next BM25 search
+        self._sparse = None   # the lexical index is brought up to date by the next BM25 search (DESIGN §4.4k)
+        self._log_lexical("append", list(texts))
         self._mutations += 1
         base = self.num_entities
         for j, pk in enumerate(ids):
@@ -670,7 +701,8 @@ class CorpusStore:
         keep_mask = ~mask
         keep = np.flatnonzero(keep_mask)
         n_old = self.num_entities
-        self._sparse = None   # the lexical index is rebuilt by the next BM25 search
+        self._sparse = None   # the lexical index is brought up to date by the next BM25 search
+        self._log_lexical("delete", keep_mask)
         self._mutations += 1
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
@@ -954,15 +986,60 @@ class CorpusStore:
         return [data] if isinstance(data, str) else list(data)
 
     def _sparse_index(self):
-        """(postings, SparseIndex | None) over the current text column, built when a mutation (or
-        create_index) has invalidated the last one.  None: no row holds a term.  Caller holds the
-        read lock."""
+        """(postings, SparseIndex | None) over the current text column.  After a mutation the last one
+        is brought up to date on the GPU (_replay_lexical); it is built whole, on the host, the first
+        time and whenever there is nothing to replay from.  None: no row holds a term.  Caller holds
+        the read lock."""
         with self._sparse_lock:
             if self._sparse is None:
                 p = self._sparse_params
-                postings = lexical.build_postings(self.columns["text"], p["bm25_k1"], p["bm25_b"], self.analyzer)
-                self._sparse = (postings, SparseIndex(postings, self.index.device) if postings.nnz else None)
+                built = self._replay_lexical((p["bm25_k1"], p["bm25_b"]))
+                if built is None:
+                    postings = lexical.build_postings(self.columns["text"], p["bm25_k1"], p["bm25_b"], self.analyzer)
+                    built = (postings, SparseIndex(postings, self.index.device) if postings.nnz else None)
+                self._lexical_log = []
+                self._lexical_kept = None
+                if built[1] is not None and getattr(built[1], "supports_update", False):
+                    self._lexical_kept = (built[0], built[1], self.analyzer, (p["bm25_k1"], p["bm25_b"]))
+                self._sparse = built   # (published whole: a replay that raised left nothing behind)
             return self._sparse
+
+    def _replay_lexical(self, params):
+        """The pending mutations applied to the retained index, in order, through SparseIndex.compacted /
+        .appended -> (postings, SparseIndex), or None when there is nothing to replay from, the retained
+        state was built with other parameters or another analyzer, no posting survives, or a step raised
+        (the caller then builds whole).  The analyzer sees the appended texts only, once."""
+        kept = self._lexical_kept
+        if kept is None or kept[2] is not self.analyzer or kept[3] != params:
+            return None
+        postings, sp = kept[0], kept[1]
+        k1, b = params
+        try:
+            vocab, term_id, post_off, dl = postings.vocab, postings.term_id, postings.post_off, postings.dl
+            for kind, arg in self._lexical_log:
+                if kind == "delete":
+                    row_map = np.where(arg, np.cumsum(arg) - 1, -1).astype(np.int32)
+                    dl = dl[arg]
+                    sp, alive, post_off = sp.compacted(row_map, dl, k1, b)
+                    if sp is None:
+                        return None
+                    if not alive.all():
+                        vocab, term_id = list(itertools.compress(vocab, alive.tolist())), None
+                else:
+                    delta = lexical.count_terms(arg, self.analyzer)
+                    if term_id is None:
+                        term_id = {t: i for i, t in enumerate(vocab)}
+                    merged, map_old, map_delta = lexical.merge_vocab(vocab, term_id, delta.vocab)
+                    if merged is not vocab:
+                        vocab, term_id = merged, None
+                    post_off = lexical.merged_offsets(len(vocab), post_off, map_old, delta.post_off, map_delta)
+                    dl = np.concatenate([dl, delta.dl])
+                    sp = sp.appended(delta, map_old, map_delta, post_off, dl, k1, b)
+            if dl.size != self.num_entities:
+                return None
+            return lexical.LivePostings(vocab, term_id, post_off, dl, k1, b, sp.host_array), sp
+        except Exception:   # a half-updated index is never published: the caller builds whole
+            return None
 
     def _sparse_arm(self, texts, limit: int, expr):
         """The BM25 arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors, or None

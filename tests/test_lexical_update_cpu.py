@@ -1,0 +1,470 @@
+"""Lexical index maintenance without a GPU: the numpy definitions of an append and of a
+compaction against a fresh build of the surviving texts, the store's life cycle -- which mutations
+are replayed through SparseIndex.appended / .compacted, which force a whole build -- with doubles,
+and the host-side argument checks of the new rf_sparse_* entry points.
+
+UpdatableSparse stands in for SparseIndex: it answers searches with bm25_reference and implements
+the update methods through lexical.append_reference / compact_reference, checking on the way that
+the host bookkeeping the store hands it (term maps, offsets, row lengths) is the definition's."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import synth_text
+from rag_fin_amd import _lib, filter_expr, lexical
+from rag_fin_amd import store as store_mod
+from rag_fin_amd.store import SCALAR_FIELDS, CorpusStore
+
+SPARSE = {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"}
+BM25 = {"metric_type": "BM25"}
+PARAMS = [(1.2, 0.75), (0.0, 0.75), (1.2, 0.0), (1.2, 1.0)]
+EDGE_TEXTS = ["", "   ", "!!! aaa first of all terms", "zzzz zzzz the last of all terms", "eps eps eps eps",
+              "a term in the middle: mmmm"]
+
+
+def assert_same_postings(p, q):
+    assert list(p.vocab) == list(q.vocab)
+    assert p.term_id == q.term_id
+    for name in ("post_off", "post_row", "post_tf", "dl"):
+        a, b = np.asarray(getattr(p, name)), np.asarray(getattr(q, name))
+        assert a.shape == b.shape and np.array_equal(a, b), name
+    assert np.array_equal(np.asarray(p.post_imp).view(np.uint32), np.asarray(q.post_imp).view(np.uint32))
+    assert (p.k1, p.b, p.n_rows, p.n_terms, p.nnz) == (q.k1, q.b, q.n_rows, q.n_terms, q.nnz)
+
+
+def assert_fresh(p, positions, texts, k1, b):
+    q = lexical.build_postings(texts, k1, b)
+    assert_same_postings(p, q)
+    pos_off, pos = lexical.build_positions(q, texts)
+    assert np.array_equal(positions[0], pos_off) and np.array_equal(positions[1], pos)
+    assert positions[1].dtype == np.uint32 and positions[0].dtype == np.int64
+
+
+# ---- the definitions ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k1,b", PARAMS)
+def test_append_and_compact_definitions_equal_a_fresh_build(k1, b):
+    rng = np.random.default_rng(7)
+    pool = synth_text.retemplated_texts(160, 3) + EDGE_TEXTS
+    cur = pool[:60]
+    p = lexical.build_postings(cur, k1, b)
+    assert p.post_tf.dtype == np.uint32 and p.post_tf.shape == p.post_row.shape
+    positions = lexical.build_positions(p, cur)
+    for step in range(6):
+        add = [pool[i] for i in rng.integers(0, len(pool), int(rng.integers(1, 12)))]
+        if step == 0:
+            add = list(EDGE_TEXTS)                       # new terms before, between and after all old ones
+        if step == 1:
+            add = ["", "  "]                             # rows without a token
+        if step == 2:
+            add = add + ["zzzz once more", "and zzzz zzzz"]
+        p, positions = lexical.append_reference(p, positions, lexical.count_terms(add))
+        cur = cur + add
+        assert_fresh(p, positions, cur, k1, b)
+        keep = rng.random(len(cur)) > 0.25
+        if step == 2:                                    # every row holding one term: the term leaves the dictionary
+            keep = np.array(["zzzz" not in lexical.basic_tokens(t) for t in cur])
+            assert not keep.all() and "zzzz" in p.term_id
+        p, positions = lexical.compact_reference(p, positions, keep)
+        cur = [t for t, k in zip(cur, keep.tolist()) if k]
+        assert_fresh(p, positions, cur, k1, b)
+        if step == 2:
+            assert "zzzz" not in p.term_id
+
+
+def test_count_terms_is_a_build_without_impacts():
+    texts = synth_text.retemplated_texts(40, 5) + EDGE_TEXTS
+    c = lexical.count_terms(texts)
+    q = lexical.build_postings(texts)
+    pos_off, pos = lexical.build_positions(q, texts)
+    assert c.vocab == q.vocab and c.nnz == q.nnz
+    for a, b in ((c.post_off, q.post_off), (c.post_row, q.post_row), (c.post_tf, q.post_tf), (c.dl, q.dl),
+                 (c.pos_off, pos_off), (c.pos, pos)):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
+    empty = lexical.count_terms(["", " "])
+    assert empty.vocab == [] and empty.nnz == 0 and empty.post_off.tolist() == [0] and empty.pos_off.tolist() == [0]
+
+
+def test_merge_vocab_maps_both_sides():
+    old = ["b", "d", "f"]
+    tid = {t: i for i, t in enumerate(old)}
+    merged, mo, md = lexical.merge_vocab(old, tid, ["a", "d", "e", "g"])
+    assert merged == ["a", "b", "d", "e", "f", "g"] and mo.tolist() == [1, 2, 4] and md.tolist() == [0, 2, 3, 5]
+    merged, mo, md = lexical.merge_vocab(old, tid, ["b", "f"])
+    assert merged is old and mo.tolist() == [0, 1, 2] and md.tolist() == [0, 2]
+    merged, mo, md = lexical.merge_vocab(old, tid, [])
+    assert merged is old and md.size == 0
+
+
+# ---- doubles -----------------------------------------------------------------------------------------------
+class FakeIndex:
+    def __init__(self, dim=8, capacity=64, device=None):
+        self.dim, self.capacity, self.device, self.size = dim, capacity, torch.device("cpu"), 0
+
+    def add(self, rows):
+        self.size += rows.shape[0]
+
+    def reset(self):
+        self.size = 0
+
+    def compact(self, keep, window_rows=None):
+        self.size = len(keep)
+
+    def to_fp16(self, x, normalize=True):
+        return torch.as_tensor(np.asarray(x, dtype=np.float32)).half()
+
+
+class PlainSparse:
+    """A double WITHOUT the update methods (what the older CPU tests use)."""
+    built = []
+
+    def __init__(self, postings, device=None):
+        self.postings = postings
+        type(self).built.append(self)
+
+    def search(self, q_off, q_term, q_weight, k, id_base=0, filt=None, want_exact=True):
+        s, i, e = lexical.bm25_reference(self.postings, q_off, q_term, q_weight, k, id_base=id_base)
+        return torch.from_numpy(s), torch.from_numpy(i), None
+
+
+class UpdatableSparse(PlainSparse):
+    """A double WITH them: the numpy definitions, and a record of the calls."""
+    built = []
+    calls = []
+    fail_next = False
+    supports_update = True
+
+    def host_array(self, name):
+        return getattr(self.postings, name)
+
+    def _child(self, postings):
+        new = object.__new__(UpdatableSparse)
+        new.postings = postings
+        return new
+
+    def appended(self, delta, map_old, map_delta, post_off, dl, k1, b):
+        UpdatableSparse.calls.append(("appended", int(delta.dl.size)))
+        if UpdatableSparse.fail_next:
+            UpdatableSparse.fail_next = False
+            raise RuntimeError("the device said no")
+        want_vocab, want_old, want_delta = lexical.merge_vocab(self.postings.vocab, self.postings.term_id, delta.vocab)
+        assert np.array_equal(map_old, want_old) and np.array_equal(map_delta, want_delta)
+        new, _ = lexical.append_reference(self.postings, None, delta)
+        assert np.array_equal(post_off, new.post_off) and np.array_equal(dl, new.dl)
+        assert (k1, b) == (self.postings.k1, self.postings.b)
+        return self._child(new)
+
+    def compacted(self, row_map, dl, k1, b):
+        UpdatableSparse.calls.append(("compacted", int((np.asarray(row_map) < 0).sum())))
+        keep = np.asarray(row_map) >= 0
+        assert np.array_equal(np.asarray(row_map)[keep], np.arange(int(keep.sum())))
+        new, _ = lexical.compact_reference(self.postings, None, keep)
+        assert np.array_equal(dl, new.dl)
+        alive = np.array([t in new.term_id for t in self.postings.vocab], dtype=bool)
+        return (self._child(new) if new.nnz else None), alive, new.post_off
+
+
+class RecordingAnalyzer:
+    def __init__(self):
+        self.calls = []
+
+    def __call__(self, texts):
+        self.calls.append(list(texts))
+        return lexical.analyze(texts)
+
+
+class HostStore(CorpusStore):
+    """delete(expr) evaluated with the parser's host semantics (rf_filter_eval is the GPU tests')."""
+
+    def _match_mask(self, expr):
+        node = filter_expr.parse(expr)
+        return np.array([node.eval({f: self.columns[f][r] for f in SCALAR_FIELDS})
+                         for r in range(self.num_entities)], dtype=bool)
+
+
+TEXTS = ["basic eps was 15.22 in q1", "diluted eps was 14.90", "net profit rose in q1", "net interest income grew",
+         "total deposits grew", "advances grew faster", "capital ratio tier one", "eps eps eps", "q2 profit fell",
+         "nothing else here"]
+
+
+def cols(ids, texts):
+    n = len(ids)
+    return [list(ids), list(texts), np.ones((n, 8), dtype=np.float32), ["Q0"] * n, ["a"] * n, ["s"] * n, [1.0] * n]
+
+
+@pytest.fixture
+def updatable(monkeypatch):
+    monkeypatch.setattr(store_mod, "SparseIndex", UpdatableSparse)
+    UpdatableSparse.built = []
+    UpdatableSparse.calls = []
+    UpdatableSparse.fail_next = False
+
+
+def make_store(analyzer=None, texts=TEXTS):
+    st = HostStore("c", dim=8, capacity=1024, index=FakeIndex(capacity=1024))
+    st.analyzer = analyzer
+    st.insert(cols([f"k{i}" for i in range(len(texts))], texts))
+    st.create_index("sparse", SPARSE)
+    return st
+
+
+def eps_ids(st):
+    return sorted(h.id for h in st.search(["eps"], "sparse", BM25, limit=20)[0])
+
+
+def assert_published_is_fresh(st):
+    p = st._sparse_params
+    assert_same_postings(st._sparse[0], lexical.build_postings(st.columns["text"], p["bm25_k1"], p["bm25_b"]))
+
+
+# ---- the store's life cycle ------------------------------------------------------------------------------------
+def test_every_mutation_is_replayed_once_and_only_new_texts_are_analysed(updatable):
+    rec = RecordingAnalyzer()
+    st = make_store(rec)
+    assert eps_ids(st) == ["k0", "k1", "k7"]
+    assert rec.calls == [TEXTS, ["eps"]] and len(UpdatableSparse.built) == 1      # the first build is whole
+    steps = [
+        (lambda: st.add(["n1"], ["fresh eps row"], np.ones((1, 8), dtype=np.float32), ["Q0"], ["a"], ["s"], [1.0]),
+         [("appended", 1)], [["fresh eps row"]], ["k0", "k1", "k7", "n1"]),
+        (lambda: st.insert(cols(["n2", "n3"], ["aardvark eps", ""])),
+         [("appended", 2)], [["aardvark eps", ""]], ["k0", "k1", "k7", "n1", "n2"]),
+        (lambda: st.upsert(cols(["k1", "n9"], ["restated: no such word", "zzzz eps"])),
+         [("compacted", 1), ("appended", 2)], [["restated: no such word", "zzzz eps"]], ["k0", "k7", "n1", "n2", "n9"]),
+        (lambda: st.delete('id in ["k7", "n2"]'),
+         [("compacted", 2)], [], ["k0", "n1", "n9"]),
+    ]
+    for mutate, calls, analysed, ids in steps:
+        rec.calls.clear()
+        UpdatableSparse.calls.clear()
+        before = st._sparse[1]
+        mutate()
+        assert st._sparse is None                                                  # as ever
+        assert eps_ids(st) == ids
+        assert UpdatableSparse.calls == calls                                      # one replay, in order
+        assert rec.calls == analysed + [["eps"]]                                   # surviving rows: never again
+        assert len(UpdatableSparse.built) == 1                                     # no whole build
+        assert st._sparse[1] is not before
+        assert_published_is_fresh(st)
+        assert eps_ids(st) == ids and UpdatableSparse.calls == calls               # reused while nothing changes
+
+
+def test_several_mutations_before_one_search_replay_in_order(updatable):
+    rec = RecordingAnalyzer()
+    st = make_store(rec)
+    eps_ids(st)
+    rec.calls.clear()
+    st.insert(cols(["a1"], ["eps one"]))
+    st.delete('id in ["k0", "k1"]')
+    st.upsert(cols(["a1", "a2"], ["eps one again", "two"]))
+    st.delete('id in ["absent"]')                                                  # matches nothing: not logged
+    st.insert(cols(["a3"], ["eps three"]))
+    assert eps_ids(st) == ["a1", "a3", "k7"]
+    assert UpdatableSparse.calls == [("appended", 1), ("compacted", 2), ("compacted", 1), ("appended", 2), ("appended", 1)]
+    assert rec.calls == [["eps one"], ["eps one again", "two"], ["eps three"], ["eps"]]
+    assert len(UpdatableSparse.built) == 1
+    assert_published_is_fresh(st)
+
+
+def whole_builds(mutate_and_more):
+    """The whole builds (constructor calls of the double) a step causes, and that no update method ran."""
+    n = len(UpdatableSparse.built)
+    UpdatableSparse.calls.clear()
+    mutate_and_more()
+    assert UpdatableSparse.calls == []
+    return len(UpdatableSparse.built) - n
+
+
+def test_each_discard_rule_leads_to_a_whole_build(updatable, tmp_path):
+    st = make_store()
+    eps_ids(st)
+
+    def after_create_index():
+        st.insert(cols(["b1"], ["eps b1"]))
+        st.create_index("sparse", dict(SPARSE, params={"bm25_b": 0.5}))
+        assert eps_ids(st) == ["b1", "k0", "k1", "k7"]
+    assert whole_builds(after_create_index) == 1
+
+    def after_drop_index():
+        st.insert(cols(["b2"], ["eps b2"]))
+        st.drop_index(field_name="sparse")
+        st.create_index("sparse", SPARSE)
+        assert "b2" in eps_ids(st)
+    assert whole_builds(after_drop_index) == 1
+
+    def after_a_changed_analyzer():
+        st.insert(cols(["b3"], ["eps b3"]))
+        st.analyzer = RecordingAnalyzer()
+        assert "b3" in eps_ids(st)
+        assert st.analyzer.calls[0] == st.columns["text"]
+    assert whole_builds(after_a_changed_analyzer) == 1
+
+    def then_updates_again():
+        st.insert(cols(["b4"], ["eps b4"]))
+        assert "b4" in eps_ids(st)
+        assert UpdatableSparse.calls == [("appended", 1)]
+        UpdatableSparse.calls.clear()
+    assert whole_builds(then_updates_again) == 0
+
+    def after_too_many_pending_mutations():
+        for i in range(CorpusStore.LEXICAL_LOG_MAX + 1):
+            st.insert(cols([f"m{i}"], [f"eps m{i}"]))
+        assert "m0" in eps_ids(st)
+    assert whole_builds(after_too_many_pending_mutations) == 1
+
+    def after_drop():
+        st.drop()
+        assert eps_ids(st) == []                                                   # no postings: no index
+        st.insert(cols(["c1"], ["eps c1"]))
+        assert eps_ids(st) == ["c1"]
+    assert whole_builds(after_drop) == 1
+
+    st.delete('id in ["c1"]')
+    st.insert(cols(["c2"], [""]))
+    assert eps_ids(st) == [] and st._sparse[1] is None                             # (the replay found no posting left)
+
+    def after_no_row_held_a_term():
+        st.insert(cols(["c3"], ["eps c3"]))
+        assert eps_ids(st) == ["c3"]
+    assert whole_builds(after_no_row_held_a_term) == 1
+    assert_published_is_fresh(st)
+
+
+def test_a_delete_of_every_posting_falls_back_to_a_whole_build(updatable):
+    st = make_store(texts=["eps", ""])
+    assert eps_ids(st) == ["k0"]
+    st.delete('id in ["k0"]')
+    assert eps_ids(st) == [] and st._sparse[1] is None
+    assert UpdatableSparse.calls == [("compacted", 1)]
+
+
+def test_a_loaded_store_builds_whole(updatable, tmp_path):
+    class Loadable(HostStore):
+        def __init__(self, name="c", dim=8, capacity=64, device=None, metric_type="COSINE", index=None):
+            CorpusStore.__init__(self, name, dim=dim, capacity=capacity, metric_type=metric_type, index=index or FakeIndex())
+
+        def save(self, path):
+            import os
+            os.makedirs(path, exist_ok=True)
+            self._write_meta(path, self.num_entities)
+
+        def _load_rows(self, path, n, lo, hi, chunk_rows):
+            self.index.size = n
+
+    st = Loadable()
+    st.insert(cols([f"k{i}" for i in range(len(TEXTS))], TEXTS))
+    st.create_index("sparse", SPARSE)
+    eps_ids(st)
+    st.insert(cols(["x"], ["eps x"]))
+    st.save(str(tmp_path / "s"))
+    back = Loadable.load_from(str(tmp_path / "s"))
+    assert back._lexical_kept is None and back._lexical_log == []
+    assert whole_builds(lambda: eps_ids(back)) == 1
+    assert eps_ids(back) == ["k0", "k1", "k7", "x"]
+
+
+def test_a_double_without_the_update_methods_always_gets_a_whole_build(monkeypatch):
+    monkeypatch.setattr(store_mod, "SparseIndex", PlainSparse)
+    PlainSparse.built = []
+    rec = RecordingAnalyzer()
+    st = make_store(rec)
+    eps_ids(st)
+    for i, mutate in enumerate([lambda: st.insert(cols(["p1"], ["eps p1"])), lambda: st.delete('id in ["k0"]'),
+                                lambda: st.upsert(cols(["k1"], ["eps again"]))]):
+        rec.calls.clear()
+        mutate()
+        assert st._lexical_kept is None and st._lexical_log == []
+        eps_ids(st)
+        assert len(PlainSparse.built) == i + 2
+        assert rec.calls[0] == st.columns["text"]                                  # the whole column, as before
+        assert_same_postings(st._sparse[0], lexical.build_postings(st.columns["text"]))
+
+
+def test_an_exception_inside_a_replay_is_followed_by_a_whole_build(updatable):
+    st = make_store()
+    eps_ids(st)
+    st.delete('id in ["k0"]')
+    st.insert(cols(["e1"], ["eps e1"]))
+    UpdatableSparse.fail_next = True
+    assert eps_ids(st) == ["e1", "k1", "k7"]                                       # correct all the same
+    assert UpdatableSparse.calls == [("compacted", 1), ("appended", 1)] and len(UpdatableSparse.built) == 2
+    assert st._sparse[1] is UpdatableSparse.built[-1]                              # the whole build is what is published
+    assert_published_is_fresh(st)
+    st.insert(cols(["e2"], ["eps e2"]))                                            # and the next update replays again
+    assert eps_ids(st) == ["e1", "e2", "k1", "k7"] and len(UpdatableSparse.built) == 2
+
+
+# ---- host-side argument checks (no device) ---------------------------------------------------------------------
+GOOD, ODD = 0x10000, 0x10004   # never dereferenced: every call below fails a host-side check first
+
+
+def desc(n_rows=10, n_terms=4, nnz=20, n_pos=0, pos=False, **over):
+    d = _lib.Postings(n_rows, n_terms, nnz, n_pos if pos else 0)
+    d.post_off, d.post_row, d.post_tf = GOOD, GOOD, GOOD
+    if pos:
+        d.pos_off, d.pos = GOOD, GOOD
+    for k, v in over.items():
+        setattr(d, k, v)
+    return d
+
+
+def test_host_side_argument_checks_need_no_gpu():
+    lib = _lib.load_library()
+    INVALID = -1
+    ref = ctypes.byref
+    P = ctypes.c_void_p
+    assert _lib.RF_LEX_CHUNK == 1024
+
+    def impacts(off=GOOD, row=GOOD, tf=GOOD, idf=GOOD, dl=GOOD, n=10, v=4, nnz=20, avgdl=3.0, k1=1.2, b=0.75, imp=GOOD):
+        return lib.rf_sparse_impacts(P(off), P(row), P(tf), P(idf), P(dl), n, v, nnz, avgdl, k1, b, P(imp), None)
+    for bad in (dict(off=None), dict(row=None), dict(tf=None), dict(idf=None), dict(dl=None), dict(imp=None),
+                dict(off=ODD), dict(tf=ODD), dict(idf=ODD), dict(imp=ODD), dict(n=-1), dict(n=0), dict(n=1 << 31), dict(v=-1),
+                dict(nnz=-5), dict(avgdl=0.0), dict(avgdl=float("nan")), dict(k1=-1.0), dict(b=1.5), dict(b=float("nan"))):
+        assert impacts(**bad) == INVALID, bad
+        assert b"rf_sparse_impacts" in lib.rf_last_error()
+
+    assert lib.rf_sparse_append_workspace_bytes(-1, 0) == 0 and lib.rf_sparse_append_workspace_bytes(0, -1) == 0
+    assert lib.rf_sparse_append_workspace_bytes(4, 2) >= 2 * 6 * 8
+
+    def append(old=None, delta=None, merged=None, mo=GOOD, md=GOOD, ws=GOOD, ws_bytes=1 << 20):
+        old = desc() if old is None else old
+        delta = desc(n_rows=2, n_terms=2, nnz=3) if delta is None else delta
+        merged = desc(n_rows=12, n_terms=5, nnz=23) if merged is None else merged
+        return lib.rf_sparse_append(ref(old) if old else None, ref(delta) if delta else None, P(mo), P(md),
+                                    ref(merged) if merged else None, P(ws), ws_bytes, None)
+    for bad in (dict(old=False), dict(delta=False), dict(merged=False), dict(mo=None), dict(md=None), dict(ws=None),
+                dict(mo=ODD), dict(ws=ODD), dict(ws_bytes=8), dict(old=desc(post_row=None)), dict(old=desc(post_off=ODD)),
+                dict(delta=desc(n_rows=2, n_terms=2, nnz=-3)), dict(delta=desc(n_rows=-2, n_terms=2, nnz=3)),
+                dict(merged=desc(n_rows=12, n_terms=5, nnz=22)), dict(merged=desc(n_rows=11, n_terms=5, nnz=23)),
+                dict(merged=desc(n_rows=12, n_terms=3, nnz=23)), dict(merged=desc(n_rows=12, n_terms=7, nnz=23)),
+                dict(merged=desc(n_rows=12, n_terms=5, nnz=23, pos=True, n_pos=9)),        # positions on one side only
+                dict(old=desc(pos_off=GOOD)),                                              # pos_off without pos
+                dict(old=desc(n_rows=1 << 31))):
+        assert append(**bad) == INVALID, bad
+        assert b"rf_sparse_append" in lib.rf_last_error()
+
+    assert lib.rf_sparse_compact_workspace_bytes(0) == 0 and lib.rf_sparse_compact_workspace_bytes(-4) == 0
+    assert lib.rf_sparse_compact_workspace_bytes(_lib.RF_LEX_CHUNK + 1) == 2 * 2 * 8
+
+    def plan(old=None, rm=GOOD, dpost=GOOD, dpos=None, tdst=GOOD, ws=GOOD, ws_bytes=1 << 20):
+        old = desc() if old is None else old
+        return lib.rf_sparse_compact_plan(ref(old) if old else None, P(rm), P(dpost), P(dpos), P(tdst), P(ws), ws_bytes, None)
+    for bad in (dict(old=False), dict(rm=None), dict(dpost=None), dict(tdst=None), dict(ws=None), dict(rm=ODD),
+                dict(dpost=ODD), dict(tdst=ODD), dict(ws=ODD), dict(ws_bytes=8), dict(dpos=GOOD),   # dst_pos without positions
+                dict(old=desc(pos=True, n_pos=30)),                                                 # positions without dst_pos
+                dict(old=desc(nnz=0)), dict(old=desc(nnz=-1)), dict(old=desc(n_rows=0)), dict(old=desc(n_terms=0)),
+                dict(old=desc(post_off=None)), dict(old=desc(post_tf=ODD))):
+        assert plan(**bad) == INVALID, bad
+        assert b"rf_sparse_compact_plan" in lib.rf_last_error()
+
+    def apply(old=None, out=None, rm=GOOD, dpost=GOOD, dpos=None):
+        old = desc() if old is None else old
+        out = desc(n_rows=8, n_terms=3, nnz=15) if out is None else out
+        return lib.rf_sparse_compact_apply(ref(old) if old else None, P(rm), P(dpost), P(dpos), ref(out) if out else None, None)
+    for bad in (dict(old=False), dict(out=False), dict(rm=None), dict(dpost=None), dict(rm=ODD), dict(dpost=ODD),
+                dict(dpos=GOOD), dict(out=desc(n_rows=8, n_terms=3, nnz=15, pos=True, n_pos=5)),
+                dict(out=desc(n_rows=8, n_terms=3, nnz=21)), dict(out=desc(n_rows=11, n_terms=3, nnz=15)),
+                dict(out=desc(n_rows=8, n_terms=3, nnz=0)), dict(out=desc(n_rows=8, n_terms=3, nnz=15, post_row=ODD)),
+                dict(old=desc(nnz=-1)), dict(old=desc(post_tf=None))):
+        assert apply(**bad) == INVALID, bad
+        assert b"rf_sparse_compact_apply" in lib.rf_last_error()
