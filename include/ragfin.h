@@ -595,6 +595,37 @@ int rf_sparse_compact_plan(const rf_postings* old_p, const int32_t* row_map_dev,
                            void* stream);
 int rf_sparse_compact_apply(const rf_postings* old_p, const int32_t* row_map_dev, const int64_t* dst_post_dev,
                             const int64_t* dst_pos_dev, const rf_postings* out, void* stream);
+/* ---- lexical index build: a token stream -> the posting arrays, on the device ------------------------
+ * What rag_fin_amd/lexical.py's count_terms computes, from term ids instead of strings (DESIGN 4.4l;
+ * the definition in numpy: lexical.counts_from_tokens).  tok_dev int32 [n_tokens]: the term id of
+ * every token of the corpus in (row, position) order (rf_analyze's tok); row_start_dev int64
+ * [n_rows + 1]: where each row's tokens start, closed by n_tokens (rows may be empty).  A stable sort
+ * by term id puts the tokens in (term, row, position) order; a token whose (term, row) differs from
+ * its predecessor's heads a posting, the exclusive scan of the heads numbers the postings, a run's
+ * length is its tf, a head's sorted index its pos_off, and pos[i] is sorted token i's index minus its
+ * row's start.  The sort is a least-significant-digit radix sort with 8-bit digits,
+ * ceil(bits(n_terms - 1) / 8) passes over tiles of RF_LEX_SORT_TILE tokens, the token index as
+ * payload; the scans are the reduce-then-scan over chunks of RF_LEX_CHUNK of the compaction plan.
+ *   rf_sparse_count_workspace_bytes   0 = out of range (n_tokens or n_terms < 1 or >= 2^31)
+ *   rf_sparse_count_plan    writes post_off_dev int64 [n_terms + 1] and totals_dev int64 [2] = { nnz,
+ *                           n_pos = n_tokens } (8-byte aligned: it may follow post_off in one buffer,
+ *                           read back in one copy), and leaves the sorted stream in the workspace
+ *   rf_sparse_count_apply   same sizes and the same, untouched workspace.  out: post_row / post_tf
+ *                           [nnz] are written, with want_positions also pos_off int64 [nnz + 1] and pos
+ *                           uint32 [n_pos]; nnz and n_pos are capacities (a slot past them is not
+ *                           written); post_off is not read.
+ * Stream-ordered, no allocation, no synchronisation; integers only, LDS counters, no global atomics:
+ * the same bits on every run.  RF_ERR_INVALID from host-side checks before any device call, as above.
+ * A term id outside [0, n_terms) is clamped into it; a malformed row_start gives wrong rows, never an
+ * out-of-range access.  New in this build; the reference has no lexical index. */
+#define RF_LEX_SORT_TILE 4096
+size_t rf_sparse_count_workspace_bytes(int64_t n_tokens, int64_t n_terms);
+int rf_sparse_count_plan(const int32_t* tok_dev, const int64_t* row_start_dev, int64_t n_tokens, int64_t n_rows,
+                         int64_t n_terms, int64_t* post_off_dev, int64_t* totals_dev, void* workspace_dev,
+                         size_t workspace_bytes, void* stream);
+int rf_sparse_count_apply(const int64_t* row_start_dev, int64_t n_tokens, int64_t n_rows, int64_t n_terms,
+                          void* workspace_dev, size_t workspace_bytes, const rf_postings* out, int want_positions,
+                          void* stream);
 /* Cross-shard merge after the RCCL all-gather: in [W, B, k] (exact fp64, id
  * int64) -> out [B, k] by (score desc, id asc).  New in this build (the
  * reference is single-process); see SURVEY.md 8e. */
@@ -833,6 +864,34 @@ int rf_utf8_offsets(const char* text_bytes, int64_t n_bytes, const int64_t* char
  * n_threads <= 0: one per hardware thread (at most 64). */
 int rf_tokenize_batch(const rf_tokenizer_t* t, const char* text_bytes, const int64_t* offsets, int n,
                       int max_len, int32_t* ids_out, int32_t* lens_out, int n_threads);
+
+/* ---- analyzer: texts -> the term-id stream that rf_sparse_count_plan consumes -------------------
+ * The basic tokenisation in front of the lexical index, host code, multi-threaded: the
+ * ASCII rules rf_tokenize_batch applies before its WordPiece step -- ASCII control characters dropped
+ * without splitting on them, " \t\n\r" the whitespace, A-Z lower-cased, every character of the four
+ * ASCII punctuation ranges and every code point of punct_cps (int32 [n_punct], any order; NULL with
+ * 0) a term of its own, every other byte sequence a word character.  Text with other non-ASCII
+ * characters is pre-normalised by the caller (rag_fin_amd/lexical.py, analyze_native).
+ * text_bytes / offsets int64 [n + 1]: as in rf_tokenize_batch.  Malformed UTF-8 is memory-safe (a
+ * sequence cut short ends with its text) and gives terms that are not UTF-8.
+ * The result, behind the handle:
+ *   dictionary  the distinct terms in ascending order of their UTF-8 BYTES (= code-point order, the
+ *               order of Python's sorted() on str); term id = position.  vocab_blob holds every term
+ *               followed by '\n' (no term contains one), vocab_off int64 [n_terms + 1] where each
+ *               starts: term t = blob[vocab_off[t], vocab_off[t + 1] - 1).
+ *   tok         int32 [n_tokens]: the term id of every token in text order, texts back to back
+ *   dl          int64 [n]: the tokens of every text
+ * The result does not depend on n_threads (<= 0: one per hardware thread, at most 64; at least 64
+ * texts per thread).  rf_analysis_sizes: sizes4 <- { n, n_tokens, n_terms, bytes of vocab_blob }.
+ * rf_analysis_read copies into the caller's arrays; a NULL array is skipped.  More than 2^31 - 1
+ * distinct terms: RF_ERR_INVALID.  Host memory that ran out, in the call or in one of its threads:
+ * RF_ERR_CAPACITY (*out stays NULL, nothing is leaked), so that a caller can tell it from a bad argument.  New in this build; the reference has no lexical index. */
+typedef struct rf_analysis rf_analysis_t;
+int rf_analyze(const char* text_bytes, const int64_t* offsets, int64_t n, const int32_t* punct_cps, int n_punct,
+               int n_threads, rf_analysis_t** out);
+int rf_analysis_sizes(const rf_analysis_t* a, int64_t* sizes4);
+int rf_analysis_read(const rf_analysis_t* a, char* vocab_blob, int64_t* vocab_off, int32_t* tok, int64_t* dl);
+int rf_analysis_destroy(rf_analysis_t* a);
 
 #ifdef __cplusplus
 }

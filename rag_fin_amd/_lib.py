@@ -28,6 +28,8 @@ RF_TEXT_PHRASE = 2
 RF_TEXT_MAX_LEAVES = 16      # text leaves one rf_text_match call (one filter expression) holds
 # lexical index maintenance (include/ragfin.h, "lexical index maintenance")
 RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
+# lexical index build (include/ragfin.h, "lexical index build")
+RF_LEX_SORT_TILE = 4096      # tokens per workgroup of a radix-sort pass
 
 
 class RagfinError(RuntimeError):
@@ -160,6 +162,11 @@ SIGNATURES = {
     "rf_sparse_compact_plan": (c_int, [POINTER(Postings), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
     "rf_sparse_compact_apply": (c_int, [POINTER(Postings), c_void_p, c_void_p, c_void_p, POINTER(Postings), c_void_p]),
+    "rf_sparse_count_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rf_sparse_count_plan": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
+    "rf_sparse_count_apply": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_size_t, POINTER(Postings), c_int,
+                                      c_void_p]),
     "rf_fuse_rrf": (c_int, [c_int, c_void_p, c_int, POINTER(c_double), c_double, c_int, c_int, c_void_p, c_void_p,
                             c_void_p, c_void_p]),
     "rf_merge_shards": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
@@ -181,6 +188,10 @@ SIGNATURES = {
     "rf_tokenizer_special_ids": (c_int, [c_void_p, c_void_p]),
     "rf_tokenize_batch": (c_int, [c_void_p, c_char_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int]),
     "rf_utf8_offsets": (c_int, [c_char_p, c_int64, c_void_p, c_int, c_void_p]),
+    "rf_analyze": (c_int, [c_char_p, c_void_p, c_int64, c_void_p, c_int, c_int, POINTER(c_void_p)]),
+    "rf_analysis_sizes": (c_int, [c_void_p, c_void_p]),
+    "rf_analysis_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rf_analysis_destroy": (c_int, [c_void_p]),
     "rf_debug_scores": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rf_sq8_storage_bytes": (c_size_t, [c_int, c_int64]),
     "rf_index_attach_sq8": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),

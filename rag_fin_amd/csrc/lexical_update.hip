@@ -12,13 +12,7 @@
 // posting arrays, the chunk's term range found once by two binary searches and a posting's term inside
 // that range.  Integers only apart from the impacts, no atomics: the same bits on every run.
 // Mirrored in numpy by rag_fin_amd/lexical.py (append_reference, compact_reference, impacts).
-#include "rf_internal.h"
-
-#define LEX_THREADS 256
-#define LEX_WAVES (LEX_THREADS / 64)
-#define LEX_PER_THREAD (RF_LEX_CHUNK / LEX_THREADS)
-
-static_assert(RF_LEX_CHUNK % LEX_THREADS == 0, "a thread owns whole strided slots of a chunk");
+#include "lexical_common.h"
 
 // the device view of one rf_postings (n_pos, pos_off, pos: 0 / nullptr without positions)
 struct LexSide {
@@ -36,8 +30,6 @@ struct LexOut {
   uint32_t* pos;
   int64_t nnz, n_pos;
 };
-
-__device__ __forceinline__ int64_t lex_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the last t in [lo, hi] with off[t] <= p (lo if none): the term that owns posting p
 __device__ __forceinline__ int64_t lex_term_of(const int64_t* __restrict__ off, int64_t lo, int64_t hi, int64_t p) {
@@ -110,41 +102,7 @@ __global__ void __launch_bounds__(LEX_THREADS) k_lex_impacts(LexImpacts P) {
   }
 }
 
-// ---- the prefix sum: reduce per chunk, scan the chunk sums, scan inside the chunks -------------------
-// Exclusive scan of (a, b) over the workgroup in thread order; (ta, tb) = the workgroup's totals.
-__device__ __forceinline__ void lex_block_scan2(int64_t& a, int64_t& b, int64_t& ta, int64_t& tb, int64_t (*s_w)[2]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  long long ia = a, ib = b;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long va = __shfl_up(ia, o), vb = __shfl_up(ib, o);
-    if (lane >= o) {
-      ia += va;
-      ib += vb;
-    }
-  }
-  if (lane == 63) {
-    s_w[w][0] = ia;
-    s_w[w][1] = ib;
-  }
-  __syncthreads();
-  int64_t oa = 0, ob = 0;
-  ta = 0;
-  tb = 0;
-#pragma unroll
-  for (int i = 0; i < LEX_WAVES; ++i) {
-    if (i < w) {
-      oa += s_w[i][0];
-      ob += s_w[i][1];
-    }
-    ta += s_w[i][0];
-    tb += s_w[i][1];
-  }
-  __syncthreads();   // s_w is free for the next round
-  a = oa + (int64_t)ia - a;
-  b = ob + (int64_t)ib - b;
-}
-
+// ---- the compaction plan (the prefix sum helpers: lexical_common.h) ------------------------------------
 struct LexPlan {
   LexSide S;
   const int32_t* row_map;   // [n_rows]: the new row number, or < 0

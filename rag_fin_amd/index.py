@@ -889,6 +889,108 @@ class SparseIndex:
         if positions is not None:
             self._attach(*positions)
 
+    # -- the device build (include/ragfin.h, "lexical index build") ------------------------
+    @staticmethod
+    def count_tokens(n_terms: int, tok, dl, device=None, positions: bool = False, timing: dict | None = None):
+        """rf_sparse_count_plan / _apply over a token stream -> (post_off int64 [n_terms + 1] host array,
+        post_row, post_tf int32 device tensors [nnz] (uint32 bit patterns), (pos_off, pos) device tensors
+        or None): what lexical.counts_from_tokens defines.  tok int32 [n_tokens] (>= 1 token): the term id
+        of every token in (row, position) order; dl int64 [n]: the tokens per row.  One synchronisation,
+        to read post_off and the totals back.  timing: filled with the seconds of the stages (each ended
+        by a synchronisation of its own: for tools)."""
+        import time
+        torch = _torch()
+        device = require_gpu(device)
+        lib = _lib.load_library()
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        dl = np.asarray(dl, dtype=np.int64)
+        n_tokens, n_rows, n_terms = int(tok.size), int(dl.size), int(n_terms)
+        row_start = np.zeros(n_rows + 1, dtype=np.int64)
+        np.cumsum(dl, out=row_start[1:])
+        if n_tokens < 1 or int(row_start[-1]) != n_tokens:
+            raise ValueError(f"count_tokens: {n_tokens} tokens for rows that hold {int(row_start[-1])} (at least one)")
+        need = lib.rf_sparse_count_workspace_bytes(n_tokens, n_terms)
+        if need == 0:
+            raise ValueError(f"count_tokens: {n_tokens} tokens over {n_terms} terms is out of range")
+
+        def lap(name, t0):
+            if timing is not None:
+                torch.cuda.synchronize(device)
+                timing[name] = timing.get(name, 0.0) + time.perf_counter() - t0
+            return time.perf_counter()
+        with torch.cuda.device(device):
+            t0 = time.perf_counter()
+            tok_d = torch.from_numpy(tok).to(device)
+            start_d = torch.from_numpy(row_start).to(device)
+            t0 = lap("upload_s", t0)
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            head = torch.empty(n_terms + 3, dtype=torch.int64, device=device)   # post_off, then nnz and n_pos
+            stream = _lib.current_stream_ptr()
+            _lib.check(lib.rf_sparse_count_plan(_ptr(tok_d), _ptr(start_d), n_tokens, n_rows, n_terms, _ptr(head),
+                                                c_void_p(head.data_ptr() + 8 * (n_terms + 1)), _ptr(ws), need, stream))
+            t0 = lap("plan_s", t0)
+            raw = head.cpu().numpy()   # the one synchronisation
+            t0 = lap("readback_s", t0)
+            post_off, nnz, n_pos = raw[:n_terms + 1].copy(), int(raw[n_terms + 1]), int(raw[n_terms + 2])
+            if not (1 <= nnz <= n_tokens and n_pos == n_tokens and int(post_off[-1]) == nnz and int(post_off[0]) == 0):
+                raise RuntimeError(f"rf_sparse_count_plan: inconsistent totals (nnz {nnz}, n_pos {n_pos}, {n_tokens} tokens)")
+            row = torch.empty(nnz, dtype=torch.int32, device=device)
+            tf = torch.empty(nnz, dtype=torch.int32, device=device)
+            pos = None
+            if positions:
+                pos = (torch.empty(nnz + 1, dtype=torch.int64, device=device),
+                       torch.empty(n_tokens, dtype=torch.int32, device=device))
+            out = _lib.Postings(n_rows, n_terms, nnz, n_tokens if positions else 0)
+            out.post_row, out.post_tf = row.data_ptr(), tf.data_ptr()
+            if positions:
+                out.pos_off, out.pos = pos[0].data_ptr(), pos[1].data_ptr()
+            _lib.check(lib.rf_sparse_count_apply(_ptr(start_d), n_tokens, n_rows, n_terms, _ptr(ws), need, ctypes.byref(out),
+                                                 1 if positions else 0, stream))
+            lap("apply_s", t0)
+        return post_off, row, tf, pos
+
+    @classmethod
+    def from_tokens(cls, vocab_size: int, tok, dl, k1: float, b: float, device=None, positions: bool = False,
+                    timing: dict | None = None):
+        """The index of a corpus given as a token stream (lexical.analyze_native's tok and dl), built on the
+        device: count_tokens, idf on the host (lexical.term_idf: numpy's log), rf_sparse_impacts.  The arrays
+        equal lexical.build_postings' bit for bit; `host_post_off` keeps the term offsets for the caller's
+        Postings.  build_postings' guard -- every impact a positive normal fp32 value -- is checked here on
+        the device array (one reduction, one synchronisation); ValueError as there.  `supports_update` holds."""
+        import time
+        torch = _torch()
+        from . import lexical
+        device = require_gpu(device)
+        k1, b = lexical.check_bm25_params(k1, b)
+        dl = np.asarray(dl, dtype=np.int64)
+        post_off, row, tf, pos = cls.count_tokens(vocab_size, tok, dl, device, positions, timing)
+        t0 = time.perf_counter()
+        seed = cls.__new__(cls)
+        seed.device, seed.lib = device, _lib.load_library()
+        new = seed._updated(int(dl.size), post_off, row, tf, dl, k1, b, pos)
+        with torch.cuda.device(device):
+            tiny = float(np.finfo(np.float32).tiny)
+            ok = bool((torch.isfinite(new.post_imp) & (new.post_imp >= tiny)).all().item())
+        if timing is not None:
+            timing["impacts_s"] = timing.get("impacts_s", 0.0) + time.perf_counter() - t0
+        if not ok:
+            raise ValueError("BM25 impacts must be positive normal fp32 values (check bm25_k1 / bm25_b)")
+        new.host_post_off = post_off
+        return new
+
+    def attach_token_positions(self, tok, dl) -> None:
+        """The token positions of an index that from_tokens built, from the same token stream: the device
+        build again, with positions, whose (pos_off, pos) are attached.  ValueError when the stream does
+        not give this index's postings."""
+        torch = _torch()
+        post_off, row, tf, pos = self.count_tokens(self.n_terms, tok, dl, self.device, positions=True)
+        with torch.cuda.device(self.device):
+            same = int(row.numel()) == self.nnz and int(np.asarray(dl).size) == self.n_rows and \
+                bool(torch.equal(row, self.post_row)) and (self.post_tf is None or bool(torch.equal(tf, self.post_tf)))
+        if not same:
+            raise ValueError("attach_token_positions: the token stream does not give the postings of this index")
+        self._attach(*pos)
+
     @property
     def supports_update(self) -> bool:
         """`appended` / `compacted` can run: the term frequencies and row lengths are on the device."""

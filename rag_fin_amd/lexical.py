@@ -36,6 +36,10 @@ Definition
                      rank among the kept rows, a term whose df became 0 leaves the dictionary and the
                      later ids move down; positions follow their postings (compact_reference).
             Then idf from the new N and df (term_idf, on the host) and imp by the formula above.
+  build      build_postings / build_positions below are the definition and the route of a
+            store with a custom analyzer.  Otherwise the product builds through analyze_native (the
+            analyzer in C++: dictionary, a term id per token, tokens per row) and SparseIndex.from_tokens
+            (the postings from that stream, on the device); counts_from_tokens restates the device part.
 """
 from __future__ import annotations
 
@@ -96,6 +100,175 @@ def basic_tokens(text: str) -> list[str]:
 def analyze(texts: Sequence[str]) -> list[list[str]]:
     """The default analyzer: basic_tokens of every text."""
     return [basic_tokens(t) for t in texts]
+
+
+# ---- the native analyzer (csrc/analyzer.cpp; DESIGN §4.4l) -------------------------------------------
+_NATIVE = None
+# whitespace of str.split() that the native rules do not split on (they know " \t\n\r" only)
+_ODD_SPACE = re.compile(r"[^\S \t\n\r]")
+
+
+def _native_tables():
+    """(regex of the characters that need the Python pre-pass, the 'simple' non-ASCII punctuation as
+    int32, and the two str.translate tables of the pre-pass), built once."""
+    global _NATIVE
+    if _NATIVE is None:
+        from .tokenizer import _LazyTable, _clean_map, _simple_tables
+        complex_re, punct = _simple_tables()
+        # precomposed Hangul has no entry in unicodedata.decomposition() (it decomposes by rule), yet NFD takes it
+        # apart and nothing puts it together again: a term keeps the jamo, so such text needs the pre-pass too
+        complex_re = re.compile("(?:" + complex_re.pattern + ")|[\uac00-\ud7a3]")
+
+        def mn_punct(cp):
+            cat = unicodedata.category(chr(cp))
+            if cat == "Mn":
+                return None
+            return " " + chr(cp) + " " if cp >= 128 and cat.startswith("P") else cp
+
+        def clean(cp):
+            # ASCII controls go HERE, not on the native side: what basic_tokens drops before NFC and lower() must
+            # be gone before them too (a control between a cased letter and a capital sigma decides Final_Sigma)
+            if cp < 128:
+                return None if (cp < 32 and cp not in (9, 10, 13)) or cp == 127 else cp
+            return _clean_map(cp)
+
+        _NATIVE = (complex_re, np.asarray(punct, dtype=np.int32), _LazyTable(clean), _LazyTable(mn_punct))
+    return _NATIVE
+
+
+def _prenormalise(text: str, clean_tab, mn_punct_tab) -> str:
+    """Non-ASCII text -> a string on which the native rules give basic_tokens(text): clean, NFC, lower,
+    NFD, Mn stripped and non-ASCII punctuation padded with spaces, with C-speed string primitives.  What
+    the tables cannot express (a character str.split() splits on is still there) comes back as the
+    tokens of basic_tokens joined by spaces: each of them re-tokenises to itself."""
+    s = text.translate(clean_tab)
+    if not unicodedata.is_normalized("NFC", s):
+        s = unicodedata.normalize("NFC", s)
+    s = s.lower()
+    if not unicodedata.is_normalized("NFD", s):
+        s = unicodedata.normalize("NFD", s)
+    s = s.translate(mn_punct_tab)
+    if _ODD_SPACE.search(s) is not None:
+        return " ".join(basic_tokens(text))
+    return s
+
+
+def native_input(texts: list) -> tuple:
+    """What analyze_native hands to rf_analyze: (the texts' UTF-8 bytes back to back, pre-normalised
+    where they need it, and their byte offsets int64 [n + 1])."""
+    from ctypes import c_void_p
+    from . import _lib
+    from .tokenizer import only_simple_non_ascii
+    lib = _lib.load_library()
+    n = len(texts)
+    complex_re, _, clean_tab, mn_punct_tab = _native_tables()
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    joined = "".join(texts)
+    blob = None
+    if joined.isascii() or only_simple_non_ascii(joined, complex_re):
+        try:
+            blob = joined.encode("utf-8")
+        except UnicodeEncodeError:               # a lone surrogate somewhere: the per-text path sorts it out
+            blob = None
+    if blob is not None:
+        np.cumsum(np.fromiter(map(len, texts), dtype=np.int64, count=n), out=offsets[1:])
+        if len(blob) != int(offsets[n]):         # non-ASCII present: characters -> bytes
+            chars = offsets.copy()
+            if lib.rf_utf8_offsets(blob, len(blob), c_void_p(chars.ctypes.data), n, c_void_p(offsets.ctypes.data)) != 0:
+                raise RuntimeError("rf_utf8_offsets: the character counts do not match the blob")
+    else:
+        enc = []
+        for t in texts:
+            if not t.isascii() and complex_re.search(t) is not None:
+                t = _prenormalise(t, clean_tab, mn_punct_tab)
+            try:
+                enc.append(t.encode("utf-8"))
+            except UnicodeEncodeError:           # lone surrogates: basic_tokens drops them
+                enc.append(" ".join(basic_tokens(t)).encode("utf-8"))
+        np.cumsum([len(b) for b in enc], out=offsets[1:])
+        blob = b"".join(enc)
+    return blob, offsets
+
+
+def analyze_native(texts: Sequence[str], n_threads: int = 0, timing: dict | None = None):
+    """`analyze` through rf_analyze (csrc/analyzer.cpp) -> (vocab list[str], tok int32 [n_tokens], dl
+    int64 [n]): the sorted distinct terms, the term id of every token in text order (texts back to
+    back) and the tokens per text; [vocab[i] for i in tok] cut by dl is analyze(texts), for every str.
+    Division of labour as in WordPieceTokenizer.batch_native: an ASCII batch, or one whose non-ASCII
+    characters are all "simple", goes over as one joined blob; other non-ASCII texts are pre-normalised
+    one by one (_prenormalise).  timing: a dict the seconds of the stages are added into (for tools)."""
+    import time
+    from ctypes import byref, c_void_p
+    from . import _lib
+    texts = list(texts)
+    n = len(texts)
+    if n == 0:
+        return [], np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int64)
+    if n_threads <= 0 and n < 64:
+        n_threads = 1        # a query-sized batch: no pool
+    if n_threads <= 0:       # the CPUs the process may burn, not the ones it may run on: hostcpu.py
+        from .hostcpu import cpu_budget
+        n_threads = min(cpu_budget(), 64)
+    t_start = time.perf_counter()
+    lib = _lib.load_library()
+    blob, offsets = native_input(texts)
+    punct = _native_tables()[1]
+    t_native = time.perf_counter()
+    handle = c_void_p()
+    _lib.check(lib.rf_analyze(blob, c_void_p(offsets.ctypes.data), n, c_void_p(punct.ctypes.data), int(punct.size),
+                              int(n_threads), byref(handle)))
+    try:
+        sizes = np.zeros(4, dtype=np.int64)
+        _lib.check(lib.rf_analysis_sizes(handle, c_void_p(sizes.ctypes.data)))
+        vocab_blob = np.empty(max(int(sizes[3]), 1), dtype=np.uint8)
+        tok = np.empty(int(sizes[1]), dtype=np.int32)
+        dl = np.empty(n, dtype=np.int64)
+        _lib.check(lib.rf_analysis_read(handle, c_void_p(vocab_blob.ctypes.data), None,
+                                        c_void_p(tok.ctypes.data) if tok.size else None, c_void_p(dl.ctypes.data)))
+    finally:
+        lib.rf_analysis_destroy(handle)
+    t_read = time.perf_counter()
+    # every term is followed by '\n' and holds none: one decode and one split give the list
+    vocab = vocab_blob[:int(sizes[3])].tobytes().decode("utf-8").split("\n")[:-1]
+    if len(vocab) != int(sizes[2]):
+        raise RuntimeError("analyze_native: the dictionary does not split into its terms")
+    t_done = time.perf_counter()
+    if timing is not None:
+        for k, v in (("prepass_s", t_native - t_start), ("native_s", t_read - t_native), ("vocab_s", t_done - t_read)):
+            timing[k] = timing.get(k, 0.0) + v
+    return vocab, tok, dl
+
+
+def tokens_from_native(vocab, tok, dl) -> list[list[str]]:
+    """The term lists that (vocab, tok, dl) of analyze_native stand for (tests and tools)."""
+    terms = [vocab[i] for i in np.asarray(tok).tolist()]
+    ends = np.cumsum(dl).tolist()
+    return [terms[e - int(d):e] for e, d in zip(ends, np.asarray(dl).tolist())]
+
+
+def counts_from_tokens(tok, dl, n_terms: int, vocab=None) -> "TermCounts":
+    """count_terms from term ids instead of strings: the definition, in numpy, of what
+    rf_sparse_count_plan / _apply compute (csrc/lexical_build.hip).  tok int32 [n_tokens]: the term id
+    of every token in (row, position) order, dl int64 [n]: the tokens per row.  A stable sort by term
+    id alone gives (term, row, position) order; a token whose (term, row) differs from its
+    predecessor's heads a posting.  For tests and tools only."""
+    tok = np.clip(np.asarray(tok, dtype=np.int64), 0, max(int(n_terms) - 1, 0))
+    dl = np.asarray(dl, dtype=np.int64)
+    total = int(tok.size)
+    row_start = np.zeros(dl.size + 1, dtype=np.int64)
+    np.cumsum(dl, out=row_start[1:])
+    order = np.argsort(tok, kind="stable")
+    term = tok[order]
+    row = np.searchsorted(row_start, order, side="right") - 1   # the last row that starts at or before the token
+    head = np.ones(total, dtype=bool)
+    head[1:] = (term[1:] != term[:-1]) | (row[1:] != row[:-1])
+    scan = np.zeros(total + 1, dtype=np.int64)
+    np.cumsum(head, out=scan[1:])
+    post_off = scan[np.searchsorted(term, np.arange(int(n_terms) + 1), side="left")]
+    first = np.flatnonzero(head)
+    pos_off = np.concatenate([first, [total]]).astype(np.int64)
+    return TermCounts(vocab, post_off, row[first].astype(np.uint32), np.diff(pos_off).astype(np.uint32), dl, pos_off,
+                      (order - row_start[row]).astype(np.uint32))
 
 
 class Postings:

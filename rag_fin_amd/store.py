@@ -412,6 +412,8 @@ class CorpusStore:
         # Written under the write lock, replayed under `_sparse_lock` with the read side held.
         self._lexical_kept = None
         self._lexical_log: list = []
+        self.lexical_fallback_reason = None   # why the device route last gave way to the host's (None: it never did)
+        self._lexical_route = "host"        # what built the retained index whole: "host" or "device" 
         # bumped by every change of the rows (insert, delete, upsert, drop): a search_iterator's
         # bound is a row number, so it refuses to go on once this has moved
         self._mutations = 0
@@ -489,7 +491,8 @@ class CorpusStore:
         field_name "sparse" with {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25",
         "params": {"bm25_k1": 1.2, "bm25_b": 0.75}} declares the lexical index over the `text` column
         and leaves the vector index as it is.  The posting lists are built from the texts by the first
-        BM25 search (on the host).  After an add / insert / upsert / delete the first BM25 search or
+        BM25 search: through the native analyzer and the device build (RAGFIN_LEXICAL_BUILD=
+        host|device|auto pins the route), on the host with a custom `analyzer`.  After an add / insert / upsert / delete the first BM25 search or
         keyword filter brings them up to date on the GPU: the mutations since the last build are replayed
         through SparseIndex.appended / .compacted, which analyse only the appended texts and leave the
         arrays bit for bit as a build of the surviving rows would.  They are built whole
@@ -987,13 +990,17 @@ class CorpusStore:
 
     def _sparse_index(self):
         """(postings, SparseIndex | None) over the current text column.  After a mutation the last one
-        is brought up to date on the GPU (_replay_lexical); it is built whole, on the host, the first
-        time and whenever there is nothing to replay from.  None: no row holds a term.  Caller holds
-        the read lock."""
+        is brought up to date on the GPU (_replay_lexical); it is built whole the first
+        time and whenever there is nothing to replay from -- on the device (_build_lexical_device), or on
+        the host with a custom analyzer, with RAGFIN_LEXICAL_BUILD=host or when the device route raised.
+        None: no row holds a term.  Caller holds the read lock."""
         with self._sparse_lock:
             if self._sparse is None:
                 p = self._sparse_params
                 built = self._replay_lexical((p["bm25_k1"], p["bm25_b"]))
+                if built is None:
+                    built = self._build_lexical_device(p["bm25_k1"], p["bm25_b"])
+                    self._lexical_route = "device" if built is not None else "host"
                 if built is None:
                     postings = lexical.build_postings(self.columns["text"], p["bm25_k1"], p["bm25_b"], self.analyzer)
                     built = (postings, SparseIndex(postings, self.index.device) if postings.nnz else None)
@@ -1003,6 +1010,46 @@ class CorpusStore:
                     self._lexical_kept = (built[0], built[1], self.analyzer, (p["bm25_k1"], p["bm25_b"]))
                 self._sparse = built   # (published whole: a replay that raised left nothing behind)
             return self._sparse
+
+    def _lexical_build_route(self) -> str:
+        """"device" or "host" for a whole build of the lexical index: RAGFIN_LEXICAL_BUILD=host|device|auto
+        (default auto: the device for every non-empty corpus -- it was the faster route at every size
+        measured, 10 k rows included: DESIGN §5.0m).  A custom analyzer and an empty corpus always build
+        on the host."""
+        want = os.environ.get("RAGFIN_LEXICAL_BUILD", "auto").strip().lower() or "auto"
+        if want not in ("host", "device", "auto"):
+            raise ValueError(f"RAGFIN_LEXICAL_BUILD must be host, device or auto, got {want!r}")
+        n = self.num_entities
+        if self.analyzer is not None or n == 0 or want == "host":
+            return "host"
+        return "device"
+
+    def _build_lexical_device(self, k1, b):
+        """The whole build through the native analyzer and SparseIndex.from_tokens ->
+        (LivePostings, SparseIndex), or None when the route is the host's, no row holds a term, or the
+        native route raised (the caller then builds on the host, exactly as before; _lexical_fell_back says so)."""
+        if self._lexical_build_route() != "device":
+            return None
+        try:
+            vocab, tok, dl = lexical.analyze_native(self.columns["text"])
+            if tok.size == 0:
+                return None
+            sp = SparseIndex.from_tokens(len(vocab), tok, dl, k1, b, self.index.device)
+            return lexical.LivePostings(vocab, None, sp.host_post_off, dl, k1, b, sp.host_array), sp
+        except Exception as e:
+            if isinstance(e, ValueError) and "BM25 impacts" in str(e):   # build_postings' guard: the host build raises the same
+                raise
+            self._lexical_fell_back("the first build", e)
+            return None
+
+    def _lexical_fell_back(self, what: str, exc: Exception) -> None:
+        """The device route raised and the host route takes over: the answers are the same, the build is
+        many times slower, so it must not pass unseen -- one RuntimeWarning, and the reason
+        kept in `lexical_fallback_reason` for whoever looks later."""
+        import warnings
+        self.lexical_fallback_reason = f"{what}: {type(exc).__name__}: {exc}"
+        warnings.warn(f"lexical index: the device route failed for {self.lexical_fallback_reason}; building on the host",
+                      RuntimeWarning, stacklevel=3)
 
     def _replay_lexical(self, params):
         """The pending mutations applied to the retained index, in order, through SparseIndex.compacted /
@@ -1308,7 +1355,7 @@ class CorpusStore:
         TEXT_MATCH / PHRASE_MATCH leaves read the lexical index (create_index("sparse", ...) first:
         ValueError without it): rf_text_match turns their posting lists into row bitmaps and the
         filter program reads those, both on the current stream.  The first PHRASE_MATCH after a
-        change of the rows also builds the token positions (lexical.build_positions), once.
+        change of the rows also builds the token positions, once (by the route that built the index).
 
         Lock order: the read/write lock (held by the caller: search, query and delete take it; delete
         holds the WRITE side, so nothing here may ask for it again), then `_sparse_lock` (inside
@@ -1336,9 +1383,25 @@ class CorpusStore:
         postings, sp = self._sparse_index()
         if sp is not None and any(isinstance(n, filter_expr.PhraseMatch) for n in leaves):
             with self._sparse_lock:
-                if sp.positions is None:
+                if sp.positions is None and not self._attach_positions_device(postings, sp):
                     sp.attach_positions(*lexical.build_positions(postings, self.columns["text"], self.analyzer))
         return postings.term_id, sp
+
+    def _attach_positions_device(self, postings, sp) -> bool:
+        """The token positions of an index that came from the device route, through the device route again
+        (native analysis, rf_sparse_count_* with positions); False: not that route, or it raised, and the
+        caller builds them on the host.  The stream must give the index's own dictionary and postings."""
+        if self._lexical_route != "device" or self.analyzer is not None:
+            return False
+        try:
+            vocab, tok, dl = lexical.analyze_native(self.columns["text"])
+            if vocab != postings.vocab:
+                raise ValueError("the native analysis does not give the dictionary of the index")
+            sp.attach_token_positions(tok, dl)
+            return True
+        except Exception as e:
+            self._lexical_fell_back("the token positions", e)
+            return False
 
     def filter_rows(self, expr: str) -> np.ndarray:
         """Row numbers (ascending) that pass `expr`."""

@@ -101,6 +101,24 @@ def _simple_tables():
     return _SIMPLE
 
 
+def only_simple_non_ascii(joined: str, complex_re) -> bool:
+    """True if every non-ASCII character of the batch is one the native rules handle as they are (no
+    pre-normalisation): decided on the batch's DISTINCT non-ASCII code units -- a handful -- instead of running
+    the character-class regex over megabytes of text (30 ms per 4 M characters; this: a UTF-16 view, one
+    comparison and one `unique` in numpy).  complex_re: the regex of _simple_tables()."""
+    import numpy as np
+    try:
+        u16 = np.frombuffer(joined.encode("utf-16-le"), dtype=np.uint16)
+    except UnicodeEncodeError:                   # lone surrogates
+        return False
+    hi = np.unique(u16[u16 >= 128])
+    if hi.size == 0:
+        return True
+    if hi.size > 4096 or bool(((hi >= 0xD800) & (hi <= 0xDFFF)).any()):   # beyond the BMP: let the per-text path look
+        return False
+    return complex_re.search("".join(map(chr, hi.tolist()))) is None
+
+
 def assemble_pairs(q_ids, q_lens, d_ids, d_lens, max_length: int, cls_id: int, sep_id: int, pad_id: int):
     """[CLS] q [SEP] d [SEP] rows of a cross-encoder from token ids WITHOUT specials (q_ids [n, Tq], d_ids
     [n, Td] int32, padded; q_lens, d_lens [n] token counts -- they may exceed the arrays' widths, which need
@@ -288,21 +306,7 @@ class WordPieceTokenizer:
         return s.translate(self._punct_tab)
 
     def _only_simple_non_ascii(self, joined: str) -> bool:
-        """True if every non-ASCII character of the batch is one the native rules handle as they are (no
-        pre-normalisation): decided on the batch's DISTINCT non-ASCII code units -- a handful -- instead of running
-        the character-class regex over megabytes of text (30 ms per 4 M characters; this: a UTF-16 view, one
-        comparison and one `unique` in numpy)."""
-        import numpy as np
-        try:
-            u16 = np.frombuffer(joined.encode("utf-16-le"), dtype=np.uint16)
-        except UnicodeEncodeError:                   # lone surrogates
-            return False
-        hi = np.unique(u16[u16 >= 128])
-        if hi.size == 0:
-            return True
-        if hi.size > 4096 or bool(((hi >= 0xD800) & (hi <= 0xDFFF)).any()):   # beyond the BMP: let the per-text path look
-            return False
-        return self._complex_re.search("".join(map(chr, hi.tolist()))) is None
+        return only_simple_non_ascii(joined, self._complex_re)
 
     def batch_native(self, texts: list[str], max_length: int = 256, n_threads: int = 0):
         """Same result as batch(), through rf_tokenize_batch.  -> (ids int32 [B, T], lens int32 [B])."""
