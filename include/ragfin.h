@@ -277,6 +277,49 @@ int rf_search_multi_filtered(const rf_index_t* ix, const void* multi_dev, int n_
                              const int32_t* qfilter_dev, const void* q_dev, int B, int k, int64_t id_base,
                              float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
                              void* workspace_dev, size_t workspace_bytes, void* stream);
+/* ---- boosted search: Collection.search(..., ranker=Function(..., params={"reranker": "boost", ...})) ----
+ * Milvus' Boost Ranker multiplies the score of the rows a filter selects by a weight.  Here the
+ * boosted ranking is the exact top-k of the whole corpus under the boosted score (the
+ * definition in numpy: rag_fin_amd/ranker.py, boost_reference).  m <= RF_BOOST_MAX boosts
+ * (filter_i, weight_i) split the rows into 2^m CLASSES: bit i of a row's class c is set iff the row
+ * passes filter_i, and W[c] is the product of the weights of the set bits.  With s the fp64 contract
+ * score, boosted = W[class] * s (one fp64 multiplication) and rows rank by (boosted desc, s desc,
+ * row asc).  Inside a class that order is the plain (s desc, row asc) one, so the boosted top-k is
+ * the top-k of the union of every class's plain filtered top-k: the caller runs the classes as
+ * queries of rf_search_multi_filtered (or rf_search_filtered) and merges their answers.
+ *
+ * rf_boost_classes: the class masks of m filter buffers built for n_rows (boost_filters: a HOST array
+ * of m device pointers, copied into the launch's arguments), within the rows of base_filter_dev when
+ * that is not NULL.  class_masks_dev uint32 [2^m][stride], stride = rf_boost_class_stride_words(n_rows)
+ * (ceil(n_rows / 32) rounded up to a multiple of 4, so every class mask is 16-byte aligned; 0 for an
+ * n_rows outside 1..2^32 - 33): word w of class c = base[w] AND, for each i, F_i[w] when bit i of c is
+ * set and NOT F_i[w] otherwise -- the mask format of the filter buffer, ready for rf_filter_from_mask.
+ * Bits at positions >= n_rows and the words from ceil(n_rows / 32) to the stride are ZERO in every
+ * class.  class_counts_dev int64 [2^m]: the rows of each class (integer sums: independent of the order
+ * of the atomics); they add up to the rows the base filter passes.  A filter buffer whose header was
+ * built for another row count contributes no row.  Stream-ordered, no allocation, captures into a
+ * hipGraph; the same inputs give the same bytes.  RF_ERR_INVALID before any device call: a NULL array,
+ * entry or output, m outside 1..RF_BOOST_MAX, a filter or class_masks_dev not 16-byte aligned,
+ * class_counts_dev not 8-byte aligned, n_rows out of range.
+ *
+ * rf_merge_boosted: per query b the C <= 8 class answers exact_dev fp64 / ids_dev int64 [B, C, k_in]
+ * (the outputs of the class searches; an id < 0 is padding, ids are distinct within a query) ->
+ * the best k candidates by (boosted desc, s desc, id asc), boosted = class_weight[c] * s as ONE fp64
+ * multiplication (never contracted), as scores_dev = (float)boosted, ids_out_dev, boosted_dev and
+ * base_dev = s ([B, k]; the two fp64 outputs may be NULL); the tail is -inf / -1 / -inf / -inf.
+ * class_weight_host: C doubles in HOST memory (they travel in the launch arguments), finite and > 0.
+ * One workgroup per query, the C k_in <= 512 candidates ranked by counting in LDS; no workspace,
+ * stream-ordered, captures into a hipGraph.  RF_ERR_INVALID before any device call: a NULL argument
+ * (but the two nullable ones), B < 1, C outside 1..8, k or k_in outside 1..RF_MAX_K, a weight that is
+ * not finite or not > 0.
+ * New in this build; the reference calls Milvus without a ranker on this path. */
+#define RF_BOOST_MAX 3
+size_t rf_boost_class_stride_words(int64_t n_rows);
+int rf_boost_classes(const void* base_filter_dev, const void* const* boost_filters, int m, int64_t n_rows,
+                     uint32_t* class_masks_dev, int64_t* class_counts_dev, void* stream);
+int rf_merge_boosted(const double* exact_dev, const int64_t* ids_dev, int B, int C, int k_in,
+                     const double* class_weight_host, int k, float* scores_dev, int64_t* ids_out_dev,
+                     double* boosted_dev, double* base_dev, void* stream);
 /* ---- range search: Collection.search(..., param={"params": {"radius": r, "range_filter": f}}) ----
  * The best k hits whose score lies in the band  radius < score <= range_filter  (COSINE / IP:
  * higher is better), i.e. the (score desc, row asc) ranking of rf_search with every row outside

@@ -22,6 +22,8 @@ RF_GROUP_MAX_CODES = 64   # dictionary size the fused grouped path serves (inclu
 RF_SPARSE_MAX_TERMS = 64     # distinct known terms of one query
 RF_SPARSE_TILE_ROWS = 8192   # rows a workgroup of the posting scan accumulates in LDS
 RF_FUSE_MAX_ARMS = 4         # answers rf_fuse_rrf fuses
+# boosted search (include/ragfin.h, "boosted search")
+RF_BOOST_MAX = 3             # boosts of one search: 2^3 = 8 row classes, the most rf_merge_boosted takes
 # keyword filters (include/ragfin.h, "keyword filters")
 RF_TEXT_MATCH = 1
 RF_TEXT_PHRASE = 2
@@ -125,6 +127,10 @@ SIGNATURES = {
     "rf_multi_filter_build": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rf_search_multi_filtered": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int64,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_boost_class_stride_words": (c_size_t, [c_int64]),
+    "rf_boost_classes": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "rf_merge_boosted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
     "rf_search_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_exhaustive_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double,

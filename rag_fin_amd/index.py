@@ -1,6 +1,7 @@
 """The device layer under rag_fin_amd/store.py (which re-exports these names): `GpuIndex` over
 rf_index_* / rf_search (include/ragfin.h), the flagged-query ladder, the filter-mask helpers and
-rf_filter_eval; `SparseIndex` over rf_sparse_* (BM25 posting lists) and `fuse_rrf` over rf_fuse_rrf.
+rf_filter_eval; `SparseIndex` over rf_sparse_* (BM25 posting lists), `fuse_rrf` over rf_fuse_rrf, and
+`boost_classes` / `merge_boosted` over rf_boost_classes / rf_merge_boosted (boosted search).
 All arithmetic goes through libragfin_hip.so; there is no CPU path."""
 from __future__ import annotations
 
@@ -1219,6 +1220,68 @@ def fuse_rrf(arm_ids, k: int, weights=None, rrf_k: float = 60.0):
         _lib.check(_lib.load_library().rf_fuse_rrf(A, _ptr(arm_ids), F, w, float(rrf_k), B, k, _ptr(scores), _ptr(ids),
                                                    _ptr(fused), _lib.current_stream_ptr()))
     return scores, ids, fused
+
+
+BOOST_MAX = _lib.RF_BOOST_MAX   # boosts of one search (include/ragfin.h, "boosted search")
+
+
+def boost_classes(filters, n_rows: int, base=None):
+    """Enqueue rf_boost_classes on the current stream: m = 1..3 filter buffers built for n_rows (and
+    the base filter's buffer, or None) -> (class masks int32 [2^m, stride] on the device, in the mask
+    format of rf_filter_from_mask, the rows of every class int64 [2^m] on the device)."""
+    torch = _torch()
+    lib = _lib.load_library()
+    filters = list(filters)
+    m = len(filters)
+    if not 1 <= m <= BOOST_MAX:
+        raise ValueError(f"boost_classes: 1..{BOOST_MAX} boost filters, got {m}")
+    stride = lib.rf_boost_class_stride_words(int(n_rows))
+    if stride == 0:
+        raise ValueError(f"boost_classes: no class masks for {n_rows} rows")
+    dev = filters[0].device
+    with torch.cuda.device(dev):
+        masks = torch.empty((1 << m, stride), dtype=torch.int32, device=dev)
+        counts = torch.empty((1 << m,), dtype=torch.int64, device=dev)
+        ptrs = (c_void_p * m)(*[c_void_p(f.data_ptr()) for f in filters])
+        _lib.check(lib.rf_boost_classes(_ptr(base), ptrs, m, int(n_rows), _ptr(masks), _ptr(counts),
+                                        _lib.current_stream_ptr()))
+    return masks, counts
+
+
+def merge_boosted(cand_exact, cand_ids, class_weights, k: int):
+    """Enqueue rf_merge_boosted on the current stream: the class answers fp64 / int64 [B, C, k_in] on
+    the device (an id < 0 = padding) and the C class weights (host floats) -> (scores f32 [B,k],
+    ids i64 [B,k], boosted f64 [B,k], base f64 [B,k]) on the device."""
+    torch = _torch()
+    if cand_ids.dim() != 3 or cand_ids.dtype != torch.int64 or cand_exact.dtype != torch.float64 or \
+            cand_exact.shape != cand_ids.shape:
+        raise ValueError("merge_boosted expects fp64 scores and int64 ids, both [B, C, k_in]")
+    cand_exact, cand_ids = cand_exact.contiguous(), cand_ids.contiguous()
+    B, C, k_in = cand_ids.shape
+    if len(class_weights) != C:
+        raise ValueError(f"merge_boosted: {len(class_weights)} weights for {C} classes")
+    w = (ctypes.c_double * C)(*[float(x) for x in class_weights])
+    dev = cand_ids.device
+    scores = torch.empty((B, k), dtype=torch.float32, device=dev)
+    ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+    boosted = torch.empty((B, k), dtype=torch.float64, device=dev)
+    base = torch.empty((B, k), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load_library().rf_merge_boosted(_ptr(cand_exact), _ptr(cand_ids), B, C, k_in, w, k, _ptr(scores),
+                                                        _ptr(ids), _ptr(boosted), _ptr(base),
+                                                        _lib.current_stream_ptr()))
+    return scores, ids, boosted, base
+
+
+def filter_from_mask(words, n_rows: int):
+    """rf_filter_from_mask of mask words (int32 [>= ceil(n_rows / 32)] on the device, contiguous) into a
+    fresh filter buffer, enqueued on the current stream."""
+    torch = _torch()
+    lib = _lib.load_library()
+    with torch.cuda.device(words.device):
+        buf = torch.empty(lib.rf_filter_bytes(n_rows), dtype=torch.uint8, device=words.device)
+        _lib.check(lib.rf_filter_from_mask(_ptr(words), n_rows, _ptr(buf), _lib.current_stream_ptr()))
+    return buf
 
 
 def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None):

@@ -58,7 +58,8 @@ def _searcher():
 def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: float | None = None,
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                    mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
-                   hybrid: bool = False, offset: int | None = None):
+                   hybrid: bool = False, offset: int | None = None, boost_filter: str = "",
+                   boost_weight: float | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -74,8 +75,28 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     rerank; not with min_score / max_score, group_by or mmr_lambda.  Needs the store's lexical index
     (LEXICAL_INDEX=1 at ingest).
     offset: optional paging -- skip that many of the best chunks, return the next top_k.  With filter and
-    min_score / max_score; not with rerank, hybrid, mmr_lambda or group_by."""
+    min_score / max_score; not with rerank, hybrid, mmr_lambda or group_by.
+    boost_filter / boost_weight: optional soft filter -- the chunks the expression boost_filter selects
+    have their score multiplied by boost_weight (> 0; below 1 demotes), the rest stay in the ranking;
+    `score` is then the boosted score.  Both or neither; with filter, not with min_score / max_score,
+    group_by, mmr_lambda, rerank, hybrid or offset."""
     try:
+        boosted = bool(boost_filter and boost_filter.strip()) or boost_weight is not None
+        if boosted:
+            # a boosted call bypasses the micro-batcher: one batch shares one boost (VectorRAG refuses
+            # what does not combine with it, and a filter without a weight or the reverse)
+            if not (boost_filter and boost_filter.strip()) or boost_weight is None:
+                raise ValueError("boost_filter and boost_weight go together")
+            kw = {name: v for name, v in (("min_score", min_score), ("max_score", max_score), ("group_by", group_by),
+                                          ("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k), ("offset", offset))
+                  if v is not None}
+            if rerank:
+                kw["rerank"] = True
+            if hybrid:
+                kw["hybrid"] = True
+            contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
+                                        boost={"filter": boost_filter, "weight": boost_weight}, **kw)
+            return {"status": "success", "query": query, "results": contexts, "result_count": len(contexts)}
         # (only what was given travels on; diversified, reranked and hybrid calls bypass the micro-batcher as well)
         mmr = {name: v for name, v in (("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k)) if v is not None}
         if rerank:

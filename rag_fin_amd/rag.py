@@ -79,7 +79,7 @@ class VectorRAG:
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
-               hybrid: bool = False, offset: int | None = None) -> list[dict]:
+               hybrid: bool = False, offset: int | None = None, boost=None) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -101,7 +101,13 @@ class VectorRAG:
         (ValueError).
         offset: skip that many of the best chunks first -- the chunks of ranks offset + 1 ...
         offset + top_k (`rank` counts from 1 within the page); with expr and min_score / max_score,
-        not with rerank, hybrid, mmr_lambda or group_by (ValueError)."""
+        not with rerank, hybrid, mmr_lambda or group_by (ValueError).
+        boost: {"filter": expression, "weight": w > 0}, or a list of up to 3 such dicts -- a soft
+        filter: the chunks the expression selects have their score multiplied by w (below 1:
+        demoted; several boosts multiply) and the top_k are the exact best of the whole store under
+        that boosted score, which is what `score` then holds.  With expr (one string); not with
+        rerank, hybrid, group_by, mmr_lambda, min_score / max_score or offset (ValueError)."""
+        ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
@@ -114,8 +120,24 @@ class VectorRAG:
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
                                          **self._group_args(group_by, group_size),
-                                         **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset))
+                                         **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset), **ranker)
         return self._contexts(results[0])
+
+    @staticmethod
+    def _boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr) -> dict:
+        """The store's ranker argument from `boost`; nothing when it was not given (the call of before)."""
+        if boost is None:
+            return {}
+        if rerank or hybrid or group_by is not None or mmr_lambda is not None or min_score is not None or \
+                max_score is not None or offset is not None or isinstance(expr, (list, tuple)):
+            raise ValueError("boost re-weighs the plain ranking: it does not combine with rerank, hybrid, group_by, "
+                             "mmr_lambda, min_score / max_score, offset or a list expr")
+        from .ranker import MAX_BOOSTS, BoostRanker
+        items = list(boost) if isinstance(boost, (list, tuple)) else [boost]
+        if not 1 <= len(items) <= MAX_BOOSTS or not all(isinstance(b, dict) and set(b) == {"filter", "weight"}
+                                                        for b in items):
+            raise ValueError(f'boost must be {{"filter": str, "weight": float}} or a list of 1..{MAX_BOOSTS} such dicts')
+        return {"ranker": [BoostRanker(b["filter"], b["weight"]) for b in items]}
 
     def _embed(self, texts):
         """`.encode(texts)` of the reference (main.py:50) -- kept on the device when the embedder
@@ -199,7 +221,8 @@ class VectorRAG:
                      min_score: float | None = None, max_score: float | None = None,
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
-                     rerank: bool = False, hybrid: bool = False, offset: int | None = None) -> list[list[dict]]:
+                     rerank: bool = False, hybrid: bool = False, offset: int | None = None,
+                     boost=None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
@@ -209,7 +232,9 @@ class VectorRAG:
         expr may also be a list or tuple with one entry per query (a filter string, or None for "no
         filter"): per-query filters, still one corpus sweep per 64 queries
         (CorpusStore.search(expr=[...])).  The list form is the plain path only: with rerank, hybrid,
-        min_score / max_score, group_by, mmr_lambda or offset it raises ValueError."""
+        min_score / max_score, group_by, mmr_lambda or offset it raises ValueError.
+        boost: one boost (or up to 3) for the whole batch, as in search(); not with a list expr."""
+        ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         if isinstance(expr, (list, tuple)):
             if rerank or hybrid or min_score is not None or max_score is not None or group_by is not None or \
                     mmr_lambda is not None or offset is not None:
@@ -231,7 +256,7 @@ class VectorRAG:
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
                                          **self._group_args(group_by, group_size),
-                                         **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset))
+                                         **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset), **ranker)
         return [self._contexts(r) for r in results]
 
     # -- generation (out of scope; interface kept) -----------------------------------------

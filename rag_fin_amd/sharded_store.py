@@ -277,7 +277,10 @@ class ShardedCorpusStore(CorpusStore):
     # -- filters: not over shards (yet) -----------------------------------------------------------------
     def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
                output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False,
-               mmr_lambda=None, mmr_fetch_k=None, offset=None):
+               mmr_lambda=None, mmr_fetch_k=None, offset=None, ranker=None):
+        if ranker is not None:
+            # (the class masks need the filter programs, which do not run over shards)
+            raise NotImplementedError("boosted search (ranker) is not implemented for the sharded store")
         if check_offset(offset, param, limit):
             # (a page past the first 64 hits needs the search-after sweep on every shard and a merge per page)
             raise NotImplementedError("paged search (offset) is not implemented for the sharded store")

@@ -30,6 +30,7 @@ import json
 import os
 import re
 import threading
+import time
 from typing import Any, Iterable, Sequence
 
 import numpy as np
@@ -39,8 +40,10 @@ from . import filter_expr
 from . import lexical
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, eval_filter, filter_mask_bits, fuse_rrf,  # noqa: F401
-                    grouped_exhaustive, mask_words, plan_filter_chunks, require_gpu, rerun_flagged, words_mask)
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, eval_filter, filter_from_mask,  # noqa: F401
+                    filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted, plan_filter_chunks,
+                    require_gpu, rerun_flagged, words_mask)
+from .ranker import BoostRanker, check_rankers, class_weights  # noqa: F401
 
 
 SCALAR_FIELDS = ("id", "text", "period", "chunk_type", "statement_type", "primary_value")
@@ -50,6 +53,25 @@ FORMAT = "ragfin-corpus-v1"   # columns.json "format"
 def _torch():
     import torch
     return torch
+
+
+class _StageClock:
+    """The milliseconds of a call's stages, added into a caller's dict under the key of each lap.
+    It synchronises the device at every lap; with no dict it does nothing at all."""
+
+    def __init__(self, timing, device):
+        self.timing, self.device = timing, device
+        if timing is not None:
+            _torch().cuda.synchronize(device)
+            self.t = time.perf_counter()
+
+    def lap(self, key: str) -> None:
+        if self.timing is None:
+            return
+        _torch().cuda.synchronize(self.device)
+        now = time.perf_counter()
+        self.timing[key] = self.timing.get(key, 0.0) + (now - self.t) * 1e3
+        self.t = now
 
 
 def check_band(radius, range_filter=None):
@@ -785,8 +807,17 @@ class CorpusStore:
     def search(self, data, anns_field: str = "embedding", param: dict | None = None,
                limit: int = 3, expr=None, output_fields: Iterable[str] | None = None,
                group_by_field: str | None = None, group_size: int = 1, strict_group_size: bool = False,
-               mmr_lambda=None, mmr_fetch_k=None, offset: int | None = None):
+               mmr_lambda=None, mmr_fetch_k=None, offset: int | None = None, ranker=None):
         """pymilvus-shaped search: one list of hits per query vector, best first.
+        ranker (a BoostRanker, or a list / tuple of 1..3 of them, which multiply): boosted search --
+        the rows a boost's filter selects have their score multiplied by its weight (below 1:
+        demoted), and the hits are the exact top `limit` of the whole collection (of the rows passing
+        expr) by (boosted score desc, plain score desc, row asc); hit.score is float32(boosted).
+        The boost filters split the rows into at most 8 classes of equal weight; every (query, class)
+        pair is one query of the per-query-filter sweep and rf_merge_boosted merges their answers
+        (DESIGN §4.4m): ceil(B * classes / 64) sweeps of the corpus.  The plain dense search only:
+        one expr string, limit <= 64, no offset, radius / range_filter, group_by_field, mmr_lambda /
+        mmr_fetch_k or anns_field="sparse" (ValueError); an SQ8 collection answers from its fp16 rows.
         offset (or param["offset"], as pymilvus accepts it; the keyword wins when both are given): the
         hits of ranks offset + 1 ... offset + limit, i.e. search(limit=offset + limit)[offset:].  An
         int >= 0 with offset + limit <= 16384 (Milvus' window), else ValueError.  With expr, range
@@ -831,6 +862,9 @@ class CorpusStore:
         plain search only: limit <= 64, and no offset, radius / range_filter, group_by_field,
         mmr_lambda / mmr_fetch_k or anns_field="sparse" (ValueError; neither search_iterator,
         hybrid_search arms, query nor delete take a list).  These can follow later."""
+        if ranker is not None:
+            return self._search_boosted(data, anns_field, param, limit, expr, output_fields, group_by_field,
+                                        mmr_lambda, mmr_fetch_k, offset, ranker)
         if isinstance(expr, (list, tuple)):
             return self._search_expr_list(data, anns_field, param, limit, expr, output_fields, group_by_field,
                                           mmr_lambda, mmr_fetch_k, offset)
@@ -935,6 +969,99 @@ class CorpusStore:
                     s, r = self.index.search_host(qc, int(limit), filt=mf)
                 scores[idx] = s[:, :kk]
                 rows[idx] = r[:, :kk]
+            return [self._hits(rows[b], scores[b], fields) for b in range(B)]
+
+    # -- boosted search: search(ranker=...) ---------------------------------------------
+    def _check_boosted(self, data, anns_field, param, limit, expr, group_by_field, mmr_lambda, mmr_fetch_k, offset,
+                       ranker) -> list:
+        """Everything a boosted search refuses, before anything runs -> the list of its boosts."""
+        boosts = check_rankers(ranker)
+        if isinstance(expr, (list, tuple)):
+            raise ValueError("boosted search (ranker) cannot be combined with per-query filters (a list expr)")
+        if anns_field == "sparse":
+            raise ValueError("boosted search (ranker) has no BM25 form (anns_field='sparse')")
+        if anns_field != "embedding":
+            raise ValueError(f"unknown vector field {anns_field!r}")
+        if self._is_text(data):
+            raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
+        if group_by_field is not None:
+            raise ValueError("boosted search (ranker) cannot be combined with group_by_field")
+        if mmr_lambda is not None or mmr_fetch_k is not None:
+            raise ValueError("boosted search (ranker) cannot be combined with mmr_lambda / mmr_fetch_k")
+        if check_offset(offset, param, limit):
+            raise ValueError("boosted search (ranker) takes no offset")
+        if self._band_of(param) is not None:
+            raise ValueError("boosted search (ranker) has no range form (radius / range_filter)")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= limit <= _lib.RF_MAX_K:
+            raise ValueError(f"boosted search (ranker): limit must be an integer in 1..{_lib.RF_MAX_K}, "
+                             f"got {limit!r} (boosted results are not paged)")
+        metric = (param or {}).get("metric_type", self.metric_type).upper()
+        if metric != self.metric_type:
+            raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
+        return boosts
+
+    def _search_boosted(self, data, anns_field, param, limit, expr, output_fields, group_by_field, mmr_lambda,
+                        mmr_fetch_k, offset, ranker, timing: dict | None = None):
+        """search(ranker=...).  timing: a dict that receives the milliseconds of the call's stages
+        (filters, classes, sweeps, merge) and its sweep count; it synchronises between the stages
+        (tools/bench_boost.py) -- None: the call synchronises for the class counts and the download only."""
+        boosts = self._check_boosted(data, anns_field, param, limit, expr, group_by_field, mmr_lambda, mmr_fetch_k,
+                                     offset, ranker)
+        weights = class_weights(boosts)   # (a product that leaves the doubles raises here)
+        fields = self._check_output_fields(output_fields)
+        B = self._query_count(data)
+        k = int(limit)
+        with self._rw.read():
+            n = self.num_entities
+            if n == 0 or B == 0:
+                return [[] for _ in range(B)]
+            torch = _torch()
+            device = self.index.device
+            clock = _StageClock(timing, device)
+            # every expression is parsed and built once, before any sweep runs
+            base = None if filter_expr.is_empty(expr) else self.build_filter(expr)
+            filters = [self.build_filter(b.filter) for b in boosts]
+            clock.lap("filters_ms")
+            masks, counts = boost_classes(filters, n, base)
+            counts = counts.cpu().numpy()   # the one small download the plan needs
+            live = [c for c in range(len(weights)) if counts[c] > 0]
+            if not live:   # no row passes expr
+                return [[] for _ in range(B)]
+            q16 = self._prepare_queries(data)
+            C = len(live)
+            if C == 1:
+                # every passing row is in one class: the plain (or filtered) search, scaled by that class's weight
+                kw = {} if base is None else {"filt": base}
+                clock.lap("classes_ms")
+                _, ids, exact = self.index.search(q16, k, want_exact=True, **kw)
+                cand_exact, cand_ids = exact.view(B, 1, k), ids.view(B, 1, k)
+                sweeps = -(-B // _lib.RF_QCHUNK)
+            else:
+                class_filters = [filter_from_mask(masks[c], n) for c in live]
+                clock.lap("classes_ms")
+                # virtual query v = b C + j: query b over the rows of class live[j]; skipped slots stay padded
+                cand_exact = torch.full((B * C, k), -np.inf, dtype=torch.float64, device=device)
+                cand_ids = torch.full((B * C, k), -1, dtype=torch.int64, device=device)
+                plan = plan_filter_chunks(np.tile(np.arange(C), B))
+                for idx, used, local in plan:
+                    qc = q16[(idx // C).tolist()]   # the chunk's queries, in the order of `local`
+                    if len(used) == 1:
+                        filt = class_filters[used[0]]
+                    else:
+                        filt = MultiFilter([class_filters[j] for j in used], local, n, device)
+                    _, ids, exact = self.index.search(qc, k, want_exact=True, filt=filt)
+                    at = torch.from_numpy(idx).to(device)
+                    cand_exact[at] = exact
+                    cand_ids[at] = ids
+                cand_exact, cand_ids = cand_exact.view(B, C, k), cand_ids.view(B, C, k)
+                sweeps = len(plan)
+            clock.lap("sweeps_ms")
+            scores, rows, _, _ = merge_boosted(cand_exact, cand_ids, [weights[c] for c in live], k)
+            packed = torch.cat([rows, scores.view(torch.int32).to(torch.int64)], 1).cpu().numpy()   # the one download
+            clock.lap("merge_ms")
+            if timing is not None:
+                timing.update(sweeps=sweeps, classes=C)
+            rows, scores = packed[:, :k], packed[:, k:].astype(np.int32).view(np.float32)
             return [self._hits(rows[b], scores[b], fields) for b in range(B)]
 
     def _check_group_by(self, field, group_size, limit, param):
@@ -1125,7 +1252,7 @@ class CorpusStore:
             kw["sq8"] = True
         return self.index.search(q16, limit, **kw)[1]
 
-    def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields: Iterable[str] | None = None):
+    def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields: Iterable[str] | None = None, ranker=None):
         """pymilvus-shaped hybrid search: every AnnSearchRequest of `reqs` (1..4; anns_field "embedding"
         with query vectors, or "sparse" with query strings) runs on the GPU with its own limit (<= 64)
         and its own expr, and `rerank` -- an RRFRanker -- fuses the arms' ranked lists per query:
@@ -1133,8 +1260,11 @@ class CorpusStore:
         (fused desc, row asc).  One list of hits per query; hit.score is the fused score.  The fusion
         runs on the device (rf_fuse_rrf) and the call downloads once.  All arms must carry the same
         number of queries; range, grouping and MMR arguments have no hybrid form.  A score-normalising
-        ranker is not offered (WeightedRanker raises NotImplementedError; weigh by RRFRanker(weights=...))."""
+        ranker is not offered (WeightedRanker raises NotImplementedError; weigh by RRFRanker(weights=...)).
+        A boost ranker (ranker=, or a BoostRanker as rerank) has no hybrid form: ValueError."""
         torch = _torch()
+        if ranker is not None or isinstance(rerank, BoostRanker):
+            raise ValueError("boosted search (ranker) cannot be combined with hybrid_search")
         reqs = list(reqs)
         if not 1 <= len(reqs) <= MAX_ARMS or not all(isinstance(r, AnnSearchRequest) for r in reqs):
             raise ValueError(f"hybrid_search takes 1..{MAX_ARMS} AnnSearchRequest objects")
@@ -1236,7 +1366,7 @@ class CorpusStore:
 
     def search_iterator(self, data, anns_field: str = "embedding", param: dict | None = None,
                         batch_size: int = 1000, limit: int = -1, expr=None,
-                        output_fields: Iterable[str] | None = None):
+                        output_fields: Iterable[str] | None = None, ranker=None):
         """pymilvus-shaped search_iterator: an object with next() -> the next batch_size hits (a list
         of Hit, [] when done) and close().  ONE query vector (ValueError for more, as pymilvus).
         The pages concatenated are search(limit=N): the iterator keeps the last hit's fp64 score and
@@ -1244,7 +1374,9 @@ class CorpusStore:
         (GpuIndex.search_after), not a search from the top.  expr: the filter buffer is built once.
         param["params"] may hold radius / range_filter.  limit: hits in all (-1: until the collection
         is exhausted).  The bound is a row number: an insert, delete, upsert or drop between two
-        next() calls makes the next one raise RuntimeError."""
+        next() calls makes the next one raise RuntimeError.  A boost ranker is not paged: ValueError."""
+        if ranker is not None:
+            raise ValueError("boosted search (ranker) cannot be combined with search_iterator")
         if isinstance(expr, (list, tuple)):
             raise ValueError("search_iterator takes one expr string, not a list (per-query filters)")
         return SearchIterator(self, data, anns_field, param, batch_size, limit, expr, output_fields)
