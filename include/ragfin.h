@@ -879,6 +879,45 @@ int rf_score_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_
                    const int32_t* seg_dev, int B, int T, const rf_pair_head* head, float* logits_dev,
                    void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Extractive reading: the best answer spans of (question, chunk) pairs from a BertForQuestionAnswering
+ * checkpoint of the same family (e.g. deepset/minilm-uncased-squad2): the encoder handle holds the BertModel
+ * weights, `head` the span head qa_outputs (device fp16, row-major as nn.Linear stores it; kept alive by the
+ * caller for the call).  ids_dev, lens_dev, seg_dev, B, T, the workspace and the stream are rf_score_pairs':
+ * [CLS] question [SEP] chunk [SEP] rows, seg = index of the chunk's first token.  The layers are rf_encode's;
+ * the call is always plain launches and never touches rf_encode's cached hipGraphs.  Per pair b (csrc/reader.hip):
+ *   logits      s[t] = qa_w[0] . x_t + qa_b[0], e[t] = qa_w[1] . x_t + qa_b[1] for t < lens[b], x_t the last
+ *               hidden state of token t, accumulated in fp32 in one fixed order; written to logits_dev
+ *               [B, T, 2] (start, end per position) when it is not NULL, positions >= lens[b] untouched
+ *   candidates  the context is lo = seg[b] .. hi = lens[b] - 2 (the closing [SEP] excluded); a candidate is
+ *               (i, j) with lo <= i <= j <= hi and j - i + 1 <= max_answer_len, z = s[i] + e[j] (one fp32
+ *               add).  spans_dev [B, n_best]: the best n_best by (z descending, i ascending, j ascending),
+ *               token positions in the pair; slots beyond the number of candidates are (-1, -1, -inf).
+ *               seg >= lens - 1 or lens < 3: no candidates, every slot empty, the call succeeds
+ *   norm_dev    [B, 3]: z_null = s[0] + e[0] (the [CLS] slot, SQuAD 2's "no answer"),
+ *               lse_start = log sum exp(s[t]) over t in {0} u [lo, hi], lse_end the same over e (maximum
+ *               subtracted, summed in fp64 in a fixed order, rounded to fp32 once).  exp(z - lse_start -
+ *               lse_end) is the product of the two softmax probabilities; the library returns no probability.
+ *               A row with lens < 1 has no [CLS] token: its three values are -inf and its slots empty
+ * All of it is a function of the pair alone -- no atomics, no arrival-order reduction: the same pair gives the
+ * same bits at any place of any batch.
+ * RF_ERR_INVALID: n_best outside 1..RF_READER_MAX_BEST, max_answer_len outside 1..RF_READER_MAX_SPAN, a null or
+ * misaligned pointer.  RF_ERR_UNSUPPORTED: an encoder with type_vocab < 2, T > max_position, T > 512 (the
+ * positions one workgroup of the span stage holds).  RF_ERR_CAPACITY: workspace too small or misaligned. */
+#define RF_READER_MAX_BEST 16
+#define RF_READER_MAX_SPAN 64
+typedef struct rf_qa_head {
+  const void* qa_w;   /* [2, H]  qa_outputs.weight: row 0 = start, row 1 = end (16-byte aligned) */
+  const void* qa_b;   /* [2] */
+} rf_qa_head;
+typedef struct rf_span {
+  int32_t start, end;   /* token positions in the pair; -1, -1 = none */
+  float z;              /* s[start] + e[end]; -inf = none */
+} rf_span;
+int rf_answer_spans(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev,
+                    const int32_t* seg_dev, int B, int T, const rf_qa_head* head, int max_answer_len, int n_best,
+                    rf_span* spans_dev, float* norm_dev, float* logits_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- tokenizer: the text -> token-id stage in front of rf_encode ------------------------
  * Reference: the WordPiece tokenizer SentenceTransformer('all-MiniLM-L6-v2') loads by name
  * (vector_rag_mcp/main.py:41,50; "chunking_storing (1).py":8,380).  Host code, multi-threaded.

@@ -87,6 +87,17 @@ class PairHead(Structure):
                 ("num_labels", c_int32)]
 
 
+# extractive reading (include/ragfin.h, rf_answer_spans)
+RF_READER_MAX_BEST = 16      # spans per pair one call returns
+RF_READER_MAX_SPAN = 64      # tokens of the longest span
+RF_READER_MAX_T = 512        # positions of a pair the span stage holds
+
+
+class QaHead(Structure):
+    """rf_qa_head: qa_outputs of a BertForQuestionAnswering (device fp16 pointers)."""
+    _fields_ = [("qa_w", c_void_p), ("qa_b", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/ragfin.h declares
 SIGNATURES = {
     "rf_version": (c_int, []),
@@ -219,6 +230,8 @@ SIGNATURES = {
                           c_size_t, c_void_p]),
     "rf_score_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(PairHead), c_void_p,
                                c_void_p, c_size_t, c_void_p]),
+    "rf_answer_spans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(QaHead), c_int, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 # present only in the experiments build (libragfin_hip_exp.so, tools/): bound when exported

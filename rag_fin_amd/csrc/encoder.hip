@@ -28,7 +28,8 @@
 //                   kept for longer sequences
 //   k_qkv_attn_one  a single sequence of <= 32 tokens: K2 + K3 of a head in one launch
 //   k_pool_norm     mean over the sequence, L2-normalise                      (K7)
-// A cross-encoder forward (rf_score_pairs) runs the same layers between the two kernels of rerank.hip.
+// A cross-encoder forward (rf_score_pairs) runs the same layers between the two kernels of rerank.hip; a reader
+// forward (rf_answer_spans) opens like it and closes with the span kernel of reader.hip.
 #include "encoder_internal.h"
 #include <mutex>
 #include <new>
@@ -1594,19 +1595,20 @@ extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const 
   return encode_enqueue(enc, ids_dev, lens_dev, B, T, out_f16_dev, out_f32_dev, workspace_dev, st);
 }
 
-// rf_score_pairs (rerank.hip) behind its pointer checks.  Always the plain launches: the cached hipGraphs are
+// rf_score_pairs (rerank.hip) and rf_answer_spans (reader.hip) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
 // rf_encode's alone, so a pair forward can never replay an embedding graph, nor the other way round.
 int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
-                    const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st) {
+                    const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
+                    const char* who) {
   if (enc->cfg.type_vocab < 2) {
-    rf_set_error("rf_score_pairs: the encoder has %d token-type row(s); a pair needs 2", enc->cfg.type_vocab);
+    rf_set_error("%s: the encoder has %d token-type row(s); a pair needs 2", who, enc->cfg.type_vocab);
     return RF_ERR_UNSUPPORTED;
   }
   if (T > enc->cfg.max_position) {
-    rf_set_error("rf_score_pairs: T=%d exceeds max_position %d", T, enc->cfg.max_position);
+    rf_set_error("%s: T=%d exceeds max_position %d", who, T, enc->cfg.max_position);
     return RF_ERR_UNSUPPORTED;
   }
-  const int crc = encode_check("rf_score_pairs", enc, B, T, workspace_dev, workspace_bytes);
+  const int crc = encode_check(who, enc, B, T, workspace_dev, workspace_bytes);
   if (crc != RF_OK) return crc;
   return encode_enqueue(enc, ids_dev, lens_dev, B, T, nullptr, nullptr, workspace_dev, st, &ends);
 }
@@ -1691,7 +1693,9 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
                                                  tiles, m_ptr, y, (const _Float16*)w.ln2_g + (size_t)l * HID,
                                                  (const _Float16*)w.ln2_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
   }
-  if (ends)
+  if (ends && ends->qa)
+    rf_launch_qa_spans(x, ws.tok_off, B, T, *ends, st);
+  else if (ends)
     rf_launch_cls_head(x, ws.tok_off, B, *ends->head, ends->logits, st);
   else
     hipLaunchKernelGGL(k_pool_norm, dim3(B), dim3(256), 0, st, x, ws.tok_off, (_Float16*)out_f16_dev, out_f32_dev);

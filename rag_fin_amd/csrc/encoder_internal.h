@@ -152,15 +152,26 @@ int rf_launch_post_block(const rf_post_args& a, int token_slots, hipStream_t st)
 // encode_enqueue's option: which embedding launch opens the forward and which launch closes it.  nullptr is
 // the sentence embedder (k_embed_ln ... k_pool_norm); with it the forward opens with k_embed_pair_ln (segment
 // ids) and closes with k_cls_head (pooler + classifier on the [CLS] row) instead.  The layer loop is the same.
+// A second pair of ends (reader.hip): with `qa` set the forward closes with k_qa_spans (QA head + span search on
+// every row of the pair) instead of k_cls_head; `head` and `logits` are then unused.
 struct rf_pair_ends {
   const int32_t* seg;         // [B] first segment-1 position per sequence
   const rf_pair_head* head;   // device pointers of the classification head
   float* logits;              // [B]
+  const rf_qa_head* qa;       // device pointers of the span head, or nullptr: the classification head closes
+  int max_answer_len, n_best;
+  rf_span* spans;             // [B, n_best]
+  float* norm;                // [B, 3]
+  float* qa_logits;           // [B, T, 2] or nullptr
 };
 void rf_launch_embed_pair(const int32_t* ids, const int32_t* lens, const int32_t* seg, int32_t* tok_off, int B, int T,
                           const rf_encoder_config& c, const rf_encoder_weights& w, _Float16* out, hipStream_t st);
 void rf_launch_cls_head(const _Float16* x, const int32_t* tok_off, int B, const rf_pair_head& head, float* logits,
                         hipStream_t st);
-// encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph)
+void rf_launch_qa_spans(const _Float16* x, const int32_t* tok_off, int B, int T, const rf_pair_ends& ends,
+                        hipStream_t st);
+// encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph);
+// `who` names the public entry in the error text
 int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
-                    const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st);
+                    const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
+                    const char* who = "rf_score_pairs");

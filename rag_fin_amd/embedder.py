@@ -78,6 +78,16 @@ def stack_hf_pair_head(sd: dict) -> dict:
             "cls_w": get("classifier.weight"), "cls_b": get("classifier.bias")}
 
 
+def stack_hf_qa_head(sd: dict) -> dict:
+    """The span head of a Hugging Face BertForQuestionAnswering state dict -> the tensors of rf_qa_head:
+    qa_outputs, row 0 the start logit's, row 1 the end logit's."""
+    def get(name):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name} (not a BertForQuestionAnswering?)")
+        return np.asarray(sd[name], dtype=np.float32)
+    return {"qa_w": get("qa_outputs.weight"), "qa_b": get("qa_outputs.bias")}
+
+
 def hf_encoder_config(hc: dict) -> dict:
     """config.json of a BERT checkpoint -> the fields of rf_encoder_config."""
     if hc.get("hidden_act", "gelu") != "gelu":

@@ -4,8 +4,10 @@ same method names, defaults and return keys, backed by the in-process GPU
 embedder + corpus store instead of sentence-transformers + a Milvus server.
 
 The LLM generation step (Gemini, main.py:40,97) is outside this build's scope: a
-`generator` callable can be plugged in; without one `search_and_answer` returns the
-reference's own failure shape {"error", "contexts", "context_count"}.
+`generator` callable can be plugged in.  Without one, a `reader`
+(rag_fin_amd.reader.ExtractiveReader) answers with a span of a retrieved chunk; with
+neither, `search_and_answer` returns the reference's own failure shape
+{"error", "contexts", "context_count"}.
 """
 from __future__ import annotations
 
@@ -27,17 +29,21 @@ DEFAULT_PROMPT = "Question: {question}\n\nRetrieved contexts:\n{context}\n\nAnsw
 class VectorRAG:
     def __init__(self, gemini_api_key: str | None = None, collection_name: str = "fin_chunks", *,
                  embedder=None, store=None, generator: Callable[[str], str] | None = None,
-                 llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None):
+                 llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None, reader=None):
         """embedder: .encode(list[str]) -> [n, dim] (rag_fin_amd.embedder.Embedder);
         store: rag_fin_amd.store.CorpusStore.  `gemini_api_key` is accepted for
         signature compatibility and only handed to `generator` factories upstream.
         reranker: .predict(list[(query, text)]) -> [n] scores (rag_fin_amd.reranker.CrossEncoder), the
-        second stage of search(..., rerank=True)."""
+        second stage of search(..., rerank=True).
+        reader: .predict(question, list[text], top_k=1) -> [{"answer", "score", "start", "end",
+        "context_index"}] (rag_fin_amd.reader.ExtractiveReader): the answer step of search_and_answer when no
+        generator is set."""
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
         self.similarity_model = embedder
         self.reranker = reranker
+        self.reader = reader
         self.collection = store
         self.collection_name = collection_name
         self.generator = generator
@@ -267,11 +273,21 @@ class VectorRAG:
 
     def search_and_answer(self, question: str, top_k: int = 3, min_score: float | None = None) -> dict:
         """min_score: only chunks scoring above it reach the prompt (possibly none: the prompt is
-        then built from zero contexts and the payload keeps its keys)."""
+        then built from zero contexts and the payload keeps its keys).
+        With a generator: {"answer", "contexts", "context_count"}, as ever.  Without one but with a reader the
+        answer is the reader's best span over the retrieved chunks' texts:
+        {"answer", "answer_span": {"context_index", "start", "end", "score"}, "answer_source": "reader",
+        "contexts", "context_count"} with answer == contexts[context_index]["text"][start:end]; zero contexts
+        or no candidate span give answer "" and answer_span None.  With neither: the error payload."""
         contexts = self.search(question, top_k) if min_score is None else \
             self.search(question, top_k, min_score=min_score)
         prompt = self.build_prompt(question, contexts)
         try:
+            if self.generator is None and self.reader is not None:
+                best = self.reader.predict(question, [c["text"] for c in contexts], top_k=1) if contexts else []
+                span = {k: best[0][k] for k in ("context_index", "start", "end", "score")} if best else None
+                return {"answer": best[0]["answer"] if best else "", "answer_span": span, "answer_source": "reader",
+                        "contexts": contexts, "context_count": len(contexts)}
             if self.generator is None:
                 raise RuntimeError("no LLM generator configured (generation is outside this build)")
             if self.llm_delay_s:

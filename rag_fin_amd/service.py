@@ -5,6 +5,9 @@ Environment (dotenv-style names):
                        model.safetensors).  Required: nothing is fetched by name.
   RERANKER_MODEL_DIR   optional local cross-encoder directory (e.g. ms-marco-MiniLM-L-6-v2, same three
                        files): enables search(..., rerank=True)
+  READER_MODEL_DIR     optional local extractive-reader directory (a BertForQuestionAnswering such as
+                       minilm-uncased-squad2, same three files): search_and_answer answers with a span of a
+                       retrieved chunk when no generator is plugged in
   LEXICAL_INDEX        1: declare the lexical (BM25) index at ingest: enables search(..., hybrid=True)
   RAGFIN_DATA_DIR      folder with icici_q{1..4}_2023/*.json (default: extract_data)
   RAGFIN_DEVICE        torch device string (default cuda:0)
@@ -44,9 +47,16 @@ def _load_reranker(reranker_dir, device):
     return CrossEncoder.from_local(reranker_dir, device=device)
 
 
+def _load_reader(reader_dir, device):
+    if not reader_dir:
+        return None
+    from .reader import ExtractiveReader
+    return ExtractiveReader.from_local(reader_dir, device=device)
+
+
 def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
-              hybrid: bool = False):
+              hybrid: bool = False, reader_dir: str | None = None):
     """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
     can run; its posting lists are built by the first such search."""
     from .embedder import Embedder
@@ -58,7 +68,7 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     if hybrid:
         store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
-                     reranker=_load_reranker(reranker_dir, device))
+                     reranker=_load_reranker(reranker_dir, device), reader=_load_reader(reader_dir, device))
 
 
 def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
@@ -83,7 +93,7 @@ def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
 
 def build_sharded_rag(model_dir: str, data_dir: str = "extract_data", local_rank: int = 0,
                       collection_name: str = "fin_chunks", generator=None, backend: str = "nccl",
-                      reranker_dir: str | None = None):
+                      reranker_dir: str | None = None, reader_dir: str | None = None):
     """One process per GPU (launched by torch.distributed.run): every rank builds an embedder
     replica and its shard of the store.  Returns the VectorRAG on EVERY rank; a serving
     deployment then calls `rag.collection.start_workers()` on all ranks -- rank 0 comes back and
@@ -103,7 +113,7 @@ def build_sharded_rag(model_dir: str, data_dir: str = "extract_data", local_rank
     ingest_sharded(store, embedder, chunker.build_all_chunks(data_dir))
     # (the serving rank reranks; the others only hold a replica like the embedder's)
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
-                     reranker=_load_reranker(reranker_dir, dev))
+                     reranker=_load_reranker(reranker_dir, dev), reader=_load_reader(reader_dir, dev))
 
 
 def build_rag_from_env():
@@ -113,10 +123,11 @@ def build_rag_from_env():
                            "directory (the reference fetches the model by name; this build never "
                            "touches the network)")
     reranker_dir = os.getenv("RERANKER_MODEL_DIR") or None
+    reader_dir = os.getenv("READER_MODEL_DIR") or None
     if int(os.getenv("WORLD_SIZE", "1")) > 1:
         return build_sharded_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                                  int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
-                                 reranker_dir=reranker_dir)
+                                 reranker_dir=reranker_dir, reader_dir=reader_dir)
     return build_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                      os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
-                     reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1")
+                     reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1", reader_dir=reader_dir)

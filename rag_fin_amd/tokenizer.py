@@ -258,6 +258,85 @@ class WordPieceTokenizer:
         ids = ids[:max(0, max_length - 2)]
         return [self.cls_id] + ids + [self.sep_id]
 
+    # -- token -> character offsets (the extractive reader maps an answer span back to its text) ----------
+    def _wordpiece_spans(self, word: str) -> list[tuple[int, int, int]]:
+        """wordpiece() with each piece's [start, end) in `word`; an [UNK] word is one piece over all of it."""
+        whole = [(self.unk_id, 0, len(word))]
+        if len(word) > self.max_chars:
+            return whole
+        out, start = [], 0
+        while start < len(word):
+            end = len(word)
+            cur = None
+            while start < end:
+                sub = word[start:end] if start == 0 else "##" + word[start:end]
+                if sub in self.vocab:
+                    cur = self.vocab[sub]
+                    break
+                end -= 1
+            if cur is None:
+                return whole
+            out.append((cur, start, end))
+            start = end
+        return out
+
+    def _fold(self, s: str) -> str:
+        """What basic_tokens() does to a word between the whitespace split and the punctuation split."""
+        if not self.do_lower_case:
+            return s
+        return "".join(c for c in unicodedata.normalize("NFD", s.lower()) if unicodedata.category(c) != "Mn")
+
+    def encode_with_offsets(self, text: str, max_length: int = 256):
+        """encode() with, per token, the [char_start, char_end) range of the CALLER's string it came from (the
+        `offset_mapping` of Hugging Face's fast tokenizers): -> (ids, offsets), offsets[k] for ids[k], (0, 0) for
+        [CLS] and [SEP].  A token's range runs from the source of its first character to the end of the source of
+        its last one: an input character that vanishes (a control character, a combining mark once the accent
+        is stripped) widens no range unless it lies inside the token, a character that is lower-cased or loses its
+        accent stands for its one output character, a "##" piece has the range of its characters without the
+        prefix, and every piece of a word that became [UNK] has the whole word's range.  Where a word's
+        characters cannot be traced one by one (normalisation merged or reordered them across characters) its
+        tokens all get the word's range.  Host-side pure Python: a reader call tokenises a handful of chunks."""
+        ids, offs = [self.cls_id], [(0, 0)]
+        # the words of basic_tokens(), each as the indices of the input characters that survive _clean()
+        words, cur = [], []
+        for k, ch in enumerate(text):
+            cp = ord(ch)
+            if cp == 0 or cp == 0xFFFD or _is_control(ch):
+                continue
+            if _is_cjk(cp):
+                if cur:
+                    words.append(cur)
+                words.append([k])
+                cur = []
+            elif _is_whitespace(ch) or ch.isspace():   # (str.split() of basic_tokens also splits on Zl / Zp ...)
+                if cur:
+                    words.append(cur)
+                cur = []
+            else:
+                cur.append(k)
+        if cur:
+            words.append(cur)
+        for src in words:
+            raw = "".join(text[k] for k in src)
+            w0, w1 = src[0], src[-1] + 1
+            word = unicodedata.normalize("NFC", raw)
+            if word in self.special:
+                ids.append(self.vocab[word])
+                offs.append((w0, w1))
+                continue
+            word = self._fold(word)
+            # character by character: the source index of every output character, if the word folds that way
+            per = [self._fold(text[k]) for k in src]
+            origin = [k for k, p in zip(src, per) for _ in p] if "".join(per) == word else None
+            pos = 0
+            for piece in self._split_punct(word):
+                for tid, a, b in self._wordpiece_spans(piece):
+                    ids.append(tid)
+                    offs.append((origin[pos + a], origin[pos + b - 1] + 1) if origin is not None and b > a else (w0, w1))
+                pos += len(piece)
+        keep = max(0, max_length - 2) + 1
+        return ids[:keep] + [self.sep_id], offs[:keep] + [(0, 0)]
+
     # -- native path (libragfin_hip.so: csrc/tokenizer.cpp, multi-threaded) ---------------
     # The C++ tokenizer applies the ASCII rules; text with non-ASCII characters is first
     # brought to a form in which those rules are all that is left to apply, using only
