@@ -918,6 +918,51 @@ int rf_answer_spans(const rf_encoder_t* enc, const int32_t* ids_dev, const int32
                     rf_span* spans_dev, float* norm_dev, float* logits_dev,
                     void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Sliding windows over a long context: a context of more tokens than a pair row holds is read as W overlapping
+ * windows, each a pair row of rf_answer_spans (called with logits_dev), and rf_stitch_spans decodes ONE ranking
+ * and ONE pair of normalisers per context from the windows' logits -- not one softmax per window, whose scores
+ * are not comparable between windows (a window without the answer puts a probability near 1 on its best wrong
+ * span) and which reports a span seen by two windows twice.  csrc/reader_windows.hip; three launches per call.
+ *   win_dev      [W] windows; rows ctx_win_dev[c] .. ctx_win_dev[c + 1] (a CSR over the C contexts) are context
+ *                c's, in ascending `first`, each with count <= T.  Row w of win_dev describes row w of logits_dev
+ *   L            max(first + count) over the context's windows, the context's token count
+ *                (<= RF_READER_MAX_CONTEXT; every token lies in one of the windows)
+ *   owner        of context token t: the window w holding t with the largest min(t - first_w, first_w + count_w
+ *                - 1 - t), ties to the smallest w (BERT's "max context" rule in integers)
+ *   S[t], E[t]   logits[owner, seg_owner + t - first_owner, 0 / 1], copied, no arithmetic
+ *   null slot    the window with the smallest fp32 s_w[0] + e_w[0] (its [CLS] position), ties to the smallest w
+ *                (run_squad's minimum over features); z_null is that sum
+ *   candidates   (i, j), 0 <= i <= j < L, j - i + 1 <= max_answer_len, z = S[i] + E[j] (one fp32 add); a span
+ *                may cross the seam between two owners.  spans_dev [C, n_best]: the best n_best by (z descending,
+ *                i ascending, j ascending), CONTEXT-token indices; slots beyond the candidates are (-1, -1, -inf)
+ *   norm_dev     [C, 3]: z_null, lse_start = log sum exp over the null slot's s[0] and S[0 .. L), lse_end the same
+ *                over e[0] and E: the exact maximum subtracted, exp summed in fp64 in one fixed order (the null
+ *                term, then the 512-token tiles ascending, each by a fixed tree), max + log(sum) rounded to fp32
+ *                once
+ *   L == 0       no candidates, the normalisers are the null slot's alone; a context without windows: three -inf
+ * No atomics and no arrival-order reduction; every selection is the maximum of the strict total order
+ * (z, (i << 6) | (j - i)): a context gives the same bits at any place among any other contexts, in every call.
+ * Malformed windows (descending `first`, count > T, a token in no window, L beyond the limit) give wrong numbers,
+ * never an access out of range: every index is clamped to W, T and L.
+ * The workspace is scratch of the call (rf_stitch_workspace_bytes; 16-byte aligned): concurrent calls need one
+ * each.  It holds a 512-token tile per window (~4.3 KB), which bounds every context's tokens because count <= T
+ * <= 512, so its size follows from W; C and max_context_tokens (the largest L of the call) are checked against
+ * their ranges, and 0 is returned for C < 1, W < 0 or a context beyond RF_READER_MAX_CONTEXT.
+ * Checked before anything is launched (a refused call writes nothing).  RF_ERR_INVALID: a null pointer, n_best
+ * outside 1..RF_READER_MAX_BEST, max_answer_len outside 1..RF_READER_MAX_SPAN, W < 0, C < 1, T < 1.
+ * RF_ERR_UNSUPPORTED: T > 512.  RF_ERR_CAPACITY: workspace too small or misaligned. */
+typedef struct rf_window {
+  int32_t first;   /* context-token index of the window's first context token */
+  int32_t count;   /* context tokens in the window (>= 0) */
+  int32_t seg;     /* position of that first context token in the window's pair row */
+  int32_t pad;
+} rf_window;
+#define RF_READER_MAX_CONTEXT 65536   /* tokens of one stitched context */
+int rf_stitch_spans(const float* logits_dev, int W, int T, const rf_window* win_dev, const int32_t* ctx_win_dev,
+                    int C, int max_answer_len, int n_best, rf_span* spans_dev, float* norm_dev,
+                    void* workspace_dev, size_t workspace_bytes, void* stream);
+size_t rf_stitch_workspace_bytes(int W, int C, int max_context_tokens);
+
 /* ---- tokenizer: the text -> token-id stage in front of rf_encode ------------------------
  * Reference: the WordPiece tokenizer SentenceTransformer('all-MiniLM-L6-v2') loads by name
  * (vector_rag_mcp/main.py:41,50; "chunking_storing (1).py":8,380).  Host code, multi-threaded.

@@ -91,6 +91,7 @@ class PairHead(Structure):
 RF_READER_MAX_BEST = 16      # spans per pair one call returns
 RF_READER_MAX_SPAN = 64      # tokens of the longest span
 RF_READER_MAX_T = 512        # positions of a pair the span stage holds
+RF_READER_MAX_CONTEXT = 65536   # tokens of one context stitched from sliding windows (rf_stitch_spans)
 
 
 class QaHead(Structure):
@@ -232,6 +233,9 @@ SIGNATURES = {
                                c_void_p, c_size_t, c_void_p]),
     "rf_answer_spans": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(QaHead), c_int, c_int,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_stitch_spans": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
+    "rf_stitch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
 }
 
 # present only in the experiments build (libragfin_hip_exp.so, tools/): bound when exported
