@@ -963,6 +963,48 @@ int rf_stitch_spans(const float* logits_dev, int W, int T, const rf_window* win_
                     void* workspace_dev, size_t workspace_bytes, void* stream);
 size_t rf_stitch_workspace_bytes(int W, int C, int max_context_tokens);
 
+/* ---- learned sparse vectors (SPLADE): an MLM head over the encoder, max-pooled over a row's tokens ----
+ * The model is a BertForMaskedLM of the same family (sentence-transformers' SparseEncoder; a Milvus
+ * SPARSE_FLOAT_VECTOR field with metric IP): the encoder handle holds the BertModel weights, `head` the
+ * cls.predictions module (device fp16, row-major as nn.Linear stores it; kept alive by the caller for the call).
+ * ids_dev int32 [B, T], lens_dev int32 [B] as for rf_encode; token types are 0.  For row b and term v
+ * (csrc/splade.hip):
+ *   g_t = LayerNorm(gelu(tr_w x_t + tr_b))   x_t = last hidden state of token t < lens[b], [CLS] and [SEP] included
+ *   m   = max_t (dec_w[v] . g_t + dec_b[v])
+ *   weights[b, v] = log1p(max(m, 0))         applied once per (b, v), after the max: log1p o relu is monotone
+ * fp16 operands, fp32 accumulation; g_t is rounded to fp16 before the decoder GEMM.  Every output is exactly
+ * +0.0f or a normal positive float (anything below FLT_MIN is flushed to +0.0f; no -0.0, no denormal); a row
+ * with lens < 1 is all zeros; padding positions contribute nothing.  A row's values are a function of the row
+ * and of (B, T) alone -- no atomics, no arrival-order reduction: the same row gives the same bits at any place
+ * of the batch.  The [tokens, V] logits are never stored: the workspace is rf_encode's plus one fp16
+ * [tokens, H] matrix.  The layers are rf_encode's (all its paths by B and T); the call is always plain
+ * launches and never touches rf_encode's cached hipGraphs.  Stream-ordered, no host sync, no allocation.
+ * RF_ERR_UNSUPPORTED: head->vocab != the encoder's vocab_size, T > max_position.  RF_ERR_INVALID: a null or
+ * misaligned pointer (tr_w, dec_w: 16 bytes), B or T < 1.  RF_ERR_CAPACITY: workspace too small or misaligned.
+ *
+ * rf_sparsify_terms: dense fp32 [B, V] weights -> packed CSR of each row's heaviest terms, exact.  The entries
+ * > 0 are kept; of more than max_terms (1..RF_TERMS_MAX) the best max_terms by (value descending, term id
+ * ascending).  Row b's entries are term_dev / val_dev [off_dev[b] .. off_dev[b + 1]), term ids ascending;
+ * off_dev int32 [B + 1], term_dev int32 and val_dev fp32 with room for B * max_terms entries (what lies past
+ * off_dev[B] is not written).  One workgroup per row: a radix selection on the bit patterns of the positive
+ * floats and a sweep in term order; integers only, LDS counters whose arrival order shows nowhere: the same
+ * bits on every run.  Stream-ordered, no allocation, no host sync, no workspace.  RF_ERR_INVALID before any
+ * device call: a null or misaligned pointer, B or V < 1, max_terms out of range.
+ * New in this build; the reference has no learned sparse arm. */
+typedef struct rf_mlm_head {        /* device fp16, nn.Linear layout, 16-byte aligned, caller keeps alive */
+  const void *tr_w, *tr_b;          /* [H,H], [H]  cls.predictions.transform.dense */
+  const void *tr_ln_g, *tr_ln_b;    /* [H]         cls.predictions.transform.LayerNorm */
+  const void *dec_w, *dec_b;        /* [V,H], [V]  cls.predictions.decoder (tied: the word embeddings), cls.predictions.bias */
+  int32_t vocab;
+} rf_mlm_head;
+size_t rf_encode_terms_workspace_bytes(const rf_encoder_t* enc, int B, int T);
+int rf_encode_terms(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
+                    const rf_mlm_head* head, float* weights_dev, void* workspace_dev, size_t workspace_bytes,
+                    void* stream);
+#define RF_TERMS_MAX 256
+int rf_sparsify_terms(const float* weights_dev, int B, int V, int max_terms, int32_t* off_dev, int32_t* term_dev,
+                      float* val_dev, void* stream);
+
 /* ---- tokenizer: the text -> token-id stage in front of rf_encode ------------------------
  * Reference: the WordPiece tokenizer SentenceTransformer('all-MiniLM-L6-v2') loads by name
  * (vector_rag_mcp/main.py:41,50; "chunking_storing (1).py":8,380).  Host code, multi-threaded.

@@ -99,6 +99,16 @@ class QaHead(Structure):
     _fields_ = [("qa_w", c_void_p), ("qa_b", c_void_p)]
 
 
+# learned sparse vectors (include/ragfin.h, rf_encode_terms)
+RF_TERMS_MAX = 256           # terms rf_sparsify_terms keeps of one row, at most
+
+
+class MlmHead(Structure):
+    """rf_mlm_head: cls.predictions of a BertForMaskedLM (device fp16 pointers)."""
+    _fields_ = [("tr_w", c_void_p), ("tr_b", c_void_p), ("tr_ln_g", c_void_p), ("tr_ln_b", c_void_p),
+                ("dec_w", c_void_p), ("dec_b", c_void_p), ("vocab", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/ragfin.h declares
 SIGNATURES = {
     "rf_version": (c_int, []),
@@ -236,6 +246,10 @@ SIGNATURES = {
     "rf_stitch_spans": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
     "rf_stitch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "rf_encode_terms_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rf_encode_terms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(MlmHead), c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
+    "rf_sparsify_terms": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # present only in the experiments build (libragfin_hip_exp.so, tools/): bound when exported

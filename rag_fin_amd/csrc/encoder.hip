@@ -1595,12 +1595,14 @@ extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const 
   return encode_enqueue(enc, ids_dev, lens_dev, B, T, out_f16_dev, out_f32_dev, workspace_dev, st);
 }
 
-// rf_score_pairs (rerank.hip) and rf_answer_spans (reader.hip) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
+const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc) { return enc->cfg; }
+
+// rf_score_pairs (rerank.hip), rf_answer_spans (reader.hip) and rf_encode_terms (splade.hip) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
 // rf_encode's alone, so a pair forward can never replay an embedding graph, nor the other way round.
 int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
                     const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
                     const char* who) {
-  if (enc->cfg.type_vocab < 2) {
+  if (!ends.terms && enc->cfg.type_vocab < 2) {
     rf_set_error("%s: the encoder has %d token-type row(s); a pair needs 2", who, enc->cfg.type_vocab);
     return RF_ERR_UNSUPPORTED;
   }
@@ -1625,7 +1627,7 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
   const int32_t* m_ptr = ws.tok_off + B;
 
   if (B > 1) hipLaunchKernelGGL(k_tok_offsets, dim3(1), dim3(256), 0, st, lens_dev, B, T, ws.tok_off);   // B == 1: the embedding launch writes them
-  if (ends) {
+  if (ends && !ends->terms) {
     rf_launch_embed_pair(ids_dev, lens_dev, ends->seg, ws.tok_off, B, T, c, w, ws.x, st);
   } else {
     const int chunks = B * ((T + 31) / 32);   // one workgroup per 32 positions of a row
@@ -1693,7 +1695,9 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
                                                  tiles, m_ptr, y, (const _Float16*)w.ln2_g + (size_t)l * HID,
                                                  (const _Float16*)w.ln2_b + (size_t)l * HID, c.ln_eps, ws.pre, st);
   }
-  if (ends && ends->qa)
+  if (ends && ends->terms)
+    rf_launch_terms_head(x, ws.tok_off, B, T, *ends->terms, c.ln_eps, st);
+  else if (ends && ends->qa)
     rf_launch_qa_spans(x, ws.tok_off, B, T, *ends, st);
   else if (ends)
     rf_launch_cls_head(x, ws.tok_off, B, *ends->head, ends->logits, st);

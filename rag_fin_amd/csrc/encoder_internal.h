@@ -163,6 +163,7 @@ struct rf_pair_ends {
   rf_span* spans;             // [B, n_best]
   float* norm;                // [B, 3]
   float* qa_logits;           // [B, T, 2] or nullptr
+  const struct rf_terms_end* terms;   // a third pair of ends (splade.hip), or nullptr: see below
 };
 void rf_launch_embed_pair(const int32_t* ids, const int32_t* lens, const int32_t* seg, int32_t* tok_off, int B, int T,
                           const rf_encoder_config& c, const rf_encoder_weights& w, _Float16* out, hipStream_t st);
@@ -170,6 +171,18 @@ void rf_launch_cls_head(const _Float16* x, const int32_t* tok_off, int B, const 
                         hipStream_t st);
 void rf_launch_qa_spans(const _Float16* x, const int32_t* tok_off, int B, int T, const rf_pair_ends& ends,
                         hipStream_t st);
+// ---- splade.hip: a term forward = the same layers between the embedder's embedding launch and an MLM head ---------
+// With `terms` set in rf_pair_ends the forward opens with k_embed_ln (token types 0: `seg` is not read and the
+// encoder needs no second token-type row) and closes with k_mlm_transform + k_mlm_decode_max; the other fields
+// are unused.
+struct rf_terms_end {
+  const rf_mlm_head* head;    // device pointers of the masked-language-model head
+  float* weights;             // [B, vocab]
+  _Float16* g;                // [ceil32(B * T), 384] tiled: the transformed tokens (workspace)
+};
+void rf_launch_terms_head(const _Float16* x, const int32_t* tok_off, int B, int T, const rf_terms_end& e, float eps,
+                          hipStream_t st);
+const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc);   // encoder.hip
 // encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph);
 // `who` names the public entry in the error text
 int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,

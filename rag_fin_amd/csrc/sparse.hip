@@ -27,9 +27,14 @@ __device__ __forceinline__ unsigned long long sparse_key(float score, uint32_t r
   return ((unsigned long long)__builtin_bit_cast(uint32_t, score) << 32) | (unsigned long long)(0xFFFFFFFFu - row);
 }
 
-// acc + (w * imp) with two roundings: the intrinsics are never contracted into an fma.
+// acc + (w * imp) with two roundings.  (__fadd_rn(acc, __fmul_rn(w, imp)) is plain `acc + w * imp` to the
+// compiler, which contracted it into v_fmac_f32 -- invisible while the weights were the small term counts of
+// BM25 queries, whose products are exact, and 1-2 ulp off the definition with the real-valued weights of
+// learned sparse vectors.  The pragma keeps the product and the sum apart.)
 __device__ __forceinline__ float sparse_add(float acc, float w, float imp) {
-  return __fadd_rn(acc, __fmul_rn(w, imp));
+#pragma clang fp contract(off)
+  const float prod = w * imp;
+  return acc + prod;
 }
 
 // first p in [lo, hi) with rows[p] >= row (rows ascending), hi if none

@@ -59,7 +59,7 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                    mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
                    hybrid: bool = False, offset: int | None = None, boost_filter: str = "",
-                   boost_weight: float | None = None):
+                   boost_weight: float | None = None, lexical: str | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -74,6 +74,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     fetch_k each and are fused by reciprocal rank; `score` is then the fused score.  With filter and
     rerank; not with min_score / max_score, group_by or mmr_lambda.  Needs the store's lexical index
     (LEXICAL_INDEX=1 at ingest).
+    lexical: optional choice of the lexical arm of a hybrid search -- "bm25" (the default), "learned" (the
+    learned sparse vectors of a SPLADE model; needs SPARSE_MODEL_DIR) or "both" (three arms fused).
     offset: optional paging -- skip that many of the best chunks, return the next top_k.  With filter and
     min_score / max_score; not with rerank, hybrid, mmr_lambda or group_by.
     boost_filter / boost_weight: optional soft filter -- the chunks the expression boost_filter selects
@@ -94,6 +96,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                 kw["rerank"] = True
             if hybrid:
                 kw["hybrid"] = True
+            if lexical is not None:
+                kw["lexical"] = lexical
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
                                         boost={"filter": boost_filter, "weight": boost_weight}, **kw)
             return {"status": "success", "query": query, "results": contexts, "result_count": len(contexts)}
@@ -103,6 +107,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
             mmr["rerank"] = True
         if hybrid:
             mmr["hybrid"] = True
+        if lexical is not None:
+            mmr["lexical"] = lexical
         if offset is not None:   # (a paged call bypasses the micro-batcher too: one batch shares one offset)
             mmr["offset"] = offset
         if group_by is not None:

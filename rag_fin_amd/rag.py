@@ -29,7 +29,8 @@ DEFAULT_PROMPT = "Question: {question}\n\nRetrieved contexts:\n{context}\n\nAnsw
 class VectorRAG:
     def __init__(self, gemini_api_key: str | None = None, collection_name: str = "fin_chunks", *,
                  embedder=None, store=None, generator: Callable[[str], str] | None = None,
-                 llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None, reader=None):
+                 llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None, reader=None,
+                 sparse_encoder=None):
         """embedder: .encode(list[str]) -> [n, dim] (rag_fin_amd.embedder.Embedder);
         store: rag_fin_amd.store.CorpusStore.  `gemini_api_key` is accepted for
         signature compatibility and only handed to `generator` factories upstream.
@@ -37,14 +38,21 @@ class VectorRAG:
         second stage of search(..., rerank=True).
         reader: .predict(question, list[text], top_k=1) -> [{"answer", "score", "start", "end",
         "context_index"}] (rag_fin_amd.reader.ExtractiveReader): the answer step of search_and_answer when no
-        generator is set."""
+        generator is set.
+        sparse_encoder: .encode_document / .encode_query(list[str]) -> sparse [n, V] (rag_fin_amd.sparse_encoder.
+        SparseEncoder): declared on the store as its learned sparse field ("sparse_embedding"), the arm of
+        search(..., hybrid=True, lexical="learned" | "both")."""
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
         self.similarity_model = embedder
         self.reranker = reranker
         self.reader = reader
+        self.sparse_encoder = sparse_encoder
         self.collection = store
+        if sparse_encoder is not None:
+            store.create_index("sparse_embedding", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "IP"},
+                               encoder=sparse_encoder)
         self.collection_name = collection_name
         self.generator = generator
         self.prompt_template = prompt_template
@@ -85,7 +93,7 @@ class VectorRAG:
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
-               hybrid: bool = False, offset: int | None = None, boost=None) -> list[dict]:
+               hybrid: bool = False, offset: int | None = None, boost=None, lexical: str = "bm25") -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -105,6 +113,10 @@ class VectorRAG:
         kept; `score` is the fused score.  With expr (both arms) and with rerank (the cross-encoder
         scores the fused candidates); not with min_score / max_score, group_by or mmr_lambda
         (ValueError).
+        lexical (with hybrid): which lexical arm is fused with the dense one -- "bm25" (the default), "learned"
+        (the learned sparse field: the query's SPLADE vector against the chunks', inner product; needs
+        VectorRAG(..., sparse_encoder=)) or "both" (three arms).  Anything but "bm25" without hybrid or
+        without a sparse encoder raises ValueError.
         offset: skip that many of the best chunks first -- the chunks of ranks offset + 1 ...
         offset + top_k (`rank` counts from 1 within the page); with expr and min_score / max_score,
         not with rerank, hybrid, mmr_lambda or group_by (ValueError).
@@ -115,13 +127,14 @@ class VectorRAG:
         rerank, hybrid, group_by, mmr_lambda, min_score / max_score or offset (ValueError)."""
         ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
+        self._check_lexical(lexical, hybrid)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if rerank:
             return self._search_reranked([query], top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
-                                         hybrid)[0]
+                                         hybrid, lexical)[0]
         if hybrid:
-            return self._contexts(self._search_hybrid([query], top_k, top_k, expr, fetch_k)[0])
+            return self._contexts(self._search_hybrid([query], top_k, top_k, expr, fetch_k, lexical)[0])
         q = self._embed([query])
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,
@@ -176,20 +189,34 @@ class VectorRAG:
         if mmr_lambda is not None:
             raise ValueError("hybrid search does not combine with mmr_lambda")
 
-    def _search_hybrid(self, queries, top_k, limit, expr, fetch_k):
-        """The dense and the BM25 arm at fetch_k each, fused by RRF -> `limit` hits per query."""
+    def _check_lexical(self, lexical, hybrid) -> None:
+        if lexical not in ("bm25", "learned", "both"):
+            raise ValueError(f"lexical must be 'bm25', 'learned' or 'both', got {lexical!r}")
+        if lexical != "bm25":
+            if not hybrid:
+                raise ValueError(f"lexical={lexical!r} chooses the lexical arm of a hybrid search: pass hybrid=True")
+            if self.sparse_encoder is None:
+                raise ValueError(f"lexical={lexical!r} needs a sparse encoder (VectorRAG(..., sparse_encoder="
+                                 "SparseEncoder.from_local(dir)))")
+
+    def _search_hybrid(self, queries, top_k, limit, expr, fetch_k, lexical: str = "bm25"):
+        """The dense arm and the lexical arm(s) -- BM25, the learned sparse field, or both -- at fetch_k each,
+        fused by RRF -> `limit` hits per query."""
         from .hybrid import AnnSearchRequest, RRFRanker
         fk = self._default_fetch_k(top_k) if fetch_k is None else fetch_k
         if isinstance(fk, bool) or not isinstance(fk, int) or not 1 <= fk <= 64:
             raise ValueError(f"hybrid search: fetch_k must be an integer in 1..64, got {fk!r}")
         if not 1 <= limit <= fk:
             raise ValueError(f"hybrid search: need 1 <= top_k <= fetch_k (got top_k = {limit}, fetch_k = {fk})")
-        reqs = [AnnSearchRequest(self._embed(list(queries)), "embedding", {"metric_type": "COSINE"}, fk, expr),
-                AnnSearchRequest(list(queries), "sparse", {"metric_type": "BM25"}, fk, expr)]
+        reqs = [AnnSearchRequest(self._embed(list(queries)), "embedding", {"metric_type": "COSINE"}, fk, expr)]
+        if lexical in ("bm25", "both"):
+            reqs.append(AnnSearchRequest(list(queries), "sparse", {"metric_type": "BM25"}, fk, expr))
+        if lexical in ("learned", "both"):
+            reqs.append(AnnSearchRequest(list(queries), "sparse_embedding", {"metric_type": "IP"}, fk, expr))
         return self.collection.hybrid_search(reqs, RRFRanker(), limit, output_fields=OUTPUT_FIELDS)
 
     def _search_reranked(self, queries, top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
-                         hybrid: bool = False):
+                         hybrid: bool = False, lexical: str = "bm25"):
         if self.reranker is None:
             raise ValueError("rerank=True needs a reranker (VectorRAG(..., reranker=CrossEncoder.from_local(dir)))")
         if mmr_lambda is not None:
@@ -200,7 +227,7 @@ class VectorRAG:
         if fk < top_k:
             raise ValueError(f"fetch_k={fk} is less than top_k={top_k}")
         if hybrid:   # the fused candidates: `score` is then the fused score
-            results = self._search_hybrid(queries, top_k, fk, expr, fk)
+            results = self._search_hybrid(queries, top_k, fk, expr, fk, lexical)
         else:
             q = self._embed(list(queries))
             results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
@@ -228,13 +255,13 @@ class VectorRAG:
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
                      rerank: bool = False, hybrid: bool = False, offset: int | None = None,
-                     boost=None) -> list[list[dict]]:
+                     boost=None, lexical: str = "bm25") -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
         the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call; hybrid:
-        dense + BM25 fused by reciprocal rank for every query, as in search(); offset: one for the
-        whole batch, as in search().
+        dense + BM25 (lexical: or the learned sparse arm, or both) fused by reciprocal rank for every query, as
+        in search(); offset: one for the whole batch, as in search().
         expr may also be a list or tuple with one entry per query (a filter string, or None for "no
         filter"): per-query filters, still one corpus sweep per 64 queries
         (CorpusStore.search(expr=[...])).  The list form is the plain path only: with rerank, hybrid,
@@ -249,15 +276,16 @@ class VectorRAG:
             if len(expr) != len(queries):
                 raise ValueError(f"expr list: {len(expr)} entries for {len(queries)} queries (one entry per query)")
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
+        self._check_lexical(lexical, hybrid)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if not queries:
             return []
         if rerank:
             return self._search_reranked(list(queries), top_k, expr, min_score, max_score, group_by, mmr_lambda,
-                                         fetch_k, hybrid)
+                                         fetch_k, hybrid, lexical)
         if hybrid:
-            return [self._contexts(r) for r in self._search_hybrid(list(queries), top_k, top_k, expr, fetch_k)]
+            return [self._contexts(r) for r in self._search_hybrid(list(queries), top_k, top_k, expr, fetch_k, lexical)]
         q = self._embed(list(queries))
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
                                          expr=expr, output_fields=OUTPUT_FIELDS,

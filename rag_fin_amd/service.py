@@ -10,6 +10,9 @@ Environment (dotenv-style names):
                        retrieved chunk when no generator is plugged in
   READER_DOC_STRIDE    optional overlap in tokens: the reader reads a context that does not fit its window in
                        sliding windows decoded as one context (ExtractiveReader(doc_stride=...)); unset: it is cut
+  SPARSE_MODEL_DIR     optional local SPLADE directory (a BertForMaskedLM of the MiniLM-H384 family, same three
+                       files): declares the learned sparse field, enables search(..., hybrid=True,
+                       lexical="learned" | "both")
   LEXICAL_INDEX        1: declare the lexical (BM25) index at ingest: enables search(..., hybrid=True)
   RAGFIN_DATA_DIR      folder with icici_q{1..4}_2023/*.json (default: extract_data)
   RAGFIN_DEVICE        torch device string (default cuda:0)
@@ -56,11 +59,21 @@ def _load_reader(reader_dir, device, doc_stride=None):
     return ExtractiveReader.from_local(reader_dir, device=device, doc_stride=doc_stride)
 
 
+def _load_sparse_encoder(sparse_dir, device):
+    if not sparse_dir:
+        return None
+    from .sparse_encoder import SparseEncoder
+    return SparseEncoder.from_local(sparse_dir, device=device)
+
+
 def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
-              hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None):
+              hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None,
+              sparse_dir: str | None = None):
     """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
-    can run; its posting lists are built by the first such search."""
+    can run; its posting lists are built by the first such search.
+    sparse_dir: a local SPLADE checkpoint: the learned sparse field is declared on the store (VectorRAG does
+    it), its vectors are encoded by the first search(..., hybrid=True, lexical="learned" | "both")."""
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
@@ -69,8 +82,10 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     ingest(store, embedder, chunker.build_all_chunks(data_dir))
     if hybrid:
         store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
+    sparse = _load_sparse_encoder(sparse_dir, device)
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
-                     reranker=_load_reranker(reranker_dir, device), reader=_load_reader(reader_dir, device, reader_doc_stride))
+                     reranker=_load_reranker(reranker_dir, device), reader=_load_reader(reader_dir, device, reader_doc_stride),
+                     **({} if sparse is None else {"sparse_encoder": sparse}))
 
 
 def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
@@ -128,6 +143,7 @@ def build_rag_from_env():
     reranker_dir = os.getenv("RERANKER_MODEL_DIR") or None
     reader_dir = os.getenv("READER_MODEL_DIR") or None
     reader_doc_stride = int(os.environ["READER_DOC_STRIDE"]) if os.getenv("READER_DOC_STRIDE") else None
+    sparse_dir = os.getenv("SPARSE_MODEL_DIR") or None
     if int(os.getenv("WORLD_SIZE", "1")) > 1:
         return build_sharded_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                                  int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
@@ -135,4 +151,4 @@ def build_rag_from_env():
     return build_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                      os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
                      reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1", reader_dir=reader_dir,
-                     reader_doc_stride=reader_doc_stride)
+                     reader_doc_stride=reader_doc_stride, **({"sparse_dir": sparse_dir} if sparse_dir else {}))

@@ -264,6 +264,9 @@ class _RWLock:
                 self._cond.notify_all()
 
 
+LEARNED_FIELD = "sparse_embedding"   # the learned sparse field (create_index(..., encoder=))
+
+
 class MutationResult:
     """What delete / upsert return, shaped like pymilvus' MutationResult."""
 
@@ -428,6 +431,13 @@ class CorpusStore:
         # (the token positions a PHRASE_MATCH filter needs live on that SparseIndex: attached once,
         # by the first such filter, and gone with it on any mutation)
         self._sparse_lock = threading.Lock()
+        # the learned sparse field (create_index("sparse_embedding", ..., encoder=)): the attached encoder, the
+        # per-row term vectors of the rows encoded so far as host CSR (indptr int64, indices int32, data fp32: a
+        # prefix of the rows; the rest is encoded by the next search) and the (postings, SparseIndex) over them
+        # (None: to be transposed again).  Guarded like the lexical index.
+        self._learned = None
+        self._learned_rows = None
+        self._learned_index = None
         # index maintenance: the last built (postings, SparseIndex, analyzer, params) and, in
         # order, the mutations since -- ("delete", keep mask) / ("append", texts) -- which the next
         # _sparse_index() replays through SparseIndex.compacted / .appended instead of building whole.
@@ -462,6 +472,8 @@ class CorpusStore:
             self._dcols = None
             self._sparse = None
             self._forget_lexical()
+            self._learned_rows = None
+            self._learned_index = None
 
     def _forget_lexical(self) -> None:
         """Drop the retained lexical state: the next _sparse_index() builds whole."""
@@ -519,8 +531,23 @@ class CorpusStore:
         through SparseIndex.appended / .compacted, which analyse only the appended texts and leave the
         arrays bit for bit as a build of the surviving rows would.  They are built whole
         instead after drop(), create_index / drop_index of "sparse", a changed `analyzer`, more than
-        LEXICAL_LOG_MAX pending mutations, when no row held a term, or when a replay raised."""
+        LEXICAL_LOG_MAX pending mutations, when no row held a term, or when a replay raised.
+        field_name "sparse_embedding" with {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "IP"} and
+        encoder=<a SparseEncoder> declares the learned sparse field (Milvus: a SPARSE_FLOAT_VECTOR field
+        filled by a function): the store derives each row's term vector from its `text` with the attached
+        encoder (encode_document), lazily at the first search of the field; after an add / insert / upsert
+        only the new rows are encoded, a delete drops its rows, and the per-row vectors (host CSR) are
+        transposed again on the host -- a stable sort by term, rows ascending within a term -- into the
+        posting arrays a SparseIndex serves.  They are not saved: a loaded store encodes
+        again, as the lexical index is rebuilt."""
         params = dict(index_params or {})
+        if field_name == LEARNED_FIELD:
+            self._check_learned_params(params, kwargs.get("encoder"))
+            with self._rw.write():
+                self._learned = {"encoder": kwargs["encoder"]}
+                self._learned_rows = None
+                self._learned_index = None
+            return
         if field_name == "sparse":
             sparse = self._check_sparse_params(params)
             with self._rw.write():
@@ -567,12 +594,37 @@ class CorpusStore:
         return {"bm25_k1": k1, "bm25_b": b}
 
     @staticmethod
+    def _check_learned_params(params, encoder) -> None:
+        itype = str(params.get("index_type", "SPARSE_INVERTED_INDEX")).upper()
+        if itype != "SPARSE_INVERTED_INDEX":
+            raise ValueError(f"create_index: the sparse_embedding field takes index_type SPARSE_INVERTED_INDEX, got {itype!r}")
+        metric = str(params.get("metric_type", "IP")).upper()
+        if metric != "IP":
+            raise ValueError(f"create_index: the sparse_embedding field takes metric_type IP, got {metric!r}")
+        p = params.get("params")
+        if p is not None and not isinstance(p, dict):
+            raise ValueError("create_index: params must be a dict")
+        if encoder is None or not all(hasattr(encoder, a) for a in ("encode_document", "encode_query", "vocab_size")):
+            raise ValueError("create_index: the sparse_embedding field is derived from the text column and needs "
+                             "encoder=<a SparseEncoder> (encode_document, encode_query, vocab_size)")
+
+    @staticmethod
+    def _is_learned_field(kwargs) -> bool:
+        return LEARNED_FIELD in (kwargs.get("field_name"), kwargs.get("index_name"))
+
+    @staticmethod
     def _is_sparse_field(kwargs) -> bool:
         return "sparse" in (kwargs.get("field_name"), kwargs.get("index_name"))
 
     def drop_index(self, **kwargs) -> None:
         """Back to FLAT (the shadow of SQ8 is freed).  field_name="sparse" (or index_name="sparse"):
         drop the lexical index instead and leave the vector index alone."""
+        if self._is_learned_field(kwargs):
+            with self._rw.write():
+                self._learned = None
+                self._learned_rows = None
+                self._learned_index = None
+            return
         if self._is_sparse_field(kwargs):
             with self._rw.write():
                 self._sparse_params = None
@@ -587,6 +639,8 @@ class CorpusStore:
 
     def has_index(self, **kwargs) -> bool:
         """field_name="sparse" (or index_name="sparse") asks about the lexical index."""
+        if self._is_learned_field(kwargs):
+            return self._learned is not None
         if self._is_sparse_field(kwargs):
             return self._sparse_params is not None
         return self._index_params is not None
@@ -646,6 +700,7 @@ class CorpusStore:
         texts, periods, chunk_types, statement_types, primary_values = cols
         self._sparse = None   # the lexical index is brought up to date by the next BM25 search
         self._log_lexical("append", list(texts))
+        self._learned_index = None   # the new rows are encoded by the next search of the learned field
         self._mutations += 1
         base = self.num_entities
         for j, pk in enumerate(ids):
@@ -728,6 +783,7 @@ class CorpusStore:
         n_old = self.num_entities
         self._sparse = None   # the lexical index is brought up to date by the next BM25 search
         self._log_lexical("delete", keep_mask)
+        self._learned_drop_rows(keep_mask)
         self._mutations += 1
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
@@ -869,6 +925,13 @@ class CorpusStore:
             return self._search_expr_list(data, anns_field, param, limit, expr, output_fields, group_by_field,
                                           mmr_lambda, mmr_fetch_k, offset)
         offset = check_offset(offset, param, limit)
+        if anns_field == LEARNED_FIELD:
+            if offset or group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
+                raise ValueError("learned sparse search (anns_field='sparse_embedding') has no offset, grouping or MMR form")
+            q = self._check_learned_search(data, param, limit)
+            fields = self._check_output_fields(output_fields)
+            with self._rw.read():
+                return self._search_learned(q, limit, expr, fields)
         if offset and (anns_field == "sparse" or group_by_field is not None or mmr_lambda is not None
                        or mmr_fetch_k is not None):
             raise ValueError("offset has no BM25 (anns_field='sparse'), grouping (group_by_field) or MMR (mmr_lambda) form")
@@ -901,6 +964,8 @@ class CorpusStore:
         string, or None for "no filter"."""
         if anns_field == "sparse":
             raise ValueError("per-query filters (a list expr) have no BM25 form (anns_field='sparse')")
+        if anns_field == LEARNED_FIELD:
+            raise ValueError("per-query filters (a list expr) have no learned sparse form (anns_field='sparse_embedding')")
         if self._is_text(data):
             raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
         if group_by_field is not None:
@@ -980,6 +1045,8 @@ class CorpusStore:
             raise ValueError("boosted search (ranker) cannot be combined with per-query filters (a list expr)")
         if anns_field == "sparse":
             raise ValueError("boosted search (ranker) has no BM25 form (anns_field='sparse')")
+        if anns_field == LEARNED_FIELD:
+            raise ValueError("boosted search (ranker) has no learned sparse form (anns_field='sparse_embedding')")
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         if self._is_text(data):
@@ -1233,6 +1300,100 @@ class CorpusStore:
         scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
         return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
 
+    # -- the learned sparse field: search(anns_field="sparse_embedding") ----------------------
+    def _check_learned_search(self, data, param, limit):
+        """Everything a learned sparse search refuses -> the queries: a list of strings (encoded with the
+        attached encoder's encode_query) or the checked CSR batch (q_off, q_term, q_weight) of supplied vectors."""
+        from .sparse_encoder import check_query_rows
+        if self._learned is None:
+            raise ValueError("no sparse_embedding index: call create_index('sparse_embedding', {'index_type': "
+                             "'SPARSE_INVERTED_INDEX', 'metric_type': 'IP'}, encoder=...) first")
+        metric = str((param or {}).get("metric_type", "IP")).upper()
+        if metric != "IP":
+            raise ValueError(f"the sparse_embedding field is searched with metric_type IP, search asked for {metric}")
+        params = (param or {}).get("params")
+        if params is not None and not isinstance(params, dict):
+            raise ValueError("search: param['params'] must be a dict")
+        if params and (params.get("radius") is not None or params.get("range_filter") is not None):
+            raise ValueError("learned sparse search (anns_field='sparse_embedding') has no range form (radius / range_filter)")
+        if isinstance(param, dict) and param.get("offset"):
+            raise ValueError("learned sparse search (anns_field='sparse_embedding') takes no offset")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
+            raise ValueError("limit must be an integer >= 1")
+        if limit > _lib.RF_MAX_K:
+            raise ValueError(f"learned sparse search: limit = {limit} > {_lib.RF_MAX_K} (the sparse arm is not paged)")
+        if self._is_text(data):
+            return [data] if isinstance(data, str) else list(data)
+        if hasattr(data, "tocsr") or (isinstance(data, (list, tuple)) and all(isinstance(r, dict) for r in data)):
+            return check_query_rows(data, int(self._learned["encoder"].vocab_size))
+        raise ValueError("the sparse_embedding field is searched with query strings, a scipy sparse matrix or a "
+                         "list of {term_id: weight} dicts")
+
+    @staticmethod
+    def _learned_query_count(q) -> int:
+        return len(q) if isinstance(q, list) else int(q[0].size - 1)
+
+    def _learned_drop_rows(self, keep_mask) -> None:
+        """A delete on the learned field: the encoded rows that go are dropped from the host CSR (rows not
+        encoded yet are simply not there).  Caller holds the write lock."""
+        self._learned_index = None
+        if self._learned_rows is None:
+            return
+        indptr, indices, data = self._learned_rows
+        done = indptr.size - 1
+        keep = np.asarray(keep_mask[:done], dtype=bool)
+        counts = np.diff(indptr)
+        entry = np.repeat(keep, counts)
+        new_ptr = np.zeros(int(keep.sum()) + 1, dtype=np.int64)
+        np.cumsum(counts[keep], out=new_ptr[1:])
+        self._learned_rows = (new_ptr, indices[entry], data[entry])
+
+    def _learned_postings(self):
+        """(TermPostings, SparseIndex | None) over the current text column: the rows not encoded yet go through
+        the attached encoder, then the per-row vectors are transposed on the host."""
+        from .sparse_encoder import TermPostings
+        with self._sparse_lock:
+            if self._learned_index is None:
+                enc = self._learned["encoder"]
+                V, n = int(enc.vocab_size), self.num_entities
+                rows = self._learned_rows or (np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
+                done = rows[0].size - 1
+                if done < n:
+                    new = enc.encode_document(self.columns["text"][done:n]).tocsr()
+                    new.sort_indices()
+                    if new.shape != (n - done, V):
+                        raise ValueError(f"the sparse encoder returned {new.shape}, expected {(n - done, V)}")
+                    rows = (np.concatenate([rows[0], rows[0][-1] + np.asarray(new.indptr[1:], dtype=np.int64)]),
+                            np.concatenate([rows[1], np.asarray(new.indices, dtype=np.int32)]),
+                            np.concatenate([rows[2], np.asarray(new.data, dtype=np.float32)]))
+                    self._learned_rows = rows
+                tp = TermPostings(rows[0], rows[1], rows[2], V)
+                self._learned_index = (tp, SparseIndex(tp, self.index.device) if tp.nnz else None)
+            return self._learned_index
+
+    def _learned_arm(self, q, limit: int, expr):
+        """The learned sparse arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors, or
+        None when nothing can hit (no row holds a term)."""
+        _, sp = self._learned_postings()
+        if sp is None:
+            return None
+        if isinstance(q, list):
+            m = self._learned["encoder"].encode_query(q).tocsr()
+            m.sort_indices()
+            q = (np.asarray(m.indptr, dtype=np.int32), np.asarray(m.indices, dtype=np.int32),
+                 np.asarray(m.data, dtype=np.float32))
+        kw = {} if filter_expr.is_empty(expr) else {"filt": self.build_filter(expr)}
+        scores, rows, _ = sp.search(q[0], q[1], q[2], limit, want_exact=False, **kw)
+        return scores, rows
+
+    def _search_learned(self, q, limit, expr, fields):
+        B = self._learned_query_count(q)
+        res = self._learned_arm(q, limit, expr) if self.num_entities and B else None
+        if res is None:
+            return [[] for _ in range(B)]
+        scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
+        return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
+
     def _hits(self, rows, scores, fields) -> list:
         """The Hit list of one query from its row numbers (best first, -1 ends it) and scores."""
         hits = []
@@ -1254,7 +1415,7 @@ class CorpusStore:
 
     def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields: Iterable[str] | None = None, ranker=None):
         """pymilvus-shaped hybrid search: every AnnSearchRequest of `reqs` (1..4; anns_field "embedding"
-        with query vectors, or "sparse" with query strings) runs on the GPU with its own limit (<= 64)
+        with query vectors, "sparse" with query strings, or "sparse_embedding" with query strings or sparse vectors) runs on the GPU with its own limit (<= 64)
         and its own expr, and `rerank` -- an RRFRanker -- fuses the arms' ranked lists per query:
         fused(d) = sum over the arms holding d of weight / (k + rank), the best `limit` (<= 64) rows by
         (fused desc, row asc).  One list of hits per query; hit.score is the fused score.  The fusion
@@ -1286,6 +1447,9 @@ class CorpusStore:
                 if r.anns_field == "sparse":
                     q = self._check_sparse_search(r.data, r.param, r.limit)
                     prepared.append((r, q, len(q)))
+                elif r.anns_field == LEARNED_FIELD:
+                    q = self._check_learned_search(r.data, r.param, r.limit)
+                    prepared.append((r, q, self._learned_query_count(q)))
                 elif r.anns_field == "embedding":
                     if self._is_text(r.data):
                         raise ValueError("the embedding field is searched with vectors, not with strings")
@@ -1312,6 +1476,9 @@ class CorpusStore:
             for r, q, _ in prepared:
                 if r.anns_field == "sparse":
                     res = self._sparse_arm(q, r.limit, r.expr)
+                    rows = None if res is None else res[1]
+                elif r.anns_field == LEARNED_FIELD:
+                    res = self._learned_arm(q, r.limit, r.expr)
                     rows = None if res is None else res[1]
                 else:
                     rows = self._dense_arm(q, r.limit, r.expr)

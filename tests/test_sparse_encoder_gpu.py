@@ -1,0 +1,295 @@
+"""GPU tests of learned sparse search: rf_encode_terms and rf_sparsify_terms through
+rag_fin_amd.sparse_encoder.SparseEncoder, and the store's "sparse_embedding" field.
+
+The numeric stage (the dense [B, V] term weights) is judged by tolerance against the fp64 numpy mirror
+terms_reference of tests/test_sparse_encoder_cpu.py (itself pinned to transformers.BertForMaskedLM), evaluated
+on the SAME fp16-rounded weights; seeded random weights, the decoder tied to the word embeddings.  The selection
+stage and the search are judged exactly.
+
+TOL = 3 x the largest |w - mirror| measured on the MI355X over the parity shapes below
+(profiles/sparse_encoder_measurements.jsonl), the margin rule of tests/test_encoder_gpu.py."""
+import numpy as np
+import pytest
+
+from test_sparse_encoder_cpu import SHAPES, case, mirror, model
+
+pytestmark = pytest.mark.gpu
+TOL = 7.4e-3          # 3 x the 2.48e-3 measured (64 x 128, the fused layer path; the other shapes: 1.3e-3 .. 2.2e-3)
+FLT_MIN = float(np.finfo(np.float32).tiny)
+
+
+@pytest.fixture(scope="module")
+def encoders(gpu_device):
+    from rag_fin_amd.sparse_encoder import SparseEncoder
+    made = {}
+
+    def get(which):
+        if which not in made:
+            cfg, _, w, head, _, _ = model(which)
+            made[which] = SparseEncoder(w, head, cfg, device=gpu_device)
+        return made[which]
+    return get
+
+
+@pytest.fixture(scope="module")
+def dense(encoders):
+    """The kernel's dense output per parity case, computed once: float32 [B, V] host arrays."""
+    got = {}
+
+    def get(name):
+        if name not in got:
+            which, ids, lens = case(name)
+            got[name] = encoders(which).encode_ids(ids, lens).cpu().numpy()
+        return got[name]
+    return get
+
+
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_term_weights_match_the_mirror(dense, name):
+    from conftest import record_measurement
+    got, want = dense(name), mirror(name)
+    _, _, lens = case(name)
+    assert got.dtype == np.float32 and got.shape == want.shape
+    err = float(np.abs(got - want).max())
+    record_measurement(f"sparse_encoder_{name}", max_abs_weight=err, weight_max=float(want.max()),
+                       zero_fraction=float((want == 0).mean()))
+    print(f"sparse_encoder_{name}: max |w - mirror| = {err:.3e} (weights up to {want.max():.2f}, "
+          f"{(want == 0).mean():.2f} zero)")
+    assert np.isfinite(got).all() and not (got < 0).any()
+    assert not np.signbit(got).any()                                  # no -0.0
+    assert ((got == 0) | (got >= FLT_MIN)).all()                      # +0.0 or a normal float
+    for b in np.flatnonzero(lens < 1):
+        assert not got[b].any()
+    assert err < TOL, err
+
+
+def test_same_row_same_bits_anywhere_in_the_batch_and_across_calls(encoders):
+    enc = encoders("l2")
+    rng = np.random.default_rng(3)
+    lens = np.array([40, 17, 33, 40, 5, 29, 1], dtype=np.int32)
+    ids = rng.integers(1, 2005, (7, 40)).astype(np.int32)
+    a = enc.encode_ids(ids, lens).cpu().numpy().view(np.uint32)
+    b = enc.encode_ids(ids, lens).cpu().numpy().view(np.uint32)
+    assert np.array_equal(a, b)
+    for seed in (0, 1):
+        perm = np.random.default_rng(seed).permutation(7)
+        p = enc.encode_ids(ids[perm], lens[perm]).cpu().numpy().view(np.uint32)
+        assert np.array_equal(p, a[perm])
+    assert len({r.tobytes() for r in a}) == 7 and a.any()
+
+
+def test_unsupported_and_invalid_calls_are_refused(encoders, gpu_device):
+    import ctypes
+    import torch
+    from rag_fin_amd import _lib
+    from rag_fin_amd.sparse_encoder import SparseEncoder, random_mlm_head
+    from oracle import encoder as oenc
+    cfg = dict(oenc.MINILM_L6, layers=1, vocab_size=100, max_position=32)
+    enc = SparseEncoder(oenc.random_weights(cfg, 1), random_mlm_head(cfg, 1), cfg, device=gpu_device)
+    with pytest.raises(_lib.RagfinError) as e:                        # T > max_position
+        enc.encode_ids(np.ones((1, 33), np.int32), np.array([8], np.int32))
+    assert e.value.code == -2
+    enc._head_c.vocab = 99                                            # a head of another vocabulary
+    with pytest.raises(_lib.RagfinError) as e:
+        enc.encode_ids(np.ones((1, 8), np.int32), np.array([8], np.int32))
+    assert e.value.code == -2 and "vocab" in str(e.value)
+    enc._head_c.vocab = 100
+    ids = torch.ones((1, 8), dtype=torch.int32, device=gpu_device)
+    lens = torch.full((1,), 8, dtype=torch.int32, device=gpu_device)
+    out = torch.empty((1, 100), dtype=torch.float32, device=gpu_device)
+    need = enc.lib.rf_encode_terms_workspace_bytes(enc.encoder.handle, 1, 8)
+    assert need <= enc.lib.rf_encode_workspace_bytes(enc.encoder.handle, 1, 8) + 256 + 32 * 384 * 2   # no tokens x V term
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu_device)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    call = lambda nbytes: enc.lib.rf_encode_terms(enc.encoder.handle, p(ids), p(lens), 1, 8,   # noqa: E731
+                                                  ctypes.byref(enc._head_c), p(out), p(ws), nbytes,
+                                                  _lib.current_stream_ptr())
+    assert call(need - 1) == -3                                       # workspace too small
+    enc._head_c.dec_w += 2                                            # misaligned decoder matrix
+    assert call(need) == -1
+    enc._head_c.dec_w -= 2
+    one_type = dict(cfg, type_vocab=1)                                # token types 0: one row is enough
+    e1 = SparseEncoder(oenc.random_weights(one_type, 1), random_mlm_head(one_type, 1), one_type, device=gpu_device)
+    assert np.isfinite(e1.encode_ids(np.ones((1, 8), np.int32), np.array([8], np.int32)).cpu().numpy()).all()
+
+
+# ---- rf_sparsify_terms: exact ---------------------------------------------------------------------------------------
+def crafted_rows(max_terms: int, V: int = 2005) -> np.ndarray:
+    rng = np.random.default_rng(max_terms)
+    rows = []
+    rows.append(np.zeros(V, np.float32))                                             # all zero
+    r = np.zeros(V, np.float32)
+    r[rng.choice(V, max_terms, replace=False)] = rng.uniform(0.1, 3.0, max_terms).astype(np.float32)
+    rows.append(r)                                                                   # exactly max_terms positives
+    r = np.zeros(V, np.float32)
+    cols = np.sort(rng.choice(V, max_terms + 1, replace=False))
+    r[cols] = (2.0 + rng.uniform(0.1, 3.0, max_terms + 1)).astype(np.float32)
+    lo, hi = cols[[len(cols) // 3, -1]] if max_terms > 1 else cols[[0, 1]]
+    r[lo] = r[hi] = np.float32(1.25)                                                 # two equal values at the cut:
+    rows.append(r)                                                                   # the lower term id wins
+    rows.append(np.full(V, 0.75, np.float32))                                        # all V equal
+    r = np.zeros(V, np.float32)
+    r[-5:] = [0.5, 1e-38, 3.0, 0.5, np.float32(np.finfo(np.float32).max)]
+    rows.append(r)                                                                   # positives only in the last 5 columns
+    r = rng.uniform(-1.0, 1.0, V).astype(np.float32)                                 # negatives, -0.0 and ties by rounding
+    r[::7] = -0.0
+    r[1::5] = np.float32(0.3)
+    rows.append(r)
+    return np.stack(rows)
+
+
+@pytest.mark.parametrize("max_terms", [1, 64, 256])
+def test_sparsify_equals_the_definition_exactly(encoders, max_terms):
+    from rag_fin_amd.sparse_encoder import sparsify_reference
+    enc = encoders("l2")
+    rows = crafted_rows(max_terms)
+    for order in ([0, 1, 2, 3, 4, 5], [5, 3, 1, 4, 2, 0], [2, 2, 0, 4, 3, 1, 5, 2], [3]):
+        w = rows[order]
+        off, term, val = (t.cpu().numpy() for t in enc.sparsify(w, max_terms))
+        roff, rterm, rval = sparsify_reference(w, max_terms)
+        assert np.array_equal(off, roff), (order, off, roff)
+        n = int(roff[-1])
+        assert np.array_equal(term[:n], rterm), order
+        assert np.array_equal(val[:n].view(np.uint32), rval.view(np.uint32)), order
+
+
+@pytest.mark.parametrize("name,max_terms", [("ragged_5x96", 128), ("fused_64x128", 64), ("vocab_30522", 256),
+                                            ("empty_row_3x20", 1)])
+def test_sparsify_of_the_kernels_own_output_equals_the_definition(encoders, dense, name, max_terms):
+    from rag_fin_amd.sparse_encoder import sparsify_reference
+    w = dense(name)
+    off, term, val = (t.cpu().numpy() for t in encoders(case(name)[0]).sparsify(w, max_terms))
+    roff, rterm, rval = sparsify_reference(w, max_terms)
+    assert np.array_equal(off, roff)
+    assert np.array_equal(term[:roff[-1]], rterm) and np.array_equal(val[:roff[-1]].view(np.uint32), rval.view(np.uint32))
+    assert (np.diff(roff) == max_terms).any() or name == "empty_row_3x20"     # the cut is exercised
+
+
+# ---- the store's learned sparse field -------------------------------------------------------------------------------
+FIELD = "sparse_embedding"
+SPEC = {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "IP"}
+IP = {"metric_type": "IP"}
+PERIODS = ["Q1_FY2024", "Q2_FY2024", "Q3_FY2024", "Q4_FY2024"]
+N0, N_ADD = 300, 7
+
+
+@pytest.fixture(scope="module")
+def corpus(gpu_device):
+    from oracle import synth_text
+    from rag_fin_amd.sparse_encoder import SparseEncoder
+    from rag_fin_amd.tokenizer import WordPieceTokenizer
+    cfg, _, w, head, _, _ = model("l2")
+    tok = WordPieceTokenizer(synth_text.vocab_for(size=cfg["vocab_size"]))
+    enc = SparseEncoder(w, head, cfg, tokenizer=tok, device=gpu_device, max_seq_length=64, max_terms=48,
+                        query_max_terms=24)
+    texts = synth_text.retemplated_texts(N0 + N_ADD, 41)
+    rng = np.random.default_rng(7)
+    vec = rng.standard_normal((N0 + N_ADD, 384)).astype(np.float32)
+    return dict(enc=enc, texts=texts, vec=vec, queries=synth_text.retemplated_texts(5, 42),
+                periods=[PERIODS[i % 4] for i in range(N0 + N_ADD)], device=gpu_device)
+
+
+def make_store(c, rows):
+    from rag_fin_amd.store import CorpusStore
+    st = CorpusStore("t", dim=384, capacity=512, device=c["device"])
+    rows = list(rows)
+    st.add([f"c{i}" for i in rows], [c["texts"][i] for i in rows], c["vec"][rows], [c["periods"][i] for i in rows],
+           ["t"] * len(rows), ["s"] * len(rows), [float(i) for i in rows])
+    st.create_index(FIELD, SPEC, encoder=c["enc"])
+    return st
+
+
+def held_csr(st, V):
+    from scipy.sparse import csr_array
+    indptr, indices, data = st._learned_rows
+    return csr_array((data, indices, indptr), shape=(indptr.size - 1, V))
+
+
+def check_against_the_definition(st, c, limit, expr=None, mask=None):
+    from rag_fin_amd.sparse_encoder import sparse_ip_reference
+    enc = c["enc"]
+    hits = st.search(c["queries"], FIELD, IP, limit, expr=expr, output_fields=["period"])
+    q = enc.encode_query(c["queries"])
+    assert q.shape == (5, enc.vocab_size) and 0 < np.diff(q.indptr).max() <= 24
+    want_s, want_i = sparse_ip_reference(held_csr(st, enc.vocab_size), q, limit, mask=mask)
+    assert (want_i[:, 0] >= 0).all()                                  # every query hits something
+    for b in range(5):
+        n = int((want_i[b] >= 0).sum())
+        assert [h.row for h in hits[b]] == want_i[b, :n].tolist()
+        got = np.array([h.score for h in hits[b]], dtype=np.float32)
+        assert np.array_equal(got.view(np.uint32), want_s[b, :n].view(np.uint32))
+    return hits
+
+
+def test_store_search_equals_the_definition_with_and_without_a_filter(corpus):
+    st = make_store(corpus, range(N0))
+    hits = check_against_the_definition(st, corpus, 10)
+    csr = held_csr(st, corpus["enc"].vocab_size)
+    assert csr.shape[0] == N0 and 0 < np.diff(csr.indptr).max() <= 48 and (csr.data > 0).all()
+    mask = np.array([p == "Q2_FY2024" for p in corpus["periods"][:N0]])
+    filtered = check_against_the_definition(st, corpus, 10, expr='period == "Q2_FY2024"', mask=mask)
+    assert all(h.entity.period == "Q2_FY2024" for q in filtered for h in q) and any(len(q) for q in filtered)
+    assert [h.row for h in hits[0]] != [h.row for h in filtered[0]]
+    # a supplied vector: the first query's own, as {term: weight}
+    q0 = corpus["enc"].encode_query(corpus["queries"][:1])
+    by_dict = st.search([dict(zip(q0.indices.tolist(), q0.data.tolist()))], FIELD, IP, 10)
+    assert [(h.row, h.score) for h in by_dict[0]] == [(h.row, h.score) for h in hits[0]]
+    assert corpus["enc"].decode(q0[[0]], 3)[0][1] == float(q0.data.max())
+
+
+def test_store_after_add_and_delete_answers_as_a_fresh_store(corpus):
+    c = corpus
+    st = make_store(c, range(N0))
+    st.search(c["queries"], FIELD, IP, 10)
+    new = list(range(N0, N0 + N_ADD))
+    st.add([f"c{i}" for i in new], [c["texts"][i] for i in new], c["vec"][new], [c["periods"][i] for i in new],
+           ["t"] * N_ADD, ["s"] * N_ADD, [float(i) for i in new])
+    st.search(c["queries"], FIELD, IP, 10)                            # encodes the 7 new rows alone
+    assert st.delete('period == "Q3_FY2024"').delete_count > 0
+    survivors = [i for i in range(N0 + N_ADD) if c["periods"][i] != "Q3_FY2024"]
+    fresh = make_store(c, survivors)
+    got = check_against_the_definition(st, c, 10)
+    want = check_against_the_definition(fresh, c, 10)
+    assert [[(h.id, h.score) for h in q] for q in got] == [[(h.id, h.score) for h in q] for q in want]
+    a, b = st._learned_postings()[0], fresh._learned_postings()[0]
+    assert np.array_equal(a.post_off, b.post_off) and np.array_equal(a.post_row, b.post_row)
+    assert np.array_equal(a.post_imp.view(np.uint32), b.post_imp.view(np.uint32))
+
+
+def test_hybrid_of_a_dense_and_a_learned_arm_is_the_rrf_of_the_two_lists(corpus):
+    from rag_fin_amd import lexical
+    from rag_fin_amd.hybrid import AnnSearchRequest, RRFRanker
+    c = corpus
+    st = make_store(c, range(N0))
+    qv = c["vec"][[3, 50, 99, 200, 299]] + 0.5 * c["vec"][[4, 51, 100, 201, 0]]
+    dense = st.search(qv, "embedding", {"metric_type": "COSINE"}, 12)
+    learned = st.search(c["queries"], FIELD, IP, 9)
+    got = st.hybrid_search([AnnSearchRequest(qv, "embedding", {"metric_type": "COSINE"}, 12),
+                            AnnSearchRequest(c["queries"], FIELD, IP, 9)], RRFRanker(), 10)
+    pad = lambda hits: [h.row for h in hits] + [-1] * (12 - len(hits))   # noqa: E731
+    arms = np.array([[pad(q) for q in dense], [pad(q) for q in learned]])
+    _, want, fused = lexical.rrf_reference(arms, 10)
+    for b in range(5):
+        n = int((want[b] >= 0).sum())
+        assert [h.row for h in got[b]] == want[b, :n].tolist()
+        assert [h.score for h in got[b]] == fused[b, :n].tolist()
+
+
+def test_store_refuses_what_the_learned_field_has_no_form_for_on_the_device(corpus):
+    st = make_store(corpus, range(40))
+    q = corpus["queries"][:1]
+    V = corpus["enc"].vocab_size
+    for kw in (dict(param={"metric_type": "BM25"}), dict(limit=65), dict(param=dict(IP, params={"radius": 0.1})),
+               dict(offset=1), dict(group_by_field="period"), dict(mmr_lambda=0.5), dict(expr=['period == "Q1_FY2024"']),
+               dict(ranker={"filter": 'period == "Q1_FY2024"', "weight": 2.0}),
+               dict(data=[{i: 1.0 for i in range(65)}]), dict(data=[{V: 1.0}]), dict(data=[{0: -1.0}]),
+               dict(data=[{0: float("inf")}]), dict(data=np.ones((1, 384), np.float32))):
+        args = dict(data=q, anns_field=FIELD, param=IP, limit=3)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            st.search(**args)
+    with pytest.raises(ValueError):
+        st.create_index(FIELD, SPEC)                                  # no encoder
+    st.drop_index(field_name=FIELD)
+    with pytest.raises(ValueError):
+        st.search(q, FIELD, IP, 3)
