@@ -1005,6 +1005,84 @@ int rf_encode_terms(const rf_encoder_t* enc, const int32_t* ids_dev, const int32
 int rf_sparsify_terms(const float* weights_dev, int B, int V, int max_terms, int32_t* off_dev, int32_t* term_dev,
                       float* val_dev, void* stream);
 
+/* ---- late interaction (ColBERT): token vectors, MaxSim, the exact best rows (csrc/late_interaction.hip) ----
+ * The model is a BertModel of the same family with a bias-free projection to `dim` features (Stanford
+ * HF_ColBERT "linear.weight", PyLate "1_Dense"); a Milvus embedding list with metric MAX_SIM_IP.
+ *
+ * rf_encode_tokens: ids_dev int32 [B, T], lens_dev int32 [B] as for rf_encode; token types are 0.  The forward
+ * opens with the embedder's embedding launch, runs rf_encode's layers (all its paths by B and T; always plain
+ * launches, never rf_encode's cached hipGraphs) and closes with two launches:
+ *   1. the kept tokens per row and their exclusive scan over the rows, integers in a fixed order.  A token is
+ *      kept when t < lens[b] (lens clamped to 0..T) and bit `id` of head->skip is clear (skip NULL: none is
+ *      dropped; ids clamped into the vocabulary as the embedding clamps them).
+ *   2. for every kept token v = proj_w . x_t, an fp32 fma chain over k ascending from 0, then
+ *      v / max(|v|, 1e-12) with |v|^2 summed in fp32 in one fixed order, rounded to fp16 once, written at
+ *      out_off_dev[b] + (rank of the token among the row's kept tokens).
+ * Row b's vectors are out_vec_dev[out_off_dev[b] .. out_off_dev[b + 1]) (units of `dim` halfs), in token
+ * order; out_vec_dev has room for B * T vectors and nothing past out_off_dev[B] is written.  A row with
+ * lens < 1 has no tokens.  A row's vectors depend on the row and on (B, T) alone -- no atomics, no
+ * arrival-order reduction: the same row gives the same bits at any place of the batch and in every call.
+ * Stream-ordered, no host sync, no allocation; the workspace is rf_encode's
+ * (rf_encode_tokens_workspace_bytes; 0 for a shape that is out of range).
+ * Refusals, all before any launch.  RF_ERR_INVALID: a null or misaligned pointer (proj_w, out_vec_dev: 16
+ * bytes), B or T < 1.  RF_ERR_UNSUPPORTED: dim not a multiple of 16 in 16..RF_MAXSIM_DIM, head->vocab != the
+ * encoder's vocab_size, T > max_position.  RF_ERR_CAPACITY: workspace too small or misaligned.
+ *
+ * rf_maxsim: score(q, r) = sum over i < q_len of max over the tokens j of row r of (q_i . d_j).
+ * v_mfma_f32_32x32x16_f16 with the document's tokens on the A rows and the query's on the B columns: every dot
+ * product is one fp32 MFMA chain over the D/16 feature blocks in ascending order from 0 (an order that depends
+ * on D alone), the max is exact, and the sum is s = 0.0f; s = s + m_i for i = 0 .. q_len - 1, one fp32 add
+ * each.  A row without tokens, a query with q_len == 0, a row whose filter bit is clear and a candidate row
+ * outside [0, n_rows) score -inf ("not a hit"; such a row's tokens are not read).  Query slots i >= q_len are
+ * never read.  Document lanes past the end of a row enter the max as -inf.  A score depends on the (query, row)
+ * pair alone: the same bits in either mode, at any place of any call.  q_len_dev values are clamped to
+ * 0..RF_MAXSIM_QTOK.  filter_dev: NULL, or a filter buffer built for docs->n_rows rows (a header for another
+ * row count passes no row), as rf_sparse_search takes it.
+ *   candidate mode (cand_off_dev given): query b scores the rows cand_row_dev[cand_off_dev[b] ..
+ *     cand_off_dev[b + 1]); scores_dev is parallel to cand_row_dev.  A wave per (query, row) pair.
+ *   all-rows mode (cand_off_dev NULL): scores_dev is [B, n_rows].  A workgroup takes 64 consecutive rows and
+ *     walks over the B queries; a wave keeps up to 128 tokens of its row in registers meanwhile, so the field is
+ *     read from memory once per call, not once per query.
+ * Stream-ordered, no host sync, no allocation, no workspace, no atomics.  Before any launch -- RF_ERR_INVALID:
+ * a null or misaligned pointer (vectors, filter: 16 bytes; offsets, rows: 8), B < 1, n_rows < 0;
+ * RF_ERR_UNSUPPORTED: dim not a multiple of 16 in 16..RF_MAXSIM_DIM.  docs->off must ascend and end at the
+ * number of vectors: a malformed field gives wrong bits or reads outside docs->vec.
+ *
+ * rf_maxsim_topk: per query b the best k (1..RF_MAX_K) entries of scores_dev[seg_off_dev[b] .. seg_off_dev[b + 1])
+ * by (score descending, position in the segment ascending); -inf and NaN entries are never hits; floats order
+ * by their bit patterns (-0.0 below +0.0; rf_maxsim never gives -0.0).  The id of a hit is rows_dev[seg_off_dev[b]
+ * + position], or id_base + position when rows_dev is NULL -- (score descending, row ascending) there.  Outputs
+ * [B, k], padded with -inf / -1 as rf_sparse_search pads; exact_out (nullable) holds the scores as doubles.  One
+ * workgroup per query: a radix selection on the bit patterns and an ordered emit; integers only, LDS counters
+ * whose arrival order shows nowhere: the same bits on every run.  Segments of 0 to 2^40 entries.
+ * Stream-ordered, no allocation, no host sync, no workspace.  RF_ERR_INVALID before any launch: a null or
+ * misaligned pointer (but the two nullable ones), B < 1, k outside 1..RF_MAX_K.
+ * New in this build; the reference has no late-interaction stage. */
+#define RF_MAXSIM_QTOK 32   /* token slots of one query */
+#define RF_MAXSIM_DIM 128   /* largest token vector */
+typedef struct rf_token_head {      /* caller keeps alive for the call */
+  const void* proj_w;               /* [dim, H] device fp16, nn.Linear layout, no bias, 16-byte aligned */
+  int32_t dim;                      /* a multiple of 16, 16..RF_MAXSIM_DIM */
+  const uint32_t* skip;             /* NULL, or a device bitmap over the vocabulary (ceil(vocab / 32) words):
+                                       tokens whose id is set are dropped */
+  int32_t vocab;
+} rf_token_head;
+typedef struct rf_token_field {
+  const void* vec;                  /* device fp16 [n_tok, dim], 16-byte aligned */
+  const int64_t* off;               /* device [n_rows + 1], ascending, off[n_rows] = n_tok */
+  int64_t n_rows;
+  int32_t dim;
+} rf_token_field;
+size_t rf_encode_tokens_workspace_bytes(const rf_encoder_t* enc, int B, int T);
+int rf_encode_tokens(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
+                     const rf_token_head* head, int32_t* out_off_dev, void* out_vec_dev, void* workspace_dev,
+                     size_t workspace_bytes, void* stream);
+int rf_maxsim(const rf_token_field* docs, const void* q_vec_dev, const int32_t* q_len_dev, int B,
+              const int64_t* cand_off_dev, const int64_t* cand_row_dev, const void* filter_dev, float* scores_dev,
+              void* stream);
+int rf_maxsim_topk(const float* scores_dev, const int64_t* seg_off_dev, const int64_t* rows_dev, int B, int k,
+                   int64_t id_base, float* scores_out, int64_t* ids_out, double* exact_out, void* stream);
+
 /* ---- tokenizer: the text -> token-id stage in front of rf_encode ------------------------
  * Reference: the WordPiece tokenizer SentenceTransformer('all-MiniLM-L6-v2') loads by name
  * (vector_rag_mcp/main.py:41,50; "chunking_storing (1).py":8,380).  Host code, multi-threaded.

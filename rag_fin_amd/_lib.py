@@ -109,6 +109,21 @@ class MlmHead(Structure):
                 ("dec_w", c_void_p), ("dec_b", c_void_p), ("vocab", c_int32)]
 
 
+# late interaction (include/ragfin.h, rf_encode_tokens / rf_maxsim)
+RF_MAXSIM_QTOK = 32          # token slots of one query
+RF_MAXSIM_DIM = 128          # largest token vector
+
+
+class TokenHead(Structure):
+    """rf_token_head: the projection of a ColBERT model and the skip bitmap (device pointers)."""
+    _fields_ = [("proj_w", c_void_p), ("dim", c_int32), ("skip", c_void_p), ("vocab", c_int32)]
+
+
+class TokenField(Structure):
+    """rf_token_field: the token vectors of the rows of a collection as CSR (device pointers)."""
+    _fields_ = [("vec", c_void_p), ("off", c_void_p), ("n_rows", c_int64), ("dim", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/ragfin.h declares
 SIGNATURES = {
     "rf_version": (c_int, []),
@@ -250,6 +265,13 @@ SIGNATURES = {
     "rf_encode_terms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(MlmHead), c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
     "rf_sparsify_terms": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rf_encode_tokens_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "rf_encode_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(TokenHead), c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "rf_maxsim": (c_int, [POINTER(TokenField), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p]),
+    "rf_maxsim_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
 }
 
 # present only in the experiments build (libragfin_hip_exp.so, tools/): bound when exported

@@ -164,6 +164,7 @@ struct rf_pair_ends {
   float* norm;                // [B, 3]
   float* qa_logits;           // [B, T, 2] or nullptr
   const struct rf_terms_end* terms;   // a third pair of ends (splade.hip), or nullptr: see below
+  const struct rf_tokens_end* tokens; // a fourth pair of ends (late_interaction.hip), or nullptr: see below
 };
 void rf_launch_embed_pair(const int32_t* ids, const int32_t* lens, const int32_t* seg, int32_t* tok_off, int B, int T,
                           const rf_encoder_config& c, const rf_encoder_weights& w, _Float16* out, hipStream_t st);
@@ -182,6 +183,16 @@ struct rf_terms_end {
 };
 void rf_launch_terms_head(const _Float16* x, const int32_t* tok_off, int B, int T, const rf_terms_end& e, float eps,
                           hipStream_t st);
+// ---- late_interaction.hip: a token forward = the same layers between the embedder's embedding launch and a projection --
+// With `tokens` set in rf_pair_ends the forward opens with k_embed_ln (token types 0, as for `terms`) and closes
+// with k_token_offsets + k_token_project; the other fields are unused.
+struct rf_tokens_end {
+  const rf_token_head* head;  // device pointers of the projection and the skip bitmap
+  int32_t* out_off;           // [B + 1]
+  _Float16* out_vec;          // [<= B * T, dim]
+};
+void rf_launch_tokens_head(const _Float16* x, const int32_t* tok_off, const int32_t* ids, const int32_t* lens, int B,
+                           int T, const rf_tokens_end& e, hipStream_t st);
 const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc);   // encoder.hip
 // encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph);
 // `who` names the public entry in the error text

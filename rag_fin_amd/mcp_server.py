@@ -59,7 +59,7 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                    mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
                    hybrid: bool = False, offset: int | None = None, boost_filter: str = "",
-                   boost_weight: float | None = None, lexical: str | None = None):
+                   boost_weight: float | None = None, lexical: str | None = None, rerank_with: str | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -70,6 +70,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     the top_k are picked from (at most 64).
     rerank: optional second stage -- the best fetch_k chunks are re-scored as (query, text) pairs by the
     cross-encoder and the best top_k of them returned, each with a rerank_score.
+    rerank_with: optional choice of that second stage -- "cross" (the default) or "late" (MaxSim of the query's
+    token vectors against the chunks' stored ones, ColBERT late interaction; needs COLBERT_MODEL_DIR).
     hybrid: optional lexical arm -- the semantic search and a BM25 search of the chunk texts run at
     fetch_k each and are fused by reciprocal rank; `score` is then the fused score.  With filter and
     rerank; not with min_score / max_score, group_by or mmr_lambda.  Needs the store's lexical index
@@ -98,6 +100,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                 kw["hybrid"] = True
             if lexical is not None:
                 kw["lexical"] = lexical
+            if rerank_with is not None:
+                kw["rerank_with"] = rerank_with
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
                                         boost={"filter": boost_filter, "weight": boost_weight}, **kw)
             return {"status": "success", "query": query, "results": contexts, "result_count": len(contexts)}
@@ -109,6 +113,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
             mmr["hybrid"] = True
         if lexical is not None:
             mmr["lexical"] = lexical
+        if rerank_with is not None:
+            mmr["rerank_with"] = rerank_with
         if offset is not None:   # (a paged call bypasses the micro-batcher too: one batch shares one offset)
             mmr["offset"] = offset
         if group_by is not None:

@@ -30,7 +30,7 @@ class VectorRAG:
     def __init__(self, gemini_api_key: str | None = None, collection_name: str = "fin_chunks", *,
                  embedder=None, store=None, generator: Callable[[str], str] | None = None,
                  llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None, reader=None,
-                 sparse_encoder=None):
+                 sparse_encoder=None, late_encoder=None):
         """embedder: .encode(list[str]) -> [n, dim] (rag_fin_amd.embedder.Embedder);
         store: rag_fin_amd.store.CorpusStore.  `gemini_api_key` is accepted for
         signature compatibility and only handed to `generator` factories upstream.
@@ -41,7 +41,10 @@ class VectorRAG:
         generator is set.
         sparse_encoder: .encode_document / .encode_query(list[str]) -> sparse [n, V] (rag_fin_amd.sparse_encoder.
         SparseEncoder): declared on the store as its learned sparse field ("sparse_embedding"), the arm of
-        search(..., hybrid=True, lexical="learned" | "both")."""
+        search(..., hybrid=True, lexical="learned" | "both").
+        late_encoder: .encode(list[str], is_query=) -> one [n_tok, D] matrix per text (rag_fin_amd.late_interaction.
+        ColBERT): declared on the store as its late-interaction field ("token_embeddings"), the second stage of
+        search(..., rerank=True, rerank_with="late")."""
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
@@ -53,6 +56,10 @@ class VectorRAG:
         if sparse_encoder is not None:
             store.create_index("sparse_embedding", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "IP"},
                                encoder=sparse_encoder)
+        self.late_encoder = late_encoder
+        if late_encoder is not None:
+            store.create_index("token_embeddings", {"index_type": "EMB_LIST_FLAT", "metric_type": "MAX_SIM_IP"},
+                               encoder=late_encoder)
         self.collection_name = collection_name
         self.generator = generator
         self.prompt_template = prompt_template
@@ -93,7 +100,8 @@ class VectorRAG:
     def search(self, query: str, top_k: int = 3, expr: str | None = None, min_score: float | None = None,
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
-               hybrid: bool = False, offset: int | None = None, boost=None, lexical: str = "bm25") -> list[dict]:
+               hybrid: bool = False, offset: int | None = None, boost=None, lexical: str = "bm25",
+               rerank_with: str = "cross") -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -107,6 +115,10 @@ class VectorRAG:
         rerank: two-stage search -- the best fetch_k chunks (same default) are scored as (query, text)
         pairs by the cross-encoder and the best top_k of them are kept; `rank` is the rerank order,
         `score` stays the cosine and `rerank_score` (only here) is the cross-encoder's.
+        rerank_with (with rerank): "cross" (the default: the cross-encoder) or "late" -- the fetch_k chunks are
+        scored by MaxSim of the query's token vectors against the chunks' STORED token vectors (the
+        late-interaction field; no forward per candidate), the best top_k by (MaxSim descending, retrieval order)
+        are kept and `rerank_score` is the MaxSim.  Needs VectorRAG(..., late_encoder=), else ValueError.
         hybrid: the dense search and a BM25 search of the chunk texts (the store needs its lexical
         index: create_index("sparse", ...), service.build_rag(..., hybrid=True)) run at fetch_k each
         (same default), their lists are fused by reciprocal rank (RRF, k = 60) and the best top_k are
@@ -128,11 +140,12 @@ class VectorRAG:
         ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         self._check_lexical(lexical, hybrid)
+        self._check_rerank_with(rerank_with, rerank)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if rerank:
             return self._search_reranked([query], top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
-                                         hybrid, lexical)[0]
+                                         hybrid, lexical, rerank_with)[0]
         if hybrid:
             return self._contexts(self._search_hybrid([query], top_k, top_k, expr, fetch_k, lexical)[0])
         q = self._embed([query])
@@ -199,6 +212,16 @@ class VectorRAG:
                 raise ValueError(f"lexical={lexical!r} needs a sparse encoder (VectorRAG(..., sparse_encoder="
                                  "SparseEncoder.from_local(dir)))")
 
+    def _check_rerank_with(self, rerank_with, rerank) -> None:
+        if rerank_with not in ("cross", "late"):
+            raise ValueError(f"rerank_with must be 'cross' or 'late', got {rerank_with!r}")
+        if rerank_with == "late":
+            if not rerank:
+                raise ValueError("rerank_with='late' chooses the second stage of a reranked search: pass rerank=True")
+            if self.late_encoder is None:
+                raise ValueError("rerank_with='late' needs a late encoder (VectorRAG(..., late_encoder="
+                                 "ColBERT.from_local(dir)))")
+
     def _search_hybrid(self, queries, top_k, limit, expr, fetch_k, lexical: str = "bm25"):
         """The dense arm and the lexical arm(s) -- BM25, the learned sparse field, or both -- at fetch_k each,
         fused by RRF -> `limit` hits per query."""
@@ -216,8 +239,8 @@ class VectorRAG:
         return self.collection.hybrid_search(reqs, RRFRanker(), limit, output_fields=OUTPUT_FIELDS)
 
     def _search_reranked(self, queries, top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
-                         hybrid: bool = False, lexical: str = "bm25"):
-        if self.reranker is None:
+                         hybrid: bool = False, lexical: str = "bm25", rerank_with: str = "cross"):
+        if rerank_with == "cross" and self.reranker is None:
             raise ValueError("rerank=True needs a reranker (VectorRAG(..., reranker=CrossEncoder.from_local(dir)))")
         if mmr_lambda is not None:
             raise ValueError("rerank and mmr_lambda both re-order the best fetch_k chunks: give one of them")
@@ -233,9 +256,14 @@ class VectorRAG:
             results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
                                              expr=expr, output_fields=OUTPUT_FIELDS)
         hits = [list(r) for r in results]
-        # every query's candidates in ONE cross-encoder call
-        pairs = [(query, h.entity.text) for query, r in zip(queries, hits) for h in r]
-        scores = self.reranker.predict(pairs) if pairs else []
+        if rerank_with == "late":
+            # every query's candidates in ONE candidate-mode MaxSim call on the stored token vectors
+            per_query = self.collection.rerank_tokens(list(queries), [[h.row for h in r] for r in hits])
+            scores = [v for s in per_query for v in s]
+        else:
+            # every query's candidates in ONE cross-encoder call
+            pairs = [(query, h.entity.text) for query, r in zip(queries, hits) for h in r]
+            scores = self.reranker.predict(pairs) if pairs else []
         out, at = [], 0
         for r in hits:
             s = [float(v) for v in scores[at:at + len(r)]]
@@ -255,11 +283,12 @@ class VectorRAG:
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
                      rerank: bool = False, hybrid: bool = False, offset: int | None = None,
-                     boost=None, lexical: str = "bm25") -> list[list[dict]]:
+                     boost=None, lexical: str = "bm25", rerank_with: str = "cross") -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
-        the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call; hybrid:
+        the whole batch; rerank: every query's fetch_k candidates in one cross-encoder call (rerank_with="late": in
+        one MaxSim call on the stored token vectors); hybrid:
         dense + BM25 (lexical: or the learned sparse arm, or both) fused by reciprocal rank for every query, as
         in search(); offset: one for the whole batch, as in search().
         expr may also be a list or tuple with one entry per query (a filter string, or None for "no
@@ -277,13 +306,14 @@ class VectorRAG:
                 raise ValueError(f"expr list: {len(expr)} entries for {len(queries)} queries (one entry per query)")
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         self._check_lexical(lexical, hybrid)
+        self._check_rerank_with(rerank_with, rerank)
         if hybrid:
             self._check_hybrid(min_score, max_score, group_by, mmr_lambda)
         if not queries:
             return []
         if rerank:
             return self._search_reranked(list(queries), top_k, expr, min_score, max_score, group_by, mmr_lambda,
-                                         fetch_k, hybrid, lexical)
+                                         fetch_k, hybrid, lexical, rerank_with)
         if hybrid:
             return [self._contexts(r) for r in self._search_hybrid(list(queries), top_k, top_k, expr, fetch_k, lexical)]
         q = self._embed(list(queries))

@@ -13,6 +13,9 @@ Environment (dotenv-style names):
   SPARSE_MODEL_DIR     optional local SPLADE directory (a BertForMaskedLM of the MiniLM-H384 family, same three
                        files): declares the learned sparse field, enables search(..., hybrid=True,
                        lexical="learned" | "both")
+  COLBERT_MODEL_DIR    optional local ColBERT directory (a BertModel of the same family plus a projection, Stanford
+                       or PyLate layout): declares the late-interaction field, enables search(..., rerank=True,
+                       rerank_with="late")
   LEXICAL_INDEX        1: declare the lexical (BM25) index at ingest: enables search(..., hybrid=True)
   RAGFIN_DATA_DIR      folder with icici_q{1..4}_2023/*.json (default: extract_data)
   RAGFIN_DEVICE        torch device string (default cuda:0)
@@ -66,14 +69,23 @@ def _load_sparse_encoder(sparse_dir, device):
     return SparseEncoder.from_local(sparse_dir, device=device)
 
 
+def _load_late_encoder(late_dir, device):
+    if not late_dir:
+        return None
+    from .late_interaction import ColBERT
+    return ColBERT.from_local(late_dir, device=device)
+
+
 def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
               hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None,
-              sparse_dir: str | None = None):
+              sparse_dir: str | None = None, late_dir: str | None = None):
     """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
     can run; its posting lists are built by the first such search.
     sparse_dir: a local SPLADE checkpoint: the learned sparse field is declared on the store (VectorRAG does
-    it), its vectors are encoded by the first search(..., hybrid=True, lexical="learned" | "both")."""
+    it), its vectors are encoded by the first search(..., hybrid=True, lexical="learned" | "both").
+    late_dir: a local ColBERT checkpoint: the late-interaction field is declared on the store (VectorRAG does it),
+    its token vectors are encoded by the first search(..., rerank=True, rerank_with="late")."""
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
@@ -83,9 +95,11 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     if hybrid:
         store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     sparse = _load_sparse_encoder(sparse_dir, device)
+    late = _load_late_encoder(late_dir, device)
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
                      reranker=_load_reranker(reranker_dir, device), reader=_load_reader(reader_dir, device, reader_doc_stride),
-                     **({} if sparse is None else {"sparse_encoder": sparse}))
+                     **({} if sparse is None else {"sparse_encoder": sparse}),
+                     **({} if late is None else {"late_encoder": late}))
 
 
 def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
@@ -144,6 +158,7 @@ def build_rag_from_env():
     reader_dir = os.getenv("READER_MODEL_DIR") or None
     reader_doc_stride = int(os.environ["READER_DOC_STRIDE"]) if os.getenv("READER_DOC_STRIDE") else None
     sparse_dir = os.getenv("SPARSE_MODEL_DIR") or None
+    late_dir = os.getenv("COLBERT_MODEL_DIR") or None
     if int(os.getenv("WORLD_SIZE", "1")) > 1:
         return build_sharded_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                                  int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
@@ -151,4 +166,5 @@ def build_rag_from_env():
     return build_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                      os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
                      reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1", reader_dir=reader_dir,
-                     reader_doc_stride=reader_doc_stride, **({"sparse_dir": sparse_dir} if sparse_dir else {}))
+                     reader_doc_stride=reader_doc_stride, **({"sparse_dir": sparse_dir} if sparse_dir else {}),
+                     **({"late_dir": late_dir} if late_dir else {}))

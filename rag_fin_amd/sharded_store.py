@@ -30,7 +30,7 @@ import threading
 
 from . import _lib, filter_expr
 from .sharded import HipShardBackend, ShardedSearcher
-from .store import LEARNED_FIELD, CorpusStore, MutationResult, _id_in_keys, check_offset
+from .store import LEARNED_FIELD, TOKEN_FIELD, CorpusStore, MutationResult, _id_in_keys, check_offset
 
 
 logger = logging.getLogger(__name__)
@@ -119,6 +119,9 @@ class ShardedCorpusStore(CorpusStore):
         if field_name == LEARNED_FIELD:
             raise NotImplementedError("the learned sparse field (sparse_embedding) is not implemented for the sharded "
                                       "store (single-GPU CorpusStore only)")
+        if field_name == TOKEN_FIELD:
+            raise NotImplementedError("the late-interaction field (token_embeddings) is not implemented for the sharded "
+                                      "store (single-GPU CorpusStore only)")
         itype, metric = self._check_index_params(field_name, dict(index_params or {}))
         if itype == "SQ8":
             raise NotImplementedError("SQ8 is not supported by ShardedCorpusStore (single-GPU CorpusStore only)")
@@ -130,11 +133,15 @@ class ShardedCorpusStore(CorpusStore):
     def drop_index(self, **kwargs) -> None:
         if self._is_learned_field(kwargs):
             raise NotImplementedError("the learned sparse field (sparse_embedding) is not implemented for the sharded store")
+        if self._is_token_field(kwargs):
+            raise NotImplementedError("the late-interaction field (token_embeddings) is not implemented for the sharded store")
         super().drop_index(**kwargs)
 
     def has_index(self, **kwargs) -> bool:
         if self._is_learned_field(kwargs):
             raise NotImplementedError("the learned sparse field (sparse_embedding) is not implemented for the sharded store")
+        if self._is_token_field(kwargs):
+            raise NotImplementedError("the late-interaction field (token_embeddings) is not implemented for the sharded store")
         return super().has_index(**kwargs)
 
     # -- mutation (COLLECTIVE) ----------------------------------------------------------------------
@@ -302,6 +309,9 @@ class ShardedCorpusStore(CorpusStore):
             raise NotImplementedError("BM25 search (anns_field='sparse') is not implemented for the sharded store")
         if anns_field == LEARNED_FIELD:
             raise NotImplementedError("learned sparse search (anns_field='sparse_embedding') is not implemented for "
+                                      "the sharded store")
+        if anns_field == TOKEN_FIELD:
+            raise NotImplementedError("late-interaction search (anns_field='token_embeddings') is not implemented for "
                                       "the sharded store")
         if mmr_lambda is not None or mmr_fetch_k is not None:
             # (the candidate vectors live on different ranks)

@@ -265,6 +265,7 @@ class _RWLock:
 
 
 LEARNED_FIELD = "sparse_embedding"   # the learned sparse field (create_index(..., encoder=))
+TOKEN_FIELD = "token_embeddings"     # the late-interaction field (create_index(..., encoder=))
 
 
 class MutationResult:
@@ -438,6 +439,11 @@ class CorpusStore:
         self._learned = None
         self._learned_rows = None
         self._learned_index = None
+        # the late-interaction field (create_index("token_embeddings", ..., encoder=)): the attached encoder and
+        # the token vectors of the rows encoded so far (late_interaction.TokenField: device CSR over a prefix of
+        # the rows, grown by doubling; the rest is encoded by the next search).  Guarded like the learned field.
+        self._tokens = None
+        self._token_field = None
         # index maintenance: the last built (postings, SparseIndex, analyzer, params) and, in
         # order, the mutations since -- ("delete", keep mask) / ("append", texts) -- which the next
         # _sparse_index() replays through SparseIndex.compacted / .appended instead of building whole.
@@ -474,6 +480,7 @@ class CorpusStore:
             self._forget_lexical()
             self._learned_rows = None
             self._learned_index = None
+            self._token_field = None
 
     def _forget_lexical(self) -> None:
         """Drop the retained lexical state: the next _sparse_index() builds whole."""
@@ -539,8 +546,20 @@ class CorpusStore:
         only the new rows are encoded, a delete drops its rows, and the per-row vectors (host CSR) are
         transposed again on the host -- a stable sort by term, rows ascending within a term -- into the
         posting arrays a SparseIndex serves.  They are not saved: a loaded store encodes
-        again, as the lexical index is rebuilt."""
+        again, as the lexical index is rebuilt.
+        field_name "token_embeddings" with {"index_type": "EMB_LIST_FLAT", "metric_type": "MAX_SIM_IP"} and
+        encoder=<a ColBERT> declares the late-interaction field (Milvus: an embedding list filled by a
+        function): one unit vector per kept token of each row's `text` (encoder.encode(texts, is_query=False)),
+        encoded lazily at the first search of the field; after an add / insert / upsert only the new rows are
+        encoded and appended to the device CSR, a delete drops its rows from it, so the field always equals
+        that of a fresh store.  It is not saved: a loaded store encodes again."""
         params = dict(index_params or {})
+        if field_name == TOKEN_FIELD:
+            self._check_token_params(params, kwargs.get("encoder"))
+            with self._rw.write():
+                self._tokens = {"encoder": kwargs["encoder"]}
+                self._token_field = None
+            return
         if field_name == LEARNED_FIELD:
             self._check_learned_params(params, kwargs.get("encoder"))
             with self._rw.write():
@@ -613,6 +632,25 @@ class CorpusStore:
         return LEARNED_FIELD in (kwargs.get("field_name"), kwargs.get("index_name"))
 
     @staticmethod
+    def _check_token_params(params, encoder) -> None:
+        itype = str(params.get("index_type", "EMB_LIST_FLAT")).upper()
+        if itype != "EMB_LIST_FLAT":
+            raise ValueError(f"create_index: the token_embeddings field takes index_type EMB_LIST_FLAT, got {itype!r}")
+        metric = str(params.get("metric_type", "MAX_SIM_IP")).upper()
+        if metric != "MAX_SIM_IP":
+            raise ValueError(f"create_index: the token_embeddings field takes metric_type MAX_SIM_IP, got {metric!r}")
+        p = params.get("params")
+        if p is not None and not isinstance(p, dict):
+            raise ValueError("create_index: params must be a dict")
+        if encoder is None or not all(hasattr(encoder, a) for a in ("encode", "dim")):
+            raise ValueError("create_index: the token_embeddings field is derived from the text column and needs "
+                             "encoder=<a ColBERT> (encode(texts, is_query=), dim)")
+
+    @staticmethod
+    def _is_token_field(kwargs) -> bool:
+        return TOKEN_FIELD in (kwargs.get("field_name"), kwargs.get("index_name"))
+
+    @staticmethod
     def _is_sparse_field(kwargs) -> bool:
         return "sparse" in (kwargs.get("field_name"), kwargs.get("index_name"))
 
@@ -624,6 +662,11 @@ class CorpusStore:
                 self._learned = None
                 self._learned_rows = None
                 self._learned_index = None
+            return
+        if self._is_token_field(kwargs):
+            with self._rw.write():
+                self._tokens = None
+                self._token_field = None
             return
         if self._is_sparse_field(kwargs):
             with self._rw.write():
@@ -641,6 +684,8 @@ class CorpusStore:
         """field_name="sparse" (or index_name="sparse") asks about the lexical index."""
         if self._is_learned_field(kwargs):
             return self._learned is not None
+        if self._is_token_field(kwargs):
+            return self._tokens is not None
         if self._is_sparse_field(kwargs):
             return self._sparse_params is not None
         return self._index_params is not None
@@ -784,6 +829,8 @@ class CorpusStore:
         self._sparse = None   # the lexical index is brought up to date by the next BM25 search
         self._log_lexical("delete", keep_mask)
         self._learned_drop_rows(keep_mask)
+        if self._token_field is not None:
+            self._token_field.keep(keep_mask)
         self._mutations += 1
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
@@ -925,6 +972,13 @@ class CorpusStore:
             return self._search_expr_list(data, anns_field, param, limit, expr, output_fields, group_by_field,
                                           mmr_lambda, mmr_fetch_k, offset)
         offset = check_offset(offset, param, limit)
+        if anns_field == TOKEN_FIELD:
+            if offset or group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
+                raise ValueError("late-interaction search (anns_field='token_embeddings') has no offset, grouping or MMR form")
+            q = self._check_token_search(data, param, limit)
+            fields = self._check_output_fields(output_fields)
+            with self._rw.read():
+                return self._search_tokens(q, limit, expr, fields)
         if anns_field == LEARNED_FIELD:
             if offset or group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
                 raise ValueError("learned sparse search (anns_field='sparse_embedding') has no offset, grouping or MMR form")
@@ -966,6 +1020,8 @@ class CorpusStore:
             raise ValueError("per-query filters (a list expr) have no BM25 form (anns_field='sparse')")
         if anns_field == LEARNED_FIELD:
             raise ValueError("per-query filters (a list expr) have no learned sparse form (anns_field='sparse_embedding')")
+        if anns_field == TOKEN_FIELD:
+            raise ValueError("per-query filters (a list expr) have no late-interaction form (anns_field='token_embeddings')")
         if self._is_text(data):
             raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
         if group_by_field is not None:
@@ -1047,6 +1103,8 @@ class CorpusStore:
             raise ValueError("boosted search (ranker) has no BM25 form (anns_field='sparse')")
         if anns_field == LEARNED_FIELD:
             raise ValueError("boosted search (ranker) has no learned sparse form (anns_field='sparse_embedding')")
+        if anns_field == TOKEN_FIELD:
+            raise ValueError("boosted search (ranker) has no late-interaction form (anns_field='token_embeddings')")
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         if self._is_text(data):
@@ -1394,6 +1452,100 @@ class CorpusStore:
         scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
         return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
 
+    # -- the late-interaction field: search(anns_field="token_embeddings") ---------------------
+    def _check_token_search(self, data, param, limit):
+        """Everything a late-interaction search refuses -> the queries: a list of strings (encoded with the
+        attached encoder, is_query=True) or the supplied list of [n_tok <= 32, D] arrays, checked."""
+        from . import late_interaction
+        if self._tokens is None:
+            raise ValueError("no token_embeddings index: call create_index('token_embeddings', {'index_type': "
+                             "'EMB_LIST_FLAT', 'metric_type': 'MAX_SIM_IP'}, encoder=...) first")
+        metric = str((param or {}).get("metric_type", "MAX_SIM_IP")).upper()
+        if metric != "MAX_SIM_IP":
+            raise ValueError(f"the token_embeddings field is searched with metric_type MAX_SIM_IP, search asked for {metric}")
+        params = (param or {}).get("params")
+        if params is not None and not isinstance(params, dict):
+            raise ValueError("search: param['params'] must be a dict")
+        if params and (params.get("radius") is not None or params.get("range_filter") is not None):
+            raise ValueError("late-interaction search (anns_field='token_embeddings') has no range form (radius / range_filter)")
+        if isinstance(param, dict) and param.get("offset"):
+            raise ValueError("late-interaction search (anns_field='token_embeddings') takes no offset")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
+            raise ValueError("late-interaction search (anns_field='token_embeddings'): limit must be an integer >= 1")
+        if limit > _lib.RF_MAX_K:
+            raise ValueError(f"late-interaction search (anns_field='token_embeddings'): limit = {limit} > {_lib.RF_MAX_K}")
+        if self._is_text(data):
+            return [data] if isinstance(data, str) else list(data)
+        if isinstance(data, (list, tuple)) and all(isinstance(q, np.ndarray) and q.ndim == 2 for q in data):
+            try:
+                late_interaction.pack_queries(list(data), int(self._tokens["encoder"].dim))
+            except ValueError as e:
+                raise ValueError(f"the token_embeddings field: {e}") from None
+            return [np.asarray(q) for q in data]
+        raise ValueError("the token_embeddings field is searched with query strings or a list of [n_tok, D] arrays")
+
+    def _token_index(self):
+        """The TokenField over the current text column: the rows not encoded yet go through the attached
+        encoder and are appended."""
+        from . import late_interaction
+        with self._sparse_lock:
+            enc = self._tokens["encoder"]
+            if self._token_field is None:
+                self._token_field = late_interaction.TokenField(int(enc.dim), self.index.device)
+            f, n = self._token_field, self.num_entities
+            if f.n_rows < n:
+                new = enc.encode(self.columns["text"][f.n_rows:n], is_query=False)
+                if len(new) != n - f.n_rows:
+                    raise ValueError(f"the token encoder returned {len(new)} rows, expected {n - f.n_rows}")
+                f.append(new)
+            return f
+
+    def _token_queries(self, q):
+        if q and isinstance(q[0], str):
+            return self._tokens["encoder"].encode(q, is_query=True)
+        return q
+
+    def _token_arm(self, q, limit: int, expr):
+        """The late-interaction arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors:
+        all-rows MaxSim of the passing rows, then the exact top-k."""
+        f = self._token_index()
+        filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
+        return f.search(self._token_queries(q), limit, filt)
+
+    def _search_tokens(self, q, limit, expr, fields):
+        if not self.num_entities or not q:
+            return [[] for _ in q]
+        res = self._token_arm(q, limit, expr)
+        scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
+        return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
+
+    def token_vectors(self, rows) -> list:
+        """The stored float16 token vectors of the given rows of the token_embeddings field, one [n_tok, D]
+        array each (rows not encoded yet are encoded first)."""
+        if self._tokens is None:
+            raise ValueError("no token_embeddings index: call create_index('token_embeddings', ...) first")
+        with self._rw.read():
+            return self._token_index().vectors(rows)
+
+    def rerank_tokens(self, queries, candidates):
+        """Candidate-mode MaxSim on the stored token vectors: queries (strings or [n_tok, D] arrays), candidates
+        one list of row numbers per query -> one float32 array of scores per query, parallel to its rows (-inf:
+        a row without tokens or outside the collection).  One rf_maxsim call for the whole batch."""
+        from . import late_interaction
+        if self._tokens is None:
+            raise ValueError("no token_embeddings index: call create_index('token_embeddings', ...) first")
+        queries = [queries] if isinstance(queries, str) else list(queries)
+        if len(queries) != len(candidates):
+            raise ValueError(f"{len(candidates)} candidate lists for {len(queries)} queries")
+        if not queries:
+            return []
+        with self._rw.read():
+            f = self._token_index()
+            scores = late_interaction.maxsim(f, self._token_queries(queries), [list(c) for c in candidates])
+            scores = np.asarray(scores.cpu().numpy() if hasattr(scores, "cpu") else scores, dtype=np.float32)
+        cut = np.cumsum([len(c) for c in candidates])[:-1]
+        return np.split(scores, cut)
+
     def _hits(self, rows, scores, fields) -> list:
         """The Hit list of one query from its row numbers (best first, -1 ends it) and scores."""
         hits = []
@@ -1415,7 +1567,8 @@ class CorpusStore:
 
     def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields: Iterable[str] | None = None, ranker=None):
         """pymilvus-shaped hybrid search: every AnnSearchRequest of `reqs` (1..4; anns_field "embedding"
-        with query vectors, "sparse" with query strings, or "sparse_embedding" with query strings or sparse vectors) runs on the GPU with its own limit (<= 64)
+        with query vectors, "sparse" with query strings, "sparse_embedding" with query strings or sparse vectors, or
+        "token_embeddings" with query strings or lists of token vectors) runs on the GPU with its own limit (<= 64)
         and its own expr, and `rerank` -- an RRFRanker -- fuses the arms' ranked lists per query:
         fused(d) = sum over the arms holding d of weight / (k + rank), the best `limit` (<= 64) rows by
         (fused desc, row asc).  One list of hits per query; hit.score is the fused score.  The fusion
@@ -1450,6 +1603,9 @@ class CorpusStore:
                 elif r.anns_field == LEARNED_FIELD:
                     q = self._check_learned_search(r.data, r.param, r.limit)
                     prepared.append((r, q, self._learned_query_count(q)))
+                elif r.anns_field == TOKEN_FIELD:
+                    q = self._check_token_search(r.data, r.param, r.limit)
+                    prepared.append((r, q, len(q)))
                 elif r.anns_field == "embedding":
                     if self._is_text(r.data):
                         raise ValueError("the embedding field is searched with vectors, not with strings")
@@ -1480,6 +1636,8 @@ class CorpusStore:
                 elif r.anns_field == LEARNED_FIELD:
                     res = self._learned_arm(q, r.limit, r.expr)
                     rows = None if res is None else res[1]
+                elif r.anns_field == TOKEN_FIELD:
+                    rows = self._token_arm(q, r.limit, r.expr)[1]
                 else:
                     rows = self._dense_arm(q, r.limit, r.expr)
                 block = torch.full((B, F), -1, dtype=torch.int64, device=device)
@@ -1546,6 +1704,8 @@ class CorpusStore:
             raise ValueError("boosted search (ranker) cannot be combined with search_iterator")
         if isinstance(expr, (list, tuple)):
             raise ValueError("search_iterator takes one expr string, not a list (per-query filters)")
+        if anns_field == TOKEN_FIELD:
+            raise ValueError("search_iterator has no late-interaction form (anns_field='token_embeddings')")
         return SearchIterator(self, data, anns_field, param, batch_size, limit, expr, output_fields)
 
     @staticmethod
