@@ -693,7 +693,7 @@ int rf_merge_shards_packed(const int64_t* packed_dev, int W, int B, int k,
  * LOCAL row numbers it wrote into global ids through the shard's table, in place, on `stream`:
  * ids_dev[i] = id_map_dev[ids_dev[i]] for ids >= 0 (-1 = "no hit" stays; a row number past n_map
  * becomes -1).  Between the scan and the all-gather: the N > 1 step is then four enqueues
- * (rf_search, rf_map_ids, ncclAllGather, rf_merge_shards_packed) and no host library touches
+ * (rf_search_fp16, rf_map_ids, ncclAllGather, rf_merge_shards_packed) and no host library touches
  * the ids.  New in this build; stands beside vector_rag_mcp/main.py:51-57. */
 int rf_map_ids(int64_t* ids_dev, int64_t n, const int64_t* id_map_dev, int64_t n_map, void* stream);
 /* ---- the sharded step as ONE call (rf_comm_init / rf_search_sharded; 8e) ----------
@@ -702,7 +702,9 @@ int rf_map_ids(int64_t* ids_dev, int64_t n, const int64_t* id_map_dev, int64_t n
  *   rf_comm_unique_id   rank 0 draws the job's 128-byte id (RF_COMM_ID_BYTES, host memory); the HOST
  *                       ships it to the other ranks (MPI, a socket, torch.distributed, a file)
  *   rf_comm_init        every rank: ncclCommInitRank on `device` -- blocks until all `world` ranks arrive
- *   rf_search_sharded   every rank, same B and k, calls in the same order on all ranks: rf_search into
+ *   rf_search_sharded   every rank, same B and k, calls in the same order on all ranks: rf_search_fp16 (the
+ *                       fp16 chain even on an index with rf_index_set_shadow_first: the step's flag
+ *                       resolution has no fp16 tier to put behind a shadow pass) into
  *                       the packed send buffer, rf_map_ids when id_map_dev is given (id_base is then
  *                       ignored), ncclAllGather of rf_packed_shard_words(B, k) words, rf_merge_shards_packed.
  *                       Four enqueues on `stream`, no host synchronisation; scores_dev / ids_dev hold the
@@ -749,12 +751,13 @@ int rf_debug_scores(const rf_index_t* ix, const void* q_dev, int B, int64_t n,
  *   rf_index_detach_sq8    forget the shadow (the caller frees it after the stream has drained)
  *   rf_search_sq8          rf_search's arguments and outputs; 64-query sweeps for any B.  A corpus of
  *                          <= 8192 rows (every row a candidate) runs the FLAT path.  A flagged query
- *                          is re-run through rf_search and, only if that flags too, rf_search_exhaustive.
+ *                          is re-run through rf_search_fp16 and, only if that flags too, rf_search_exhaustive.
  *                          A query whose bound is too loose for the int8 sweep (most sample partitions
  *                          clear its threshold) is given up before the sweep and flagged.
  *                          workspace_bytes >= rf_search_sq8_workspace_bytes (> rf_search_workspace_bytes)
  *   rf_search_sq8_profile  the first sweep with HIP events: stage_ms_host (host) receives {query
- *                          quantization, sample, threshold, int8 emit, merge} in ms; SYNCHRONISES
+ *                          quantization, sample, threshold, int8 emit, prune + refine, merge} in ms
+ *                          (six floats); SYNCHRONISES
  *   rf_debug_scores_sq8    test hook: a~ fp32 [B, n] of the first n rows, delta_dev (nullable) fp32 [B]
  *                          the bound delta_q >= |a - a~| of every row
  *   rf_index_get_rows_sq8  test hook: the un-tiled int8 rows [n, dim], s_r fp32 [n], e_r fp32 [n] */
@@ -772,6 +775,28 @@ int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int B, int64_t 
                         float* delta_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 int rf_index_get_rows_sq8(const rf_index_t* ix, const int64_t* rows_dev, int64_t n, void* out_dev,
                           float* scales_dev, float* err_dev, void* stream);
+
+/* ---- shadow first: rf_search over a large index reads the int8 shadow ------------------------------
+ * An SQ8 sweep is: quantize the queries -> fp16 sample -> threshold -> int8 emit -> prune + refine ->
+ * merge.  The refine stage drops every candidate whose upper bound a~ + beta_r lies under the k-th
+ * largest lower bound a~ - beta_r and gives the survivors their fp16 score, so the merge works on what a
+ * FLAT emit would have handed it: about half the bytes of the fp16 sweep per batch.
+ *   rf_index_set_shadow_first  min_rows > 0: rf_search and rf_search_profile run that chain when a shadow
+ *                          is attached, the index holds >= min_rows rows (and > 8192) and the batch is one
+ *                          plain sweep (B <= 64); wider batches and every other search form stay on fp16.
+ *                          min_rows <= 0 turns it off (the default); attaching a shadow alone changes
+ *                          nothing.  While it is set and a shadow is attached, rf_search_workspace_bytes
+ *                          is the SQ8 size: read it after the switch.  Host state of the index: like
+ *                          rf_index_add_f16, never concurrent with a search.
+ *                          rf_search_profile keeps its four stages: `sample` includes the query
+ *                          quantization, `emit` the refine stage.
+ *   rf_search_fp16         rf_search's arguments and outputs through the fp16 chain whatever is attached:
+ *                          the tier a query flagged by a shadow-first rf_search or by rf_search_sq8 is
+ *                          re-run through (rf_search again would sweep the shadow a second time). */
+int rf_index_set_shadow_first(rf_index_t* ix, int64_t min_rows);
+int rf_search_fp16(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                   float* scores_dev, int64_t* ids_dev, double* exact_dev, uint32_t* flags_dev,
+                   void* workspace_dev, size_t workspace_bytes, void* stream);
 
 #ifdef RF_EXPERIMENTS
 /* ---- experiments build only (python -m rag_fin_amd.build --experiments ->

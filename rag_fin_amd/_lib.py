@@ -15,6 +15,7 @@ from . import build as _build
 RF_OK = 0
 RF_MAX_K = 64
 RF_QCHUNK = 64
+RF_SMALL_ROWS = 8192      # rows up to which every row is a candidate (no sample pass, no shadow chain)
 RF_FLAG_CAND_OVERFLOW = 1
 RF_FLAG_TIE_OVERFLOW = 2
 RF_GROUP_MAX_CODES = 64   # dictionary size the fused grouped path serves (include/ragfin.h)
@@ -242,6 +243,9 @@ SIGNATURES = {
     "rf_search_sq8_workspace_bytes": (c_size_t, [c_void_p]),
     "rf_search_sq8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_index_set_shadow_first": (c_int, [c_void_p, c_int64]),
+    "rf_search_fp16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_sq8_profile": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "rf_debug_scores_sq8": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p,

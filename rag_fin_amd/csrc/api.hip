@@ -92,6 +92,7 @@ extern "C" int rf_set_tuning(const char* key, int value) {
   for (const auto& k : keys)
     if (!strcmp(key, k.name) && value >= k.lo && value <= k.hi) {
       if (k.var == &rf_knob_ring24 && value != 6 && value != 8 && value != 12 && value != 24) break;
+      if (k.var == &rf_knob_sq8_ring12 && value != 4 && value != 6 && value != 12) break;
       *k.var = value;
       return RF_OK;
     }
@@ -100,10 +101,15 @@ extern "C" int rf_set_tuning(const char* key, int value) {
 }
 #endif
 
+// rf_search sweeps the shadow first (rf_index_set_shadow_first) when one is attached and the index has
+// the rows for it; the sweep itself also needs a plain batch of at most 64 queries (shadow_sweep).
+static bool shadow_first(const rf_index_t* ix) { return ix && ix->shadow_min_rows > 0 && ix->sq8_tiles; }
+
+// (with shadow-first set the rf_search workspace holds the SQ8 query area too)
 extern "C" size_t rf_search_workspace_bytes(const rf_index_t* ix) {
-  (void)ix;
   rf_arena a{nullptr, 0};
-  carve(a);
+  if (shadow_first(ix)) carve_sq8(a, nullptr);
+  else carve(a);
   return a.off;
 }
 
@@ -133,9 +139,10 @@ static int check_search_args(const char* fn, const rf_index_t* ix, const void* q
     rf_set_error("%s: q / workspace must be 16-byte aligned", fn);
     return RF_ERR_INVALID;
   }
-  if (ws_bytes < rf_search_workspace_bytes(ix)) {
+  // (the FLAT size, which every form needs; the index itself is not read here)
+  if (ws_bytes < rf_search_workspace_bytes(nullptr)) {
     rf_set_error("%s: workspace %zu B < required %zu B", fn, ws_bytes,
-                 rf_search_workspace_bytes(ix));
+                 rf_search_workspace_bytes(nullptr));
     return RF_ERR_CAPACITY;
   }
   return RF_OK;
@@ -247,6 +254,7 @@ struct rf_variant {
   const rf_band* band;
   const rf_after* after;
   const rf_multi* multi;
+  bool coarse;   // SQ8 timed as the four FLAT stages: quantize + sample | threshold | emit + refine | merge
 };
 
 static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
@@ -258,7 +266,7 @@ static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
 // after each; the marks - 1 stage times in ms go to stage_ms.
 template <class F>
 static int time_stages(int marks, float* stage_ms, F run) {
-  hipEvent_t ev[6];
+  hipEvent_t ev[7];
   for (int i = 0; i < marks; ++i) RF_HIP(hipEventCreate(&ev[i]));
   const int rc = run(ev);
   if (rc == RF_OK) {
@@ -270,7 +278,8 @@ static int time_stages(int marks, float* stage_ms, F run) {
 }
 
 // One sweep of nb <= RF_QWIDE queries: (SQ8: quantize the queries ->) sample -> threshold -> emit ->
-// merge.  ev: nullable; one event before the first stage and one after each (5, with SQ8 6).
+// (SQ8: prune + refine ->) merge.  ev: nullable; one event before the first stage and one after each
+// (5; SQ8 unless v.coarse: 7).
 static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, int nb, int k, int64_t id_base,
                  const rf_workspace& ws, const rf_out& o, hipStream_t st, hipEvent_t* ev) {
   const int JB = nb <= 32 ? 1 : 2;
@@ -282,7 +291,7 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   int rc = mark(ev, &n_ev, st);
   if (v.sq8) {
     if (rc == RF_OK) rc = rf_launch_sq8_queries(ix, qc, nb, *v.sq8, st);
-    if (rc == RF_OK) rc = mark(ev, &n_ev, st);
+    if (rc == RF_OK && !v.coarse) rc = mark(ev, &n_ev, st);
   }
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS && v.band) rc = rf_launch_band_eps(ix, qc, nb, ws, st);
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
@@ -295,6 +304,10 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
     rc = v.wide  ? rf_launch_wide_emit(ix, qc, nb, ws, st)
          : v.sq8 ? rf_launch_sq8_emit(ix, nb, JB, ws, *v.sq8, st)
                  : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band, v.after, v.multi);
+  if (v.sq8) {
+    if (rc == RF_OK && !v.coarse) rc = mark(ev, &n_ev, st);
+    if (rc == RF_OK) rc = rf_launch_shadow_refine(ix, qc, nb, k, ws, *v.sq8, st);
+  }
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band, v.after);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
@@ -302,18 +315,20 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
 }
 
 // Every search entry point below: the whole batch (stage_ms == nullptr), or its first sweep alone
-// with HIP events around the stages, whose times in ms go to stage_ms (4 floats, with SQ8 5).
+// with HIP events around the stages, whose times in ms go to stage_ms (4 floats, RF_SQ8 6).
 // sq8 on a small corpus runs the FLAT chain: every row is a candidate there anyway (no sample pass
 // to gain from).
+enum { RF_FP16 = 0, RF_SQ8 = 1, RF_SHADOW = 2 };   // RF_SHADOW: the SQ8 chain, timed as the four FLAT stages
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, const rf_out& o,
-                          void* workspace_dev, hipStream_t st, const rf_filter_view* filt, bool sq8,
+                          void* workspace_dev, hipStream_t st, const rf_filter_view* filt, int sq8,
                           float* stage_ms = nullptr, const rf_band* band = nullptr,
                           const rf_after* after = nullptr, const rf_multi* multi = nullptr) {
   if (ix->size == 0) return fill_empty(B, k, o, st);
   rf_arena a{(unsigned char*)workspace_dev, 0};
   rf_workspace ws;
   const rf_sq8_ws sw = carve_sq8(a, &ws);   // (the SQ8 area is only touched by an SQ8 sweep)
-  const rf_sq8_ws* sq = sq8 && ix->size > RF_SMALL_ROWS ? &sw : nullptr;
+  const rf_sq8_ws* sq = sq8 != RF_FP16 && ix->size > RF_SMALL_ROWS ? &sw : nullptr;
+  const bool coarse = sq8 == RF_SHADOW;
   const bool widen = !filt && !sq && !band;
   if (!stage_ms)
     return for_chunks(ix, q_dev, B, k, (size_t)k, widen, o,
@@ -321,15 +336,32 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
                         const rf_after ac{after ? after->score + q0 : nullptr, after ? after->id + q0 : nullptr};
                         const rf_multi mc{multi ? multi->masks_t : nullptr, multi ? multi->qfilter + q0 : nullptr,
                                           multi ? multi->gp : 0u};
-                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr, multi ? &mc : nullptr},
+                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr, multi ? &mc : nullptr, coarse},
                                      qc, nb, k, id_base, ws, oc, st, nullptr);
                       });
   bool wide;
   const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
-  return time_stages(sq ? 6 : 5, stage_ms, [&](hipEvent_t* ev) {
-    return sweep(ix, rf_variant{filt, sq, wide, band, after, multi}, (const _Float16*)q_dev, nb, k, id_base, ws, o, st,
-                 ev);
+  return time_stages(sq && !coarse ? 7 : 5, stage_ms, [&](hipEvent_t* ev) {
+    return sweep(ix, rf_variant{filt, sq, wide, band, after, multi, coarse}, (const _Float16*)q_dev, nb, k, id_base, ws,
+                 o, st, ev);
   });
+}
+
+// The chain of a plain search of B queries: the shadow first (rf_index_set_shadow_first) when the index
+// carries one, has the rows for it and the batch is one 64-query sweep; otherwise fp16 (wide sweeps
+// and the 64-query chunks of a larger batch included).
+static int plain_chain(const rf_index_t* ix, int B) {
+  return shadow_first(ix) && ix->size >= ix->shadow_min_rows && ix->size > RF_SMALL_ROWS && B <= RF_QCHUNK ? RF_SHADOW
+                                                                                                          : RF_FP16;
+}
+
+extern "C" int rf_index_set_shadow_first(rf_index_t* ix, int64_t min_rows) {
+  if (!ix) {
+    rf_set_error("rf_index_set_shadow_first: null index");
+    return RF_ERR_INVALID;
+  }
+  ix->shadow_min_rows = min_rows > 0 ? min_rows : 0;
+  return RF_OK;
 }
 
 extern "C" int rf_search(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
@@ -338,9 +370,22 @@ extern "C" int rf_search(const rf_index_t* ix, const void* q_dev, int B, int k, 
                          void* stream) {
   int rc = check_search_args("rf_search", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
                              workspace_bytes);
+  if (rc == RF_OK && plain_chain(ix, B) == RF_SHADOW) rc = check_sq8("rf_search", ix, workspace_bytes);
   if (rc != RF_OK) return rc;
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, nullptr, false);
+                        (hipStream_t)stream, nullptr, plain_chain(ix, B));
+}
+
+// The fp16 chain whatever is attached: the FLAT tier of the flagged-query ladder.
+extern "C" int rf_search_fp16(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
+                              float* scores_dev, int64_t* ids_dev, double* exact_dev,
+                              uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes,
+                              void* stream) {
+  int rc = check_search_args("rf_search_fp16", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc != RF_OK) return rc;
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
+                        (hipStream_t)stream, nullptr, RF_FP16);
 }
 
 extern "C" int rf_search_profile(const rf_index_t* ix, const void* q_dev, int B, int k,
@@ -349,13 +394,14 @@ extern "C" int rf_search_profile(const rf_index_t* ix, const void* q_dev, int B,
                                  size_t workspace_bytes, void* stream, float* stage_ms_host) {
   int rc = check_search_args("rf_search_profile", ix, q_dev, B, k, scores_dev, ids_dev,
                              workspace_dev, workspace_bytes);
+  if (rc == RF_OK && plain_chain(ix, B) == RF_SHADOW) rc = check_sq8("rf_search_profile", ix, workspace_bytes);
   if (rc != RF_OK) return rc;
   if (!stage_ms_host || ix->size == 0) {
     rf_set_error("rf_search_profile: null stage buffer or empty index");
     return RF_ERR_INVALID;
   }
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, nullptr, false, stage_ms_host);
+                        (hipStream_t)stream, nullptr, plain_chain(ix, B), stage_ms_host);
 }
 
 // ---- SQ8 (include/ragfin.h, "SQ8 index") ------------------------------------------------------------
@@ -368,7 +414,7 @@ extern "C" int rf_search_sq8(const rf_index_t* ix, const void* q_dev, int B, int
   rc = check_sq8("rf_search_sq8", ix, workspace_bytes);
   if (rc != RF_OK) return rc;
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, nullptr, true);
+                        (hipStream_t)stream, nullptr, RF_SQ8);
 }
 
 extern "C" int rf_search_sq8_profile(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base,
@@ -385,7 +431,7 @@ extern "C" int rf_search_sq8_profile(const rf_index_t* ix, const void* q_dev, in
     return RF_ERR_INVALID;
   }
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, nullptr, true, stage_ms_host);
+                        (hipStream_t)stream, nullptr, RF_SQ8, stage_ms_host);
 }
 
 extern "C" int rf_debug_scores_sq8(const rf_index_t* ix, const void* q_dev, int B, int64_t n, float* out_dev,
@@ -458,7 +504,7 @@ extern "C" int rf_search_filtered(const rf_index_t* ix, const void* filter_dev, 
   if (rc != RF_OK) return rc;
   const rf_filter_view f = rf_filter_carve(filter_dev, ix->size);
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, &f, false);
+                        (hipStream_t)stream, &f, RF_FP16);
 }
 
 extern "C" int rf_search_exhaustive_filtered(const rf_index_t* ix, const void* filter_dev, const void* q_dev,
@@ -500,7 +546,7 @@ extern "C" int rf_search_multi_filtered(const rf_index_t* ix, const void* multi_
   rf_multi_layout(ix->size, n_filters, &so);
   const rf_multi m{(const uint32_t*)((const unsigned char*)multi_dev + so), qfilter_dev, rf_multi_columns(n_filters)};
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, &f, false, nullptr, nullptr, nullptr, &m);
+                        (hipStream_t)stream, &f, RF_FP16, nullptr, nullptr, nullptr, &m);
 }
 
 // ---- range search (include/ragfin.h, "range search") ----------------------------------------------
@@ -524,7 +570,7 @@ extern "C" int rf_search_range(const rf_index_t* ix, const void* filter_dev, con
   const rf_band band{radius, range_filter};
   const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix->size) : rf_filter_view{};
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
-                        (hipStream_t)stream, filter_dev ? &f : nullptr, false, nullptr, &band);
+                        (hipStream_t)stream, filter_dev ? &f : nullptr, RF_FP16, nullptr, &band);
 }
 
 extern "C" int rf_search_exhaustive_range(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B,
@@ -567,7 +613,7 @@ static int search_after_impl(const char* fn, const rf_index_t* ix, const void* f
   const rf_after after{after_score_dev, after_id_dev};
   const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix->size) : rf_filter_view{};
   return search_enqueue(ix, q_dev, B, k, id_base, o, workspace_dev, (hipStream_t)stream, filter_dev ? &f : nullptr,
-                        false, stage_ms, &band, &after);
+                        RF_FP16, stage_ms, &band, &after);
 }
 
 extern "C" int rf_search_after(const rf_index_t* ix, const void* filter_dev, const void* q_dev, int B, int k,

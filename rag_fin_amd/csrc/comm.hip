@@ -160,8 +160,10 @@ extern "C" int rf_search_sharded(const rf_index_t* ix, rf_comm_t* c, const void*
   int64_t* const send = scratch_dev;
   int64_t* const gathered = scratch_dev + words;
   float* const local_scores = (float*)(scratch_dev + ((size_t)c->world + 1) * words);
-  // 1. the local shard's exact top-k straight into the send buffer {fp64 scores, ids, flags}
-  int rc = rf_search(ix, q_dev, B, k, id_map_dev ? 0 : id_base, local_scores, send + bk, (double*)send, (uint32_t*)(send + 2 * bk),
+  // 1. the local shard's exact top-k straight into the send buffer {fp64 scores, ids, flags}: the fp16 chain
+  //    whatever is attached -- a flagged query of this step goes straight to the exhaustive kernel on every
+  //    shard, so the local scan must not add the shadow's flags
+  int rc = rf_search_fp16(ix,q_dev, B, k, id_map_dev ? 0 : id_base, local_scores, send + bk, (double*)send, (uint32_t*)(send + 2 * bk),
                      workspace_dev, workspace_bytes, stream);
   if (rc) return rc;
   // 2. local row numbers -> global ids where the shard is not a contiguous range

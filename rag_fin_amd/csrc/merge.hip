@@ -17,14 +17,7 @@
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// Wave-wide reductions on the DPP network (row_shr 1/2/4/8, row_bcast 15/31):
-// six VALU-rate steps instead of six LDS-crossbar shuffles.  The full result
-// lands in lane 63 and is broadcast with readlane.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_keep(uint32_t v) {
-  // lanes without a valid source (or in a masked row) keep their own value
-  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xF, false);
-}
+// (dpp_keep and wave_max_u64: merge_common.h)
 __device__ __forceinline__ float wave_max_f(float v) {
 #define RF_STEP(ctrl, rm) \
   v = fmaxf(v, __builtin_bit_cast(float, dpp_keep<ctrl, rm>(__builtin_bit_cast(uint32_t, v))));
@@ -36,21 +29,6 @@ __device__ __forceinline__ float wave_max_f(float v) {
 __device__ __forceinline__ float wave_sum_f(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#define RF_STEP(ctrl, rm)                                                           \
-  {                                                                                 \
-    const uint32_t lo = dpp_keep<ctrl, rm>((uint32_t)v);                            \
-    const uint32_t hi = dpp_keep<ctrl, rm>((uint32_t)(v >> 32));                    \
-    const unsigned long long w = ((unsigned long long)hi << 32) | lo;               \
-    v = w > v ? w : v;                                                              \
-  }
-  RF_STEP(0x111, 0xF) RF_STEP(0x112, 0xF) RF_STEP(0x114, 0xF) RF_STEP(0x118, 0xF)
-  RF_STEP(0x142, 0xA) RF_STEP(0x143, 0xC)
-#undef RF_STEP
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
 }
 
 // fp64 ranking score of the contract: eight interleaved chains (chain j takes
@@ -100,8 +78,8 @@ struct ThrFold {
   int force;                  // every list counts as incomplete (diagnostics)
 };
 // SQ8 (rf_search_sq8; mx == nullptr: FLAT).  The k-th partition maximum m_k of the fp16 sample
-// then becomes the int8 emit threshold thr_q = m_k - eps - f_q N' - slack, and eps_out receives
-// delta_q = n_q E + f_q N' + slack, the bound the merge widens its rescoring set by.
+// then becomes the int8 emit threshold thr_q = m_k - eps - f_q N' - slack; eps_out
+// receives the FLAT eps as ever, for the merge behind the refine stage (shadow_refine.hip).
 struct ThrSq8 {
   const float* nq;
   const float* fq;
@@ -221,9 +199,7 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
   if (BAND && qi < B) t = fmaxf(t, rf_band_floor(bd.lo - (double)eps));
   if (lane == 0) {
     thr[qi] = t;
-    eps_out[qi] = (sq.mx && qi < B) ? rf_sq8_delta(sq.nq[qi], sq.fq[qi], __builtin_bit_cast(float, sq.mx[0]),
-                                                   __builtin_bit_cast(float, sq.mx[1]))
-                                    : eps;
+    eps_out[qi] = eps;   // SQ8 too: the merge runs behind the refine stage, on fp16-accurate scores (§4.4n)
   }
   uint32_t appended = 0u;  // wave-uniform; entry g goes to shard g % RF_CAND_SHARDS
   if (folding) {

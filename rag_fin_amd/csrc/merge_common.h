@@ -8,6 +8,30 @@
 #define MERGE_THREADS 256     // one workgroup per query
 #define MERGE_STAGE_ROWS 32   // rows of R staged in LDS at a time: 8 lanes per row
 
+// Wave-wide reductions on the DPP network (row_shr 1/2/4/8, row_bcast 15/31):
+// six VALU-rate steps instead of six LDS-crossbar shuffles.  The full result
+// lands in lane 63 and is broadcast with readlane.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_keep(uint32_t v) {
+  // lanes without a valid source (or in a masked row) keep their own value
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#define RF_STEP(ctrl, rm)                                                           \
+  {                                                                                 \
+    const uint32_t lo = dpp_keep<ctrl, rm>((uint32_t)v);                            \
+    const uint32_t hi = dpp_keep<ctrl, rm>((uint32_t)(v >> 32));                    \
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;               \
+    v = w > v ? w : v;                                                              \
+  }
+  RF_STEP(0x111, 0xF) RF_STEP(0x112, 0xF) RF_STEP(0x114, 0xF) RF_STEP(0x118, 0xF)
+  RF_STEP(0x142, 0xA) RF_STEP(0x143, 0xC)
+#undef RF_STEP
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 // larger key <=> (higher MFMA score, then lower row)
 __device__ __forceinline__ unsigned long long cand_key(uint2 e) {
   return ((unsigned long long)rf_f2ord(__builtin_bit_cast(float, e.y)) << 32) |

@@ -39,6 +39,8 @@ struct rf_index {
   float* sq8_scale;    // device: [capacity_blocks][32] s_r, in accumulator order (rf_sq8_slot)
   float* sq8_err;      // device: [capacity_blocks][32] e_r, same order
   uint32_t* sq8_max;   // device: {bits of N' = max ||s_r c^_r||, bits of E = max e_r}
+  // rf_index_set_shadow_first: rf_search sweeps the shadow first from this many rows on (0: never)
+  int64_t shadow_min_rows;
 };
 // An index is immutable during searches (no mutable host state: any number of threads may
 // search one index concurrently, each with its own workspace and stream); rf_index_add_f16 /
@@ -56,6 +58,7 @@ struct rf_index {
   X(ring24, 8, 6, 24)            /* register-ring depth (fragments) of the dim-384 emit sweep: 6 | 8 | 12 | 24 */    \
   X(emit_wgs_per_cu, 0, 0, 4)    /* emit grid = CUs x this (0 = default for the dim) */                              \
   X(sample_bpw, 2, 1, 8)         /* sample blocks per wave */                                                        \
+  X(sq8_ring12, 6, 4, 12)        /* register-ring depth (fragments) of the dim-384 int8 emit: 12 | 6 | 4 (A/B only: the product ships 6) */ \
   X(sample_fold, 1, 0, 1)        /* 64-query sweep: the emit skips the sampled blocks (k_threshold appends what the sample kept) */ \
   X(fold_dbg, 0, 0, 3)           /* sample fold diagnostics: 1 = every kept list counts as incomplete (all rescanned), 2 = k_merge leaves the candidate counters */ \
   X(wide_sample_pairs, 4, 1, 8)  /* wide sample pass: block pairs per workgroup, at most */                          \
@@ -245,6 +248,10 @@ int rf_launch_sq8_emit(const rf_index* ix, int B, int JB, const rf_workspace& ws
                        hipStream_t st);
 int rf_launch_sq8_debug(const rf_index* ix, int B, int64_t n, const rf_sq8_ws& sw, float* out, float* delta,
                         hipStream_t st);
+// shadow_refine.hip: behind rf_launch_sq8_emit -- prune each query's candidates by the per-row bound
+// and replace them by {row, fp16-accurate score} of the survivors
+int rf_launch_shadow_refine(const rf_index* ix, const void* q, int B, int k, const rf_workspace& ws,
+                            const rf_sq8_ws& sw, hipStream_t st);
 // merge.hip
 int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
                         const rf_workspace& ws, hipStream_t st, const rf_fold* fold = nullptr,

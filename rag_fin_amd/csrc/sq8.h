@@ -19,6 +19,12 @@ __device__ __forceinline__ float rf_sq8_delta(float nq, float fq, float Np, floa
   const double d = (double)nq * E + (double)fq * Np + rf_sq8_slack(nq, fq, Np, E);
   return __double2float_ru(d);
 }
+// beta_r = n_q e_r + f_q N' + slack, rounded up: bounds |a - a~| for the row whose residual norm is
+// e_r (e_r <= E, so beta_r <= delta_q); what the refine stage prunes by
+__device__ __forceinline__ float rf_sq8_beta(float nq, float er, float fq, float Np, float E) {
+  const double d = (double)nq * er + (double)fq * Np + rf_sq8_slack(nq, fq, Np, E);
+  return __double2float_ru(d);
+}
 // emit threshold thr_q = m_k - eps - f_q N' - slack, rounded down; a row is emitted when
 // a~ + n_q e_r >= thr_q
 __device__ __forceinline__ float rf_sq8_thr(float mk, float eps, float nq, float fq, float Np, float E) {

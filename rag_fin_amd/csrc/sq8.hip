@@ -465,12 +465,21 @@ int rf_launch_sq8_emit(const rf_index* ix, int B, int JB, const rf_workspace& ws
   p.cand_cnt = ws.cand_cnt;
   p.cand = ws.cand;
   p.cap = RF_SHARD_CAP;
-  // ring: a whole block up to 12 KiB, otherwise 8 or 12 fragments (must divide KS8)
+  // ring: a whole block up to 8 KiB, otherwise 6, 8 or 12 fragments (must divide KS8); dim 384 takes half a
+  // block: 6 beat 12 by 2.4 us per sweep in the interleaved A/B, 4 did not beat 6
 #define RF_SQ8(ks8, r) \
   case ks8:            \
     return JB == 1 ? launch_sq8<ks8, r, 1>(p, grid, st) : launch_sq8<ks8, r, 2>(p, grid, st);
+#ifdef RF_EXPERIMENTS
+  // A/B of the ring depth at dim 384 (tools/bench_sq8_ring.py, profiles/flat_shadow_emit_ab.txt); the product
+  // below dispatches the ring of 6 that won it
+  if (ix->dim / 32 == 12 && rf_knob_sq8_ring12 == 12)
+    return JB == 1 ? launch_sq8<12, 12, 1>(p, grid, st) : launch_sq8<12, 12, 2>(p, grid, st);
+  if (ix->dim / 32 == 12 && rf_knob_sq8_ring12 == 4)
+    return JB == 1 ? launch_sq8<12, 4, 1>(p, grid, st) : launch_sq8<12, 4, 2>(p, grid, st);
+#endif
   switch (ix->dim / 32) {
-    RF_SQ8(2, 2) RF_SQ8(4, 4) RF_SQ8(8, 8) RF_SQ8(12, 12) RF_SQ8(16, 8) RF_SQ8(24, 12) RF_SQ8(32, 8)
+    RF_SQ8(2, 2) RF_SQ8(4, 4) RF_SQ8(8, 8) RF_SQ8(12, 6) RF_SQ8(16, 8) RF_SQ8(24, 12) RF_SQ8(32, 8)
     default:
       break;
   }

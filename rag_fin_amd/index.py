@@ -42,8 +42,9 @@ def require_gpu(device=None):
 
 def rerun_flagged(q16, k: int, id_base: int, flags, sq8: bool, filt, flat, exhaustive):
     """The flagged-query ladder ("fallback"): a query the first pass could not prove
-    exact (flags != 0) is re-run one tier down.  A query flagged by an SQ8 first pass (`sq8`) goes
-    through the FLAT chain, and only one that flags there too goes to the exhaustive kernel; one
+    exact (flags != 0) is re-run one tier down.  A query flagged by a first pass over the int8 shadow
+    (`sq8`: rf_search_sq8, or rf_search on a shadow-first index) goes through the fp16 chain
+    (`flat`: rf_search_fp16), and only one that flags there too goes to the exhaustive kernel; one
     flagged by a FLAT or filtered (`filt`) first pass goes straight to the exhaustive kernel, over
     the same passing rows.  The tiers are callables, on whatever device their tensors live:
       flat(q, k, id_base)             -> (scores, ids, exact | None, flags)
@@ -182,9 +183,27 @@ class GpuIndex:
     exceptions are `search_raw(workspace=None)` and `enqueue_search`: the benchmark and the
     sharded lanes call them on streams of their own, and the caller serialises.  The lock is not
     re-entrant: public locked methods call the private unlocked ones (`_exhaustive`,
-    `_rerun_flagged`), never each other."""
+    `_rerun_flagged`), never each other.
 
-    def __init__(self, dim: int, capacity: int, device=None):
+    shadow: the int8 shadow behind plain searches.  "auto" attaches one and lets
+    rf_search sweep it first when capacity >= SHADOW_MIN_ROWS and dim % 32 == 0; True forces it for
+    any capacity (dim % 32 == 0 still, else RagfinError); False never attaches.  The shadow costs
+    dim + 8 bytes per row of capacity next to the 2 dim of the fp16 rows (+51 % at dim 384).  The
+    answers do not depend on it.  `.sq8` stays "the caller enabled SQ8" (enable_sq8 reuses an
+    auto-attached shadow, disable_sq8 keeps it)."""
+
+    # Rows of capacity from which "auto" takes the shadow first (None would switch "auto" off).  Measured with
+    # bench.py --rows N, shadow forced (tools/bench_shadow_rows.py lowers this attribute for one run), against
+    # the parent commit (profiles/flat_shadow_min_rows.json, DESIGN
+    # §5.0s): the int8 chain loses at 100 k and 250 k rows (two more launches on a launch-bound step), wins
+    # 3 % at 500 k, 6 % at 2^19 and a third at 1 M; 2^19 is 500 k rounded to a power of two.
+    SHADOW_MIN_ROWS = 1 << 19
+    shadow_first = False      # rf_search sweeps the shadow first on this index (set by the constructor)
+    _shadow_min_rows = 0
+    _sq8_storage = None
+    _sq8_enabled = False
+
+    def __init__(self, dim: int, capacity: int, device=None, shadow="auto"):
         torch = _torch()
         self.device = require_gpu(device)
         self.lib = _lib.load_library()
@@ -200,6 +219,21 @@ class GpuIndex:
                                                 c_void_p(self.storage.data_ptr()), nbytes,
                                                 self.device.index))
             self.handle = handle
+            self._lock = threading.Lock()
+            self._sq8_storage = None   # the int8 shadow: a separate allocation
+            self._sq8_enabled = False  # enable_sq8 was called (the shadow may be there without it)
+            if isinstance(shadow, np.bool_):
+                shadow = bool(shadow)
+            if not (isinstance(shadow, bool) or (isinstance(shadow, str) and shadow == "auto")):   # (1 == True: no ints)
+                raise ValueError(f"shadow must be 'auto', True or False, got {shadow!r}")
+            self.shadow = shadow       # as asked for: what a store passes on when it rebuilds the index
+            self.shadow_first = shadow is True or (shadow == "auto" and self.SHADOW_MIN_ROWS is not None
+                                                   and self.capacity >= self.SHADOW_MIN_ROWS and self.dim % 32 == 0)
+            # rows from which the library takes the shadow chain (rf_index_set_shadow_first); 0: never
+            self._shadow_min_rows = 0 if not self.shadow_first else 1 if shadow is True else int(self.SHADOW_MIN_ROWS)
+            if self.shadow_first:   # before workspace_bytes is read: it then covers the SQ8 query area
+                self._attach_shadow()
+                _lib.check(self.lib.rf_index_set_shadow_first(self.handle, self._shadow_min_rows))
             ws = self.lib.rf_search_workspace_bytes(self.handle)
             # one workspace serves both paths: the SQ8 one is the FLAT one plus its query area
             self.sq8_workspace_bytes = self.lib.rf_search_sq8_workspace_bytes(self.handle)
@@ -208,9 +242,7 @@ class GpuIndex:
             self.workspace_bytes = ws
             self._alloc_bytes = max(ws, self.sq8_workspace_bytes, self.grouped_workspace_bytes)
             self.workspace = self.new_workspace()
-        self._lock = threading.Lock()
         self._host_bufs = {}
-        self._sq8_storage = None   # the SQ8 shadow (enable_sq8), a separate allocation
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -294,15 +326,12 @@ class GpuIndex:
     # -- SQ8 shadow (include/ragfin.h, "SQ8 index") ----------------------------------------
     @property
     def sq8(self) -> bool:
-        """True while an int8 shadow is attached (rf_search_sq8 can run)."""
-        return self._sq8_storage is not None
+        """True while the caller has SQ8 enabled (enable_sq8; rf_search_sq8 can run).  A shadow that
+        only the `shadow` argument attached does not count."""
+        return self._sq8_enabled
 
-    def enable_sq8(self) -> None:
-        """Attach an int8 shadow (dim + 8 bytes per row of capacity) and quantize every row; adds,
-        compactions and resets keep it current from then on.  Needs dim % 32 == 0."""
+    def _attach_shadow(self) -> None:
         torch = _torch()
-        if self._sq8_storage is not None:
-            return
         nbytes = self.lib.rf_sq8_storage_bytes(self.dim, self.capacity)
         if nbytes == 0:
             raise _lib.RagfinError(-2, f"SQ8 needs dim % 32 == 0 (dim {self.dim})")
@@ -312,9 +341,18 @@ class GpuIndex:
                                                     _lib.current_stream_ptr()))
             self._sq8_storage = storage
 
+    def enable_sq8(self) -> None:
+        """Attach an int8 shadow (dim + 8 bytes per row of capacity) and quantize every row; adds,
+        compactions and resets keep it current from then on.  Needs dim % 32 == 0.  An index that
+        already carries one (the `shadow` argument) reuses it."""
+        if self._sq8_storage is None:
+            self._attach_shadow()
+        self._sq8_enabled = True
+
     def disable_sq8(self) -> None:
         torch = _torch()
-        if self._sq8_storage is None:
+        self._sq8_enabled = False
+        if self._sq8_storage is None or self.shadow_first:   # (the shadow behind plain searches stays)
             return
         with self._lock, torch.cuda.device(self.device):
             _lib.check(self.lib.rf_index_detach_sq8(self.handle))
@@ -353,7 +391,7 @@ class GpuIndex:
     def search_sq8_profile(self, q16, k: int):
         """rf_search_sq8_profile: per-stage HIP-event times in ms of the first 64-query sweep."""
         return self._profile(self.lib.rf_search_sq8_profile, q16, min(q16.shape[0], _lib.RF_QCHUNK), k,
-                             self.workspace.numel(), ("quantize", "sample", "threshold", "emit", "merge"))
+                             self.workspace.numel(), ("quantize", "sample", "threshold", "emit", "refine", "merge"))
 
     def _profile(self, fn, q16, B: int, k: int, workspace_bytes: int, stages, lead=(), k_args=None):
         """The first sweep of a B-query batch through a *_profile entry point -> {stage: ms}.
@@ -387,7 +425,8 @@ class GpuIndex:
                 torch.empty((B,), dtype=torch.int32, device=self.device) if flags else None)
 
     def search_raw(self, q16, k: int, id_base: int = 0, want_exact: bool = False, out=None,
-                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None, group=None, mmr=None):
+                   workspace=None, stream_ptr=None, filt=None, sq8: bool = False, band=None, group=None, mmr=None,
+                   fp16: bool = False):
         """Enqueue rf_search on the current stream (or on `stream_ptr`, a c_void_p holding a
         hipStream_t of this device); no host sync.  Returns
         (scores f32 [B,k], ids i64 [B,k], exact f64 [B,k] | None, flags u32 [B]).
@@ -397,6 +436,8 @@ class GpuIndex:
         exactly these B queries; no sq8, band, group or mmr form: ValueError).
         sq8: rf_search_sq8 (needs enable_sq8; not with filt).  A workspace passed in must hold
         sq8_workspace_bytes (new_workspace does).
+        fp16: the plain search through rf_search_fp16 -- the fp16 chain even on a shadow-first index
+        (the FLAT tier of the ladder, the sharded lanes); no effect on the other forms.
         band: (radius, range_filter) -- rf_search_range: the best k rows with
         radius < fp64 score <= range_filter (within the passing rows with filt; not with sq8).
         group: (codes int32 [size] on this device, n_codes, n_groups, group_size) -- rf_search_grouped:
@@ -414,6 +455,9 @@ class GpuIndex:
         lanes call it on their own streams, and whoever shares the index's workspace serialises."""
         torch = _torch()
         self._check_variant(filt, sq8, band, group, k, mmr)
+        if sq8 and not self._sq8_enabled and self._sq8_storage is not None:   # (no shadow at all: the library says so)
+            raise _lib.RagfinError(-1, "rf_search_sq8: SQ8 not enabled on this index (enable_sq8); the shadow it "
+                                       "carries serves plain searches only")
         if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
             raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
         if not q16.is_contiguous() or q16.device != self.device:
@@ -435,7 +479,7 @@ class GpuIndex:
             res = self._outputs(B, k, want_exact, out=out)
             _, cand_ids, cand_exact, _ = self.search_raw(
                 q16, int(mmr[0]), id_base, True, out=self._outputs(B, int(mmr[0]), True, flags=False)[:3] + (res[3],),
-                workspace=workspace, stream_ptr=stream_ptr, filt=filt, sq8=sq8, band=band)
+                workspace=workspace, stream_ptr=stream_ptr, filt=filt, sq8=sq8, band=band, fp16=fp16)
             self._mmr_select(cand_exact, cand_ids, k, mmr, id_base, res, stream_ptr)
             return res
         scores, ids, exact, flags = self._outputs(B, k, want_exact, out=out)
@@ -454,7 +498,7 @@ class GpuIndex:
             elif sq8:
                 _lib.check(self.lib.rf_search_sq8(self.handle, *args))
             elif filt is None:
-                _lib.check(self.lib.rf_search(self.handle, *args))
+                _lib.check((self.lib.rf_search_fp16 if fp16 else self.lib.rf_search)(self.handle, *args))
             else:
                 _lib.check(self.lib.rf_search_filtered(self.handle, _ptr(filt), *args))
         return scores, ids, exact, flags
@@ -513,13 +557,14 @@ class GpuIndex:
                              lead=(_ptr(filt), _ptr(group[0]), int(group[1])), k_args=(n, s))
 
     def enqueue_search(self, q_ptr: int, B: int, k: int, id_base: int, scores_ptr: int, ids_ptr: int,
-                       exact_ptr: int, flags_ptr: int, workspace_ptr: int, stream_ptr):
+                       exact_ptr: int, flags_ptr: int, workspace_ptr: int, stream_ptr, fp16: bool = False):
         """The bare rf_search enqueue for callers that own every buffer (the sharded step: no
         tensor checks, no allocations, no stream / device context).  The caller guarantees that
         this index's device is the thread's current HIP device, and serialises the use of
-        the workspace it passes: no lock is taken here."""
-        rc = self.lib.rf_search(self.handle, q_ptr, B, k, id_base, scores_ptr, ids_ptr, exact_ptr, flags_ptr,
-                                workspace_ptr, self.workspace_bytes, stream_ptr)
+        the workspace it passes: no lock is taken here.  fp16: rf_search_fp16 (the sharded lanes)."""
+        fn = self.lib.rf_search_fp16 if fp16 else self.lib.rf_search
+        rc = fn(self.handle, q_ptr, B, k, id_base, scores_ptr, ids_ptr, exact_ptr, flags_ptr,
+                workspace_ptr, self.workspace_bytes, stream_ptr)
         if rc:
             _lib.check(rc)
 
@@ -729,9 +774,19 @@ class GpuIndex:
         if group is not None:
             return rerun_flagged(q16, k, id_base, flags, False, filt, None,
                                  lambda q, k, base, f: self._grouped_exhaustive(q, group, base, want_exact, f))
-        return rerun_flagged(q16, k, id_base, flags, sq8, filt,
-                             lambda q, k, base: self.search_raw(q, k, base, want_exact, band=band),
+        # (a plain first pass on a shadow-first index swept the shadow like an SQ8 one: fp16 comes next)
+        shadow = sq8 or (filt is None and band is None and self._plain_chain_is_shadow(q16.shape[0]))
+        return rerun_flagged(q16, k, id_base, flags, shadow, filt,
+                             lambda q, k, base: self.search_raw(q, k, base, want_exact, band=band, fp16=True),
                              lambda q, k, base, f: self._exhaustive(q, k, base, want_exact, f, band=band))
+
+    def _plain_chain_is_shadow(self, B: int) -> bool:
+        """Whether a plain rf_search of B queries takes the shadow chain: plain_chain in api.hip, condition
+        for condition (switch set, size >= min_rows, size > RF_SMALL_ROWS, one 64-query sweep)."""
+        if not self.shadow_first or B > _lib.RF_QCHUNK:
+            return False
+        n = self.size
+        return n >= self._shadow_min_rows and n > _lib.RF_SMALL_ROWS
 
     def _grouped_first_pass(self, q16, k: int, id_base: int, want_exact: bool, filt, sq8: bool, band, group,
                             out=None):

@@ -35,7 +35,9 @@ SHARD_FAILED = -(1 << 31)
 
 
 class HipShardBackend:
-    """Local scan = rf_search / rf_search_exhaustive, merge = rf_merge_shards* (all HIP)."""
+    """Local scan = rf_search_fp16 / rf_search_exhaustive, merge = rf_merge_shards* (all HIP).
+    The local scan stays on the fp16 chain even where the index sweeps its int8 shadow first: a
+    flagged query of a sharded step goes straight to the exhaustive kernel (no FLAT tier between)."""
 
     def __init__(self, index):
         self.index = index
@@ -45,7 +47,7 @@ class HipShardBackend:
     # -- generic contract (also what the CPU test backend implements) ----------------------
     def local_topk(self, q16, k: int, row_base: int, workspace=None):
         scores, ids, exact, flags = self.index.search_raw(q16, k, id_base=row_base, want_exact=True,
-                                                          workspace=workspace)
+                                                          workspace=workspace, fp16=True)
         return exact, ids, flags
 
     def local_exhaustive(self, q16, k: int, row_base: int):
@@ -84,7 +86,7 @@ class HipShardBackend:
             ids=torch.empty((B, k), dtype=torch.int64, device=dev))
 
     def local_topk_into(self, q16, k: int, row_base: int, lane, workspace=None):
-        self.index.search_raw(q16, k, id_base=row_base, want_exact=True, workspace=workspace,
+        self.index.search_raw(q16, k, id_base=row_base, want_exact=True, workspace=workspace, fp16=True,
                               out=(lane["local_scores"], lane["local_ids"], lane["exact"], lane["local_flags"]))
 
     def merge_packed(self, flat, lane):
@@ -151,7 +153,7 @@ class ShardedSearcher:
                 out_s=lane["scores"].data_ptr(), out_i=lane["ids"].data_ptr(), out_f=lane["flags"].data_ptr())
         ix = self.backend.index
         ix.enqueue_search(q16.data_ptr(), B, k, 0 if self.id_map is not None else self.row_base, st["scores_local"],
-                          st["ids"], st["exact"], st["lflags"], st["ws"], st["sp"])
+                          st["ids"], st["exact"], st["lflags"], st["ws"], st["sp"], fp16=True)
         if self.id_map is not None:   # shards not contiguous in the global numbering: local rows -> global ids (HIP)
             rc = self.backend.lib.rf_map_ids(st["ids"], B * k, self.id_map.data_ptr(), self.id_map.numel(), st["sp"])
             if rc:

@@ -50,6 +50,9 @@ class ShardedCorpusStore(CorpusStore):
         if not dist.is_initialized():
             raise RuntimeError("ShardedCorpusStore needs an initialised torch.distributed process group "
                                "(one process per GPU); use CorpusStore on a single GPU")
+        if index is None:   # the sharded lanes stay on the fp16 chain: no int8 shadow to carry
+            from .index import GpuIndex
+            index = GpuIndex(dim, capacity, device, shadow=False)
         super().__init__(name, dim, capacity, device, metric_type, index=index)
         torch = _torch()
         self.group = group

@@ -506,7 +506,8 @@ class CorpusStore:
     def _grow(self, need: int) -> None:
         old = self.index
         cap = max(need, old.capacity * 2)
-        new = type(old)(self.dim, cap, old.device)
+        # (a CPU double of GpuIndex takes no shadow argument)
+        new = type(old)(self.dim, cap, old.device, **({"shadow": old.shadow} if hasattr(old, "shadow") else {}))
         n = old.size
         step = 1 << 18
         for s in range(0, n, step):
