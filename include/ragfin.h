@@ -568,6 +568,48 @@ size_t rf_text_match_workspace_bytes(const rf_sparse_t* sp, int n_leaves);
 int rf_text_match(const rf_sparse_t* sp, const rf_text_leaf* leaves_host, int n_leaves, const int32_t* terms_dev,
                   int64_t n_terms_total, uint32_t* bitmaps_dev, int64_t words_per_leaf, void* workspace_dev,
                   size_t workspace_bytes, void* stream);
+/* ---- user-defined scalar fields: the leaves of `expr` over a collection's own columns --------------
+ * A pymilvus user declares FieldSchemas of their own next to the reference's seven
+ * (rag_fin_amd/schema.py: VARCHAR, INT64, DOUBLE, BOOL).  The filter program above reads four
+ * hard-wired columns; a leaf over any other column is evaluated here into a row bitmap, which a
+ * RF_FOP_BITMAP leaf of rf_filter_eval_bitmaps then reads -- the door rf_text_match uses.
+ * Leaf kinds (column_dev: the leaf's column in device memory, [n_rows], aligned to its element):
+ *   RF_CLEAF_CODESET    int32 dictionary codes (VARCHAR, BOOL): row passes iff its code x has
+ *                       0 <= x < 32 len and bit x of code_sets_dev[off .. off + len) is set
+ *   RF_CLEAF_I64_RANGE  int64 values: ilo <= x <= ihi, both ends inclusive (ilo > ihi passes nothing)
+ *   RF_CLEAF_I64_SET    int64 values: x is in value_sets_dev[off .. off + len) (sorted ascending,
+ *                       binary search), len <= RF_COLUMN_MAX_SET
+ *   RF_CLEAF_F64_RANGE  fp64 values: flo <(=) x <(=) fhi, RF_FRANGE_* bits in flags say which ends
+ *                       are inclusive; IEEE comparisons, so a NaN value fails
+ * leaves_host: n_leaves (1..RF_COLUMN_MAX_LEAVES) leaves in HOST memory (they travel in the launch
+ * arguments, so the call captures into a hipGraph); leaf l writes EVERY word of bitmaps_dev[l * nwords ..
+ * (l + 1) * nwords), nwords = ceil(n_rows / 32): bit r & 31 of word r >> 5 = row r passes; bits past
+ * n_rows are zero, so the caller need not clear the buffer.  One launch for all leaves, grid (row chunks,
+ * leaves): a lane owns one row, a wave's 64 predicates become two words by ballot.  Stream-ordered, no
+ * host sync, no allocation, no atomics; integers and IEEE comparisons only: the same bits on every run.
+ * RF_ERR_INVALID before any device call: a NULL leaves_host / bitmaps_dev, n_leaves or n_rows out of
+ * range, an unknown kind, a negative off or len, a set of more than RF_COLUMN_MAX_SET values, a leaf
+ * that needs code_sets_dev / value_sets_dev when that is NULL, unknown flags, a column that is NULL or
+ * misaligned.  A code or a search position outside the leaf's [off, off + len) is never dereferenced.
+ * n_rows == 0 writes nothing and returns RF_OK.
+ * New in this build; the reference's collection carries no field of its own. */
+#define RF_COLUMN_MAX_LEAVES 16
+#define RF_COLUMN_MAX_SET 65536
+#define RF_CLEAF_CODESET 1
+#define RF_CLEAF_I64_RANGE 2
+#define RF_CLEAF_I64_SET 3
+#define RF_CLEAF_F64_RANGE 4
+typedef struct rf_column_leaf {
+  int32_t kind;            /* RF_CLEAF_* */
+  int32_t flags;           /* F64_RANGE: RF_FRANGE_* bits */
+  const void* column_dev;  /* int32 codes | int64 | fp64, [n_rows] */
+  int64_t off;             /* CODESET: first word in code_sets_dev; I64_SET: first entry in value_sets_dev */
+  int64_t len;             /* CODESET: words; I64_SET: entries */
+  int64_t ilo, ihi;        /* I64_RANGE bounds, inclusive */
+  double flo, fhi;         /* F64_RANGE bounds */
+} rf_column_leaf;
+int rf_column_match(const rf_column_leaf* leaves_host, int n_leaves, const uint32_t* code_sets_dev,
+                    const int64_t* value_sets_dev, int64_t n_rows, uint32_t* bitmaps_dev, void* stream);
 /* ---- lexical index maintenance: the postings after an append or a delete, without the old texts -------
  * A write changes N, avgdl and df, and through them every BM25 impact -- but with the term frequencies
  * kept beside the postings (post_tf uint32 [nnz]) everything is re-derivable: the arrays after a write

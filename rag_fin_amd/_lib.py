@@ -29,6 +29,10 @@ RF_BOOST_MAX = 3             # boosts of one search: 2^3 = 8 row classes, the mo
 RF_TEXT_MATCH = 1
 RF_TEXT_PHRASE = 2
 RF_TEXT_MAX_LEAVES = 16      # text leaves one rf_text_match call (one filter expression) holds
+# user-defined scalar fields (include/ragfin.h, "user-defined scalar fields")
+RF_COLUMN_MAX_LEAVES = 16    # column leaves one rf_column_match call (one filter expression) holds
+RF_COLUMN_MAX_SET = 65536    # values of one INT64 `in` list
+RF_CLEAF_CODESET, RF_CLEAF_I64_RANGE, RF_CLEAF_I64_SET, RF_CLEAF_F64_RANGE = 1, 2, 3, 4
 # lexical index maintenance (include/ragfin.h, "lexical index maintenance")
 RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
 # lexical index build (include/ragfin.h, "lexical index build")
@@ -64,6 +68,12 @@ class FilterOp(Structure):
 
 class TextLeaf(Structure):
     _fields_ = [("kind", c_int32), ("term_off", c_int32), ("n_terms", c_int32), ("min_match", c_int32)]
+
+
+class ColumnLeaf(Structure):
+    """rf_column_leaf: one leaf of a filter expression over an extra column."""
+    _fields_ = [("kind", c_int32), ("flags", c_int32), ("column_dev", c_void_p), ("off", c_int64), ("len", c_int64),
+                ("ilo", c_int64), ("ihi", c_int64), ("flo", c_double), ("fhi", c_double)]
 
 
 class Postings(Structure):
@@ -197,6 +207,7 @@ SIGNATURES = {
     "rf_text_match_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "rf_text_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
                               c_void_p]),
+    "rf_column_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_sparse_impacts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,
                                   c_double, c_double, c_void_p, c_void_p]),
     "rf_sparse_append_workspace_bytes": (c_size_t, [c_int64, c_int64]),

@@ -52,7 +52,8 @@ class MicroBatcher:
         if filter_expr.is_empty(expr):
             expr = None
         else:
-            filter_expr.parse(expr, getattr(getattr(self.rag, "collection", None), "analyzer", None))
+            store = getattr(self.rag, "collection", None)
+            filter_expr.parse(expr, getattr(store, "analyzer", None), getattr(store, "schema", None))
         req = _Request(query, top_k, expr)
         with self._cv:
             if self._stop:

@@ -55,6 +55,7 @@ from typing import Any, Sequence
 import numpy as np
 
 from . import _lib, lexical
+from .schema import INT64_MAX, INT64_MIN, DataType
 
 VARCHAR_FIELDS = ("period", "chunk_type", "statement_type")   # device columns 0, 1, 2
 DOUBLE_FIELDS = ("primary_value",)                             # device column 3
@@ -265,10 +266,11 @@ def like_match(s: str, pattern: str) -> bool:
 
 # ---- parser ------------------------------------------------------------------------------------
 class _Parser:
-    def __init__(self, text: str, analyzer=None):
+    def __init__(self, text: str, analyzer=None, schema=None):
         self.toks = tokenize(text)
         self.i = 0
         self.analyzer = analyzer
+        self.extra = {f.name: f.dtype for f in schema or ()}   # the collection's own fields (schema.py)
 
     def peek(self, k: int = 0) -> Tok:
         return self.toks[min(self.i + k, len(self.toks) - 1)]
@@ -291,7 +293,8 @@ class _Parser:
             raise _err("empty expression", self.peek())
         node = self.expr()
         if self.peek().kind != "end":
-            raise _err("unexpected token", self.peek())
+            t = self.peek()
+            raise _err("unexpected token" + (" (arithmetic is not supported)" if t.kind == "op" and t.value in "+-" else ""), t)
         return node
 
     def expr(self) -> Node:
@@ -329,9 +332,19 @@ class _Parser:
         name = t.value
         if name in UNFILTERABLE:
             raise _err(f"field {name!r} cannot be filtered on", t)
-        if name not in VARCHAR_FIELDS + DOUBLE_FIELDS + (PK_FIELD,):
+        if name not in VARCHAR_FIELDS + DOUBLE_FIELDS + (PK_FIELD,) and name not in self.extra:
+            if name.lower().startswith(("json_", "array_")) and self.op("("):
+                raise _err(f"unknown function {name!r} (ARRAY and JSON fields are not supported)", t)
             raise _err(f"unknown field {name!r}", t)
         return name, t
+
+    def dtype(self, name: str):
+        """The DataType of a filterable scalar field (None: the primary key)."""
+        if name in VARCHAR_FIELDS:
+            return DataType.VARCHAR
+        if name in DOUBLE_FIELDS:
+            return DataType.DOUBLE
+        return self.extra.get(name)
 
     def literal(self) -> tuple[Any, Tok]:
         t = self.take()
@@ -344,6 +357,10 @@ class _Parser:
             t = self.take()
         if t.kind == "num":
             return sign * t.value, first
+        if first is t and t.kind == "name" and t.value.lower() in ("true", "false"):
+            return t.value.lower() == "true", t
+        if first.kind == "name":
+            raise _err("expected a literal (a field compared with a field is not supported)", first)
         raise _err("expected a literal", first)
 
     def cmp_op(self) -> Tok | None:
@@ -354,7 +371,8 @@ class _Parser:
 
     def compare(self) -> Node:
         t = self.peek()
-        if t.kind in ("str", "num") or (t.kind == "op" and t.value in "+-"):
+        if t.kind in ("str", "num") or (t.kind == "op" and t.value in "+-") or \
+                (t.kind == "name" and t.value.lower() in ("true", "false") and t.value not in self.extra):
             # literal CMP field [CMP literal]
             lit, lt = self.literal()
             o1 = self.cmp_op()
@@ -383,7 +401,7 @@ class _Parser:
             return In(name, self._list(name, kt), negate)
         if self.kw("like"):
             kt = self.take()
-            if name not in VARCHAR_FIELDS:
+            if self.dtype(name) != DataType.VARCHAR:
                 raise _err(f"'like' needs a VARCHAR field, {name!r} is not one", kt)
             pt = self.take()
             if pt.kind != "str":
@@ -391,7 +409,12 @@ class _Parser:
             if "%" in pt.value.strip("%") or pt.value in ("%", "%%"):
                 raise _err("'like' supports 'p%', '%s' and '%i%' only", pt)
             return Like(name, pt.value)
-        raise _err("expected a comparison, 'in' or 'like'", self.peek())
+        nt = self.peek()
+        if nt.kind == "op" and nt.value in "+-":
+            raise _err("expected a comparison, 'in' or 'like' (arithmetic is not supported)", nt)
+        if nt.kind == "op" and nt.value == "[":
+            raise _err("expected a comparison, 'in' or 'like' (ARRAY and JSON fields are not supported)", nt)
+        raise _err("expected a comparison, 'in' or 'like'", nt)
 
     def text_func(self) -> Node:
         """The keyword leaf of the grammar: FUNC ( text , STRING [, NAME = NUM | , NUM] )."""
@@ -446,7 +469,7 @@ class _Parser:
         if not self.op("]"):
             while True:
                 lit, lt = self.literal()
-                vals.append(_check_type(name, lit, lt))
+                vals.append(self._check_type(name, lit, lt))
                 if self.op(","):
                     self.take()
                     continue
@@ -459,26 +482,48 @@ class _Parser:
     def _leaf_cmp(self, name, ft, op, lit, lt, ot) -> Node:
         if name == PK_FIELD and op not in ("==", "!="):
             raise _err(f"the primary key supports == != in / not in only, not {ot.value!r}", ot)
-        return Cmp(name, op, _check_type(name, lit, lt))
+        if self.dtype(name) == DataType.BOOL and op not in ("==", "!="):
+            raise _err(f"a BOOL field supports == != in / not in only, not {ot.value!r}", ot)
+        return Cmp(name, op, self._check_type(name, lit, lt))
+
+    def _check_type(self, name: str, lit, tok: Tok):
+        t = self.dtype(name)
+        if t == DataType.VARCHAR:
+            if not isinstance(lit, str):
+                raise _err(f"{name} is VARCHAR, the literal is not a string", tok)
+            return lit
+        if t == DataType.DOUBLE:
+            if isinstance(lit, str):
+                raise _err(f"{name} is DOUBLE, the literal is a string", tok)
+            if isinstance(lit, bool):
+                raise _err(f"{name} is DOUBLE, the literal is a boolean", tok)
+            return float(lit)
+        if t == DataType.BOOL:
+            if not isinstance(lit, bool):
+                raise _err(f"{name} is BOOL, the literal is not true or false", tok)
+            return lit
+        if t == DataType.INT64:
+            if isinstance(lit, (str, bool)):
+                raise _err(f"{name} is INT64, the literal is a {'string' if isinstance(lit, str) else 'boolean'}", tok)
+            if isinstance(lit, float):
+                if not math.isfinite(lit):
+                    raise _err(f"{name} is INT64, the literal is not finite", tok)
+                return lit   # compared mathematically: x > 2.5 is x >= 3
+            if not INT64_MIN <= lit <= INT64_MAX:
+                raise _err(f"{name} is INT64, the literal is outside the int64 range", tok)
+            return lit
+        if isinstance(lit, bool):
+            raise _err("the primary key is compared with its keys, not with a boolean", tok)
+        return lit   # id: int or str keys, as inserted
 
 
-def _check_type(name: str, lit, tok: Tok):
-    if name in VARCHAR_FIELDS:
-        if not isinstance(lit, str):
-            raise _err(f"{name} is VARCHAR, the literal is not a string", tok)
-        return lit
-    if name in DOUBLE_FIELDS:
-        if isinstance(lit, str):
-            raise _err(f"{name} is DOUBLE, the literal is a string", tok)
-        return float(lit)
-    return lit   # id: int or str keys, as inserted
-
-
-def parse(text: str, analyzer=None) -> Node:
-    """analyzer: what the keyword leaves analyse their strings with (None = lexical.analyze)."""
+def parse(text: str, analyzer=None, schema=None) -> Node:
+    """analyzer: what the keyword leaves analyse their strings with (None = lexical.analyze).
+    schema: the collection's own fields (a sequence of schema.FieldSchema; None = none: a name outside
+    the reference's fields is an unknown field)."""
     if not isinstance(text, str):
         raise ValueError(f"filter expression must be a string, got {type(text).__name__}")
-    return _Parser(text, analyzer).parse()
+    return _Parser(text, analyzer, schema).parse()
 
 
 def text_leaves(node: Node) -> list:
@@ -490,6 +535,15 @@ def text_leaves(node: Node) -> list:
     return [node] if isinstance(node, (TextMatch, PhraseMatch)) else []
 
 
+def fields_of(node: Node) -> set:
+    """The names of the fields a tree's leaves read."""
+    if isinstance(node, (And, Or)):
+        return fields_of(node.a) | fields_of(node.b)
+    if isinstance(node, Not):
+        return fields_of(node.a)
+    return {node.field}
+
+
 # ---- compilation -------------------------------------------------------------------------------
 @dataclass
 class Program:
@@ -497,17 +551,34 @@ class Program:
     the code-set bitmap words and the sorted row lists the leaves point into.  text_leaves: the
     keyword leaves as (kind RF_TEXT_*, term ids, min_match), the input of rf_text_match; the
     RF_FOP_BITMAP op of leaf l carries l in `off`, and ops_ctypes turns it into the leaf's word range
-    once the caller knows how many words a leaf's bitmap has."""
+    once the caller knows how many words a leaf's bitmap has.
+    column_leaves: the leaves over the collection's own fields (schema.py), the input of rf_column_match:
+    ("codeset", field, code-set words) | ("irange", field, lo, hi) -- inclusive int64 bounds |
+    ("iset", field, sorted distinct int64 values) | ("frange", field, RF_FRANGE_* flags, lo, hi).  The
+    RF_FOP_BITMAP op of column leaf c carries c in `off` and COLUMN_LEAF in `column`; the column leaves'
+    bitmaps (column_words words each) follow the keyword leaves' from word column_base of the one
+    bitmap array the program indexes."""
     ops: list = field(default_factory=list)
     code_sets: list = field(default_factory=list)
     row_lists: list = field(default_factory=list)
     text_leaves: list = field(default_factory=list)
+    column_leaves: list = field(default_factory=list)
 
-    def ops_ctypes(self, words_per_leaf: int = 0):
-        arr = (_lib.FilterOp * len(self.ops))()
-        for i, (op, col, off, ln, flags, lo, hi) in enumerate(self.ops):
-            if op == _lib.RF_FOP_BITMAP:
+    def resolved_ops(self, words_per_leaf: int = 0, column_base: int = 0, column_words: int = 0) -> list:
+        """The op tuples as the device takes them: every RF_FOP_BITMAP leaf with its word range."""
+        out = []
+        for op, col, off, ln, flags, lo, hi in self.ops:
+            if op == _lib.RF_FOP_BITMAP and col == COLUMN_LEAF:
+                col, off, ln = 0, column_base + off * column_words, column_words
+            elif op == _lib.RF_FOP_BITMAP:
                 off, ln = off * words_per_leaf, words_per_leaf
+            out.append((op, col, off, ln, flags, lo, hi))
+        return out
+
+    def ops_ctypes(self, words_per_leaf: int = 0, column_base: int = 0, column_words: int = 0):
+        arr = (_lib.FilterOp * len(self.ops))()
+        for i, (op, col, off, ln, flags, lo, hi) in enumerate(self.resolved_ops(words_per_leaf, column_base,
+                                                                                column_words)):
             arr[i].op, arr[i].column, arr[i].off, arr[i].len = op, col, off, ln
             arr[i].flags, arr[i].lo, arr[i].hi = flags, lo, hi
         return arr
@@ -520,11 +591,38 @@ class Program:
         return m
 
 
+COLUMN_LEAF = 1   # `column` of an RF_FOP_BITMAP op in Program.ops: the bitmap of a column leaf, not of a keyword leaf
+MAX_INT_SET = _lib.RF_COLUMN_MAX_SET
+
+
+def int_interval(op: str, v) -> tuple[int, int] | None:
+    """An INT64 comparison `x op v` (v an int, or a finite float compared mathematically) as the inclusive
+    int64 interval (lo, hi) it selects; None: no int64 passes.  `!=` is the caller's (not ==)."""
+    lo, hi = INT64_MIN, INT64_MAX
+    if op == "==":
+        if v != math.floor(v):
+            return None
+        lo = hi = int(v)
+    elif op == ">":
+        lo = math.floor(v) + 1
+    elif op == ">=":
+        lo = math.ceil(v)
+    elif op == "<":
+        hi = math.ceil(v) - 1
+    else:
+        hi = math.floor(v)
+    lo, hi = max(lo, INT64_MIN), min(hi, INT64_MAX)
+    return (lo, hi) if lo <= hi else None
+
+
 class _Compiler:
-    def __init__(self, dicts: dict[str, Sequence[str]], pk_row: dict, term_id: dict | None = None):
+    def __init__(self, dicts: dict[str, Sequence[str]], pk_row: dict, term_id: dict | None = None, schema=None,
+                 extra_dicts: dict | None = None):
         self.dicts = dicts
         self.pk_row = pk_row
         self.term_id = term_id
+        self.extra = {f.name: f.dtype for f in schema or ()}
+        self.extra_dicts = extra_dicts or {}
         self.p = Program()
 
     def leaf(self, op, col=0, off=0, ln=0, flags=0, lo=0.0, hi=0.0):
@@ -540,6 +638,8 @@ class _Compiler:
             self.leaf(_lib.RF_FOP_NOT)
         elif isinstance(n, (TextMatch, PhraseMatch)):
             self.text(n)
+        elif n.field in self.extra:
+            self.column(n, self.extra[n.field])
         elif n.field in VARCHAR_FIELDS:
             self.codeset(n)
         elif n.field in DOUBLE_FIELDS:
@@ -567,6 +667,65 @@ class _Compiler:
             raise ValueError(f"filter expression: more than {_lib.RF_TEXT_MAX_LEAVES} TEXT_MATCH / PHRASE_MATCH leaves")
         self.leaf(_lib.RF_FOP_BITMAP, 0, len(self.p.text_leaves))
         self.p.text_leaves.append((kind, ids, need))
+
+    # -- leaves over the collection's own fields: one RF_FOP_BITMAP op + one entry of column_leaves each --
+    def column_leaf(self, *leaf) -> None:
+        self.leaf(_lib.RF_FOP_BITMAP, COLUMN_LEAF, len(self.p.column_leaves))
+        self.p.column_leaves.append(leaf)
+
+    def column(self, n: Node, t) -> None:
+        negate = (isinstance(n, Cmp) and n.op == "!=") or (isinstance(n, In) and n.negate)
+        if t in (DataType.VARCHAR, DataType.BOOL):
+            # against the field's dictionary (first-seen order = code), as for period
+            d = self.extra_dicts.get(n.field, ())
+            codes = [c for c, s in enumerate(d) if n.eval({n.field: s})]
+            if not codes:
+                self.leaf(_lib.RF_FOP_FALSE)
+                return
+            words = [0] * ((max(codes) >> 5) + 1)
+            for c in codes:
+                words[c >> 5] |= 1 << (c & 31)
+            self.column_leaf("codeset", n.field, words)
+            return
+        if t == DataType.INT64:
+            if isinstance(n, Cmp):
+                iv = int_interval("==" if n.op == "!=" else n.op, n.value)
+                if iv is None:
+                    self.leaf(_lib.RF_FOP_FALSE)
+                else:
+                    self.column_leaf("irange", n.field, iv[0], iv[1])
+            else:
+                # (2.5 equals no integer, 1e30 no int64)
+                vals = sorted({int(v) for v in n.values if v == math.floor(v) and INT64_MIN <= v <= INT64_MAX})
+                if len(vals) > MAX_INT_SET:
+                    raise ValueError(f"filter expression: {n.field} {'not in' if n.negate else 'in'} [...] holds "
+                                     f"{len(vals)} distinct values, at most {MAX_INT_SET} are taken")
+                if vals:
+                    self.column_leaf("iset", n.field, vals)
+                else:
+                    self.leaf(_lib.RF_FOP_FALSE)
+            if negate:
+                self.leaf(_lib.RF_FOP_NOT)
+            return
+        # DOUBLE: as primary_value, IEEE semantics
+        if isinstance(n, Cmp):
+            self.column_frange(n.field, "==" if n.op == "!=" else n.op, n.value)
+        else:
+            if not n.values:
+                self.leaf(_lib.RF_FOP_FALSE)
+            for j, v in enumerate(n.values):
+                self.column_frange(n.field, "==", v)
+                if j:
+                    self.leaf(_lib.RF_FOP_OR)
+        if negate:   # NaN != v holds: the negation of an IEEE == test
+            self.leaf(_lib.RF_FOP_NOT)
+
+    def column_frange(self, name: str, op: str, v: float) -> None:
+        inf = math.inf
+        L, H = _lib.RF_FRANGE_LO_INCL, _lib.RF_FRANGE_HI_INCL
+        lo, hi, flags = {"==": (v, v, L | H), "<": (-inf, v, L), "<=": (-inf, v, L | H),
+                         ">": (v, inf, H), ">=": (v, inf, L | H)}[op]
+        self.column_leaf("frange", name, flags, lo, hi)
 
     def codeset(self, n: Node) -> None:
         d = self.dicts.get(n.field, ())
@@ -628,13 +787,15 @@ def _hashable(k) -> bool:
 
 
 def compile_expr(node: Node | str, dicts: dict[str, Sequence[str]], pk_row: dict,
-                 term_id: dict | None = None) -> Program:
+                 term_id: dict | None = None, schema=None, extra_dicts: dict | None = None) -> Program:
     """AST (or expression text) -> Program.  dicts: VARCHAR field -> its dictionary (code i =
     dicts[field][i]); pk_row: primary key -> row number; term_id: term -> id in the lexical index's
-    dictionary (`Postings.term_id`), None = no lexical index: a keyword leaf raises ValueError."""
+    dictionary (`Postings.term_id`), None = no lexical index: a keyword leaf raises ValueError.
+    schema: the collection's own fields (schema.FieldSchema; None = none); extra_dicts: VARCHAR / BOOL
+    field of the schema -> its dictionary of values, code i = extra_dicts[field][i]."""
     if isinstance(node, str):
-        node = parse(node)
-    c = _Compiler(dicts, pk_row, term_id)
+        node = parse(node, schema=schema)
+    c = _Compiler(dicts, pk_row, term_id, schema, extra_dicts)
     c.emit(node)
     p = c.p
     if len(p.ops) > _lib.RF_FILTER_MAX_OPS:
@@ -653,6 +814,50 @@ def text_leaf_arrays(p: Program):
         arr[i].kind, arr[i].term_off, arr[i].n_terms, arr[i].min_match = kind, len(terms), len(ids), need
         terms.extend(ids)
     return arr, np.asarray(terms, dtype=np.int32).reshape(-1)
+
+
+def column_leaf_arrays(p: Program, column_ptr: dict):
+    """(rf_column_leaf array, code-set words uint32, value sets int64) of p.column_leaves.  column_ptr: field ->
+    the device address of its column."""
+    arr = (_lib.ColumnLeaf * len(p.column_leaves))()
+    words: list = []
+    values: list = []
+    for i, leaf in enumerate(p.column_leaves):
+        kind, name = leaf[0], leaf[1]
+        arr[i].column_dev = column_ptr[name]
+        if kind == "codeset":
+            arr[i].kind, arr[i].off, arr[i].len = _lib.RF_CLEAF_CODESET, len(words), len(leaf[2])
+            words.extend(leaf[2])
+        elif kind == "irange":
+            arr[i].kind, arr[i].ilo, arr[i].ihi = _lib.RF_CLEAF_I64_RANGE, leaf[2], leaf[3]
+        elif kind == "iset":
+            arr[i].kind, arr[i].off, arr[i].len = _lib.RF_CLEAF_I64_SET, len(values), len(leaf[2])
+            values.extend(leaf[2])
+        else:
+            arr[i].kind, arr[i].flags, arr[i].flo, arr[i].fhi = _lib.RF_CLEAF_F64_RANGE, leaf[2], leaf[3], leaf[4]
+    return arr, np.asarray(words, dtype=np.uint32).reshape(-1), np.asarray(values, dtype=np.int64).reshape(-1)
+
+
+def column_leaf_reference(leaf, column: np.ndarray) -> np.ndarray:
+    """What rf_column_match computes for one entry of Program.column_leaves, in numpy: bool [n].  column: the
+    field's device representation (int32 codes | int64 | fp64)."""
+    kind = leaf[0]
+    if kind == "codeset":
+        words = np.asarray(leaf[2], dtype=np.uint32)
+        c = column.astype(np.int64)
+        ok = (c >= 0) & (c < 32 * words.size)
+        w = words[np.clip(c >> 5, 0, words.size - 1)]
+        return ok & (((w >> (c & 31).astype(np.uint32)) & 1) == 1)
+    if kind == "irange":
+        return (column >= np.int64(leaf[2])) & (column <= np.int64(leaf[3])) if leaf[2] <= leaf[3] \
+            else np.zeros(column.size, bool)
+    if kind == "iset":
+        return np.isin(column, np.asarray(leaf[2], dtype=np.int64))
+    flags, lo, hi = leaf[2], leaf[3], leaf[4]
+    with np.errstate(invalid="ignore"):
+        a = column >= lo if flags & _lib.RF_FRANGE_LO_INCL else column > lo
+        b = column <= hi if flags & _lib.RF_FRANGE_HI_INCL else column < hi
+    return a & b
 
 
 def program_arrays(p: Program) -> tuple[np.ndarray, np.ndarray]:

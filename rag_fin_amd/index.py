@@ -1200,19 +1200,23 @@ class SparseIndex:
                 positions = (positions[0], positions[1][:0])
         return self._updated(dl.size, post_off, row, tf, dl, k1, b, positions), alive, post_off
 
-    def text_match(self, leaves):
+    def text_match(self, leaves, out=None):
         """Enqueue rf_text_match on the current stream; no host sync.  leaves: (kind, term ids,
         min_match) as in filter_expr.Program.text_leaves, 1..RF_TEXT_MAX_LEAVES of them.  -> the row
         bitmaps, an int32 device tensor [L, words_per_leaf] of uint32 bit patterns: bit r & 31 of word
         r >> 5 of row l = row r passes leaf l; words_per_leaf = ceil(n_rows / 32) rounded up to 4 (a
-        leaf's words start 16-byte aligned), every word written, bits past n_rows zero."""
+        leaf's words start 16-byte aligned), every word written, bits past n_rows zero.  out: a
+        contiguous int32 device tensor of that shape to write into instead of a fresh one."""
         torch = _torch()
         prog = filter_expr.Program(text_leaves=list(leaves))
         arr, terms = filter_expr.text_leaf_arrays(prog)
         L = len(arr)
         words = ((self.n_rows + 31) // 32 + 3) // 4 * 4
         terms_d = torch.from_numpy(np.concatenate([terms, np.zeros(1, dtype=np.int32)])).to(self.device)
-        out = torch.empty((L, words), dtype=torch.int32, device=self.device)
+        if out is None:
+            out = torch.empty((L, words), dtype=torch.int32, device=self.device)
+        elif tuple(out.shape) != (L, words) or out.dtype != torch.int32 or not out.is_contiguous():
+            raise ValueError(f"text_match: out must be a contiguous int32 tensor [{L}, {words}]")
         with self._lock, torch.cuda.device(self.device):
             need = self.lib.rf_text_match_workspace_bytes(self.handle, L)
             if need == 0:
@@ -1339,22 +1343,63 @@ def filter_from_mask(words, n_rows: int):
     return buf
 
 
-def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None):
+def text_words_per_leaf(n_rows: int) -> int:
+    """Words of one keyword leaf's bitmap (SparseIndex.text_match)."""
+    return ((n_rows + 31) // 32 + 3) // 4 * 4
+
+
+def column_match(device, program: "filter_expr.Program", extra_columns: dict, n_rows: int, out=None):
+    """rf_column_match of program.column_leaves, enqueued on the current stream; no host sync.
+    extra_columns: field -> its device column (int32 codes | int64 | fp64, [n_rows]).  -> the row bitmaps,
+    an int32 device tensor [C * ceil(n_rows / 32)] of uint32 bit patterns, leaf after leaf (`out`: a
+    contiguous int32 tensor of that size to write into).  One launch per RF_COLUMN_MAX_LEAVES leaves."""
+    torch = _torch()
+    lib = _lib.load_library()
+    C = len(program.column_leaves)
+    nwords = (n_rows + 31) // 32
+    ptrs = {f: (c_void_p(t.data_ptr()) if t.numel() else None) for f, t in extra_columns.items()}
+    arr, words, values = filter_expr.column_leaf_arrays(program, ptrs)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(C * nwords, dtype=torch.int32, device=device)
+        elif out.numel() != C * nwords or out.dtype != torch.int32 or not out.is_contiguous():
+            raise ValueError(f"column_match: out must be a contiguous int32 tensor of {C * nwords} words")
+        cs_d = torch.from_numpy(words.view(np.int32)).to(device) if words.size else None
+        vs_d = torch.from_numpy(values).to(device) if values.size else None
+        step = _lib.RF_COLUMN_MAX_LEAVES
+        for c0 in range(0, C, step):
+            c1 = min(C, c0 + step)
+            part = (_lib.ColumnLeaf * (c1 - c0)).from_buffer(arr, c0 * ctypes.sizeof(_lib.ColumnLeaf))
+            _lib.check(lib.rf_column_match(part, c1 - c0, _ptr(cs_d), _ptr(vs_d), n_rows,
+                                           c_void_p(out.data_ptr() + 4 * c0 * nwords) if nwords else None,
+                                           _lib.current_stream_ptr()))
+    # (cs_d / vs_d may be freed now: the caching allocator reuses their memory in stream order)
+    return out
+
+
+def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None, column_base: int = 0):
     """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
     rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors
     {period, chunk_type, statement_type codes int32 [n_rows], primary_value fp64 [n_rows]}.
     bitmaps: SparseIndex.text_match(program.text_leaves), enqueued on the same stream, when the
-    program has keyword leaves (rf_filter_eval_bitmaps)."""
+    program has keyword leaves (rf_filter_eval_bitmaps).  With column leaves (program.column_leaves),
+    bitmaps is the one flat int32 array that holds the keyword leaves' bitmaps (text_words_per_leaf(n_rows)
+    words each) and, from word column_base, the column leaves' (column_match; ceil(n_rows / 32) words each)."""
     torch = _torch()
     lib = _lib.load_library()
     cs, rl = filter_expr.program_arrays(program)
+    if program.column_leaves:
+        ops = program.ops_ctypes(text_words_per_leaf(n_rows), column_base, (n_rows + 31) // 32)
+        if column_base + len(program.column_leaves) * ((n_rows + 31) // 32) > 0x7FFFFFFF:
+            raise ValueError("filter expression: the leaves' bitmaps do not fit int32 word offsets")
+    else:
+        ops = program.ops_ctypes(0 if bitmaps is None else int(bitmaps.shape[1]))
     with torch.cuda.device(device):
         buf = torch.empty(lib.rf_filter_bytes(n_rows), dtype=torch.uint8, device=device)
         cs_d = torch.from_numpy(cs.view(np.int32)).to(device) if cs.size else None
         rl_d = torch.from_numpy(rl.view(np.int32)).to(device) if rl.size else None
         ptrs = (c_void_p * _lib.RF_FILTER_COLUMNS)(*[c_void_p(t.data_ptr()) if t is not None and t.numel() else None
                                                      for t in columns])
-        ops = program.ops_ctypes(0 if bitmaps is None else int(bitmaps.shape[1]))
         _lib.check(lib.rf_filter_eval_bitmaps(ops, len(ops), c_void_p(cs_d.data_ptr()) if cs_d is not None else None,
                                               c_void_p(rl_d.data_ptr()) if rl_d is not None else None, _ptr(bitmaps),
                                               ptrs, n_rows, c_void_p(buf.data_ptr()), _lib.current_stream_ptr()))

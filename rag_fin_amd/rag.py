@@ -27,10 +27,14 @@ DEFAULT_PROMPT = "Question: {question}\n\nRetrieved contexts:\n{context}\n\nAnsw
 
 
 class VectorRAG:
+    # (class-level defaults: the context dicts keep exactly the reference's keys)
+    extra_output_fields: tuple = ()
+    output_fields = OUTPUT_FIELDS
+
     def __init__(self, gemini_api_key: str | None = None, collection_name: str = "fin_chunks", *,
                  embedder=None, store=None, generator: Callable[[str], str] | None = None,
                  llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None, reader=None,
-                 sparse_encoder=None, late_encoder=None):
+                 sparse_encoder=None, late_encoder=None, extra_output_fields=None):
         """embedder: .encode(list[str]) -> [n, dim] (rag_fin_amd.embedder.Embedder);
         store: rag_fin_amd.store.CorpusStore.  `gemini_api_key` is accepted for
         signature compatibility and only handed to `generator` factories upstream.
@@ -44,7 +48,9 @@ class VectorRAG:
         search(..., hybrid=True, lexical="learned" | "both").
         late_encoder: .encode(list[str], is_query=) -> one [n_tok, D] matrix per text (rag_fin_amd.late_interaction.
         ColBERT): declared on the store as its late-interaction field ("token_embeddings"), the second stage of
-        search(..., rerank=True, rerank_with="late")."""
+        search(..., rerank=True, rerank_with="late").
+        extra_output_fields: names of the store's own fields (CorpusStore(fields=...)) whose values are added to
+        the context dicts under their names; by default the keys stay exactly the reference's."""
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
@@ -53,6 +59,14 @@ class VectorRAG:
         self.reader = reader
         self.sparse_encoder = sparse_encoder
         self.collection = store
+        if extra_output_fields:
+            own = [f.name for f in getattr(store, "schema", ())]
+            for name in extra_output_fields:
+                if name not in own:
+                    raise ValueError(f"extra_output_fields: {name!r} is not a field the store declares"
+                                     + (f" ({', '.join(own)})" if own else ""))
+            self.extra_output_fields = tuple(dict.fromkeys(extra_output_fields))
+            self.output_fields = OUTPUT_FIELDS + list(self.extra_output_fields)
         if sparse_encoder is not None:
             store.create_index("sparse_embedding", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "IP"},
                                encoder=sparse_encoder)
@@ -69,11 +83,11 @@ class VectorRAG:
                     self.collection.num_entities)
 
     # -- retrieval ---------------------------------------------------------------------
-    @staticmethod
-    def _contexts(hits) -> list[dict]:
+    def _contexts(self, hits) -> list[dict]:
         return [{"rank": i + 1, "text": h.entity.text, "period": h.entity.period,
                  "chunk_type": h.entity.chunk_type, "statement_type": h.entity.statement_type,
-                 "primary_value": h.entity.primary_value, "score": float(h.score)}
+                 "primary_value": h.entity.primary_value, "score": float(h.score),
+                 **{name: h.entity.get(name) for name in self.extra_output_fields}}
                 for i, h in enumerate(hits)]
 
     @staticmethod
@@ -150,7 +164,7 @@ class VectorRAG:
             return self._contexts(self._search_hybrid([query], top_k, top_k, expr, fetch_k, lexical)[0])
         q = self._embed([query])
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
-                                         expr=expr, output_fields=OUTPUT_FIELDS,
+                                         expr=expr, output_fields=self.output_fields,
                                          **self._group_args(group_by, group_size),
                                          **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset), **ranker)
         return self._contexts(results[0])
@@ -236,7 +250,7 @@ class VectorRAG:
             reqs.append(AnnSearchRequest(list(queries), "sparse", {"metric_type": "BM25"}, fk, expr))
         if lexical in ("learned", "both"):
             reqs.append(AnnSearchRequest(list(queries), "sparse_embedding", {"metric_type": "IP"}, fk, expr))
-        return self.collection.hybrid_search(reqs, RRFRanker(), limit, output_fields=OUTPUT_FIELDS)
+        return self.collection.hybrid_search(reqs, RRFRanker(), limit, output_fields=self.output_fields)
 
     def _search_reranked(self, queries, top_k, expr, min_score, max_score, group_by, mmr_lambda, fetch_k,
                          hybrid: bool = False, lexical: str = "bm25", rerank_with: str = "cross"):
@@ -254,7 +268,7 @@ class VectorRAG:
         else:
             q = self._embed(list(queries))
             results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
-                                             expr=expr, output_fields=OUTPUT_FIELDS)
+                                             expr=expr, output_fields=self.output_fields)
         hits = [list(r) for r in results]
         if rerank_with == "late":
             # every query's candidates in ONE candidate-mode MaxSim call on the stored token vectors
@@ -318,7 +332,7 @@ class VectorRAG:
             return [self._contexts(r) for r in self._search_hybrid(list(queries), top_k, top_k, expr, fetch_k, lexical)]
         q = self._embed(list(queries))
         results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
-                                         expr=expr, output_fields=OUTPUT_FIELDS,
+                                         expr=expr, output_fields=self.output_fields,
                                          **self._group_args(group_by, group_size),
                                          **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset), **ranker)
         return [self._contexts(r) for r in results]

@@ -1,0 +1,140 @@
+"""User-defined scalar fields of a collection: `CorpusStore(..., fields=[FieldSchema(...), ...])`.
+
+The reference's collection has seven fields ("chunking_storing (1).py":14-22); a pymilvus user declares
+further `FieldSchema`s of their own, and `DataType` / `FieldSchema` here take pymilvus' shape for the four
+scalar types this store serves: VARCHAR, INT64, DOUBLE and BOOL.  ARRAY, JSON, nullable and dynamic fields
+are not offered.
+"""
+from __future__ import annotations
+
+import enum
+import numbers
+import re
+from typing import Any, Iterable, Sequence
+
+import numpy as np
+
+MAX_FIELDS = 32
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+# the reference's seven fields, the vector fields this store derives, and the words of the expression grammar
+REFERENCE_FIELDS = ("id", "text", "embedding", "period", "chunk_type", "statement_type", "primary_value")
+RESERVED = REFERENCE_FIELDS + ("sparse", "sparse_embedding", "token_embeddings")
+_KEYWORDS = ("and", "or", "not", "in", "like", "true", "false", "text_match", "phrase_match")
+_IDENT = re.compile(r"^[A-Za-z_][A-Za-z0-9_]*$")
+
+
+class DataType(enum.IntEnum):
+    """pymilvus' numbering, for the types offered."""
+    BOOL = 1
+    INT64 = 5
+    DOUBLE = 11
+    VARCHAR = 21
+
+
+class FieldSchema:
+    """One extra scalar field: its name (an identifier), its DataType and, optionally, the value a row takes
+    when an insert does not supply the column."""
+
+    def __init__(self, name: str, dtype, default: Any = None, **_ignored):
+        if not isinstance(name, str) or not _IDENT.match(name):
+            raise ValueError(f"field name {name!r} is not an identifier")
+        if name.lower() in _KEYWORDS:
+            raise ValueError(f"field name {name!r} is a word of the expression grammar")
+        try:
+            dtype = DataType[dtype.upper()] if isinstance(dtype, str) else DataType(int(dtype))
+        except (KeyError, ValueError, TypeError):
+            raise ValueError(f"field {name!r}: dtype {dtype!r} is not supported (VARCHAR, INT64, DOUBLE or BOOL; "
+                             "ARRAY, JSON and vector fields cannot be declared)") from None
+        self.name = name
+        self.dtype = dtype
+        self.default = None if default is None else check_value(self, default, "default")
+
+    def to_dict(self) -> dict:
+        d = {"name": self.name, "dtype": self.dtype.name}
+        if self.default is not None:
+            d["default"] = self.default   # (json spells NaN / Infinity, as it does for primary_value)
+        return d
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "FieldSchema":
+        default = d.get("default")
+        if default is not None and DataType[d["dtype"]] == DataType.DOUBLE:
+            default = float(default)
+        return cls(d["name"], d["dtype"], default)
+
+    def __eq__(self, other):
+        return isinstance(other, FieldSchema) and self.to_dict() == other.to_dict()
+
+    def __repr__(self):
+        return f"FieldSchema({self.name!r}, DataType.{self.dtype.name}" + \
+            ("" if self.default is None else f", default={self.default!r}") + ")"
+
+
+def check_value(field: FieldSchema, v, where: str = "value"):
+    """`v` as the field stores it (str / int / float / bool), or ValueError."""
+    t = field.dtype
+    if t == DataType.VARCHAR:
+        if isinstance(v, str):
+            return v
+    elif t == DataType.BOOL:
+        if isinstance(v, (bool, np.bool_)):
+            return bool(v)
+    elif t == DataType.INT64:
+        if isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)):
+            if not INT64_MIN <= int(v) <= INT64_MAX:
+                raise ValueError(f"field {field.name!r}: {where} {v!r} is outside the int64 range")
+            return int(v)
+    else:
+        if isinstance(v, (numbers.Real, np.floating, np.integer)) and not isinstance(v, (bool, np.bool_)):
+            return float(v)
+    raise ValueError(f"field {field.name!r} is {t.name}, {where} {v!r} ({type(v).__name__}) is not")
+
+
+def check_fields(fields: Iterable | None) -> tuple:
+    """The declared extra fields as a tuple of FieldSchema, or ValueError: at most MAX_FIELDS, and no name that
+    collides with the reference's fields, the derived vector fields or another declared field."""
+    out = []
+    for f in fields or ():
+        if isinstance(f, dict):
+            f = FieldSchema.from_dict(f)
+        if not isinstance(f, FieldSchema):
+            raise ValueError(f"fields takes FieldSchema objects, got {type(f).__name__}")
+        if f.name in RESERVED:
+            raise ValueError(f"field name {f.name!r} collides with a field of the collection")
+        if any(f.name == g.name for g in out):
+            raise ValueError(f"field name {f.name!r} is declared twice")
+        out.append(f)
+    if len(out) > MAX_FIELDS:
+        raise ValueError(f"{len(out)} extra fields declared, at most {MAX_FIELDS} are taken")
+    return tuple(out)
+
+
+def check_columns(fields: Sequence[FieldSchema], extra: dict | None, n: int, what: str = "insert") -> list:
+    """The extra columns of a batch of n rows, in schema order and as stored; a column that is not supplied is
+    filled with the field's default.  ValueError: an unknown name, a length other than n, a value of the wrong
+    type, a missing column of a field without a default.  Nothing is changed."""
+    extra = dict(extra or {})
+    names = [f.name for f in fields]
+    for name in extra:
+        if name not in names:
+            raise ValueError(f"{what}: unknown extra field {name!r}" + (f" (declared: {', '.join(names)})" if names else
+                                                                       " (the collection declares none)"))
+    cols = []
+    for f in fields:
+        if f.name not in extra or extra[f.name] is None:
+            if f.default is None:
+                raise ValueError(f"{what}: field {f.name!r} has no default and no column was supplied")
+            cols.append([f.default] * n)
+            continue
+        col = list(extra[f.name])
+        if len(col) != n:
+            raise ValueError(f"{what} columns differ in length (field {f.name!r}: {len(col)} values for {n} rows)")
+        cols.append([check_value(f, v) for v in col])
+    return cols
+
+
+def column_from_json(field: FieldSchema, values) -> list:
+    if field.dtype == DataType.DOUBLE:
+        return [float(v) for v in values]
+    return [check_value(field, v) for v in values]

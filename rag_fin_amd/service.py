@@ -31,17 +31,46 @@ import os
 from . import chunker
 
 
-def ingest(store, embedder, chunks, upsert: bool = False) -> int:
+def extra_columns(fields, chunks, values=None) -> dict:
+    """The columns of a store's own fields for a list of chunks.  values: {field name: a constant, or a
+    function of the chunk dict}; a field without an entry is read from the chunk dicts when every chunk holds
+    its name, and is otherwise left to its default.  E.g. {"bank": "ICICI", "fiscal_year": lambda c:
+    2000 + int(c["period"][-2:])}."""
+    values = dict(values or {})
+    names = [f.name for f in fields]
+    for name in values:
+        if name not in names:
+            raise ValueError(f"field_values: {name!r} is not a declared field" + (f" ({', '.join(names)})" if names else ""))
+    out = {}
+    for name in names:
+        if name in values:
+            v = values[name]
+            out[name] = [v(c) for c in chunks] if callable(v) else [v] * len(chunks)
+        elif chunks and all(name in c for c in chunks):
+            out[name] = [c[name] for c in chunks]
+    return out
+
+
+def ingest(store, embedder, chunks, upsert: bool = False, field_values: dict | None = None) -> int:
     """The reference's encode + insert + flush + load
     ("chunking_storing (1).py":377-397) on the GPU: texts are embedded by rf_encode
     and the fp16 rows go straight into the HBM corpus (no host round trip).
     upsert=True: chunks whose id is already stored replace the stored rows (a restated
     quarter is re-ingested in place of dropping the collection); otherwise an existing id
-    raises ValueError."""
+    raises ValueError.
+    field_values: the values of the store's own fields (CorpusStore(fields=...)), as extra_columns takes them."""
     if not chunks:
         return 0
     emb = embedder.encode_to_device([c["text"] for c in chunks])
     cols = chunker.insert_columns(chunks, emb)
+    fields = getattr(store, "schema", ())
+    if fields or field_values:
+        own = extra_columns(fields, chunks, field_values)
+        missing = [f.name for f in fields if f.name not in own and f.default is None]
+        if missing:
+            raise ValueError(f"ingest: no value for the field(s) {', '.join(missing)} (field_values, a key of the chunk "
+                             "dicts, or a default)")
+        cols = cols + [own.get(f.name) if f.name in own else [f.default] * len(chunks) for f in fields]
     n = store.upsert(cols).upsert_count if upsert else store.insert(cols)
     store.flush()
     store.load()
@@ -79,19 +108,22 @@ def _load_late_encoder(late_dir, device):
 def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
               hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None,
-              sparse_dir: str | None = None, late_dir: str | None = None):
+              sparse_dir: str | None = None, late_dir: str | None = None, fields=None, field_values: dict | None = None,
+              extra_output_fields=None):
     """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
     can run; its posting lists are built by the first such search.
     sparse_dir: a local SPLADE checkpoint: the learned sparse field is declared on the store (VectorRAG does
     it), its vectors are encoded by the first search(..., hybrid=True, lexical="learned" | "both").
     late_dir: a local ColBERT checkpoint: the late-interaction field is declared on the store (VectorRAG does it),
-    its token vectors are encoded by the first search(..., rerank=True, rerank_with="late")."""
+    its token vectors are encoded by the first search(..., rerank=True, rerank_with="late").
+    fields: FieldSchema objects of the collection's own scalar fields (rag_fin_amd.schema); field_values: their
+    values per chunk, as extra_columns takes them; extra_output_fields: those of them the context dicts carry."""
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
     embedder = Embedder.from_local(model_dir, device=device)
-    store = CorpusStore(collection_name, dim=embedder.dim, device=device)
-    ingest(store, embedder, chunker.build_all_chunks(data_dir))
+    store = CorpusStore(collection_name, dim=embedder.dim, device=device, **({"fields": fields} if fields else {}))
+    ingest(store, embedder, chunker.build_all_chunks(data_dir), **({"field_values": field_values} if field_values else {}))
     if hybrid:
         store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     sparse = _load_sparse_encoder(sparse_dir, device)
@@ -99,7 +131,8 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
                      reranker=_load_reranker(reranker_dir, device), reader=_load_reader(reader_dir, device, reader_doc_stride),
                      **({} if sparse is None else {"sparse_encoder": sparse}),
-                     **({} if late is None else {"late_encoder": late}))
+                     **({} if late is None else {"late_encoder": late}),
+                     **({"extra_output_fields": extra_output_fields} if extra_output_fields else {}))
 
 
 def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:

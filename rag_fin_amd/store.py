@@ -38,11 +38,13 @@ import numpy as np
 from . import _lib
 from . import filter_expr
 from . import lexical
+from . import schema as schema_
+from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, eval_filter, filter_from_mask,  # noqa: F401
-                    filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted, plan_filter_chunks,
-                    require_gpu, rerun_flagged, words_mask)
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, column_match, eval_filter,  # noqa: F401
+                    filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
+                    plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
 from .ranker import BoostRanker, check_rankers, class_weights  # noqa: F401
 
 
@@ -196,6 +198,49 @@ class _DeviceColumns:
 
     def tensors(self):
         return [self.codes[f] for f in filter_expr.VARCHAR_FIELDS] + [self.values]
+
+
+class _ExtraColumn:
+    """The device mirror of one column of a collection's own fields (schema.py), synced lazily from the host
+    list like _DeviceColumns: int64 for INT64, fp64 for DOUBLE, and int32 codes into an append-only dictionary
+    (first-seen order) for VARCHAR and BOOL -- and for an INT64 field that is grouped by (coded=True)."""
+
+    def __init__(self, device, dtype, coded: bool = False):
+        torch = _torch()
+        self.device = device
+        self.coded = coded or dtype in (DataType.VARCHAR, DataType.BOOL)
+        self.np_dtype = np.int32 if self.coded else (np.int64 if dtype == DataType.INT64 else np.float64)
+        self.dict: list = []
+        self._code: dict = {}
+        self.data = torch.empty(0, dtype=getattr(torch, np.dtype(self.np_dtype).name), device=device)
+        self.n = 0
+
+    def sync(self, values: list, n: int) -> None:
+        torch = _torch()
+        if n < self.n:   # a shorter collection: re-encode from row 0 (the dictionary stays)
+            self.data = self.data[:0]
+            self.n = 0
+        if n == self.n:
+            return
+        lo = self.n
+        if self.coded:
+            d, code = self.dict, self._code
+            enc = np.empty(n - lo, dtype=np.int32)
+            for j, v in enumerate(values[lo:n]):
+                c = code.get(v)
+                if c is None:
+                    c = code[v] = len(d)
+                    d.append(v)
+                enc[j] = c
+        else:
+            enc = np.asarray(values[lo:n], dtype=self.np_dtype)
+        self.data = torch.cat([self.data, torch.from_numpy(enc).to(self.device)])
+        self.n = n
+
+    def compact(self, k) -> None:
+        """Keep rows k (ascending, an int64 device tensor) of a mirror synced to the whole collection."""
+        self.data = self.data.index_select(0, k)
+        self.n = int(k.numel())
 
 
 class _RWLock:
@@ -406,8 +451,18 @@ _ID_IN = re.compile(r"^\s*id\s+in\s+\[(.*)\]\s*$", re.S)
 class CorpusStore:
     """Drop-in for the reference's `Collection("fin_chunks")` on this path."""
 
+    # the collection's own fields (schema.py) and their device mirrors.  Class-level defaults: a subclass
+    # whose __init__ does not call this one is a store without extra fields.
+    schema: tuple = ()
+    _xcols = None        # {(field, coded): _ExtraColumn}, built by the first filter / grouping that reads the field
+
     def __init__(self, name: str = "fin_chunks", dim: int = 384, capacity: int = 4096,
-                 device=None, metric_type: str = "COSINE", index=None):
+                 device=None, metric_type: str = "COSINE", index=None, fields=None):
+        """fields: FieldSchema objects (rag_fin_amd.schema) of extra scalar fields next to the reference's
+        seven: VARCHAR, INT64, DOUBLE or BOOL, at most 32.  They are inserted (add(extra=), the columns after
+        primary_value of insert / upsert), filtered on in expr, grouped by, returned as output fields, and
+        saved and loaded like `period`."""
+        self.schema = schema_.check_fields(fields)
         self.name = name
         self.dim = dim
         self.metric_type = metric_type.upper()
@@ -415,8 +470,9 @@ class CorpusStore:
             raise ValueError("metric_type must be COSINE or IP")
         # `index`: an already-built GpuIndex (tests of the sharded store pass a CPU double)
         self.index = index if index is not None else GpuIndex(dim, capacity, device)
-        self.columns: dict[str, list] = {f: [] for f in SCALAR_FIELDS}
+        self.columns: dict[str, list] = {f: [] for f in SCALAR_FIELDS + tuple(f.name for f in self.schema)}
         self._pk_row: dict[Any, int] = {}
+        self._xcols = None
         self._dcols = None                  # _DeviceColumns, built by the first filtered call
         self._filter_lock = threading.Lock()
         # search / query / save read; add / delete / upsert / drop write.  A search hands out row
@@ -476,6 +532,7 @@ class CorpusStore:
                 col.clear()
             self._pk_row.clear()
             self._dcols = None
+            self._xcols = None
             self._sparse = None
             self._forget_lexical()
             self._learned_rows = None
@@ -699,11 +756,14 @@ class CorpusStore:
     # -- ingest ------------------------------------------------------------------
     def add(self, ids: Sequence, texts: Sequence[str], embeddings, periods: Sequence[str],
             chunk_types: Sequence[str], statement_types: Sequence[str],
-            primary_values: Sequence[float]) -> int:
+            primary_values: Sequence[float], extra: dict | None = None) -> int:
+        """extra: {field name: column} for the collection's own fields (schema.py); a field that is not given
+        takes its default, and has to have one."""
         cols = (texts, periods, chunk_types, statement_types, primary_values)
         with self._rw.write():
+            xcols = schema_.check_columns(self.schema, extra, len(ids), "insert")   # before anything changes
             self._store_vectors(self._check_batch(ids, cols, embeddings, len(ids), "insert"))
-            self._append_rows(ids, cols)
+            self._append_rows(ids, cols, xcols)
         return len(ids)
 
     def _check_batch(self, ids, cols, embeddings, n_vec_rows: int, what: str):
@@ -741,8 +801,9 @@ class CorpusStore:
             self._grow(need)
         self.index.add(vec)
 
-    def _append_rows(self, ids, cols) -> None:
-        """The host side of an append: the pk map and the six scalar columns."""
+    def _append_rows(self, ids, cols, xcols=()) -> None:
+        """The host side of an append: the pk map, the six scalar columns and the checked extra columns
+        (schema.check_columns: in schema order)."""
         texts, periods, chunk_types, statement_types, primary_values = cols
         self._sparse = None   # the lexical index is brought up to date by the next BM25 search (DESIGN §4.4k)
         self._log_lexical("append", list(texts))
@@ -757,6 +818,18 @@ class CorpusStore:
         self.columns["chunk_type"].extend(chunk_types)
         self.columns["statement_type"].extend(statement_types)
         self.columns["primary_value"].extend(float(v) for v in primary_values)
+        for f, col in zip(self.schema, xcols):
+            self.columns[f.name].extend(col)
+
+    def _split_extra(self, data, what: str):
+        """Column-major `data` of 7 + len(schema) columns -> (the reference's seven, {field: column}): the
+        collection's own fields follow primary_value in schema order."""
+        if not self.schema:
+            return data, None
+        if len(data) != 7 + len(self.schema):
+            raise ValueError(f"{what} expects {7 + len(self.schema)} columns: id, text, embedding, period, chunk_type, "
+                             f"statement_type, primary_value, {', '.join(f.name for f in self.schema)}")
+        return list(data[:7]), {f.name: col for f, col in zip(self.schema, data[7:])}
 
     @staticmethod
     def _split_columns(data, what: str):
@@ -769,9 +842,11 @@ class CorpusStore:
 
     def insert(self, data: Sequence[Sequence]) -> int:
         """Column-major insert in the reference's order
-        [id, text, embedding, period, chunk_type, statement_type, primary_value]."""
+        [id, text, embedding, period, chunk_type, statement_type, primary_value], then the collection's own
+        fields in schema order."""
+        data, extra = self._split_extra(data, "insert")
         ids, cols, emb = self._split_columns(data, "insert")
-        return self.add(ids, cols[0], emb, *cols[1:])
+        return self.add(ids, cols[0], emb, *cols[1:], **({} if extra is None else {"extra": extra}))
 
     # -- mutation: Collection.delete(expr) / Collection.upsert(data) -----------------------
     # Deletes compact eagerly: the index, the host columns, the pk map and the device filter
@@ -791,13 +866,15 @@ class CorpusStore:
         row is appended in the given order: a replaced row moves to the END of the collection (so
         on an exact score tie -- ranked by score desc, then row asc -- it ranks after older rows).
         Duplicate keys inside one batch raise ValueError, as insert does."""
+        data, extra = self._split_extra(data, "upsert")
         ids, cols, emb = self._split_columns(data, "upsert")
         ids = list(ids)
         with self._rw.write():
+            xcols = schema_.check_columns(self.schema, extra, len(ids), "upsert")
             vec = self._check_batch(ids, cols, emb, len(ids), "upsert")   # before any row goes
             self._delete_mask(self._pk_mask(ids))
             self._store_vectors(vec)
-            self._append_rows(ids, cols)
+            self._append_rows(ids, cols, xcols)
         return MutationResult(ids, insert_count=len(ids), upsert_count=len(ids))
 
     def _match_mask(self, expr: str) -> np.ndarray:
@@ -805,9 +882,9 @@ class CorpusStore:
         n = self.num_entities
         if n == 0:
             with self._filter_lock:   # still reject a bad expression
-                filter_expr.compile_expr(filter_expr.parse(expr, self.analyzer),
+                filter_expr.compile_expr(filter_expr.parse(expr, self.analyzer, self.schema),
                                          {f: [] for f in filter_expr.VARCHAR_FIELDS}, {},
-                                         None if self._sparse_params is None else {})
+                                         None if self._sparse_params is None else {}, self.schema, {})
             return np.zeros(0, dtype=bool)
         return filter_mask_bits(self.build_filter(expr), n)
 
@@ -835,7 +912,7 @@ class CorpusStore:
         self._mutations += 1
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
-        for f in SCALAR_FIELDS:
+        for f in list(self.columns):
             self.columns[f] = list(itertools.compress(self.columns[f], sel))
         self._pk_row = dict(zip(self.columns["id"], range(keep.size)))
         with self._filter_lock:
@@ -844,6 +921,13 @@ class CorpusStore:
                     self._dcols.compact(keep)
                 else:   # not synced to the old rows: the next filtered call re-encodes from row 0
                     self._dcols = None
+            if self._xcols:
+                synced = {key: c for key, c in self._xcols.items() if c.n == n_old}   # the others: as above
+                if synced:
+                    k = _torch().from_numpy(np.ascontiguousarray(keep, dtype=np.int64)).to(self.index.device)
+                    for c in synced.values():
+                        c.compact(k)
+                self._xcols = synced
         return MutationResult(pks, delete_count=len(pks))
 
     def _compact_index(self, keep_mask: np.ndarray, keep: np.ndarray) -> None:
@@ -878,8 +962,29 @@ class CorpusStore:
 
     GROUP_BY_FIELDS = filter_expr.VARCHAR_FIELDS   # period, chunk_type, statement_type ("id": the plain search)
 
+    def _extra_column(self, field: FieldSchema, coded: bool = False) -> _ExtraColumn:
+        """The synced device mirror of one of the collection's own fields.  Caller holds `_filter_lock`."""
+        if self._xcols is None:
+            self._xcols = {}
+        key = (field.name, coded or field.dtype in (DataType.VARCHAR, DataType.BOOL))   # (those are coded anyway)
+        col = self._xcols.get(key)
+        if col is None:
+            col = self._xcols[key] = _ExtraColumn(self.index.device, field.dtype, coded)
+        col.sync(self.columns[field.name], self.num_entities)
+        return col
+
+    def _field(self, name: str):
+        """The FieldSchema of one of the collection's own fields, or None."""
+        return next((f for f in self.schema if f.name == name), None)
+
     def _group_codes(self, field: str):
-        """(codes int32 [n] on the device, n_codes) of a group-by field, from the device mirror."""
+        """(codes int32 [n] on the device, n_codes) of a group-by field, from the device mirror.  An INT64
+        field of the collection's own is dictionary-coded on first use."""
+        own = self._field(field)
+        if own is not None:
+            with self._filter_lock:
+                col = self._extra_column(own, coded=True)
+                return col.data.contiguous(), len(col.dict)
         with self._filter_lock:
             if self._dcols is None:
                 self._dcols = _DeviceColumns(self.index.device)
@@ -1192,7 +1297,10 @@ class CorpusStore:
 
     def _check_group_by(self, field, group_size, limit, param):
         """-> (field, group_size), or None for "id" (every row its own group: the plain search)."""
-        if field != "id" and field not in self.GROUP_BY_FIELDS:
+        own = self._field(field)
+        if own is not None and own.dtype == DataType.DOUBLE:
+            raise ValueError(f"group_by_field {field!r}: a DOUBLE field cannot be grouped by")
+        if field != "id" and field not in self.GROUP_BY_FIELDS and own is None:
             raise ValueError(f"group_by_field {field!r}: only {', '.join(self.GROUP_BY_FIELDS)} (or id) can be grouped by")
         if isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or group_size < 1:
             raise ValueError(f"group_size must be an integer >= 1, got {group_size!r}")
@@ -1744,6 +1852,8 @@ class CorpusStore:
         """columns.json, written to a temporary file and moved into place."""
         meta = {"format": FORMAT, "name": self.name, "dim": self.dim,
                 "metric_type": self.metric_type, "n": n, "columns": self.columns}
+        if self.schema:   # (directories of a store without fields of its own stay exactly as before)
+            meta["fields"] = [f.to_dict() for f in self.schema]
         if self.index_type != "FLAT":   # FLAT directories stay exactly as before
             meta["index_type"] = self.index_type
         if self._sparse_params is not None:   # (and so do directories without a lexical index)
@@ -1780,9 +1890,11 @@ class CorpusStore:
     def _adopt_columns(self, path: str, meta: dict, n: int) -> None:
         """The scalar columns of a loaded columns.json become this store's; the pk map is rebuilt."""
         cols = meta["columns"]
-        if any(len(cols[f]) != n for f in SCALAR_FIELDS):
+        if any(len(cols[f]) != n for f in SCALAR_FIELDS) or any(len(cols.get(f.name, ())) != n for f in self.schema):
             raise ValueError(f"{path}: column lengths do not match n={n}")
         self.columns = {f: list(cols[f]) for f in SCALAR_FIELDS}
+        for f in self.schema:
+            self.columns[f.name] = schema_.column_from_json(f, cols[f.name])
         self._pk_row = {pk: i for i, pk in enumerate(self.columns["id"])}
 
     @classmethod
@@ -1792,7 +1904,8 @@ class CorpusStore:
         in host RAM)."""
         meta, n, dim = cls._read_meta(path)
         st = cls(meta["name"], dim=dim, capacity=max(capacity or 0, n, 1), device=device,
-                 metric_type=meta["metric_type"])
+                 metric_type=meta["metric_type"],
+                 **({"fields": [FieldSchema.from_dict(d) for d in meta["fields"]]} if meta.get("fields") else {}))
         st._load_rows(path, n, 0, n, chunk_rows)
         st._adopt_columns(path, meta, n)
         itype = meta.get("index_type", "FLAT")   # a missing key means FLAT
@@ -1821,16 +1934,28 @@ class CorpusStore:
         holds the WRITE side, so nothing here may ask for it again), then `_sparse_lock` (inside
         _sparse_index and _text_index, released before the next), then `_filter_lock`, then the
         SparseIndex's own `_lock` (inside text_match).  No path takes them the other way round."""
-        node = filter_expr.parse(expr, self.analyzer)
+        node = filter_expr.parse(expr, self.analyzer, self.schema)
         term_id, sp = self._text_index(filter_expr.text_leaves(node))
         with self._filter_lock:
             n = self.num_entities
             if self._dcols is None:
                 self._dcols = _DeviceColumns(self.index.device)
             self._dcols.sync(self.columns, n)
-            prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row, term_id)
-            bitmaps = sp.text_match(prog.text_leaves) if prog.text_leaves else None
-            return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps)
+            own = {f.name: self._extra_column(f) for f in self.schema if f.name in filter_expr.fields_of(node)}
+            prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row, term_id, self.schema,
+                                            {name: c.dict for name, c in own.items() if c.coded})
+            if not prog.column_leaves:
+                bitmaps = sp.text_match(prog.text_leaves) if prog.text_leaves else None
+                return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps)
+            # leaves over the collection's own fields: rf_column_match writes their row bitmaps behind the
+            # keyword leaves', into the one array the program's RF_FOP_BITMAP leaves index (DESIGN §4.4o)
+            T, C = len(prog.text_leaves), len(prog.column_leaves)
+            base, nwords = T * text_words_per_leaf(n), (n + 31) // 32
+            bitmaps = _torch().empty(base + C * nwords, dtype=_torch().int32, device=self.index.device)
+            if T:
+                sp.text_match(prog.text_leaves, out=bitmaps[:base].view(T, -1))
+            column_match(self.index.device, prog, {name: c.data for name, c in own.items()}, n, out=bitmaps[base:])
+            return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps, column_base=base)
 
     def _text_index(self, leaves):
         """What the keyword leaves of a filter need -> (term -> id map, SparseIndex), (None, None)
