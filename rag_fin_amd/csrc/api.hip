@@ -254,7 +254,7 @@ struct rf_variant {
   const rf_band* band;
   const rf_after* after;
   const rf_multi* multi;
-  bool coarse;   // SQ8 timed as the four FLAT stages: quantize + sample | threshold | emit + refine | merge
+  bool coarse;   // SQ8 timed as the four FLAT stages: sample | threshold | quantize + emit + refine | merge
 };
 
 static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
@@ -279,7 +279,7 @@ static int time_stages(int marks, float* stage_ms, F run) {
 
 // One sweep of nb <= RF_QWIDE queries: (SQ8: quantize the queries ->) sample -> threshold -> emit ->
 // (SQ8: prune + refine ->) merge.  ev: nullable; one event before the first stage and one after each
-// (5; SQ8 unless v.coarse: 7).
+// (5; SQ8: 7, or 6 with v.coarse, which times emit + refine as one).
 static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, int nb, int k, int64_t id_base,
                  const rf_workspace& ws, const rf_out& o, hipStream_t st, hipEvent_t* ev) {
   const int JB = nb <= 32 ? 1 : 2;
@@ -291,7 +291,7 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   int rc = mark(ev, &n_ev, st);
   if (v.sq8) {
     if (rc == RF_OK) rc = rf_launch_sq8_queries(ix, qc, nb, *v.sq8, st);
-    if (rc == RF_OK && !v.coarse) rc = mark(ev, &n_ev, st);
+    if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   }
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS && v.band) rc = rf_launch_band_eps(ix, qc, nb, ws, st);
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
@@ -341,10 +341,22 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
                       });
   bool wide;
   const int nb = chunk_width(ix, B, k, widen, &wide);   // the first sweep the batch would run
-  return time_stages(sq && !coarse ? 7 : 5, stage_ms, [&](hipEvent_t* ev) {
+  // The four coarse stages of the shadow chain: `sample` and `threshold` are the kernels the fp16 chain
+  // runs under those names, `emit` is everything that stands in the fp16 emit's place -- the query
+  // quantization (only the int8 sweep reads q^), the int8 sweep and the prune + refine.
+  float t[6];
+  const bool fold4 = sq && coarse;
+  const int rc = time_stages(sq ? (coarse ? 6 : 7) : 5, fold4 ? t : stage_ms, [&](hipEvent_t* ev) {
     return sweep(ix, rf_variant{filt, sq, wide, band, after, multi, coarse}, (const _Float16*)q_dev, nb, k, id_base, ws,
                  o, st, ev);
   });
+  if (rc == RF_OK && fold4) {
+    stage_ms[0] = t[1];
+    stage_ms[1] = t[2];
+    stage_ms[2] = t[0] + t[3];
+    stage_ms[3] = t[4];
+  }
+  return rc;
 }
 
 // The chain of a plain search of B queries: the shadow first (rf_index_set_shadow_first) when the index
