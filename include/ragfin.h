@@ -610,6 +610,61 @@ typedef struct rf_column_leaf {
 } rf_column_leaf;
 int rf_column_match(const rf_column_leaf* leaves_host, int n_leaves, const uint32_t* code_sets_dev,
                     const int64_t* value_sets_dev, int64_t n_rows, uint32_t* bitmaps_dev, void* stream);
+/* ---- dynamic fields: the leaves of `expr` over schemaless metadata, typed per row ---------------------
+ * pymilvus' enable_dynamic_field: a row may carry keys the schema does not declare, and two rows may hold
+ * values of different types under one key, or none.  The device mirror of one key is a tagged column:
+ *   tags_dev     uint8 [n_rows]: RF_DTAG_ABSENT (the row lacks the key) | BOOL | INT | DOUBLE | STRING
+ *   payload_dev  8 bytes [n_rows], 8-byte aligned: the int64 value, the fp64 bits, a bool as 0 / 1, or the
+ *                string's code into the key's append-only dictionary (as an int64 >= 0); unread for ABSENT
+ * A leaf is evaluated into a row bitmap that an RF_FOP_BITMAP leaf of rf_filter_eval_bitmaps reads -- the
+ * door rf_text_match and rf_column_match use.  Leaf kinds:
+ *   RF_DLEAF_TAGS         the row's tag t has bit t of flags set (flags: 8 bits; a tag >= 8 fails)
+ *   RF_DLEAF_STR_CODESET  tag STRING and the code x has 0 <= x < 32 len and bit x of
+ *                         code_sets_dev[off .. off + len) set
+ *   RF_DLEAF_BOOL         tag BOOL and the value v (0 / 1; anything else fails) has bit v of flags set
+ *   RF_DLEAF_NUM_RANGE    tag INT: ilo <= x <= ihi, both ends inclusive (ilo > ihi passes no INT row);
+ *                         tag DOUBLE: flo <(=) x <(=) fhi, RF_FRANGE_* bits in flags say which ends are
+ *                         inclusive, IEEE comparisons, so a NaN value fails
+ *   RF_DLEAF_NUM_SET      tag INT: x is in int_sets_dev[off .. off + len); tag DOUBLE: x equals (IEEE ==) an
+ *                         entry of f64_sets_dev[foff .. foff + flen); both sorted ascending, binary search,
+ *                         at most RF_COLUMN_MAX_SET entries each
+ * A row whose tag the kind does not name fails.  Otherwise the contract of rf_column_match: leaves_host is
+ * HOST memory, n_leaves in 1..RF_DYNAMIC_MAX_LEAVES (they travel in the launch arguments, so the call
+ * captures into a hipGraph); leaf l writes EVERY word of bitmaps_dev[l * nwords .. (l + 1) * nwords),
+ * nwords = ceil(n_rows / 32), bits past n_rows zero; one launch, grid (row chunks, leaves), a lane owns a
+ * row, a wave's 64 predicates become two words by ballot; stream-ordered, no host sync, no allocation, no
+ * atomics; integers and IEEE comparisons only: the same bits on every run.
+ * RF_ERR_INVALID before any device call: a NULL leaves_host / bitmaps_dev, n_leaves or n_rows out of range,
+ * an unknown kind, flags outside the kind's bits, a negative or too large off / len / foff / flen, a leaf
+ * that needs code_sets_dev / int_sets_dev / f64_sets_dev when that is NULL, a misaligned set or bitmap
+ * pointer, tags_dev NULL, payload_dev NULL (any kind but TAGS) or not 8-byte aligned.  A set of length 0 is
+ * legal and passes nothing; a code or a search position outside the leaf's slice is never dereferenced.
+ * n_rows == 0 writes nothing and returns RF_OK.
+ * New in this build; the reference's collection has no dynamic field. */
+#define RF_DYNAMIC_MAX_LEAVES 16
+#define RF_DTAG_ABSENT 0
+#define RF_DTAG_BOOL 1
+#define RF_DTAG_INT 2
+#define RF_DTAG_DOUBLE 3
+#define RF_DTAG_STRING 4
+#define RF_DLEAF_TAGS 1
+#define RF_DLEAF_STR_CODESET 2
+#define RF_DLEAF_BOOL 3
+#define RF_DLEAF_NUM_RANGE 4
+#define RF_DLEAF_NUM_SET 5
+typedef struct rf_dynamic_leaf {
+  int32_t kind;             /* RF_DLEAF_* */
+  int32_t flags;            /* TAGS: tag mask; BOOL: value set (bits 0, 1); NUM_RANGE: RF_FRANGE_* bits; else 0 */
+  const uint8_t* tags_dev;  /* [n_rows] */
+  const void* payload_dev;  /* 8 bytes [n_rows]; TAGS does not read it */
+  int64_t off, len;         /* STR_CODESET: words of code_sets_dev; NUM_SET: entries of int_sets_dev */
+  int64_t foff, flen;       /* NUM_SET: entries of f64_sets_dev */
+  int64_t ilo, ihi;         /* NUM_RANGE: the INT rows' bounds, inclusive */
+  double flo, fhi;          /* NUM_RANGE: the DOUBLE rows' bounds */
+} rf_dynamic_leaf;
+int rf_dynamic_match(const rf_dynamic_leaf* leaves_host, int n_leaves, const uint32_t* code_sets_dev,
+                     const int64_t* int_sets_dev, const double* f64_sets_dev, int64_t n_rows,
+                     uint32_t* bitmaps_dev, void* stream);
 /* ---- lexical index maintenance: the postings after an append or a delete, without the old texts -------
  * A write changes N, avgdl and df, and through them every BM25 impact -- but with the term frequencies
  * kept beside the postings (post_tf uint32 [nnz]) everything is re-derivable: the arrays after a write

@@ -33,6 +33,10 @@ RF_TEXT_MAX_LEAVES = 16      # text leaves one rf_text_match call (one filter ex
 RF_COLUMN_MAX_LEAVES = 16    # column leaves one rf_column_match call (one filter expression) holds
 RF_COLUMN_MAX_SET = 65536    # values of one INT64 `in` list
 RF_CLEAF_CODESET, RF_CLEAF_I64_RANGE, RF_CLEAF_I64_SET, RF_CLEAF_F64_RANGE = 1, 2, 3, 4
+# dynamic fields (include/ragfin.h, "dynamic fields")
+RF_DYNAMIC_MAX_LEAVES = 16   # dynamic leaves one rf_dynamic_match call holds
+RF_DTAG_ABSENT, RF_DTAG_BOOL, RF_DTAG_INT, RF_DTAG_DOUBLE, RF_DTAG_STRING = range(5)
+RF_DLEAF_TAGS, RF_DLEAF_STR_CODESET, RF_DLEAF_BOOL, RF_DLEAF_NUM_RANGE, RF_DLEAF_NUM_SET = 1, 2, 3, 4, 5
 # lexical index maintenance (include/ragfin.h, "lexical index maintenance")
 RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
 # lexical index build (include/ragfin.h, "lexical index build")
@@ -73,6 +77,13 @@ class TextLeaf(Structure):
 class ColumnLeaf(Structure):
     """rf_column_leaf: one leaf of a filter expression over an extra column."""
     _fields_ = [("kind", c_int32), ("flags", c_int32), ("column_dev", c_void_p), ("off", c_int64), ("len", c_int64),
+                ("ilo", c_int64), ("ihi", c_int64), ("flo", c_double), ("fhi", c_double)]
+
+
+class DynamicLeaf(Structure):
+    """rf_dynamic_leaf: one leaf of a filter expression over a dynamic key's tagged column."""
+    _fields_ = [("kind", c_int32), ("flags", c_int32), ("tags_dev", c_void_p), ("payload_dev", c_void_p),
+                ("off", c_int64), ("len", c_int64), ("foff", c_int64), ("flen", c_int64),
                 ("ilo", c_int64), ("ihi", c_int64), ("flo", c_double), ("fhi", c_double)]
 
 
@@ -208,6 +219,7 @@ SIGNATURES = {
     "rf_text_match": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t,
                               c_void_p]),
     "rf_column_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rf_dynamic_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_sparse_impacts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,
                                   c_double, c_double, c_void_p, c_void_p]),
     "rf_sparse_append_workspace_bytes": (c_size_t, [c_int64, c_int64]),

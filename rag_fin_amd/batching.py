@@ -53,7 +53,8 @@ class MicroBatcher:
             expr = None
         else:
             store = getattr(self.rag, "collection", None)
-            filter_expr.parse(expr, getattr(store, "analyzer", None), getattr(store, "schema", None))
+            filter_expr.parse(expr, getattr(store, "analyzer", None), getattr(store, "schema", None),
+                              getattr(store, "enable_dynamic_field", False))
         req = _Request(query, top_k, expr)
         with self._cv:
             if self._stop:

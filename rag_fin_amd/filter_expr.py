@@ -11,6 +11,7 @@ Grammar (keywords case-insensitive; precedence not > and > or)::
     and_    := unary (("and" | "&&") unary)*
     unary   := ("not" | "!") unary | "(" expr ")" | compare
     compare := FIELD CMP literal | literal CMP FIELD [CMP literal]
+             | "exists" FIELD                       (dynamic fields only; there FIELD is also NAME | $meta[STRING])
              | FIELD ["not"] "in" "[" [literal ("," literal)*] "]" | FIELD "like" STRING
              | FUNC "(" "text" "," STRING ["," (NAME "=" NUM | NUM)] ")"
     FUNC    := "TEXT_MATCH" | "PHRASE_MATCH"
@@ -38,6 +39,31 @@ String literals take single or double quotes (backslash escapes the next charact
 else -- an unknown field, `embedding`, `text` outside the two functions, a type mismatch such as `period > 3` or
 `primary_value == "x"`, a syntax error -- raises ValueError naming the token and its position.
 
+Dynamic fields (`parse(..., dynamic=True)`, what a store with enable_dynamic_field=True passes; pymilvus'
+`$meta`).  A dynamic operand stands wherever a scalar field does: a bare identifier that is no field of the
+collection, no reserved name and no word of the grammar, or `$meta["any key"]` (single or double quotes).  It
+takes == != < <= > >= (literal-first and chained forms included), in / not in (at most RF_COLUMN_MAX_SET values
+of one type class), like, and `exists KEY`.  A row holds under a key a bool, an int (int64), a float or a str,
+or lacks the key.  The semantics below are THIS PROJECT'S definition (Milvus leaves mixed types to its JSON
+engine), written once as the `eval` of DynCmp / DynIn / DynLike / Exists and, for the compiled leaves, as
+`dynamic_leaf_reference`:
+  * three type classes: string, number (int and float together), boolean;
+  * a comparison leaf passes a row iff the row holds the key, the value's class is the literal's class, and the
+    comparison holds: strings in code-point order; numbers as Python compares them -- an int against a float
+    exactly, not "both to double" (2**53 + 1 > 2.0**53 holds, 3 == 3.0 holds); floats by IEEE, so a NaN row
+    fails everything except !=; booleans take == != in / not in only;
+  * a row that lacks the key, or holds a value of another class, fails EVERY leaf, `!=` and `not in` included
+    (as an SQL NULL would); `k in []` and `k not in []` name no class and pass no row;
+  * `not (...)` is plain negation, as everywhere in the grammar, so `not (k == 1)` passes the rows that lack k;
+  * `exists k` passes iff the row holds k;
+  * a key that no row holds is no error: its leaves are FALSE.
+A dynamic leaf compiles into entries of `Program.dynamic_leaves`, which rf_dynamic_match evaluates over the
+key's tagged column (tag uint8, payload 8 bytes; `encode_dynamic`) into row bitmaps: TAGS (the tag is in a
+mask: `exists`, and the class guard of a numeric `!=` / `not in`, which is TAGS(number) and not EQ), STR_CODESET
+(the leaf evaluated against the key's dictionary, as a VARCHAR leaf), BOOL, NUM_RANGE (an int64 interval for the
+int rows and an fp64 interval for the float rows, both derived exactly from the one literal: `int_interval` and
+`f64_interval`) and NUM_SET (a sorted int64 set and a sorted fp64 set).
+
 Compilation.  A VARCHAR leaf is evaluated once against the column's dictionary (every distinct
 string, in first-seen order = its code) and becomes a set of codes, so a literal that is not in
 the dictionary matches nothing; numeric leaves become interval tests; id leaves become a sorted
@@ -55,7 +81,7 @@ from typing import Any, Sequence
 import numpy as np
 
 from . import _lib, lexical
-from .schema import INT64_MAX, INT64_MIN, DataType
+from .schema import INT64_MAX, INT64_MIN, RESERVED, DataType
 
 VARCHAR_FIELDS = ("period", "chunk_type", "statement_type")   # device columns 0, 1, 2
 DOUBLE_FIELDS = ("primary_value",)                             # device column 3
@@ -68,6 +94,7 @@ TEXT_FUNCS = ("text_match", "phrase_match")
 TEXT_FIELD = "text"
 NO_LEXICAL_INDEX = ("TEXT_MATCH / PHRASE_MATCH need the lexical index over the text column: call "
                     "create_index('sparse', {'index_type': 'SPARSE_INVERTED_INDEX', 'metric_type': 'BM25'}) first")
+DYNAMIC_KEYWORDS = ("and", "or", "not", "in", "like", "true", "false", "exists")   # never a bare dynamic key
 _FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<=", "==": "==", "!=": "!="}
 
 
@@ -79,7 +106,7 @@ def is_empty(expr) -> bool:
 # ---- tokens ------------------------------------------------------------------------------------
 @dataclass
 class Tok:
-    kind: str      # "name" | "str" | "num" | "op" | "end"
+    kind: str      # "name" | "str" | "num" | "op" | "end" | "meta" ($meta, with dynamic fields only)
     value: Any
     pos: int
     text: str
@@ -93,6 +120,10 @@ _TOKEN = re.compile(r"""
 """, re.X)
 
 
+META = "$meta"   # the dynamic field's name: $meta["key"] in expr, "$meta" as an output field
+_META = re.compile(r"\$meta(?![A-Za-z0-9_])")
+
+
 def _err(msg: str, tok: Tok | None = None, pos: int | None = None) -> ValueError:
     if tok is not None:
         where = "end of expression" if tok.kind == "end" else f"{tok.text!r} at position {tok.pos}"
@@ -100,11 +131,15 @@ def _err(msg: str, tok: Tok | None = None, pos: int | None = None) -> ValueError
     return ValueError(f"filter expression: {msg} at position {pos}")
 
 
-def tokenize(s: str) -> list[Tok]:
+def tokenize(s: str, dynamic: bool = False) -> list[Tok]:
     out: list[Tok] = []
     i = 0
     while i < len(s):
         c = s[i]
+        if dynamic and _META.match(s, i):
+            out.append(Tok("meta", META, i, META))
+            i += len(META)
+            continue
         if c in "'\"":
             j = i + 1
             buf = []
@@ -211,6 +246,72 @@ class PhraseMatch(Node):
         return m > 0 and any(d[j:j + m] == p for j in range(len(d) - m + 1))
 
 
+# -- dynamic fields: the semantics of a leaf over a key of $meta (module docstring), in pure Python --
+def dynamic_class(v) -> str | None:
+    """The type class of a dynamic value: "boolean", "number" (int and float together), "string"; None: the
+    row lacks the key."""
+    if v is None:
+        return None
+    if isinstance(v, bool):
+        return "boolean"
+    return "string" if isinstance(v, str) else "number"
+
+
+def _dynamic_value(row: dict, key: str):
+    """row: {field or dynamic key: value}, or a row that keeps its dynamic keys under "$meta"."""
+    meta = row.get(META)
+    return (row if meta is None else meta).get(key)
+
+
+@dataclass
+class DynCmp(Node):
+    key: str
+    op: str
+    value: Any
+    field = None
+
+    def eval(self, row):
+        x = _dynamic_value(row, self.key)
+        return x is not None and dynamic_class(x) == dynamic_class(self.value) and _compare(x, self.op, self.value)
+
+
+@dataclass
+class DynIn(Node):
+    key: str
+    values: list
+    negate: bool = False
+    field = None
+
+    def eval(self, row):
+        x = _dynamic_value(row, self.key)
+        if x is None or not self.values or dynamic_class(x) != dynamic_class(self.values[0]):
+            return False
+        return any(x == v for v in self.values) != self.negate
+
+
+@dataclass
+class DynLike(Node):
+    key: str
+    pattern: str
+    field = None
+
+    def eval(self, row):
+        x = _dynamic_value(row, self.key)
+        return isinstance(x, str) and like_match(x, self.pattern)
+
+
+@dataclass
+class Exists(Node):
+    key: str
+    field = None
+
+    def eval(self, row):
+        return _dynamic_value(row, self.key) is not None
+
+
+DYNAMIC_NODES = (DynCmp, DynIn, DynLike, Exists)
+
+
 @dataclass
 class And(Node):
     a: Node
@@ -266,10 +367,11 @@ def like_match(s: str, pattern: str) -> bool:
 
 # ---- parser ------------------------------------------------------------------------------------
 class _Parser:
-    def __init__(self, text: str, analyzer=None, schema=None):
-        self.toks = tokenize(text)
+    def __init__(self, text: str, analyzer=None, schema=None, dynamic: bool = False):
+        self.toks = tokenize(text, dynamic)
         self.i = 0
         self.analyzer = analyzer
+        self.dynamic = dynamic   # a name that is no field of the collection is a key of $meta
         self.extra = {f.name: f.dtype for f in schema or ()}   # the collection's own fields (schema.py)
 
     def peek(self, k: int = 0) -> Tok:
@@ -332,11 +434,33 @@ class _Parser:
         name = t.value
         if name in UNFILTERABLE:
             raise _err(f"field {name!r} cannot be filtered on", t)
-        if name not in VARCHAR_FIELDS + DOUBLE_FIELDS + (PK_FIELD,) and name not in self.extra:
+        if not self.known(name):
             if name.lower().startswith(("json_", "array_")) and self.op("("):
                 raise _err(f"unknown function {name!r} (ARRAY and JSON fields are not supported)", t)
-            raise _err(f"unknown field {name!r}", t)
+            if not self.dynamic or name in RESERVED or name.lower() in DYNAMIC_KEYWORDS:
+                raise _err(f"unknown field {name!r}", t)
         return name, t
+
+    def known(self, name: str) -> bool:
+        return name in VARCHAR_FIELDS + DOUBLE_FIELDS + (PK_FIELD,) or name in self.extra
+
+    def operand(self) -> tuple[str, Tok, bool]:
+        """A scalar field, or with dynamic fields a key of $meta: (name, its token, is a dynamic key)."""
+        t = self.peek()
+        if t.kind != "meta":
+            name, ft = self.field()
+            return name, ft, not self.known(name)
+        self.take()
+        if not self.op("["):
+            raise _err("expected '[' after $meta", self.peek())
+        self.take()
+        kt = self.take()
+        if kt.kind != "str" or kt.value == "":
+            raise _err("$meta takes a non-empty string key, as in $meta[\"key\"]", kt)
+        if not self.op("]"):
+            raise _err("expected ']'", self.peek())
+        self.take()
+        return kt.value, t, True
 
     def dtype(self, name: str):
         """The DataType of a filterable scalar field (None: the primary key)."""
@@ -378,37 +502,48 @@ class _Parser:
             o1 = self.cmp_op()
             if o1 is None:
                 raise _err("expected a comparison operator", self.peek())
-            name, ft = self.field()
-            left = self._leaf_cmp(name, ft, _FLIP[o1.value], lit, lt, o1)
+            name, ft, dyn = self.operand()
+            leaf = self._dynamic_cmp if dyn else self._leaf_cmp
+            left = leaf(name, ft, _FLIP[o1.value], lit, lt, o1)
             o2 = self.cmp_op()
             if o2 is None:
                 return left
             lit2, lt2 = self.literal()
-            return And(left, self._leaf_cmp(name, ft, o2.value, lit2, lt2, o2))
+            return And(left, leaf(name, ft, o2.value, lit2, lt2, o2))
         if t.kind == "name" and t.value.lower() in TEXT_FUNCS and self.op("(", 1):
             return self.text_func()
-        name, ft = self.field()
+        if self.dynamic and self.kw("exists") and not self.known("exists"):
+            et = self.take()
+            if self.peek().kind not in ("name", "meta"):
+                raise _err("'exists' takes a dynamic key", self.peek() if self.peek().kind != "end" else et)
+            name, ft, dyn = self.operand()
+            if not dyn:
+                raise _err(f"'exists' takes a dynamic key, {name!r} is a field of the collection", ft)
+            return Exists(name)
+        name, ft, dyn = self.operand()
         o = self.cmp_op()
         if o is not None:
             lit, lt = self.literal()
-            return self._leaf_cmp(name, ft, o.value, lit, lt, o)
+            return (self._dynamic_cmp if dyn else self._leaf_cmp)(name, ft, o.value, lit, lt, o)
         negate = False
         if self.kw("not") and self.kw("in", 1):
             self.take()
             negate = True
         if self.kw("in"):
             kt = self.take()
+            if dyn:
+                return DynIn(name, self._list(name, kt, dynamic=True), negate)
             return In(name, self._list(name, kt), negate)
         if self.kw("like"):
             kt = self.take()
-            if self.dtype(name) != DataType.VARCHAR:
+            if not dyn and self.dtype(name) != DataType.VARCHAR:
                 raise _err(f"'like' needs a VARCHAR field, {name!r} is not one", kt)
             pt = self.take()
             if pt.kind != "str":
                 raise _err("'like' needs a string pattern", pt)
             if "%" in pt.value.strip("%") or pt.value in ("%", "%%"):
                 raise _err("'like' supports 'p%', '%s' and '%i%' only", pt)
-            return Like(name, pt.value)
+            return DynLike(name, pt.value) if dyn else Like(name, pt.value)
         nt = self.peek()
         if nt.kind == "op" and nt.value in "+-":
             raise _err("expected a comparison, 'in' or 'like' (arithmetic is not supported)", nt)
@@ -461,7 +596,7 @@ class _Parser:
                        f"{lexical.MAX_QUERY_TERMS} are taken", st)
         return node
 
-    def _list(self, name: str, kt: Tok) -> list:
+    def _list(self, name: str, kt: Tok, dynamic: bool = False) -> list:
         if not self.op("["):
             raise _err("expected '['", self.peek())
         self.take()
@@ -469,7 +604,9 @@ class _Parser:
         if not self.op("]"):
             while True:
                 lit, lt = self.literal()
-                vals.append(self._check_type(name, lit, lt))
+                if dynamic and vals and dynamic_class(lit) != dynamic_class(vals[0]):
+                    raise _err(f"an 'in' list over a dynamic key holds one type class, {dynamic_class(vals[0])}s here", lt)
+                vals.append(lit if dynamic else self._check_type(name, lit, lt))
                 if self.op(","):
                     self.take()
                     continue
@@ -478,6 +615,11 @@ class _Parser:
             raise _err("expected ']'", self.peek())
         self.take()
         return vals
+
+    def _dynamic_cmp(self, key, ft, op, lit, lt, ot) -> Node:
+        if isinstance(lit, bool) and op not in ("==", "!="):
+            raise _err(f"a boolean supports == != in / not in only, not {ot.value!r}", ot)
+        return DynCmp(key, op, lit)
 
     def _leaf_cmp(self, name, ft, op, lit, lt, ot) -> Node:
         if name == PK_FIELD and op not in ("==", "!="):
@@ -517,13 +659,14 @@ class _Parser:
         return lit   # id: int or str keys, as inserted
 
 
-def parse(text: str, analyzer=None, schema=None) -> Node:
+def parse(text: str, analyzer=None, schema=None, dynamic: bool = False) -> Node:
     """analyzer: what the keyword leaves analyse their strings with (None = lexical.analyze).
     schema: the collection's own fields (a sequence of schema.FieldSchema; None = none: a name outside
-    the reference's fields is an unknown field)."""
+    the reference's fields is an unknown field).  dynamic: the collection has enable_dynamic_field: such a
+    name is a key of $meta instead, and $meta["key"] and `exists key` are taken (module docstring)."""
     if not isinstance(text, str):
         raise ValueError(f"filter expression must be a string, got {type(text).__name__}")
-    return _Parser(text, analyzer, schema).parse()
+    return _Parser(text, analyzer, schema, dynamic).parse()
 
 
 def text_leaves(node: Node) -> list:
@@ -541,7 +684,16 @@ def fields_of(node: Node) -> set:
         return fields_of(node.a) | fields_of(node.b)
     if isinstance(node, Not):
         return fields_of(node.a)
-    return {node.field}
+    return set() if isinstance(node, DYNAMIC_NODES) else {node.field}
+
+
+def dynamic_keys_of(node: Node) -> set:
+    """The dynamic keys a tree's leaves read."""
+    if isinstance(node, (And, Or)):
+        return dynamic_keys_of(node.a) | dynamic_keys_of(node.b)
+    if isinstance(node, Not):
+        return dynamic_keys_of(node.a)
+    return {node.key} if isinstance(node, DYNAMIC_NODES) else set()
 
 
 # ---- compilation -------------------------------------------------------------------------------
@@ -557,12 +709,18 @@ class Program:
     ("iset", field, sorted distinct int64 values) | ("frange", field, RF_FRANGE_* flags, lo, hi).  The
     RF_FOP_BITMAP op of column leaf c carries c in `off` and COLUMN_LEAF in `column`; the column leaves'
     bitmaps (column_words words each) follow the keyword leaves' from word column_base of the one
-    bitmap array the program indexes."""
+    bitmap array the program indexes.
+    dynamic_leaves: the leaves over dynamic keys, the input of rf_dynamic_match:
+    ("tags", key, tag mask) | ("codeset", key, code-set words) | ("bool", key, 2-bit value set) |
+    ("nrange", key, ilo, ihi, RF_FRANGE_* flags, flo, fhi) | ("nset", key, sorted int64 values, sorted fp64
+    values).  The RF_FOP_BITMAP op of dynamic leaf d carries d in `off` and DYNAMIC_LEAF in `column`; their
+    bitmaps (column_words words each) follow the column leaves'."""
     ops: list = field(default_factory=list)
     code_sets: list = field(default_factory=list)
     row_lists: list = field(default_factory=list)
     text_leaves: list = field(default_factory=list)
     column_leaves: list = field(default_factory=list)
+    dynamic_leaves: list = field(default_factory=list)
 
     def resolved_ops(self, words_per_leaf: int = 0, column_base: int = 0, column_words: int = 0) -> list:
         """The op tuples as the device takes them: every RF_FOP_BITMAP leaf with its word range."""
@@ -570,6 +728,8 @@ class Program:
         for op, col, off, ln, flags, lo, hi in self.ops:
             if op == _lib.RF_FOP_BITMAP and col == COLUMN_LEAF:
                 col, off, ln = 0, column_base + off * column_words, column_words
+            elif op == _lib.RF_FOP_BITMAP and col == DYNAMIC_LEAF:
+                col, off, ln = 0, column_base + (len(self.column_leaves) + off) * column_words, column_words
             elif op == _lib.RF_FOP_BITMAP:
                 off, ln = off * words_per_leaf, words_per_leaf
             out.append((op, col, off, ln, flags, lo, hi))
@@ -592,7 +752,10 @@ class Program:
 
 
 COLUMN_LEAF = 1   # `column` of an RF_FOP_BITMAP op in Program.ops: the bitmap of a column leaf, not of a keyword leaf
+DYNAMIC_LEAF = 2  # ... the bitmap of a dynamic leaf
 MAX_INT_SET = _lib.RF_COLUMN_MAX_SET
+NUMBER_TAGS = 1 << _lib.RF_DTAG_INT | 1 << _lib.RF_DTAG_DOUBLE
+HELD_TAGS = 1 << _lib.RF_DTAG_BOOL | NUMBER_TAGS | 1 << _lib.RF_DTAG_STRING   # every tag but ABSENT
 
 
 def int_interval(op: str, v) -> tuple[int, int] | None:
@@ -615,9 +778,60 @@ def int_interval(op: str, v) -> tuple[int, int] | None:
     return (lo, hi) if lo <= hi else None
 
 
+def _int_interval(op: str, v) -> tuple[int, int] | None:
+    """int_interval for any number literal: an infinite float too."""
+    if isinstance(v, float) and math.isinf(v):
+        return (INT64_MIN, INT64_MAX) if op in (("<", "<=") if v > 0 else (">", ">=")) else None
+    return int_interval(op, v)
+
+
+def _exact_float(v) -> float | None:
+    """The double that equals the number v (an int of any size, or a float), or None when there is none."""
+    try:
+        f = float(v)
+    except OverflowError:
+        return None
+    return f if f == v else None   # (Python compares an int with a float exactly)
+
+
+def _float_below(v) -> float:
+    """The largest double <= v."""
+    try:
+        f = float(v)   # round to nearest: at most one step off
+    except OverflowError:
+        return -math.inf if v < 0 else math.nextafter(math.inf, 0.0)   # (an int beyond the doubles' range)
+    return f if f <= v else math.nextafter(f, -math.inf)
+
+
+def _float_above(v) -> float:
+    """The smallest double >= v."""
+    return -_float_below(-v)
+
+
+def f64_interval(op: str, v) -> tuple[int, float, float]:
+    """A comparison `x op v` of an fp64 x with a number literal v (an int of any size, or a float), compared
+    mathematically, as the IEEE interval test (RF_FRANGE_* flags, lo, hi) that selects exactly the same doubles.
+    An int that no double represents lies strictly between two neighbouring doubles, so rounding it DOWN for a
+    lower bound of `>` (UP for `>=`) and UP for the upper bound of `<` (DOWN for `<=`) loses nothing; `==` with
+    such an int passes nothing (lo = +inf, hi = -inf, both exclusive).  `!=` is the caller's (not ==)."""
+    inf = math.inf
+    L, H = _lib.RF_FRANGE_LO_INCL, _lib.RF_FRANGE_HI_INCL
+    if op == "==":
+        f = _exact_float(v)
+        return (0, inf, -inf) if f is None else (L | H, f, f)
+    if op == ">":
+        return H, _float_below(v), inf
+    if op == ">=":
+        return L | H, _float_above(v), inf
+    if op == "<":
+        return L, -inf, _float_above(v)
+    return L | H, -inf, _float_below(v)
+
+
 class _Compiler:
     def __init__(self, dicts: dict[str, Sequence[str]], pk_row: dict, term_id: dict | None = None, schema=None,
-                 extra_dicts: dict | None = None):
+                 extra_dicts: dict | None = None, dynamic: dict | None = None):
+        self.dynamic = dynamic or {}   # dynamic key some row holds -> its dictionary of strings (code = index)
         self.dicts = dicts
         self.pk_row = pk_row
         self.term_id = term_id
@@ -638,6 +852,8 @@ class _Compiler:
             self.leaf(_lib.RF_FOP_NOT)
         elif isinstance(n, (TextMatch, PhraseMatch)):
             self.text(n)
+        elif isinstance(n, DYNAMIC_NODES):
+            self.dynamic_node(n)
         elif n.field in self.extra:
             self.column(n, self.extra[n.field])
         elif n.field in VARCHAR_FIELDS:
@@ -727,6 +943,62 @@ class _Compiler:
                          ">": (v, inf, H), ">=": (v, inf, L | H)}[op]
         self.column_leaf("frange", name, flags, lo, hi)
 
+    # -- leaves over dynamic keys: RF_FOP_BITMAP ops + entries of dynamic_leaves (module docstring) --
+    def dynamic_leaf(self, *leaf) -> None:
+        self.leaf(_lib.RF_FOP_BITMAP, DYNAMIC_LEAF, len(self.p.dynamic_leaves))
+        self.p.dynamic_leaves.append(leaf)
+
+    def dynamic_node(self, n: Node) -> None:
+        key = n.key
+        if key not in self.dynamic:   # no row holds the key
+            self.leaf(_lib.RF_FOP_FALSE)
+            return
+        if isinstance(n, Exists):
+            self.dynamic_leaf("tags", key, HELD_TAGS)
+            return
+        cls = "string" if isinstance(n, DynLike) else \
+            dynamic_class(n.value if isinstance(n, DynCmp) else (n.values[0] if n.values else None))
+        if cls is None:   # k in [] / k not in []
+            self.leaf(_lib.RF_FOP_FALSE)
+        elif cls == "string":
+            # against the key's dictionary (first-seen order = code), as for period; != and not in included
+            codes = [c for c, s in enumerate(self.dynamic[key]) if n.eval({key: s})]
+            if not codes:
+                self.leaf(_lib.RF_FOP_FALSE)
+                return
+            words = [0] * ((max(codes) >> 5) + 1)
+            for c in codes:
+                words[c >> 5] |= 1 << (c & 31)
+            self.dynamic_leaf("codeset", key, words)
+        elif cls == "boolean":
+            bits = sum(1 << int(b) for b in (False, True) if n.eval({key: b}))
+            if bits:
+                self.dynamic_leaf("bool", key, bits)
+            else:
+                self.leaf(_lib.RF_FOP_FALSE)
+        else:
+            self.dynamic_number(n)
+
+    def dynamic_number(self, n: Node) -> None:
+        negate = (isinstance(n, DynCmp) and n.op == "!=") or (isinstance(n, DynIn) and n.negate)
+        if negate:   # k != v: holds a number, and not k == v (a NaN row passes, a row without a number does not)
+            self.dynamic_leaf("tags", n.key, NUMBER_TAGS)
+        if isinstance(n, DynCmp):
+            op = "==" if negate else n.op
+            iv = _int_interval(op, n.value) or (0, -1)   # (ilo > ihi: no int row passes)
+            self.dynamic_leaf("nrange", n.key, iv[0], iv[1], *f64_interval(op, n.value))
+        else:
+            ints = sorted({int(v) for v in n.values if not (isinstance(v, float) and math.isinf(v))
+                           and v == math.floor(v) and INT64_MIN <= v <= INT64_MAX})
+            floats = sorted({f for f in map(_exact_float, n.values) if f is not None})
+            if max(len(ints), len(floats)) > MAX_INT_SET:
+                raise ValueError(f"filter expression: {n.key} {'not in' if n.negate else 'in'} [...] holds "
+                                 f"{max(len(ints), len(floats))} distinct values, at most {MAX_INT_SET} are taken")
+            self.dynamic_leaf("nset", n.key, ints, floats)
+        if negate:
+            self.leaf(_lib.RF_FOP_NOT)
+            self.leaf(_lib.RF_FOP_AND)
+
     def codeset(self, n: Node) -> None:
         d = self.dicts.get(n.field, ())
         codes = [c for c, s in enumerate(d) if n.eval({n.field: s})]
@@ -787,15 +1059,18 @@ def _hashable(k) -> bool:
 
 
 def compile_expr(node: Node | str, dicts: dict[str, Sequence[str]], pk_row: dict,
-                 term_id: dict | None = None, schema=None, extra_dicts: dict | None = None) -> Program:
+                 term_id: dict | None = None, schema=None, extra_dicts: dict | None = None,
+                 dynamic: dict | None = None) -> Program:
     """AST (or expression text) -> Program.  dicts: VARCHAR field -> its dictionary (code i =
     dicts[field][i]); pk_row: primary key -> row number; term_id: term -> id in the lexical index's
     dictionary (`Postings.term_id`), None = no lexical index: a keyword leaf raises ValueError.
     schema: the collection's own fields (schema.FieldSchema; None = none); extra_dicts: VARCHAR / BOOL
-    field of the schema -> its dictionary of values, code i = extra_dicts[field][i]."""
+    field of the schema -> its dictionary of values, code i = extra_dicts[field][i].
+    dynamic: None = the collection has no dynamic field; else dynamic key that some row holds -> the
+    dictionary of its strings, code i = dynamic[key][i] (a key that is not in it compiles to FALSE)."""
     if isinstance(node, str):
-        node = parse(node, schema=schema)
-    c = _Compiler(dicts, pk_row, term_id, schema, extra_dicts)
+        node = parse(node, schema=schema, dynamic=dynamic is not None)
+    c = _Compiler(dicts, pk_row, term_id, schema, extra_dicts, dynamic)
     c.emit(node)
     p = c.p
     if len(p.ops) > _lib.RF_FILTER_MAX_OPS:
@@ -858,6 +1133,92 @@ def column_leaf_reference(leaf, column: np.ndarray) -> np.ndarray:
         a = column >= lo if flags & _lib.RF_FRANGE_LO_INCL else column > lo
         b = column <= hi if flags & _lib.RF_FRANGE_HI_INCL else column < hi
     return a & b
+
+
+def encode_dynamic(values, code: dict, strings: list) -> tuple[np.ndarray, np.ndarray]:
+    """The tagged column of a dynamic key's values (None | bool | int | float | str, one per row): (tags uint8
+    [n], payload int64 [n]).  payload: the int64, the fp64's bits, a bool as 0 / 1, or the string's code; a new
+    string is appended to `strings` and entered into `code` (string -> code: first-seen order)."""
+    n = len(values)
+    tags = np.zeros(n, dtype=np.uint8)
+    payload = np.zeros(n, dtype=np.int64)
+    fbits = payload.view(np.float64)
+    for j, v in enumerate(values):
+        if v is None:
+            continue
+        if isinstance(v, bool):
+            tags[j], payload[j] = _lib.RF_DTAG_BOOL, int(v)
+        elif isinstance(v, int):
+            tags[j], payload[j] = _lib.RF_DTAG_INT, v
+        elif isinstance(v, float):
+            tags[j], fbits[j] = _lib.RF_DTAG_DOUBLE, v
+        else:
+            c = code.get(v)
+            if c is None:
+                c = code[v] = len(strings)
+                strings.append(v)
+            tags[j], payload[j] = _lib.RF_DTAG_STRING, c
+    return tags, payload
+
+
+def dynamic_leaf_arrays(p: Program, column_ptr: dict):
+    """(rf_dynamic_leaf array, code-set words uint32, int sets int64, fp64 sets) of p.dynamic_leaves.
+    column_ptr: key -> (device address of its tags, of its payload)."""
+    arr = (_lib.DynamicLeaf * len(p.dynamic_leaves))()
+    words: list = []
+    ints: list = []
+    floats: list = []
+    for i, leaf in enumerate(p.dynamic_leaves):
+        kind, key = leaf[0], leaf[1]
+        arr[i].tags_dev, arr[i].payload_dev = column_ptr[key]
+        if kind == "tags":
+            arr[i].kind, arr[i].flags = _lib.RF_DLEAF_TAGS, leaf[2]
+        elif kind == "codeset":
+            arr[i].kind, arr[i].off, arr[i].len = _lib.RF_DLEAF_STR_CODESET, len(words), len(leaf[2])
+            words.extend(leaf[2])
+        elif kind == "bool":
+            arr[i].kind, arr[i].flags = _lib.RF_DLEAF_BOOL, leaf[2]
+        elif kind == "nrange":
+            arr[i].kind = _lib.RF_DLEAF_NUM_RANGE
+            arr[i].ilo, arr[i].ihi, arr[i].flags, arr[i].flo, arr[i].fhi = leaf[2:7]
+        else:
+            arr[i].kind = _lib.RF_DLEAF_NUM_SET
+            arr[i].off, arr[i].len, arr[i].foff, arr[i].flen = len(ints), len(leaf[2]), len(floats), len(leaf[3])
+            ints.extend(leaf[2])
+            floats.extend(leaf[3])
+    return (arr, np.asarray(words, dtype=np.uint32).reshape(-1), np.asarray(ints, dtype=np.int64).reshape(-1),
+            np.asarray(floats, dtype=np.float64).reshape(-1))
+
+
+def dynamic_leaf_reference(leaf, tags: np.ndarray, payload: np.ndarray) -> np.ndarray:
+    """What rf_dynamic_match computes for one entry of Program.dynamic_leaves, in numpy: bool [n].  tags uint8
+    [n], payload int64 [n]: the key's tagged column (encode_dynamic)."""
+    kind = leaf[0]
+    tags = np.asarray(tags, dtype=np.uint8)
+    payload = np.ascontiguousarray(payload, dtype=np.int64)
+    if kind == "tags":
+        return (tags < 8) & (((leaf[2] >> np.minimum(tags, 7).astype(np.int64)) & 1) == 1)
+    if kind == "codeset":
+        words = np.asarray(leaf[2], dtype=np.uint32)
+        if words.size == 0:
+            return np.zeros(tags.size, bool)
+        ok = (tags == _lib.RF_DTAG_STRING) & (payload >= 0) & (payload < 32 * words.size)
+        w = words[np.clip(payload >> 5, 0, words.size - 1)]
+        return ok & (((w >> (payload & 31).astype(np.uint32)) & 1) == 1)
+    if kind == "bool":
+        ok = (tags == _lib.RF_DTAG_BOOL) & (payload >= 0) & (payload < 2)
+        return ok & (((leaf[2] >> np.clip(payload, 0, 1)) & 1) == 1)
+    is_int, is_f64 = tags == _lib.RF_DTAG_INT, tags == _lib.RF_DTAG_DOUBLE
+    x = payload.view(np.float64)
+    if kind == "nrange":
+        ilo, ihi, flags, lo, hi = leaf[2:7]
+        i_ok = (payload >= np.int64(ilo)) & (payload <= np.int64(ihi)) if ilo <= ihi else np.zeros(tags.size, bool)
+        with np.errstate(invalid="ignore"):
+            a = x >= lo if flags & _lib.RF_FRANGE_LO_INCL else x > lo
+            b = x <= hi if flags & _lib.RF_FRANGE_HI_INCL else x < hi
+        return (is_int & i_ok) | (is_f64 & a & b)
+    return (is_int & np.isin(payload, np.asarray(leaf[2], dtype=np.int64))) | \
+        (is_f64 & np.isin(x, np.asarray(leaf[3], dtype=np.float64)))
 
 
 def program_arrays(p: Program) -> tuple[np.ndarray, np.ndarray]:

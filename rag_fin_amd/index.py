@@ -1377,6 +1377,36 @@ def column_match(device, program: "filter_expr.Program", extra_columns: dict, n_
     return out
 
 
+def dynamic_match(device, program: "filter_expr.Program", columns: dict, n_rows: int, out=None):
+    """rf_dynamic_match of program.dynamic_leaves, enqueued on the current stream; no host sync.
+    columns: dynamic key -> (tags uint8 [n_rows], payload int64 [n_rows]) on the device.  -> the row bitmaps, an
+    int32 device tensor [D * ceil(n_rows / 32)] of uint32 bit patterns, leaf after leaf (`out`: a contiguous
+    int32 tensor of that size to write into).  One launch per RF_DYNAMIC_MAX_LEAVES leaves."""
+    torch = _torch()
+    lib = _lib.load_library()
+    D = len(program.dynamic_leaves)
+    nwords = (n_rows + 31) // 32
+    ptrs = {k: ((t.data_ptr(), p.data_ptr()) if t.numel() else (None, None)) for k, (t, p) in columns.items()}
+    arr, words, ints, floats = filter_expr.dynamic_leaf_arrays(program, ptrs)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(D * nwords, dtype=torch.int32, device=device)
+        elif out.numel() != D * nwords or out.dtype != torch.int32 or not out.is_contiguous():
+            raise ValueError(f"dynamic_match: out must be a contiguous int32 tensor of {D * nwords} words")
+        cs_d = torch.from_numpy(words.view(np.int32)).to(device) if words.size else None
+        is_d = torch.from_numpy(ints).to(device) if ints.size else None
+        fs_d = torch.from_numpy(floats).to(device) if floats.size else None
+        step = _lib.RF_DYNAMIC_MAX_LEAVES
+        for d0 in range(0, D, step):
+            d1 = min(D, d0 + step)
+            part = (_lib.DynamicLeaf * (d1 - d0)).from_buffer(arr, d0 * ctypes.sizeof(_lib.DynamicLeaf))
+            _lib.check(lib.rf_dynamic_match(part, d1 - d0, _ptr(cs_d), _ptr(is_d), _ptr(fs_d), n_rows,
+                                            c_void_p(out.data_ptr() + 4 * d0 * nwords) if nwords else None,
+                                            _lib.current_stream_ptr()))
+    # (the sets may be freed now: the caching allocator reuses their memory in stream order)
+    return out
+
+
 def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None, column_base: int = 0):
     """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
     rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors
@@ -1384,13 +1414,14 @@ def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bi
     bitmaps: SparseIndex.text_match(program.text_leaves), enqueued on the same stream, when the
     program has keyword leaves (rf_filter_eval_bitmaps).  With column leaves (program.column_leaves),
     bitmaps is the one flat int32 array that holds the keyword leaves' bitmaps (text_words_per_leaf(n_rows)
-    words each) and, from word column_base, the column leaves' (column_match; ceil(n_rows / 32) words each)."""
+    words each) and, from word column_base, the column leaves' (column_match; ceil(n_rows / 32) words each) and
+    behind them the dynamic leaves' (program.dynamic_leaves; dynamic_match, the same width)."""
     torch = _torch()
     lib = _lib.load_library()
     cs, rl = filter_expr.program_arrays(program)
-    if program.column_leaves:
+    if program.column_leaves or program.dynamic_leaves:
         ops = program.ops_ctypes(text_words_per_leaf(n_rows), column_base, (n_rows + 31) // 32)
-        if column_base + len(program.column_leaves) * ((n_rows + 31) // 32) > 0x7FFFFFFF:
+        if column_base + (len(program.column_leaves) + len(program.dynamic_leaves)) * ((n_rows + 31) // 32) > 0x7FFFFFFF:
             raise ValueError("filter expression: the leaves' bitmaps do not fit int32 word offsets")
     else:
         ops = program.ops_ctypes(0 if bitmaps is None else int(bitmaps.shape[1]))

@@ -50,7 +50,8 @@ class VectorRAG:
         ColBERT): declared on the store as its late-interaction field ("token_embeddings"), the second stage of
         search(..., rerank=True, rerank_with="late").
         extra_output_fields: names of the store's own fields (CorpusStore(fields=...)) whose values are added to
-        the context dicts under their names; by default the keys stay exactly the reference's."""
+        the context dicts under their names; by default the keys stay exactly the reference's.  On a store with
+        enable_dynamic_field a name that is no declared field is a dynamic key (None where a chunk lacks it)."""
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
@@ -62,7 +63,8 @@ class VectorRAG:
         if extra_output_fields:
             own = [f.name for f in getattr(store, "schema", ())]
             for name in extra_output_fields:
-                if name not in own:
+                if name not in own and not (getattr(store, "enable_dynamic_field", False) and isinstance(name, str)
+                                            and name not in OUTPUT_FIELDS):
                     raise ValueError(f"extra_output_fields: {name!r} is not a field the store declares"
                                      + (f" ({', '.join(own)})" if own else ""))
             self.extra_output_fields = tuple(dict.fromkeys(extra_output_fields))

@@ -2,8 +2,13 @@
 
 The reference's collection has seven fields ("chunking_storing (1).py":14-22); a pymilvus user declares
 further `FieldSchema`s of their own, and `DataType` / `FieldSchema` here take pymilvus' shape for the four
-scalar types this store serves: VARCHAR, INT64, DOUBLE and BOOL.  ARRAY, JSON, nullable and dynamic fields
-are not offered.
+scalar types this store serves: VARCHAR, INT64, DOUBLE and BOOL.  ARRAY, JSON and nullable fields are not
+offered.
+
+Dynamic fields (`CorpusStore(..., enable_dynamic_field=True)`, pymilvus' `$meta`): a row may carry keys that
+no FieldSchema declares.  A key is any non-empty string, a collection holds at most MAX_DYNAMIC_KEYS distinct
+ones, and a row holds under a key a bool, an int in the int64 range, a float (NaN and +-inf allowed) or a str
+-- or lacks the key (None).  Lists, dicts and everything else are refused (`check_dynamic`).
 """
 from __future__ import annotations
 
@@ -15,6 +20,7 @@ from typing import Any, Iterable, Sequence
 import numpy as np
 
 MAX_FIELDS = 32
+MAX_DYNAMIC_KEYS = 64   # distinct dynamic keys of one collection
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 
 # the reference's seven fields, the vector fields this store derives, and the words of the expression grammar
@@ -138,3 +144,58 @@ def column_from_json(field: FieldSchema, values) -> list:
     if field.dtype == DataType.DOUBLE:
         return [float(v) for v in values]
     return [check_value(field, v) for v in values]
+
+
+def dynamic_value(key: str, v):
+    """`v` as a dynamic key stores it (None = the row lacks the key | bool | int | float | str), or ValueError."""
+    if v is None or isinstance(v, str):
+        return v
+    if isinstance(v, (bool, np.bool_)):
+        return bool(v)
+    if isinstance(v, (int, np.integer)):
+        if not INT64_MIN <= int(v) <= INT64_MAX:
+            raise ValueError(f"dynamic field {key!r}: value {v!r} is outside the int64 range")
+        return int(v)
+    if isinstance(v, (float, np.floating)):
+        return float(v)
+    raise ValueError(f"dynamic field {key!r}: value {v!r} ({type(v).__name__}) is not a bool, an int, a float, a str "
+                     "or None (nested and ARRAY / JSON values are not supported)")
+
+
+def check_dynamic(columns: dict | None, n: int, held: Iterable[str] = (), what: str = "insert") -> dict:
+    """The dynamic columns of a batch of n rows as stored, {key: n values}; a key whose every value is None is
+    dropped.  ValueError: a key that is no non-empty string, a length other than n, a value dynamic_value
+    refuses, more than MAX_DYNAMIC_KEYS distinct keys together with `held` (the collection's).  Nothing is
+    changed."""
+    out = {}
+    for key, col in (columns or {}).items():
+        if not isinstance(key, str) or key == "":
+            raise ValueError(f"{what}: a dynamic key is a non-empty string, got {key!r}")
+        col = [None] * n if col is None else list(col)
+        if len(col) != n:
+            raise ValueError(f"{what} columns differ in length (dynamic field {key!r}: {len(col)} values for {n} rows)")
+        col = [dynamic_value(key, v) for v in col]
+        if any(v is not None for v in col):
+            out[key] = col
+    total = len(set(held) | set(out))
+    if total > MAX_DYNAMIC_KEYS:
+        raise ValueError(f"{what}: {total} distinct dynamic keys, a collection holds at most {MAX_DYNAMIC_KEYS}")
+    return out
+
+
+def dynamic_columns_of_rows(rows, n: int, what: str = "insert") -> dict:
+    """The $meta column of a column-major insert -- n dicts (or None), one per row -- as {key: n values}."""
+    rows = [None] * n if rows is None else list(rows)
+    if len(rows) != n:
+        raise ValueError(f"{what} columns differ in length ($meta: {len(rows)} values for {n} rows)")
+    out: dict = {}
+    for j, meta in enumerate(rows):
+        if meta is None:
+            continue
+        if not isinstance(meta, dict):
+            raise ValueError(f"{what}: the $meta column holds one dict (or None) per row, got {type(meta).__name__}")
+        for key, v in meta.items():
+            if not isinstance(key, str) or key == "":   # (before it becomes a dict key of its own)
+                raise ValueError(f"{what}: a dynamic key is a non-empty string, got {key!r}")
+            out.setdefault(key, [None] * n)[j] = v
+    return out

@@ -31,15 +31,17 @@ import os
 from . import chunker
 
 
-def extra_columns(fields, chunks, values=None) -> dict:
+def extra_columns(fields, chunks, values=None, dynamic: bool = False) -> dict:
     """The columns of a store's own fields for a list of chunks.  values: {field name: a constant, or a
     function of the chunk dict}; a field without an entry is read from the chunk dicts when every chunk holds
     its name, and is otherwise left to its default.  E.g. {"bank": "ICICI", "fiscal_year": lambda c:
-    2000 + int(c["period"][-2:])}."""
+    2000 + int(c["period"][-2:])}.
+    dynamic: the store has enable_dynamic_field: a name of `values` that is no declared field is a dynamic key
+    (its column follows the declared ones in the result); a function may return None: that chunk lacks the key."""
     values = dict(values or {})
     names = [f.name for f in fields]
     for name in values:
-        if name not in names:
+        if name not in names and not dynamic:
             raise ValueError(f"field_values: {name!r} is not a declared field" + (f" ({', '.join(names)})" if names else ""))
     out = {}
     for name in names:
@@ -48,6 +50,9 @@ def extra_columns(fields, chunks, values=None) -> dict:
             out[name] = [v(c) for c in chunks] if callable(v) else [v] * len(chunks)
         elif chunks and all(name in c for c in chunks):
             out[name] = [c[name] for c in chunks]
+    for name, v in values.items():
+        if name not in names:
+            out[name] = [v(c) for c in chunks] if callable(v) else [v] * len(chunks)
     return out
 
 
@@ -58,19 +63,24 @@ def ingest(store, embedder, chunks, upsert: bool = False, field_values: dict | N
     upsert=True: chunks whose id is already stored replace the stored rows (a restated
     quarter is re-ingested in place of dropping the collection); otherwise an existing id
     raises ValueError.
-    field_values: the values of the store's own fields (CorpusStore(fields=...)), as extra_columns takes them."""
+    field_values: the values of the store's own fields (CorpusStore(fields=...)), as extra_columns takes them;
+    on a store with enable_dynamic_field a name that is no declared field becomes a dynamic key."""
     if not chunks:
         return 0
     emb = embedder.encode_to_device([c["text"] for c in chunks])
     cols = chunker.insert_columns(chunks, emb)
     fields = getattr(store, "schema", ())
+    dynamic = bool(getattr(store, "enable_dynamic_field", False))
     if fields or field_values:
-        own = extra_columns(fields, chunks, field_values)
+        own = extra_columns(fields, chunks, field_values, dynamic)
         missing = [f.name for f in fields if f.name not in own and f.default is None]
         if missing:
             raise ValueError(f"ingest: no value for the field(s) {', '.join(missing)} (field_values, a key of the chunk "
                              "dicts, or a default)")
         cols = cols + [own.get(f.name) if f.name in own else [f.default] * len(chunks) for f in fields]
+        keys = [k for k in own if k not in {f.name for f in fields}]
+        if keys:   # the rows' $meta: the trailing column of insert / upsert
+            cols = cols + [[{k: own[k][j] for k in keys if own[k][j] is not None} for j in range(len(chunks))]]
     n = store.upsert(cols).upsert_count if upsert else store.insert(cols)
     store.flush()
     store.load()
@@ -109,7 +119,7 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
               hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None,
               sparse_dir: str | None = None, late_dir: str | None = None, fields=None, field_values: dict | None = None,
-              extra_output_fields=None):
+              extra_output_fields=None, enable_dynamic_field: bool = False):
     """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
     can run; its posting lists are built by the first such search.
     sparse_dir: a local SPLADE checkpoint: the learned sparse field is declared on the store (VectorRAG does
@@ -117,12 +127,15 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     late_dir: a local ColBERT checkpoint: the late-interaction field is declared on the store (VectorRAG does it),
     its token vectors are encoded by the first search(..., rerank=True, rerank_with="late").
     fields: FieldSchema objects of the collection's own scalar fields (rag_fin_amd.schema); field_values: their
-    values per chunk, as extra_columns takes them; extra_output_fields: those of them the context dicts carry."""
+    values per chunk, as extra_columns takes them; extra_output_fields: those of them the context dicts carry.
+    enable_dynamic_field: the store takes keys no field declares (a name of field_values that is no declared field
+    becomes one; extra_output_fields may name them)."""
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
     embedder = Embedder.from_local(model_dir, device=device)
-    store = CorpusStore(collection_name, dim=embedder.dim, device=device, **({"fields": fields} if fields else {}))
+    store = CorpusStore(collection_name, dim=embedder.dim, device=device, **({"fields": fields} if fields else {}),
+                        **({"enable_dynamic_field": True} if enable_dynamic_field else {}))
     ingest(store, embedder, chunker.build_all_chunks(data_dir), **({"field_values": field_values} if field_values else {}))
     if hybrid:
         store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})

@@ -43,12 +43,16 @@ def _torch():
 
 class ShardedCorpusStore(CorpusStore):
     def __init__(self, name: str = "fin_chunks", dim: int = 384, capacity: int = 4096, device=None,
-                 metric_type: str = "COSINE", group=None, index=None, backend=None, fields=None):
+                 metric_type: str = "COSINE", group=None, index=None, backend=None, fields=None,
+                 enable_dynamic_field: bool = False):
         """capacity: rows of THIS rank's shard to reserve (grows on demand).  index / backend:
         test doubles (CPU); the product builds a GpuIndex + HipShardBackend."""
         import torch.distributed as dist
         if fields:
             raise NotImplementedError("user-defined scalar fields (fields=) are not implemented for the sharded store "
+                                      "(single-GPU CorpusStore only)")
+        if enable_dynamic_field:
+            raise NotImplementedError("dynamic fields (enable_dynamic_field) are not implemented for the sharded store "
                                       "(single-GPU CorpusStore only)")
         if not dist.is_initialized():
             raise RuntimeError("ShardedCorpusStore needs an initialised torch.distributed process group "
@@ -410,6 +414,9 @@ class ShardedCorpusStore(CorpusStore):
         if meta.get("fields"):
             raise NotImplementedError(f"{path} holds user-defined scalar fields, which are not implemented for the "
                                       "sharded store (single-GPU CorpusStore only)")
+        if meta.get("enable_dynamic_field"):
+            raise NotImplementedError(f"{path} holds dynamic fields, which are not implemented for the sharded store "
+                                      "(single-GPU CorpusStore only)")
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         lo, hi = ShardedSearcher.shard_bounds(n, world, rank)
         cap = max(capacity or 0, hi - lo, 1)

@@ -42,8 +42,8 @@ from . import schema as schema_
 from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, column_match, eval_filter,  # noqa: F401
-                    filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, column_match, dynamic_match,  # noqa: F401
+                    eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
                     plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
 from .ranker import BoostRanker, check_rankers, class_weights  # noqa: F401
 
@@ -240,6 +240,39 @@ class _ExtraColumn:
     def compact(self, k) -> None:
         """Keep rows k (ascending, an int64 device tensor) of a mirror synced to the whole collection."""
         self.data = self.data.index_select(0, k)
+        self.n = int(k.numel())
+
+
+class _DynamicColumn:
+    """The device mirror of one dynamic key: a tag per row (uint8: absent | bool | int | double | string) and 8
+    bytes of payload (int64 | fp64 bits | 0 / 1 | the string's code into an append-only dictionary in first-seen
+    order) -- 9 bytes per row.  Synced lazily from the host list like _ExtraColumn."""
+
+    def __init__(self, device):
+        torch = _torch()
+        self.device = device
+        self.dict: list = []
+        self._code: dict = {}
+        self.tags = torch.empty(0, dtype=torch.uint8, device=device)
+        self.payload = torch.empty(0, dtype=torch.int64, device=device)
+        self.n = 0
+
+    def sync(self, values: list, n: int) -> None:
+        torch = _torch()
+        if n < self.n:   # a shorter collection: re-encode from row 0 (the dictionary stays)
+            self.tags, self.payload = self.tags[:0], self.payload[:0]
+            self.n = 0
+        if n == self.n:
+            return
+        tags, payload = filter_expr.encode_dynamic(values[self.n:n], self._code, self.dict)
+        self.tags = torch.cat([self.tags, torch.from_numpy(tags).to(self.device)])
+        self.payload = torch.cat([self.payload, torch.from_numpy(payload).to(self.device)])
+        self.n = n
+
+    def compact(self, k) -> None:
+        """Keep rows k (ascending, an int64 device tensor) of a mirror synced to the whole collection."""
+        self.tags = self.tags.index_select(0, k)
+        self.payload = self.payload.index_select(0, k)
         self.n = int(k.numel())
 
 
@@ -455,14 +488,27 @@ class CorpusStore:
     # whose __init__ does not call this one is a store without extra fields.
     schema: tuple = ()
     _xcols = None        # {(field, coded): _ExtraColumn}, built by the first filter / grouping that reads the field
+    # dynamic fields (pymilvus' enable_dynamic_field / $meta): {key: column of num_entities values, None where
+    # the row lacks the key} for every key some row holds, and the mirrors of the keys an expression has read
+    enable_dynamic_field = False
+    dynamic: dict = {}
+    _dyncols = None      # {key: _DynamicColumn}
 
     def __init__(self, name: str = "fin_chunks", dim: int = 384, capacity: int = 4096,
-                 device=None, metric_type: str = "COSINE", index=None, fields=None):
+                 device=None, metric_type: str = "COSINE", index=None, fields=None, enable_dynamic_field: bool = False):
         """fields: FieldSchema objects (rag_fin_amd.schema) of extra scalar fields next to the reference's
         seven: VARCHAR, INT64, DOUBLE or BOOL, at most 32.  They are inserted (add(extra=), the columns after
         primary_value of insert / upsert), filtered on in expr, grouped by, returned as output fields, and
-        saved and loaded like `period`."""
+        saved and loaded like `period`.
+        enable_dynamic_field: rows may carry keys that no field declares (pymilvus' $meta; schema.py): a key of
+        add(extra=) that is no declared field, or the dict of a trailing column of insert / upsert.  At most 64
+        distinct keys; a value is a bool, an int64, a float, a str or None.  Such a key is filtered on in expr
+        (bare, or as $meta["key"]; filter_expr's docstring has the semantics) and returned as an output field,
+        as is "$meta" (the dict of the keys a row holds)."""
         self.schema = schema_.check_fields(fields)
+        self.enable_dynamic_field = bool(enable_dynamic_field)
+        self.dynamic = {}
+        self._dyncols = None
         self.name = name
         self.dim = dim
         self.metric_type = metric_type.upper()
@@ -531,8 +577,10 @@ class CorpusStore:
             for col in self.columns.values():
                 col.clear()
             self._pk_row.clear()
+            self.dynamic = {}
             self._dcols = None
             self._xcols = None
+            self._dyncols = None
             self._sparse = None
             self._forget_lexical()
             self._learned_rows = None
@@ -758,13 +806,25 @@ class CorpusStore:
             chunk_types: Sequence[str], statement_types: Sequence[str],
             primary_values: Sequence[float], extra: dict | None = None) -> int:
         """extra: {field name: column} for the collection's own fields (schema.py); a field that is not given
-        takes its default, and has to have one."""
+        takes its default, and has to have one.  With enable_dynamic_field a key that is no declared field is a
+        dynamic key: its column holds a bool, an int, a float, a str or None (the row lacks the key) per row."""
         cols = (texts, periods, chunk_types, statement_types, primary_values)
         with self._rw.write():
-            xcols = schema_.check_columns(self.schema, extra, len(ids), "insert")   # before anything changes
+            xcols, dyn = self._check_extra(extra, len(ids), "insert")   # before anything changes
             self._store_vectors(self._check_batch(ids, cols, embeddings, len(ids), "insert"))
-            self._append_rows(ids, cols, xcols)
+            self._append_rows(ids, cols, xcols, dyn)
         return len(ids)
+
+    def _check_extra(self, extra, n: int, what: str):
+        """`extra` of an insert / upsert -> (the declared fields' columns in schema order, {dynamic key:
+        column}), everything checked and nothing changed."""
+        if not self.enable_dynamic_field:
+            return schema_.check_columns(self.schema, extra, n, what), {}
+        names = {f.name for f in self.schema}
+        extra = dict(extra or {})
+        own = {k: v for k, v in extra.items() if k in names}
+        dyn = schema_.check_dynamic({k: v for k, v in extra.items() if k not in names}, n, self.dynamic, what)
+        return schema_.check_columns(self.schema, own, n, what), dyn
 
     def _check_batch(self, ids, cols, embeddings, n_vec_rows: int, what: str):
         """Everything an insert / upsert (`what`) refuses, checked before anything changes; returns
@@ -801,9 +861,9 @@ class CorpusStore:
             self._grow(need)
         self.index.add(vec)
 
-    def _append_rows(self, ids, cols, xcols=()) -> None:
-        """The host side of an append: the pk map, the six scalar columns and the checked extra columns
-        (schema.check_columns: in schema order)."""
+    def _append_rows(self, ids, cols, xcols=(), dyn=None) -> None:
+        """The host side of an append: the pk map, the six scalar columns, the checked extra columns
+        (schema.check_columns: in schema order) and the checked dynamic columns (schema.check_dynamic)."""
         texts, periods, chunk_types, statement_types, primary_values = cols
         self._sparse = None   # the lexical index is brought up to date by the next BM25 search (DESIGN §4.4k)
         self._log_lexical("append", list(texts))
@@ -820,14 +880,30 @@ class CorpusStore:
         self.columns["primary_value"].extend(float(v) for v in primary_values)
         for f, col in zip(self.schema, xcols):
             self.columns[f.name].extend(col)
+        if self.enable_dynamic_field:
+            dyn = dyn or {}
+            for key in dyn:
+                if key not in self.dynamic:
+                    self.dynamic[key] = [None] * base   # the rows so far lack the key
+            for key, col in self.dynamic.items():
+                col.extend(dyn.get(key) or [None] * len(ids))
 
     def _split_extra(self, data, what: str):
         """Column-major `data` of 7 + len(schema) columns -> (the reference's seven, {field: column}): the
-        collection's own fields follow primary_value in schema order."""
+        collection's own fields follow primary_value in schema order.  With enable_dynamic_field one more column
+        may follow them: the rows' $meta, a dict (or None) per row, whose keys join the {field: column}."""
+        S = len(self.schema)
+        if self.enable_dynamic_field and len(data) == 8 + S:
+            extra = schema_.dynamic_columns_of_rows(data[7 + S], len(data[0]), what)
+            declared = [f.name for f in self.schema if f.name in extra]
+            if declared:
+                raise ValueError(f"{what}: $meta holds the declared field {declared[0]!r}; it has a column of its own")
+            extra.update({f.name: col for f, col in zip(self.schema, data[7:7 + S])})
+            return list(data[:7]), extra
         if not self.schema:
             return data, None
-        if len(data) != 7 + len(self.schema):
-            raise ValueError(f"{what} expects {7 + len(self.schema)} columns: id, text, embedding, period, chunk_type, "
+        if len(data) != 7 + S:
+            raise ValueError(f"{what} expects {7 + S} columns: id, text, embedding, period, chunk_type, "
                              f"statement_type, primary_value, {', '.join(f.name for f in self.schema)}")
         return list(data[:7]), {f.name: col for f, col in zip(self.schema, data[7:])}
 
@@ -870,11 +946,11 @@ class CorpusStore:
         ids, cols, emb = self._split_columns(data, "upsert")
         ids = list(ids)
         with self._rw.write():
-            xcols = schema_.check_columns(self.schema, extra, len(ids), "upsert")
+            xcols, dyn = self._check_extra(extra, len(ids), "upsert")
             vec = self._check_batch(ids, cols, emb, len(ids), "upsert")   # before any row goes
             self._delete_mask(self._pk_mask(ids))
             self._store_vectors(vec)
-            self._append_rows(ids, cols, xcols)
+            self._append_rows(ids, cols, xcols, dyn)
         return MutationResult(ids, insert_count=len(ids), upsert_count=len(ids))
 
     def _match_mask(self, expr: str) -> np.ndarray:
@@ -882,9 +958,9 @@ class CorpusStore:
         n = self.num_entities
         if n == 0:
             with self._filter_lock:   # still reject a bad expression
-                filter_expr.compile_expr(filter_expr.parse(expr, self.analyzer, self.schema),
+                filter_expr.compile_expr(filter_expr.parse(expr, self.analyzer, self.schema, self.enable_dynamic_field),
                                          {f: [] for f in filter_expr.VARCHAR_FIELDS}, {},
-                                         None if self._sparse_params is None else {}, self.schema, {})
+                                         None if self._sparse_params is None else {}, self.schema, {}, {})
             return np.zeros(0, dtype=bool)
         return filter_mask_bits(self.build_filter(expr), n)
 
@@ -915,6 +991,10 @@ class CorpusStore:
         for f in list(self.columns):
             self.columns[f] = list(itertools.compress(self.columns[f], sel))
         self._pk_row = dict(zip(self.columns["id"], range(keep.size)))
+        # (a key that no surviving row holds is gone, as in a fresh store of the surviving rows)
+        self.dynamic = {key: col for key, col in ((key, list(itertools.compress(col, sel)))
+                                                  for key, col in self.dynamic.items())
+                        if any(v is not None for v in col)}
         with self._filter_lock:
             if self._dcols is not None:
                 if self._dcols.n == n_old:
@@ -928,6 +1008,13 @@ class CorpusStore:
                     for c in synced.values():
                         c.compact(k)
                 self._xcols = synced
+            if self._dyncols:
+                synced = {key: c for key, c in self._dyncols.items() if c.n == n_old and key in self.dynamic}
+                if synced:
+                    k = _torch().from_numpy(np.ascontiguousarray(keep, dtype=np.int64)).to(self.index.device)
+                    for c in synced.values():
+                        c.compact(k)
+                self._dyncols = synced
         return MutationResult(pks, delete_count=len(pks))
 
     def _compact_index(self, keep_mask: np.ndarray, keep: np.ndarray) -> None:
@@ -971,6 +1058,16 @@ class CorpusStore:
         if col is None:
             col = self._xcols[key] = _ExtraColumn(self.index.device, field.dtype, coded)
         col.sync(self.columns[field.name], self.num_entities)
+        return col
+
+    def _dynamic_column(self, key: str) -> _DynamicColumn:
+        """The synced device mirror of a dynamic key some row holds.  Caller holds `_filter_lock`."""
+        if self._dyncols is None:
+            self._dyncols = {}
+        col = self._dyncols.get(key)
+        if col is None:
+            col = self._dyncols[key] = _DynamicColumn(self.index.device)
+        col.sync(self.dynamic[key], self.num_entities)
         return col
 
     def _field(self, name: str):
@@ -1300,6 +1397,8 @@ class CorpusStore:
         own = self._field(field)
         if own is not None and own.dtype == DataType.DOUBLE:
             raise ValueError(f"group_by_field {field!r}: a DOUBLE field cannot be grouped by")
+        if self.enable_dynamic_field and field != "id" and field not in self.GROUP_BY_FIELDS and own is None:
+            raise ValueError(f"group_by_field {field!r}: a dynamic key cannot be grouped by")
         if field != "id" and field not in self.GROUP_BY_FIELDS and own is None:
             raise ValueError(f"group_by_field {field!r}: only {', '.join(self.GROUP_BY_FIELDS)} (or id) can be grouped by")
         if isinstance(group_size, bool) or not isinstance(group_size, (int, np.integer)) or group_size < 1:
@@ -1322,11 +1421,28 @@ class CorpusStore:
                                          and all(isinstance(t, str) for t in data))
 
     def _check_output_fields(self, output_fields) -> list:
+        """With enable_dynamic_field a name that is no field is a dynamic key (the value, or None where the row
+        lacks it), and "$meta" is the dict of the keys the row holds."""
         fields = list(output_fields or [])
         for f in fields:
-            if f not in self.columns:
+            if f not in self.columns and not (self.enable_dynamic_field and isinstance(f, str)):
                 raise KeyError(f"unknown output field {f!r}")
         return fields
+
+    def _entity(self, r: int, fields) -> dict:
+        """The output fields of row r."""
+        if not self.enable_dynamic_field:
+            return {f: self.columns[f][r] for f in fields}
+        out = {}
+        for f in fields:
+            if f in self.columns:
+                out[f] = self.columns[f][r]
+            elif f == filter_expr.META:
+                out[f] = {key: col[r] for key, col in self.dynamic.items() if col[r] is not None}
+            else:
+                col = self.dynamic.get(f)
+                out[f] = None if col is None else col[r]
+        return out
 
     def _check_sparse_search(self, data, param, limit) -> list:
         """Everything a BM25 search refuses -> the query strings."""
@@ -1661,7 +1777,7 @@ class CorpusStore:
         for r, s in zip(rows.tolist(), scores.tolist()):
             if r < 0:
                 break
-            hits.append(Hit(r, self.columns["id"][r], float(s), {f: self.columns[f][r] for f in fields}))
+            hits.append(Hit(r, self.columns["id"][r], float(s), self._entity(r, fields)))
         return hits
 
     def _dense_arm(self, q16, limit: int, expr):
@@ -1766,10 +1882,7 @@ class CorpusStore:
         metric = (param or {}).get("metric_type", self.metric_type).upper()
         if metric != self.metric_type:
             raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
-        fields = list(output_fields or [])
-        for f in fields:
-            if f not in self.columns:
-                raise KeyError(f"unknown output field {f!r}")
+        fields = self._check_output_fields(output_fields)
         band = self._band_of(param)
         kw = {} if band is None else {"band": band}
         if mmr is not None:
@@ -1793,8 +1906,7 @@ class CorpusStore:
                     if group is not None:
                         continue
                     break
-                hits.append(Hit(r, self.columns["id"][r], float(scores[b, j]),
-                                {f: self.columns[f][r] for f in fields}))
+                hits.append(Hit(r, self.columns["id"][r], float(scores[b, j]), self._entity(r, fields)))
             out.append(hits)
         return out
 
@@ -1854,6 +1966,9 @@ class CorpusStore:
                 "metric_type": self.metric_type, "n": n, "columns": self.columns}
         if self.schema:   # (directories of a store without fields of its own stay exactly as before)
             meta["fields"] = [f.to_dict() for f in self.schema]
+        if self.enable_dynamic_field:   # (None -> null; json keeps 3 apart from 3.0 and true apart from 1)
+            meta["enable_dynamic_field"] = True
+            meta["dynamic"] = self.dynamic
         if self.index_type != "FLAT":   # FLAT directories stay exactly as before
             meta["index_type"] = self.index_type
         if self._sparse_params is not None:   # (and so do directories without a lexical index)
@@ -1895,6 +2010,8 @@ class CorpusStore:
         self.columns = {f: list(cols[f]) for f in SCALAR_FIELDS}
         for f in self.schema:
             self.columns[f.name] = schema_.column_from_json(f, cols[f.name])
+        if self.enable_dynamic_field:
+            self.dynamic = schema_.check_dynamic(meta.get("dynamic"), n, what=path)
         self._pk_row = {pk: i for i, pk in enumerate(self.columns["id"])}
 
     @classmethod
@@ -1905,7 +2022,8 @@ class CorpusStore:
         meta, n, dim = cls._read_meta(path)
         st = cls(meta["name"], dim=dim, capacity=max(capacity or 0, n, 1), device=device,
                  metric_type=meta["metric_type"],
-                 **({"fields": [FieldSchema.from_dict(d) for d in meta["fields"]]} if meta.get("fields") else {}))
+                 **({"fields": [FieldSchema.from_dict(d) for d in meta["fields"]]} if meta.get("fields") else {}),
+                 **({"enable_dynamic_field": True} if meta.get("enable_dynamic_field") else {}))
         st._load_rows(path, n, 0, n, chunk_rows)
         st._adopt_columns(path, meta, n)
         itype = meta.get("index_type", "FLAT")   # a missing key means FLAT
@@ -1934,7 +2052,7 @@ class CorpusStore:
         holds the WRITE side, so nothing here may ask for it again), then `_sparse_lock` (inside
         _sparse_index and _text_index, released before the next), then `_filter_lock`, then the
         SparseIndex's own `_lock` (inside text_match).  No path takes them the other way round."""
-        node = filter_expr.parse(expr, self.analyzer, self.schema)
+        node = filter_expr.parse(expr, self.analyzer, self.schema, self.enable_dynamic_field)
         term_id, sp = self._text_index(filter_expr.text_leaves(node))
         with self._filter_lock:
             n = self.num_entities
@@ -1942,19 +2060,29 @@ class CorpusStore:
                 self._dcols = _DeviceColumns(self.index.device)
             self._dcols.sync(self.columns, n)
             own = {f.name: self._extra_column(f) for f in self.schema if f.name in filter_expr.fields_of(node)}
+            # (only the dynamic keys this expression reads, and of those the ones some row holds, are mirrored)
+            dyn = {key: self._dynamic_column(key) for key in sorted(filter_expr.dynamic_keys_of(node))
+                   if key in self.dynamic} if self.enable_dynamic_field else None
             prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row, term_id, self.schema,
-                                            {name: c.dict for name, c in own.items() if c.coded})
-            if not prog.column_leaves:
+                                            {name: c.dict for name, c in own.items() if c.coded},
+                                            None if dyn is None else {key: c.dict for key, c in dyn.items()})
+            if not prog.column_leaves and not prog.dynamic_leaves:
                 bitmaps = sp.text_match(prog.text_leaves) if prog.text_leaves else None
                 return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps)
             # leaves over the collection's own fields: rf_column_match writes their row bitmaps behind the
             # keyword leaves', into the one array the program's RF_FOP_BITMAP leaves index
-            T, C = len(prog.text_leaves), len(prog.column_leaves)
+            # and rf_dynamic_match the dynamic leaves' behind those
+            T, C, D = len(prog.text_leaves), len(prog.column_leaves), len(prog.dynamic_leaves)
             base, nwords = T * text_words_per_leaf(n), (n + 31) // 32
-            bitmaps = _torch().empty(base + C * nwords, dtype=_torch().int32, device=self.index.device)
+            mid = base + C * nwords
+            bitmaps = _torch().empty(mid + D * nwords, dtype=_torch().int32, device=self.index.device)
             if T:
                 sp.text_match(prog.text_leaves, out=bitmaps[:base].view(T, -1))
-            column_match(self.index.device, prog, {name: c.data for name, c in own.items()}, n, out=bitmaps[base:])
+            if C:
+                column_match(self.index.device, prog, {name: c.data for name, c in own.items()}, n, out=bitmaps[base:mid])
+            if D:
+                dynamic_match(self.index.device, prog, {key: (c.tags, c.payload) for key, c in dyn.items()}, n,
+                              out=bitmaps[mid:])
             return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps, column_base=base)
 
     def _text_index(self, leaves):
@@ -2008,10 +2136,7 @@ class CorpusStore:
     def _query(self, expr, limit, output_fields, offset: int = 0) -> list[dict]:
         fields = list(output_fields or ["id"])
         want_vec = "embedding" in fields
-        fields = [f for f in fields if f != "embedding"]
-        for f in fields:
-            if f not in self.columns:
-                raise KeyError(f"unknown output field {f!r}")
+        fields = self._check_output_fields(f for f in fields if f != "embedding")
         if expr is None or expr.strip() == "":
             rows = list(range(self.num_entities))
         else:
@@ -2028,7 +2153,7 @@ class CorpusStore:
             if (want_vec and rows) else None
         out = []
         for j, r in enumerate(rows):
-            rec = {f: self.columns[f][r] for f in fields}
+            rec = self._entity(r, fields)
             if "id" not in rec:
                 rec["id"] = self.columns["id"][r]
             if vecs is not None:
