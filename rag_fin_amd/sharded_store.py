@@ -30,7 +30,7 @@ import threading
 
 from . import _lib, filter_expr
 from .sharded import HipShardBackend, ShardedSearcher
-from .store import LEARNED_FIELD, TOKEN_FIELD, CorpusStore, MutationResult, _id_in_keys, check_offset
+from .store import CorpusStore, MutationResult, _id_in_keys, check_offset
 
 
 logger = logging.getLogger(__name__)
@@ -126,11 +126,9 @@ class ShardedCorpusStore(CorpusStore):
         if field_name == "sparse":
             raise NotImplementedError("the lexical (BM25) index is not implemented for the sharded store "
                                       "(single-GPU CorpusStore only)")
-        if field_name == LEARNED_FIELD:
-            raise NotImplementedError("the learned sparse field (sparse_embedding) is not implemented for the sharded "
-                                      "store (single-GPU CorpusStore only)")
-        if field_name == TOKEN_FIELD:
-            raise NotImplementedError("the late-interaction field (token_embeddings) is not implemented for the sharded "
+        field = self._text_field(field_name)
+        if field is not None:
+            raise NotImplementedError(f"the {field.form} field ({field.name}) is not implemented for the sharded "
                                       "store (single-GPU CorpusStore only)")
         itype, metric = self._check_index_params(field_name, dict(index_params or {}))
         if itype == "SQ8":
@@ -140,18 +138,18 @@ class ShardedCorpusStore(CorpusStore):
             self._index_params = {"index_type": itype, "metric_type": metric,
                                   "params": dict((index_params or {}).get("params") or {})}
 
+    def _refuse_encoded_field(self, kwargs) -> None:
+        """(The lexical index is never declared here: dropping it changes nothing and has_index says no.)"""
+        field = self._text_field(kwargs.get("field_name"), kwargs.get("index_name"))
+        if field is not None and field.encoder_attrs:
+            raise NotImplementedError(f"the {field.form} field ({field.name}) is not implemented for the sharded store")
+
     def drop_index(self, **kwargs) -> None:
-        if self._is_learned_field(kwargs):
-            raise NotImplementedError("the learned sparse field (sparse_embedding) is not implemented for the sharded store")
-        if self._is_token_field(kwargs):
-            raise NotImplementedError("the late-interaction field (token_embeddings) is not implemented for the sharded store")
+        self._refuse_encoded_field(kwargs)
         super().drop_index(**kwargs)
 
     def has_index(self, **kwargs) -> bool:
-        if self._is_learned_field(kwargs):
-            raise NotImplementedError("the learned sparse field (sparse_embedding) is not implemented for the sharded store")
-        if self._is_token_field(kwargs):
-            raise NotImplementedError("the late-interaction field (token_embeddings) is not implemented for the sharded store")
+        self._refuse_encoded_field(kwargs)
         return super().has_index(**kwargs)
 
     # -- mutation (COLLECTIVE) ----------------------------------------------------------------------
@@ -314,15 +312,10 @@ class ShardedCorpusStore(CorpusStore):
         if check_offset(offset, param, limit):
             # (a page past the first 64 hits needs the search-after sweep on every shard and a merge per page)
             raise NotImplementedError("paged search (offset) is not implemented for the sharded store")
-        if anns_field == "sparse":
-            # (the texts are replicated, but no rank holds posting lists)
-            raise NotImplementedError("BM25 search (anns_field='sparse') is not implemented for the sharded store")
-        if anns_field == LEARNED_FIELD:
-            raise NotImplementedError("learned sparse search (anns_field='sparse_embedding') is not implemented for "
-                                      "the sharded store")
-        if anns_field == TOKEN_FIELD:
-            raise NotImplementedError("late-interaction search (anns_field='token_embeddings') is not implemented for "
-                                      "the sharded store")
+        field = self._text_field(anns_field)
+        if field is not None:
+            # (the texts are replicated, but no rank holds posting lists or encoded rows)
+            raise NotImplementedError(f"{field.where} is not implemented for the sharded store")
         if mmr_lambda is not None or mmr_fetch_k is not None:
             # (the candidate vectors live on different ranks)
             raise NotImplementedError("diversified search (mmr_lambda) is not implemented for the sharded store")

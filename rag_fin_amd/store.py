@@ -37,7 +37,6 @@ import numpy as np
 
 from . import _lib
 from . import filter_expr
-from . import lexical
 from . import schema as schema_
 from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
@@ -46,6 +45,7 @@ from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, col
                     eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
                     plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
 from .ranker import BoostRanker, check_rankers, class_weights  # noqa: F401
+from .text_fields import LEARNED_FIELD, TOKEN_FIELD, LearnedSparseField, LexicalField, TokenVectorField, is_text  # noqa: F401
 
 
 SCALAR_FIELDS = ("id", "text", "period", "chunk_type", "statement_type", "primary_value")
@@ -342,10 +342,6 @@ class _RWLock:
                 self._cond.notify_all()
 
 
-LEARNED_FIELD = "sparse_embedding"   # the learned sparse field (create_index(..., encoder=))
-TOKEN_FIELD = "token_embeddings"     # the late-interaction field (create_index(..., encoder=))
-
-
 class MutationResult:
     """What delete / upsert return, shaped like pymilvus' MutationResult."""
 
@@ -493,6 +489,7 @@ class CorpusStore:
     enable_dynamic_field = False
     dynamic: dict = {}
     _dyncols = None      # {key: _DynamicColumn}
+    _text_fields: dict = {}   # the fields derived from the text column, by name (a subclass that skips __init__ has none)
 
     def __init__(self, name: str = "fin_chunks", dim: int = 384, capacity: int = 4096,
                  device=None, metric_type: str = "COSINE", index=None, fields=None, enable_dynamic_field: bool = False):
@@ -527,33 +524,10 @@ class CorpusStore:
         self._rw = _RWLock()
         self.index_type = "FLAT"            # create_index: "FLAT" (IVF_FLAT is served as FLAT) or "SQ8"
         self._index_params = None           # what create_index was given (None: no create_index call)
-        # the lexical index (create_index("sparse", ...)): its parameters, and the SparseIndex built from
-        # the text column by the first BM25 search after a change of the rows (None: to be built)
-        self._sparse_params = None
-        self._sparse = None
-        # (the token positions a PHRASE_MATCH filter needs live on that SparseIndex: attached once,
-        # by the first such filter, and gone with it on any mutation)
+        # the fields derived from the text column (text_fields.py: the lexical index, the learned sparse field, the
+        # late-interaction field), each with its declaration and what it built, and the one lock all three build under
         self._sparse_lock = threading.Lock()
-        # the learned sparse field (create_index("sparse_embedding", ..., encoder=)): the attached encoder, the
-        # per-row term vectors of the rows encoded so far as host CSR (indptr int64, indices int32, data fp32: a
-        # prefix of the rows; the rest is encoded by the next search) and the (postings, SparseIndex) over them
-        # (None: to be transposed again).  Guarded like the lexical index.
-        self._learned = None
-        self._learned_rows = None
-        self._learned_index = None
-        # the late-interaction field (create_index("token_embeddings", ..., encoder=)): the attached encoder and
-        # the token vectors of the rows encoded so far (late_interaction.TokenField: device CSR over a prefix of
-        # the rows, grown by doubling; the rest is encoded by the next search).  Guarded like the learned field.
-        self._tokens = None
-        self._token_field = None
-        # index maintenance: the last built (postings, SparseIndex, analyzer, params) and, in
-        # order, the mutations since -- ("delete", keep mask) / ("append", texts) -- which the next
-        # _sparse_index() replays through SparseIndex.compacted / .appended instead of building whole.
-        # Written under the write lock, replayed under `_sparse_lock` with the read side held.
-        self._lexical_kept = None
-        self._lexical_log: list = []
-        self.lexical_fallback_reason = None   # why the device route last gave way to the host's (None: it never did)
-        self._lexical_route = "host"        # what built the retained index whole: "host" or "device" 
+        self._text_fields = {f.name: f for f in (LexicalField(self), LearnedSparseField(self), TokenVectorField(self))}
         # bumped by every change of the rows (insert, delete, upsert, drop): a search_iterator's
         # bound is a row number, so it refuses to go on once this has moved
         self._mutations = 0
@@ -581,28 +555,15 @@ class CorpusStore:
             self._dcols = None
             self._xcols = None
             self._dyncols = None
-            self._sparse = None
-            self._forget_lexical()
-            self._learned_rows = None
-            self._learned_index = None
-            self._token_field = None
+            for field in self._text_fields.values():
+                field.reset()
 
-    def _forget_lexical(self) -> None:
-        """Drop the retained lexical state: the next _sparse_index() builds whole."""
-        self._lexical_kept = None
-        self._lexical_log = []
+    LEXICAL_LOG_MAX = 64   # pending mutations the lexical field replays; beyond, it builds whole
 
-    def _log_lexical(self, kind: str, arg) -> None:
-        """Record a mutation for the next replay (caller holds the write lock).  A log longer than
-        LEXICAL_LOG_MAX is not worth replaying step by step: the state is dropped."""
-        if self._lexical_kept is None:
-            return
-        if len(self._lexical_log) >= self.LEXICAL_LOG_MAX:
-            self._forget_lexical()
-            return
-        self._lexical_log.append((kind, arg))
-
-    LEXICAL_LOG_MAX = 64
+    # (the two the store itself turns to: for keyword filters and columns.json; for token_vectors and rerank_tokens)
+    _lexical = property(lambda self: self._text_fields[LexicalField.name])
+    _late = property(lambda self: self._text_fields[TokenVectorField.name])
+    lexical_fallback_reason = property(lambda self: self._lexical.fallback_reason)
 
     @property
     def num_entities(self) -> int:
@@ -660,25 +621,11 @@ class CorpusStore:
         encoded and appended to the device CSR, a delete drops its rows from it, so the field always equals
         that of a fresh store.  It is not saved: a loaded store encodes again."""
         params = dict(index_params or {})
-        if field_name == TOKEN_FIELD:
-            self._check_token_params(params, kwargs.get("encoder"))
+        field = self._text_field(field_name)
+        if field is not None:
+            checked = field.check_params(params, kwargs.get("encoder"))
             with self._rw.write():
-                self._tokens = {"encoder": kwargs["encoder"]}
-                self._token_field = None
-            return
-        if field_name == LEARNED_FIELD:
-            self._check_learned_params(params, kwargs.get("encoder"))
-            with self._rw.write():
-                self._learned = {"encoder": kwargs["encoder"]}
-                self._learned_rows = None
-                self._learned_index = None
-            return
-        if field_name == "sparse":
-            sparse = self._check_sparse_params(params)
-            with self._rw.write():
-                self._sparse_params = sparse
-                self._sparse = None
-                self._forget_lexical()
+                field.declare(checked)
             return
         itype, metric = self._check_index_params(field_name, params)
         with self._rw.write():
@@ -703,84 +650,18 @@ class CorpusStore:
             raise ValueError("create_index: params must be a dict")
         return itype, metric
 
-    @staticmethod
-    def _check_sparse_params(params) -> dict:
-        itype = str(params.get("index_type", "SPARSE_INVERTED_INDEX")).upper()
-        if itype != "SPARSE_INVERTED_INDEX":
-            raise ValueError(f"create_index: the sparse field takes index_type SPARSE_INVERTED_INDEX, got {itype!r}")
-        metric = str(params.get("metric_type", "BM25")).upper()
-        if metric != "BM25":
-            raise ValueError(f"create_index: the sparse field takes metric_type BM25, got {metric!r}")
-        p = params.get("params")
-        if p is not None and not isinstance(p, dict):
-            raise ValueError("create_index: params must be a dict")
-        k1, b = lexical.check_bm25_params((p or {}).get("bm25_k1", lexical.DEFAULT_K1),
-                                          (p or {}).get("bm25_b", lexical.DEFAULT_B))
-        return {"bm25_k1": k1, "bm25_b": b}
-
-    @staticmethod
-    def _check_learned_params(params, encoder) -> None:
-        itype = str(params.get("index_type", "SPARSE_INVERTED_INDEX")).upper()
-        if itype != "SPARSE_INVERTED_INDEX":
-            raise ValueError(f"create_index: the sparse_embedding field takes index_type SPARSE_INVERTED_INDEX, got {itype!r}")
-        metric = str(params.get("metric_type", "IP")).upper()
-        if metric != "IP":
-            raise ValueError(f"create_index: the sparse_embedding field takes metric_type IP, got {metric!r}")
-        p = params.get("params")
-        if p is not None and not isinstance(p, dict):
-            raise ValueError("create_index: params must be a dict")
-        if encoder is None or not all(hasattr(encoder, a) for a in ("encode_document", "encode_query", "vocab_size")):
-            raise ValueError("create_index: the sparse_embedding field is derived from the text column and needs "
-                             "encoder=<a SparseEncoder> (encode_document, encode_query, vocab_size)")
-
-    @staticmethod
-    def _is_learned_field(kwargs) -> bool:
-        return LEARNED_FIELD in (kwargs.get("field_name"), kwargs.get("index_name"))
-
-    @staticmethod
-    def _check_token_params(params, encoder) -> None:
-        itype = str(params.get("index_type", "EMB_LIST_FLAT")).upper()
-        if itype != "EMB_LIST_FLAT":
-            raise ValueError(f"create_index: the token_embeddings field takes index_type EMB_LIST_FLAT, got {itype!r}")
-        metric = str(params.get("metric_type", "MAX_SIM_IP")).upper()
-        if metric != "MAX_SIM_IP":
-            raise ValueError(f"create_index: the token_embeddings field takes metric_type MAX_SIM_IP, got {metric!r}")
-        p = params.get("params")
-        if p is not None and not isinstance(p, dict):
-            raise ValueError("create_index: params must be a dict")
-        if encoder is None or not all(hasattr(encoder, a) for a in ("encode", "dim")):
-            raise ValueError("create_index: the token_embeddings field is derived from the text column and needs "
-                             "encoder=<a ColBERT> (encode(texts, is_query=), dim)")
-
-    @staticmethod
-    def _is_token_field(kwargs) -> bool:
-        return TOKEN_FIELD in (kwargs.get("field_name"), kwargs.get("index_name"))
-
-    @staticmethod
-    def _is_sparse_field(kwargs) -> bool:
-        return "sparse" in (kwargs.get("field_name"), kwargs.get("index_name"))
+    def _text_field(self, *names):
+        """The field derived from the text column (text_fields.py) that one of `names` names, or None."""
+        return next((self._text_fields[n] for n in names if isinstance(n, str) and n in self._text_fields), None)
 
     def drop_index(self, **kwargs) -> None:
         """Back to FLAT (the shadow of SQ8 is freed).  field_name="sparse" (or index_name="sparse"):
         drop the lexical index instead and leave the vector index alone."""
-        if self._is_learned_field(kwargs):
-            with self._rw.write():
-                self._learned = None
-                self._learned_rows = None
-                self._learned_index = None
-            return
-        if self._is_token_field(kwargs):
-            with self._rw.write():
-                self._tokens = None
-                self._token_field = None
-            return
-        if self._is_sparse_field(kwargs):
-            with self._rw.write():
-                self._sparse_params = None
-                self._sparse = None
-                self._forget_lexical()
-            return
+        field = self._text_field(kwargs.get("field_name"), kwargs.get("index_name"))
         with self._rw.write():
+            if field is not None:
+                field.declare(None)
+                return
             if self._has_sq8:
                 self.index.disable_sq8()
             self.index_type = "FLAT"
@@ -788,13 +669,8 @@ class CorpusStore:
 
     def has_index(self, **kwargs) -> bool:
         """field_name="sparse" (or index_name="sparse") asks about the lexical index."""
-        if self._is_learned_field(kwargs):
-            return self._learned is not None
-        if self._is_token_field(kwargs):
-            return self._tokens is not None
-        if self._is_sparse_field(kwargs):
-            return self._sparse_params is not None
-        return self._index_params is not None
+        field = self._text_field(kwargs.get("field_name"), kwargs.get("index_name"))
+        return self._index_params is not None if field is None else field.declared
 
     def _use_sq8(self, B: int, limit: int, band=None) -> bool:
         # the routing rule (INTEGRATION §2): unfiltered, no range parameters, limit <= RF_MAX_K,
@@ -865,9 +741,8 @@ class CorpusStore:
         """The host side of an append: the pk map, the six scalar columns, the checked extra columns
         (schema.check_columns: in schema order) and the checked dynamic columns (schema.check_dynamic)."""
         texts, periods, chunk_types, statement_types, primary_values = cols
-        self._sparse = None   # the lexical index is brought up to date by the next BM25 search (DESIGN §4.4k)
-        self._log_lexical("append", list(texts))
-        self._learned_index = None   # the new rows are encoded by the next search of the learned field
+        for field in self._text_fields.values():   # each is brought up to date by its next search
+            field.rows_appended(texts)
         self._mutations += 1
         base = self.num_entities
         for j, pk in enumerate(ids):
@@ -960,7 +835,7 @@ class CorpusStore:
             with self._filter_lock:   # still reject a bad expression
                 filter_expr.compile_expr(filter_expr.parse(expr, self.analyzer, self.schema, self.enable_dynamic_field),
                                          {f: [] for f in filter_expr.VARCHAR_FIELDS}, {},
-                                         None if self._sparse_params is None else {}, self.schema, {}, {})
+                                         {} if self._lexical.declared else None, self.schema, {}, {})
             return np.zeros(0, dtype=bool)
         return filter_mask_bits(self.build_filter(expr), n)
 
@@ -980,11 +855,8 @@ class CorpusStore:
         keep_mask = ~mask
         keep = np.flatnonzero(keep_mask)
         n_old = self.num_entities
-        self._sparse = None   # the lexical index is brought up to date by the next BM25 search
-        self._log_lexical("delete", keep_mask)
-        self._learned_drop_rows(keep_mask)
-        if self._token_field is not None:
-            self._token_field.keep(keep_mask)
+        for field in self._text_fields.values():
+            field.rows_deleted(keep_mask)
         self._mutations += 1
         self._compact_index(keep_mask, keep)
         sel = keep_mask.tolist()
@@ -1175,30 +1047,17 @@ class CorpusStore:
             return self._search_expr_list(data, anns_field, param, limit, expr, output_fields, group_by_field,
                                           mmr_lambda, mmr_fetch_k, offset)
         offset = check_offset(offset, param, limit)
-        if anns_field == TOKEN_FIELD:
-            if offset or group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
-                raise ValueError("late-interaction search (anns_field='token_embeddings') has no offset, grouping or MMR form")
-            q = self._check_token_search(data, param, limit)
-            fields = self._check_output_fields(output_fields)
-            with self._rw.read():
-                return self._search_tokens(q, limit, expr, fields)
-        if anns_field == LEARNED_FIELD:
-            if offset or group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
-                raise ValueError("learned sparse search (anns_field='sparse_embedding') has no offset, grouping or MMR form")
-            q = self._check_learned_search(data, param, limit)
-            fields = self._check_output_fields(output_fields)
-            with self._rw.read():
-                return self._search_learned(q, limit, expr, fields)
-        if offset and (anns_field == "sparse" or group_by_field is not None or mmr_lambda is not None
-                       or mmr_fetch_k is not None):
+        field = self._text_field(anns_field)
+        other_form = group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None
+        if field is not None:
+            field.refuse_forms(offset, other_form)
+        if offset and (anns_field == "sparse" or other_form):
             raise ValueError("offset has no BM25 (anns_field='sparse'), grouping (group_by_field) or MMR (mmr_lambda) form")
-        if anns_field == "sparse":
-            if group_by_field is not None or mmr_lambda is not None or mmr_fetch_k is not None:
-                raise ValueError("BM25 search (anns_field='sparse') has no grouping and no MMR form")
-            texts = self._check_sparse_search(data, param, limit)
+        if field is not None:
+            q = field.check_search(data, param, limit)
             fields = self._check_output_fields(output_fields)
             with self._rw.read():
-                return self._search_sparse(texts, limit, expr, fields)
+                return self._search_text_field(field, q, limit, expr, fields)
         mmr = check_mmr(mmr_lambda, mmr_fetch_k, limit)
         if mmr is not None and group_by_field is not None:
             raise ValueError("diversified search (mmr_lambda) cannot be combined with group_by_field")
@@ -1219,12 +1078,9 @@ class CorpusStore:
                          offset) -> list:
         """Everything a list expr refuses, before anything runs -> one key per query: the filter
         string, or None for "no filter"."""
-        if anns_field == "sparse":
-            raise ValueError("per-query filters (a list expr) have no BM25 form (anns_field='sparse')")
-        if anns_field == LEARNED_FIELD:
-            raise ValueError("per-query filters (a list expr) have no learned sparse form (anns_field='sparse_embedding')")
-        if anns_field == TOKEN_FIELD:
-            raise ValueError("per-query filters (a list expr) have no late-interaction form (anns_field='token_embeddings')")
+        field = self._text_field(anns_field)
+        if field is not None:
+            raise ValueError(f"per-query filters (a list expr) have no {field.form} form (anns_field='{field.name}')")
         if self._is_text(data):
             raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
         if group_by_field is not None:
@@ -1302,12 +1158,9 @@ class CorpusStore:
         boosts = check_rankers(ranker)
         if isinstance(expr, (list, tuple)):
             raise ValueError("boosted search (ranker) cannot be combined with per-query filters (a list expr)")
-        if anns_field == "sparse":
-            raise ValueError("boosted search (ranker) has no BM25 form (anns_field='sparse')")
-        if anns_field == LEARNED_FIELD:
-            raise ValueError("boosted search (ranker) has no learned sparse form (anns_field='sparse_embedding')")
-        if anns_field == TOKEN_FIELD:
-            raise ValueError("boosted search (ranker) has no late-interaction form (anns_field='token_embeddings')")
+        field = self._text_field(anns_field)
+        if field is not None:
+            raise ValueError(f"boosted search (ranker) has no {field.form} form (anns_field='{field.name}')")
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         if self._is_text(data):
@@ -1415,10 +1268,7 @@ class CorpusStore:
         return field, int(group_size)
 
     # -- lexical and hybrid search (rag_fin_amd/lexical.py, rag_fin_amd/hybrid.py) --------
-    @staticmethod
-    def _is_text(data) -> bool:
-        return isinstance(data, str) or (isinstance(data, (list, tuple)) and len(data) > 0
-                                         and all(isinstance(t, str) for t in data))
+    _is_text = staticmethod(is_text)
 
     def _check_output_fields(self, output_fields) -> list:
         """With enable_dynamic_field a name that is no field is a dynamic key (the value, or None where the row
@@ -1444,332 +1294,27 @@ class CorpusStore:
                 out[f] = None if col is None else col[r]
         return out
 
-    def _check_sparse_search(self, data, param, limit) -> list:
-        """Everything a BM25 search refuses -> the query strings."""
-        if self._sparse_params is None:
-            raise ValueError("no sparse index: call create_index('sparse', {'index_type': 'SPARSE_INVERTED_INDEX', "
-                             "'metric_type': 'BM25'}) first")
-        if not self._is_text(data):
-            raise ValueError("the sparse field is searched with query strings (a list of str), not with vectors")
-        metric = str((param or {}).get("metric_type", "BM25")).upper()
-        if metric != "BM25":
-            raise ValueError(f"the sparse field is searched with metric_type BM25, search asked for {metric}")
-        params = (param or {}).get("params")
-        if params is not None and not isinstance(params, dict):
-            raise ValueError("search: param['params'] must be a dict")
-        if params and (params.get("radius") is not None or params.get("range_filter") is not None):
-            raise ValueError("BM25 search (anns_field='sparse') has no range form (radius / range_filter)")
-        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
-            raise ValueError("limit must be an integer >= 1")
-        if limit > _lib.RF_MAX_K:
-            raise ValueError(f"BM25 search: limit = {limit} > {_lib.RF_MAX_K} (the sparse arm is not paged)")
-        return [data] if isinstance(data, str) else list(data)
-
-    def _sparse_index(self):
-        """(postings, SparseIndex | None) over the current text column.  After a mutation the last one
-        is brought up to date on the GPU (_replay_lexical); it is built whole the first
-        time and whenever there is nothing to replay from -- on the device (_build_lexical_device), or on
-        the host with a custom analyzer, with RAGFIN_LEXICAL_BUILD=host or when the device route raised.
-        None: no row holds a term.  Caller holds the read lock."""
-        with self._sparse_lock:
-            if self._sparse is None:
-                p = self._sparse_params
-                built = self._replay_lexical((p["bm25_k1"], p["bm25_b"]))
-                if built is None:
-                    built = self._build_lexical_device(p["bm25_k1"], p["bm25_b"])
-                    self._lexical_route = "device" if built is not None else "host"
-                if built is None:
-                    postings = lexical.build_postings(self.columns["text"], p["bm25_k1"], p["bm25_b"], self.analyzer)
-                    built = (postings, SparseIndex(postings, self.index.device) if postings.nnz else None)
-                self._lexical_log = []
-                self._lexical_kept = None
-                if built[1] is not None and getattr(built[1], "supports_update", False):
-                    self._lexical_kept = (built[0], built[1], self.analyzer, (p["bm25_k1"], p["bm25_b"]))
-                self._sparse = built   # (published whole: a replay that raised left nothing behind)
-            return self._sparse
-
-    def _lexical_build_route(self) -> str:
-        """"device" or "host" for a whole build of the lexical index: RAGFIN_LEXICAL_BUILD=host|device|auto
-        (default auto: the device for every non-empty corpus -- it was the faster route at every size
-        measured, 10 k rows included: DESIGN §5.0m).  A custom analyzer and an empty corpus always build
-        on the host."""
-        want = os.environ.get("RAGFIN_LEXICAL_BUILD", "auto").strip().lower() or "auto"
-        if want not in ("host", "device", "auto"):
-            raise ValueError(f"RAGFIN_LEXICAL_BUILD must be host, device or auto, got {want!r}")
-        n = self.num_entities
-        if self.analyzer is not None or n == 0 or want == "host":
-            return "host"
-        return "device"
-
-    def _build_lexical_device(self, k1, b):
-        """The whole build through the native analyzer and SparseIndex.from_tokens ->
-        (LivePostings, SparseIndex), or None when the route is the host's, no row holds a term, or the
-        native route raised (the caller then builds on the host, exactly as before; _lexical_fell_back says so)."""
-        if self._lexical_build_route() != "device":
-            return None
-        try:
-            vocab, tok, dl = lexical.analyze_native(self.columns["text"])
-            if tok.size == 0:
-                return None
-            sp = SparseIndex.from_tokens(len(vocab), tok, dl, k1, b, self.index.device)
-            return lexical.LivePostings(vocab, None, sp.host_post_off, dl, k1, b, sp.host_array), sp
-        except Exception as e:
-            if isinstance(e, ValueError) and "BM25 impacts" in str(e):   # build_postings' guard: the host build raises the same
-                raise
-            self._lexical_fell_back("the first build", e)
-            return None
-
-    def _lexical_fell_back(self, what: str, exc: Exception) -> None:
-        """The device route raised and the host route takes over: the answers are the same, the build is
-        many times slower, so it must not pass unseen -- one RuntimeWarning, and the reason
-        kept in `lexical_fallback_reason` for whoever looks later."""
-        import warnings
-        self.lexical_fallback_reason = f"{what}: {type(exc).__name__}: {exc}"
-        warnings.warn(f"lexical index: the device route failed for {self.lexical_fallback_reason}; building on the host",
-                      RuntimeWarning, stacklevel=3)
-
-    def _replay_lexical(self, params):
-        """The pending mutations applied to the retained index, in order, through SparseIndex.compacted /
-        .appended -> (postings, SparseIndex), or None when there is nothing to replay from, the retained
-        state was built with other parameters or another analyzer, no posting survives, or a step raised
-        (the caller then builds whole).  The analyzer sees the appended texts only, once."""
-        kept = self._lexical_kept
-        if kept is None or kept[2] is not self.analyzer or kept[3] != params:
-            return None
-        postings, sp = kept[0], kept[1]
-        k1, b = params
-        try:
-            vocab, term_id, post_off, dl = postings.vocab, postings.term_id, postings.post_off, postings.dl
-            for kind, arg in self._lexical_log:
-                if kind == "delete":
-                    row_map = np.where(arg, np.cumsum(arg) - 1, -1).astype(np.int32)
-                    dl = dl[arg]
-                    sp, alive, post_off = sp.compacted(row_map, dl, k1, b)
-                    if sp is None:
-                        return None
-                    if not alive.all():
-                        vocab, term_id = list(itertools.compress(vocab, alive.tolist())), None
-                else:
-                    delta = lexical.count_terms(arg, self.analyzer)
-                    if term_id is None:
-                        term_id = {t: i for i, t in enumerate(vocab)}
-                    merged, map_old, map_delta = lexical.merge_vocab(vocab, term_id, delta.vocab)
-                    if merged is not vocab:
-                        vocab, term_id = merged, None
-                    post_off = lexical.merged_offsets(len(vocab), post_off, map_old, delta.post_off, map_delta)
-                    dl = np.concatenate([dl, delta.dl])
-                    sp = sp.appended(delta, map_old, map_delta, post_off, dl, k1, b)
-            if dl.size != self.num_entities:
-                return None
-            return lexical.LivePostings(vocab, term_id, post_off, dl, k1, b, sp.host_array), sp
-        except Exception:   # a half-updated index is never published: the caller builds whole
-            return None
-
-    def _sparse_arm(self, texts, limit: int, expr):
-        """The BM25 arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors, or None
-        when nothing can hit (no row holds a term)."""
-        postings, sp = self._sparse_index()
-        if sp is None:
-            return None
-        q_off, q_term, q_weight = lexical.encode_queries(postings, texts, self.analyzer)
-        kw = {} if filter_expr.is_empty(expr) else {"filt": self.build_filter(expr)}
-        scores, rows, _ = sp.search(q_off, q_term, q_weight, limit, want_exact=False, **kw)
-        return scores, rows
-
-    def _search_sparse(self, texts, limit, expr, fields):
-        res = self._sparse_arm(texts, limit, expr)
+    def _search_text_field(self, field, q, limit, expr, fields):
+        """The hits of a checked search of one derived field.  Caller holds the read lock."""
+        res = field.arm(q, limit, expr)
         if res is None:
-            return [[] for _ in texts]
+            return [[] for _ in range(field.query_count(q))]
         scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
         return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
 
-    # -- the learned sparse field: search(anns_field="sparse_embedding") (DESIGN §4.5f) ----------------------
-    def _check_learned_search(self, data, param, limit):
-        """Everything a learned sparse search refuses -> the queries: a list of strings (encoded with the
-        attached encoder's encode_query) or the checked CSR batch (q_off, q_term, q_weight) of supplied vectors."""
-        from .sparse_encoder import check_query_rows
-        if self._learned is None:
-            raise ValueError("no sparse_embedding index: call create_index('sparse_embedding', {'index_type': "
-                             "'SPARSE_INVERTED_INDEX', 'metric_type': 'IP'}, encoder=...) first")
-        metric = str((param or {}).get("metric_type", "IP")).upper()
-        if metric != "IP":
-            raise ValueError(f"the sparse_embedding field is searched with metric_type IP, search asked for {metric}")
-        params = (param or {}).get("params")
-        if params is not None and not isinstance(params, dict):
-            raise ValueError("search: param['params'] must be a dict")
-        if params and (params.get("radius") is not None or params.get("range_filter") is not None):
-            raise ValueError("learned sparse search (anns_field='sparse_embedding') has no range form (radius / range_filter)")
-        if isinstance(param, dict) and param.get("offset"):
-            raise ValueError("learned sparse search (anns_field='sparse_embedding') takes no offset")
-        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
-            raise ValueError("limit must be an integer >= 1")
-        if limit > _lib.RF_MAX_K:
-            raise ValueError(f"learned sparse search: limit = {limit} > {_lib.RF_MAX_K} (the sparse arm is not paged)")
-        if self._is_text(data):
-            return [data] if isinstance(data, str) else list(data)
-        if hasattr(data, "tocsr") or (isinstance(data, (list, tuple)) and all(isinstance(r, dict) for r in data)):
-            return check_query_rows(data, int(self._learned["encoder"].vocab_size))
-        raise ValueError("the sparse_embedding field is searched with query strings, a scipy sparse matrix or a "
-                         "list of {term_id: weight} dicts")
-
-    @staticmethod
-    def _learned_query_count(q) -> int:
-        return len(q) if isinstance(q, list) else int(q[0].size - 1)
-
-    def _learned_drop_rows(self, keep_mask) -> None:
-        """A delete on the learned field: the encoded rows that go are dropped from the host CSR (rows not
-        encoded yet are simply not there).  Caller holds the write lock."""
-        self._learned_index = None
-        if self._learned_rows is None:
-            return
-        indptr, indices, data = self._learned_rows
-        done = indptr.size - 1
-        keep = np.asarray(keep_mask[:done], dtype=bool)
-        counts = np.diff(indptr)
-        entry = np.repeat(keep, counts)
-        new_ptr = np.zeros(int(keep.sum()) + 1, dtype=np.int64)
-        np.cumsum(counts[keep], out=new_ptr[1:])
-        self._learned_rows = (new_ptr, indices[entry], data[entry])
-
-    def _learned_postings(self):
-        """(TermPostings, SparseIndex | None) over the current text column: the rows not encoded yet go through
-        the attached encoder, then the per-row vectors are transposed on the host."""
-        from .sparse_encoder import TermPostings
-        with self._sparse_lock:
-            if self._learned_index is None:
-                enc = self._learned["encoder"]
-                V, n = int(enc.vocab_size), self.num_entities
-                rows = self._learned_rows or (np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros(0, np.float32))
-                done = rows[0].size - 1
-                if done < n:
-                    new = enc.encode_document(self.columns["text"][done:n]).tocsr()
-                    new.sort_indices()
-                    if new.shape != (n - done, V):
-                        raise ValueError(f"the sparse encoder returned {new.shape}, expected {(n - done, V)}")
-                    rows = (np.concatenate([rows[0], rows[0][-1] + np.asarray(new.indptr[1:], dtype=np.int64)]),
-                            np.concatenate([rows[1], np.asarray(new.indices, dtype=np.int32)]),
-                            np.concatenate([rows[2], np.asarray(new.data, dtype=np.float32)]))
-                    self._learned_rows = rows
-                tp = TermPostings(rows[0], rows[1], rows[2], V)
-                self._learned_index = (tp, SparseIndex(tp, self.index.device) if tp.nnz else None)
-            return self._learned_index
-
-    def _learned_arm(self, q, limit: int, expr):
-        """The learned sparse arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors, or
-        None when nothing can hit (no row holds a term)."""
-        _, sp = self._learned_postings()
-        if sp is None:
-            return None
-        if isinstance(q, list):
-            m = self._learned["encoder"].encode_query(q).tocsr()
-            m.sort_indices()
-            q = (np.asarray(m.indptr, dtype=np.int32), np.asarray(m.indices, dtype=np.int32),
-                 np.asarray(m.data, dtype=np.float32))
-        kw = {} if filter_expr.is_empty(expr) else {"filt": self.build_filter(expr)}
-        scores, rows, _ = sp.search(q[0], q[1], q[2], limit, want_exact=False, **kw)
-        return scores, rows
-
-    def _search_learned(self, q, limit, expr, fields):
-        B = self._learned_query_count(q)
-        res = self._learned_arm(q, limit, expr) if self.num_entities and B else None
-        if res is None:
-            return [[] for _ in range(B)]
-        scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
-        return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
-
-    # -- the late-interaction field: search(anns_field="token_embeddings") (DESIGN §4.5g) ---------------------
-    def _check_token_search(self, data, param, limit):
-        """Everything a late-interaction search refuses -> the queries: a list of strings (encoded with the
-        attached encoder, is_query=True) or the supplied list of [n_tok <= 32, D] arrays, checked."""
-        from . import late_interaction
-        if self._tokens is None:
-            raise ValueError("no token_embeddings index: call create_index('token_embeddings', {'index_type': "
-                             "'EMB_LIST_FLAT', 'metric_type': 'MAX_SIM_IP'}, encoder=...) first")
-        metric = str((param or {}).get("metric_type", "MAX_SIM_IP")).upper()
-        if metric != "MAX_SIM_IP":
-            raise ValueError(f"the token_embeddings field is searched with metric_type MAX_SIM_IP, search asked for {metric}")
-        params = (param or {}).get("params")
-        if params is not None and not isinstance(params, dict):
-            raise ValueError("search: param['params'] must be a dict")
-        if params and (params.get("radius") is not None or params.get("range_filter") is not None):
-            raise ValueError("late-interaction search (anns_field='token_embeddings') has no range form (radius / range_filter)")
-        if isinstance(param, dict) and param.get("offset"):
-            raise ValueError("late-interaction search (anns_field='token_embeddings') takes no offset")
-        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or limit < 1:
-            raise ValueError("late-interaction search (anns_field='token_embeddings'): limit must be an integer >= 1")
-        if limit > _lib.RF_MAX_K:
-            raise ValueError(f"late-interaction search (anns_field='token_embeddings'): limit = {limit} > {_lib.RF_MAX_K}")
-        if self._is_text(data):
-            return [data] if isinstance(data, str) else list(data)
-        if isinstance(data, (list, tuple)) and all(isinstance(q, np.ndarray) and q.ndim == 2 for q in data):
-            try:
-                late_interaction.pack_queries(list(data), int(self._tokens["encoder"].dim))
-            except ValueError as e:
-                raise ValueError(f"the token_embeddings field: {e}") from None
-            return [np.asarray(q) for q in data]
-        raise ValueError("the token_embeddings field is searched with query strings or a list of [n_tok, D] arrays")
-
-    def _token_index(self):
-        """The TokenField over the current text column: the rows not encoded yet go through the attached
-        encoder and are appended."""
-        from . import late_interaction
-        with self._sparse_lock:
-            enc = self._tokens["encoder"]
-            if self._token_field is None:
-                self._token_field = late_interaction.TokenField(int(enc.dim), self.index.device)
-            f, n = self._token_field, self.num_entities
-            if f.n_rows < n:
-                new = enc.encode(self.columns["text"][f.n_rows:n], is_query=False)
-                if len(new) != n - f.n_rows:
-                    raise ValueError(f"the token encoder returned {len(new)} rows, expected {n - f.n_rows}")
-                f.append(new)
-            return f
-
-    def _token_queries(self, q):
-        if q and isinstance(q[0], str):
-            return self._tokens["encoder"].encode(q, is_query=True)
-        return q
-
-    def _token_arm(self, q, limit: int, expr):
-        """The late-interaction arm on the device -> (scores f32 [B, limit], rows i64 [B, limit]) tensors:
-        all-rows MaxSim of the passing rows, then the exact top-k."""
-        f = self._token_index()
-        filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
-        return f.search(self._token_queries(q), limit, filt)
-
-    def _search_tokens(self, q, limit, expr, fields):
-        if not self.num_entities or not q:
-            return [[] for _ in q]
-        res = self._token_arm(q, limit, expr)
-        scores, rows = res[0].cpu().numpy(), res[1].cpu().numpy()
-        return [self._hits(rows[b], scores[b], fields) for b in range(rows.shape[0])]
-
+    # -- the late-interaction field's stored vectors (DESIGN §4.5g) -----------------------------------------------
     def token_vectors(self, rows) -> list:
         """The stored float16 token vectors of the given rows of the token_embeddings field, one [n_tok, D]
         array each (rows not encoded yet are encoded first)."""
-        if self._tokens is None:
-            raise ValueError("no token_embeddings index: call create_index('token_embeddings', ...) first")
         with self._rw.read():
-            return self._token_index().vectors(rows)
+            return self._late.vectors(rows)
 
     def rerank_tokens(self, queries, candidates):
         """Candidate-mode MaxSim on the stored token vectors: queries (strings or [n_tok, D] arrays), candidates
         one list of row numbers per query -> one float32 array of scores per query, parallel to its rows (-inf:
         a row without tokens or outside the collection).  One rf_maxsim call for the whole batch."""
-        from . import late_interaction
-        if self._tokens is None:
-            raise ValueError("no token_embeddings index: call create_index('token_embeddings', ...) first")
-        queries = [queries] if isinstance(queries, str) else list(queries)
-        if len(queries) != len(candidates):
-            raise ValueError(f"{len(candidates)} candidate lists for {len(queries)} queries")
-        if not queries:
-            return []
         with self._rw.read():
-            f = self._token_index()
-            scores = late_interaction.maxsim(f, self._token_queries(queries), [list(c) for c in candidates])
-            scores = np.asarray(scores.cpu().numpy() if hasattr(scores, "cpu") else scores, dtype=np.float32)
-        cut = np.cumsum([len(c) for c in candidates])[:-1]
-        return np.split(scores, cut)
+            return self._late.rerank(queries, candidates)
 
     def _hits(self, rows, scores, fields) -> list:
         """The Hit list of one query from its row numbers (best first, -1 ends it) and scores."""
@@ -1822,15 +1367,10 @@ class CorpusStore:
                     raise ValueError("hybrid_search: an arm takes one expr string, not a list (per-query filters)")
                 if r.limit > _lib.RF_MAX_K:
                     raise ValueError(f"hybrid_search: an arm's limit is at most {_lib.RF_MAX_K}, got {r.limit}")
-                if r.anns_field == "sparse":
-                    q = self._check_sparse_search(r.data, r.param, r.limit)
-                    prepared.append((r, q, len(q)))
-                elif r.anns_field == LEARNED_FIELD:
-                    q = self._check_learned_search(r.data, r.param, r.limit)
-                    prepared.append((r, q, self._learned_query_count(q)))
-                elif r.anns_field == TOKEN_FIELD:
-                    q = self._check_token_search(r.data, r.param, r.limit)
-                    prepared.append((r, q, len(q)))
+                field = self._text_field(r.anns_field)
+                if field is not None:
+                    q = field.check_search(r.data, r.param, r.limit)
+                    prepared.append((r, q, field.query_count(q)))
                 elif r.anns_field == "embedding":
                     if self._is_text(r.data):
                         raise ValueError("the embedding field is searched with vectors, not with strings")
@@ -1855,14 +1395,10 @@ class CorpusStore:
             device = self.index.device
             arms = []
             for r, q, _ in prepared:
-                if r.anns_field == "sparse":
-                    res = self._sparse_arm(q, r.limit, r.expr)
+                field = self._text_field(r.anns_field)
+                if field is not None:
+                    res = field.arm(q, r.limit, r.expr)
                     rows = None if res is None else res[1]
-                elif r.anns_field == LEARNED_FIELD:
-                    res = self._learned_arm(q, r.limit, r.expr)
-                    rows = None if res is None else res[1]
-                elif r.anns_field == TOKEN_FIELD:
-                    rows = self._token_arm(q, r.limit, r.expr)[1]
                 else:
                     rows = self._dense_arm(q, r.limit, r.expr)
                 block = torch.full((B, F), -1, dtype=torch.int64, device=device)
@@ -1971,8 +1507,8 @@ class CorpusStore:
             meta["dynamic"] = self.dynamic
         if self.index_type != "FLAT":   # FLAT directories stay exactly as before
             meta["index_type"] = self.index_type
-        if self._sparse_params is not None:   # (and so do directories without a lexical index)
-            meta["sparse_index"] = dict(self._sparse_params)
+        if self._lexical.declared:   # (and so do directories without a lexical index)
+            meta["sparse_index"] = dict(self._lexical.params)
         tmp = os.path.join(path, "columns.json.tmp")
         with open(tmp, "w", encoding="utf-8") as f:
             json.dump(meta, f, ensure_ascii=False)
@@ -2035,8 +1571,9 @@ class CorpusStore:
     def _adopt_sparse(self, meta: dict) -> None:
         """Re-declare the lexical index a saved store had (the postings are rebuilt on first use)."""
         if meta.get("sparse_index") is not None:
-            self.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25",
-                                         "params": dict(meta["sparse_index"])})
+            field = self._lexical
+            self.create_index(field.name, {"index_type": field.index_type, "metric_type": field.metric_type,
+                                           "params": dict(meta["sparse_index"])})
 
     # -- filters -------------------------------------------------------------------------
     def build_filter(self, expr: str):
@@ -2049,11 +1586,12 @@ class CorpusStore:
         change of the rows also builds the token positions, once (by the route that built the index).
 
         Lock order: the read/write lock (held by the caller: search, query and delete take it; delete
-        holds the WRITE side, so nothing here may ask for it again), then `_sparse_lock` (inside
-        _sparse_index and _text_index, released before the next), then `_filter_lock`, then the
+        holds the WRITE side, so nothing here may ask for it again), then `_sparse_lock` (the one lock of the
+        fields derived from the text column: inside LexicalField.index and .text_index, released before the next;
+        the learned sparse and token fields build under it too), then `_filter_lock`, then the
         SparseIndex's own `_lock` (inside text_match).  No path takes them the other way round."""
         node = filter_expr.parse(expr, self.analyzer, self.schema, self.enable_dynamic_field)
-        term_id, sp = self._text_index(filter_expr.text_leaves(node))
+        term_id, sp = self._lexical.text_index(filter_expr.text_leaves(node))
         with self._filter_lock:
             n = self.num_entities
             if self._dcols is None:
@@ -2084,37 +1622,6 @@ class CorpusStore:
                 dynamic_match(self.index.device, prog, {key: (c.tags, c.payload) for key, c in dyn.items()}, n,
                               out=bitmaps[mid:])
             return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps, column_base=base)
-
-    def _text_index(self, leaves):
-        """What the keyword leaves of a filter need -> (term -> id map, SparseIndex), (None, None)
-        without such leaves.  No postings at all (no row holds a term): an empty map and no index,
-        so every leaf compiles to RF_FOP_FALSE."""
-        if not leaves:
-            return None, None
-        if self._sparse_params is None:
-            raise ValueError("filter expression: " + filter_expr.NO_LEXICAL_INDEX)
-        postings, sp = self._sparse_index()
-        if sp is not None and any(isinstance(n, filter_expr.PhraseMatch) for n in leaves):
-            with self._sparse_lock:
-                if sp.positions is None and not self._attach_positions_device(postings, sp):
-                    sp.attach_positions(*lexical.build_positions(postings, self.columns["text"], self.analyzer))
-        return postings.term_id, sp
-
-    def _attach_positions_device(self, postings, sp) -> bool:
-        """The token positions of an index that came from the device route, through the device route again
-        (native analysis, rf_sparse_count_* with positions); False: not that route, or it raised, and the
-        caller builds them on the host.  The stream must give the index's own dictionary and postings."""
-        if self._lexical_route != "device" or self.analyzer is not None:
-            return False
-        try:
-            vocab, tok, dl = lexical.analyze_native(self.columns["text"])
-            if vocab != postings.vocab:
-                raise ValueError("the native analysis does not give the dictionary of the index")
-            sp.attach_token_positions(tok, dl)
-            return True
-        except Exception as e:
-            self._lexical_fell_back("the token positions", e)
-            return False
 
     def filter_rows(self, expr: str) -> np.ndarray:
         """Row numbers (ascending) that pass `expr`."""

@@ -225,9 +225,9 @@ def test_the_sparse_index_is_rebuilt_after_a_delete(gpu_device):
     q = torch.from_numpy(np.array(q16)).to(gpu_device)
     st = make_store(gpu_device)
     before = st.search(qtexts, "sparse", BM25, limit=20)
-    built = st._sparse[1]
+    built = st._lexical.built[1]
     assert st.delete('period == "Q2_FY2023"').delete_count == periods.count("Q2_FY2023") > 0
-    assert st._sparse is None
+    assert st._lexical.built is None
     keep = [i for i in range(N) if periods[i] != "Q2_FY2023"]
     fresh = make_store(gpu_device, keep)
 
@@ -237,7 +237,7 @@ def test_the_sparse_index_is_rebuilt_after_a_delete(gpu_device):
     for a, b in ((st.search(qtexts, "sparse", BM25, limit=20), fresh.search(qtexts, "sparse", BM25, limit=20)),
                  (st.hybrid_search(reqs(), RRFRanker(), limit=10), fresh.hybrid_search(reqs(), RRFRanker(), limit=10))):
         assert [[(h.id, h.row, h.score) for h in r] for r in a] == [[(h.id, h.row, h.score) for h in r] for r in b]
-    assert st._sparse[1] is not built and st._sparse[1].n_rows == len(keep)
+    assert st._lexical.built[1] is not built and st._lexical.built[1].n_rows == len(keep)
     after = st.search(qtexts, "sparse", BM25, limit=20)
     want = bm25_restated([texts[i] for i in keep], qtexts, 20)
     assert [[h.row for h in r] for r in after] == want

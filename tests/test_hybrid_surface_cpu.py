@@ -17,6 +17,7 @@ import torch
 
 from rag_fin_amd import _lib, filter_expr, lexical, mcp_server
 from rag_fin_amd import store as store_mod
+from rag_fin_amd import text_fields
 from rag_fin_amd.hybrid import AnnSearchRequest, RRFRanker, WeightedRanker
 from rag_fin_amd.store import SCALAR_FIELDS, CorpusStore
 
@@ -99,7 +100,7 @@ def fake_fuse(arm_ids, k, weights=None, rrf_k=60.0):
 
 @pytest.fixture(autouse=True)
 def doubles(monkeypatch):
-    monkeypatch.setattr(store_mod, "SparseIndex", FakeSparse)
+    monkeypatch.setattr(text_fields, "SparseIndex", FakeSparse)
     monkeypatch.setattr(store_mod, "fuse_rrf", fake_fuse)
     FakeSparse.built.clear()
     FUSE_CALLS.clear()
@@ -140,14 +141,14 @@ def test_create_has_drop_index_learn_the_sparse_field():
     st.create_index("sparse", dict(SPARSE, params={"bm25_k1": 0.9, "bm25_b": 0.4}))
     assert st.has_index(field_name="sparse") and st.has_index(index_name="sparse")
     assert not st.has_index() and st.index_type == "FLAT" and st._index_params is None       # the vector index is untouched
-    assert st._sparse_params == {"bm25_k1": 0.9, "bm25_b": 0.4}
+    assert st._lexical.params == {"bm25_k1": 0.9, "bm25_b": 0.4}
     st.create_index("embedding", {"index_type": "FLAT", "metric_type": "COSINE"})
     st.drop_index()                                                                          # as before: the vector index
     assert not st.has_index() and st.has_index(field_name="sparse")
     st.drop_index(field_name="sparse")
     assert not st.has_index(field_name="sparse")
     st.create_index("sparse")                                                                # defaults
-    assert st._sparse_params == {"bm25_k1": 1.2, "bm25_b": 0.75}
+    assert st._lexical.params == {"bm25_k1": 1.2, "bm25_b": 0.75}
 
 
 @pytest.mark.parametrize("params", [
@@ -182,7 +183,7 @@ def test_the_index_is_built_by_the_first_search_and_rebuilt_after_every_mutation
     want = [["k0", "k1", "k7", "n1"], ["k0", "k1", "k7", "n1", "n2"], ["k0", "k7", "n1", "n2"], ["k0", "n1", "n2"]]
     for mutate, ids in zip(mutations, want):
         mutate()
-        assert st._sparse is None
+        assert st._lexical.built is None
         hits = st.search(["eps"], "sparse", BM25, limit=10)
         n_built += 1
         assert len(FakeSparse.built) == n_built
@@ -195,7 +196,7 @@ def test_the_index_is_built_by_the_first_search_and_rebuilt_after_every_mutation
     st.search(["eps"], "sparse", BM25, limit=10)
     assert len(FakeSparse.built) == n_built + 1 and FakeSparse.built[-1].postings.b == 0.0
     st.drop()
-    assert st._sparse is None and st.has_index(field_name="sparse")
+    assert st._lexical.built is None and st.has_index(field_name="sparse")
     assert st.search(["eps"], "sparse", BM25, limit=10) == [[]]
 
 
@@ -365,8 +366,8 @@ def test_save_records_the_sparse_index_and_load_redeclares_it(tmp_path):
     meta = json.load(open(tmp_path / "lex" / "columns.json"))
     assert meta["sparse_index"] == {"bm25_k1": 1.5, "bm25_b": 0.5}
     back = LoadableStore.load_from(str(tmp_path / "lex"))
-    assert back.has_index(field_name="sparse") and back._sparse_params == {"bm25_k1": 1.5, "bm25_b": 0.5}
-    assert back._sparse is None                                                    # rebuilt on first use
+    assert back.has_index(field_name="sparse") and back._lexical.params == {"bm25_k1": 1.5, "bm25_b": 0.5}
+    assert back._lexical.built is None                                                    # rebuilt on first use
     assert sorted(h.id for h in back.search(["eps"], "sparse", BM25, limit=5)[0]) == ["k0", "k1", "k7"]
     assert FakeSparse.built[-1].postings.k1 == 1.5
 
@@ -374,7 +375,7 @@ def test_save_records_the_sparse_index_and_load_redeclares_it(tmp_path):
 def test_the_recorded_v1_directory_still_loads():
     st = LoadableStore.load_from(GOLD_STORE)
     assert st.num_entities == 5 and st.dim == 32 and st.index_type == "FLAT"
-    assert not st.has_index() and not st.has_index(field_name="sparse") and st._sparse_params is None
+    assert not st.has_index() and not st.has_index(field_name="sparse") and st._lexical.params is None
     with pytest.raises(ValueError, match="no sparse index"):
         st.search(["gold"], "sparse", BM25, limit=3)
     st.create_index("sparse", SPARSE)

@@ -328,7 +328,7 @@ def make_store(texts=TEXTS, declare=True):
 
 
 def field_arrays(st):
-    f = st._token_index()
+    f = st._text_fields[FIELD].index()
     return f.off_host.tolist(), [r.tolist() for r in f.rows]
 
 
@@ -351,7 +351,7 @@ def test_store_declares_searches_and_drops_the_token_field(doubles):
     # a filter travels as the filt of the search
     st.build_filter = lambda expr: np.arange(len(TEXTS)) != 0
     filtered = st.search(["eps q1"], FIELD, MS, 3, expr='period == "Q0"')
-    assert 0 not in [h.row for h in filtered[0]] and st._token_index().calls[-1][1] is not None
+    assert 0 not in [h.row for h in filtered[0]] and st._text_fields[FIELD].index().calls[-1][1] is not None
     # candidate mode on the stored vectors
     got = st.rerank_tokens(["eps q1", "deposits"], [[7, 0, 99], []])
     assert [g.tolist() for g in got] == [[1.0, 2.0, -np.inf], []]
@@ -407,7 +407,7 @@ def test_store_encodes_only_new_rows_and_a_delete_leaves_the_field_of_a_fresh_bu
     assert len(enc.doc_calls) == 2                                       # a delete encodes nothing
     survivors = list(st.columns["text"])
     fresh, _ = make_store(survivors)
-    assert field_arrays(st) == field_arrays(fresh) and st._token_index().n_rows == len(survivors)
+    assert field_arrays(st) == field_arrays(fresh) and st._text_fields[FIELD].index().n_rows == len(survivors)
     # rows appended and deleted before they were ever encoded
     st.add(["m0", "m1"], ["eps eps", "words"], np.ones((2, 8), np.float32), ["Q0", "Q1"], ["a"] * 2, ["s"] * 2, [1.0, 2.0])
     st.delete('id == "m0"')

@@ -343,7 +343,7 @@ def check_against_the_definition(st, c, limit, expr=None, mask=None):
     q = c["enc"].encode(c["queries"], is_query=True)
     assert all(v.shape == (32, 96) for v in q)                              # expanded to 32 tokens
     n = st.num_entities
-    field = st._token_index()
+    field = st._text_fields[FIELD].index()
     filt = None if expr is None else st.build_filter(expr)
     scores = late.maxsim(field, q, filter=filt).cpu().numpy()
     want_s, want_i = late.topk_reference(scores, limit)
@@ -387,7 +387,7 @@ def test_store_after_add_and_delete_answers_as_a_fresh_store(corpus):
     got = check_against_the_definition(st, c, 10)
     want = check_against_the_definition(fresh, c, 10)
     assert [[(h.id, h.score) for h in q] for q in got] == [[(h.id, h.score) for h in q] for q in want]
-    a, b = st._token_index(), fresh._token_index()
+    a, b = st._text_fields[FIELD].index(), fresh._text_fields[FIELD].index()
     assert np.array_equal(a.off_host, b.off_host) and a.n_rows == len(survivors)
     assert np.array_equal(a.off[:a.n_rows + 1].cpu().numpy(), a.off_host)
     assert np.array_equal(a.vec[:a.n_tok].cpu().numpy().view(np.uint16), b.vec[:b.n_tok].cpu().numpy().view(np.uint16))
@@ -410,6 +410,59 @@ def test_hybrid_of_a_dense_and_a_token_arm_is_the_rrf_of_the_two_lists(corpus):
         n = int((want[b] >= 0).sum())
         assert [h.row for h in got[b]] == want[b, :n].tolist()
         assert [h.score for h in got[b]] == fused[b, :n].tolist()
+
+
+def test_a_four_arm_hybrid_search_equals_a_fresh_store_after_a_delete_and_an_append(corpus):
+    """The dense field and the three fields derived from the text column on ONE store of 70 rows (a filter mask of
+    three 32-bit words, the last one partial): 2 queries, 8 hits per arm, one arm with an expr, the best 5 fused.
+    As built, after a delete of 7 rows (row 0, the last row, both sides of a mask word) and after an append of 5
+    the hits -- rows, primary keys, fused scores -- are bit for bit those of a fresh store of the surviving rows."""
+    from oracle import synth_text
+    from rag_fin_amd.hybrid import AnnSearchRequest, RRFRanker
+    from rag_fin_amd.sparse_encoder import SparseEncoder
+    from rag_fin_amd.store import CorpusStore
+    from rag_fin_amd.tokenizer import WordPieceTokenizer
+    from test_sparse_encoder_cpu import model
+    c = corpus
+    cfg, _, w, head, _, _ = model("l2")
+    splade = SparseEncoder(w, head, cfg, tokenizer=WordPieceTokenizer(synth_text.vocab_for(size=cfg["vocab_size"])),
+                           device=c["device"], max_seq_length=64, max_terms=48, query_max_terms=24)
+
+    def add(st, rows):
+        st.add([f"c{i}" for i in rows], [c["texts"][i] for i in rows], c["vec"][rows], [c["periods"][i] for i in rows],
+               ["t"] * len(rows), ["s"] * len(rows), [float(i) for i in rows])
+
+    def store_of(rows):
+        st = CorpusStore("t", dim=384, capacity=128, device=c["device"])
+        add(st, rows)
+        st.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
+        st.create_index("sparse_embedding", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "IP"}, encoder=splade)
+        st.create_index(FIELD, SPEC, encoder=c["enc"])
+        return st
+
+    words = [" ".join(q.split()[:8]) for q in c["queries"][:2]]              # (a BM25 query holds at most 64 terms)
+    qv = c["vec"][[3, 50]] + 0.5 * c["vec"][[4, 51]]
+
+    def ask(st):
+        reqs = [AnnSearchRequest(qv, "embedding", {"metric_type": "COSINE"}, 8),
+                AnnSearchRequest(words, "sparse", {"metric_type": "BM25"}, 8),
+                AnnSearchRequest(words, "sparse_embedding", {"metric_type": "IP"}, 8, expr='period != "Q3_FY2024"'),
+                AnnSearchRequest(words, FIELD, MS, 8)]
+        hits = st.hybrid_search(reqs, RRFRanker(), 5)
+        assert [len(q) for q in hits] == [5, 5]
+        return [[(h.row, h.id, np.float64(h.score).tobytes()) for h in q] for q in hits]
+
+    rows = list(range(70))
+    st = store_of(rows)
+    assert ask(st) == ask(store_of(rows))                                      # as built
+    gone = [0, 13, 31, 32, 63, 64, 69]
+    assert st.delete("id in [" + ", ".join(f'"c{i}"' for i in gone) + "]").delete_count == 7
+    rows = [i for i in rows if i not in gone]
+    assert st.num_entities == 63 and ask(st) == ask(store_of(rows))
+    new = list(range(70, 75))
+    add(st, new)
+    rows += new
+    assert st.num_entities == 68 and ask(st) == ask(store_of(rows))
 
 
 class RowEmbedder:
@@ -435,7 +488,7 @@ def test_vector_rag_reranks_by_maxsim_of_the_stored_token_vectors(corpus):
     per_query = [rag.search(q, 5, rerank=True, rerank_with="late", fetch_k=24) for q in c["queries"]]
     batch = rag.search_batch(c["queries"], 5, rerank=True, rerank_with="late", fetch_k=24)
     assert batch == per_query
-    field = st._token_index()
+    field = st._text_fields[FIELD].index()
     for b, query in enumerate(c["queries"]):
         fetched = st.search(RowEmbedder(c).encode([query]), "embedding", {"metric_type": "COSINE"}, 24,
                             output_fields=["text"])[0]

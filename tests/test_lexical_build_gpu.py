@@ -194,7 +194,7 @@ def host_reference(idx, k1, b):
 
 def assert_store_equals_host_build(st, idx, k1, b, positions=True):
     want, (pos_off, pos) = host_reference(tuple(idx), k1, b)
-    postings, sp = st._sparse
+    postings, sp = st._lexical.built
     assert postings.vocab == want.vocab and postings.term_id == want.term_id
     assert np.array_equal(postings.post_off, want.post_off) and postings.post_off.dtype == np.int64
     assert np.array_equal(postings.dl, want.dl)
@@ -231,7 +231,7 @@ def test_a_store_built_on_the_device_equals_the_host_build(gpu_device, monkeypat
     monkeypatch.setattr(lexical, "build_postings", None)                     # the host build is not what runs
     monkeypatch.setattr(lexical, "build_positions", None)
     assert st.search(QTEXTS, "sparse", BM25, limit=5)[0]
-    assert st._lexical_route == "device" and st._sparse[1].positions is None
+    assert st._lexical.route == "device" and st._lexical.built[1].positions is None
     assert st.filter_rows(FILTERS[1]).size > 0                               # the first phrase: positions, on the device
     monkeypatch.undo()
     assert_store_equals_host_build(st, idx, k1, b)
@@ -243,8 +243,8 @@ def test_writes_on_top_of_a_device_built_index_equal_a_fresh_host_build(gpu_devi
     texts, v16 = corpus()
     idx = list(range(N0))
     st = build_store(gpu_device, idx)
-    assert st.filter_rows(FILTERS[1]).size > 0 and st._lexical_route == "device"
-    first = st._sparse[1]
+    assert st.filter_rows(FILTERS[1]).size > 0 and st._lexical.route == "device"
+    first = st._lexical.built[1]
 
     def batch(keys, rows):
         return [keys, [texts[i] for i in rows], torch.from_numpy(v16[rows]).to(gpu_device), [f"P{i % 5}" for i in rows],
@@ -264,7 +264,7 @@ def test_writes_on_top_of_a_device_built_index_equal_a_fresh_host_build(gpu_devi
     idx = [i for i in idx if i % 5 != 3]
     assert st.search(QTEXTS, "sparse", BM25, limit=5)[0]
     assert_store_equals_host_build(st, idx, 1.2, 0.75)
-    assert st._sparse[1] is not first and st._lexical_route == "device"
+    assert st._lexical.built[1] is not first and st._lexical.route == "device"
 
 
 def test_answers_equal_the_host_routes_and_a_custom_analyzer_stays_on_the_host(gpu_device, monkeypatch):
@@ -272,14 +272,14 @@ def test_answers_equal_the_host_routes_and_a_custom_analyzer_stays_on_the_host(g
     monkeypatch.setenv("RAGFIN_LEXICAL_BUILD", "host")
     host = build_store(gpu_device, idx)
     want = answers(host, gpu_device)
-    assert host._lexical_route == "host"
+    assert host._lexical.route == "host"
     monkeypatch.setenv("RAGFIN_LEXICAL_BUILD", "auto")
     dev = build_store(gpu_device, idx)
     assert answers(dev, gpu_device) == want
-    assert dev._lexical_route == "device"                                    # auto: every non-empty corpus
+    assert dev._lexical.route == "device"                                    # auto: every non-empty corpus
     monkeypatch.setenv("RAGFIN_LEXICAL_BUILD", "device")
     dev = build_store(gpu_device, idx)
-    assert answers(dev, gpu_device) == want and dev._lexical_route == "device"
+    assert answers(dev, gpu_device) == want and dev._lexical.route == "device"
     assert dev.lexical_fallback_reason is None
 
     def broken(texts, *args, **kw):
@@ -288,11 +288,11 @@ def test_answers_equal_the_host_routes_and_a_custom_analyzer_stays_on_the_host(g
     fell = build_store(gpu_device, idx)
     with pytest.warns(RuntimeWarning, match="the device route failed for the first build: OSError: no analyzer today"):
         got = answers(fell, gpu_device)
-    assert got == want and fell._lexical_route == "host" and "no analyzer today" in fell.lexical_fallback_reason
+    assert got == want and fell._lexical.route == "host" and "no analyzer today" in fell.lexical_fallback_reason
     monkeypatch.undo()
     monkeypatch.setenv("RAGFIN_LEXICAL_BUILD", "device")
     custom = build_store(gpu_device, idx, analyzer=lexical.analyze)
-    assert answers(custom, gpu_device) == want and custom._lexical_route == "host"
+    assert answers(custom, gpu_device) == want and custom._lexical.route == "host"
     monkeypatch.setenv("RAGFIN_LEXICAL_BUILD", "gpu")
     with pytest.raises(ValueError, match="RAGFIN_LEXICAL_BUILD"):
         build_store(gpu_device, idx).search(QTEXTS, "sparse", BM25, limit=5)

@@ -14,7 +14,7 @@ import torch
 
 from oracle import synth_text
 from rag_fin_amd import _lib, filter_expr, lexical
-from rag_fin_amd import store as store_mod
+from rag_fin_amd import text_fields
 from rag_fin_amd.store import SCALAR_FIELDS, CorpusStore
 
 SPARSE = {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"}
@@ -195,7 +195,7 @@ def cols(ids, texts):
 
 @pytest.fixture
 def updatable(monkeypatch):
-    monkeypatch.setattr(store_mod, "SparseIndex", UpdatableSparse)
+    monkeypatch.setattr(text_fields, "SparseIndex", UpdatableSparse)
     UpdatableSparse.built = []
     UpdatableSparse.calls = []
     UpdatableSparse.fail_next = False
@@ -214,8 +214,8 @@ def eps_ids(st):
 
 
 def assert_published_is_fresh(st):
-    p = st._sparse_params
-    assert_same_postings(st._sparse[0], lexical.build_postings(st.columns["text"], p["bm25_k1"], p["bm25_b"]))
+    p = st._lexical.params
+    assert_same_postings(st._lexical.built[0], lexical.build_postings(st.columns["text"], p["bm25_k1"], p["bm25_b"]))
 
 
 # ---- the store's life cycle ------------------------------------------------------------------------------------
@@ -237,14 +237,14 @@ def test_every_mutation_is_replayed_once_and_only_new_texts_are_analysed(updatab
     for mutate, calls, analysed, ids in steps:
         rec.calls.clear()
         UpdatableSparse.calls.clear()
-        before = st._sparse[1]
+        before = st._lexical.built[1]
         mutate()
-        assert st._sparse is None                                                  # as ever
+        assert st._lexical.built is None                                                  # as ever
         assert eps_ids(st) == ids
         assert UpdatableSparse.calls == calls                                      # one replay, in order
         assert rec.calls == analysed + [["eps"]]                                   # surviving rows: never again
         assert len(UpdatableSparse.built) == 1                                     # no whole build
-        assert st._sparse[1] is not before
+        assert st._lexical.built[1] is not before
         assert_published_is_fresh(st)
         assert eps_ids(st) == ids and UpdatableSparse.calls == calls               # reused while nothing changes
 
@@ -321,7 +321,7 @@ def test_each_discard_rule_leads_to_a_whole_build(updatable, tmp_path):
 
     st.delete('id in ["c1"]')
     st.insert(cols(["c2"], [""]))
-    assert eps_ids(st) == [] and st._sparse[1] is None                             # (the replay found no posting left)
+    assert eps_ids(st) == [] and st._lexical.built[1] is None                             # (the replay found no posting left)
 
     def after_no_row_held_a_term():
         st.insert(cols(["c3"], ["eps c3"]))
@@ -334,7 +334,7 @@ def test_a_delete_of_every_posting_falls_back_to_a_whole_build(updatable):
     st = make_store(texts=["eps", ""])
     assert eps_ids(st) == ["k0"]
     st.delete('id in ["k0"]')
-    assert eps_ids(st) == [] and st._sparse[1] is None
+    assert eps_ids(st) == [] and st._lexical.built[1] is None
     assert UpdatableSparse.calls == [("compacted", 1)]
 
 
@@ -358,13 +358,13 @@ def test_a_loaded_store_builds_whole(updatable, tmp_path):
     st.insert(cols(["x"], ["eps x"]))
     st.save(str(tmp_path / "s"))
     back = Loadable.load_from(str(tmp_path / "s"))
-    assert back._lexical_kept is None and back._lexical_log == []
+    assert back._lexical.kept is None and back._lexical.log == []
     assert whole_builds(lambda: eps_ids(back)) == 1
     assert eps_ids(back) == ["k0", "k1", "k7", "x"]
 
 
 def test_a_double_without_the_update_methods_always_gets_a_whole_build(monkeypatch):
-    monkeypatch.setattr(store_mod, "SparseIndex", PlainSparse)
+    monkeypatch.setattr(text_fields, "SparseIndex", PlainSparse)
     PlainSparse.built = []
     rec = RecordingAnalyzer()
     st = make_store(rec)
@@ -373,11 +373,11 @@ def test_a_double_without_the_update_methods_always_gets_a_whole_build(monkeypat
                                 lambda: st.upsert(cols(["k1"], ["eps again"]))]):
         rec.calls.clear()
         mutate()
-        assert st._lexical_kept is None and st._lexical_log == []
+        assert st._lexical.kept is None and st._lexical.log == []
         eps_ids(st)
         assert len(PlainSparse.built) == i + 2
         assert rec.calls[0] == st.columns["text"]                                  # the whole column, as before
-        assert_same_postings(st._sparse[0], lexical.build_postings(st.columns["text"]))
+        assert_same_postings(st._lexical.built[0], lexical.build_postings(st.columns["text"]))
 
 
 def test_an_exception_inside_a_replay_is_followed_by_a_whole_build(updatable):
@@ -388,7 +388,7 @@ def test_an_exception_inside_a_replay_is_followed_by_a_whole_build(updatable):
     UpdatableSparse.fail_next = True
     assert eps_ids(st) == ["e1", "k1", "k7"]                                       # correct all the same
     assert UpdatableSparse.calls == [("compacted", 1), ("appended", 1)] and len(UpdatableSparse.built) == 2
-    assert st._sparse[1] is UpdatableSparse.built[-1]                              # the whole build is what is published
+    assert st._lexical.built[1] is UpdatableSparse.built[-1]                              # the whole build is what is published
     assert_published_is_fresh(st)
     st.insert(cols(["e2"], ["eps e2"]))                                            # and the next update replays again
     assert eps_ids(st) == ["e1", "e2", "k1", "k7"] and len(UpdatableSparse.built) == 2

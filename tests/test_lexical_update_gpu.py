@@ -249,7 +249,7 @@ def answers(st, device):
 
 
 def assert_same_index(live, fresh):
-    (lp, ls), (fp, fs) = live._sparse, fresh._sparse
+    (lp, ls), (fp, fs) = live._lexical.built, fresh._lexical.built
     assert lp.vocab == fp.vocab and lp.term_id == fp.term_id
     assert np.array_equal(lp.post_off, fp.post_off) and np.array_equal(lp.dl, fp.dl)
     for name in ("post_off", "post_row", "post_imp"):
@@ -269,7 +269,7 @@ def test_a_live_store_equals_a_fresh_one_after_every_step(gpu_device):
     live = build_store(gpu_device, rows, rec)
     fresh = build_store(gpu_device, rows)
     assert answers(live, gpu_device) == answers(fresh, gpu_device)      # (the phrase filters attached the positions)
-    first = live._sparse[1]
+    first = live._lexical.built[1]
     assert first.positions is not None and first.supports_update
     rng = np.random.default_rng(19)
     spare = list(range(N0, N0 + 400))
@@ -302,20 +302,20 @@ def test_a_live_store_equals_a_fresh_one_after_every_step(gpu_device):
             rows = [r for r in rows if r[1] % 5 != step % 5]
         else:                                                           # every row holding a word: the term leaves the dictionary
             expr = 'TEXT_MATCH(text, "deposits")'
-            assert "deposits" in live._sparse[0].term_id
+            assert "deposits" in live._lexical.built[0].term_id
             a, b = live.delete(expr), fresh.delete(expr)
             assert a.delete_count == b.delete_count > 0 and list(a.primary_keys) == list(b.primary_keys)
             gone = set(a.primary_keys)
             rows = [r for r in rows if r[0] not in gone]
             rec.calls.clear()                                           # (the expression's own terms were analysed)
-        assert live._sparse is None
+        assert live._lexical.built is None
         fresh = build_store(gpu_device, rows)
         assert answers(live, gpu_device) == answers(fresh, gpu_device)
         assert live.columns["id"] == [k for k, _ in rows]
         assert_same_index(live, fresh)
-        assert live._sparse[1] is not first and live._sparse[1].n_rows == len(rows)
+        assert live._lexical.built[1] is not first and live._lexical.built[1].n_rows == len(rows)
         if kind == "word":
-            assert "deposits" not in live._sparse[0].term_id
+            assert "deposits" not in live._lexical.built[0].term_id
         # the analyzer saw the new rows once, then queries and filter strings: never the surviving rows
         assert rec.calls[0] == (n_new or rec.calls[0]) and max(rec.calls[1:] + [0]) <= len(QTEXTS)
         assert sum(rec.calls) < len(rows) // 4

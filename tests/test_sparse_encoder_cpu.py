@@ -220,6 +220,7 @@ def test_terms_abi_is_declared_and_bound():
 
 # ---- the store's surface, with a fake encoder -----------------------------------------------------------------------
 from rag_fin_amd import store as store_mod  # noqa: E402
+from rag_fin_amd import text_fields  # noqa: E402
 from rag_fin_amd.hybrid import AnnSearchRequest, RRFRanker  # noqa: E402
 from rag_fin_amd.rag import VectorRAG  # noqa: E402
 from test_hybrid_surface_cpu import TEXTS, FakeIndex, FakeSparse, HostStore, fake_fuse  # noqa: E402
@@ -257,7 +258,7 @@ class FakeSparseEncoder:
 
 @pytest.fixture
 def doubles(monkeypatch):
-    monkeypatch.setattr(store_mod, "SparseIndex", FakeSparse)
+    monkeypatch.setattr(text_fields, "SparseIndex", FakeSparse)
     monkeypatch.setattr(store_mod, "fuse_rrf", fake_fuse)
     FakeSparse.built.clear()
 
@@ -274,7 +275,7 @@ def make_store(texts=TEXTS, declare=True):
 
 
 def posting_arrays(st):
-    tp = st._learned_postings()[0]
+    tp = st._text_fields[FIELD].postings()[0]
     return tp.post_off.tolist(), tp.post_row.tolist(), tp.post_imp.tolist()
 
 
@@ -350,7 +351,7 @@ def test_store_encodes_only_new_rows_and_a_delete_leaves_the_postings_of_a_fresh
     assert len(enc.doc_calls) == 2                                       # a delete encodes nothing
     survivors = list(st.columns["text"])
     fresh, _ = make_store(survivors)
-    assert posting_arrays(st) == posting_arrays(fresh) and st._learned_postings()[0].n_rows == len(survivors)
+    assert posting_arrays(st) == posting_arrays(fresh) and st._text_fields[FIELD].postings()[0].n_rows == len(survivors)
     # rows appended and deleted before they were ever encoded
     st.add(["m0", "m1"], ["eps eps", "words"], np.ones((2, 8), np.float32), ["Q0", "Q1"], ["a"] * 2, ["s"] * 2, [1.0, 2.0])
     st.delete('id == "m0"')

@@ -201,7 +201,7 @@ def make_store(c, rows):
 
 def held_csr(st, V):
     from scipy.sparse import csr_array
-    indptr, indices, data = st._learned_rows
+    indptr, indices, data = st._text_fields[FIELD].rows
     return csr_array((data, indices, indptr), shape=(indptr.size - 1, V))
 
 
@@ -251,7 +251,7 @@ def test_store_after_add_and_delete_answers_as_a_fresh_store(corpus):
     got = check_against_the_definition(st, c, 10)
     want = check_against_the_definition(fresh, c, 10)
     assert [[(h.id, h.score) for h in q] for q in got] == [[(h.id, h.score) for h in q] for q in want]
-    a, b = st._learned_postings()[0], fresh._learned_postings()[0]
+    a, b = st._text_fields[FIELD].postings()[0], fresh._text_fields[FIELD].postings()[0]
     assert np.array_equal(a.post_off, b.post_off) and np.array_equal(a.post_row, b.post_row)
     assert np.array_equal(a.post_imp.view(np.uint32), b.post_imp.view(np.uint32))
 

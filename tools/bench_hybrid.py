@@ -125,7 +125,7 @@ def main():
         store.add(list(range(s, s + m)), texts[s:s + m], x, ["p"] * m, ["c"] * m, ["s"] * m, [0.0] * m)
     store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     t0 = time.perf_counter()
-    postings, sparse = store._sparse_index()
+    postings, sparse = store._lexical.index()
     torch.cuda.synchronize()
     res["index_build_s"] = round(time.perf_counter() - t0, 2)
     res["nnz"], res["terms"], res["avgdl"] = postings.nnz, postings.n_terms, round(postings.avgdl, 2)

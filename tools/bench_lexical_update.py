@@ -125,13 +125,13 @@ def main():
         return (lambda: store.insert(data)) if kind == "add" else (lambda: store.upsert(data))
 
     def arrays():
-        sp = store._sparse[1]
+        sp = store._lexical.built[1]
         return [sp.post_off, sp.post_row, sp.post_imp] + list(sp.positions or ())
 
     t0 = time.perf_counter()
     first_answer(None)
     res["index_build_s"] = round(time.perf_counter() - t0, 2)
-    postings = store._sparse[0]
+    postings = store._lexical.built[0]
     res["nnz"], res["terms"], res["avgdl"] = postings.nnz, postings.n_terms, round(postings.avgdl, 2)
     cases = {}
     for with_pos in (False, True):
@@ -140,7 +140,7 @@ def main():
             t0 = time.perf_counter()
             first_answer(expr)
             res["positions_build_s"] = round(time.perf_counter() - t0, 2)
-            res["positions"] = int(store._sparse[1].positions[1].numel())
+            res["positions"] = int(store._lexical.built[1].positions[1].numel())
         for kind in ("add", "upsert", "delete"):                       # warm-up: kernels loaded, allocator primed
             mutate(kind)()
             first_answer(expr)
@@ -155,11 +155,11 @@ def main():
                 first_answer(expr)
                 upd.append(time.perf_counter() - t0)
                 mut.append(t1 - t0)
-                assert store._lexical_kept is not None and store._sparse[1].supports_update
+                assert store._lexical.kept is not None and store._lexical.built[1].supports_update
             live = arrays()
-            assert with_pos == (store._sparse[1].positions is not None)
-            store._sparse = None
-            store._forget_lexical()
+            assert with_pos == (store._lexical.built[1].positions is not None)
+            store._lexical.built = None
+            store._lexical.forget()
             t0 = time.perf_counter()
             first_answer(expr)
             rebuild_search = time.perf_counter() - t0
@@ -176,7 +176,7 @@ def main():
 
     # ---- the entry points on the full index, by HIP events -----------------------------------------------
     from rag_fin_amd import index as index_mod
-    postings, sp = store._sparse_index()
+    postings, sp = store._lexical.index()
     lib = TimedLib(sp.lib, torch)
     index_mod._lib.load_library = lambda: lib
     sp.lib = lib

@@ -83,12 +83,12 @@ def main():
         store.add(list(range(s, s + m)), texts[s:s + m], x, periods[s:s + m], ["c"] * m, ["s"] * m, [0.0] * m)
     store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     t0 = time.perf_counter()
-    postings, sparse = store._sparse_index()
+    postings, sparse = store._lexical.index()
     torch.cuda.synchronize()
     res["postings_build_s"] = round(time.perf_counter() - t0, 2)
     res["nnz"] = postings.nnz
     t0 = time.perf_counter()
-    store._text_index(filter_expr.text_leaves(filter_expr.parse(LEAVES["phrase3"])))   # builds and attaches the positions
+    store._lexical.text_index(filter_expr.text_leaves(filter_expr.parse(LEAVES["phrase3"])))   # builds and attaches the positions
     torch.cuda.synchronize()
     res["positions_build_s"] = round(time.perf_counter() - t0, 2)
     positions = lexical.build_positions(postings, texts)
