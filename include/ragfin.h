@@ -320,6 +320,54 @@ int rf_boost_classes(const void* base_filter_dev, const void* const* boost_filte
 int rf_merge_boosted(const double* exact_dev, const int64_t* ids_dev, int B, int C, int k_in,
                      const double* class_weight_host, int k, float* scores_dev, int64_t* ids_out_dev,
                      double* boosted_dev, double* base_dev, void* stream);
+/* ---- decayed search: Collection.search(..., ranker=Function(..., params={"reranker": "decay", ...})) ----
+ * Milvus' decay rankers scale a score by how far a numeric field's value lies from an origin.  The
+ * weight differs row by row, so the exact decayed top-k is no merge of plain top-k lists: the sweep
+ * itself runs on the weighted score (the definitions in numpy: rag_fin_amd/ranker.py,
+ * decay_weights_reference and decay_reference).
+ *
+ * rf_decay_weights: one weight per row of a device column (int64 when column_is_int64, rounded to the
+ * nearest double, else fp64).  d = max(0, |v - origin| - offset);
+ *   RF_DECAY_GAUSS   w = 2^-(shape (d / scale)^2)      shape = -log2(decay)
+ *   RF_DECAY_EXP     w = 2^-(shape (d / scale))        shape = -log2(decay)
+ *   RF_DECAY_LINEAR  w = max(0, (shape - d) / shape)   shape = scale / (1 - decay)
+ * so w is in [0, 1], 1 within `offset` of the origin and `decay` at distance offset + scale; a NaN value
+ * weighs 0.  Every step is one IEEE fp64 operation and 2^-t is defined by its arithmetic (0 unless
+ * t < 1100; n = floor(t + 0.5), the degree-13 Taylor polynomial of e^x at x = -(t - n) ln2 in Horner
+ * form, scaled by 2^-n as ldexp does), so w64_dev [n_rows] is bit for bit the numpy definition and
+ * w32_dev [n_rows] its rounding to nearest.  Stream-ordered, no allocation, captures into a hipGraph.
+ * RF_ERR_INVALID before any device call: a NULL or misaligned pointer, n_rows outside 0..2^32 - 33, an
+ * unknown function, an origin that is not finite, a scale or shape that is not finite and > 0, an
+ * offset that is not finite and >= 0.
+ *
+ * rf_search_weighted: per query the best k rows (of the rows filter_dev passes; NULL: of all rows)
+ * by (decayed desc, s desc, row asc), with s the fp64 contract score and decayed = w64[row] * s as ONE
+ * fp64 multiplication; scores_dev = (float)decayed, decayed_dev and base_dev = s may be NULL, the
+ * tail is -inf / -1 / -inf / -inf.  PRECONDITION: every weight lies in [0, 1] -- no NaN, nothing above
+ * 1 -- and w32[row] is w64[row] rounded to nearest (what rf_decay_weights writes); w32_dev [n_rows]
+ * 16-byte, w64_dev [n_rows] 8-byte aligned.  One sweep of the fp16 rows per 64 queries (the masked
+ * 64-query chain; an attached SQ8 shadow is not used): sample, threshold, emit and merge all see
+ * fl32(w32[row] * MFMA score), which lies within eps_w = 2 eps of decayed, so eps_w stands wherever
+ * rf_search uses eps.  A negative score is multiplied like any other: a small weight moves it
+ * towards 0, i.e. up.  Flags, workspace (rf_search_workspace_bytes), stream order and capture as for
+ * rf_search_filtered; a flagged query is re-run by the caller through
+ * rf_search_exhaustive_weighted, the fp64 kernel over the same rows and weights (no flags; it uses
+ * the workspace's candidate area for its lists).  No range, search-after, per-query-filter, grouping
+ * or SQ8 form.
+ * New in this build; the reference calls Milvus without a ranker on this path. */
+#define RF_DECAY_GAUSS 0
+#define RF_DECAY_EXP 1
+#define RF_DECAY_LINEAR 2
+int rf_decay_weights(const void* column_dev, int column_is_int64, int64_t n_rows, int function, double origin,
+                     double scale, double offset, double shape, double* w64_dev, float* w32_dev, void* stream);
+int rf_search_weighted(const rf_index_t* ix, const void* filter_dev, const float* w32_dev, const double* w64_dev,
+                       const void* q_dev, int B, int k, int64_t id_base, float* scores_dev, int64_t* ids_dev,
+                       double* decayed_dev, double* base_dev, uint32_t* flags_dev, void* workspace_dev,
+                       size_t workspace_bytes, void* stream);
+int rf_search_exhaustive_weighted(const rf_index_t* ix, const void* filter_dev, const float* w32_dev,
+                                  const double* w64_dev, const void* q_dev, int B, int k, int64_t id_base,
+                                  float* scores_dev, int64_t* ids_dev, double* decayed_dev, double* base_dev,
+                                  void* workspace_dev, size_t workspace_bytes, void* stream);
 /* ---- range search: Collection.search(..., param={"params": {"radius": r, "range_filter": f}}) ----
  * The best k hits whose score lies in the band  radius < score <= range_filter  (COSINE / IP:
  * higher is better), i.e. the (score desc, row asc) ranking of rf_search with every row outside

@@ -25,6 +25,8 @@ RF_SPARSE_TILE_ROWS = 8192   # rows a workgroup of the posting scan accumulates 
 RF_FUSE_MAX_ARMS = 4         # answers rf_fuse_rrf fuses
 # boosted search (include/ragfin.h, "boosted search")
 RF_BOOST_MAX = 3             # boosts of one search: 2^3 = 8 row classes, the most rf_merge_boosted takes
+# decayed search (include/ragfin.h, "decayed search"): the function codes of rf_decay_weights
+RF_DECAY_GAUSS, RF_DECAY_EXP, RF_DECAY_LINEAR = 0, 1, 2
 # keyword filters (include/ragfin.h, "keyword filters")
 RF_TEXT_MATCH = 1
 RF_TEXT_PHRASE = 2
@@ -190,6 +192,12 @@ SIGNATURES = {
     "rf_boost_classes": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "rf_merge_boosted": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
+    "rf_decay_weights": (c_int, [c_void_p, c_int, c_int64, c_int, c_double, c_double, c_double, c_double, c_void_p,
+                                 c_void_p, c_void_p]),
+    "rf_search_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rf_search_exhaustive_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_search_exhaustive_range": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_double, c_double,

@@ -5,7 +5,8 @@ Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
   GET /health      {"status": "healthy", "mcp": ...} | {"status": "unhealthy", "mcp": "unavailable"}
   POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional), rerank: bool (optional),
                    hybrid: bool (optional), lexical: "bm25" | "learned" | "both" (optional), rerank_with: "cross" | "late" (optional), offset: int >= 0 (optional), boost_filter: str + boost_weight: float > 0
-                   (optional)}
+                   (optional), decay_field: str + decay_function: "gauss" | "exp" | "linear" + decay_origin: float +
+                   decay_scale: float > 0 [+ decay_offset: float >= 0, decay_rate: 0 < float < 1] (optional)}
                                                                -> tool search_vectors
   POST /answer     {question: str >= 5 chars, top_k: 1..10 = 3} -> tool answer_question
   GET /stats       -> tool get_collection_stats
@@ -59,15 +60,24 @@ class SearchRequest(BaseModel):
     # boosted search (the chunks boost_filter selects have their score multiplied by boost_weight); new
     boost_filter: Optional[str] = None
     boost_weight: Optional[float] = Field(default=None, gt=0.0)
+    # decayed search (scores fall off with the distance of the numeric field decay_field from decay_origin:
+    # to decay_rate at decay_offset + decay_scale, along decay_function = "gauss" | "exp" | "linear"); new
+    decay_field: Optional[str] = None
+    decay_function: Optional[str] = None
+    decay_origin: Optional[float] = None
+    decay_scale: Optional[float] = Field(default=None, gt=0.0)
+    decay_offset: Optional[float] = Field(default=None, ge=0.0)
+    decay_rate: Optional[float] = Field(default=None, gt=0.0, lt=1.0)
 
 
 def search_args(req: SearchRequest) -> dict:
     """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by`, `group_size`,
-    `mmr_lambda`, `fetch_k`, `offset`, `boost_filter`, `boost_weight`, `lexical` and `rerank_with` only when they were given, `rerank` and
+    `mmr_lambda`, `fetch_k`, `offset`, `boost_filter`, `boost_weight`, `decay_*`, `lexical` and `rerank_with` only when they were given, `rerank` and
     `hybrid` only when set, so the reference's payload {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
     for name in ("filter", "min_score", "max_score", "group_by", "group_size", "mmr_lambda", "fetch_k", "offset",
-                 "boost_filter", "boost_weight", "lexical", "rerank_with"):
+                 "boost_filter", "boost_weight", "lexical", "rerank_with", "decay_field", "decay_function", "decay_origin",
+                 "decay_scale", "decay_offset", "decay_rate"):
         if getattr(req, name) is not None:
             args[name] = getattr(req, name)
     if req.rerank:

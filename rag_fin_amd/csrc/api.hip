@@ -184,14 +184,18 @@ __global__ void k_fill_empty(int n, int B, float* scores, int64_t* ids, double* 
 struct rf_out {
   float* scores;
   int64_t* ids;
-  double* exact;
+  double* exact;     // (a weighted search: the decayed scores)
   uint32_t* flags;
+  double* base;      // a weighted search only: the plain fp64 scores
 };
 
 static int fill_empty(int B, int k, const rf_out& o, hipStream_t st) {
   const int n = B * k;
   hipLaunchKernelGGL(k_fill_empty, dim3((n + 255) / 256), dim3(256), 0, st, n, B, o.scores, o.ids,
                      o.exact, o.flags);
+  if (o.base)   // (a weighted search: its second fp64 output, through the same kernel)
+    hipLaunchKernelGGL(k_fill_empty, dim3((n + 255) / 256), dim3(256), 0, st, n, 0, o.scores, o.ids, o.base,
+                       (uint32_t*)nullptr);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }
@@ -226,7 +230,7 @@ static int for_chunks(const rf_index_t* ix, const void* q_dev, int B, int k, siz
     const int nb = chunk_width(ix, B - q0, k, widen, &wide);
     const size_t r0 = (size_t)q0 * row;
     const int rc = body(q0, nb, wide, (const _Float16*)q_dev + (size_t)q0 * ix->dim,
-                        rf_out{at(o.scores, r0), at(o.ids, r0), at(o.exact, r0), at(o.flags, (size_t)q0)});
+                        rf_out{at(o.scores, r0), at(o.ids, r0), at(o.exact, r0), at(o.flags, (size_t)q0), at(o.base, r0)});
     if (rc != RF_OK) return rc;
     q0 += nb;
   }
@@ -247,6 +251,9 @@ static int for_chunks(const rf_index_t* ix, const void* q_dev, int B, int k, siz
 // multi: per-query filters (always with filt, which is then the union of the batch's filters;
 // never with sq8, wide, band or after): both sweeps walk the union's blocks and test each query's
 // rows against its own filter's words; threshold and merge are per query as ever.
+// weights: per-row weights (with or without filt; never with sq8, wide, band, after or multi, and no
+// sample fold): both sweeps run on w32[row] * score, threshold and merge take eps_w = 2 eps, and the
+// merge ranks by (w64[row] * s desc, s desc, row asc) -- DESIGN 4.4q.
 struct rf_variant {
   const rf_filter_view* filt;
   const rf_sq8_ws* sq8;
@@ -255,6 +262,7 @@ struct rf_variant {
   const rf_after* after;
   const rf_multi* multi;
   bool coarse;   // SQ8 timed as the four FLAT stages: sample | threshold | quantize + emit + refine | merge
+  const rf_weights* weights;
 };
 
 static int mark(hipEvent_t* ev, int* n, hipStream_t st) {
@@ -287,7 +295,8 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   // the unfiltered 64-query FLAT sweep folds the sample into the emit; n_samp stays 0 unless the
   // sample pass keeps its lists
   rf_fold kept{};
-  rf_fold* fold = (v.wide || v.sq8 || v.filt || v.band) ? nullptr : &kept;
+  rf_fold* fold = (v.wide || v.sq8 || v.filt || v.band || v.weights) ? nullptr : &kept;
+  const float* w32 = v.weights ? v.weights->w32 : nullptr;
   int rc = mark(ev, &n_ev, st);
   if (v.sq8) {
     if (rc == RF_OK) rc = rf_launch_sq8_queries(ix, qc, nb, *v.sq8, st);
@@ -296,20 +305,25 @@ static int sweep(const rf_index_t* ix, const rf_variant& v, const _Float16* qc, 
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS && v.band) rc = rf_launch_band_eps(ix, qc, nb, ws, st);
   if (rc == RF_OK && ix->size > RF_SMALL_ROWS)
     rc = v.wide ? rf_launch_wide_sample(ix, qc, nb, ws, &P, st)
-                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band, v.after, v.multi);
+                : rf_launch_sample(ix, qc, nb, JB, ws, &P, st, v.filt, fold, v.band, v.after, v.multi, w32);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
-  if (rc == RF_OK) rc = rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8, v.band);
+  if (rc == RF_OK)
+    rc = v.weights ? rf_launch_threshold_weighted(ix, qc, nb, k, P, ws, st)
+                   : rf_launch_threshold(ix, qc, nb, k, P, ws, st, fold, v.sq8, v.band);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   if (rc == RF_OK)
     rc = v.wide  ? rf_launch_wide_emit(ix, qc, nb, ws, st)
          : v.sq8 ? rf_launch_sq8_emit(ix, nb, JB, ws, *v.sq8, st)
-                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band, v.after, v.multi);
+                 : rf_launch_emit(ix, qc, nb, JB, ws, st, v.filt, fold, v.band, v.after, v.multi, w32);
   if (v.sq8) {
     if (rc == RF_OK && !v.coarse) rc = mark(ev, &n_ev, st);
     if (rc == RF_OK) rc = rf_launch_shadow_refine(ix, qc, nb, k, ws, *v.sq8, st);
   }
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
-  if (rc == RF_OK) rc = rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band, v.after);
+  if (rc == RF_OK)
+    rc = v.weights ? rf_launch_merge_weighted(ix, qc, nb, k, id_base, ws, v.weights->w64, o.scores, o.ids, o.exact, o.base,
+                                              o.flags, st)
+                   : rf_launch_merge(ix, qc, nb, k, id_base, ws, o.scores, o.ids, o.exact, o.flags, st, v.band, v.after);
   if (rc == RF_OK) rc = mark(ev, &n_ev, st);
   return rc;
 }
@@ -322,21 +336,23 @@ enum { RF_FP16 = 0, RF_SQ8 = 1, RF_SHADOW = 2 };   // RF_SHADOW: the SQ8 chain, 
 static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k, int64_t id_base, const rf_out& o,
                           void* workspace_dev, hipStream_t st, const rf_filter_view* filt, int sq8,
                           float* stage_ms = nullptr, const rf_band* band = nullptr,
-                          const rf_after* after = nullptr, const rf_multi* multi = nullptr) {
+                          const rf_after* after = nullptr, const rf_multi* multi = nullptr,
+                          const rf_weights* weights = nullptr) {
   if (ix->size == 0) return fill_empty(B, k, o, st);
   rf_arena a{(unsigned char*)workspace_dev, 0};
   rf_workspace ws;
   const rf_sq8_ws sw = carve_sq8(a, &ws);   // (the SQ8 area is only touched by an SQ8 sweep)
   const rf_sq8_ws* sq = sq8 != RF_FP16 && ix->size > RF_SMALL_ROWS ? &sw : nullptr;
   const bool coarse = sq8 == RF_SHADOW;
-  const bool widen = !filt && !sq && !band;
+  const bool widen = !filt && !sq && !band && !weights;
   if (!stage_ms)
     return for_chunks(ix, q_dev, B, k, (size_t)k, widen, o,
                       [&](int q0, int nb, bool wide, const _Float16* qc, const rf_out& oc) {
                         const rf_after ac{after ? after->score + q0 : nullptr, after ? after->id + q0 : nullptr};
                         const rf_multi mc{multi ? multi->masks_t : nullptr, multi ? multi->qfilter + q0 : nullptr,
                                           multi ? multi->gp : 0u};
-                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr, multi ? &mc : nullptr, coarse},
+                        return sweep(ix, rf_variant{filt, sq, wide, band, after ? &ac : nullptr, multi ? &mc : nullptr, coarse,
+                                                    weights},
                                      qc, nb, k, id_base, ws, oc, st, nullptr);
                       });
   bool wide;
@@ -347,8 +363,8 @@ static int search_enqueue(const rf_index_t* ix, const void* q_dev, int B, int k,
   float t[6];
   const bool fold4 = sq && coarse;
   const int rc = time_stages(sq ? (coarse ? 6 : 7) : 5, fold4 ? t : stage_ms, [&](hipEvent_t* ev) {
-    return sweep(ix, rf_variant{filt, sq, wide, band, after, multi, coarse}, (const _Float16*)q_dev, nb, k, id_base, ws,
-                 o, st, ev);
+    return sweep(ix, rf_variant{filt, sq, wide, band, after, multi, coarse, weights}, (const _Float16*)q_dev, nb, k,
+                 id_base, ws, o, st, ev);
   });
   if (rc == RF_OK && fold4) {
     stage_ms[0] = t[1];
@@ -559,6 +575,58 @@ extern "C" int rf_search_multi_filtered(const rf_index_t* ix, const void* multi_
   const rf_multi m{(const uint32_t*)((const unsigned char*)multi_dev + so), qfilter_dev, rf_multi_columns(n_filters)};
   return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, exact_dev, flags_dev}, workspace_dev,
                         (hipStream_t)stream, &f, RF_FP16, nullptr, nullptr, nullptr, &m);
+}
+
+// ---- decayed search (include/ragfin.h, "decayed search") ------------------------------------------
+static int check_weights(const char* fn, const rf_index_t* ix, const void* filter_dev, const float* w32_dev,
+                         const double* w64_dev) {
+  if (!w32_dev || !w64_dev || (((uintptr_t)w32_dev) & 15) || (((uintptr_t)w64_dev) & 7)) {
+    rf_set_error("%s: weights null, or w32 not 16-byte / w64 not 8-byte aligned", fn);
+    return RF_ERR_INVALID;
+  }
+  if (ix && ix->size > (int64_t)0xFFFFFFFFll - 32) {
+    rf_set_error("%s: %lld rows out of range", fn, (long long)ix->size);
+    return RF_ERR_INVALID;
+  }
+  return filter_dev ? check_filter_arg(fn, filter_dev) : RF_OK;
+}
+
+extern "C" int rf_search_weighted(const rf_index_t* ix, const void* filter_dev, const float* w32_dev,
+                                  const double* w64_dev, const void* q_dev, int B, int k, int64_t id_base,
+                                  float* scores_dev, int64_t* ids_dev, double* decayed_dev, double* base_dev,
+                                  uint32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  int rc = check_search_args("rf_search_weighted", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc == RF_OK) rc = check_weights("rf_search_weighted", ix, filter_dev, w32_dev, w64_dev);
+  if (rc != RF_OK) return rc;
+  const rf_filter_view f = filter_dev ? rf_filter_carve(filter_dev, ix->size) : rf_filter_view{};
+  const rf_weights w{w32_dev, w64_dev};
+  return search_enqueue(ix, q_dev, B, k, id_base, rf_out{scores_dev, ids_dev, decayed_dev, flags_dev, base_dev},
+                        workspace_dev, (hipStream_t)stream, filter_dev ? &f : nullptr, RF_FP16, nullptr, nullptr, nullptr,
+                        nullptr, &w);
+}
+
+extern "C" int rf_search_exhaustive_weighted(const rf_index_t* ix, const void* filter_dev, const float* w32_dev,
+                                             const double* w64_dev, const void* q_dev, int B, int k, int64_t id_base,
+                                             float* scores_dev, int64_t* ids_dev, double* decayed_dev,
+                                             double* base_dev, void* workspace_dev, size_t workspace_bytes,
+                                             void* stream) {
+  int rc = check_search_args("rf_search_exhaustive_weighted", ix, q_dev, B, k, scores_dev, ids_dev, workspace_dev,
+                             workspace_bytes);
+  if (rc == RF_OK) rc = check_weights("rf_search_exhaustive_weighted", ix, filter_dev, w32_dev, w64_dev);
+  if (rc != RF_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const rf_out o{scores_dev, ids_dev, decayed_dev, nullptr, base_dev};
+  if (ix->size == 0) return fill_empty(B, k, o, st);
+  rf_arena a{(unsigned char*)workspace_dev, 0};
+  const rf_workspace ws = carve(a);
+  // (as in rf_search_exhaustive_filtered, the mask of a buffer built for this index covers its rows)
+  const uint32_t* mask = filter_dev ? rf_filter_carve(filter_dev, ix->size).mask : nullptr;
+  return for_chunks(ix, q_dev, B, k, (size_t)k, false, o,
+                    [&](int, int nb, bool, const _Float16* qc, const rf_out& oc) {
+                      return rf_launch_exhaustive_weighted(ix, qc, nb, k, id_base, ws, w64_dev, oc.scores, oc.ids, oc.exact,
+                                                           oc.base, st, mask);
+                    });
 }
 
 // ---- range search (include/ragfin.h, "range search") ----------------------------------------------

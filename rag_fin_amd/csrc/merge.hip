@@ -241,6 +241,58 @@ __global__ void __launch_bounds__(64) k_threshold(const _Float16* __restrict__ q
                                                                  : (appended + RF_CAND_SHARDS - 1u - lane) / RF_CAND_SHARDS;
 }
 
+// The threshold of a sweep with per-row weights: pmax holds maxima of w32[row] * score,
+// which lie within eps_w = 2 eps of the fp64 decayed scores, so thr = m_k - 2 eps_w, and eps_w goes to
+// eps_out for the merge.  k_threshold's selection of the k-th partition maximum, without a fold, SQ8
+// or a band (a kernel of its own, so that k_threshold stays what it is).
+__global__ void __launch_bounds__(64) k_threshold_weighted(const _Float16* __restrict__ q, int B, int dim,
+                                                           int k, const float* __restrict__ pmax, int P,
+                                                           const uint32_t* __restrict__ max_norm2,
+                                                           float* __restrict__ thr, float* __restrict__ eps_out,
+                                                           uint32_t* __restrict__ cand_cnt) {
+  const int qi = blockIdx.x;
+  const int lane = threadIdx.x;
+  const float eps_w = 2.f * query_eps(q, qi, B, dim, lane, max_norm2);
+  float t;
+  if (qi >= B) {
+    t = INFINITY;
+  } else if (P <= 0) {
+    t = -INFINITY;
+  } else {
+    float v[RF_SAMPLE_WGS / 64];
+#pragma unroll
+    for (int i = 0; i < RF_SAMPLE_WGS / 64; ++i) {
+      const int j = lane + 64 * i;
+      v[i] = (j < P) ? pmax[(size_t)qi * P + j] : -INFINITY;
+    }
+    float kth = -INFINITY;
+    for (int r = 0; r < k; ++r) {
+      float m = v[0];
+#pragma unroll
+      for (int i = 1; i < RF_SAMPLE_WGS / 64; ++i) m = fmaxf(m, v[i]);
+      const float wm = wave_max_f(m);
+      kth = wm;
+      if (wm == -INFINITY) break;
+      const int winner = __ffsll((long long)__ballot(m == wm)) - 1;
+      if (lane == winner) {
+        bool done = false;
+#pragma unroll
+        for (int i = 0; i < RF_SAMPLE_WGS / 64; ++i)
+          if (!done && v[i] == wm) {
+            v[i] = -INFINITY;
+            done = true;
+          }
+      }
+    }
+    t = (kth == -INFINITY) ? -INFINITY : kth - 2.f * eps_w;
+  }
+  if (lane == 0) {
+    thr[qi] = t;
+    eps_out[qi] = eps_w;
+  }
+  if (lane < RF_CAND_SHARDS) cand_cnt[qi * RF_CAND_SHARDS + lane] = 0u;
+}
+
 // ---- candidate merge + exact rescoring --------------------------------------------
 // One workgroup per query:
 //   1. find the k-th largest candidate by (MFMA score, row): rank counting over
@@ -267,15 +319,21 @@ static size_t merge_lds_bytes(int dim) {
 // strict per-query one (rf_after_ceiling: a key at or below it is eligible whatever its row), and a
 // row of R also leaves unless it ranks strictly after the bound (after_s[qi], after_r[qi]) by the
 // fp64 (score, id) rule.
-template <bool BAND, bool AFTER>
+// WEIGHTED (per-row weights, never with BAND): the candidates' score bits are those of
+// w32[row] * score and eps_in holds eps_w, so R is the near-tie set of the weighted order.  After the
+// fp64 chains decayed = w64[row] * s is formed as ONE multiplication and R is ranked by (decayed
+// desc, s desc, row asc); `exact` receives decayed and base_out s.
+template <bool BAND, bool AFTER, bool WEIGHTED = false>
 __device__ __forceinline__ void merge_body(
     unsigned char* lds, const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
     int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
     uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
     int64_t* __restrict__ ids, double* __restrict__ exact, uint32_t* __restrict__ flags,
     uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows, int keep_cnt, rf_band bd,
-    const double* __restrict__ after_s, const int64_t* __restrict__ after_r) {
+    const double* __restrict__ after_s, const int64_t* __restrict__ after_r,
+    const double* __restrict__ w64 = nullptr, double* __restrict__ base_out = nullptr) {
   static_assert(!AFTER || BAND, "a search-after merge is a band merge");
+  static_assert(!WEIGHTED || !BAND, "the weighted merge has no band form");
   unsigned long long* skeys = (unsigned long long*)lds;                       // [1024]
   unsigned long long* wtop = skeys + MERGE_RANK_MAX;                          // [4][RF_MAX_K]
   double* r_exact = (double*)(wtop + (MERGE_THREADS / 64) * RF_MAX_K);        // [RESCORE_CAP]
@@ -450,17 +508,40 @@ __device__ __forceinline__ void merge_body(
     __syncthreads();
     n_in = *n_band;
   }
-  for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
-    const double s = r_exact[i];
-    const uint32_t row = r_row[i];
-    if (BAND && s == -INFINITY) continue;
-    uint32_t rank = 0;
-    for (uint32_t j = 0; j < R; ++j) rank += ranks_before(r_exact[j], r_row[j], s, row) ? 1u : 0u;
-    if (rank < (uint32_t)k) {
-      const size_t o = (size_t)qi * k + rank;
-      scores[o] = (float)s;
-      ids[o] = (int64_t)row + id_base;
-      if (exact) exact[o] = s;
+  if constexpr (WEIGHTED) {
+    // the key area of passes 1 and 2 is free from here on: the decayed scores of R
+    double* r_dec = (double*)skeys;   // [RF_RESCORE_CAP] <= MERGE_RANK_MAX entries
+    for (uint32_t i = tid; i < R; i += MERGE_THREADS) r_dec[i] = __dmul_rn(w64[r_row[i]], r_exact[i]);
+    __syncthreads();
+    for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
+      const double d = r_dec[i], s = r_exact[i];
+      const uint32_t row = r_row[i];
+      uint32_t rank = 0;
+      for (uint32_t j = 0; j < R; ++j) {
+        const double od = r_dec[j];
+        rank += (od > d || (od == d && ranks_before(r_exact[j], r_row[j], s, row))) ? 1u : 0u;
+      }
+      if (rank < (uint32_t)k) {
+        const size_t o = (size_t)qi * k + rank;
+        scores[o] = (float)d;
+        ids[o] = (int64_t)row + id_base;
+        if (exact) exact[o] = d;
+        if (base_out) base_out[o] = s;
+      }
+    }
+  } else {
+    for (uint32_t i = tid; i < R; i += MERGE_THREADS) {
+      const double s = r_exact[i];
+      const uint32_t row = r_row[i];
+      if (BAND && s == -INFINITY) continue;
+      uint32_t rank = 0;
+      for (uint32_t j = 0; j < R; ++j) rank += ranks_before(r_exact[j], r_row[j], s, row) ? 1u : 0u;
+      if (rank < (uint32_t)k) {
+        const size_t o = (size_t)qi * k + rank;
+        scores[o] = (float)s;
+        ids[o] = (int64_t)row + id_base;
+        if (exact) exact[o] = s;
+      }
     }
   }
   const uint32_t filled = n_in < (uint32_t)k ? n_in : (uint32_t)k;
@@ -469,6 +550,7 @@ __device__ __forceinline__ void merge_body(
     scores[o] = -INFINITY;
     ids[o] = -1;
     if (exact) exact[o] = -INFINITY;
+    if (WEIGHTED && base_out) base_out[o] = -INFINITY;
   }
   if (flags && __syncthreads_or(bad_row ? 1 : 0)) fl |= RF_FLAG_CAND_OVERFLOW;
   if (tid == 0 && flags) flags[qi] = fl;
@@ -502,6 +584,19 @@ __global__ void __launch_bounds__(MERGE_THREADS) k_merge_after(
   merge_body<true, true>(lds, q, dim, KS, tiles, k, id_base, cand_cnt, cand, cap, eps_in, scores, ids, exact, flags,
                          cand_cnt_rw, n_rows, 0, bd, after_s, after_r);
 }
+// (a kernel of its own, so that the names and arguments of the others stay what they are)
+__global__ void __launch_bounds__(MERGE_THREADS) k_merge_weighted(
+    const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int k,
+    int64_t id_base, const uint32_t* __restrict__ cand_cnt, const uint2* __restrict__ cand,
+    uint32_t cap, const float* __restrict__ eps_in, float* __restrict__ scores,
+    int64_t* __restrict__ ids, double* __restrict__ decayed, double* __restrict__ base,
+    uint32_t* __restrict__ flags, uint32_t* __restrict__ cand_cnt_rw, uint32_t n_rows,
+    const double* __restrict__ w64) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  merge_body<false, false, true>(lds, q, dim, KS, tiles, k, id_base, cand_cnt, cand, cap, eps_in, scores, ids, decayed,
+                                 flags, cand_cnt_rw, n_rows, 0, rf_band{}, nullptr, nullptr, w64, base);
+}
+
 // ---- exhaustive exact path ----------------------------------------------------------
 // Workgroup-level running top-k list (sorted, in LDS) updated 256 entries at a
 // time by rank counting.  Used for queries the fused path could not prove
@@ -686,6 +781,116 @@ __global__ void __launch_bounds__(EX_THREADS) k_exhaustive_final(
   }
 }
 
+// ---- exhaustive path with per-row weights ------------------------------------
+// The running top-k list of above with one more key: entries rank by (decayed desc, s desc, row
+// asc), decayed = w64[row] * s as one fp64 multiplication.
+struct ExListW {
+  double d[RF_MAX_K];
+  double s[RF_MAX_K];
+  int64_t r[RF_MAX_K];
+  int n;
+};
+__device__ __forceinline__ bool ranks_before_w(double d1, double s1, int64_t r1, double d2, double s2, int64_t r2) {
+  return d1 > d2 || (d1 == d2 && ranks_before(s1, r1, s2, r2));
+}
+
+__device__ void exlist_update_w(ExListW* L, double* t_d, double* t_s, int64_t* t_r, int* t_n, int k, double d,
+                                double s, int64_t row, bool valid, int tid) {
+  bool pass = valid;
+  if (valid && L->n >= k) pass = ranks_before_w(d, s, row, L->d[k - 1], L->s[k - 1], L->r[k - 1]);
+  if (__syncthreads_or(pass ? 1 : 0) == 0) return;
+  if (tid == 0) *t_n = L->n;
+  __syncthreads();
+  if (tid < L->n) {
+    t_d[tid] = L->d[tid];
+    t_s[tid] = L->s[tid];
+    t_r[tid] = L->r[tid];
+  }
+  if (pass) {
+    const int slot = atomicAdd(t_n, 1);   // < RF_MAX_K + EX_THREADS: the list and one entry per thread
+    t_d[slot] = d;
+    t_s[slot] = s;
+    t_r[slot] = row;
+  }
+  __syncthreads();
+  const int m = *t_n;
+  for (int i = tid; i < m; i += EX_THREADS) {
+    const double di = t_d[i], si = t_s[i];
+    const int64_t ri = t_r[i];
+    int rank = 0;
+    for (int j = 0; j < m; ++j) rank += ranks_before_w(t_d[j], t_s[j], t_r[j], di, si, ri) ? 1 : 0;
+    if (rank < k) {
+      L->d[rank] = di;
+      L->s[rank] = si;
+      L->r[rank] = ri;
+    }
+  }
+  if (tid == 0) L->n = m < k ? m : k;
+  __syncthreads();
+}
+
+// mask: nullptr = every row
+__global__ void __launch_bounds__(EX_THREADS) k_exhaustive_scan_weighted(
+    const _Float16* __restrict__ q, int dim, int KS, const uint4* __restrict__ tiles, int64_t n_rows,
+    int k, double* __restrict__ out_d, double* __restrict__ out_s, int64_t* __restrict__ out_r,
+    const uint32_t* __restrict__ mask, const double* __restrict__ w64) {
+  __shared__ ExListW L;
+  __shared__ double t_d[RF_MAX_K + EX_THREADS];
+  __shared__ double t_s[RF_MAX_K + EX_THREADS];
+  __shared__ int64_t t_r[RF_MAX_K + EX_THREADS];
+  __shared__ int t_n;
+  const int tid = threadIdx.x;
+  const int qi = blockIdx.y;
+  if (tid == 0) L.n = 0;
+  __syncthreads();
+  const _Float16* qrow = q + (size_t)qi * dim;
+  const int64_t step = (int64_t)gridDim.x * EX_THREADS;
+  for (int64_t base = (int64_t)blockIdx.x * EX_THREADS; base < n_rows; base += step) {
+    const int64_t row = base + tid;
+    const bool valid = row < n_rows && (!mask || ((mask[row >> 5] >> (row & 31)) & 1u) != 0u);
+    const double s = valid ? exact_dot(qrow, tiles, row, KS) : 0.0;
+    const double d = valid ? __dmul_rn(w64[row], s) : 0.0;
+    exlist_update_w(&L, t_d, t_s, t_r, &t_n, k, d, s, row, valid, tid);
+  }
+  const size_t o = ((size_t)qi * gridDim.x + blockIdx.x) * RF_MAX_K;
+  if (tid < RF_MAX_K) {
+    out_d[o + tid] = tid < L.n ? L.d[tid] : -INFINITY;
+    out_s[o + tid] = tid < L.n ? L.s[tid] : -INFINITY;
+    out_r[o + tid] = tid < L.n ? L.r[tid] : -1;
+  }
+}
+
+__global__ void __launch_bounds__(EX_THREADS) k_exhaustive_final_weighted(
+    const double* __restrict__ in_d, const double* __restrict__ in_s, const int64_t* __restrict__ in_r, int lists,
+    int k, int64_t id_base, float* __restrict__ scores, int64_t* __restrict__ ids, double* __restrict__ decayed,
+    double* __restrict__ base_out) {
+  __shared__ ExListW L;
+  __shared__ double t_d[RF_MAX_K + EX_THREADS];
+  __shared__ double t_s[RF_MAX_K + EX_THREADS];
+  __shared__ int64_t t_r[RF_MAX_K + EX_THREADS];
+  __shared__ int t_n;
+  const int tid = threadIdx.x;
+  const int qi = blockIdx.x;
+  if (tid == 0) L.n = 0;
+  __syncthreads();
+  const size_t base = (size_t)qi * lists * RF_MAX_K;
+  const int total = lists * RF_MAX_K;
+  for (int b = 0; b < total; b += EX_THREADS) {
+    const int i = b + tid;
+    const bool valid = i < total && in_r[base + i] >= 0;
+    exlist_update_w(&L, t_d, t_s, t_r, &t_n, k, valid ? in_d[base + i] : 0.0, valid ? in_s[base + i] : 0.0,
+                    valid ? in_r[base + i] : 0, valid, tid);
+  }
+  for (int j = tid; j < k; j += EX_THREADS) {
+    const size_t o = (size_t)qi * k + j;
+    const bool have = j < L.n;
+    scores[o] = have ? (float)L.d[j] : -INFINITY;
+    ids[o] = have ? L.r[j] + id_base : -1;
+    if (decayed) decayed[o] = have ? L.d[j] : -INFINITY;
+    if (base_out) base_out[o] = have ? L.s[j] : -INFINITY;
+  }
+}
+
 // ---- cross-shard merge ---------------------------------------------------------------
 // in [W][B][k] (exact fp64, global id) -> out [B][k].  Ids are global and unique,
 // so ranking by (score desc, id asc) reproduces the single-device order bit for bit.
@@ -770,6 +975,46 @@ int rf_launch_threshold(const rf_index* ix, const void* q, int B, int k, int P,
   else
     hipLaunchKernelGGL(k_threshold<false>, grid, dim3(64), 0, st, (const _Float16*)q, B, ix->dim, k, ws.pmax, P,
                        ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt, fd, sq, rf_band{});
+  RF_HIP(hipGetLastError());
+  return RF_OK;
+}
+
+int rf_launch_threshold_weighted(const rf_index* ix, const void* q, int B, int k, int P, const rf_workspace& ws,
+                                 hipStream_t st) {
+  hipLaunchKernelGGL(k_threshold_weighted, dim3(RF_QCHUNK), dim3(64), 0, st, (const _Float16*)q, B, ix->dim, k, ws.pmax,
+                     P, ix->max_norm2, ws.thr, ws.eps, ws.cand_cnt);
+  RF_HIP(hipGetLastError());
+  return RF_OK;
+}
+
+int rf_launch_merge_weighted(const rf_index* ix, const void* q, int B, int k, int64_t id_base, const rf_workspace& ws,
+                             const double* w64, float* scores, int64_t* ids, double* decayed, double* base,
+                             uint32_t* flags, hipStream_t st) {
+  const size_t lds = merge_lds_bytes(ix->dim);
+  static rf_lds_attr lds_attr;
+  RF_HIP(rf_ensure_lds(lds_attr, (const void*)k_merge_weighted, lds));
+  hipLaunchKernelGGL(k_merge_weighted, dim3(B), dim3(MERGE_THREADS), lds, st, (const _Float16*)q, ix->dim, ix->KS,
+                     ix->tiles, k, id_base, ws.cand_cnt, ws.cand, (uint32_t)RF_SHARD_CAP, ws.eps, scores, ids, decayed,
+                     base, flags, ws.cand_cnt, (uint32_t)ix->size, w64);
+  RF_HIP(hipGetLastError());
+  return RF_OK;
+}
+
+int rf_launch_exhaustive_weighted(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
+                                  const rf_workspace& ws, const double* w64, float* scores, int64_t* ids,
+                                  double* decayed, double* base, hipStream_t st, const uint32_t* mask) {
+  const int64_t need = (ix->size + EX_THREADS - 1) / EX_THREADS;
+  const int lists = (int)(need < RF_EX_WGS ? (need < 1 ? 1 : need) : RF_EX_WGS);
+  // the third list array, the plain scores: the candidate area, which this path does not use otherwise
+  // (RF_QCHUNK * RF_EX_WGS * RF_MAX_K doubles = 8 MiB of its 32)
+  static_assert((size_t)RF_QCHUNK * RF_EX_WGS * RF_MAX_K * sizeof(double) <=
+                    (size_t)RF_QWIDE * RF_CAND_SHARDS * RF_SHARD_CAP * sizeof(uint2),
+                "the plain scores of the weighted exhaustive lists fit the candidate area");
+  double* ex_base = (double*)ws.cand;
+  hipLaunchKernelGGL(k_exhaustive_scan_weighted, dim3(lists, B), dim3(EX_THREADS), 0, st, (const _Float16*)q, ix->dim,
+                     ix->KS, ix->tiles, ix->size, k, ws.ex_score, ex_base, ws.ex_row, mask, w64);
+  hipLaunchKernelGGL(k_exhaustive_final_weighted, dim3(B), dim3(EX_THREADS), 0, st, ws.ex_score, ex_base, ws.ex_row,
+                     lists, k, id_base, scores, ids, decayed, base);
   RF_HIP(hipGetLastError());
   return RF_OK;
 }

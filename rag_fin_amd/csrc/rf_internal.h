@@ -206,14 +206,16 @@ struct rf_after {
 // rf_launch_threshold and rf_launch_emit take what it filled, nullptr = no fold
 // multi: nullptr = one filter for the batch; otherwise per-query filters -- filt is the union of
 // the batch's filters and each query's row bits are its own filter's (never with band / after)
+// w32: nullptr = plain scores; otherwise per-row weights -- the sweep runs on w32[row] * score, over
+// the filter's rows or, without filt, over every row (never with fold / band / after / multi)
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt = nullptr,
                      rf_fold* fold = nullptr, const rf_band* band = nullptr, const rf_after* after = nullptr,
-                     const rf_multi* multi = nullptr);
+                     const rf_multi* multi = nullptr, const float* w32 = nullptr);
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                    hipStream_t st, const rf_filter_view* filt = nullptr, const rf_fold* fold = nullptr,
                    const rf_band* band = nullptr, const rf_after* after = nullptr,
-                   const rf_multi* multi = nullptr);
+                   const rf_multi* multi = nullptr, const float* w32 = nullptr);
 // Shape of the 64-query sweeps (scan.hip, grouped.hip): waves per workgroup by dim, and the emit
 // grid = CUs x workgroups per CU (0 = the default of the dim), at most one wave per 32-row block.
 static inline int rf_waves_per_wg(int KS) { return KS >= 48 ? 8 : 4; }
@@ -266,6 +268,22 @@ int rf_launch_exhaustive(const rf_index* ix, const void* q, int B, int k, int64_
                          const rf_workspace& ws, float* scores, int64_t* ids, double* exact,
                          const double* after_s, const int64_t* after_r, hipStream_t st,
                          const uint32_t* mask = nullptr, const rf_band* band = nullptr);
+// Per-row weights (include/ragfin.h, "decayed search"): w32 / w64 [n_rows] on the device, every weight
+// in [0, 1].  The sweeps run on w32[row] * score; threshold and merge take eps_w = 2 eps for eps
+// (DESIGN 4.4q), and the merge ranks by (w64[row] * s desc, s desc, row asc).
+struct rf_weights {
+  const float* w32;
+  const double* w64;
+};
+int rf_launch_threshold_weighted(const rf_index* ix, const void* q, int B, int k, int P, const rf_workspace& ws,
+                                 hipStream_t st);
+int rf_launch_merge_weighted(const rf_index* ix, const void* q, int B, int k, int64_t id_base, const rf_workspace& ws,
+                             const double* w64, float* scores, int64_t* ids, double* decayed, double* base,
+                             uint32_t* flags, hipStream_t st);
+// (uses ws.cand as the third list array beside ws.ex_score / ws.ex_row)
+int rf_launch_exhaustive_weighted(const rf_index* ix, const void* q, int B, int k, int64_t id_base,
+                                  const rf_workspace& ws, const double* w64, float* scores, int64_t* ids,
+                                  double* decayed, double* base, hipStream_t st, const uint32_t* mask);
 // grouped.hip (include/ragfin.h, "grouping search"): one code per row, the best n_groups groups by
 // their best group_size rows.  The sweeps write one partition of group maxima per workgroup.
 #define RF_GROUP_PARTS 512   // partitions (workgroups) of the group-maximum sweep, at most

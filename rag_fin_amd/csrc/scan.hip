@@ -70,17 +70,47 @@ __device__ __forceinline__ void fold_top2(const f32x16& a, uint32_t rbase, float
 // MULTI (per-query filters, always with FILTER and without BAND): the filter word is per lane and
 // query group, `mwl[jb]` -- the word of the lane's own query's filter for this block -- instead of
 // the wave's `mword`.  A block of the union in which the lane's query has no row has word 0 there.
-template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false, bool BAND = false, bool MULTI = false>
+// WEIGHTED (per-row weights, always with FILTER, without BAND and MULTI): every score is multiplied
+// by the weight of its row, w32[row] in [0, 1], before anything looks at it -- the sample maxima,
+// the threshold test and the appended score bits are those of the weighted score.  Multiply first,
+// mask afterwards: a rejected row is set to -inf, and -inf * 0 would be a NaN.  The 16 weights of a
+// lane (four runs of four rows) are requested ahead of the MFMA chain; rows past the end weigh 0.
+template <int KS, int R, int JB, int MODE, bool LAST, bool FILTER = false, bool BAND = false, bool MULTI = false,
+          bool WEIGHTED = false>
 __device__ __forceinline__ void block_step(u32x4 (&ring)[R], const uint4* cur,
                                            const uint4* nxt, const u32x4* smemQ, int lane,
                                            uint32_t row0, const float (&th)[JB], float (&pm)[JB],
                                            float (&m1)[JB], uint32_t (&r1)[JB], float (&m2)[JB],
                                            EmitState& es, const ScanParams& p,
                                            uint32_t mword = 0u, const float* tc = nullptr,
-                                           const uint32_t* mwl = nullptr) {
+                                           const uint32_t* mwl = nullptr, const float* w32 = nullptr) {
   static_assert(!MULTI || (FILTER && !BAND && MODE != MODE_FOLD), "per-query filters: the plain masked sweep only");
+  static_assert(!WEIGHTED || (FILTER && !BAND && !MULTI && MODE != MODE_FOLD), "per-row weights: the plain masked sweep only");
   f32x16 acc[JB];
+  float wv[WEIGHTED ? 16 : 1];
+  if constexpr (WEIGHTED) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const uint32_t r0 = row0 + 8u * (uint32_t)g + 4u * (uint32_t)(lane >> 5);   // rows of registers 4 g .. 4 g + 3
+      if (r0 + 4u <= p.n_rows) {
+        const float4 v = *(const float4*)(w32 + r0);
+        wv[4 * g + 0] = v.x;
+        wv[4 * g + 1] = v.y;
+        wv[4 * g + 2] = v.z;
+        wv[4 * g + 3] = v.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wv[4 * g + j] = r0 + (uint32_t)j < p.n_rows ? w32[r0 + (uint32_t)j] : 0.f;
+      }
+    }
+  }
   mfma_block<KS, R, JB, LAST>(ring, cur, nxt, smemQ, lane, acc);
+  if constexpr (WEIGHTED) {
+#pragma unroll
+    for (int jb = 0; jb < JB; ++jb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[jb][i] *= wv[i];
+  }
 
   if (MODE != MODE_EMIT) {
     if (MULTI) {
@@ -156,6 +186,10 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   // filters, the row bits per lane those of its own query's filter
   constexpr bool MULTI = std::is_same<PT, ScanParamsM>::value;
   static_assert(!MULTI || (FILTER && !BAND), "per-query filters: the plain masked sweep only");
+  // WEIGHTED (p is a ScanParamsW): the masked sweep over w32[row] * score; without a filter
+  // (hdr == nullptr) the pass list is every block and the mask word the rows that exist
+  constexpr bool WEIGHTED = std::is_same<PT, ScanParamsW>::value;
+  static_assert(!WEIGHTED || (FILTER && !BAND), "per-row weights: the plain masked sweep only");
   u32x4* smemQ = (u32x4*)smem_raw;                                  // JB*KS*64 uint4
   unsigned char* tail = smem_raw + (size_t)JB * KS * RF_FRAG_BYTES;  // per-mode scratch
 
@@ -198,7 +232,9 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
   // partitions instead of P / G, and the k-th partition maximum of its queries exists.
   const uint32_t gw = (MULTI && MODE == MODE_SAMPLE) ? wave * gridDim.x + blockIdx.x : blockIdx.x * WAVES + wave;
   if constexpr (FILTER) {
-    const uint32_t npb = filter_pass_blocks(p.hdr, p.n_rows, p.n_blocks);
+    uint32_t npb;
+    if constexpr (WEIGHTED) npb = p.hdr ? filter_pass_blocks(p.hdr, p.n_rows, p.n_blocks) : p.n_blocks;
+    else npb = filter_pass_blocks(p.hdr, p.n_rows, p.n_blocks);
     if (MODE == MODE_SAMPLE) {  // ~1/16 of the pass blocks, spread evenly (rf_launch_sample)
       uint32_t n = npb / 16;
       n = n < p.work_lo ? p.work_lo : n;
@@ -249,11 +285,28 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
     }
   };
   (void)fitem;
+  // WEIGHTED: entry i of the pass list and the mask word of block b, with or without a filter
+  auto wblock = [&](uint32_t i) -> uint32_t {
+    if constexpr (WEIGHTED) return p.hdr ? p.blocks[i] : i;
+    else return i;
+  };
+  auto wmask = [&](uint32_t b) -> uint32_t {
+    if constexpr (WEIGHTED) {
+      if (p.hdr) return p.mask[b];
+      const uint32_t rows = p.n_rows - b * 32u;   // > 0: b is a block of the index
+      return rows < 32u ? (1u << rows) - 1u : 0xFFFFFFFFu;
+    } else {
+      return 0u;
+    }
+  };
+  (void)wblock;
+  (void)wmask;
 
   u32x4 ring[R];
   if (FILTER ? gw < p.n_work : gw < M) {
     const uint4* src;
-    if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[fitem(gw)] * (KS * 64) + lane;
+    if constexpr (WEIGHTED) src = p.corpus + (size_t)wblock(fitem(gw)) * (KS * 64) + lane;
+    else if constexpr (FILTER) src = p.corpus + (size_t)p.blocks[fitem(gw)] * (KS * 64) + lane;
     else if constexpr (MODE == MODE_EMIT && !BAND) src = p.corpus + (size_t)block_of(gw) * (KS * 64) + lane;
     else src = p.corpus + (size_t)gw * p.bstride * (KS * 64) + lane;
 #pragma unroll
@@ -301,6 +354,22 @@ __device__ __forceinline__ void scan_body(PT p, unsigned char* smem_raw) {
         for (int jb = 0; jb < JB; ++jb) mwl[jb] = p.masks_t[(size_t)b * p.gp + gcol[jb]];
         const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
         block_step<KS, R, JB, MODE, true, true, false, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, 0u, tc, mwl);
+      }
+    } else if constexpr (WEIGHTED) {
+      // the masked sweep below, over the weighted scores
+      uint32_t b = wblock(w * p.bstride);
+      for (uint32_t i = 0; i + 1 < cnt; ++i, w += W) {
+        const uint32_t bn = wblock((w + W) * p.bstride);
+        const uint32_t mw = wmask(b);
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        const uint4* nxt = p.corpus + (size_t)bn * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, false, true, false, false, true>(ring, cur, nxt, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw, tc, nullptr, p.w32);
+        b = bn;
+      }
+      {
+        const uint32_t mw = wmask(b);
+        const uint4* cur = p.corpus + (size_t)b * (KS * 64) + lane;
+        block_step<KS, R, JB, MODE, true, true, false, false, true>(ring, cur, cur, smemQ, lane, b * 32u, th, pm, m1, r1, m2, es, p, mw, tc, nullptr, p.w32);
       }
     } else if constexpr (FILTER) {
       uint32_t b = p.blocks[w * p.bstride];
@@ -418,6 +487,14 @@ k_scan_filtered(typename std::conditional<MULTI, ScanParamsM, ScanParamsF>::type
   scan_body<KS, R, JB, WAVES, MODE, true, BAND, false>(p, smem_raw);
 }
 
+// Per-row weights: the masked sweep over w32[row] * score (a kernel of its own, so that the names
+// and arguments of the others stay what they are).
+template <int KS, int R, int JB, int WAVES, int MODE>
+__global__ void __launch_bounds__(WAVES * 64, 2) k_scan_weighted(ScanParamsW p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  scan_body<KS, R, JB, WAVES, MODE, true, false, false>(p, smem_raw);
+}
+
 // The search-after sweeps: the band sweeps above with the per-query ceiling.
 template <int KS, int R, int JB, int WAVES, int MODE>
 __global__ void __launch_bounds__(WAVES * 64, 2) k_scan_after(ScanParamsA p) {
@@ -468,6 +545,7 @@ static int launch_scan(const PT& p, int grid, hipStream_t st) {
   auto kern = [] {
     if constexpr (std::is_same<PT, ScanParamsF>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE, BAND>;
     else if constexpr (std::is_same<PT, ScanParamsM>::value) return k_scan_filtered<KS, R, JB, WAVES, MODE, BAND, true>;
+    else if constexpr (std::is_same<PT, ScanParamsW>::value) return k_scan_weighted<KS, R, JB, WAVES, MODE>;
     else if constexpr (std::is_same<PT, ScanParamsFA>::value) return k_scan_filtered_after<KS, R, JB, WAVES, MODE>;
     else if constexpr (std::is_same<PT, ScanParamsA>::value) return k_scan_after<KS, R, JB, WAVES, MODE>;
     else return k_scan<KS, R, JB, WAVES, MODE, BAND>;
@@ -550,9 +628,17 @@ static ScanParamsM multi_params(const ScanParamsF& f, const rf_multi& multi) {
   return m;
 }
 
+// Per-row weights: the masked sweep's arguments (filt: the filter's, or none of them) with the weights.
+static ScanParamsW weighted_params(const ScanParamsF& f, const float* w32) {
+  ScanParamsW w{};
+  static_cast<ScanParamsF&>(w) = f;
+  w.w32 = w32;
+  return w;
+}
+
 int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                      int* P_out, hipStream_t st, const rf_filter_view* filt, rf_fold* fold,
-                     const rf_band* band, const rf_after* after, const rf_multi* multi) {
+                     const rf_band* band, const rf_after* after, const rf_multi* multi, const float* w32) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int WAVES = rf_waves_per_wg(KS);
@@ -587,17 +673,20 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
     p.eps = ws.eps;
     p.band_hi = band->hi;
   }
-  if (filt) {
+  if (filt || w32) {
     // the grid (= partitions) is sized from the whole corpus; the kernel derives the sampled
     // count and stride from the filter's device count of pass blocks, within the same bounds
     ScanParamsF f{};
     static_cast<ScanParams&>(f) = p;
-    f.hdr = filt->hdr;
-    f.mask = filt->mask;
-    f.blocks = filt->blocks;
+    if (filt) {
+      f.hdr = filt->hdr;
+      f.mask = filt->mask;
+      f.blocks = filt->blocks;
+    }
     f.n_blocks = nblk;
     f.work_lo = lo;
     f.work_hi = hi;
+    if (w32) return dispatch_scan<MODE_SAMPLE>(KS, JB, weighted_params(f, w32), grid, grid, st);
     if (multi) return dispatch_scan<MODE_SAMPLE>(KS, JB, multi_params(f, *multi), grid, grid, st);
     if (band && after) {
       ScanParamsFA fa{};
@@ -628,7 +717,7 @@ int rf_launch_sample(const rf_index* ix, const void* q, int B, int JB, const rf_
 
 int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_workspace& ws,
                    hipStream_t st, const rf_filter_view* filt, const rf_fold* fold, const rf_band* band,
-                   const rf_after* after, const rf_multi* multi) {
+                   const rf_after* after, const rf_multi* multi, const float* w32) {
   const int KS = ix->KS;
   const uint32_t nblk = (uint32_t)((ix->size + 31) / 32);
   const int grid = rf_emit_grid(ix, rf_knob_emit_wgs_per_cu);
@@ -657,14 +746,17 @@ int rf_launch_emit(const rf_index* ix, const void* q, int B, int JB, const rf_wo
     p.s_bs = fold->bstride;
     p.s_W = fold->W;
   }
-  if (filt) {
+  if (filt || w32) {
     // grid and ring depth as for the whole corpus; waves past the device count exit
     ScanParamsF f{};
     static_cast<ScanParams&>(f) = p;
-    f.hdr = filt->hdr;
-    f.mask = filt->mask;
-    f.blocks = filt->blocks;
+    if (filt) {
+      f.hdr = filt->hdr;
+      f.mask = filt->mask;
+      f.blocks = filt->blocks;
+    }
     f.n_blocks = nblk;
+    if (w32) return dispatch_scan<MODE_EMIT>(KS, JB, weighted_params(f, w32), grid, grid, st);
     if (multi) return dispatch_scan<MODE_EMIT>(KS, JB, multi_params(f, *multi), grid, grid, st);
     if (band && after) {
       ScanParamsFA fa{};

@@ -62,6 +62,14 @@ struct ScanParamsM : ScanParamsF {
   uint32_t gp;               // words per block: a power of two >= the number of filters
 };
 
+// Per-row weights (k_scan_weighted; decayed search): the masked sweep over
+// w32[row] * score.  hdr == nullptr: no filter -- the work items are the blocks of the index and the
+// mask word of a block has the bits of its existing rows (mask / blocks are not read then).  A type
+// of its own, so that the arguments of the other sweeps stay what they are.
+struct ScanParamsW : ScanParamsF {
+  const float* w32;   // [n_rows], 16-byte aligned, every weight in [0, 1]
+};
+
 // Search-after (k_scan_after / k_scan_filtered_after, always the band form): the fp64 score of each
 // query's bound.  The ceiling of query b is rf_after_ceiling(band_hi, after_s[b], ...) instead of
 // band_hi: min(hi, bound) in the emit, the strict one in the sample pass.  Types of

@@ -1,7 +1,8 @@
 """The device layer under rag_fin_amd/store.py (which re-exports these names): `GpuIndex` over
 rf_index_* / rf_search (include/ragfin.h), the flagged-query ladder, the filter-mask helpers and
 rf_filter_eval; `SparseIndex` over rf_sparse_* (BM25 posting lists), `fuse_rrf` over rf_fuse_rrf, and
-`boost_classes` / `merge_boosted` over rf_boost_classes / rf_merge_boosted (boosted search).
+`boost_classes` / `merge_boosted` over rf_boost_classes / rf_merge_boosted (boosted search), and
+`decay_weights` over rf_decay_weights (decayed search; the sweep itself is `GpuIndex.search(weights=)`).
 All arithmetic goes through libragfin_hip.so; there is no CPU path."""
 from __future__ import annotations
 
@@ -827,15 +828,94 @@ class GpuIndex:
         self._mmr_select(cand[2].contiguous(), cand[1].contiguous(), k, mmr, id_base, rows)
         return res, bad, list(rows)
 
+    # -- per-row weights (include/ragfin.h, "decayed search") --------------------------------
+    def _check_weights(self, weights, filt, sq8: bool = False, band=None, group=None, mmr=None):
+        """weights = (w32 float32 [size], w64 float64 [size]) on this device, contiguous, every weight in [0, 1]
+        (decay_weights gives such a pair); with at most one filter buffer and no other form."""
+        torch = _torch()
+        for name, on in (("per-query filter (MultiFilter)", isinstance(filt, MultiFilter)), ("SQ8", sq8),
+                         ("range (band)", band is not None), ("grouping", group is not None), ("MMR", mmr is not None)):
+            if on:
+                raise ValueError(f"weighted search has no {name} form")
+        n = self.size
+        ok = isinstance(weights, (tuple, list)) and len(weights) == 2 and all(torch.is_tensor(w) for w in weights)
+        if ok:
+            w32, w64 = weights
+            ok = w32.dtype == torch.float32 and w64.dtype == torch.float64 and tuple(w32.shape) == (n,) and \
+                tuple(w64.shape) == (n,) and w32.device == self.device and w64.device == self.device and \
+                w32.is_contiguous() and w64.is_contiguous() and w32.data_ptr() % 16 == 0
+        if not ok:
+            raise ValueError(f"weights must be (float32 [{n}], float64 [{n}]) contiguous tensors on {self.device}, "
+                             "the first 16-byte aligned")
+        return weights
+
+    def search_weighted_raw(self, q16, k: int, weights, id_base: int = 0, filt=None):
+        """Enqueue rf_search_weighted on the current stream; no host sync, no lock (as search_raw).
+        -> (scores f32 [B,k], ids i64 [B,k], decayed f64 [B,k], base f64 [B,k], flags i32 [B]): per
+        query the best k rows (of the rows `filt` passes) by (w64[row] * s desc, s desc, row asc)."""
+        torch = _torch()
+        w32, w64 = self._check_weights(weights, filt)
+        if q16.dtype != torch.float16 or q16.dim() != 2 or q16.shape[1] != self.dim:
+            raise ValueError(f"search expects fp16 [B, {self.dim}] queries")
+        if not q16.is_contiguous() or q16.device != self.device:
+            q16 = q16.to(self.device).contiguous()
+        B = q16.shape[0]
+        scores, ids, decayed, flags = self._outputs(B, k, True)
+        base = torch.empty((B, k), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_search_weighted(self.handle, _ptr(filt), _ptr(w32), _ptr(w64), _ptr(q16), B, k, id_base,
+                                                   _ptr(scores), _ptr(ids), _ptr(decayed), _ptr(base), _ptr(flags),
+                                                   _ptr(self.workspace), self.workspace_bytes, _lib.current_stream_ptr()))
+        return scores, ids, decayed, base, flags
+
+    def _exhaustive_weighted(self, q16, k: int, weights, id_base: int = 0, filt=None):
+        """rf_search_exhaustive_weighted -> (scores, ids, decayed, base).  Uses the index workspace: the
+        caller holds the lock."""
+        torch = _torch()
+        w32, w64 = weights
+        q16 = q16.to(self.device).contiguous()
+        B = q16.shape[0]
+        scores, ids, decayed, _ = self._outputs(B, k, True, flags=False)
+        base = torch.empty((B, k), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.rf_search_exhaustive_weighted(
+                self.handle, _ptr(filt), _ptr(w32), _ptr(w64), _ptr(q16), B, k, id_base, _ptr(scores), _ptr(ids),
+                _ptr(decayed), _ptr(base), _ptr(self.workspace), self.workspace_bytes, _lib.current_stream_ptr()))
+        return scores, ids, decayed, base
+
+    def search_exhaustive_weighted(self, q16, k: int, weights, id_base: int = 0, filt=None):
+        self._check_weights(weights, filt)
+        with self._lock:
+            return self._exhaustive_weighted(q16, k, weights, id_base, filt)
+
+    def _search_weighted(self, q16, k: int, weights, id_base: int, filt):
+        """search_weighted_raw, then the flagged queries again through the exhaustive weighted kernel,
+        over the same rows and weights -> (scores, ids, decayed, base)."""
+        with self._lock:
+            *res, flags = self.search_weighted_raw(q16, k, weights, id_base, filt)
+            bad, rows = rerun_flagged(q16, k, id_base, flags, False, filt, None,
+                                      lambda q, k, base, f: self._exhaustive_weighted(q, k, weights, base, f))
+            if rows is not None:
+                for dst, src in zip(res, rows):
+                    dst[bad] = src
+        return tuple(res)
+
     def search(self, q16, k: int, id_base: int = 0, want_exact: bool = False, filt=None, sq8: bool = False,
-               band=None, group=None, mmr=None):
+               band=None, group=None, mmr=None, weights=None):
         """rf_search, then the flagged-query ladder (rerun_flagged) for any query the fused path
         could not prove exact.  filt: over the passing rows.  sq8: rf_search_sq8 first.
         band: (radius, range_filter) -- rf_search_range, flagged queries through the exhaustive
         band kernel.  group: as in search_raw -- rf_search_grouped, flagged queries (and every query
         of a dictionary above RF_GROUP_MAX_CODES) group by group through the exhaustive kernel.
         mmr: (fetch_k, lam), as in search_raw -- k of the best fetch_k hits by maximal marginal
-        relevance; flagged queries get their candidates from the ladder and are selected again."""
+        relevance; flagged queries get their candidates from the ladder and are selected again.
+        weights: (w32, w64) per-row weights in [0, 1] (decay_weights) -- rf_search_weighted: the best k
+        rows by (w64[row] * s desc, s desc, row asc), flagged queries through the exhaustive weighted
+        kernel; the result is then (scores, ids, decayed f64, base f64).  With filt (one filter
+        buffer) or without; no other form (ValueError)."""
+        if weights is not None:
+            self._check_weights(weights, filt, sq8, band, group, mmr)
+            return self._search_weighted(q16, k, weights, id_base, filt)
         with self._lock:
             (scores, ids, exact, _), bad, rows = self._search_ladder(q16, k, id_base, want_exact, filt, sq8, band, group,
                                                                      mmr=mmr)
@@ -1330,6 +1410,27 @@ def merge_boosted(cand_exact, cand_ids, class_weights, k: int):
                                                         _ptr(ids), _ptr(boosted), _ptr(base),
                                                         _lib.current_stream_ptr()))
     return scores, ids, boosted, base
+
+
+def decay_weights(column, ranker):
+    """Enqueue rf_decay_weights on the current stream: the row weights of `ranker` (a ranker.DecayRanker) over
+    `column`, an int64 or float64 device tensor [n] -> (w32 float32 [n], w64 float64 [n]) on its device, bit for
+    bit ranker.decay_weights_reference and its float32 rounding."""
+    torch = _torch()
+    if not torch.is_tensor(column) or column.dim() != 1 or column.dtype not in (torch.int64, torch.float64):
+        raise ValueError("decay_weights expects an int64 or float64 device tensor [n]")
+    column = column.contiguous()
+    n = column.numel()
+    dev = column.device
+    with torch.cuda.device(dev):
+        w64 = torch.empty((n,), dtype=torch.float64, device=dev)
+        w32 = torch.empty((n,), dtype=torch.float32, device=dev)
+        if n:
+            _lib.check(_lib.load_library().rf_decay_weights(
+                _ptr(column), 1 if column.dtype == torch.int64 else 0, n, int(ranker.function_code), float(ranker.origin),
+                float(ranker.scale), float(ranker.offset), float(ranker.shape), _ptr(w64), _ptr(w32),
+                _lib.current_stream_ptr()))
+    return w32, w64
 
 
 def filter_from_mask(words, n_rows: int):

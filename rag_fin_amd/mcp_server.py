@@ -59,7 +59,10 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                    max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                    mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
                    hybrid: bool = False, offset: int | None = None, boost_filter: str = "",
-                   boost_weight: float | None = None, lexical: str | None = None, rerank_with: str | None = None):
+                   boost_weight: float | None = None, lexical: str | None = None, rerank_with: str | None = None,
+                   decay_field: str = "", decay_function: str | None = None, decay_origin: float | None = None,
+                   decay_scale: float | None = None, decay_offset: float | None = None,
+                   decay_rate: float | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -83,8 +86,34 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     boost_filter / boost_weight: optional soft filter -- the chunks the expression boost_filter selects
     have their score multiplied by boost_weight (> 0; below 1 demotes), the rest stay in the ranking;
     `score` is then the boosted score.  Both or neither; with filter, not with min_score / max_score,
-    group_by, mmr_lambda, rerank, hybrid or offset."""
+    group_by, mmr_lambda, rerank, hybrid or offset.
+    decay_field / decay_function / decay_origin / decay_scale (and optionally decay_offset, default 0, and
+    decay_rate, default 0.5): optional time decay -- every chunk's score is multiplied by a weight that is 1
+    where the numeric field decay_field lies within decay_offset of decay_origin and falls to decay_rate at
+    distance decay_offset + decay_scale, along a "gauss", "exp" or "linear" curve; `score` is then the decayed
+    score.  The first four go together; with filter, with the exclusions of the boost and not together with it."""
     try:
+        decay_given = [v is not None for v in (decay_function, decay_origin, decay_scale, decay_offset, decay_rate)]
+        if bool(decay_field and decay_field.strip()) or any(decay_given):
+            # a decayed call bypasses the micro-batcher like a boosted one: one batch shares one decay
+            if not (decay_field and decay_field.strip()) or not all(decay_given[:3]):
+                raise ValueError("decay_field, decay_function, decay_origin and decay_scale go together")
+            decay = {"field": decay_field, "function": decay_function, "origin": decay_origin, "scale": decay_scale}
+            if decay_offset is not None:
+                decay["offset"] = decay_offset
+            if decay_rate is not None:
+                decay["decay"] = decay_rate
+            kw = {name: v for name, v in (("min_score", min_score), ("max_score", max_score), ("group_by", group_by),
+                                          ("mmr_lambda", mmr_lambda), ("fetch_k", fetch_k), ("offset", offset))
+                  if v is not None}
+            if rerank:
+                kw["rerank"] = True
+            if hybrid:
+                kw["hybrid"] = True
+            if bool(boost_filter and boost_filter.strip()) or boost_weight is not None:
+                kw["boost"] = {"filter": boost_filter, "weight": boost_weight}   # (VectorRAG refuses the combination)
+            contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None, decay=decay, **kw)
+            return {"status": "success", "query": query, "results": contexts, "result_count": len(contexts)}
         boosted = bool(boost_filter and boost_filter.strip()) or boost_weight is not None
         if boosted:
             # a boosted call bypasses the micro-batcher: one batch shares one boost (VectorRAG refuses

@@ -117,7 +117,7 @@ class VectorRAG:
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
                hybrid: bool = False, offset: int | None = None, boost=None, lexical: str = "bm25",
-               rerank_with: str = "cross") -> list[dict]:
+               rerank_with: str = "cross", decay=None) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -152,8 +152,15 @@ class VectorRAG:
         filter: the chunks the expression selects have their score multiplied by w (below 1:
         demoted; several boosts multiply) and the top_k are the exact best of the whole store under
         that boosted score, which is what `score` then holds.  With expr (one string); not with
-        rerank, hybrid, group_by, mmr_lambda, min_score / max_score or offset (ValueError)."""
+        rerank, hybrid, group_by, mmr_lambda, min_score / max_score or offset (ValueError).
+        decay: {"field", "function", "origin", "scale"} and optionally "offset" (default 0) and "decay" (default
+        0.5) -- time decay: every chunk's score is multiplied by a weight in [0, 1] that is 1 where the numeric
+        field (primary_value, or an INT64 / DOUBLE field of the store) lies within `offset` of `origin` and falls
+        to `decay` at distance offset + scale, along a "gauss", "exp" or "linear" curve; the top_k are the exact
+        best of the whole store under that decayed score, which is what `score` then holds.  With expr (one
+        string); with the same exclusions as boost, and not together with boost (ValueError)."""
         ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
+        ranker = self._decay_args(decay, ranker, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
         self._check_lexical(lexical, hybrid)
         self._check_rerank_with(rerank_with, rerank)
@@ -186,6 +193,25 @@ class VectorRAG:
                                                         for b in items):
             raise ValueError(f'boost must be {{"filter": str, "weight": float}} or a list of 1..{MAX_BOOSTS} such dicts')
         return {"ranker": [BoostRanker(b["filter"], b["weight"]) for b in items]}
+
+    @staticmethod
+    def _decay_args(decay, boosts: dict, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr) -> dict:
+        """The store's ranker argument from `decay`; `boosts` (what _boost_args gave) when it was not given."""
+        if decay is None:
+            return boosts
+        if boosts:
+            raise ValueError("decay and boost do not combine yet: pass one of them")
+        if rerank or hybrid or group_by is not None or mmr_lambda is not None or min_score is not None or \
+                max_score is not None or offset is not None or isinstance(expr, (list, tuple)):
+            raise ValueError("decay re-weighs the plain ranking: it does not combine with rerank, hybrid, group_by, "
+                             "mmr_lambda, min_score / max_score, offset or a list expr")
+        from .ranker import DecayRanker
+        keys = {"field", "function", "origin", "scale", "offset", "decay"}
+        if not isinstance(decay, dict) or not {"field", "function", "origin", "scale"} <= set(decay) <= keys:
+            raise ValueError('decay must be {"field": str, "function": "gauss" | "exp" | "linear", "origin": float, '
+                             '"scale": float} with optional "offset" and "decay"')
+        return {"ranker": DecayRanker(decay["field"], decay["function"], decay["origin"], decay["scale"],
+                                      decay.get("offset", 0.0), decay.get("decay", 0.5))}
 
     def _embed(self, texts):
         """`.encode(texts)` of the reference (main.py:50) -- kept on the device when the embedder
@@ -299,7 +325,7 @@ class VectorRAG:
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
                      rerank: bool = False, hybrid: bool = False, offset: int | None = None,
-                     boost=None, lexical: str = "bm25", rerank_with: str = "cross") -> list[list[dict]]:
+                     boost=None, lexical: str = "bm25", rerank_with: str = "cross", decay=None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
@@ -311,8 +337,10 @@ class VectorRAG:
         filter"): per-query filters, still one corpus sweep per 64 queries
         (CorpusStore.search(expr=[...])).  The list form is the plain path only: with rerank, hybrid,
         min_score / max_score, group_by, mmr_lambda or offset it raises ValueError.
-        boost: one boost (or up to 3) for the whole batch, as in search(); not with a list expr."""
+        boost: one boost (or up to 3) for the whole batch, as in search(); not with a list expr.
+        decay: one time decay for the whole batch, as in search(); not with a list expr."""
         ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
+        ranker = self._decay_args(decay, ranker, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         if isinstance(expr, (list, tuple)):
             if rerank or hybrid or min_score is not None or max_score is not None or group_by is not None or \
                     mmr_lambda is not None or offset is not None:

@@ -306,6 +306,10 @@ class ShardedCorpusStore(CorpusStore):
     def search(self, data, anns_field: str = "embedding", param=None, limit: int = 3, expr=None,
                output_fields=None, group_by_field=None, group_size: int = 1, strict_group_size: bool = False,
                mmr_lambda=None, mmr_fetch_k=None, offset=None, ranker=None):
+        from .ranker import DecayRanker
+        if isinstance(ranker, DecayRanker):
+            # (the weights come from the live column mirrors, which no shard holds)
+            raise NotImplementedError("decayed search (ranker) is not implemented for the sharded store")
         if ranker is not None:
             # (the class masks need the filter programs, which do not run over shards)
             raise NotImplementedError("boosted search (ranker) is not implemented for the sharded store")

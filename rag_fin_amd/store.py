@@ -42,9 +42,9 @@ from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
 from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, column_match, dynamic_match,  # noqa: F401
-                    eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
+                    decay_weights, eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
                     plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
-from .ranker import BoostRanker, check_rankers, class_weights  # noqa: F401
+from .ranker import BoostRanker, DecayRanker, check_rankers, class_weights  # noqa: F401
 from .text_fields import LEARNED_FIELD, TOKEN_FIELD, LearnedSparseField, LexicalField, TokenVectorField, is_text  # noqa: F401
 
 
@@ -996,6 +996,12 @@ class CorpusStore:
         (DESIGN §4.4m): ceil(B * classes / 64) sweeps of the corpus.  The plain dense search only:
         one expr string, limit <= 64, no offset, radius / range_filter, group_by_field, mmr_lambda /
         mmr_fetch_k or anns_field="sparse" (ValueError); an SQ8 collection answers from its fp16 rows.
+        ranker may instead be ONE DecayRanker(field, function, origin, scale, offset, decay): decayed search --
+        every row's score is multiplied by a weight in [0, 1] from the distance of `field` (primary_value or an
+        INT64 / DOUBLE field of the collection) to `origin`, and the hits are the exact top `limit` (of the rows
+        passing expr) by (decayed desc, plain score desc, row asc); hit.score is float32(decayed).  The weights are
+        computed from the live column on every call and sit inside the sweep: one sweep per 64 queries (DESIGN
+        §4.4q).  The same exclusions as a boost; a list of rankers that holds a DecayRanker raises ValueError.
         offset (or param["offset"], as pymilvus accepts it; the keyword wins when both are given): the
         hits of ranks offset + 1 ... offset + limit, i.e. search(limit=offset + limit)[offset:].  An
         int >= 0 with offset + limit <= 16384 (Milvus' window), else ValueError.  With expr, range
@@ -1040,6 +1046,12 @@ class CorpusStore:
         plain search only: limit <= 64, and no offset, radius / range_filter, group_by_field,
         mmr_lambda / mmr_fetch_k or anns_field="sparse" (ValueError; neither search_iterator,
         hybrid_search arms, query nor delete take a list).  These can follow later."""
+        if isinstance(ranker, DecayRanker):
+            return self._search_decayed(data, anns_field, param, limit, expr, output_fields, group_by_field,
+                                        mmr_lambda, mmr_fetch_k, offset, ranker)
+        if isinstance(ranker, (list, tuple)) and any(isinstance(r, DecayRanker) for r in ranker):
+            raise ValueError("a DecayRanker is passed on its own (ranker=DecayRanker(...)): lists of rankers and a decay "
+                             "mixed with boosts are not served yet")
         if ranker is not None:
             return self._search_boosted(data, anns_field, param, limit, expr, output_fields, group_by_field,
                                         mmr_lambda, mmr_fetch_k, offset, ranker)
@@ -1156,30 +1168,37 @@ class CorpusStore:
                        ranker) -> list:
         """Everything a boosted search refuses, before anything runs -> the list of its boosts."""
         boosts = check_rankers(ranker)
+        self._check_ranked_form("boosted", data, anns_field, param, limit, expr, group_by_field, mmr_lambda, mmr_fetch_k,
+                                offset)
+        return boosts
+
+    def _check_ranked_form(self, kind, data, anns_field, param, limit, expr, group_by_field, mmr_lambda, mmr_fetch_k,
+                           offset) -> None:
+        """The forms a search with a ranker (kind: "boosted" or "decayed") does not have."""
+        what = f"{kind} search (ranker)"
         if isinstance(expr, (list, tuple)):
-            raise ValueError("boosted search (ranker) cannot be combined with per-query filters (a list expr)")
+            raise ValueError(f"{what} cannot be combined with per-query filters (a list expr)")
         field = self._text_field(anns_field)
         if field is not None:
-            raise ValueError(f"boosted search (ranker) has no {field.form} form (anns_field='{field.name}')")
+            raise ValueError(f"{what} has no {field.form} form (anns_field='{field.name}')")
         if anns_field != "embedding":
             raise ValueError(f"unknown vector field {anns_field!r}")
         if self._is_text(data):
             raise ValueError("the embedding field is searched with vectors, not with strings (BM25: anns_field='sparse')")
         if group_by_field is not None:
-            raise ValueError("boosted search (ranker) cannot be combined with group_by_field")
+            raise ValueError(f"{what} cannot be combined with group_by_field")
         if mmr_lambda is not None or mmr_fetch_k is not None:
-            raise ValueError("boosted search (ranker) cannot be combined with mmr_lambda / mmr_fetch_k")
+            raise ValueError(f"{what} cannot be combined with mmr_lambda / mmr_fetch_k")
         if check_offset(offset, param, limit):
-            raise ValueError("boosted search (ranker) takes no offset")
+            raise ValueError(f"{what} takes no offset")
         if self._band_of(param) is not None:
-            raise ValueError("boosted search (ranker) has no range form (radius / range_filter)")
+            raise ValueError(f"{what} has no range form (radius / range_filter)")
         if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)) or not 1 <= limit <= _lib.RF_MAX_K:
-            raise ValueError(f"boosted search (ranker): limit must be an integer in 1..{_lib.RF_MAX_K}, "
-                             f"got {limit!r} (boosted results are not paged)")
+            raise ValueError(f"{what}: limit must be an integer in 1..{_lib.RF_MAX_K}, "
+                             f"got {limit!r} ({kind} results are not paged)")
         metric = (param or {}).get("metric_type", self.metric_type).upper()
         if metric != self.metric_type:
             raise ValueError(f"collection was built for {self.metric_type}, search asked for {metric}")
-        return boosts
 
     def _search_boosted(self, data, anns_field, param, limit, expr, output_fields, group_by_field, mmr_lambda,
                         mmr_fetch_k, offset, ranker, timing: dict | None = None):
@@ -1243,6 +1262,65 @@ class CorpusStore:
             if timing is not None:
                 timing.update(sweeps=sweeps, classes=C)
             rows, scores = packed[:, :k], packed[:, k:].astype(np.int32).view(np.float32)
+            return [self._hits(rows[b], scores[b], fields) for b in range(B)]
+
+    # -- decayed search: search(ranker=DecayRanker(...)) -----------------------------------
+    def _check_decay_field(self, name: str):
+        """The field a decay ranker reads: primary_value (-> None) or an INT64 / DOUBLE field of the
+        collection's own (-> its FieldSchema).  Anything else raises ValueError naming it."""
+        if name == "primary_value":
+            return None
+        own = self._field(name)
+        if own is not None and own.dtype in (DataType.INT64, DataType.DOUBLE):
+            return own
+        if own is not None:
+            why = f"a {own.dtype.name} field"
+        elif name in SCALAR_FIELDS or name in ("embedding", "$meta") or self._text_field(name) is not None:
+            why = "a reserved field that holds no number to decay over"
+        elif self.enable_dynamic_field:
+            why = "a dynamic key (typed per row)"
+        else:
+            why = "unknown"
+        raise ValueError(f"decay ranker: field {name!r} is {why}; it must be primary_value or a declared INT64 / DOUBLE field")
+
+    def _decay_column(self, own):
+        """The live device column of a decay field: int64 or fp64 [n], from the mirrors the filters use."""
+        with self._filter_lock:
+            if own is not None:
+                return self._extra_column(own).data
+            if self._dcols is None:
+                self._dcols = _DeviceColumns(self.index.device)
+            self._dcols.sync(self.columns, self.num_entities)
+            return self._dcols.values
+
+    def _search_decayed(self, data, anns_field, param, limit, expr, output_fields, group_by_field, mmr_lambda,
+                        mmr_fetch_k, offset, ranker: DecayRanker, timing: dict | None = None):
+        """search(ranker=DecayRanker(...)): the weights of the live column (rf_decay_weights, per call: add, delete
+        and upsert need no bookkeeping), then one weighted sweep per 64 queries through the flagged-query ladder.
+        timing: a dict that receives the milliseconds of the call's stages (filter, weights, search); it
+        synchronises between them (tools/bench_decay.py)."""
+        own = self._check_decay_field(ranker.field)
+        self._check_ranked_form("decayed", data, anns_field, param, limit, expr, group_by_field, mmr_lambda, mmr_fetch_k,
+                                offset)
+        fields = self._check_output_fields(output_fields)
+        B = self._query_count(data)
+        k = int(limit)
+        with self._rw.read():
+            n = self.num_entities
+            if n == 0 or B == 0:
+                return [[] for _ in range(B)]
+            torch = _torch()
+            clock = _StageClock(timing, self.index.device)
+            filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
+            clock.lap("filter_ms")
+            weights = decay_weights(self._decay_column(own), ranker)
+            clock.lap("weights_ms")
+            q16 = self._prepare_queries(data)
+            scores, rows, _, _ = self.index.search(q16, k, filt=filt, weights=weights)
+            packed = torch.cat([rows, scores.view(torch.int32).to(torch.int64)], 1).cpu().numpy()   # the one download
+            clock.lap("search_ms")
+            rows, scores = packed[:, :k], packed[:, k:].astype(np.int32).view(np.float32)
+            # (when no row passes, every slot is padding and the lists are empty)
             return [self._hits(rows[b], scores[b], fields) for b in range(B)]
 
     def _check_group_by(self, field, group_size, limit, param):
@@ -1347,8 +1425,8 @@ class CorpusStore:
         ranker is not offered (WeightedRanker raises NotImplementedError; weigh by RRFRanker(weights=...)).
         A boost ranker (ranker=, or a BoostRanker as rerank) has no hybrid form: ValueError."""
         torch = _torch()
-        if ranker is not None or isinstance(rerank, BoostRanker):
-            raise ValueError("boosted search (ranker) cannot be combined with hybrid_search")
+        if ranker is not None or isinstance(rerank, (BoostRanker, DecayRanker)):
+            raise ValueError("boosted / decayed search (ranker) cannot be combined with hybrid_search")
         reqs = list(reqs)
         if not 1 <= len(reqs) <= MAX_ARMS or not all(isinstance(r, AnnSearchRequest) for r in reqs):
             raise ValueError(f"hybrid_search takes 1..{MAX_ARMS} AnnSearchRequest objects")
@@ -1458,7 +1536,7 @@ class CorpusStore:
         is exhausted).  The bound is a row number: an insert, delete, upsert or drop between two
         next() calls makes the next one raise RuntimeError.  A boost ranker is not paged: ValueError."""
         if ranker is not None:
-            raise ValueError("boosted search (ranker) cannot be combined with search_iterator")
+            raise ValueError("boosted / decayed search (ranker) cannot be combined with search_iterator")
         if isinstance(expr, (list, tuple)):
             raise ValueError("search_iterator takes one expr string, not a list (per-query filters)")
         if anns_field == TOKEN_FIELD:
