@@ -713,6 +713,71 @@ typedef struct rf_dynamic_leaf {
 int rf_dynamic_match(const rf_dynamic_leaf* leaves_host, int n_leaves, const uint32_t* code_sets_dev,
                      const int64_t* int_sets_dev, const double* f64_sets_dev, int64_t n_rows,
                      uint32_t* bitmaps_dev, void* stream);
+/* ---- ARRAY fields: the leaves of `expr` over a collection's multi-valued columns ---------------------
+ * pymilvus' DataType.ARRAY: a row holds 0 .. max_capacity (<= 4096) elements of one scalar type
+ * (rag_fin_amd/schema.py).  The device mirror of one ARRAY field is CSR:
+ *   offsets_dev  int64 [n_rows + 1], 8-byte aligned, offsets[0] == 0, non-decreasing: row r holds the
+ *                elements [offsets[r], offsets[r + 1])
+ *   values_dev   the elements back to back: int32 codes into the field's append-only dictionary (VARCHAR,
+ *                BOOL), int64 (INT64) or fp64 (DOUBLE), aligned to the element
+ * A leaf is evaluated into a row bitmap that an RF_FOP_BITMAP leaf of rf_filter_eval_bitmaps reads -- the
+ * door rf_text_match, rf_column_match and rf_dynamic_match use.  Leaf kinds:
+ *   RF_ALEAF_LENGTH  ilo <= offsets[r + 1] - offsets[r] <= ihi, both ends inclusive (ilo > ihi passes
+ *                    nothing); values_dev is not read
+ *   RF_ALEAF_ELEM    the row holds more than `index` elements and element `index` passes the scalar test
+ *                    `elem` names: RF_CLEAF_CODESET (int32 codes), RF_CLEAF_I64_RANGE, RF_CLEAF_I64_SET
+ *                    (int64) or RF_CLEAF_F64_RANGE (fp64), with off / len / ilo / ihi / flags / flo / fhi
+ *                    as in rf_column_leaf; a shorter row fails
+ *   RF_ALEAF_MATCH   `elem` names the element type (RF_AELEM_CODE / I64 / F64); the needles are the slice
+ *                    [off, off + len) of value_sets_dev (CODE, I64: int64, a code widened) or of
+ *                    f64_sets_dev (F64), sorted ascending and distinct, len <= RF_COLUMN_MAX_SET; the row
+ *                    passes iff at least `need` DISTINCT needles occur among its elements (int64 equality,
+ *                    IEEE == for fp64: a NaN element matches nothing, -0.0 matches 0.0).  need == 1: ANY /
+ *                    CONTAINS; need == len <= 64: ALL (need == len == 0 passes every row)
+ * LENGTH and ELEM: a lane owns one row (two offset loads, at most one element load).  MATCH is
+ * wave-cooperative: a wave owns 64 consecutive rows, stages their 65 offsets in LDS, strides over the
+ * rows' one contiguous element span with coalesced loads, looks each element up in the needle slice by
+ * binary search and, on a hit only, locates the owning row (the largest r with offsets[r] <= e) by binary
+ * search over the staged offsets and ORs the needle's bit into the row's 64-bit LDS slot; lane r then
+ * tests popcount(slot[r]) >= need.  The OR is commutative and idempotent, so the slot does not depend on
+ * the order the hits arrive in.
+ * Otherwise the contract of rf_column_match: leaves_host is HOST memory, n_leaves in
+ * 1..RF_ARRAY_MAX_LEAVES (they travel in the launch arguments); leaf l writes EVERY word of
+ * bitmaps_dev[l * nwords .. (l + 1) * nwords), nwords = ceil(n_rows / 32), bits past n_rows zero; one
+ * launch, grid (row chunks, leaves), a wave's 64 predicates become two words by ballot; stream-ordered, no
+ * host sync, no allocation, no global atomics; integers and IEEE comparisons only: the same bits on every
+ * run.
+ * RF_ERR_INVALID before any device call: a NULL leaves_host / bitmaps_dev, n_leaves or n_rows out of range,
+ * an unknown kind or elem, unknown flags, a negative off / len / index, need outside {1, len} or above 64, a
+ * set of more than RF_COLUMN_MAX_SET values (1 << 26 code-set words), a leaf that needs code_sets_dev /
+ * value_sets_dev / f64_sets_dev when that is NULL, a misaligned set or bitmap pointer, offsets_dev NULL or
+ * not 8-byte aligned, values_dev NULL (any kind but LENGTH) or not aligned to its element.  A column whose
+ * rows are all empty may pass any aligned non-NULL values_dev: none of it is read.  The offsets are trusted
+ * (the store derives them from the rows' lengths); an element or a search position outside a leaf's slice is
+ * never dereferenced.  n_rows == 0 writes nothing and returns RF_OK.
+ * New in this build; the reference's collection has no ARRAY field. */
+#define RF_ARRAY_MAX_LEAVES 16
+#define RF_ALEAF_LENGTH 1
+#define RF_ALEAF_ELEM 2
+#define RF_ALEAF_MATCH 3
+#define RF_AELEM_CODE 1
+#define RF_AELEM_I64 2
+#define RF_AELEM_F64 3
+typedef struct rf_array_leaf {
+  int32_t kind;                /* RF_ALEAF_* */
+  int32_t elem;                /* ELEM: RF_CLEAF_* (the scalar test); MATCH: RF_AELEM_* (the element type) */
+  int32_t flags;               /* ELEM with RF_CLEAF_F64_RANGE: RF_FRANGE_* bits; else 0 */
+  int32_t need;                /* MATCH: 1 or len */
+  const int64_t* offsets_dev;  /* [n_rows + 1] */
+  const void* values_dev;      /* int32 codes | int64 | fp64; LENGTH does not read it */
+  int64_t index;               /* ELEM: the element's position in its row, >= 0 */
+  int64_t off, len;            /* ELEM: as rf_column_leaf; MATCH: the needle slice */
+  int64_t ilo, ihi;            /* LENGTH, ELEM with RF_CLEAF_I64_RANGE: bounds, inclusive */
+  double flo, fhi;             /* ELEM with RF_CLEAF_F64_RANGE: bounds */
+} rf_array_leaf;
+int rf_array_match(const rf_array_leaf* leaves_host, int n_leaves, const uint32_t* code_sets_dev,
+                   const int64_t* value_sets_dev, const double* f64_sets_dev, int64_t n_rows,
+                   uint32_t* bitmaps_dev, void* stream);
 /* ---- lexical index maintenance: the postings after an append or a delete, without the old texts -------
  * A write changes N, avgdl and df, and through them every BM25 impact -- but with the term frequencies
  * kept beside the postings (post_tf uint32 [nnz]) everything is re-derivable: the arrays after a write

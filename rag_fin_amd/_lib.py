@@ -39,6 +39,11 @@ RF_CLEAF_CODESET, RF_CLEAF_I64_RANGE, RF_CLEAF_I64_SET, RF_CLEAF_F64_RANGE = 1, 
 RF_DYNAMIC_MAX_LEAVES = 16   # dynamic leaves one rf_dynamic_match call holds
 RF_DTAG_ABSENT, RF_DTAG_BOOL, RF_DTAG_INT, RF_DTAG_DOUBLE, RF_DTAG_STRING = range(5)
 RF_DLEAF_TAGS, RF_DLEAF_STR_CODESET, RF_DLEAF_BOOL, RF_DLEAF_NUM_RANGE, RF_DLEAF_NUM_SET = 1, 2, 3, 4, 5
+# ARRAY fields (include/ragfin.h, "ARRAY fields")
+RF_ARRAY_MAX_LEAVES = 16     # array leaves one rf_array_match call holds
+RF_ALEAF_LENGTH, RF_ALEAF_ELEM, RF_ALEAF_MATCH = 1, 2, 3
+RF_AELEM_CODE, RF_AELEM_I64, RF_AELEM_F64 = 1, 2, 3
+RF_ARRAY_MAX_ALL = 64        # needles of one ARRAY_CONTAINS_ALL: one bit each of a row's 64-bit slot
 # lexical index maintenance (include/ragfin.h, "lexical index maintenance")
 RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
 # lexical index build (include/ragfin.h, "lexical index build")
@@ -87,6 +92,14 @@ class DynamicLeaf(Structure):
     _fields_ = [("kind", c_int32), ("flags", c_int32), ("tags_dev", c_void_p), ("payload_dev", c_void_p),
                 ("off", c_int64), ("len", c_int64), ("foff", c_int64), ("flen", c_int64),
                 ("ilo", c_int64), ("ihi", c_int64), ("flo", c_double), ("fhi", c_double)]
+
+
+class ArrayLeaf(Structure):
+    """rf_array_leaf: one leaf of a filter expression over an ARRAY field's CSR mirror."""
+    _fields_ = [("kind", c_int32), ("elem", c_int32), ("flags", c_int32), ("need", c_int32),
+                ("offsets_dev", c_void_p), ("values_dev", c_void_p), ("index", c_int64),
+                ("off", c_int64), ("len", c_int64), ("ilo", c_int64), ("ihi", c_int64),
+                ("flo", c_double), ("fhi", c_double)]
 
 
 class Postings(Structure):
@@ -228,6 +241,7 @@ SIGNATURES = {
                               c_void_p]),
     "rf_column_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_dynamic_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rf_array_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_sparse_impacts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,
                                   c_double, c_double, c_void_p, c_void_p]),
     "rf_sparse_append_workspace_bytes": (c_size_t, [c_int64, c_int64]),

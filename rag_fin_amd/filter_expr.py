@@ -14,6 +14,10 @@ Grammar (keywords case-insensitive; precedence not > and > or)::
              | "exists" FIELD                       (dynamic fields only; there FIELD is also NAME | $meta[STRING])
              | FIELD ["not"] "in" "[" [literal ("," literal)*] "]" | FIELD "like" STRING
              | FUNC "(" "text" "," STRING ["," (NAME "=" NUM | NUM)] ")"
+             | "ARRAY_CONTAINS" "(" F "," literal ")"                  (F: a declared ARRAY field; function names
+             | ("ARRAY_CONTAINS_ALL" | "ARRAY_CONTAINS_ANY") "(" F "," "[" [literal ("," literal)*] "]" ")"
+             | "ARRAY_LENGTH" "(" F ")" CMP INT | INT CMP "ARRAY_LENGTH" "(" F ")" [CMP INT]     case-insensitive)
+             | F "[" INT "]" wherever a scalar FIELD of F's element type stands
     FUNC    := "TEXT_MATCH" | "PHRASE_MATCH"
 
 Fields and what they accept:
@@ -64,6 +68,29 @@ mask: `exists`, and the class guard of a numeric `!=` / `not in`, which is TAGS(
 int rows and an fp64 interval for the float rows, both derived exactly from the one literal: `int_interval` and
 `f64_interval`) and NUM_SET (a sorted int64 set and a sorted fp64 set).
 
+ARRAY fields (a FieldSchema of DataType.ARRAY in `schema`: a row holds a list of 0 .. max_capacity elements of one
+of the four scalar types).  The semantics below are THIS PROJECT'S definition, written once as the `eval` of
+ArrContains / ArrLength / ArrElem and, for the compiled leaves, as `array_leaf_reference`:
+  * ARRAY_CONTAINS(F, v): some element equals v -- strings by equality, int64 exactly, booleans by equality,
+    doubles by IEEE == (a NaN element is never contained, -0.0 contains 0.0).  Literals are typed by the element
+    type as a scalar field's are (an INT64 array takes 2.0 for 2; 2.5 equals no element);
+  * ARRAY_CONTAINS_ALL(F, [..]): every distinct listed value occurs in the row (duplicates in the row or the list
+    do not matter); ARRAY_CONTAINS_ANY(F, [..]): at least one does.  ALL(F, []) passes every row, ANY(F, []) none
+    (they compile to TRUE / FALSE).  ALL takes at most 64 distinct values, ANY at most RF_COLUMN_MAX_SET.  A value
+    no element can equal (a string the field's dictionary does not hold, 2.5 for an INT64 array) is dropped from
+    ANY and makes ALL FALSE;
+  * ARRAY_LENGTH(F) CMP n compares the row's element count with the integer n;
+  * F[i] (i an integer literal, 0 <= i < 4096) takes every leaf a scalar field of the element type takes (CMP,
+    chains, in / not in, like).  A row with len <= i fails EVERY leaf on F[i], `!=` and `not in` included -- the
+    rule a dynamic key follows for a row that lacks it: F[i] != v is LENGTH(F) > i AND NOT (F[i] == v);
+  * `not (...)` is plain negation: `not (F[i] == v)` passes the short rows.
+A bare F (F == .., F in .., F like ..), a negative or non-integer index and a literal of the wrong type raise
+ValueError naming the token.  An array leaf compiles into entries of `Program.array_leaves`, which rf_array_match
+evaluates over the field's CSR mirror (offsets int64 [n + 1], values: int32 dictionary codes | int64 | fp64) into
+row bitmaps: LENGTH (an inclusive interval of the count, through `int_interval`), ELEM (element i under the scalar
+leaf a column leaf would be) and MATCH (sorted distinct needles and `need`: 1 for ANY / CONTAINS, their number for
+ALL).
+
 Compilation.  A VARCHAR leaf is evaluated once against the column's dictionary (every distinct
 string, in first-seen order = its code) and becomes a set of codes, so a literal that is not in
 the dictionary matches nothing; numeric leaves become interval tests; id leaves become a sorted
@@ -96,6 +123,11 @@ NO_LEXICAL_INDEX = ("TEXT_MATCH / PHRASE_MATCH need the lexical index over the t
                     "create_index('sparse', {'index_type': 'SPARSE_INVERTED_INDEX', 'metric_type': 'BM25'}) first")
 DYNAMIC_KEYWORDS = ("and", "or", "not", "in", "like", "true", "false", "exists")   # never a bare dynamic key
 _FLIP = {"<": ">", "<=": ">=", ">": "<", ">=": "<=", "==": "==", "!=": "!="}
+
+
+def _scalar_type(f):
+    """The DataType that types a field's literals: its own, or an ARRAY field's element type."""
+    return f.element_type if f.dtype == DataType.ARRAY else f.dtype
 
 
 def is_empty(expr) -> bool:
@@ -312,6 +344,53 @@ class Exists(Node):
 DYNAMIC_NODES = (DynCmp, DynIn, DynLike, Exists)
 
 
+# -- ARRAY fields: the semantics of a leaf over a declared ARRAY field (module docstring), in pure Python --
+def _contains(arr, v) -> bool:
+    return any(x == v for x in arr)   # (IEEE == for floats: NaN is never contained, -0.0 contains 0.0)
+
+
+@dataclass
+class ArrContains(Node):
+    """ARRAY_CONTAINS(field, v) = ("any", [v]); ARRAY_CONTAINS_ANY / ARRAY_CONTAINS_ALL(field, values)."""
+    field: str
+    values: list
+    mode: str = "any"   # "any" | "all"
+
+    def eval(self, row):
+        arr = row[self.field]
+        hits = (_contains(arr, v) for v in self.values)
+        return all(hits) if self.mode == "all" else any(hits)
+
+
+@dataclass
+class ArrLength(Node):
+    """ARRAY_LENGTH(field) op value."""
+    field: str
+    op: str
+    value: int
+
+    def eval(self, row):
+        return _compare(len(row[self.field]), self.op, self.value)
+
+
+@dataclass
+class ArrElem(Node):
+    """field[index] under the scalar leaf `inner` (a Cmp, In or Like over the field's name): a row with
+    len <= index fails it, `!=` and `not in` included."""
+    field: str
+    index: int
+    inner: Node
+
+    def eval(self, row):
+        arr = row[self.field]
+        return len(arr) > self.index and self.inner.eval({self.field: arr[self.index]})
+
+
+ARRAY_NODES = (ArrContains, ArrLength, ArrElem)
+ARRAY_FUNCS = ("array_contains", "array_contains_all", "array_contains_any", "array_length")
+MAX_ARRAY_INDEX = 4096   # F[i]: i below Milvus' capacity limit
+
+
 @dataclass
 class And(Node):
     a: Node
@@ -372,7 +451,10 @@ class _Parser:
         self.i = 0
         self.analyzer = analyzer
         self.dynamic = dynamic   # a name that is no field of the collection is a key of $meta
-        self.extra = {f.name: f.dtype for f in schema or ()}   # the collection's own fields (schema.py)
+        # the collection's own fields (schema.py); an ARRAY field stands with its element type, which types the
+        # literals of its leaves, and its name is in `arrays`
+        self.extra = {f.name: _scalar_type(f) for f in schema or ()}
+        self.arrays = {f.name for f in schema or () if f.dtype == DataType.ARRAY}
 
     def peek(self, k: int = 0) -> Tok:
         return self.toks[min(self.i + k, len(self.toks) - 1)]
@@ -449,6 +531,9 @@ class _Parser:
         t = self.peek()
         if t.kind != "meta":
             name, ft = self.field()
+            if name in self.arrays:
+                raise _err(f"{name!r} is an ARRAY field: it is read through ARRAY_CONTAINS / ARRAY_CONTAINS_ALL / "
+                           f"ARRAY_CONTAINS_ANY / ARRAY_LENGTH or an index {name}[i], not compared whole", ft)
             return name, ft, not self.known(name)
         self.take()
         if not self.op("["):
@@ -502,8 +587,13 @@ class _Parser:
             o1 = self.cmp_op()
             if o1 is None:
                 raise _err("expected a comparison operator", self.peek())
-            name, ft, dyn = self.operand()
-            leaf = self._dynamic_cmp if dyn else self._leaf_cmp
+            arr = self.array_operand()
+            if arr is not None:
+                name, ft, dyn = arr[1], arr[-1], False
+                leaf = lambda *a: self._array_cmp(arr, *a[2:])   # noqa: E731
+            else:
+                name, ft, dyn = self.operand()
+                leaf = self._dynamic_cmp if dyn else self._leaf_cmp
             left = leaf(name, ft, _FLIP[o1.value], lit, lt, o1)
             o2 = self.cmp_op()
             if o2 is None:
@@ -512,6 +602,17 @@ class _Parser:
             return And(left, leaf(name, ft, o2.value, lit2, lt2, o2))
         if t.kind == "name" and t.value.lower() in TEXT_FUNCS and self.op("(", 1):
             return self.text_func()
+        if t.kind == "name" and t.value.lower() in ARRAY_FUNCS[:3] and self.op("(", 1) and self._array_name(2):
+            return self.array_func()
+        arr = self.array_operand()
+        if arr is not None:
+            if arr[0] == "elem":   # F[i] stands where a scalar field of the element type does
+                return ArrElem(arr[1], arr[2], self._after_operand(arr[1], arr[-1], False))
+            o = self.cmp_op()
+            if o is None:
+                raise _err("expected a comparison operator after ARRAY_LENGTH(...)", self.peek())
+            lit, lt = self.literal()
+            return self._array_cmp(arr, o.value, lit, lt, o)
         if self.dynamic and self.kw("exists") and not self.known("exists"):
             et = self.take()
             if self.peek().kind not in ("name", "meta"):
@@ -520,7 +621,10 @@ class _Parser:
             if not dyn:
                 raise _err(f"'exists' takes a dynamic key, {name!r} is a field of the collection", ft)
             return Exists(name)
-        name, ft, dyn = self.operand()
+        return self._after_operand(*self.operand())
+
+    def _after_operand(self, name, ft, dyn) -> Node:
+        """CMP literal | [not] in [...] | like STRING behind a scalar operand."""
         o = self.cmp_op()
         if o is not None:
             lit, lt = self.literal()
@@ -550,6 +654,62 @@ class _Parser:
         if nt.kind == "op" and nt.value == "[":
             raise _err("expected a comparison, 'in' or 'like' (ARRAY and JSON fields are not supported)", nt)
         raise _err("expected a comparison, 'in' or 'like'", nt)
+
+    # -- ARRAY fields ---------------------------------------------------------------------------
+    def _array_name(self, k: int = 0) -> bool:
+        t = self.peek(k)
+        return t.kind == "name" and t.value in self.arrays
+
+    def array_operand(self):
+        """ARRAY_LENGTH ( F ) -> ("length", F, token) | F [ INT ] -> ("elem", F, index, token) over a declared
+        ARRAY field F, consumed; None (and nothing consumed) when neither stands here."""
+        t = self.peek()
+        if t.kind == "name" and t.value.lower() == "array_length" and self.op("(", 1) and self._array_name(2):
+            self.take()
+            self.take()
+            name = self.take().value
+            if not self.op(")"):
+                raise _err("expected ')'", self.peek())
+            self.take()
+            return "length", name, t
+        if self._array_name() and self.op("[", 1):
+            self.take()
+            self.take()
+            it = self.take()
+            if it.kind != "num" or not isinstance(it.value, int) or it.value >= MAX_ARRAY_INDEX:
+                raise _err(f"an array index is a non-negative integer literal below {MAX_ARRAY_INDEX}", it)
+            if not self.op("]"):
+                raise _err("expected ']'", self.peek())
+            self.take()
+            return "elem", t.value, it.value, t
+        return None
+
+    def _array_cmp(self, arr, op, lit, lt, ot) -> Node:
+        """The comparison leaf of an array operand (array_operand) with a literal."""
+        if arr[0] == "elem":
+            return ArrElem(arr[1], arr[2], self._leaf_cmp(arr[1], arr[-1], op, lit, lt, ot))
+        if isinstance(lit, bool) or not isinstance(lit, int):
+            raise _err("ARRAY_LENGTH is compared with an integer", lt)
+        return ArrLength(arr[1], op, lit)
+
+    def array_func(self) -> Node:
+        """ARRAY_CONTAINS ( F , literal ) | ARRAY_CONTAINS_ALL / _ANY ( F , [ literal, ... ] )."""
+        ft = self.take()
+        func = ft.value.lower()
+        self.take()   # "("
+        name = self.take().value
+        if not self.op(","):
+            raise _err("expected ','", self.peek())
+        kt = self.take()
+        if func == "array_contains":
+            lit, lt = self.literal()
+            node = ArrContains(name, [self._check_type(name, lit, lt)], "any")
+        else:
+            node = ArrContains(name, self._list(name, kt), "all" if func == "array_contains_all" else "any")
+        if not self.op(")"):
+            raise _err("expected ')'", self.peek())
+        self.take()
+        return node
 
     def text_func(self) -> Node:
         """The keyword leaf of the grammar: FUNC ( text , STRING [, NAME = NUM | , NUM] )."""
@@ -687,6 +847,15 @@ def fields_of(node: Node) -> set:
     return set() if isinstance(node, DYNAMIC_NODES) else {node.field}
 
 
+def array_fields_of(node: Node) -> set:
+    """The names of the ARRAY fields a tree's leaves read."""
+    if isinstance(node, (And, Or)):
+        return array_fields_of(node.a) | array_fields_of(node.b)
+    if isinstance(node, Not):
+        return array_fields_of(node.a)
+    return {node.field} if isinstance(node, ARRAY_NODES) else set()
+
+
 def dynamic_keys_of(node: Node) -> set:
     """The dynamic keys a tree's leaves read."""
     if isinstance(node, (And, Or)):
@@ -714,13 +883,20 @@ class Program:
     ("tags", key, tag mask) | ("codeset", key, code-set words) | ("bool", key, 2-bit value set) |
     ("nrange", key, ilo, ihi, RF_FRANGE_* flags, flo, fhi) | ("nset", key, sorted int64 values, sorted fp64
     values).  The RF_FOP_BITMAP op of dynamic leaf d carries d in `off` and DYNAMIC_LEAF in `column`; their
-    bitmaps (column_words words each) follow the column leaves'."""
+    bitmaps (column_words words each) follow the column leaves'.
+    array_leaves: the leaves over ARRAY fields, the input of rf_array_match:
+    ("length", field, lo, hi) -- inclusive bounds of the row's element count |
+    ("elem", field, index, scalar leaf) -- scalar leaf: an entry as in column_leaves, tested on element `index` |
+    ("match", field, "code" | "i64" | "f64", sorted distinct needles, need) -- need 1 (ANY / CONTAINS) or
+    len(needles) <= 64 (ALL).  The RF_FOP_BITMAP op of array leaf a carries a in `off` and ARRAY_LEAF in
+    `column`; their bitmaps (column_words words each) follow the dynamic leaves'."""
     ops: list = field(default_factory=list)
     code_sets: list = field(default_factory=list)
     row_lists: list = field(default_factory=list)
     text_leaves: list = field(default_factory=list)
     column_leaves: list = field(default_factory=list)
     dynamic_leaves: list = field(default_factory=list)
+    array_leaves: list = field(default_factory=list)
 
     def resolved_ops(self, words_per_leaf: int = 0, column_base: int = 0, column_words: int = 0) -> list:
         """The op tuples as the device takes them: every RF_FOP_BITMAP leaf with its word range."""
@@ -730,6 +906,9 @@ class Program:
                 col, off, ln = 0, column_base + off * column_words, column_words
             elif op == _lib.RF_FOP_BITMAP and col == DYNAMIC_LEAF:
                 col, off, ln = 0, column_base + (len(self.column_leaves) + off) * column_words, column_words
+            elif op == _lib.RF_FOP_BITMAP and col == ARRAY_LEAF:
+                behind = len(self.column_leaves) + len(self.dynamic_leaves)
+                col, off, ln = 0, column_base + (behind + off) * column_words, column_words
             elif op == _lib.RF_FOP_BITMAP:
                 off, ln = off * words_per_leaf, words_per_leaf
             out.append((op, col, off, ln, flags, lo, hi))
@@ -753,6 +932,8 @@ class Program:
 
 COLUMN_LEAF = 1   # `column` of an RF_FOP_BITMAP op in Program.ops: the bitmap of a column leaf, not of a keyword leaf
 DYNAMIC_LEAF = 2  # ... the bitmap of a dynamic leaf
+ARRAY_LEAF = 3    # ... the bitmap of an array leaf
+MAX_ALL = _lib.RF_ARRAY_MAX_ALL   # distinct values of one ARRAY_CONTAINS_ALL
 MAX_INT_SET = _lib.RF_COLUMN_MAX_SET
 NUMBER_TAGS = 1 << _lib.RF_DTAG_INT | 1 << _lib.RF_DTAG_DOUBLE
 HELD_TAGS = 1 << _lib.RF_DTAG_BOOL | NUMBER_TAGS | 1 << _lib.RF_DTAG_STRING   # every tag but ABSENT
@@ -835,7 +1016,9 @@ class _Compiler:
         self.dicts = dicts
         self.pk_row = pk_row
         self.term_id = term_id
-        self.extra = {f.name: f.dtype for f in schema or ()}
+        self.extra = {f.name: _scalar_type(f) for f in schema or ()}
+        self.arrays = {f.name for f in schema or () if f.dtype == DataType.ARRAY}
+        self._elem = None   # (field, index) while the scalar leaf under an ArrElem is compiled
         self.extra_dicts = extra_dicts or {}
         self.p = Program()
 
@@ -854,6 +1037,8 @@ class _Compiler:
             self.text(n)
         elif isinstance(n, DYNAMIC_NODES):
             self.dynamic_node(n)
+        elif isinstance(n, ARRAY_NODES):
+            self.array_node(n)
         elif n.field in self.extra:
             self.column(n, self.extra[n.field])
         elif n.field in VARCHAR_FIELDS:
@@ -886,6 +1071,9 @@ class _Compiler:
 
     # -- leaves over the collection's own fields: one RF_FOP_BITMAP op + one entry of column_leaves each --
     def column_leaf(self, *leaf) -> None:
+        if self._elem is not None:   # the scalar leaf under F[i]: an array leaf that tests element i with it
+            self.array_leaf("elem", self._elem[0], self._elem[1], leaf)
+            return
         self.leaf(_lib.RF_FOP_BITMAP, COLUMN_LEAF, len(self.p.column_leaves))
         self.p.column_leaves.append(leaf)
 
@@ -942,6 +1130,75 @@ class _Compiler:
         lo, hi, flags = {"==": (v, v, L | H), "<": (-inf, v, L), "<=": (-inf, v, L | H),
                          ">": (v, inf, H), ">=": (v, inf, L | H)}[op]
         self.column_leaf("frange", name, flags, lo, hi)
+
+    # -- leaves over ARRAY fields: RF_FOP_BITMAP ops + entries of array_leaves (module docstring) --
+    def array_leaf(self, *leaf) -> None:
+        self.leaf(_lib.RF_FOP_BITMAP, ARRAY_LEAF, len(self.p.array_leaves))
+        self.p.array_leaves.append(leaf)
+
+    def array_length(self, name: str, op: str, v: int) -> None:
+        iv = int_interval(op, v)
+        lo, hi = (max(iv[0], 0), iv[1]) if iv is not None else (1, 0)   # (a length is never negative)
+        if lo > hi:
+            self.leaf(_lib.RF_FOP_FALSE)
+        else:
+            self.array_leaf("length", name, lo, hi)
+
+    def array_node(self, n: Node) -> None:
+        t = self.extra[n.field]   # the element type
+        if isinstance(n, ArrLength):
+            self.array_length(n.field, "==" if n.op == "!=" else n.op, n.value)
+            if n.op == "!=":
+                self.leaf(_lib.RF_FOP_NOT)
+            return
+        if isinstance(n, ArrElem):
+            # a row with len <= index fails every leaf.  The leaf of a positive test already says so; the NOT
+            # that column() puts behind a numeric `!=` / `not in` would pass the short rows, so those become
+            # LENGTH(F) > index AND NOT (F[index] == v).  (VARCHAR / BOOL: the code set holds the negation.)
+            inner = n.inner
+            guard = t in (DataType.INT64, DataType.DOUBLE) and \
+                ((isinstance(inner, Cmp) and inner.op == "!=") or (isinstance(inner, In) and inner.negate))
+            if guard:
+                self.array_length(n.field, ">", n.index)
+            self._elem = (n.field, n.index)
+            try:
+                self.column(inner, t)
+            finally:
+                self._elem = None
+            if guard:
+                self.leaf(_lib.RF_FOP_AND)
+            return
+        self.array_contains(n, t)
+
+    def array_contains(self, n: "ArrContains", t) -> None:
+        every = n.mode == "all"
+        what = "ARRAY_CONTAINS_ALL" if every else "ARRAY_CONTAINS_ANY"
+        if every and len(set(n.values)) > MAX_ALL:   # (before anything is dropped: the text's own count)
+            raise ValueError(f"filter expression: {what}({n.field}, [...]) holds {len(set(n.values))} distinct values, "
+                             f"at most {MAX_ALL} are taken")
+        if not n.values:   # ALL of nothing holds everywhere, ANY of nothing nowhere
+            self.leaf(_lib.RF_FOP_TRUE if every else _lib.RF_FOP_FALSE)
+            return
+        # the needles as the device compares them; a value no element can equal is None
+        if t in (DataType.VARCHAR, DataType.BOOL):
+            code = {v: c for c, v in enumerate(self.extra_dicts.get(n.field, ()))}   # (first-seen order = code)
+            kind, needles = "code", [code.get(v) for v in n.values]
+        elif t == DataType.INT64:   # (2.5 equals no integer, 1e30 no int64)
+            kind, needles = "i64", [int(v) if not (isinstance(v, float) and math.isinf(v)) and v == math.floor(v)
+                                    and INT64_MIN <= v <= INT64_MAX else None for v in n.values]
+        else:   # DOUBLE: IEEE ==, so NaN equals nothing and -0.0 is the needle 0.0
+            kind, needles = "f64", [None if v != v else v + 0.0 for v in n.values]
+        if every and any(v is None for v in needles):
+            self.leaf(_lib.RF_FOP_FALSE)
+            return
+        needles = sorted({v for v in needles if v is not None})
+        if len(needles) > MAX_INT_SET:
+            raise ValueError(f"filter expression: {what}({n.field}, [...]) holds {len(needles)} distinct values, at most "
+                             f"{MAX_INT_SET} are taken")
+        if not needles:
+            self.leaf(_lib.RF_FOP_FALSE)
+            return
+        self.array_leaf("match", n.field, kind, needles, len(needles) if every else 1)
 
     # -- leaves over dynamic keys: RF_FOP_BITMAP ops + entries of dynamic_leaves (module docstring) --
     def dynamic_leaf(self, *leaf) -> None:
@@ -1133,6 +1390,88 @@ def column_leaf_reference(leaf, column: np.ndarray) -> np.ndarray:
         a = column >= lo if flags & _lib.RF_FRANGE_LO_INCL else column > lo
         b = column <= hi if flags & _lib.RF_FRANGE_HI_INCL else column < hi
     return a & b
+
+
+def encode_array(rows, np_dtype, code: dict | None = None, values_of: list | None = None):
+    """The CSR of an ARRAY column's rows (lists): (lengths int64 [n], values np_dtype [sum of lengths]).  With
+    `code` (value -> code) the elements are dictionary-coded int32: a new value is appended to `values_of` and
+    entered into `code` (first-seen order, as a scalar VARCHAR / BOOL column)."""
+    lens = np.fromiter((len(r) for r in rows), dtype=np.int64, count=len(rows))
+    flat = [x for r in rows for x in r]
+    if code is None:
+        return lens, np.asarray(flat, dtype=np_dtype).reshape(-1)
+    enc = np.empty(len(flat), dtype=np.int32)
+    for j, v in enumerate(flat):
+        c = code.get(v)
+        if c is None:
+            c = code[v] = len(values_of)
+            values_of.append(v)
+        enc[j] = c
+    return lens, enc
+
+
+_AELEM = {"code": _lib.RF_AELEM_CODE, "i64": _lib.RF_AELEM_I64, "f64": _lib.RF_AELEM_F64}
+
+
+def array_leaf_arrays(p: Program, column_ptr: dict, leaves=None):
+    """(rf_array_leaf array, code-set words uint32, value sets int64, fp64 sets) of p.array_leaves (or of
+    `leaves`).  column_ptr: field -> (the device address of its offsets, of its values)."""
+    leaves = p.array_leaves if leaves is None else leaves
+    arr = (_lib.ArrayLeaf * len(leaves))()
+    words: list = []
+    values: list = []
+    floats: list = []
+    for i, leaf in enumerate(leaves):
+        kind, name = leaf[0], leaf[1]
+        arr[i].offsets_dev, arr[i].values_dev = column_ptr[name]
+        if kind == "length":
+            arr[i].kind, arr[i].ilo, arr[i].ihi = _lib.RF_ALEAF_LENGTH, leaf[2], leaf[3]
+        elif kind == "elem":
+            arr[i].kind, arr[i].index = _lib.RF_ALEAF_ELEM, leaf[2]
+            sub = leaf[3]
+            if sub[0] == "codeset":
+                arr[i].elem, arr[i].off, arr[i].len = _lib.RF_CLEAF_CODESET, len(words), len(sub[2])
+                words.extend(sub[2])
+            elif sub[0] == "irange":
+                arr[i].elem, arr[i].ilo, arr[i].ihi = _lib.RF_CLEAF_I64_RANGE, sub[2], sub[3]
+            elif sub[0] == "iset":
+                arr[i].elem, arr[i].off, arr[i].len = _lib.RF_CLEAF_I64_SET, len(values), len(sub[2])
+                values.extend(sub[2])
+            else:
+                arr[i].elem, arr[i].flags, arr[i].flo, arr[i].fhi = _lib.RF_CLEAF_F64_RANGE, sub[2], sub[3], sub[4]
+        else:
+            arr[i].kind, arr[i].elem, arr[i].need = _lib.RF_ALEAF_MATCH, _AELEM[leaf[2]], leaf[4]
+            sets = floats if leaf[2] == "f64" else values
+            arr[i].off, arr[i].len = len(sets), len(leaf[3])
+            sets.extend(leaf[3])
+    return (arr, np.asarray(words, dtype=np.uint32).reshape(-1), np.asarray(values, dtype=np.int64).reshape(-1),
+            np.asarray(floats, dtype=np.float64).reshape(-1))
+
+
+def array_leaf_reference(leaf, offsets: np.ndarray, values: np.ndarray) -> np.ndarray:
+    """What rf_array_match computes for one entry of Program.array_leaves, in numpy: bool [n].  offsets int64
+    [n + 1], values: the field's CSR mirror (int32 codes | int64 | fp64)."""
+    kind = leaf[0]
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n = offsets.size - 1
+    lens = np.diff(offsets)
+    if kind == "length":
+        return (lens >= np.int64(leaf[2])) & (lens <= np.int64(leaf[3])) if leaf[2] <= leaf[3] else np.zeros(n, bool)
+    if kind == "elem":
+        out = np.zeros(n, bool)
+        has = lens > leaf[2]
+        out[has] = column_leaf_reference(leaf[3], values[offsets[:-1][has] + leaf[2]])
+        return out
+    needles = np.asarray(leaf[3], dtype=np.float64 if leaf[2] == "f64" else np.int64)
+    x = values.astype(needles.dtype, copy=False)
+    row = np.repeat(np.arange(n, dtype=np.int64), lens)
+    if needles.size == 0:
+        return np.full(n, leaf[4] <= 0)
+    pos = np.searchsorted(needles, x)   # (a NaN element sorts behind every needle)
+    hit = pos < needles.size
+    hit[hit] = needles[pos[hit]] == x[hit]
+    pairs = np.unique(row[hit] * np.int64(needles.size) + pos[hit])   # the distinct (row, needle) pairs
+    return np.bincount(pairs // np.int64(needles.size), minlength=n)[:n] >= leaf[4]
 
 
 def encode_dynamic(values, code: dict, strings: list) -> tuple[np.ndarray, np.ndarray]:

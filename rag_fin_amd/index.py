@@ -1508,6 +1508,37 @@ def dynamic_match(device, program: "filter_expr.Program", columns: dict, n_rows:
     return out
 
 
+def array_match(device, program: "filter_expr.Program", columns: dict, n_rows: int, out=None):
+    """rf_array_match of program.array_leaves, enqueued on the current stream; no host sync.
+    columns: ARRAY field -> (offsets int64 [n_rows + 1], values int32 codes | int64 | fp64) on the device.  -> the
+    row bitmaps, an int32 device tensor [A * ceil(n_rows / 32)] of uint32 bit patterns, leaf after leaf (`out`: a
+    contiguous int32 tensor of that size to write into).  One launch per RF_ARRAY_MAX_LEAVES leaves."""
+    torch = _torch()
+    lib = _lib.load_library()
+    A = len(program.array_leaves)
+    nwords = (n_rows + 31) // 32
+    # (a field whose rows are all empty has no element to point at: its offsets stand in, and none is read)
+    ptrs = {f: (o.data_ptr(), v.data_ptr() if v.numel() else o.data_ptr()) for f, (o, v) in columns.items()}
+    arr, words, values, floats = filter_expr.array_leaf_arrays(program, ptrs)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(A * nwords, dtype=torch.int32, device=device)
+        elif out.numel() != A * nwords or out.dtype != torch.int32 or not out.is_contiguous():
+            raise ValueError(f"array_match: out must be a contiguous int32 tensor of {A * nwords} words")
+        cs_d = torch.from_numpy(words.view(np.int32)).to(device) if words.size else None
+        vs_d = torch.from_numpy(values).to(device) if values.size else None
+        fs_d = torch.from_numpy(floats).to(device) if floats.size else None
+        step = _lib.RF_ARRAY_MAX_LEAVES
+        for a0 in range(0, A, step):
+            a1 = min(A, a0 + step)
+            part = (_lib.ArrayLeaf * (a1 - a0)).from_buffer(arr, a0 * ctypes.sizeof(_lib.ArrayLeaf))
+            _lib.check(lib.rf_array_match(part, a1 - a0, _ptr(cs_d), _ptr(vs_d), _ptr(fs_d), n_rows,
+                                          c_void_p(out.data_ptr() + 4 * a0 * nwords) if nwords else None,
+                                          _lib.current_stream_ptr()))
+    # (the sets may be freed now: the caching allocator reuses their memory in stream order)
+    return out
+
+
 def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None, column_base: int = 0):
     """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
     rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors
@@ -1516,13 +1547,15 @@ def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bi
     program has keyword leaves (rf_filter_eval_bitmaps).  With column leaves (program.column_leaves),
     bitmaps is the one flat int32 array that holds the keyword leaves' bitmaps (text_words_per_leaf(n_rows)
     words each) and, from word column_base, the column leaves' (column_match; ceil(n_rows / 32) words each) and
-    behind them the dynamic leaves' (program.dynamic_leaves; dynamic_match, the same width)."""
+    behind them the dynamic leaves' (program.dynamic_leaves; dynamic_match, the same width) and the array leaves'
+    (program.array_leaves; array_match, the same width)."""
     torch = _torch()
     lib = _lib.load_library()
     cs, rl = filter_expr.program_arrays(program)
-    if program.column_leaves or program.dynamic_leaves:
+    if program.column_leaves or program.dynamic_leaves or program.array_leaves:
         ops = program.ops_ctypes(text_words_per_leaf(n_rows), column_base, (n_rows + 31) // 32)
-        if column_base + (len(program.column_leaves) + len(program.dynamic_leaves)) * ((n_rows + 31) // 32) > 0x7FFFFFFF:
+        if column_base + (len(program.column_leaves) + len(program.dynamic_leaves) + len(program.array_leaves)) * \
+                ((n_rows + 31) // 32) > 0x7FFFFFFF:
             raise ValueError("filter expression: the leaves' bitmaps do not fit int32 word offsets")
     else:
         ops = program.ops_ctypes(0 if bitmaps is None else int(bitmaps.shape[1]))

@@ -41,7 +41,7 @@ from . import schema as schema_
 from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, boost_classes, column_match, dynamic_match,  # noqa: F401
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, array_match, boost_classes, column_match, dynamic_match,  # noqa: F401
                     decay_weights, eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
                     plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
 from .ranker import BoostRanker, DecayRanker, check_rankers, class_weights  # noqa: F401
@@ -240,6 +240,52 @@ class _ExtraColumn:
     def compact(self, k) -> None:
         """Keep rows k (ascending, an int64 device tensor) of a mirror synced to the whole collection."""
         self.data = self.data.index_select(0, k)
+        self.n = int(k.numel())
+
+
+class _ArrayColumn:
+    """The device mirror of one ARRAY field, CSR: offsets int64 [n + 1] (offsets[0] == 0) and the rows' elements
+    back to back -- int64 for INT64, fp64 for DOUBLE, int32 codes into an append-only dictionary (first-seen
+    order) for VARCHAR and BOOL.  Synced lazily and append-only from the host lists, like _ExtraColumn."""
+
+    def __init__(self, device, element_type):
+        torch = _torch()
+        self.device = device
+        self.coded = element_type in (DataType.VARCHAR, DataType.BOOL)
+        self.np_dtype = np.int32 if self.coded else (np.int64 if element_type == DataType.INT64 else np.float64)
+        self.dict: list = []
+        self._code: dict = {}
+        self.offsets = torch.zeros(1, dtype=torch.int64, device=device)
+        self.values = torch.empty(0, dtype=getattr(torch, np.dtype(self.np_dtype).name), device=device)
+        self.n = 0
+        self.nnz = 0   # elements mirrored: the last offset, kept on the host
+
+    def sync(self, rows: list, n: int) -> None:
+        torch = _torch()
+        if n < self.n:   # a shorter collection: re-encode from row 0 (the dictionary stays)
+            self.offsets, self.values = self.offsets[:1], self.values[:0]
+            self.n = self.nnz = 0
+        if n == self.n:
+            return
+        lens, enc = filter_expr.encode_array(rows[self.n:n], self.np_dtype, self._code if self.coded else None, self.dict)
+        ends = self.nnz + np.cumsum(lens)
+        self.offsets = torch.cat([self.offsets, torch.from_numpy(ends).to(self.device)])
+        self.values = torch.cat([self.values, torch.from_numpy(enc).to(self.device)])
+        self.n, self.nnz = n, self.nnz + int(enc.size)
+
+    def compact(self, k) -> None:
+        """Keep rows k (ascending, an int64 device tensor) of a mirror synced to the whole collection: the
+        surviving rows' elements are gathered in row order and the offsets rebuilt from their lengths."""
+        torch = _torch()
+        starts = self.offsets[:-1].index_select(0, k)
+        lens = self.offsets[1:].index_select(0, k) - starts
+        ends = torch.cumsum(lens, 0)
+        self.nnz = int(ends[-1]) if k.numel() else 0
+        # element j of the new values comes from old position start(row) + (j - new start(row))
+        src = torch.repeat_interleave(starts - (ends - lens), lens, output_size=self.nnz) + \
+            torch.arange(self.nnz, dtype=torch.int64, device=self.device)
+        self.values = self.values.index_select(0, src)
+        self.offsets = torch.cat([self.offsets[:1], ends])
         self.n = int(k.numel())
 
 
@@ -484,6 +530,7 @@ class CorpusStore:
     # whose __init__ does not call this one is a store without extra fields.
     schema: tuple = ()
     _xcols = None        # {(field, coded): _ExtraColumn}, built by the first filter / grouping that reads the field
+    _acols = None        # {ARRAY field: _ArrayColumn}, built by the first filter that reads the field
     # dynamic fields (pymilvus' enable_dynamic_field / $meta): {key: column of num_entities values, None where
     # the row lacks the key} for every key some row holds, and the mirrors of the keys an expression has read
     enable_dynamic_field = False
@@ -496,7 +543,11 @@ class CorpusStore:
         """fields: FieldSchema objects (rag_fin_amd.schema) of extra scalar fields next to the reference's
         seven: VARCHAR, INT64, DOUBLE or BOOL, at most 32.  They are inserted (add(extra=), the columns after
         primary_value of insert / upsert), filtered on in expr, grouped by, returned as output fields, and
-        saved and loaded like `period`.
+        saved and loaded like `period`.  A field may also be an ARRAY of one of those types
+        (FieldSchema("tags", DataType.ARRAY, element_type=DataType.VARCHAR, max_capacity=16)): a row holds a
+        list; expr reads it through ARRAY_CONTAINS / ARRAY_CONTAINS_ALL / ARRAY_CONTAINS_ANY / ARRAY_LENGTH and
+        an index tags[i] (filter_expr's docstring), evaluated on the GPU over a CSR mirror; it is
+        returned as an output field, saved and loaded, and cannot be grouped by or decayed over.
         enable_dynamic_field: rows may carry keys that no field declares (pymilvus' $meta; schema.py): a key of
         add(extra=) that is no declared field, or the dict of a trailing column of insert / upsert.  At most 64
         distinct keys; a value is a bool, an int64, a float, a str or None.  Such a key is filtered on in expr
@@ -516,6 +567,7 @@ class CorpusStore:
         self.columns: dict[str, list] = {f: [] for f in SCALAR_FIELDS + tuple(f.name for f in self.schema)}
         self._pk_row: dict[Any, int] = {}
         self._xcols = None
+        self._acols = None
         self._dcols = None                  # _DeviceColumns, built by the first filtered call
         self._filter_lock = threading.Lock()
         # search / query / save read; add / delete / upsert / drop write.  A search hands out row
@@ -554,6 +606,7 @@ class CorpusStore:
             self.dynamic = {}
             self._dcols = None
             self._xcols = None
+            self._acols = None
             self._dyncols = None
             for field in self._text_fields.values():
                 field.reset()
@@ -880,6 +933,13 @@ class CorpusStore:
                     for c in synced.values():
                         c.compact(k)
                 self._xcols = synced
+            if self._acols:
+                synced = {key: c for key, c in self._acols.items() if c.n == n_old}   # the others: as above
+                if synced:
+                    k = _torch().from_numpy(np.ascontiguousarray(keep, dtype=np.int64)).to(self.index.device)
+                    for c in synced.values():
+                        c.compact(k)
+                self._acols = synced
             if self._dyncols:
                 synced = {key: c for key, c in self._dyncols.items() if c.n == n_old and key in self.dynamic}
                 if synced:
@@ -929,6 +989,16 @@ class CorpusStore:
         col = self._xcols.get(key)
         if col is None:
             col = self._xcols[key] = _ExtraColumn(self.index.device, field.dtype, coded)
+        col.sync(self.columns[field.name], self.num_entities)
+        return col
+
+    def _array_column(self, field: FieldSchema) -> _ArrayColumn:
+        """The synced device mirror of one of the collection's ARRAY fields.  Caller holds `_filter_lock`."""
+        if self._acols is None:
+            self._acols = {}
+        col = self._acols.get(field.name)
+        if col is None:
+            col = self._acols[field.name] = _ArrayColumn(self.index.device, field.element_type)
         col.sync(self.columns[field.name], self.num_entities)
         return col
 
@@ -1274,7 +1344,7 @@ class CorpusStore:
         if own is not None and own.dtype in (DataType.INT64, DataType.DOUBLE):
             return own
         if own is not None:
-            why = f"a {own.dtype.name} field"
+            why = "an ARRAY field" if own.is_array else f"a {own.dtype.name} field"
         elif name in SCALAR_FIELDS or name in ("embedding", "$meta") or self._text_field(name) is not None:
             why = "a reserved field that holds no number to decay over"
         elif self.enable_dynamic_field:
@@ -1326,8 +1396,8 @@ class CorpusStore:
     def _check_group_by(self, field, group_size, limit, param):
         """-> (field, group_size), or None for "id" (every row its own group: the plain search)."""
         own = self._field(field)
-        if own is not None and own.dtype == DataType.DOUBLE:
-            raise ValueError(f"group_by_field {field!r}: a DOUBLE field cannot be grouped by")
+        if own is not None and own.dtype in (DataType.DOUBLE, DataType.ARRAY):
+            raise ValueError(f"group_by_field {field!r}: {'an ARRAY' if own.is_array else 'a DOUBLE'} field cannot be grouped by")
         if self.enable_dynamic_field and field != "id" and field not in self.GROUP_BY_FIELDS and own is None:
             raise ValueError(f"group_by_field {field!r}: a dynamic key cannot be grouped by")
         if field != "id" and field not in self.GROUP_BY_FIELDS and own is None:
@@ -1358,13 +1428,13 @@ class CorpusStore:
         return fields
 
     def _entity(self, r: int, fields) -> dict:
-        """The output fields of row r."""
+        """The output fields of row r (a row's list of an ARRAY field as a copy: the store keeps its own)."""
         if not self.enable_dynamic_field:
-            return {f: self.columns[f][r] for f in fields}
+            return {f: _out(self.columns[f][r]) for f in fields}
         out = {}
         for f in fields:
             if f in self.columns:
-                out[f] = self.columns[f][r]
+                out[f] = _out(self.columns[f][r])
             elif f == filter_expr.META:
                 out[f] = {key: col[r] for key, col in self.dynamic.items() if col[r] is not None}
             else:
@@ -1675,30 +1745,39 @@ class CorpusStore:
             if self._dcols is None:
                 self._dcols = _DeviceColumns(self.index.device)
             self._dcols.sync(self.columns, n)
-            own = {f.name: self._extra_column(f) for f in self.schema if f.name in filter_expr.fields_of(node)}
+            own = {f.name: self._extra_column(f) for f in self.schema
+                   if not f.is_array and f.name in filter_expr.fields_of(node)}
+            # (only the ARRAY fields this expression reads are mirrored)
+            arrs = {f.name: self._array_column(f) for f in self.schema
+                    if f.is_array and f.name in filter_expr.array_fields_of(node)}
             # (only the dynamic keys this expression reads, and of those the ones some row holds, are mirrored)
             dyn = {key: self._dynamic_column(key) for key in sorted(filter_expr.dynamic_keys_of(node))
                    if key in self.dynamic} if self.enable_dynamic_field else None
             prog = filter_expr.compile_expr(node, self._dcols.dicts, self._pk_row, term_id, self.schema,
-                                            {name: c.dict for name, c in own.items() if c.coded},
+                                            {name: c.dict for name, c in {**own, **arrs}.items() if c.coded},
                                             None if dyn is None else {key: c.dict for key, c in dyn.items()})
-            if not prog.column_leaves and not prog.dynamic_leaves:
+            if not prog.column_leaves and not prog.dynamic_leaves and not prog.array_leaves:
                 bitmaps = sp.text_match(prog.text_leaves) if prog.text_leaves else None
                 return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps)
             # leaves over the collection's own fields: rf_column_match writes their row bitmaps behind the
             # keyword leaves', into the one array the program's RF_FOP_BITMAP leaves index
-            # and rf_dynamic_match the dynamic leaves' behind those
+            # and rf_dynamic_match the dynamic leaves' behind those, rf_array_match the array
+            # leaves' behind those
             T, C, D = len(prog.text_leaves), len(prog.column_leaves), len(prog.dynamic_leaves)
             base, nwords = T * text_words_per_leaf(n), (n + 31) // 32
             mid = base + C * nwords
-            bitmaps = _torch().empty(mid + D * nwords, dtype=_torch().int32, device=self.index.device)
+            end = mid + D * nwords
+            bitmaps = _torch().empty(end + len(prog.array_leaves) * nwords, dtype=_torch().int32, device=self.index.device)
             if T:
                 sp.text_match(prog.text_leaves, out=bitmaps[:base].view(T, -1))
             if C:
                 column_match(self.index.device, prog, {name: c.data for name, c in own.items()}, n, out=bitmaps[base:mid])
             if D:
                 dynamic_match(self.index.device, prog, {key: (c.tags, c.payload) for key, c in dyn.items()}, n,
-                              out=bitmaps[mid:])
+                              out=bitmaps[mid:end])
+            if prog.array_leaves:
+                array_match(self.index.device, prog, {name: (c.offsets, c.values) for name, c in arrs.items()}, n,
+                            out=bitmaps[end:])
             return eval_filter(self.index.device, prog, self._dcols.tensors(), n, bitmaps, column_base=base)
 
     def filter_rows(self, expr: str) -> np.ndarray:
@@ -1748,6 +1827,10 @@ class CorpusStore:
 
     def _expr_rows(self, expr: str) -> np.ndarray:
         return self.filter_rows(expr)
+
+
+def _out(v):
+    return list(v) if isinstance(v, list) else v
 
 
 def _id_in_keys(expr: str):
