@@ -1318,6 +1318,73 @@ int rf_maxsim(const rf_token_field* docs, const void* q_vec_dev, const int32_t* 
 int rf_maxsim_topk(const float* scores_dev, const int64_t* seg_off_dev, const int64_t* rows_dev, int B, int k,
                    int64_t id_base, float* scores_out, int64_t* ids_out, double* exact_out, void* stream);
 
+/* Entity tagging: a BertForTokenClassification head over the same encoder, and the BIO grouping of its labels
+ * into entities (the `transformers` token-classification pipeline's group_entities rule, in integers).
+ *
+ * rf_tag_logits: ids_dev int32 [B, T], lens_dev int32 [B] as for rf_encode -- single-segment rows [CLS] text
+ * [SEP], token types 0.  The layers are rf_encode's; the forward opens with the embedder's embedding launch and
+ * closes with one launch (csrc/tagger.hip) on the last hidden states x_t where rf_encode_tokens reads them:
+ *   l[t][c] = cls_w[c] . x_t + cls_b[c]   for t < lens[b], c < num_labels
+ * an fma chain over k = 0 .. H - 1 ascending from 0.f, then one fp32 add of the bias: a function of the row's own
+ * hidden states alone.  logits_dev is float [B, T, num_labels]; positions >= lens[b] are untouched.  The workspace
+ * is rf_encode's (rf_encode_workspace_bytes: the hidden states already live there).  Always plain launches; the
+ * cached hipGraphs are rf_encode's alone.
+ * Before any launch -- RF_ERR_INVALID: a null or misaligned pointer (cls_w: 16 bytes), B or T < 1.
+ * RF_ERR_UNSUPPORTED: num_labels outside 1..RF_TAGGER_MAX_LABELS, T > max_position, T > 512.
+ * RF_ERR_CAPACITY: workspace too small or misaligned.
+ *
+ * rf_group_entities: one workgroup per row of logits_dev float [B, T, L] (rf_tag_logits', or any other), no
+ * workspace, no forward.  lens_dev [B] is clamped to 0..T; word_start_dev uint8 [B, T] is read under RF_TAG_FIRST
+ * only (1 = the token starts a word) and may be NULL under RF_TAG_SIMPLE; label_tag_dev int32 [L] names the tag of
+ * each label ("B-ORG" and "I-ORG" share one), label_begin_dev uint8 [L] is 1 for the B- labels.
+ *   context   positions 1 .. lens - 2 ([CLS] and the closing [SEP] excluded); lens < 3: no units, count 0
+ *   unit      RF_TAG_SIMPLE: every context token.  RF_TAG_FIRST: a run that starts at a context token with
+ *             word_start = 1 and takes the tokens with word_start = 0 behind it; the first context token always
+ *             starts a unit
+ *   label     of a unit: argmax over c of the logits of its FIRST token, the smallest c among equals
+ *   score     of a unit: 1 / sum_c exp(l_c - l_max) over that token's logits, summed in fp64 with c ascending,
+ *             rounded to fp32 once (the softmax probability of the label)
+ *   groups    unit u joins the running group iff label_tag[label_u] == label_tag[label of the unit before it]
+ *             and label_begin[label_u] == 0; otherwise it starts a group
+ *   rf_entity tag = the tag of the group's first unit; first = the first token of its first unit, last = the last
+ *             token of its last unit; score = (its units' fp32 scores summed as fp64 in position order) / (their
+ *             number), rounded to fp32 once
+ *   output    groups whose tag == ignore_tag are dropped (-1 drops none); the others are written in position
+ *             order.  count_dev[b] = how many survive, also beyond max_entities; ent_dev [B, max_entities] holds
+ *             the first max_entities of them, the unused slots are (-1, -1, -1, -inf)
+ *   tokens    tok_label_dev int32 / tok_score_dev float [B, T] (each nullable): the RF_TAG_SIMPLE label and score
+ *             of every context token, whatever the strategy; other positions are untouched
+ * Integers and fixed-order sums only: no atomics, no arrival-order reduction, the same bits on every run.  Table
+ * indices are clamped: malformed lens give wrong numbers, never an access out of range.  Logits are expected
+ * finite.  Stream-ordered, no allocation, no host sync.
+ * RF_ERR_INVALID before any launch: a null pointer (but the nullable ones; word_start_dev under RF_TAG_FIRST is
+ * not), B < 1, T outside 1..512, L outside 1..RF_TAGGER_MAX_LABELS, strategy outside {0, 1}, max_entities outside
+ * 1..RF_TAGGER_MAX_ENTITIES.
+ * The pipeline's MAX and AVERAGE strategies compare softmax values across tokens, which is no function of the
+ * logits' order alone; they are not offered.
+ * New in this build; the reference tags entities with a hosted LLM (FinRag_knowledge_graph/entity/extraction.py). */
+#define RF_TAGGER_MAX_LABELS 64
+#define RF_TAGGER_MAX_ENTITIES 128   /* groups reported per row */
+#define RF_TAG_SIMPLE 0              /* unit = token */
+#define RF_TAG_FIRST 1               /* unit = word, labelled by its first token */
+typedef struct rf_tag_head {         /* caller keeps alive for the call */
+  const void* cls_w;                 /* [num_labels, H] classifier.weight, device fp16, 16-byte aligned */
+  const void* cls_b;                 /* [num_labels] */
+  int32_t num_labels;
+} rf_tag_head;
+typedef struct rf_entity {
+  int32_t first, last;               /* token positions in the row, inclusive; -1, -1 = none */
+  int32_t tag;
+  float score;
+} rf_entity;
+int rf_tag_logits(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
+                  const rf_tag_head* head, float* logits_dev, void* workspace_dev, size_t workspace_bytes,
+                  void* stream);
+int rf_group_entities(const float* logits_dev, const int32_t* lens_dev, const uint8_t* word_start_dev, int B, int T,
+                      int L, const int32_t* label_tag_dev, const uint8_t* label_begin_dev, int strategy,
+                      int ignore_tag, int max_entities, int32_t* tok_label_dev, float* tok_score_dev,
+                      rf_entity* ent_dev, int32_t* count_dev, void* stream);
+
 /* ---- tokenizer: the text -> token-id stage in front of rf_encode ------------------------
  * Reference: the WordPiece tokenizer SentenceTransformer('all-MiniLM-L6-v2') loads by name
  * (vector_rag_mcp/main.py:41,50; "chunking_storing (1).py":8,380).  Host code, multi-threaded.

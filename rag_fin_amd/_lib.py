@@ -161,6 +161,18 @@ class TokenField(Structure):
     _fields_ = [("vec", c_void_p), ("off", c_void_p), ("n_rows", c_int64), ("dim", c_int32)]
 
 
+# entity tagging (include/ragfin.h, rf_tag_logits / rf_group_entities)
+RF_TAGGER_MAX_LABELS = 64    # labels of a classifier
+RF_TAGGER_MAX_ENTITIES = 128   # groups reported per row
+RF_TAGGER_MAX_T = 512        # positions of a row the grouping holds
+RF_TAG_SIMPLE, RF_TAG_FIRST = 0, 1
+
+
+class TagHead(Structure):
+    """rf_tag_head: the classifier of a BertForTokenClassification (device fp16 pointers)."""
+    _fields_ = [("cls_w", c_void_p), ("cls_b", c_void_p), ("num_labels", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/ragfin.h declares
 SIGNATURES = {
     "rf_version": (c_int, []),
@@ -321,6 +333,10 @@ SIGNATURES = {
                           c_void_p]),
     "rf_maxsim_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "rf_tag_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(TagHead), c_void_p, c_void_p,
+                              c_size_t, c_void_p]),
+    "rf_group_entities": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # present only in the experiments build (libragfin_hip_exp.so, tools/): bound when exported

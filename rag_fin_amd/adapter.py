@@ -4,7 +4,7 @@ Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
   GET /            service card                         (:121-132)
   GET /health      {"status": "healthy", "mcp": ...} | {"status": "unhealthy", "mcp": "unavailable"}
   POST /search     {query: str >= 5 chars, top_k: 1..20 = 3, filter: str (optional), rerank: bool (optional),
-                   hybrid: bool (optional), lexical: "bm25" | "learned" | "both" (optional), rerank_with: "cross" | "late" (optional), offset: int >= 0 (optional), boost_filter: str + boost_weight: float > 0
+                   hybrid: bool (optional), lexical: "bm25" | "learned" | "both" (optional), rerank_with: "cross" | "late" (optional), match_entities: "any" | "all" (optional), offset: int >= 0 (optional), boost_filter: str + boost_weight: float > 0
                    (optional), decay_field: str + decay_function: "gauss" | "exp" | "linear" + decay_origin: float +
                    decay_scale: float > 0 [+ decay_offset: float >= 0, decay_rate: 0 < float < 1] (optional)}
                                                                -> tool search_vectors
@@ -55,6 +55,8 @@ class SearchRequest(BaseModel):
     lexical: Optional[str] = None
     # the second stage of a reranked search: "cross" (the default: the cross-encoder) or "late" (MaxSim); new
     rerank_with: Optional[str] = None
+    # entity filter: only chunks that mention any / all of the entities the tagger finds in the query; new
+    match_entities: Optional[str] = None
     # paging (skip the best `offset` chunks, return the next top_k); new
     offset: Optional[int] = Field(default=None, ge=0)
     # boosted search (the chunks boost_filter selects have their score multiplied by boost_weight); new
@@ -72,11 +74,11 @@ class SearchRequest(BaseModel):
 
 def search_args(req: SearchRequest) -> dict:
     """Tool arguments of POST /search: `filter`, `min_score`, `max_score`, `group_by`, `group_size`,
-    `mmr_lambda`, `fetch_k`, `offset`, `boost_filter`, `boost_weight`, `decay_*`, `lexical` and `rerank_with` only when they were given, `rerank` and
+    `mmr_lambda`, `fetch_k`, `offset`, `boost_filter`, `boost_weight`, `decay_*`, `lexical`, `rerank_with` and `match_entities` only when they were given, `rerank` and
     `hybrid` only when set, so the reference's payload {"query", "top_k"} is unchanged."""
     args = {"query": req.query, "top_k": req.top_k}
     for name in ("filter", "min_score", "max_score", "group_by", "group_size", "mmr_lambda", "fetch_k", "offset",
-                 "boost_filter", "boost_weight", "lexical", "rerank_with", "decay_field", "decay_function", "decay_origin",
+                 "boost_filter", "boost_weight", "lexical", "rerank_with", "match_entities", "decay_field", "decay_function", "decay_origin",
                  "decay_scale", "decay_offset", "decay_rate"):
         if getattr(req, name) is not None:
             args[name] = getattr(req, name)

@@ -1597,12 +1597,12 @@ extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const 
 
 const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc) { return enc->cfg; }
 
-// rf_score_pairs (rerank.hip), rf_answer_spans (reader.hip), rf_encode_terms (splade.hip) and rf_encode_tokens (late_interaction.hip) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
+// rf_score_pairs (rerank.hip), rf_answer_spans (reader.hip), rf_encode_terms (splade.hip), rf_encode_tokens (late_interaction.hip) and rf_tag_logits (tagger.hip) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
 // rf_encode's alone, so a pair forward can never replay an embedding graph, nor the other way round.
 int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
                     const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
                     const char* who) {
-  if (!ends.terms && !ends.tokens && enc->cfg.type_vocab < 2) {
+  if (!ends.terms && !ends.tokens && !ends.tags && enc->cfg.type_vocab < 2) {
     rf_set_error("%s: the encoder has %d token-type row(s); a pair needs 2", who, enc->cfg.type_vocab);
     return RF_ERR_UNSUPPORTED;
   }
@@ -1627,7 +1627,7 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
   const int32_t* m_ptr = ws.tok_off + B;
 
   if (B > 1) hipLaunchKernelGGL(k_tok_offsets, dim3(1), dim3(256), 0, st, lens_dev, B, T, ws.tok_off);   // B == 1: the embedding launch writes them
-  if (ends && !ends->terms && !ends->tokens) {
+  if (ends && !ends->terms && !ends->tokens && !ends->tags) {
     rf_launch_embed_pair(ids_dev, lens_dev, ends->seg, ws.tok_off, B, T, c, w, ws.x, st);
   } else {
     const int chunks = B * ((T + 31) / 32);   // one workgroup per 32 positions of a row
@@ -1646,7 +1646,10 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
   const AttKernel att = attention_kernel(att_kb);
   if (T <= 32 * ATT_MAX_KB) RF_HIP(rf_ensure_lds(*att.attr, (const void*)att.fn, mfma_lds));
   float* const att_dbg = (rf_knob_debug_epi == 2) ? (float*)rf_debug_buffer : nullptr;   // clock stamps (experiments build)
-  const bool one_query = rf_knob_one_query && B == 1 && T <= 32 && rf_knob_linear_small;
+  // (not for a tag forward: the one-launch form rounds a few hidden values otherwise than the two launches it
+  // stands for -- measured: a row's last fp16 bits differ between a batch of 1 and a batch of 64 on most inputs --
+  // and a token's label must not depend on how many rows were tagged with it)
+  const bool one_query = rf_knob_one_query && B == 1 && T <= 32 && rf_knob_linear_small && !(ends && ends->tags);
   _Float16* x = ws.x;
   _Float16* y = ws.y;
   for (int l = 0; l < L; ++l) {
@@ -1699,6 +1702,8 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
     rf_launch_terms_head(x, ws.tok_off, B, T, *ends->terms, c.ln_eps, st);
   else if (ends && ends->tokens)
     rf_launch_tokens_head(x, ws.tok_off, ids_dev, lens_dev, B, T, *ends->tokens, st);
+  else if (ends && ends->tags)
+    rf_launch_tags_head(x, ws.tok_off, B, T, *ends->tags, st);
   else if (ends && ends->qa)
     rf_launch_qa_spans(x, ws.tok_off, B, T, *ends, st);
   else if (ends)

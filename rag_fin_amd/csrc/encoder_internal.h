@@ -165,6 +165,7 @@ struct rf_pair_ends {
   float* qa_logits;           // [B, T, 2] or nullptr
   const struct rf_terms_end* terms;   // a third pair of ends (splade.hip), or nullptr: see below
   const struct rf_tokens_end* tokens; // a fourth pair of ends (late_interaction.hip), or nullptr: see below
+  const struct rf_tags_end* tags;     // a fifth pair of ends (tagger.hip), or nullptr: see below
 };
 void rf_launch_embed_pair(const int32_t* ids, const int32_t* lens, const int32_t* seg, int32_t* tok_off, int B, int T,
                           const rf_encoder_config& c, const rf_encoder_weights& w, _Float16* out, hipStream_t st);
@@ -193,6 +194,14 @@ struct rf_tokens_end {
 };
 void rf_launch_tokens_head(const _Float16* x, const int32_t* tok_off, const int32_t* ids, const int32_t* lens, int B,
                            int T, const rf_tokens_end& e, hipStream_t st);
+// ---- tagger.hip: a tag forward = the same layers between the embedder's embedding launch and a token classifier ------
+// With `tags` set in rf_pair_ends the forward opens with k_embed_ln (token types 0, as for `terms`) and closes
+// with k_tag_logits; the other fields are unused.
+struct rf_tags_end {
+  const rf_tag_head* head;    // device pointers of the classifier
+  float* logits;              // [B, T, num_labels]
+};
+void rf_launch_tags_head(const _Float16* x, const int32_t* tok_off, int B, int T, const rf_tags_end& e, hipStream_t st);
 const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc);   // encoder.hip
 // encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph);
 // `who` names the public entry in the error text

@@ -88,6 +88,16 @@ def stack_hf_qa_head(sd: dict) -> dict:
     return {"qa_w": get("qa_outputs.weight"), "qa_b": get("qa_outputs.bias")}
 
 
+def stack_hf_tag_head(sd: dict) -> dict:
+    """The token classifier of a Hugging Face BertForTokenClassification state dict -> the tensors of rf_tag_head:
+    classifier.weight [num_labels, H], row c the logit of label c, and classifier.bias [num_labels]."""
+    def get(name):
+        if name not in sd:
+            raise KeyError(f"checkpoint lacks {name} (not a BertForTokenClassification?)")
+        return np.asarray(sd[name], dtype=np.float32)
+    return {"cls_w": get("classifier.weight"), "cls_b": get("classifier.bias")}
+
+
 def hf_encoder_config(hc: dict) -> dict:
     """config.json of a BERT checkpoint -> the fields of rf_encoder_config."""
     if hc.get("hidden_act", "gelu") != "gelu":

@@ -62,7 +62,7 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                    boost_weight: float | None = None, lexical: str | None = None, rerank_with: str | None = None,
                    decay_field: str = "", decay_function: str | None = None, decay_origin: float | None = None,
                    decay_scale: float | None = None, decay_offset: float | None = None,
-                   decay_rate: float | None = None):
+                   decay_rate: float | None = None, match_entities: str | None = None):
     """Semantic search in vector store.  filter: an optional boolean expression over the
     scalar fields, e.g. 'period == "Q1_FY2024" and primary_value > 0' (Milvus syntax).
     min_score / max_score: optional score cut-offs, min_score < score <= max_score.
@@ -91,7 +91,10 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
     decay_rate, default 0.5): optional time decay -- every chunk's score is multiplied by a weight that is 1
     where the numeric field decay_field lies within decay_offset of decay_origin and falls to decay_rate at
     distance decay_offset + decay_scale, along a "gauss", "exp" or "linear" curve; `score` is then the decayed
-    score.  The first four go together; with filter, with the exclusions of the boost and not together with it."""
+    score.  The first four go together; with filter, with the exclusions of the boost and not together with it.
+    match_entities: optional entity filter -- "any" or "all": only chunks that mention one (all) of the entities
+    the tagger finds in the query are ranked, and-ed with filter; a query without entities searches unfiltered
+    (needs TAGGER_MODEL_DIR at ingest)."""
     try:
         decay_given = [v is not None for v in (decay_function, decay_origin, decay_scale, decay_offset, decay_rate)]
         if bool(decay_field and decay_field.strip()) or any(decay_given):
@@ -110,6 +113,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                 kw["rerank"] = True
             if hybrid:
                 kw["hybrid"] = True
+            if match_entities is not None:
+                kw["match_entities"] = match_entities
             if bool(boost_filter and boost_filter.strip()) or boost_weight is not None:
                 kw["boost"] = {"filter": boost_filter, "weight": boost_weight}   # (VectorRAG refuses the combination)
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None, decay=decay, **kw)
@@ -131,6 +136,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
                 kw["lexical"] = lexical
             if rerank_with is not None:
                 kw["rerank_with"] = rerank_with
+            if match_entities is not None:
+                kw["match_entities"] = match_entities
             contexts = get_rag().search(query, top_k, expr=filter if filter and filter.strip() else None,
                                         boost={"filter": boost_filter, "weight": boost_weight}, **kw)
             return {"status": "success", "query": query, "results": contexts, "result_count": len(contexts)}
@@ -144,6 +151,8 @@ def search_vectors(query: str, top_k: int = 3, filter: str = "", min_score: floa
             mmr["lexical"] = lexical
         if rerank_with is not None:
             mmr["rerank_with"] = rerank_with
+        if match_entities is not None:   # (an entity-filtered call bypasses the micro-batcher like a filtered one)
+            mmr["match_entities"] = match_entities
         if offset is not None:   # (a paged call bypasses the micro-batcher too: one batch shares one offset)
             mmr["offset"] = offset
         if group_by is not None:

@@ -34,7 +34,8 @@ class VectorRAG:
     def __init__(self, gemini_api_key: str | None = None, collection_name: str = "fin_chunks", *,
                  embedder=None, store=None, generator: Callable[[str], str] | None = None,
                  llm_delay_s: float = 1.0, prompt_template: str = DEFAULT_PROMPT, reranker=None, reader=None,
-                 sparse_encoder=None, late_encoder=None, extra_output_fields=None):
+                 sparse_encoder=None, late_encoder=None, extra_output_fields=None, tagger=None,
+                 entity_field: str | None = None):
         """embedder: .encode(list[str]) -> [n, dim] (rag_fin_amd.embedder.Embedder);
         store: rag_fin_amd.store.CorpusStore.  `gemini_api_key` is accepted for
         signature compatibility and only handed to `generator` factories upstream.
@@ -51,7 +52,13 @@ class VectorRAG:
         search(..., rerank=True, rerank_with="late").
         extra_output_fields: names of the store's own fields (CorpusStore(fields=...)) whose values are added to
         the context dicts under their names; by default the keys stay exactly the reference's.  On a store with
-        enable_dynamic_field a name that is no declared field is a dynamic key (None where a chunk lacks it)."""
+        enable_dynamic_field a name that is no declared field is a dynamic key (None where a chunk lacks it).
+        tagger / entity_field (both or neither): .tags(list[str]) -> the entity strings of each text
+        (rag_fin_amd.tagger.TokenClassifier) and the ARRAY VARCHAR field of the store that holds the chunks' entities
+        (service.ingest(..., tagger=, entity_field=) fills it): what search(..., match_entities=) filters on."""
+        if (tagger is None) != (entity_field is None):
+            raise ValueError("tagger and entity_field go together")
+        self.tagger, self.entity_field = tagger, entity_field
         if embedder is None or store is None:
             raise ValueError("VectorRAG needs an embedder and a corpus store (see rag_fin_amd.service."
                              "build_rag); there is no remote Milvus/sentence-transformers fallback")
@@ -117,7 +124,7 @@ class VectorRAG:
                max_score: float | None = None, group_by: str | None = None, group_size: int = 1,
                mmr_lambda: float | None = None, fetch_k: int | None = None, rerank: bool = False,
                hybrid: bool = False, offset: int | None = None, boost=None, lexical: str = "bm25",
-               rerank_with: str = "cross", decay=None) -> list[dict]:
+               rerank_with: str = "cross", decay=None, match_entities: str | None = None) -> list[dict]:
         """Ranked context dicts, keys exactly as vector_rag_mcp/main.py:59-70.  expr: a filter
         over the scalar fields (rag_fin_amd.filter_expr), e.g. 'period == "Q1_FY2024"'.
         min_score / max_score: only chunks with min_score < score <= max_score (range search;
@@ -158,7 +165,13 @@ class VectorRAG:
         field (primary_value, or an INT64 / DOUBLE field of the store) lies within `offset` of `origin` and falls
         to `decay` at distance offset + scale, along a "gauss", "exp" or "linear" curve; the top_k are the exact
         best of the whole store under that decayed score, which is what `score` then holds.  With expr (one
-        string); with the same exclusions as boost, and not together with boost (ValueError)."""
+        string); with the same exclusions as boost, and not together with boost (ValueError).
+        match_entities: "any" or "all" -- the entities the tagger finds in the query become
+        ARRAY_CONTAINS_ANY / ARRAY_CONTAINS_ALL(<entity_field>, [...]), and-ed with expr: only chunks that mention
+        one (all) of them are ranked.  A query without entities searches unfiltered.  Needs VectorRAG(...,
+        tagger=, entity_field=), else ValueError."""
+        if match_entities is not None:
+            expr = self._entity_exprs([query], expr, match_entities)[0]
         ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         ranker = self._decay_args(decay, ranker, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         self._check_offset(offset, rerank, hybrid, mmr_lambda, group_by)
@@ -212,6 +225,25 @@ class VectorRAG:
                              '"scale": float} with optional "offset" and "decay"')
         return {"ranker": DecayRanker(decay["field"], decay["function"], decay["origin"], decay["scale"],
                                       decay.get("offset", 0.0), decay.get("decay", 0.5))}
+
+    def _entity_exprs(self, queries, expr, match_entities) -> list:
+        """Per query: expr (one string or None for all, or one entry per query) and-ed with the filter on the
+        query's entities (rag_fin_amd.tagger.entity_expr); a query without entities keeps its expr."""
+        from .tagger import entity_expr
+        if match_entities not in ("any", "all"):
+            raise ValueError(f"match_entities must be 'any' or 'all', got {match_entities!r}")
+        if self.tagger is None:
+            raise ValueError("match_entities needs a tagger (VectorRAG(..., tagger=TokenClassifier.from_local(dir), "
+                             "entity_field=<the ARRAY VARCHAR field ingest filled>))")
+        own = list(expr) if isinstance(expr, (list, tuple)) else [expr] * len(queries)
+        if len(own) != len(queries):
+            raise ValueError(f"expr list: {len(own)} entries for {len(queries)} queries (one entry per query)")
+        out = []
+        for e, found in zip(own, self.tagger.tags(list(queries))):
+            f = entity_expr(self.entity_field, found, match_entities)
+            e = e if e and e.strip() else None
+            out.append(e if f is None else (f if e is None else f"({e}) and {f}"))
+        return out
 
     def _embed(self, texts):
         """`.encode(texts)` of the reference (main.py:50) -- kept on the device when the embedder
@@ -325,7 +357,8 @@ class VectorRAG:
                      group_by: str | None = None, group_size: int = 1,
                      mmr_lambda: float | None = None, fetch_k: int | None = None,
                      rerank: bool = False, hybrid: bool = False, offset: int | None = None,
-                     boost=None, lexical: str = "bm25", rerank_with: str = "cross", decay=None) -> list[list[dict]]:
+                     boost=None, lexical: str = "bm25", rerank_with: str = "cross", decay=None,
+                     match_entities: str | None = None) -> list[list[dict]]:
         """Many queries in one embed + one corpus sweep per 64 (new: the reference
         is strictly one query per call); expr, min_score / max_score, group_by / group_size,
         mmr_lambda / fetch_k: one filter, one score band, one grouping and one diversification for
@@ -338,7 +371,11 @@ class VectorRAG:
         (CorpusStore.search(expr=[...])).  The list form is the plain path only: with rerank, hybrid,
         min_score / max_score, group_by, mmr_lambda or offset it raises ValueError.
         boost: one boost (or up to 3) for the whole batch, as in search(); not with a list expr.
-        decay: one time decay for the whole batch, as in search(); not with a list expr."""
+        decay: one time decay for the whole batch, as in search(); not with a list expr.
+        match_entities: as in search(), per query: every query is filtered on its own entities, so expr becomes
+        the list form (one tagger call for the batch) with the list form's limits."""
+        if match_entities is not None and queries:
+            expr = self._entity_exprs(list(queries), expr, match_entities)
         ranker = self._boost_args(boost, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         ranker = self._decay_args(decay, ranker, rerank, hybrid, group_by, mmr_lambda, min_score, max_score, offset, expr)
         if isinstance(expr, (list, tuple)):

@@ -16,6 +16,11 @@ Environment (dotenv-style names):
   COLBERT_MODEL_DIR    optional local ColBERT directory (a BertModel of the same family plus a projection, Stanford
                        or PyLate layout): declares the late-interaction field, enables search(..., rerank=True,
                        rerank_with="late")
+  TAGGER_MODEL_DIR     optional local token-classification (NER) directory (a BertForTokenClassification of the
+                       same family, same three files, id2label in config.json): the entities of every chunk are
+                       stored at ingest and search(..., match_entities="any" | "all") filters on the query's
+  TAGGER_FIELD         the field the entities go to (default "entities"): a declared ARRAY VARCHAR field, or a
+                       dynamic key of a store with enable_dynamic_field
   LEXICAL_INDEX        1: declare the lexical (BM25) index at ingest: enables search(..., hybrid=True)
   RAGFIN_DATA_DIR      folder with icici_q{1..4}_2023/*.json (default: extract_data)
   RAGFIN_DEVICE        torch device string (default cuda:0)
@@ -56,7 +61,36 @@ def extra_columns(fields, chunks, values=None, dynamic: bool = False) -> dict:
     return out
 
 
-def ingest(store, embedder, chunks, upsert: bool = False, field_values: dict | None = None) -> int:
+ENTITY_CAPACITY = 16   # max_capacity of the entity field build_rag declares when the caller declared none
+
+
+def entity_column(store, tagger, entity_field: str, texts, batch: int = 256):
+    """The entities of `texts` as the column of `entity_field`: tagger.tags(texts) in batches of `batch` texts (one
+    forward per length bucket of a batch, not one per text).  A declared ARRAY VARCHAR field takes each row's
+    distinct entity strings, cut to its max_capacity -> (column, False).  On a store with enable_dynamic_field a
+    name that is no declared field is a dynamic key; dynamic keys hold no lists, so it takes the row's first
+    entity string, or None (the row lacks the key) -> (column, True).  Anything else: ValueError."""
+    from .schema import DataType
+    if not isinstance(entity_field, str) or not entity_field:
+        raise ValueError("entity_field must name the field the entities go to")
+    field = next((f for f in getattr(store, "schema", ()) if f.name == entity_field), None)
+    dynamic = field is None and bool(getattr(store, "enable_dynamic_field", False))
+    if field is None and not dynamic:
+        raise ValueError(f"entity_field: {entity_field!r} is not a field the store declares (declare it as ARRAY of "
+                         "VARCHAR, or create the store with enable_dynamic_field)")
+    if field is not None and not (field.is_array and field.element_type == DataType.VARCHAR):
+        raise ValueError(f"entity_field: {entity_field!r} is {field.dtype.name}, the entities need an ARRAY of VARCHAR")
+    cap = 1 if dynamic else field.max_capacity
+    rows = []
+    for i in range(0, len(texts), batch):
+        rows.extend(tagger.tags(texts[i:i + batch], max_per_row=cap))
+    if dynamic:
+        return [r[0] if r else None for r in rows], True
+    return rows, False
+
+
+def ingest(store, embedder, chunks, upsert: bool = False, field_values: dict | None = None, tagger=None,
+           entity_field: str | None = None) -> int:
     """The reference's encode + insert + flush + load
     ("chunking_storing (1).py":377-397) on the GPU: texts are embedded by rf_encode
     and the fp16 rows go straight into the HBM corpus (no host round trip).
@@ -64,15 +98,26 @@ def ingest(store, embedder, chunks, upsert: bool = False, field_values: dict | N
     quarter is re-ingested in place of dropping the collection); otherwise an existing id
     raises ValueError.
     field_values: the values of the store's own fields (CorpusStore(fields=...)), as extra_columns takes them;
-    on a store with enable_dynamic_field a name that is no declared field becomes a dynamic key."""
+    on a store with enable_dynamic_field a name that is no declared field becomes a dynamic key.
+    tagger / entity_field (both or neither): the entities a rag_fin_amd.tagger.TokenClassifier finds in every
+    chunk's text fill the field entity_field, as entity_column lays them out."""
+    if (tagger is None) != (entity_field is None):
+        raise ValueError("tagger and entity_field go together")
     if not chunks:
         return 0
+    tagged = None
+    if tagger is not None:
+        if field_values and entity_field in field_values:
+            raise ValueError(f"field_values already names {entity_field!r}, the field the tagger fills")
+        tagged = entity_column(store, tagger, entity_field, [c["text"] for c in chunks])[0]
     emb = embedder.encode_to_device([c["text"] for c in chunks])
     cols = chunker.insert_columns(chunks, emb)
     fields = getattr(store, "schema", ())
     dynamic = bool(getattr(store, "enable_dynamic_field", False))
-    if fields or field_values:
+    if fields or field_values or tagged is not None:
         own = extra_columns(fields, chunks, field_values, dynamic)
+        if tagged is not None:
+            own[entity_field] = tagged
         missing = [f.name for f in fields if f.name not in own and f.default is None]
         if missing:
             raise ValueError(f"ingest: no value for the field(s) {', '.join(missing)} (field_values, a key of the chunk "
@@ -108,6 +153,13 @@ def _load_sparse_encoder(sparse_dir, device):
     return SparseEncoder.from_local(sparse_dir, device=device)
 
 
+def _load_tagger(tagger_dir, device):
+    if not tagger_dir:
+        return None
+    from .tagger import TokenClassifier
+    return TokenClassifier.from_local(tagger_dir, device=device)
+
+
 def _load_late_encoder(late_dir, device):
     if not late_dir:
         return None
@@ -119,7 +171,8 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               collection_name: str = "fin_chunks", generator=None, reranker_dir: str | None = None,
               hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None,
               sparse_dir: str | None = None, late_dir: str | None = None, fields=None, field_values: dict | None = None,
-              extra_output_fields=None, enable_dynamic_field: bool = False):
+              extra_output_fields=None, enable_dynamic_field: bool = False, tagger_dir: str | None = None,
+              entity_field: str | None = None):
     """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
     can run; its posting lists are built by the first such search.
     sparse_dir: a local SPLADE checkpoint: the learned sparse field is declared on the store (VectorRAG does
@@ -129,14 +182,28 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     fields: FieldSchema objects of the collection's own scalar fields (rag_fin_amd.schema); field_values: their
     values per chunk, as extra_columns takes them; extra_output_fields: those of them the context dicts carry.
     enable_dynamic_field: the store takes keys no field declares (a name of field_values that is no declared field
-    becomes one; extra_output_fields may name them)."""
+    becomes one; extra_output_fields may name them).
+    tagger_dir: a local token-classification checkpoint; entity_field (default "entities" with a tagger): the
+    declared ARRAY VARCHAR field, or dynamic key, its entities fill at ingest and search(..., match_entities=)
+    filters on.  Where `fields` does not declare it and the store is not dynamic, it is declared here as an ARRAY
+    of VARCHAR with max_capacity ENTITY_CAPACITY."""
     from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
     embedder = Embedder.from_local(model_dir, device=device)
+    tagger = _load_tagger(tagger_dir, device)
+    if tagger is None and entity_field is not None:
+        raise ValueError("entity_field needs a tagger (tagger_dir)")
+    tagging = {} if tagger is None else {"tagger": tagger, "entity_field": entity_field or "entities"}
+    if tagger is not None and not enable_dynamic_field and tagging["entity_field"] not in [f.name for f in fields or ()]:
+        # the field the entities go to, declared here when the caller did not
+        from .schema import DataType, FieldSchema
+        fields = list(fields or ()) + [FieldSchema(tagging["entity_field"], DataType.ARRAY, element_type=DataType.VARCHAR,
+                                                   max_capacity=ENTITY_CAPACITY)]
     store = CorpusStore(collection_name, dim=embedder.dim, device=device, **({"fields": fields} if fields else {}),
                         **({"enable_dynamic_field": True} if enable_dynamic_field else {}))
-    ingest(store, embedder, chunker.build_all_chunks(data_dir), **({"field_values": field_values} if field_values else {}))
+    ingest(store, embedder, chunker.build_all_chunks(data_dir), **({"field_values": field_values} if field_values else {}),
+           **tagging)
     if hybrid:
         store.create_index("sparse", {"index_type": "SPARSE_INVERTED_INDEX", "metric_type": "BM25"})
     sparse = _load_sparse_encoder(sparse_dir, device)
@@ -145,7 +212,7 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
                      reranker=_load_reranker(reranker_dir, device), reader=_load_reader(reader_dir, device, reader_doc_stride),
                      **({} if sparse is None else {"sparse_encoder": sparse}),
                      **({} if late is None else {"late_encoder": late}),
-                     **({"extra_output_fields": extra_output_fields} if extra_output_fields else {}))
+                     **({"extra_output_fields": extra_output_fields} if extra_output_fields else {}), **tagging)
 
 
 def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
@@ -205,6 +272,7 @@ def build_rag_from_env():
     reader_doc_stride = int(os.environ["READER_DOC_STRIDE"]) if os.getenv("READER_DOC_STRIDE") else None
     sparse_dir = os.getenv("SPARSE_MODEL_DIR") or None
     late_dir = os.getenv("COLBERT_MODEL_DIR") or None
+    tagger_dir = os.getenv("TAGGER_MODEL_DIR") or None
     if int(os.getenv("WORLD_SIZE", "1")) > 1:
         return build_sharded_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                                  int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
@@ -213,4 +281,6 @@ def build_rag_from_env():
                      os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
                      reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1", reader_dir=reader_dir,
                      reader_doc_stride=reader_doc_stride, **({"sparse_dir": sparse_dir} if sparse_dir else {}),
-                     **({"late_dir": late_dir} if late_dir else {}))
+                     **({"late_dir": late_dir} if late_dir else {}),
+                     **({"tagger_dir": tagger_dir, "entity_field": os.getenv("TAGGER_FIELD") or "entities"}
+                        if tagger_dir else {}))
