@@ -1088,6 +1088,37 @@ int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* le
               int B, int T, void* out_f16_dev, float* out_f32_dev,
               void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* Sentence-embedder families: rf_encode with the Pooling and Normalize modules of a sentence-transformers
+ * directory (BGE and arctic-embed pool the [CLS] token, E5 excludes nothing but prepends a prompt, the
+ * multi-qa "dot" models have no Normalize module).  The forward is rf_encode's -- the same embedding launch and
+ * layers on every path by B and T -- and closes with one launch of csrc/sentence_head.hip where rf_encode pools.
+ * ids_dev, lens_dev, outputs and workspace as for rf_encode; skip_dev int32 [B] or NULL (= all 0) is the number
+ * of leading tokens of a row left out of the pooled set (a prompt's, with include_prompt false), clamped to
+ * 0..lens[b].
+ *   set       of row b: the tokens skip[b] <= t < lens[b]
+ *   MEAN      sum / max(count, 1e-9)       MEAN_SQRT_LEN  sum / sqrt(count)
+ *   MAX       the per-feature maximum over the set: exact, the hidden values are fp16
+ *   CLS       token 0, whatever skip says
+ *   empty set the zero vector in the three set modes (sentence-transformers' Pooling gives -1e9 for MAX there:
+ *             a departure, written down as such; rag_fin_amd.embedder never produces an empty set); a row with
+ *             lens < 1 gives zeros in every mode
+ *   normalize != 0 divides by max(||x||_2, 1e-12); otherwise the pooled vector is written as it is
+ * The sums are fp32 in a fixed, sequence-relative order; skip masks tokens out of that order and does not shift
+ * it, so RF_POOL_MEAN with normalize = 1 and no skip equals rf_encode's fp32 and fp16 outputs bit for bit, and a
+ * row's bits do not depend on its place in the batch.  Always plain launches: the cached hipGraphs are
+ * rf_encode's alone, so a single query pays its launches one by one.
+ * RF_ERR_INVALID before any launch: a null enc, ids, lens, head or workspace, both outputs null, pooling outside
+ * the enum, B or T < 1.  RF_ERR_UNSUPPORTED: T > max_position.  RF_ERR_CAPACITY: workspace too small or misaligned.
+ * New in this build; the reference embeds with all-MiniLM-L6-v2 alone (vector_rag_mcp/main.py:41). */
+enum { RF_POOL_MEAN = 0, RF_POOL_CLS = 1, RF_POOL_MAX = 2, RF_POOL_MEAN_SQRT_LEN = 3 };
+typedef struct rf_sentence_head {
+  int32_t pooling;                   /* RF_POOL_* */
+  int32_t normalize;                 /* != 0: L2-normalise the pooled vector */
+} rf_sentence_head;
+int rf_encode_sentences(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev,
+                        const int32_t* skip_dev, int B, int T, const rf_sentence_head* head, void* out_f16_dev,
+                        float* out_f32_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* Cross-encoder reranking: one relevance logit per (query, chunk) pair from a
  * BertForSequenceClassification checkpoint of the same family (cross-encoder/ms-marco-MiniLM-L-6-v2,
  * -L-12-v2): the encoder handle holds the BertModel weights, `head` the pooler and the classifier

@@ -173,6 +173,15 @@ class TagHead(Structure):
     _fields_ = [("cls_w", c_void_p), ("cls_b", c_void_p), ("num_labels", c_int32)]
 
 
+# sentence-embedder families (include/ragfin.h, rf_encode_sentences)
+RF_POOL_MEAN, RF_POOL_CLS, RF_POOL_MAX, RF_POOL_MEAN_SQRT_LEN = 0, 1, 2, 3
+
+
+class SentenceHead(Structure):
+    """rf_sentence_head: the Pooling mode and whether a Normalize module follows it."""
+    _fields_ = [("pooling", c_int32), ("normalize", c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/ragfin.h declares
 SIGNATURES = {
     "rf_version": (c_int, []),
@@ -335,6 +344,8 @@ SIGNATURES = {
                                c_void_p]),
     "rf_tag_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(TagHead), c_void_p, c_void_p,
                               c_size_t, c_void_p]),
+    "rf_encode_sentences": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(SentenceHead),
+                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rf_group_entities": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                   c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }

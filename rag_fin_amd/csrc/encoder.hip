@@ -1597,12 +1597,12 @@ extern "C" int rf_encode(const rf_encoder_t* enc, const int32_t* ids_dev, const 
 
 const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc) { return enc->cfg; }
 
-// rf_score_pairs (rerank.hip), rf_answer_spans (reader.hip), rf_encode_terms (splade.hip), rf_encode_tokens (late_interaction.hip) and rf_tag_logits (tagger.hip) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
+// rf_score_pairs (rerank.hip), rf_answer_spans (reader.hip), rf_encode_terms (splade.hip), rf_encode_tokens (late_interaction.hip), rf_tag_logits (tagger.hip) and rf_encode_sentences (below) behind their pointer checks.  Always the plain launches: the cached hipGraphs are
 // rf_encode's alone, so a pair forward can never replay an embedding graph, nor the other way round.
 int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
                     const rf_pair_ends& ends, void* workspace_dev, size_t workspace_bytes, hipStream_t st,
                     const char* who) {
-  if (!ends.terms && !ends.tokens && !ends.tags && enc->cfg.type_vocab < 2) {
+  if (!ends.terms && !ends.tokens && !ends.tags && !ends.sentence && enc->cfg.type_vocab < 2) {
     rf_set_error("%s: the encoder has %d token-type row(s); a pair needs 2", who, enc->cfg.type_vocab);
     return RF_ERR_UNSUPPORTED;
   }
@@ -1613,6 +1613,27 @@ int rf_encode_pairs(const rf_encoder_t* enc, const int32_t* ids_dev, const int32
   const int crc = encode_check(who, enc, B, T, workspace_dev, workspace_bytes);
   if (crc != RF_OK) return crc;
   return encode_enqueue(enc, ids_dev, lens_dev, B, T, nullptr, nullptr, workspace_dev, st, &ends);
+}
+
+// rf_encode with the pooling head of a sentence-transformers directory (sentence_head.hip) where k_pool_norm is
+// launched: the same embedding launch and layer loop, so MEAN + normalize without skip gives rf_encode's bits.
+extern "C" int rf_encode_sentences(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev,
+                                   const int32_t* skip_dev, int B, int T, const rf_sentence_head* head,
+                                   void* out_f16_dev, float* out_f32_dev, void* workspace_dev, size_t workspace_bytes,
+                                   void* stream) {
+  if (!enc || !ids_dev || !lens_dev || !head || !workspace_dev || (!out_f16_dev && !out_f32_dev)) {
+    rf_set_error("rf_encode_sentences: null argument");
+    return RF_ERR_INVALID;
+  }
+  if (head->pooling < RF_POOL_MEAN || head->pooling > RF_POOL_MEAN_SQRT_LEN) {
+    rf_set_error("rf_encode_sentences: pooling=%d is none of RF_POOL_MEAN, _CLS, _MAX, _MEAN_SQRT_LEN", head->pooling);
+    return RF_ERR_INVALID;
+  }
+  rf_sentence_end se{*head, skip_dev, (_Float16*)out_f16_dev, out_f32_dev};
+  rf_pair_ends ends{};
+  ends.sentence = &se;
+  return rf_encode_pairs(enc, ids_dev, lens_dev, B, T, ends, workspace_dev, workspace_bytes, (hipStream_t)stream,
+                         "rf_encode_sentences");
 }
 
 static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const int32_t* lens_dev, int B, int T,
@@ -1627,7 +1648,7 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
   const int32_t* m_ptr = ws.tok_off + B;
 
   if (B > 1) hipLaunchKernelGGL(k_tok_offsets, dim3(1), dim3(256), 0, st, lens_dev, B, T, ws.tok_off);   // B == 1: the embedding launch writes them
-  if (ends && !ends->terms && !ends->tokens && !ends->tags) {
+  if (ends && !ends->terms && !ends->tokens && !ends->tags && !ends->sentence) {
     rf_launch_embed_pair(ids_dev, lens_dev, ends->seg, ws.tok_off, B, T, c, w, ws.x, st);
   } else {
     const int chunks = B * ((T + 31) / 32);   // one workgroup per 32 positions of a row
@@ -1704,6 +1725,9 @@ static int encode_enqueue(const rf_encoder_t* enc, const int32_t* ids_dev, const
     rf_launch_tokens_head(x, ws.tok_off, ids_dev, lens_dev, B, T, *ends->tokens, st);
   else if (ends && ends->tags)
     rf_launch_tags_head(x, ws.tok_off, B, T, *ends->tags, st);
+  else if (ends && ends->sentence)
+    rf_launch_sentence_head(x, ws.tok_off, ends->sentence->skip, B, T, ends->sentence->head, ends->sentence->out16,
+                            ends->sentence->out32, st);
   else if (ends && ends->qa)
     rf_launch_qa_spans(x, ws.tok_off, B, T, *ends, st);
   else if (ends)

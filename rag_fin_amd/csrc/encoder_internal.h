@@ -166,6 +166,7 @@ struct rf_pair_ends {
   const struct rf_terms_end* terms;   // a third pair of ends (splade.hip), or nullptr: see below
   const struct rf_tokens_end* tokens; // a fourth pair of ends (late_interaction.hip), or nullptr: see below
   const struct rf_tags_end* tags;     // a fifth pair of ends (tagger.hip), or nullptr: see below
+  const struct rf_sentence_end* sentence;   // a sixth pair of ends (sentence_head.hip), or nullptr: see below
 };
 void rf_launch_embed_pair(const int32_t* ids, const int32_t* lens, const int32_t* seg, int32_t* tok_off, int B, int T,
                           const rf_encoder_config& c, const rf_encoder_weights& w, _Float16* out, hipStream_t st);
@@ -202,6 +203,18 @@ struct rf_tags_end {
   float* logits;              // [B, T, num_labels]
 };
 void rf_launch_tags_head(const _Float16* x, const int32_t* tok_off, int B, int T, const rf_tags_end& e, hipStream_t st);
+// ---- sentence_head.hip: a sentence forward = rf_encode's launches with another pooling launch at the end ------------
+// With `sentence` set in rf_pair_ends the forward opens with k_embed_ln (token types 0, as for `terms`), runs the
+// layer loop exactly as rf_encode does (the single-query launch included) and closes with k_sentence_head where
+// k_pool_norm is launched otherwise; the other fields are unused.
+struct rf_sentence_end {
+  rf_sentence_head head;      // pooling mode and whether to normalise (host values)
+  const int32_t* skip;        // [B] leading tokens left out of the pooled set, or nullptr: none
+  _Float16* out16;            // [B, 384] or nullptr
+  float* out32;               // [B, 384] or nullptr
+};
+void rf_launch_sentence_head(const _Float16* x, const int32_t* tok_off, const int32_t* skip, int B, int T,
+                             const rf_sentence_head& head, _Float16* out16, float* out32, hipStream_t st);
 const rf_encoder_config& rf_encoder_cfg(const rf_encoder_t* enc);   // encoder.hip
 // encoder.hip: argument checks of rf_encode + the plain launch sequence with `ends` (never a cached hipGraph);
 // `who` names the public entry in the error text

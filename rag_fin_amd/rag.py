@@ -100,10 +100,10 @@ class VectorRAG:
                 for i, h in enumerate(hits)]
 
     @staticmethod
-    def _search_param(min_score, max_score) -> dict:
+    def _search_param(min_score, max_score, metric: str = "COSINE") -> dict:
         """The pymilvus search param: a score cut-off becomes range search (radius = min_score,
         range_filter = max_score; max_score alone: a band with only a ceiling)."""
-        param = {"metric_type": "COSINE"}
+        param = {"metric_type": metric}
         if min_score is not None or max_score is not None:
             param["params"] = {"radius": float("-inf") if min_score is None else min_score}
             if max_score is not None:
@@ -185,7 +185,7 @@ class VectorRAG:
         if hybrid:
             return self._contexts(self._search_hybrid([query], top_k, top_k, expr, fetch_k, lexical)[0])
         q = self._embed([query])
-        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
+        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score, self._metric()), top_k,
                                          expr=expr, output_fields=self.output_fields,
                                          **self._group_args(group_by, group_size),
                                          **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset), **ranker)
@@ -249,8 +249,17 @@ class VectorRAG:
         """`.encode(texts)` of the reference (main.py:50) -- kept on the device when the embedder
         offers it: the unit-norm fp16 rows rf_encode writes are exactly what the store searches
         with, so the download / re-upload / re-normalise round trip of the numpy form is skipped."""
+        # a model with a query prompt ("query: ", an instruction) embeds its queries behind it; the keyword is
+        # absent otherwise, so an embedder with the signature of before is called as before
+        prompt = getattr(self.similarity_model, "query_prompt", None)
+        kw = {"prompt": prompt} if isinstance(prompt, str) and prompt else {}
         to_dev = getattr(self.similarity_model, "encode_to_device", None)
-        return to_dev(texts) if to_dev is not None else self.similarity_model.encode(texts)
+        return to_dev(texts, **kw) if to_dev is not None else self.similarity_model.encode(texts, **kw)
+
+    def _metric(self) -> str:
+        """The metric the store was built for (IP for a dot-product model: service.build_rag); COSINE otherwise."""
+        m = getattr(self.collection, "metric_type", None)
+        return m if isinstance(m, str) and m else "COSINE"
 
     @staticmethod
     def _offset_args(offset) -> dict:
@@ -305,7 +314,7 @@ class VectorRAG:
             raise ValueError(f"hybrid search: fetch_k must be an integer in 1..64, got {fk!r}")
         if not 1 <= limit <= fk:
             raise ValueError(f"hybrid search: need 1 <= top_k <= fetch_k (got top_k = {limit}, fetch_k = {fk})")
-        reqs = [AnnSearchRequest(self._embed(list(queries)), "embedding", {"metric_type": "COSINE"}, fk, expr)]
+        reqs = [AnnSearchRequest(self._embed(list(queries)), "embedding", {"metric_type": self._metric()}, fk, expr)]
         if lexical in ("bm25", "both"):
             reqs.append(AnnSearchRequest(list(queries), "sparse", {"metric_type": "BM25"}, fk, expr))
         if lexical in ("learned", "both"):
@@ -327,7 +336,7 @@ class VectorRAG:
             results = self._search_hybrid(queries, top_k, fk, expr, fk, lexical)
         else:
             q = self._embed(list(queries))
-            results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), fk,
+            results = self.collection.search(q, "embedding", self._search_param(min_score, max_score, self._metric()), fk,
                                              expr=expr, output_fields=self.output_fields)
         hits = [list(r) for r in results]
         if rerank_with == "late":
@@ -398,7 +407,7 @@ class VectorRAG:
         if hybrid:
             return [self._contexts(r) for r in self._search_hybrid(list(queries), top_k, top_k, expr, fetch_k, lexical)]
         q = self._embed(list(queries))
-        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score), top_k,
+        results = self.collection.search(q, "embedding", self._search_param(min_score, max_score, self._metric()), top_k,
                                          expr=expr, output_fields=self.output_fields,
                                          **self._group_args(group_by, group_size),
                                          **self._mmr_args(mmr_lambda, fetch_k), **self._offset_args(offset), **ranker)
@@ -440,7 +449,13 @@ class VectorRAG:
         try:
             n = self.collection.num_entities
             llm = "available" if self.generator is not None else "not configured"
+            m = self.similarity_model
+            # the ends of the embedder's forward, where the embedder states them (rag_fin_amd.embedder.Embedder
+            # does); an embedder that says nothing keeps the reference's keys
+            ends = {} if not hasattr(m, "pooling") else {
+                "pooling": m.pooling, "normalize": bool(getattr(m, "normalize", True)),
+                "prompts": bool(getattr(m, "prompts", None))}
             return {"status": "healthy", "milvus": "in-process MI355X store", "gemini": llm,
-                    "collection": self.collection_name, "total_chunks": n}
+                    "collection": self.collection_name, "total_chunks": n, **ends}
         except Exception as e:
             return {"status": "unhealthy", "error": str(e)}

@@ -2,7 +2,17 @@
 
 Environment (dotenv-style names):
   RAGFIN_MODEL_DIR     local all-MiniLM-L6-v2 directory (config.json, vocab.txt,
-                       model.safetensors).  Required: nothing is fetched by name.
+                       model.safetensors).  Required: nothing is fetched by name.  A sentence-transformers
+                       directory of the same BERT-H384 family (bge-small-en-v1.5, e5-small-v2, gte-small,
+                       multi-qa-MiniLM-L6-dot-v1, snowflake-arctic-embed-s) is read with its own modules.json,
+                       Pooling config and prompts (rag_fin_amd.embedder.sentence_config)
+  RAGFIN_QUERY_PROMPT  the prompt queries are embedded behind ("query: " for E5, which ships none in its files);
+                       overrides the directory's "query" prompt
+  RAGFIN_DOCUMENT_PROMPT  the prompt chunks are embedded behind ("passage: "); overrides the directory's
+                       "document" prompt
+  RAGFIN_POOLING       mean | cls | max | mean_sqrt_len: overrides the directory's Pooling config
+  RAGFIN_METRIC        COSINE | IP (or cosine | dot): the store's metric.  Unset: IP when the model says
+                       similarity_fn_name "dot", COSINE otherwise; euclidean / manhattan are refused
   RERANKER_MODEL_DIR   optional local cross-encoder directory (e.g. ms-marco-MiniLM-L-6-v2, same three
                        files): enables search(..., rerank=True)
   READER_MODEL_DIR     optional local extractive-reader directory (a BertForQuestionAnswering such as
@@ -61,6 +71,46 @@ def extra_columns(fields, chunks, values=None, dynamic: bool = False) -> dict:
     return out
 
 
+def store_metric(embedder, metric: str | None = None) -> str:
+    """The metric_type of the store behind `embedder`: `metric` when given (COSINE | IP, or sentence-transformers'
+    cosine | dot), else IP for a model whose similarity_fn_name is "dot" and COSINE otherwise.  euclidean and
+    manhattan raise ValueError: the store has no L2 metric."""
+    name = metric if metric else (getattr(embedder, "similarity_fn_name", None) or "cosine")
+    key = str(name).strip().lower()
+    if key in ("cosine", "cos_sim"):
+        return "COSINE"
+    if key in ("ip", "dot", "dot_product"):
+        return "IP"
+    if key in ("euclidean", "manhattan", "l2", "l1"):
+        raise ValueError(f"similarity {name!r} is not offered: the store searches by COSINE or IP (there is no L2 metric)")
+    raise ValueError(f"metric must be COSINE or IP, not {name!r}")
+
+
+def load_embedder(model_dir: str, device=None, query_prompt: str | None = None, document_prompt: str | None = None,
+                  pooling: str | None = None):
+    """Embedder.from_local with the overrides build_rag takes: a query / document prompt given here replaces the
+    directory's prompt of that name, the others stay."""
+    from .embedder import Embedder, sentence_config
+    kw = {}
+    if query_prompt or document_prompt:
+        prompts = dict(sentence_config(model_dir)["prompts"])
+        if query_prompt:
+            prompts["query"] = query_prompt
+        if document_prompt:
+            prompts["document"] = document_prompt
+        kw["prompts"] = prompts
+    if pooling:
+        kw["pooling"] = pooling
+    return Embedder.from_local(model_dir, device=device, **kw)
+
+
+def document_prompt_args(embedder) -> dict:
+    """{"prompt": the embedder's document prompt} when it has a non-empty one, else nothing: an embedder with the
+    signature of before is called as before."""
+    p = getattr(embedder, "document_prompt", None)
+    return {"prompt": p} if isinstance(p, str) and p else {}
+
+
 ENTITY_CAPACITY = 16   # max_capacity of the entity field build_rag declares when the caller declared none
 
 
@@ -110,7 +160,7 @@ def ingest(store, embedder, chunks, upsert: bool = False, field_values: dict | N
         if field_values and entity_field in field_values:
             raise ValueError(f"field_values already names {entity_field!r}, the field the tagger fills")
         tagged = entity_column(store, tagger, entity_field, [c["text"] for c in chunks])[0]
-    emb = embedder.encode_to_device([c["text"] for c in chunks])
+    emb = embedder.encode_to_device([c["text"] for c in chunks], **document_prompt_args(embedder))
     cols = chunker.insert_columns(chunks, emb)
     fields = getattr(store, "schema", ())
     dynamic = bool(getattr(store, "enable_dynamic_field", False))
@@ -172,8 +222,11 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
               hybrid: bool = False, reader_dir: str | None = None, reader_doc_stride: int | None = None,
               sparse_dir: str | None = None, late_dir: str | None = None, fields=None, field_values: dict | None = None,
               extra_output_fields=None, enable_dynamic_field: bool = False, tagger_dir: str | None = None,
-              entity_field: str | None = None):
-    """hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
+              entity_field: str | None = None, query_prompt: str | None = None, document_prompt: str | None = None,
+              pooling: str | None = None, metric: str | None = None):
+    """query_prompt / document_prompt / pooling: overrides of what the model directory says (load_embedder).
+    metric: the store's metric_type (store_metric): unset, IP for a model that says similarity_fn_name "dot".
+    hybrid: declare the lexical (BM25) index over the chunk texts, so that search(..., hybrid=True)
     can run; its posting lists are built by the first such search.
     sparse_dir: a local SPLADE checkpoint: the learned sparse field is declared on the store (VectorRAG does
     it), its vectors are encoded by the first search(..., hybrid=True, lexical="learned" | "both").
@@ -187,10 +240,10 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
     declared ARRAY VARCHAR field, or dynamic key, its entities fill at ingest and search(..., match_entities=)
     filters on.  Where `fields` does not declare it and the store is not dynamic, it is declared here as an ARRAY
     of VARCHAR with max_capacity ENTITY_CAPACITY."""
-    from .embedder import Embedder
     from .rag import VectorRAG
     from .store import CorpusStore
-    embedder = Embedder.from_local(model_dir, device=device)
+    embedder = load_embedder(model_dir, device, query_prompt, document_prompt, pooling)
+    metric_type = store_metric(embedder, metric)
     tagger = _load_tagger(tagger_dir, device)
     if tagger is None and entity_field is not None:
         raise ValueError("entity_field needs a tagger (tagger_dir)")
@@ -201,6 +254,7 @@ def build_rag(model_dir: str, data_dir: str = "extract_data", device=None,
         fields = list(fields or ()) + [FieldSchema(tagging["entity_field"], DataType.ARRAY, element_type=DataType.VARCHAR,
                                                    max_capacity=ENTITY_CAPACITY)]
     store = CorpusStore(collection_name, dim=embedder.dim, device=device, **({"fields": fields} if fields else {}),
+                        **({"metric_type": metric_type} if metric_type != "COSINE" else {}),
                         **({"enable_dynamic_field": True} if enable_dynamic_field else {}))
     ingest(store, embedder, chunker.build_all_chunks(data_dir), **({"field_values": field_values} if field_values else {}),
            **tagging)
@@ -223,7 +277,7 @@ def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
     if not chunks:
         return 0
     lo, hi = ShardedSearcher.shard_bounds(len(chunks), store.world, store.rank)
-    emb = embedder.encode_to_device([c["text"] for c in chunks[lo:hi]])
+    emb = embedder.encode_to_device([c["text"] for c in chunks[lo:hi]], **document_prompt_args(embedder))
     cols = chunker.insert_columns(chunks, None)
     if upsert:
         cols[2] = emb
@@ -238,14 +292,14 @@ def ingest_sharded(store, embedder, chunks, upsert: bool = False) -> int:
 def build_sharded_rag(model_dir: str, data_dir: str = "extract_data", local_rank: int = 0,
                       collection_name: str = "fin_chunks", generator=None, backend: str = "nccl",
                       reranker_dir: str | None = None, reader_dir: str | None = None,
-                      reader_doc_stride: int | None = None):
+                      reader_doc_stride: int | None = None, query_prompt: str | None = None,
+                      document_prompt: str | None = None, pooling: str | None = None, metric: str | None = None):
     """One process per GPU (launched by torch.distributed.run): every rank builds an embedder
     replica and its shard of the store.  Returns the VectorRAG on EVERY rank; a serving
     deployment then calls `rag.collection.start_workers()` on all ranks -- rank 0 comes back and
     serves the MCP / REST surface, the others stay inside answering its searches."""
     import torch
     import torch.distributed as dist
-    from .embedder import Embedder
     from .rag import VectorRAG
     from .sharded_store import ShardedCorpusStore
     torch.cuda.set_device(local_rank)
@@ -253,8 +307,10 @@ def build_sharded_rag(model_dir: str, data_dir: str = "extract_data", local_rank
     if not dist.is_initialized():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group(backend, device_id=dev if backend == "nccl" else None)
-    embedder = Embedder.from_local(model_dir, device=dev)
-    store = ShardedCorpusStore(collection_name, dim=embedder.dim, device=dev)
+    embedder = load_embedder(model_dir, dev, query_prompt, document_prompt, pooling)
+    metric_type = store_metric(embedder, metric)
+    store = ShardedCorpusStore(collection_name, dim=embedder.dim, device=dev,
+                               **({"metric_type": metric_type} if metric_type != "COSINE" else {}))
     ingest_sharded(store, embedder, chunker.build_all_chunks(data_dir))
     # (the serving rank reranks; the others only hold a replica like the embedder's)
     return VectorRAG(None, collection_name, embedder=embedder, store=store, generator=generator,
@@ -273,14 +329,18 @@ def build_rag_from_env():
     sparse_dir = os.getenv("SPARSE_MODEL_DIR") or None
     late_dir = os.getenv("COLBERT_MODEL_DIR") or None
     tagger_dir = os.getenv("TAGGER_MODEL_DIR") or None
+    ends = {k: v for k, v in (("query_prompt", os.getenv("RAGFIN_QUERY_PROMPT")),
+                              ("document_prompt", os.getenv("RAGFIN_DOCUMENT_PROMPT")),
+                              ("pooling", os.getenv("RAGFIN_POOLING")), ("metric", os.getenv("RAGFIN_METRIC"))) if v}
     if int(os.getenv("WORLD_SIZE", "1")) > 1:
         return build_sharded_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                                  int(os.getenv("LOCAL_RANK", "0")), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
-                                 reranker_dir=reranker_dir, reader_dir=reader_dir, reader_doc_stride=reader_doc_stride)
+                                 reranker_dir=reranker_dir, reader_dir=reader_dir, reader_doc_stride=reader_doc_stride,
+                                 **ends)
     return build_rag(model_dir, os.getenv("RAGFIN_DATA_DIR", "extract_data"),
                      os.getenv("RAGFIN_DEVICE", "cuda:0"), os.getenv("MILVUS_COLLECTION", "fin_chunks"),
                      reranker_dir=reranker_dir, hybrid=os.getenv("LEXICAL_INDEX", "0") == "1", reader_dir=reader_dir,
                      reader_doc_stride=reader_doc_stride, **({"sparse_dir": sparse_dir} if sparse_dir else {}),
                      **({"late_dir": late_dir} if late_dir else {}),
                      **({"tagger_dir": tagger_dir, "entity_field": os.getenv("TAGGER_FIELD") or "entities"}
-                        if tagger_dir else {}))
+                        if tagger_dir else {}), **ends)
