@@ -44,6 +44,14 @@ RF_ARRAY_MAX_LEAVES = 16     # array leaves one rf_array_match call holds
 RF_ALEAF_LENGTH, RF_ALEAF_ELEM, RF_ALEAF_MATCH = 1, 2, 3
 RF_AELEM_CODE, RF_AELEM_I64, RF_AELEM_F64 = 1, 2, 3
 RF_ARRAY_MAX_ALL = 64        # needles of one ARRAY_CONTAINS_ALL: one bit each of a row's 64-bit slot
+# faceted counts (include/ragfin.h, "faceted counts")
+RF_FACET_MAX_FIELDS = 16     # fields one rf_facet_counts / rf_facet_select call holds
+RF_FACET_LDS_CODES = 4096    # dictionary size up to which a workgroup counts in an LDS histogram
+RF_FACET_MAX_LIMIT = 1000    # bins rf_facet_select returns per field, at most
+RF_FACET_SCALARS = 8         # int64 scalars in front of a field's selected counts and bins
+RF_FACET_MAX_RANGES = 64     # ranges of one rf_facet_ranges call
+RF_FACET_CODES, RF_FACET_ARRAY, RF_FACET_DYNAMIC = 1, 2, 3
+RF_FRANGE_NO_LO, RF_FRANGE_NO_HI, RF_FRANGE_EMPTY = 4, 8, 16
 # lexical index maintenance (include/ragfin.h, "lexical index maintenance")
 RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
 # lexical index build (include/ragfin.h, "lexical index build")
@@ -100,6 +108,18 @@ class ArrayLeaf(Structure):
                 ("offsets_dev", c_void_p), ("values_dev", c_void_p), ("index", c_int64),
                 ("off", c_int64), ("len", c_int64), ("ilo", c_int64), ("ihi", c_int64),
                 ("flo", c_double), ("fhi", c_double)]
+
+
+class FacetField(Structure):
+    """rf_facet_field: one field of a faceted count (a coded column, a CSR array of codes, a dynamic key)."""
+    _fields_ = [("kind", c_int32), ("n_codes", c_int32), ("a_dev", c_void_p), ("b_dev", c_void_p), ("c_dev", c_void_p),
+                ("rank_dev", c_void_p), ("counter_off", c_int64)]
+
+
+class FacetRange(Structure):
+    """rf_facet_range: one [lo, hi) range of rf_facet_ranges."""
+    _fields_ = [("flags", c_int32), ("pad", c_int32), ("ilo", c_int64), ("ihi", c_int64), ("flo", c_double),
+                ("fhi", c_double)]
 
 
 class Postings(Structure):
@@ -263,6 +283,10 @@ SIGNATURES = {
     "rf_column_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_dynamic_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "rf_array_match": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "rf_facet_counts": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int64, c_void_p]),
+    "rf_array_first_occurrence": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "rf_facet_select": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "rf_facet_ranges": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rf_sparse_impacts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,
                                   c_double, c_double, c_void_p, c_void_p]),
     "rf_sparse_append_workspace_bytes": (c_size_t, [c_int64, c_int64]),

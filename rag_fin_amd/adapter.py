@@ -10,6 +10,8 @@ Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
                                                                -> tool search_vectors
   POST /answer     {question: str >= 5 chars, top_k: 1..10 = 3} -> tool answer_question
   GET /stats       -> tool get_collection_stats
+  POST /stats      {expr: str (optional), facet_fields: [str] (optional), facet_limit: 1..1000 = 10}
+                                                               -> tool get_collection_stats (faceted counts; new)
 Transport: JSON-RPC 2.0 over MCP streamable HTTP; one session, initialised on
 first use ("initialize" + "notifications/initialized"); tool calls are streamed
 and the first SSE `data:` line carrying a "result" wins; non-200 -> 503, a
@@ -191,6 +193,28 @@ async def answer(req: AnswerRequest):
 @app.get("/stats")
 async def stats():
     return await mcp.call_tool("get_collection_stats", {})
+
+
+class StatsRequest(BaseModel):
+    # faceted counts: the chunks `expr` matches and their count per value of facet_fields; new
+    expr: Optional[str] = None
+    facet_fields: Optional[list[str]] = Field(default=None, max_length=16)
+    facet_limit: int = Field(default=10, ge=1, le=1000)
+
+
+def stats_args(req: StatsRequest) -> dict:
+    """Tool arguments of POST /stats: only what was given, so an empty body is the call of GET /stats."""
+    args = {}
+    if req.expr is not None:
+        args["expr"] = req.expr
+    if req.facet_fields:
+        args["facet_fields"], args["facet_limit"] = list(req.facet_fields), req.facet_limit
+    return args
+
+
+@app.post("/stats")
+async def stats_faceted(req: StatsRequest):
+    return await mcp.call_tool("get_collection_stats", stats_args(req))
 
 
 def main() -> None:

@@ -1539,6 +1539,74 @@ def array_match(device, program: "filter_expr.Program", columns: dict, n_rows: i
     return out
 
 
+def array_first_occurrence(device, offsets, values, row_lo: int, row_hi: int, flags) -> None:
+    """rf_array_first_occurrence over rows [row_lo, row_hi) of a CSR mirror of int32 codes, enqueued on the current
+    stream: flags (uint8, one per element) gets 1 where no earlier element of the row holds the same code."""
+    torch = _torch()
+    lib = _lib.load_library()
+    if row_hi == row_lo or not values.numel():
+        return
+    with torch.cuda.device(device):
+        _lib.check(lib.rf_array_first_occurrence(_ptr(offsets), _ptr(values), row_lo, row_hi, _ptr(flags),
+                                                 _lib.current_stream_ptr()))
+
+
+def facet_counts(device, filt, specs: list, n_rows: int, limit: int, min_count: int) -> np.ndarray:
+    """rf_facet_counts + rf_facet_select of one facets() call: one launch each for all fields, on the current
+    stream, then ONE download.  filt: a filter buffer for n_rows rows, or None (every row).  specs: per field
+    {"kind": RF_FACET_*, "n_codes": dictionary size, "a" / "b" / "c": the device tensors rf_facet_field names (None
+    where unused), "rank": int32 device tensor [n_bins]}.  -> int64 [len(specs), RF_FACET_SCALARS + 2 * limit]:
+    per field the scalars {selected, distinct, selected sum, missing, sum of all bins, ...}, the selected counts and
+    their bin numbers, best first.  Buffers are allocated per call."""
+    torch = _torch()
+    lib = _lib.load_library()
+    F = len(specs)
+    if not 1 <= F <= _lib.RF_FACET_MAX_FIELDS:
+        raise ValueError(f"facet_counts: 1..{_lib.RF_FACET_MAX_FIELDS} fields per call, got {F}")
+    arr = (_lib.FacetField * F)()
+    with torch.cuda.device(device):
+        n_counters = 0
+        for i, s in enumerate(specs):
+            n_bins = s["n_codes"] + (2 if s["kind"] == _lib.RF_FACET_DYNAMIC else 0)
+            if s["rank"].numel() != n_bins or s["rank"].dtype != torch.int32 or not s["rank"].is_contiguous():
+                raise ValueError(f"facet_counts: field {i}: rank must be a contiguous int32 tensor of {n_bins} bins")
+            arr[i].kind, arr[i].n_codes, arr[i].counter_off = s["kind"], s["n_codes"], n_counters
+            a, b, c = s.get("a"), s.get("b"), s.get("c")
+            arr[i].a_dev = a.data_ptr() if a is not None else None
+            # (an ARRAY field whose rows are all empty has no element to point at: its offsets stand in, none is read)
+            arr[i].b_dev = None if b is None else (b.data_ptr() if b.numel() else a.data_ptr())
+            arr[i].c_dev = None if c is None else (c.data_ptr() if c.numel() else a.data_ptr())
+            arr[i].rank_dev = s["rank"].data_ptr() if n_bins else None
+            n_counters += n_bins + 1
+        counters = torch.empty(n_counters, dtype=torch.int64, device=device)
+        out = torch.empty((F, _lib.RF_FACET_SCALARS + 2 * limit), dtype=torch.int64, device=device)
+        st = _lib.current_stream_ptr()
+        _lib.check(lib.rf_facet_counts(_ptr(filt), arr, F, n_rows, _ptr(counters), n_counters, st))
+        _lib.check(lib.rf_facet_select(arr, F, _ptr(counters), n_counters, limit, min_count, _ptr(out), st))
+        return out.cpu().numpy()
+
+
+def facet_ranges(device, filt, column, is_f64: bool, bounds: list, n_rows: int) -> np.ndarray:
+    """rf_facet_ranges of one numeric column (int64 or fp64 device tensor [n_rows]) on the current stream.  bounds:
+    per range (no_lo, no_hi, empty, lo, hi), lo / hi ints for an int64 column and floats for an fp64 one.
+    -> int64 [RF_FACET_MAX_RANGES + 4]: the range counts, then {NaN rows, non-NaN rows, min bits, max bits}."""
+    torch = _torch()
+    lib = _lib.load_library()
+    arr = (_lib.FacetRange * len(bounds))()
+    for i, (no_lo, no_hi, empty, lo, hi) in enumerate(bounds):
+        arr[i].flags = (_lib.RF_FRANGE_NO_LO if no_lo else 0) | (_lib.RF_FRANGE_NO_HI if no_hi else 0) | \
+            (_lib.RF_FRANGE_EMPTY if empty else 0)
+        if is_f64:
+            arr[i].flo, arr[i].fhi = lo, hi
+        else:
+            arr[i].ilo, arr[i].ihi = lo, hi
+    with torch.cuda.device(device):
+        out = torch.empty(_lib.RF_FACET_MAX_RANGES + 4, dtype=torch.int64, device=device)
+        _lib.check(lib.rf_facet_ranges(_ptr(filt), _ptr(column), 1 if is_f64 else 0, arr, len(bounds), n_rows, _ptr(out),
+                                       _lib.current_stream_ptr()))
+        return out.cpu().numpy()
+
+
 def eval_filter(device, program: "filter_expr.Program", columns, n_rows: int, bitmaps=None, column_base: int = 0):
     """rf_filter_eval of a compiled program into a fresh filter buffer (uint8 device tensor of
     rf_filter_bytes(n_rows)), enqueued on the current stream.  columns: the device tensors

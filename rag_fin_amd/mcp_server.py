@@ -194,12 +194,22 @@ def answer_question(question: str, top_k: int = 3, min_score: float | None = Non
         return {"status": "error", "message": str(e), "question": question}
 
 
-def get_collection_stats():
-    """Get collection statistics"""
+def get_collection_stats(expr: str | None = None, facet_fields: list | None = None, facet_limit: int = 10):
+    """Get collection statistics.  expr and / or facet_fields: also "count", the chunks `expr` matches (all
+    without one), and "facets", their count per value of each of facet_fields (the best facet_limit values)."""
     try:
-        return {"status": "success", "collection_name": COLLECTION_NAME,
-                "total_chunks": get_rag().collection.num_entities,
-                "milvus_host": MILVUS_HOST, "milvus_port": MILVUS_PORT}
+        out = {"status": "success", "collection_name": COLLECTION_NAME,
+               "total_chunks": get_rag().collection.num_entities,
+               "milvus_host": MILVUS_HOST, "milvus_port": MILVUS_PORT}
+        if expr is not None or facet_fields:
+            expr = expr if expr and expr.strip() else None
+            if facet_fields:
+                got = get_rag().facets(list(facet_fields), expr=expr, limit=facet_limit)
+                out["count"], out["facets"] = got["count"], got["facets"]
+            else:
+                out["count"] = get_rag().collection.query(expr or "", output_fields=["count(*)"])[0]["count(*)"]
+                out["facets"] = {}
+        return out
     except Exception as e:
         return {"status": "error", "message": str(e)}
 

@@ -337,6 +337,16 @@ class ShardedCorpusStore(CorpusStore):
     def hybrid_search(self, reqs, rerank, limit: int = 10, output_fields=None):
         raise NotImplementedError("hybrid search (hybrid_search) is not implemented for the sharded store")
 
+    def facets(self, *args, **kwargs):
+        raise NotImplementedError("faceted counts are not implemented for the sharded store")
+
+    def _count(self, expr) -> int:
+        # count(*): '' and 'id in [...]' are served from the replicated columns; any other expression is
+        # refused as query refuses it
+        if not filter_expr.is_empty(expr) and _id_in_keys(expr) is None:
+            self._expr_rows(expr)
+        return super()._count(expr)
+
     def _expr_rows(self, expr):
         raise NotImplementedError(f"query expression {expr!r}: the sharded store supports '' and 'id in [...]' only")
 

@@ -41,7 +41,8 @@ from . import schema as schema_
 from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
-from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, array_match, boost_classes, column_match, dynamic_match,  # noqa: F401
+from . import facets as facets_
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, array_first_occurrence, array_match, facet_counts, facet_ranges, boost_classes, column_match, dynamic_match,  # noqa: F401
                     decay_weights, eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
                     plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
 from .ranker import BoostRanker, DecayRanker, check_rankers, class_weights  # noqa: F401
@@ -163,6 +164,9 @@ class _DeviceColumns:
         self.codes = {f: torch.empty(0, dtype=torch.int32, device=device) for f in filter_expr.VARCHAR_FIELDS}
         self.values = torch.empty(0, dtype=torch.float64, device=device)
         self.n = 0
+        # faceted counts: {key: (dictionary length, int32 value ranks on the device)} (CorpusStore._facet_rank).  The
+        # dictionaries are append-only, so the same length means the same content and a kept rank stays right.
+        self.facet_ranks: dict = {}
 
     def sync(self, columns: dict, n: int) -> None:
         torch = _torch()
@@ -214,6 +218,9 @@ class _ExtraColumn:
         self._code: dict = {}
         self.data = torch.empty(0, dtype=getattr(torch, np.dtype(self.np_dtype).name), device=device)
         self.n = 0
+        # faceted counts: {key: (dictionary length, int32 value ranks on the device)} (CorpusStore._facet_rank).  The
+        # dictionaries are append-only, so the same length means the same content and a kept rank stays right.
+        self.facet_ranks: dict = {}
 
     def sync(self, values: list, n: int) -> None:
         torch = _torch()
@@ -259,12 +266,34 @@ class _ArrayColumn:
         self.values = torch.empty(0, dtype=getattr(torch, np.dtype(self.np_dtype).name), device=device)
         self.n = 0
         self.nnz = 0   # elements mirrored: the last offset, kept on the host
+        # faceted counts: one byte per element, 1 where no earlier element of its row holds the same
+        # code, for the elements of the first `first_n` rows; None until a facet reads the field
+        self.first = None
+        self.first_n = 0
+        # faceted counts: {key: (dictionary length, int32 value ranks on the device)} (CorpusStore._facet_rank).  The
+        # dictionaries are append-only, so the same length means the same content and a kept rank stays right.
+        self.facet_ranks: dict = {}
+
+    def first_occurrence(self):
+        """The first-occurrence bytes of every mirrored element (coded fields): rf_array_first_occurrence over the
+        rows appended since the last call, so a row is scanned for duplicates once, never per facet call."""
+        torch = _torch()
+        if self.first is None or self.first_n < self.n:
+            full = torch.empty(self.nnz, dtype=torch.uint8, device=self.device)
+            if self.first is not None:
+                full[:self.first.numel()] = self.first
+            else:
+                self.first_n = 0
+            array_first_occurrence(self.device, self.offsets, self.values, self.first_n, self.n, full)
+            self.first, self.first_n = full, self.n
+        return self.first
 
     def sync(self, rows: list, n: int) -> None:
         torch = _torch()
         if n < self.n:   # a shorter collection: re-encode from row 0 (the dictionary stays)
             self.offsets, self.values = self.offsets[:1], self.values[:0]
             self.n = self.nnz = 0
+            self.first, self.first_n = None, 0
         if n == self.n:
             return
         lens, enc = filter_expr.encode_array(rows[self.n:n], self.np_dtype, self._code if self.coded else None, self.dict)
@@ -285,8 +314,12 @@ class _ArrayColumn:
         src = torch.repeat_interleave(starts - (ends - lens), lens, output_size=self.nnz) + \
             torch.arange(self.nnz, dtype=torch.int64, device=self.device)
         self.values = self.values.index_select(0, src)
+        # (a row's content never changes in place: the bytes of the surviving rows' elements stay valid)
+        whole = self.first is not None and self.first_n == self.n
+        self.first = self.first.index_select(0, src) if whole else None
         self.offsets = torch.cat([self.offsets[:1], ends])
         self.n = int(k.numel())
+        self.first_n = self.n if whole else 0
 
 
 class _DynamicColumn:
@@ -302,6 +335,9 @@ class _DynamicColumn:
         self.tags = torch.empty(0, dtype=torch.uint8, device=device)
         self.payload = torch.empty(0, dtype=torch.int64, device=device)
         self.n = 0
+        # faceted counts: {key: (dictionary length, int32 value ranks on the device)} (CorpusStore._facet_rank).  The
+        # dictionaries are append-only, so the same length means the same content and a kept rank stays right.
+        self.facet_ranks: dict = {}
 
     def sync(self, values: list, n: int) -> None:
         torch = _torch()
@@ -1790,12 +1826,165 @@ class CorpusStore:
         """`query(expr="id in [...]")` fetch-by-PK (key order), `query(expr="", limit=n)` scan, and
         any other filter expression (rag_fin_amd.filter_expr): the matching rows in ascending
         row order.  offset (an int >= 0, else ValueError): skip that many of the matching rows
-        first, on the host; `limit` counts from there."""
+        first, on the host; `limit` counts from there.
+        output_fields=["count(*)"] (pymilvus' idiom) returns [{"count(*)": n}], the number of rows `expr` matches:
+        num_entities for an empty expr, the keys present for `id in [...]`, else n_pass_rows of the filter
+        buffer's header -- no row is fetched.  count(*) beside other fields, `limit` or `offset` raises ValueError."""
         if expr is not None and not isinstance(expr, str):
             raise ValueError(f"filter expression must be a string, got {type(expr).__name__}")
+        if not isinstance(output_fields, str) and output_fields is not None:
+            output_fields = list(output_fields)
+            if facets_.COUNT_STAR in output_fields:
+                if len(output_fields) != 1:
+                    raise ValueError("query: count(*) cannot be combined with other output_fields")
+                if limit is not None:
+                    raise ValueError("query: count(*) cannot be combined with limit")
+                if offset:
+                    raise ValueError("query: count(*) cannot be combined with offset")
+                with self._rw.read():
+                    return [{facets_.COUNT_STAR: self._count(expr)}]
         offset = check_offset(offset, None, 1)
         with self._rw.read():
             return self._query(expr, limit, output_fields, offset)
+
+    def _count(self, expr) -> int:
+        """The rows `expr` matches.  Caller holds the read lock."""
+        if filter_expr.is_empty(expr):
+            return self.num_entities
+        keys = _id_in_keys(expr)
+        if keys is not None:
+            return len({k for k in keys if k in self._pk_row})
+        if self.num_entities == 0:
+            return int(self._match_mask(expr).sum())   # (still rejects a bad expression)
+        return self._filter_header(self.build_filter(expr))[1]
+
+    @staticmethod
+    def _filter_header(filt) -> tuple:
+        """(n_rows, n_pass_rows, n_pass_blocks, n_tiles) of a filter buffer (synchronises)."""
+        return tuple(int(v) for v in filt[:16].cpu().numpy().view(np.uint32))
+
+    # -- faceted counts (rag_fin_amd/facets.py; DESIGN §4.4t) ---------------------------------------
+    def facets(self, fields=None, expr: str | None = None, limit: int = 10, min_count: int = 1, ranges=None) -> dict:
+        """How many of the rows `expr` passes (every row without one; anything a filter takes) hold each value of
+        `fields`, and how many fall into each of `ranges` -- facets.py has the definition, facets_reference:
+            {"count": passing rows,
+             "facets": {field: {"buckets": [{"value", "count"}, ...], "distinct", "missing", "other"}},
+             "ranges": {field: {"ranges": [{"from", "to", "count"}, ...], "min", "max", "nan"}}}
+        fields: period / chunk_type / statement_type, the collection's VARCHAR / BOOL / INT64 fields, its ARRAY
+        fields of VARCHAR or BOOL elements (a row counts once per distinct element) and dynamic keys (bare or
+        $meta["key"]).  ranges: {field: [(lo, hi), ...]}, each [lo, hi) with None for no bound, over primary_value
+        and INT64 / DOUBLE fields.  Counted on the GPU from the columns' dictionary codes (rf_facet_counts,
+        rf_facet_select, rf_facet_ranges); exact and the same on every run.  ValueError on a bad argument."""
+        fields, limit, min_count, ranges = facets_.check_args(fields, limit, min_count, ranges)
+        if expr is not None and not isinstance(expr, str):
+            raise ValueError(f"filter expression must be a string, got {type(expr).__name__}")
+        plan = [(name,) + facets_.resolve_value_field(name, self.schema, self.enable_dynamic_field) for name in fields]
+        rplan = [(name,) + facets_.resolve_range_field(name, self.schema) for name in ranges]
+        with self._rw.read():
+            n = self.num_entities
+            if n == 0:   # nothing to count (a bad expression is still rejected)
+                if not filter_expr.is_empty(expr):
+                    self._match_mask(expr)
+                return facets_.facets_reference(self.columns, self.schema, self.dynamic if self.enable_dynamic_field
+                                                else None, fields, [], limit, min_count, ranges)
+            filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
+            return self._facets(plan, rplan, ranges, filt, n, limit, min_count)
+
+    def _facet_rank(self, holder, key, vals: list, dynamic: bool):
+        """The value rank of every bin of a dictionary (facets.value_ranks; a dynamic key's False and True behind
+        its strings) as an int32 device tensor, kept beside the mirror and derived again when the dictionary has
+        grown.  Caller holds `_filter_lock`."""
+        cache = holder.facet_ranks
+        hit = cache.get(key)
+        if hit is None or hit[0] != len(vals):
+            rank = facets_.value_ranks(vals + [False, True] if dynamic else vals)
+            hit = cache[key] = (len(vals), _torch().from_numpy(rank).to(self.index.device))
+        return hit[1]
+
+    def _facets(self, plan, rplan, ranges, filt, n: int, limit: int, min_count: int) -> dict:
+        """facets() on the device.  Caller holds the read lock.  The columns are mirrored under `_filter_lock` (after
+        build_filter has released it: the lock order of build_filter holds), which is held only until the call has
+        its references: a sync or a compaction replaces a mirror's tensors and never writes into them, and the read
+        lock keeps the rows as they are, so the kernels and their downloads run outside it and concurrent filter
+        builds do not wait for them."""
+        dev = self.index.device
+        out = {"count": n, "facets": {}, "ranges": {}}
+        with self._filter_lock:
+            specs, values = [], []
+            for name, kind, what in plan:
+                if kind == "builtin":
+                    if self._dcols is None:
+                        self._dcols = _DeviceColumns(dev)
+                    self._dcols.sync(self.columns, n)
+                    vals, holder = self._dcols.dicts[what], (self._dcols, what)
+                    spec = {"kind": _lib.RF_FACET_CODES, "a": self._dcols.codes[what].contiguous()}
+                elif kind == "own":
+                    col = self._extra_column(what, coded=True)
+                    vals, holder = col.dict, (col, None)
+                    spec = {"kind": _lib.RF_FACET_CODES, "a": col.data.contiguous()}
+                elif kind == "array":
+                    col = self._array_column(what)
+                    vals, holder = col.dict, (col, None)
+                    spec = {"kind": _lib.RF_FACET_ARRAY, "a": col.offsets, "b": col.values, "c": col.first_occurrence()}
+                elif what in self.dynamic:
+                    col = self._dynamic_column(what)
+                    vals, holder = col.dict, (col, None)
+                    spec = {"kind": _lib.RF_FACET_DYNAMIC, "a": col.tags, "b": col.payload}
+                else:   # a key no row holds: every passing row is `missing`
+                    specs.append(None)
+                    values.append(None)
+                    continue
+                # (a dictionary only grows, and under this lock: the first n_codes entries are what the codes mean)
+                spec["n_codes"] = len(vals)
+                spec["rank"] = self._facet_rank(*holder, vals, spec["kind"] == _lib.RF_FACET_DYNAMIC)
+                specs.append(spec)
+                values.append(vals)
+            rcols = []
+            for name, kind, colname in rplan:
+                if colname == "primary_value":
+                    if self._dcols is None:
+                        self._dcols = _DeviceColumns(dev)
+                    self._dcols.sync(self.columns, n)
+                    column = self._dcols.values
+                else:
+                    column = self._extra_column(self._field(colname)).data
+                rcols.append(column.contiguous())
+        live = [s for s in specs if s is not None]
+        got = iter(facet_counts(dev, filt, live, n, limit, min_count)) if live else iter(())
+        rgot = []
+        for (name, kind, colname), column in zip(rplan, rcols):
+            bounds = []
+            for lo, hi in ranges[name]:
+                if kind == "i64":
+                    bounds.append(facets_.int_bounds(lo, hi))
+                else:
+                    no_lo, no_hi, flo, fhi = facets_.float_bounds(lo, hi)
+                    bounds.append((no_lo, no_hi, False, flo, fhi))
+            rgot.append(facet_ranges(dev, filt, column, kind == "f64", bounds, n))
+        if filt is not None:
+            out["count"] = self._filter_header(filt)[1]
+        S = _lib.RF_FACET_SCALARS
+        for (name, _, _), spec, vals in zip(plan, specs, values):
+            if spec is None:
+                out["facets"][name] = {"buckets": [], "distinct": 0, "missing": out["count"], "other": 0}
+                continue
+            row = next(got)
+            sel, distinct, sel_sum, missing, total = (int(v) for v in row[:5])
+            out["facets"][name] = {
+                # (a dynamic key's bins n_codes and n_codes + 1 are False and True)
+                "buckets": [{"value": vals[int(b)] if b < spec["n_codes"] else bool(b - spec["n_codes"]), "count": int(c)}
+                            for c, b in zip(row[S:S + sel], row[S + limit:S + limit + sel])],
+                "distinct": distinct, "missing": missing, "other": total - sel_sum}
+        for (name, kind, _), r in zip(rplan, rgot):
+            M = _lib.RF_FACET_MAX_RANGES
+            any_valid = int(r[M + 1]) > 0
+            ext = r[M + 2:M + 4]
+            lo_hi = [None, None] if not any_valid else \
+                ([int(v) for v in ext] if kind == "i64" else [float(v) for v in ext.view(np.float64)])
+            out["ranges"][name] = {
+                "ranges": [{"from": lo, "to": hi, "count": int(c)} for (lo, hi), c in zip(ranges[name], r[:M])],
+                "min": lo_hi[0], "max": lo_hi[1], "nan": int(r[M])}
+        return out
 
     def _query(self, expr, limit, output_fields, offset: int = 0) -> list[dict]:
         fields = list(output_fields or ["id"])
