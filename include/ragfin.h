@@ -1567,6 +1567,75 @@ int rf_facet_select(const rf_facet_field* fields_host, int n_fields, const int64
 int rf_facet_ranges(const void* filter_dev, const void* column_dev, int is_f64, const rf_facet_range* ranges_host,
                     int n_ranges, int64_t n_rows, int64_t* out_dev, void* stream);
 
+/* ---- metric aggregations: exact sum, count, min, max of numeric columns per facet bucket -----------
+ * Collection.facets(..., metrics=[...]) and query(expr, ["sum(f)", ...]): for up to RF_STATS_MAX_METRICS
+ * numeric columns (rf_stats_metric, HOST memory: column_dev int64 or fp64 [n_rows], is_f64) the count, the
+ * NaN count, the EXACT sum, the minimum and the maximum over the units of every bucket rf_facet_select
+ * selected, and over all passing rows (the definition: rag_fin_amd/facets.py,
+ * stats_reference).  An fp64 sum is the exact sum of the finite values rounded ONCE to the nearest double,
+ * ties to even (what math.fsum returns): a finite double is M * 2^(p - 1074) with a 53-bit M, so the value
+ * is added, as three pieces below 2^32 of M << (p & 31), into limbs p >> 5, + 1, + 2 of a fixed-point
+ * accumulator of 66 limbs (limb j weighs 2^(32 j - 1074)) kept in int64 words; integer adds commute, so the
+ * accumulator -- and the result -- has the same bits on every run, whatever the grid, the filter or the
+ * arrival order.  An int64 value adds its low 32 bits (unsigned) to limb 0 and its high 32 bits (signed) to
+ * limb 1.  There is no float atomic anywhere.  All calls are stream-ordered, allocate nothing and do not
+ * synchronise; RF_ERR_INVALID comes from host-side checks before any device call.
+ *
+ * Records.  One record of RF_STATS_WORDS int64 words per (field, selected bucket, metric): 66 limbs, then
+ * { count (non-NaN values), nan, +inf values, -inf values, min, max } -- min as the largest complement of
+ * the order-preserving key of rf_facet_ranges, max as the largest key, so that a zeroed record is the
+ * identity of both.  Field f has n_slots = min(limit, n_bins) slots; its records start at record
+ * n_metrics * (the slots of the fields before it), record (slot, metric) at slot * n_metrics + metric;
+ * behind the last field come the n_metrics records of the one-slot group of ALL passing rows.
+ * rf_facet_stats_records returns the record count of a call (-1 on a bad argument).
+ * Limits: n_rows <= 2^31 - 1 (a limb takes one piece below 2^32 per value, so it stays inside an int64 for
+ * fewer than 2^31 values; a larger n_rows is RF_ERR_INVALID), n_metrics in 1..RF_STATS_MAX_METRICS,
+ * n_fields in 0..RF_FACET_MAX_FIELDS (0: the all-rows group alone -- no value field, no select),
+ * limit in 1..RF_FACET_MAX_LIMIT.
+ *
+ * rf_facet_stats_slots: select_dev is rf_facet_select's out_dev, still on the device (no host round
+ * trip); slot_of_dev int32 [n_counters], laid out as the counters are: slot_of[counter_off + bin] = the
+ * position of the bin among the field's selected buckets, -1 for every other bin.
+ *
+ * rf_facet_stats: ONE launch for all fields and metrics, grid (workgroups, n_fields + 1); the last column
+ * is the all-rows group.  It walks the filter's passing 32-row blocks with the code of rf_facet_counts:
+ * the same units (a passing row of a CODES / DYNAMIC field; a passing row and DISTINCT element of an ARRAY
+ * field, by the first-occurrence flags and the owner search), maps bin -> slot, skips -1 and `missing`,
+ * and per metric classifies the row's value as NaN (counted in nan, nothing else), +-inf (counted, min /
+ * max, its own counter) or finite (counted, min / max, three limb adds).  64-bit integer atomics only:
+ * into a workgroup-private LDS copy of the field's records when n_slots * n_metrics <=
+ * RF_STATS_LDS_RECORDS (36 KiB), flushed with one global add / max per non-zero word; straight into
+ * acc_dev beyond that.  The call zeroes acc_dev[0 .. n_records * RF_STATS_WORDS) first.  grid: workgroups
+ * per column, 0 for the default (tests compare grids: the result does not depend on it).
+ *
+ * rf_facet_stats_finish: one lane per record.  It propagates the carries through the limbs into sign and
+ * magnitude, finds the top bit, takes 53 bits with guard and sticky, rounds to nearest even (below 2^-1022
+ * nothing is rounded: every sum is a multiple of 2^-1074), maps overflow to +-inf, and applies the inf
+ * rule: NaN when +inf and -inf both occur, that infinity when one does.  An exact zero is +0.0.  The
+ * routine is csrc/exact_sum.h, which a host test compiles too.  out_dev int64 [n_records][RF_STATS_OUT]:
+ * { count, nan, the sum's bits, 0, min, max, 0, 0 } for an fp64 metric (min / max as the values' bits),
+ * { count, 0, limb 0, limb 1, min, max, 0, 0 } for an int64 one: the exact sum is limb 0 + limb 1 * 2^32,
+ * formed on the host, since it may exceed 64 bits.  min / max are undefined when count is 0.  The
+ * records' limbs are consumed.  Only out_dev is downloaded.
+ * New in this build; the reference sums on the host, in row order. */
+#define RF_STATS_MAX_METRICS 4
+#define RF_STATS_WORDS 72
+#define RF_STATS_OUT 8
+#define RF_STATS_LDS_RECORDS 64
+typedef struct rf_stats_metric {
+  const void* column_dev;   /* int64 or fp64 [n_rows] */
+  int32_t is_f64;
+  int32_t pad;
+} rf_stats_metric;
+int64_t rf_facet_stats_records(const rf_facet_field* fields_host, int n_fields, int n_metrics, int limit);
+int rf_facet_stats_slots(const rf_facet_field* fields_host, int n_fields, const int64_t* select_dev, int limit,
+                         int32_t* slot_of_dev, int64_t n_counters, void* stream);
+int rf_facet_stats(const void* filter_dev, const rf_facet_field* fields_host, int n_fields,
+                   const rf_stats_metric* metrics_host, int n_metrics, const int32_t* slot_of_dev, int64_t n_counters,
+                   int limit, int64_t n_rows, int64_t* acc_dev, int64_t n_records, int grid, void* stream);
+int rf_facet_stats_finish(int64_t* acc_dev, const rf_stats_metric* metrics_host, int n_metrics, int64_t n_records,
+                          int64_t* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,11 @@ RF_FACET_SCALARS = 8         # int64 scalars in front of a field's selected coun
 RF_FACET_MAX_RANGES = 64     # ranges of one rf_facet_ranges call
 RF_FACET_CODES, RF_FACET_ARRAY, RF_FACET_DYNAMIC = 1, 2, 3
 RF_FRANGE_NO_LO, RF_FRANGE_NO_HI, RF_FRANGE_EMPTY = 4, 8, 16
+# metric aggregations (include/ragfin.h, "metric aggregations")
+RF_STATS_MAX_METRICS = 4     # metric columns of one rf_facet_stats call
+RF_STATS_WORDS = 72          # int64 words of an accumulator record: 66 limbs, count, nan, +inf, -inf, min, max
+RF_STATS_OUT = 8             # int64 words of a finished record
+RF_STATS_LDS_RECORDS = 64    # records of a field up to which a workgroup accumulates in LDS
 # lexical index maintenance (include/ragfin.h, "lexical index maintenance")
 RF_LEX_CHUNK = 1024          # postings per workgroup, and the tile of the second level of the prefix sum
 # lexical index build (include/ragfin.h, "lexical index build")
@@ -114,6 +119,11 @@ class FacetField(Structure):
     """rf_facet_field: one field of a faceted count (a coded column, a CSR array of codes, a dynamic key)."""
     _fields_ = [("kind", c_int32), ("n_codes", c_int32), ("a_dev", c_void_p), ("b_dev", c_void_p), ("c_dev", c_void_p),
                 ("rank_dev", c_void_p), ("counter_off", c_int64)]
+
+
+class StatsMetric(Structure):
+    """rf_stats_metric: one numeric column of a metric aggregation."""
+    _fields_ = [("column_dev", c_void_p), ("is_f64", c_int32), ("pad", c_int32)]
 
 
 class FacetRange(Structure):
@@ -287,6 +297,11 @@ SIGNATURES = {
     "rf_array_first_occurrence": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "rf_facet_select": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "rf_facet_ranges": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "rf_facet_stats_records": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "rf_facet_stats_slots": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "rf_facet_stats": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p,
+                               c_int64, c_int, c_void_p]),
+    "rf_facet_stats_finish": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "rf_sparse_impacts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double,
                                   c_double, c_double, c_void_p, c_void_p]),
     "rf_sparse_append_workspace_bytes": (c_size_t, [c_int64, c_int64]),

@@ -10,8 +10,10 @@ Same routes, request bounds and error mapping as adapters/vectorrag_adapter.py:
                                                                -> tool search_vectors
   POST /answer     {question: str >= 5 chars, top_k: 1..10 = 3} -> tool answer_question
   GET /stats       -> tool get_collection_stats
-  POST /stats      {expr: str (optional), facet_fields: [str] (optional), facet_limit: 1..1000 = 10}
-                                                               -> tool get_collection_stats (faceted counts; new)
+  POST /stats      {expr: str (optional), facet_fields: [str] (optional), facet_limit: 1..1000 = 10,
+                    metric_fields: [str] (optional, at most 4)}
+                                                               -> tool get_collection_stats (faceted counts and
+                                                                  metric aggregations; new)
 Transport: JSON-RPC 2.0 over MCP streamable HTTP; one session, initialised on
 first use ("initialize" + "notifications/initialized"); tool calls are streamed
 and the first SSE `data:` line carrying a "result" wins; non-200 -> 503, a
@@ -200,6 +202,8 @@ class StatsRequest(BaseModel):
     expr: Optional[str] = None
     facet_fields: Optional[list[str]] = Field(default=None, max_length=16)
     facet_limit: int = Field(default=10, ge=1, le=1000)
+    # metric aggregations: the exact sum / avg / min / max of numeric fields, per bucket and over all matches; new
+    metric_fields: Optional[list[str]] = Field(default=None, max_length=4)
 
 
 def stats_args(req: StatsRequest) -> dict:
@@ -209,6 +213,8 @@ def stats_args(req: StatsRequest) -> dict:
         args["expr"] = req.expr
     if req.facet_fields:
         args["facet_fields"], args["facet_limit"] = list(req.facet_fields), req.facet_limit
+    if req.metric_fields:
+        args["metric_fields"] = list(req.metric_fields)
     return args
 
 

@@ -28,7 +28,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_NAME = "libragfin_hip.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 EXP_LIB_PATH = os.path.join(CSRC, "libragfin_hip_exp.so")
-SOURCES = ["index.hip", "scan.hip", "scan_wide.hip", "merge.hip", "grouped.hip", "mmr.hip", "sparse.hip", "text_match.hip", "column_match.hip", "dynamic_match.hip", "array_match.hip", "facets.hip", "lexical_update.hip", "lexical_build.hip", "filter.hip", "boost.hip", "decay.hip", "api.hip", "sq8.hip", "shadow_refine.hip", "comm.hip", "encoder.hip", "encoder_post.hip", "rerank.hip", "reader.hip", "reader_windows.hip", "splade.hip", "late_interaction.hip", "tagger.hip", "sentence_head.hip", "tokenizer.cpp", "analyzer.cpp"]
+SOURCES = ["index.hip", "scan.hip", "scan_wide.hip", "merge.hip", "grouped.hip", "mmr.hip", "sparse.hip", "text_match.hip", "column_match.hip", "dynamic_match.hip", "array_match.hip", "facets.hip", "facet_stats.hip", "lexical_update.hip", "lexical_build.hip", "filter.hip", "boost.hip", "decay.hip", "api.hip", "sq8.hip", "shadow_refine.hip", "comm.hip", "encoder.hip", "encoder_post.hip", "rerank.hip", "reader.hip", "reader_windows.hip", "splade.hip", "late_interaction.hip", "tagger.hip", "sentence_head.hip", "tokenizer.cpp", "analyzer.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

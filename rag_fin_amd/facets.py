@@ -31,7 +31,22 @@ counted on its own.  The result is
     {"ranges": [{"from": lo, "to": hi, "count": c}, ...], "min": x, "max": y, "nan": n}
 min / max over the passing non-NaN values (None when there is none).  DOUBLE compares as IEEE doubles: a NaN
 falls in no range and is counted in "nan".  INT64 compares as integers, never through a double (a bound of any
-size, or a float, is compared mathematically).  There is no sum or mean: a floating sum depends on its order.
+size, or a float, is compared mathematically).
+
+Metric aggregations.  metrics = [field, ...] (at most MAX_METRICS of primary_value and the collection's own INT64 /
+DOUBLE fields: the fields a range facet takes) adds "metrics": {field: stats} to every bucket of every value facet,
+over the bucket's units (a unit is a passing row that holds the value: an ARRAY row belongs once to each distinct
+element's bucket, exactly as it is counted), and a top-level "metrics": {field: stats} over all passing rows;
+`missing` and `other` get none.  stats (stats_reference) is {"count", "nan", "sum", "avg", "min", "max"}:
+  DOUBLE  nan: the NaN values, which take part in nothing else; count: the others; sum: NaN when +inf and -inf
+          both occur, that infinity when one does, else the EXACT rational sum of the finite values rounded once
+          to the nearest double, ties to even (float(sum(Fraction(v)))): +-inf when that exceeds the double range,
+          +0.0 when it is exactly zero.  It equals math.fsum wherever math.fsum returns.  The exact sum does not
+          depend on an order, so the device (integer adds into a fixed-point accumulator, one rounding at the end)
+          must give the same bits.  avg: sum / count, one IEEE division (None without a value); min / max over the
+          non-NaN values (None without one; which zero a -0.0 / +0.0 tie returns is unspecified)
+  INT64   sum: the exact Python int (it may exceed 64 bits); nan 0; avg: Python's sum / count; min / max ints
+An empty group: count 0, sum 0.0 (INT64: 0), avg / min / max None.  Without `metrics` no "metrics" key appears.
 """
 from __future__ import annotations
 
@@ -39,6 +54,7 @@ import math
 import numbers
 import re
 from collections import Counter
+from fractions import Fraction
 
 import numpy as np
 
@@ -49,7 +65,10 @@ COUNT_STAR = "count(*)"      # query(expr, output_fields=["count(*)"]): pymilvus
 MAX_LIMIT = 1000             # buckets per field (RF_FACET_MAX_LIMIT)
 MAX_RANGES = 64              # ranges per field (RF_FACET_MAX_RANGES)
 MAX_FIELDS = 16              # value fields of one call (RF_FACET_MAX_FIELDS)
+MAX_METRICS = 4              # metric fields of one call (RF_STATS_MAX_METRICS)
 
+_TWO_1074 = 2 ** 1074        # every finite double is an integer over it
+_AGGREGATE = re.compile(r"^(sum|avg|min|max)\(\s*([^()\s]+)\s*\)$")
 _META_KEY = re.compile(r"""^\$meta\[\s*(?:"([^"]+)"|'([^']+)')\s*\]$""")
 _NOT_FACETABLE = ("id", "text", "embedding", "primary_value")
 
@@ -58,9 +77,41 @@ def _is_int(v) -> bool:
     return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
-def check_args(fields, limit=10, min_count=1, ranges=None):
+def check_metrics(metrics, schema=()):
+    """metrics= of facets() -> [(field, "f64" | "i64"), ...] (resolve_range_field says which fields are numeric), or
+    ValueError: no list, more than MAX_METRICS names, a duplicate, an unknown or a non-numeric field."""
+    if metrics is None:
+        return []
+    if isinstance(metrics, str) or not isinstance(metrics, (list, tuple)):
+        raise ValueError(f"facets: metrics must be a list of field names, got {metrics!r}")
+    metrics = list(metrics)
+    for f in metrics:
+        if not isinstance(f, str) or not f:
+            raise ValueError(f"facets: metrics: a field name must be a non-empty string, got {f!r}")
+    if len(set(metrics)) != len(metrics):
+        raise ValueError("facets: metrics names a field twice")
+    if len(metrics) > MAX_METRICS:
+        raise ValueError(f"facets: at most {MAX_METRICS} metrics per call, got {len(metrics)}")
+    out = []
+    for f in metrics:
+        try:
+            out.append((f, resolve_range_field(f, schema)[0]))
+        except ValueError:
+            raise ValueError(f"facets: metrics: field {f!r} is no numeric field; metrics are offered on primary_value "
+                             "and the collection's INT64 / DOUBLE fields") from None
+    return out
+
+
+def parse_aggregate(name):
+    """("sum" | "avg" | "min" | "max", field) of an output field such as "sum(primary_value)", else None."""
+    m = _AGGREGATE.match(name) if isinstance(name, str) else None
+    return (m.group(1), m.group(2)) if m else None
+
+
+def check_args(fields, limit=10, min_count=1, ranges=None, metrics=None, schema=()):
     """The arguments of facets() -> (list of field names, limit, min_count, {field: [(lo, hi), ...]}), or
-    ValueError naming the argument."""
+    ValueError naming the argument.  With metrics= (a list, checked against `schema` by check_metrics) a fifth
+    element follows: [(field, "f64" | "i64"), ...]; metrics alone are something to count."""
     if fields is None:
         fields = []
     if isinstance(fields, str) or not isinstance(fields, (list, tuple)):
@@ -95,8 +146,11 @@ def check_args(fields, limit=10, min_count=1, ranges=None):
                         raise ValueError(f"facets: ranges[{name!r}]: a bound is a real number or None, got {b!r}")
                 checked.append((r[0], r[1]))
             out[name] = checked
-    if not fields and not out:
+    checked_metrics = check_metrics(metrics, schema)
+    if not fields and not out and not checked_metrics:
         raise ValueError("facets: nothing to count: give fields and / or ranges")
+    if metrics is not None:
+        return fields, int(limit), int(min_count), out, checked_metrics
     return fields, int(limit), int(min_count), out
 
 
@@ -230,37 +284,87 @@ def range_facet(values, kind: str, rs) -> dict:
     return {"ranges": out, "min": min(values) if values else None, "max": max(values) if values else None, "nan": nan}
 
 
+def stats_reference(values, kind: str) -> dict:
+    """The metrics of one group of values (kind "f64": floats; "i64": ints): {"count", "nan", "sum", "avg", "min",
+    "max"} as the module's docstring defines them.  The fp64 sum is the exact rational sum rounded once."""
+    if kind == "i64":
+        vals = [int(v) for v in values]
+        total = sum(vals)
+        return {"count": len(vals), "nan": 0, "sum": total, "avg": total / len(vals) if vals else None,
+                "min": min(vals) if vals else None, "max": max(vals) if vals else None}
+    vals = [float(v) for v in values]
+    nan = sum(1 for v in vals if v != v)
+    vals = [v for v in vals if v == v]
+    pos, neg = math.inf in vals, -math.inf in vals
+    if pos and neg:
+        total = math.nan
+    elif pos or neg:
+        total = math.inf if pos else -math.inf
+    else:
+        # sum(Fraction(v) for v in vals), over the common denominator 2^1074 every double has: integer adds
+        scaled = 0
+        for v in vals:
+            num, den = v.as_integer_ratio()   # (den is a power of two, at most 2^1074)
+            scaled += num * (_TWO_1074 // den)
+        exact = Fraction(scaled, _TWO_1074)
+        try:
+            total = float(exact)   # (correctly rounded, ties to even)
+        except OverflowError:
+            total = math.inf if exact > 0 else -math.inf
+        if total == 0.0:
+            total = 0.0   # (an exact zero sum is +0.0; a non-zero sum never rounds to zero: it is a multiple of 2^-1074)
+    return {"count": len(vals), "nan": nan, "sum": total, "avg": total / len(vals) if vals else None,
+            "min": min(vals) if vals else None, "max": max(vals) if vals else None}
+
+
 def facets_reference(columns: dict, schema, dynamic, fields, passing_rows, limit: int = 10, min_count: int = 1,
-                     ranges=None) -> dict:
+                     ranges=None, metrics=None) -> dict:
     """What CorpusStore.facets returns, over the host columns.  columns: {field: list} (a store's `columns`);
     schema: the collection's own FieldSchema objects; dynamic: {key: column with None where the row lacks it}, or
     None for a collection without enable_dynamic_field; passing_rows: the row numbers the filter passes."""
-    fields, limit, min_count, ranges = check_args(fields, limit, min_count, ranges)
+    if metrics is None:
+        fields, limit, min_count, ranges = check_args(fields, limit, min_count, ranges)
+        mplan = None
+    else:
+        fields, limit, min_count, ranges, mplan = check_args(fields, limit, min_count, ranges, metrics, schema)
     rows = [int(r) for r in passing_rows]
     out = {"count": len(rows), "facets": {}, "ranges": {}}
+
+    def stats_of(rs):
+        return {name: stats_reference([columns[name][r] for r in rs], kind) for name, kind in mplan}
     for name in fields:
         kind, what = resolve_value_field(name, schema, dynamic is not None)
         counts: Counter = Counter()
+        units: dict = {}   # value -> the rows that hold it (with metrics)
         missing = 0
-        if kind == "builtin":
-            counts.update(columns[what][r] for r in rows)
-        elif kind == "own":
-            counts.update(columns[what.name][r] for r in rows)
+        if kind in ("builtin", "own"):
+            col = columns[what if kind == "builtin" else what.name]
+            for r in rows:
+                counts[col[r]] += 1
+                units.setdefault(col[r], []).append(r)
         elif kind == "array":
             col = columns[what.name]
             for r in rows:
                 held = set(col[r])
                 counts.update(held)
                 missing += not held
+                for v in held:
+                    units.setdefault(v, []).append(r)
         else:
             col = dynamic.get(what)
             for r in rows:
                 v = None if col is None else col[r]
                 if isinstance(v, (bool, str)):
                     counts[v] += 1
+                    units.setdefault(v, []).append(r)   # (True == 1 cannot collide: only bools and strings come here)
                 else:
                     missing += 1
         out["facets"][name] = value_facet(counts, missing, limit, min_count)
+        if mplan is not None:
+            for b in out["facets"][name]["buckets"]:
+                b["metrics"] = stats_of(units[b["value"]])
+    if mplan is not None:
+        out["metrics"] = stats_of(rows)
     for name, rs in ranges.items():
         kind, col = resolve_range_field(name, schema)
         vals = [columns[col][r] for r in rows]

@@ -1551,13 +1551,65 @@ def array_first_occurrence(device, offsets, values, row_lo: int, row_hi: int, fl
                                                  _lib.current_stream_ptr()))
 
 
-def facet_counts(device, filt, specs: list, n_rows: int, limit: int, min_count: int) -> np.ndarray:
+def facet_stats_slots(spec: dict, limit: int) -> int:
+    """The slots rf_facet_stats gives a field: min(limit, its value bins)."""
+    return min(limit, spec["n_codes"] + (2 if spec["kind"] == _lib.RF_FACET_DYNAMIC else 0))
+
+
+def _stats_metrics(metrics: list, n_rows: int):
+    """The rf_stats_metric array of [(int64 / fp64 device tensor [>= n_rows], is_f64), ...]."""
+    torch = _torch()
+    if not 1 <= len(metrics) <= _lib.RF_STATS_MAX_METRICS:
+        raise ValueError(f"facet stats: 1..{_lib.RF_STATS_MAX_METRICS} metrics per call, got {len(metrics)}")
+    marr = (_lib.StatsMetric * len(metrics))()
+    for i, (col, is_f64) in enumerate(metrics):
+        if col.dtype != (torch.float64 if is_f64 else torch.int64) or col.numel() < n_rows or not col.is_contiguous():
+            raise ValueError(f"facet stats: metric {i} must be a contiguous {'fp64' if is_f64 else 'int64'} tensor of "
+                             f"{n_rows} rows")
+        marr[i].column_dev, marr[i].is_f64 = col.data_ptr(), 1 if is_f64 else 0
+    return marr
+
+
+def _facet_stats(lib, device, filt, arr, n_fields: int, marr, slot_of, n_counters: int, limit: int, n_rows: int, grid: int):
+    """rf_facet_stats + rf_facet_stats_finish on the current stream -> the finished records, on the device."""
+    torch = _torch()
+    M = len(marr)
+    n_records = lib.rf_facet_stats_records(arr, n_fields, M, limit)
+    if n_records < 1:
+        raise ValueError("facet stats: bad arguments")
+    acc = torch.empty(n_records * _lib.RF_STATS_WORDS, dtype=torch.int64, device=device)
+    out = torch.empty((n_records, _lib.RF_STATS_OUT), dtype=torch.int64, device=device)
+    st = _lib.current_stream_ptr()
+    _lib.check(lib.rf_facet_stats(_ptr(filt), arr, n_fields, marr, M, _ptr(slot_of), n_counters, limit, n_rows, _ptr(acc),
+                                  n_records, grid, st))
+    _lib.check(lib.rf_facet_stats_finish(_ptr(acc), marr, M, n_records, _ptr(out), st))
+    return out
+
+
+def facet_stats_all(device, filt, metrics: list, n_rows: int, grid: int = 0) -> np.ndarray:
+    """The metric aggregations of all the rows `filt` passes (None: every row): rf_facet_stats with its one-slot
+    group alone -- no value field, no select -- then rf_facet_stats_finish and ONE download.  metrics: [(int64 /
+    fp64 device tensor [n_rows], is_f64), ...].  -> int64 [len(metrics), RF_STATS_OUT]: {count, nan, sum bits |
+    limb 0, limb 1, min, max, 0, 0} per metric.  grid: workgroups (0: the default)."""
+    torch = _torch()
+    lib = _lib.load_library()
+    marr = _stats_metrics(metrics, n_rows)
+    with torch.cuda.device(device):
+        return _facet_stats(lib, device, filt, None, 0, marr, None, 0, 1, n_rows, grid).cpu().numpy()
+
+
+def facet_counts(device, filt, specs: list, n_rows: int, limit: int, min_count: int, metrics=None, grid: int = 0):
     """rf_facet_counts + rf_facet_select of one facets() call: one launch each for all fields, on the current
     stream, then ONE download.  filt: a filter buffer for n_rows rows, or None (every row).  specs: per field
     {"kind": RF_FACET_*, "n_codes": dictionary size, "a" / "b" / "c": the device tensors rf_facet_field names (None
     where unused), "rank": int32 device tensor [n_bins]}.  -> int64 [len(specs), RF_FACET_SCALARS + 2 * limit]:
     per field the scalars {selected, distinct, selected sum, missing, sum of all bins, ...}, the selected counts and
-    their bin numbers, best first.  Buffers are allocated per call."""
+    their bin numbers, best first.  Buffers are allocated per call.
+    metrics: [(int64 / fp64 device tensor [n_rows], is_f64), ...] adds rf_facet_stats_slots, rf_facet_stats and
+    rf_facet_stats_finish behind the select, on the same stream and without a host round trip, and returns
+    (the array above, int64 [records, RF_STATS_OUT]): per field facet_stats_slots(spec, limit) slots of one record
+    per metric, in bucket order, then one record per metric over all passing rows.  grid: the stats launch's
+    workgroups per column (0: the default)."""
     torch = _torch()
     lib = _lib.load_library()
     F = len(specs)
@@ -1583,7 +1635,13 @@ def facet_counts(device, filt, specs: list, n_rows: int, limit: int, min_count: 
         st = _lib.current_stream_ptr()
         _lib.check(lib.rf_facet_counts(_ptr(filt), arr, F, n_rows, _ptr(counters), n_counters, st))
         _lib.check(lib.rf_facet_select(arr, F, _ptr(counters), n_counters, limit, min_count, _ptr(out), st))
-        return out.cpu().numpy()
+        if metrics is None:
+            return out.cpu().numpy()
+        marr = _stats_metrics(metrics, n_rows)
+        slot_of = torch.empty(n_counters, dtype=torch.int32, device=device)
+        _lib.check(lib.rf_facet_stats_slots(arr, F, _ptr(out), limit, _ptr(slot_of), n_counters, st))
+        stats = _facet_stats(lib, device, filt, arr, F, marr, slot_of, n_counters, limit, n_rows, grid)
+        return out.cpu().numpy(), stats.cpu().numpy()
 
 
 def facet_ranges(device, filt, column, is_f64: bool, bounds: list, n_rows: int) -> np.ndarray:

@@ -194,16 +194,22 @@ def answer_question(question: str, top_k: int = 3, min_score: float | None = Non
         return {"status": "error", "message": str(e), "question": question}
 
 
-def get_collection_stats(expr: str | None = None, facet_fields: list | None = None, facet_limit: int = 10):
+def get_collection_stats(expr: str | None = None, facet_fields: list | None = None, facet_limit: int = 10,
+                         metric_fields: list | None = None):
     """Get collection statistics.  expr and / or facet_fields: also "count", the chunks `expr` matches (all
-    without one), and "facets", their count per value of each of facet_fields (the best facet_limit values)."""
+    without one), and "facets", their count per value of each of facet_fields (the best facet_limit values).
+    metric_fields (at most 4 numeric fields): also "metrics", the exact sum / avg / min / max of each over the
+    matching chunks, and the same inside every facet bucket."""
     try:
         out = {"status": "success", "collection_name": COLLECTION_NAME,
                "total_chunks": get_rag().collection.num_entities,
                "milvus_host": MILVUS_HOST, "milvus_port": MILVUS_PORT}
-        if expr is not None or facet_fields:
+        if expr is not None or facet_fields or metric_fields:
             expr = expr if expr and expr.strip() else None
-            if facet_fields:
+            if metric_fields:
+                got = get_rag().facets(list(facet_fields or []), expr=expr, limit=facet_limit, metrics=list(metric_fields))
+                out["count"], out["facets"], out["metrics"] = got["count"], got["facets"], got["metrics"]
+            elif facet_fields:
                 got = get_rag().facets(list(facet_fields), expr=expr, limit=facet_limit)
                 out["count"], out["facets"] = got["count"], got["facets"]
             else:

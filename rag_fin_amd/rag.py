@@ -445,10 +445,12 @@ class VectorRAG:
         except Exception as e:  # the reference's blanket handler (main.py:103-108)
             return {"error": str(e), "contexts": contexts, "context_count": len(contexts)}
 
-    def facets(self, fields=None, expr=None, limit: int = 10, min_count: int = 1, ranges=None) -> dict:
+    def facets(self, fields=None, expr=None, limit: int = 10, min_count: int = 1, ranges=None, metrics=None) -> dict:
         """Faceted counts of the collection (CorpusStore.facets): how many of the chunks `expr` matches hold
-        each value of `fields`, and how many fall into each of `ranges`."""
-        return self.collection.facets(fields, expr=expr, limit=limit, min_count=min_count, ranges=ranges)
+        each value of `fields`, and how many fall into each of `ranges`; with `metrics` (numeric fields) also the
+        exact sum, avg, min and max of each per bucket and over all matching chunks."""
+        extra = {} if metrics is None else {"metrics": metrics}
+        return self.collection.facets(fields, expr=expr, limit=limit, min_count=min_count, ranges=ranges, **extra)
 
     def health_check(self) -> dict:
         try:

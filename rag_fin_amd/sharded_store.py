@@ -340,6 +340,10 @@ class ShardedCorpusStore(CorpusStore):
     def facets(self, *args, **kwargs):
         raise NotImplementedError("faceted counts are not implemented for the sharded store")
 
+    def _aggregate(self, expr, mplan):
+        # sum(f) / avg(f) / min(f) / max(f) in query: refused with the facets they belong to
+        raise NotImplementedError("metric aggregations are not implemented for the sharded store")
+
     def _count(self, expr) -> int:
         # count(*): '' and 'id in [...]' are served from the replicated columns; any other expression is
         # refused as query refuses it

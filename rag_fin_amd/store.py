@@ -42,7 +42,7 @@ from .schema import DataType, FieldSchema  # noqa: F401
 from .hybrid import MAX_ARMS, AnnSearchRequest, RRFRanker
 
 from . import facets as facets_
-from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, array_first_occurrence, array_match, facet_counts, facet_ranges, boost_classes, column_match, dynamic_match,  # noqa: F401
+from .index import (GpuIndex, MultiFilter, SparseIndex, _ptr, array_first_occurrence, array_match, facet_counts, facet_ranges, facet_stats_all, facet_stats_slots, boost_classes, column_match, dynamic_match,  # noqa: F401
                     decay_weights, eval_filter, filter_from_mask, filter_mask_bits, fuse_rrf, grouped_exhaustive, mask_words, merge_boosted,
                     plan_filter_chunks, require_gpu, rerun_flagged, text_words_per_leaf, words_mask)
 from .ranker import BoostRanker, DecayRanker, check_rankers, class_weights  # noqa: F401
@@ -1829,20 +1829,40 @@ class CorpusStore:
         first, on the host; `limit` counts from there.
         output_fields=["count(*)"] (pymilvus' idiom) returns [{"count(*)": n}], the number of rows `expr` matches:
         num_entities for an empty expr, the keys present for `id in [...]`, else n_pass_rows of the filter
-        buffer's header -- no row is fetched.  count(*) beside other fields, `limit` or `offset` raises ValueError."""
+        buffer's header -- no row is fetched.  count(*) beside other fields, `limit` or `offset` raises ValueError.
+        output_fields may also hold "sum(f)", "avg(f)", "min(f)", "max(f)" (f: primary_value or an INT64 / DOUBLE field;
+        at most 4 distinct fields), beside each other and beside "count(*)": one dict keyed by those strings, from
+        the one-slot group of rf_facet_stats (facets.stats_reference defines the values: an fp64 sum is the exact sum
+        rounded once).  The same refusals hold."""
         if expr is not None and not isinstance(expr, str):
             raise ValueError(f"filter expression must be a string, got {type(expr).__name__}")
         if not isinstance(output_fields, str) and output_fields is not None:
             output_fields = list(output_fields)
-            if facets_.COUNT_STAR in output_fields:
-                if len(output_fields) != 1:
-                    raise ValueError("query: count(*) cannot be combined with other output_fields")
+            aggs = [facets_.parse_aggregate(f) for f in output_fields]
+            if facets_.COUNT_STAR in output_fields or any(aggs):
+                what = "count(*)" if facets_.COUNT_STAR in output_fields else "an aggregate"
+                if any(a is None and f != facets_.COUNT_STAR for a, f in zip(aggs, output_fields)):
+                    raise ValueError(f"query: {what} cannot be combined with other output_fields")
                 if limit is not None:
-                    raise ValueError("query: count(*) cannot be combined with limit")
+                    raise ValueError(f"query: {what} cannot be combined with limit")
                 if offset:
-                    raise ValueError("query: count(*) cannot be combined with offset")
+                    raise ValueError(f"query: {what} cannot be combined with offset")
+                if not any(aggs):
+                    if len(output_fields) != 1:
+                        raise ValueError("query: count(*) cannot be combined with other output_fields")
+                    with self._rw.read():
+                        return [{facets_.COUNT_STAR: self._count(expr)}]
+                # sum(f) / avg(f) / min(f) / max(f), beside each other and beside count(*): one dict keyed by them
+                names = list(dict.fromkeys(a[1] for a in aggs if a))
+                if len(names) > facets_.MAX_METRICS:   # (each call of the kernel takes MAX_METRICS columns)
+                    raise ValueError(f"query: aggregates over at most {facets_.MAX_METRICS} fields, got {len(names)}")
+                mplan = facets_.check_metrics(names, self.schema)
                 with self._rw.read():
-                    return [{facets_.COUNT_STAR: self._count(expr)}]
+                    stats = self._aggregate(expr, mplan)
+                    rec = {f: stats[a[1]][a[0]] for a, f in zip(aggs, output_fields) if a}
+                    if facets_.COUNT_STAR in output_fields:
+                        rec[facets_.COUNT_STAR] = self._count(expr)
+                return [{f: rec[f] for f in output_fields}]
         offset = check_offset(offset, None, 1)
         with self._rw.read():
             return self._query(expr, limit, output_fields, offset)
@@ -1864,7 +1884,8 @@ class CorpusStore:
         return tuple(int(v) for v in filt[:16].cpu().numpy().view(np.uint32))
 
     # -- faceted counts (rag_fin_amd/facets.py) ---------------------------------------
-    def facets(self, fields=None, expr: str | None = None, limit: int = 10, min_count: int = 1, ranges=None) -> dict:
+    def facets(self, fields=None, expr: str | None = None, limit: int = 10, min_count: int = 1, ranges=None,
+               metrics=None) -> dict:
         """How many of the rows `expr` passes (every row without one; anything a filter takes) hold each value of
         `fields`, and how many fall into each of `ranges` -- facets.py has the definition, facets_reference:
             {"count": passing rows,
@@ -1874,21 +1895,41 @@ class CorpusStore:
         fields of VARCHAR or BOOL elements (a row counts once per distinct element) and dynamic keys (bare or
         $meta["key"]).  ranges: {field: [(lo, hi), ...]}, each [lo, hi) with None for no bound, over primary_value
         and INT64 / DOUBLE fields.  Counted on the GPU from the columns' dictionary codes (rf_facet_counts,
-        rf_facet_select, rf_facet_ranges); exact and the same on every run.  ValueError on a bad argument."""
-        fields, limit, min_count, ranges = facets_.check_args(fields, limit, min_count, ranges)
+        rf_facet_select, rf_facet_ranges); exact and the same on every run.  ValueError on a bad argument.
+        metrics: up to 4 of primary_value and the INT64 / DOUBLE fields.  Every bucket then carries
+        "metrics": {field: {"count", "nan", "sum", "avg", "min", "max"}} over the rows counted in it, and the result
+        a top-level "metrics" over all passing rows (facets.stats_reference has the definition).  A DOUBLE sum is the
+        exact sum rounded once -- what math.fsum returns -- accumulated in fixed point with integer atomics
+        (rf_facet_stats), so it too has the same bits on every run.  On the CPU double of the index the metrics
+        come from the reference."""
+        mplan = None
+        if metrics is None:
+            fields, limit, min_count, ranges = facets_.check_args(fields, limit, min_count, ranges)
+        else:
+            fields, limit, min_count, ranges, mplan = facets_.check_args(fields, limit, min_count, ranges, metrics,
+                                                                         self.schema)
         if expr is not None and not isinstance(expr, str):
             raise ValueError(f"filter expression must be a string, got {type(expr).__name__}")
         plan = [(name,) + facets_.resolve_value_field(name, self.schema, self.enable_dynamic_field) for name in fields]
         rplan = [(name,) + facets_.resolve_range_field(name, self.schema) for name in ranges]
+        extra = {} if metrics is None else {"metrics": metrics}
         with self._rw.read():
             n = self.num_entities
             if n == 0:   # nothing to count (a bad expression is still rejected)
                 if not filter_expr.is_empty(expr):
                     self._match_mask(expr)
                 return facets_.facets_reference(self.columns, self.schema, self.dynamic if self.enable_dynamic_field
-                                                else None, fields, [], limit, min_count, ranges)
+                                                else None, fields, [], limit, min_count, ranges, **extra)
+            if mplan is not None and self._on_host():
+                rows = range(n) if filter_expr.is_empty(expr) else self._expr_rows(expr)
+                return facets_.facets_reference(self.columns, self.schema, self.dynamic if self.enable_dynamic_field
+                                                else None, fields, rows, limit, min_count, ranges, **extra)
             filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
-            return self._facets(plan, rplan, ranges, filt, n, limit, min_count)
+            return self._facets(plan, rplan, ranges, filt, n, limit, min_count, mplan)
+
+    def _on_host(self) -> bool:
+        """The index is the CPU double (tests): there is no device to aggregate on."""
+        return getattr(self.index.device, "type", "cuda") == "cpu"
 
     def _facet_rank(self, holder, key, vals: list, dynamic: bool):
         """The value rank of every bin of a dictionary (facets.value_ranks; a dynamic key's False and True behind
@@ -1901,7 +1942,65 @@ class CorpusStore:
             hit = cache[key] = (len(vals), _torch().from_numpy(rank).to(self.index.device))
         return hit[1]
 
-    def _facets(self, plan, rplan, ranges, filt, n: int, limit: int, min_count: int) -> dict:
+    def _metric_column(self, name: str, n: int):
+        """The fp64 / int64 device column of a metric or range field.  Caller holds `_filter_lock`."""
+        if name == "primary_value":
+            if self._dcols is None:
+                self._dcols = _DeviceColumns(self.index.device)
+            self._dcols.sync(self.columns, n)
+            return self._dcols.values.contiguous()
+        return self._extra_column(self._field(name)).data.contiguous()
+
+    @staticmethod
+    def _stats_dicts(stats, kinds: list) -> list:
+        """The compact records of rf_facet_stats_finish (int64 [records, RF_STATS_OUT]; record r belongs to metric
+        r % len(kinds)) -> per record the stats of facets.stats_reference.  Converted to Python numbers once for all
+        records: a call with limit=1000 has thousands."""
+        ints, floats = stats.tolist(), np.ascontiguousarray(stats).view(np.float64).tolist()
+        out = []
+        for r, (rec, frec) in enumerate(zip(ints, floats)):
+            count = rec[0]
+            if kinds[r % len(kinds)] == "i64":
+                total = rec[2] + (rec[3] << 32)
+                out.append({"count": count, "nan": 0, "sum": total, "avg": total / count if count else None,
+                            "min": rec[4] if count else None, "max": rec[5] if count else None})
+            else:
+                total = frec[2]
+                out.append({"count": count, "nan": rec[1], "sum": total, "avg": total / count if count else None,
+                            "min": frec[4] if count else None, "max": frec[5] if count else None})
+        return out
+
+    def _aggregate(self, expr, mplan) -> dict:
+        """{field: stats} over the rows `expr` matches: the one-slot group of rf_facet_stats alone, no value field
+        and no select.  Caller holds the read lock."""
+        n = self.num_entities
+        if n == 0 or self._on_host():
+            if n == 0 and not filter_expr.is_empty(expr) and _id_in_keys(expr) is None:
+                self._match_mask(expr)   # (still rejects a bad expression)
+            rows = self._aggregate_rows(expr) if n else []
+            return {name: facets_.stats_reference([self.columns[name][r] for r in rows], kind) for name, kind in mplan}
+        keys = None if filter_expr.is_empty(expr) else _id_in_keys(expr)
+        if keys is not None:   # the keys present, each once: a mask of their rows
+            mask = np.zeros((n + 31) // 32 * 32, dtype=bool)
+            mask[[self._pk_row[k] for k in keys if k in self._pk_row]] = True
+            words = np.packbits(mask, bitorder="little").view(np.int32)   # bit r of word b = row 32 b + r
+            filt = filter_from_mask(_torch().from_numpy(words).to(self.index.device), n)
+        else:
+            filt = None if filter_expr.is_empty(expr) else self.build_filter(expr)
+        with self._filter_lock:
+            cols = [(self._metric_column(name, n), kind == "f64") for name, kind in mplan]
+        got = self._stats_dicts(facet_stats_all(self.index.device, filt, cols, n), [kind for _, kind in mplan])
+        return {name: rec for (name, _), rec in zip(mplan, got)}
+
+    def _aggregate_rows(self, expr) -> list:
+        if filter_expr.is_empty(expr):
+            return list(range(self.num_entities))
+        keys = _id_in_keys(expr)
+        if keys is not None:
+            return sorted({self._pk_row[k] for k in keys if k in self._pk_row})
+        return [int(r) for r in self._expr_rows(expr)]
+
+    def _facets(self, plan, rplan, ranges, filt, n: int, limit: int, min_count: int, mplan=None) -> dict:
         """facets() on the device.  Caller holds the read lock.  The columns are mirrored under `_filter_lock` (after
         build_filter has released it: the lock order of build_filter holds), which is held only until the call has
         its references: a sync or a compaction replaces a mirror's tensors and never writes into them, and the read
@@ -1949,8 +2048,16 @@ class CorpusStore:
                 else:
                     column = self._extra_column(self._field(colname)).data
                 rcols.append(column.contiguous())
+            mcols = [(self._metric_column(name, n), kind == "f64") for name, kind in mplan or ()]
         live = [s for s in specs if s is not None]
-        got = iter(facet_counts(dev, filt, live, n, limit, min_count)) if live else iter(())
+        stats = None
+        if not mplan:   # (metrics=[] asks for nothing more: every "metrics" is {})
+            got = iter(facet_counts(dev, filt, live, n, limit, min_count)) if live else iter(())
+        elif live:
+            got, stats = facet_counts(dev, filt, live, n, limit, min_count, metrics=mcols)
+            got = iter(got)
+        else:
+            got, stats = iter(()), facet_stats_all(dev, filt, mcols, n)
         rgot = []
         for (name, kind, colname), column in zip(rplan, rcols):
             bounds = []
@@ -1964,6 +2071,10 @@ class CorpusStore:
         if filt is not None:
             out["count"] = self._filter_header(filt)[1]
         S = _lib.RF_FACET_SCALARS
+        nm = len(mplan or ())
+        if stats is not None:
+            stats = self._stats_dicts(stats, [kind for _, kind in mplan])
+        at = 0   # the field's first record in `stats`: min(limit, bins) slots of one record per metric
         for (name, _, _), spec, vals in zip(plan, specs, values):
             if spec is None:
                 out["facets"][name] = {"buckets": [], "distinct": 0, "missing": out["count"], "other": 0}
@@ -1975,6 +2086,12 @@ class CorpusStore:
                 "buckets": [{"value": vals[int(b)] if b < spec["n_codes"] else bool(b - spec["n_codes"]), "count": int(c)}
                             for c, b in zip(row[S:S + sel], row[S + limit:S + limit + sel])],
                 "distinct": distinct, "missing": missing, "other": total - sel_sum}
+            if mplan is not None:
+                for slot, b in enumerate(out["facets"][name]["buckets"]):
+                    b["metrics"] = {m: stats[at + slot * nm + j] for j, (m, _) in enumerate(mplan)}
+                at += nm * facet_stats_slots(spec, limit)
+        if mplan is not None:
+            out["metrics"] = {m: stats[at + j] for j, (m, _) in enumerate(mplan)}
         for (name, kind, _), r in zip(rplan, rgot):
             M = _lib.RF_FACET_MAX_RANGES
             any_valid = int(r[M + 1]) > 0
